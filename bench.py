@@ -7,9 +7,15 @@ hashprints) over the batch of configs[1]: 1 000 x 30 s synthetic 44.1 kHz clips 
 already resident in HBM.  `value` = hashprints/s over all ranks (weak scaling: every rank extracts
 its own 1 000 clips, no collective on this path).  The search half of the metric (configs[2]:
 10 000-clip index per GPU, 1 000 x 5 s queries, top-10, one RCCL all-gather of the per-shard
-top-k) is timed in the same run and reported under "search".
+top-k) is timed in the same run with --full and reported under "search".
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 through
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else the
+bench measures or checks: the per-kernel split and rooflines, the oracle's parity check and the CPU baseline, the
+f32-chain projection, host buffers, any-length clips, the file-level FFI, search, filter learning and streaming
+(each section can still be left out with its --no-* option).  --dump-outputs DIR writes what the last timed step
+computed (dump_outputs below), so that two builds can be compared output for output.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; for N > 1 through
 python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -39,6 +45,7 @@ VALU_PAIR_PEAK = 256 * 4 * 32 * 2.4e9 / 4            # xor/popcount kernel: 4 VA
 MFMA_FP4_PEAK_PFLOPS = 10.07                         # MI355X_MICROARCH.md: dense FP4 MFMA (32x32x64 in 32 cycles/SIMD)
 FP4_PAIR_PEAK = MFMA_FP4_PEAK_PFLOPS * 1e15 / 2 / 64 # one pair = 64 multiply-adds of +-1
 SPEC_CLIPS = 8                                       # clips per rank taken from hpfw_amd.synth.gen_clip
+DUMP_HASHPRINTS = 196608                             # --dump-outputs: 64 float32 per hashprint, 50.3 MB in all
 
 
 def synth_clips_gpu(torch, n_clips, n_samples, seed, device, chunk=25):
@@ -95,7 +102,14 @@ def main():
                     help="skip the section on clips whose length is not 7-smooth (chirp-z forward transform)")
     ap.add_argument("--cpu-clips-per-core", type=int, default=64,
                     help="CPU baseline sample: clips per usable host CPU (about 10 s of CPU work on the 16 CPUs of a GPU box: all 1000 clips)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the sections beyond the headline figure (per-kernel split and rooflines, parity and CPU "
+                         "baseline, f32 chain, host buffers, any length, FFI, search, filter learning, streaming)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output to DIR/*.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import hpfw_amd
@@ -154,7 +168,7 @@ def main():
     spec = np.stack([synth.gen_clip(rank * SPEC_CLIPS + i, args.seconds) for i in range(n_spec)])
     pcm[:n_spec] = torch.from_numpy(spec).to(device)
     clip0_sha = hashlib.sha256(spec[0].tobytes()).hexdigest() if rank == 0 else None
-    if rank == 0 and n_samples == 1323000:
+    if args.full and rank == 0 and n_samples == 1323000:
         committed = open(os.path.join(ROOT, "tests", "golden", "clip0.sha256")).read().split()[0]
         assert clip0_sha == committed, "bench clip 0 is not the committed synthetic clip"
     hp = torch.empty((n_clips, geo.n_hp), dtype=torch.int64, device=device)
@@ -166,10 +180,11 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # the two largest kernels (the row transforms and the projection): one HIP event pair per launch, on the launch stream
-    # (the forward transform's stages run in chunks of 16 clips: an event pair around each of their 126 launches per pass
-    # would cost the step 0.2 ms; they are timed as one span here and launch by launch in an extra pass further down)
-    gpu.set_kernel_timing((1 << hpfw_amd.KERNEL_KINDS.index("project_mfma")) | (1 << hpfw_amd.KERNEL_KINDS.index("fwd_span")))
+    if args.full:
+        # the two largest kernels (the row transforms and the projection): one HIP event pair per launch, on the launch stream
+        # (the forward transform's stages run in chunks of 16 clips: an event pair around each of their 126 launches per pass
+        # would cost the step 0.2 ms; they are timed as one span here and launch by launch in an extra pass further down)
+        gpu.set_kernel_timing((1 << hpfw_amd.KERNEL_KINDS.index("project_mfma")) | (1 << hpfw_amd.KERNEL_KINDS.index("fwd_span")))
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -187,8 +202,197 @@ def main():
         allt = [torch.empty_like(mine) for _ in range(world)]
         tdist.all_gather(allt, mine)
         per_rank_ms = [float(t.item()) for t in allt]
-    kt = gpu.kernel_timing()
-    gpu.set_kernel_timing(0)
+    ms_per_step = dt * 1e3 / args.steps
+    hashprints = float(n_clips) * geo.n_hp * world * args.steps
+    value = hashprints / dt
+    fixed_point = gpu.get_projection() == 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hp)
+    if args.full:
+        kt = gpu.kernel_timing()
+        gpu.set_kernel_timing(0)
+        split, rooflines = kernel_rooflines(torch, gpu, step, kt, geo, n_clips, args.steps, fixed_point)
+        roofline, roofline_second, roofline_third, roofline_fourth = rooflines
+
+    # parity and the CPU baseline (checker / reported baseline only, outside any timing): the oracle extracts a
+    # bounded sample of the same clips on the host cores and EVERY hashprint it produced is compared
+    parity = None
+    cpu_baseline = None
+    if args.full and rank == 0 and not args.no_parity:
+        from oracle import oracle
+        plan = oracle.Plan(n_samples)
+        got_all = hp.cpu().numpy().view(np.uint64)
+        if world == 1 and not args.no_cpu_baseline:
+            from hpfw_amd import hostinfo
+            budget = hostinfo.cpu_budget()                   # affinity and cgroup quota, not the machine's core count
+            ref_libs = hostinfo.reference_cpu_libraries()    # FFTW3 / Eigen3 / TBB / essentia / MKL: looked for, not assumed
+            cores = budget["usable"]
+            n_cpu = min(n_clips, max(1, args.cpu_clips_per_core * cores))
+            sample = pcm[:n_cpu].cpu().numpy()
+            t1 = time.perf_counter()
+            want = plan.extract_batch(filt, sample, n_threads=cores)
+            cdt = time.perf_counter() - t1
+            idx = np.arange(n_cpu)
+            # one thread, stage by stage (4 clips): where the CPU path spends its time
+            st = {"spectrum": 0.0, "cq": 0.0, "db": 0.0, "project": 0.0, "pack": 0.0}
+            n_one = min(4, n_cpu)
+            t_one = time.perf_counter()
+            for c in sample[:n_one]:
+                ta = time.perf_counter(); x = plan.spectrum(c)
+                tb = time.perf_counter(); m = plan.cqmag(x)
+                tc = time.perf_counter(); d = oracle.db(m)
+                td = time.perf_counter(); pr = oracle.project_q(filt, d) if oracle.get_projection() else oracle.project(filt, d)
+                te = time.perf_counter(); oracle.pack_q(pr) if oracle.get_projection() else oracle.pack(pr)
+                tf = time.perf_counter()
+                for key, dtk in zip(st, (tb - ta, tc - tb, td - tc, te - td, tf - te)):
+                    st[key] += dtk
+            one_dt = time.perf_counter() - t_one
+            scaling = (n_cpu / cdt) / (n_one / one_dt)
+            cpu_baseline = {"value": round(n_cpu * geo.n_hp / cdt, 1), "unit": "hashprints/s", "cores": cores,
+                            "kind": "port",
+                            "sample": f"{n_cpu} of the same {args.seconds:g} s clips, oracle/hpfw_oracle.c "
+                                      f"(own C restatement, -O3 -mfma), {cores} threads = the CPUs this process may use "
+                                      f"(machine: {budget['os_cpu_count']}, cgroup quota: {budget['cgroup_cpus']}) in static "
+                                      f"chunks as flow_builder.hpp:321-325, {cdt:.1f} s",
+                            "clips_per_s": round(n_cpu / cdt, 2),
+                            "host": budget,
+                            "reference_cpu_libraries": ref_libs,
+
+                            "threads_over_one_thread": round(scaling, 2),
+                            "one_thread": {"clips_per_s": round(n_one / one_dt, 2), "clips": n_one,
+                                           "ms_per_clip_by_stage": {k: round(v * 1e3 / n_one, 1) for k, v in st.items()}}}
+        else:
+            # (N > 1, or no CPU baseline asked for: 32 clips spread over the batch -- with several ranks on a box the kernels of
+            # one run beside the other's, which is where round 3's packed arithmetic went wrong)
+            idx = np.unique(np.linspace(0, n_clips - 1, min(32, n_clips)).astype(np.int64))
+            from hpfw_amd import hostinfo
+            threads = max(1, hostinfo.cpu_budget()["usable"] // max(world, 1))   # (the cgroup's CPUs, not the machine's)
+            want = plan.extract_batch(filt, pcm[idx].cpu().numpy(), n_threads=threads)
+        parity = {"clips_checked": int(len(idx)), "bit_identical": bool(np.array_equal(got_all[idx], want)),
+                  "hashprints_differing": int((got_all[idx] != want).sum())}
+
+    # the reference's arithmetic type for filters * frames is f32 (parallel_collector.h:57,127): the same pass with the f32
+    # fma chain (S9) instead of the fixed-point default (S9q), and every hashprint of the batch compared between the two
+    f32_chain = None
+    if args.full and fixed_point and not args.no_f32_chain:
+        hp32 = torch.empty_like(hp)
+        gpu.set_projection(0)
+        try:
+            def step32():
+                gpu.extract_dev(pcm.data_ptr(), n_samples, n_clips, hp32.data_ptr(), stream)
+            step32()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(2):
+                step32()
+            torch.cuda.synchronize()
+            dt32 = (time.perf_counter() - t1) / 2
+        finally:
+            gpu.set_projection(1)
+        x = torch.bitwise_xor(hp, hp32)
+        words = int((x != 0).sum().item())
+        bits = 0
+        for sh in range(0, 64, 16):                          # popcount by 16-bit table-free folding on the device
+            v = (x >> sh) & 0xFFFF
+            v = (v & 0x5555) + ((v >> 1) & 0x5555)
+            v = (v & 0x3333) + ((v >> 2) & 0x3333)
+            v = (v & 0x0F0F) + ((v >> 4) & 0x0F0F)
+            v = (v & 0x00FF) + ((v >> 8) & 0x00FF)
+            bits += int(v.sum().item())
+        f32_chain = {"ms_per_step": round(dt32 * 1e3, 3), "clips_per_s": round(n_clips / dt32, 1),
+                     "hashprints_per_s": round(n_clips * geo.n_hp / dt32, 1),
+                     "hashprints_differing_vs_fixed_point": words, "bits_differing_vs_fixed_point": bits,
+                     "hashprints_compared": int(hp.numel()), "bits_compared": int(hp.numel()) * 64,
+                     "note": "hpfw_gpu_set_projection(h, 0): filters * frames as the f32 fma chain on v_mfma_f32_32x32x2_f32, "
+                             "rank 0's batch, outside the timed region"}
+        del hp32, x
+
+    pcie = None
+    if args.full and rank == 0 and world == 1 and not args.no_pcie:
+        pcie = bench_pcie(torch, gpu, pcm, n_samples, geo, hp)
+        if hasattr(torch._C, "_host_emptyCache"):
+            torch._C._host_emptyCache()        # the section's 0.7 GB of pinned host memory go back (torch caches them)
+
+    any_len = None
+    if args.full and rank == 0 and world == 1 and not args.no_any_length:
+        any_len = bench_any_length(torch, gpu, pcm, n_samples, None if args.no_parity else __import__("oracle.oracle").oracle, filt)
+
+    ffi = None
+    if args.full and rank == 0 and world == 1 and not args.no_ffi:
+        ffi = bench_ffi(torch, pcm, n_samples, filt, hp, args.ffi_files)
+
+    search = None
+    if args.full and not args.no_search:
+        search = bench_search(torch, tdist if world > 1 else None, gpu, hdist, synth, args, rank, world, device,
+                              stream, barrier, max_over_ranks, rehearse)
+
+    learn = None
+    if args.full and not args.no_learn and rank == 0 and world == 1:
+        learn = bench_learn(torch, gpu, args, pcm, n_samples, stream, filt)
+
+    stream_res = None
+    if args.full and not args.no_search and not args.no_stream:
+        stream_res = bench_stream(torch, tdist if world > 1 else None, gpu, hdist, synth, args, rank, world, device,
+                                  stream, barrier, rehearse)
+
+    if rank == 0:
+        comm = None
+        if world > 1:
+            comm = {"backend": tdist.get_backend(), "world_size": tdist.get_world_size(), "ranks_seen": ranks_seen,
+                    "devices_seen": devices_seen,
+                    "note": "backend 'nccl' is RCCL on ROCm; one process and one GPU per rank; ranks_seen / devices_seen come from "
+                            "an all-gather of every rank's (rank, local device) at start-up"}
+        line = {
+            "metric": "hashprints/sec (index) + Hamming matches/sec (search), 30 s@44.1 kHz clips",
+            "value": round(value, 1), "unit": "hashprints/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32 (transforms, dB) + int8 digits / int64 sums (projection)" if fixed_point else "f32", "data": "synthetic",
+            "config": {"workload": f"configs[1]: {n_clips} x {args.seconds:g} s synthetic 44.1 kHz PCM16 clips per GPU, "
+                                   "hashprint extraction only (CQT + dB + projection + bit pack), inputs resident in HBM",
+                       "clips_per_gpu": n_clips, "clip_seconds": args.seconds, "hashprints_per_clip": geo.n_hp,
+                       "generator": f"clips 0..{n_spec - 1} of every rank: hpfw_amd.synth.gen_clip (the tests' generator); "
+                                    "the rest: the same recipe with the device RNG",
+                       "clip0_sha256": clip0_sha,
+                       "parallelism": f"clips sharded over {world} GPU(s), no collective on this path"},
+            "clips_per_s": round(value / geo.n_hp, 1),
+            "event_ms_per_step_rank0": round(ev_ms / args.steps, 3),
+            "per_rank_ms_per_step": [round(t, 3) for t in per_rank_ms],
+            "per_gpu_work": {"clips": n_clips, "hashprints": n_clips * geo.n_hp,
+                             "note": "weak scaling: what every rank does per step is what the N = 1 run does"},
+            "rccl": comm,
+        }
+        if args.full:
+            line.update({
+                "kernel_ms_one_pass": split,
+                "roofline": roofline, "roofline_second_kernel": roofline_second, "roofline_third_kernel": roofline_third,
+                "roofline_fourth_kernel": roofline_fourth,
+                "cpu_baseline": cpu_baseline, "parity": parity,
+                "projection_f32_chain": f32_chain,
+                "pcie_inclusive": pcie, "ffi": ffi, "any_length": any_len, "search": search,
+                "stream": stream_res, "filter_learning": learn,
+            })
+        print(json.dumps(line), flush=True)
+    gpu.close()
+    if world > 1:
+        tdist.destroy_process_group()
+
+
+def dump_outputs(out_dir, hp):
+    """The last timed step's output, for comparing two builds output for output: hashprints.npy, float32
+    [DUMP_HASHPRINTS x 64], a fixed sample (numpy default_rng(0), sorted) of the [clips x n_hp] 64-bit hashprints, each
+    row one hashprint's bits as 0.0 / 1.0 (bit j in column j), so that every flipped bit is a difference of 1."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = hp.cpu().numpy().reshape(-1)
+    n = min(DUMP_HASHPRINTS, flat.size)
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, n, replace=False))
+    bits = np.unpackbits(flat[idx].astype("<i8").view(np.uint8).reshape(n, 8), axis=1, bitorder="little")
+    np.save(os.path.join(out_dir, "hashprints.npy"), bits.astype(np.float32))
+
+
+def kernel_rooflines(torch, gpu, step, kt, geo, n_clips, steps, fixed_point):
+    """the per-kernel split of one extra (untimed) pass and the rooflines of the largest stage and kernels, from the
+    timed steps' event pairs `kt`: (split, (roofline, second, third, fourth))"""
     # one extra (untimed) pass with an event pair around every launch: the per-kernel split, and the per-launch figures
     # of the forward transform's two kernels
     gpu.set_kernel_timing(-1)
@@ -197,13 +401,9 @@ def main():
     kt_extra = gpu.kernel_timing()
     split = {k: round(v[0], 3) for k, v in kt_extra.items() if v[1]}
     gpu.set_kernel_timing(0)
-    ms_per_step = dt * 1e3 / args.steps
-    hashprints = float(n_clips) * geo.n_hp * world * args.steps
-    value = hashprints / dt
 
     pj_ms, pj_launches = kt["project_mfma"]
-    clips_per_launch = n_clips * args.steps / max(pj_launches, 1)
-    fixed_point = gpu.get_projection() == 1
+    clips_per_launch = n_clips * steps / max(pj_launches, 1)
     traffic_json = {}
     tr_path = os.path.join(ROOT, "profiles", "traffic.json")
     if os.path.exists(tr_path):
@@ -283,7 +483,7 @@ def main():
     chunked = kt_extra["fwd_cols"][1] > kt_extra["fwd_span"][1] > 0
     roof_fwd = None
     if span_n:
-        clips = n_clips * args.steps / span_n
+        clips = n_clips * steps / span_n
         span_s = span_ms / span_n * 1e-3
         # what has to cross HBM whatever the kernels do between themselves: the PCM in, the consumed bins out, and the
         # inter-stage twiddle seeds the row stage reads (the same for every clip, so mostly served by the caches -- counted
@@ -317,166 +517,7 @@ def main():
     else:
         roofline, roofline_second, roofline_third = sorted([roof_pj, roof_cols, roof_rows], key=lambda r: -r["avg_launch_ms"])
         roofline_fourth = None
-
-
-    # parity and the CPU baseline (checker / reported baseline only, outside any timing): the oracle extracts a
-    # bounded sample of the same clips on the host cores and EVERY hashprint it produced is compared
-    parity = None
-    cpu_baseline = None
-    if rank == 0 and not args.no_parity:
-        from oracle import oracle
-        plan = oracle.Plan(n_samples)
-        got_all = hp.cpu().numpy().view(np.uint64)
-        if world == 1 and not args.no_cpu_baseline:
-            from hpfw_amd import hostinfo
-            budget = hostinfo.cpu_budget()                   # affinity and cgroup quota, not the machine's core count
-            ref_libs = hostinfo.reference_cpu_libraries()    # FFTW3 / Eigen3 / TBB / essentia / MKL: looked for, not assumed
-            cores = budget["usable"]
-            n_cpu = min(n_clips, max(1, args.cpu_clips_per_core * cores))
-            sample = pcm[:n_cpu].cpu().numpy()
-            t1 = time.perf_counter()
-            want = plan.extract_batch(filt, sample, n_threads=cores)
-            cdt = time.perf_counter() - t1
-            idx = np.arange(n_cpu)
-            # one thread, stage by stage (4 clips): where the CPU path spends its time
-            st = {"spectrum": 0.0, "cq": 0.0, "db": 0.0, "project": 0.0, "pack": 0.0}
-            n_one = min(4, n_cpu)
-            t_one = time.perf_counter()
-            for c in sample[:n_one]:
-                ta = time.perf_counter(); x = plan.spectrum(c)
-                tb = time.perf_counter(); m = plan.cqmag(x)
-                tc = time.perf_counter(); d = oracle.db(m)
-                td = time.perf_counter(); pr = oracle.project_q(filt, d) if oracle.get_projection() else oracle.project(filt, d)
-                te = time.perf_counter(); oracle.pack_q(pr) if oracle.get_projection() else oracle.pack(pr)
-                tf = time.perf_counter()
-                for key, dtk in zip(st, (tb - ta, tc - tb, td - tc, te - td, tf - te)):
-                    st[key] += dtk
-            one_dt = time.perf_counter() - t_one
-            scaling = (n_cpu / cdt) / (n_one / one_dt)
-            cpu_baseline = {"value": round(n_cpu * geo.n_hp / cdt, 1), "unit": "hashprints/s", "cores": cores,
-                            "kind": "port",
-                            "sample": f"{n_cpu} of the same {args.seconds:g} s clips, oracle/hpfw_oracle.c "
-                                      f"(own C restatement, -O3 -mfma), {cores} threads = the CPUs this process may use "
-                                      f"(machine: {budget['os_cpu_count']}, cgroup quota: {budget['cgroup_cpus']}) in static "
-                                      f"chunks as flow_builder.hpp:321-325, {cdt:.1f} s",
-                            "clips_per_s": round(n_cpu / cdt, 2),
-                            "host": budget,
-                            "reference_cpu_libraries": ref_libs,
-
-                            "threads_over_one_thread": round(scaling, 2),
-                            "one_thread": {"clips_per_s": round(n_one / one_dt, 2), "clips": n_one,
-                                           "ms_per_clip_by_stage": {k: round(v * 1e3 / n_one, 1) for k, v in st.items()}}}
-        else:
-            # (N > 1, or no CPU baseline asked for: 32 clips spread over the batch -- with several ranks on a box the kernels of
-            # one run beside the other's, which is where round 3's packed arithmetic went wrong)
-            idx = np.unique(np.linspace(0, n_clips - 1, min(32, n_clips)).astype(np.int64))
-            from hpfw_amd import hostinfo
-            threads = max(1, hostinfo.cpu_budget()["usable"] // max(world, 1))   # (the cgroup's CPUs, not the machine's)
-            want = plan.extract_batch(filt, pcm[idx].cpu().numpy(), n_threads=threads)
-        parity = {"clips_checked": int(len(idx)), "bit_identical": bool(np.array_equal(got_all[idx], want)),
-                  "hashprints_differing": int((got_all[idx] != want).sum())}
-
-    # the reference's arithmetic type for filters * frames is f32 (parallel_collector.h:57,127): the same pass with the f32
-    # fma chain (S9) instead of the fixed-point default (S9q), and every hashprint of the batch compared between the two
-    f32_chain = None
-    if fixed_point and not args.no_f32_chain:
-        hp32 = torch.empty_like(hp)
-        gpu.set_projection(0)
-        try:
-            def step32():
-                gpu.extract_dev(pcm.data_ptr(), n_samples, n_clips, hp32.data_ptr(), stream)
-            step32()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(2):
-                step32()
-            torch.cuda.synchronize()
-            dt32 = (time.perf_counter() - t1) / 2
-        finally:
-            gpu.set_projection(1)
-        x = torch.bitwise_xor(hp, hp32)
-        words = int((x != 0).sum().item())
-        bits = 0
-        for sh in range(0, 64, 16):                          # popcount by 16-bit table-free folding on the device
-            v = (x >> sh) & 0xFFFF
-            v = (v & 0x5555) + ((v >> 1) & 0x5555)
-            v = (v & 0x3333) + ((v >> 2) & 0x3333)
-            v = (v & 0x0F0F) + ((v >> 4) & 0x0F0F)
-            v = (v & 0x00FF) + ((v >> 8) & 0x00FF)
-            bits += int(v.sum().item())
-        f32_chain = {"ms_per_step": round(dt32 * 1e3, 3), "clips_per_s": round(n_clips / dt32, 1),
-                     "hashprints_per_s": round(n_clips * geo.n_hp / dt32, 1),
-                     "hashprints_differing_vs_fixed_point": words, "bits_differing_vs_fixed_point": bits,
-                     "hashprints_compared": int(hp.numel()), "bits_compared": int(hp.numel()) * 64,
-                     "note": "hpfw_gpu_set_projection(h, 0): filters * frames as the f32 fma chain on v_mfma_f32_32x32x2_f32, "
-                             "rank 0's batch, outside the timed region"}
-        del hp32, x
-
-    pcie = None
-    if rank == 0 and world == 1 and not args.no_pcie:
-        pcie = bench_pcie(torch, gpu, pcm, n_samples, geo, hp)
-        if hasattr(torch._C, "_host_emptyCache"):
-            torch._C._host_emptyCache()        # the section's 0.7 GB of pinned host memory go back (torch caches them)
-
-    any_len = None
-    if rank == 0 and world == 1 and not args.no_any_length:
-        any_len = bench_any_length(torch, gpu, pcm, n_samples, None if args.no_parity else __import__("oracle.oracle").oracle, filt)
-
-    ffi = None
-    if rank == 0 and world == 1 and not args.no_ffi:
-        ffi = bench_ffi(torch, pcm, n_samples, filt, hp, args.ffi_files)
-
-    search = None
-    if not args.no_search:
-        search = bench_search(torch, tdist if world > 1 else None, gpu, hdist, synth, args, rank, world, device,
-                              stream, barrier, max_over_ranks, rehearse)
-
-    learn = None
-    if not args.no_learn and rank == 0 and world == 1:
-        learn = bench_learn(torch, gpu, args, pcm, n_samples, stream, filt)
-
-    stream_res = None
-    if not args.no_search and not args.no_stream:
-        stream_res = bench_stream(torch, tdist if world > 1 else None, gpu, hdist, synth, args, rank, world, device,
-                                  stream, barrier, rehearse)
-
-    if rank == 0:
-        comm = None
-        if world > 1:
-            comm = {"backend": tdist.get_backend(), "world_size": tdist.get_world_size(), "ranks_seen": ranks_seen,
-                    "devices_seen": devices_seen,
-                    "note": "backend 'nccl' is RCCL on ROCm; one process and one GPU per rank; ranks_seen / devices_seen come from "
-                            "an all-gather of every rank's (rank, local device) at start-up"}
-        line = {
-            "metric": "hashprints/sec (index) + Hamming matches/sec (search), 30 s@44.1 kHz clips",
-            "value": round(value, 1), "unit": "hashprints/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (transforms, dB) + int8 digits / int64 sums (projection)" if fixed_point else "f32", "data": "synthetic",
-            "config": {"workload": f"configs[1]: {n_clips} x {args.seconds:g} s synthetic 44.1 kHz PCM16 clips per GPU, "
-                                   "hashprint extraction only (CQT + dB + projection + bit pack), inputs resident in HBM",
-                       "clips_per_gpu": n_clips, "clip_seconds": args.seconds, "hashprints_per_clip": geo.n_hp,
-                       "generator": f"clips 0..{n_spec - 1} of every rank: hpfw_amd.synth.gen_clip (the tests' generator); "
-                                    "the rest: the same recipe with the device RNG",
-                       "clip0_sha256": clip0_sha,
-                       "parallelism": f"clips sharded over {world} GPU(s), no collective on this path"},
-            "clips_per_s": round(value / geo.n_hp, 1),
-            "event_ms_per_step_rank0": round(ev_ms / args.steps, 3),
-            "per_rank_ms_per_step": [round(t, 3) for t in per_rank_ms],
-            "per_gpu_work": {"clips": n_clips, "hashprints": n_clips * geo.n_hp,
-                             "note": "weak scaling: what every rank does per step is what the N = 1 run does"},
-            "kernel_ms_one_pass": split,
-            "roofline": roofline, "roofline_second_kernel": roofline_second, "roofline_third_kernel": roofline_third,
-            "roofline_fourth_kernel": roofline_fourth,
-            "cpu_baseline": cpu_baseline, "parity": parity,
-            "projection_f32_chain": f32_chain,
-            "pcie_inclusive": pcie, "ffi": ffi, "any_length": any_len, "search": search,
-            "stream": stream_res, "filter_learning": learn, "rccl": comm,
-        }
-        print(json.dumps(line), flush=True)
-    gpu.close()
-    if world > 1:
-        tdist.destroy_process_group()
+    return split, (roofline, roofline_second, roofline_third, roofline_fourth)
 
 
 def exchange_hits(tdist, hits, gathered, world, cpu_collectives=False):

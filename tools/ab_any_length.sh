@@ -1,7 +1,7 @@
 #!/bin/bash
 # the any-length (chirp-z forward transform) section of bench.py for several library builds: tools/ab_any_length.sh lib lib_old
 cd "$(dirname "$0")/.."
-ARGS="--steps 3 --warmup 1 --no-search --no-stream --no-learn --no-cpu-baseline --no-pcie --no-ffi --no-f32-chain"
+ARGS="--full --steps 3 --warmup 1 --no-search --no-stream --no-learn --no-cpu-baseline --no-pcie --no-ffi --no-f32-chain"
 for rep in 1 2; do
 for v in "$@"; do
   HPFW_GPU_LIB=$PWD/hpfw_amd/$v/libhpfw_gpu.so timeout -k 10 300 python bench.py $ARGS 2>/dev/null | python3 -c "

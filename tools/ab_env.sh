@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 VAR=$1; VAL=${2:-1}; REPS=${3:-2}
 for rep in $(seq $REPS); do
 for v in "" "$VAL"; do
-  env ${v:+$VAR=$v} timeout -k 10 300 python bench.py --no-cpu-baseline --no-search --no-pcie --no-any-length --no-learn --no-f32-chain --no-ffi --steps 10 --warmup 3 2>/dev/null | python3 -c "
+  env ${v:+$VAR=$v} timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-search --no-pcie --no-any-length --no-learn --no-f32-chain --no-ffi --steps 10 --warmup 3 2>/dev/null | python3 -c "
 import json,sys
 for ln in sys.stdin:
     if ln.startswith('{'):

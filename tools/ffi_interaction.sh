@@ -1,7 +1,7 @@
 #!/bin/bash
 # the file-level FFI section of bench.py alone and behind the host-buffer (pcie) section: distinct-length files per second
 cd "$(dirname "$0")/.."
-COMMON="--steps 3 --warmup 1 --no-search --no-stream --no-learn --no-cpu-baseline --no-f32-chain --no-any-length --no-parity"
+COMMON="--full --steps 3 --warmup 1 --no-search --no-stream --no-learn --no-cpu-baseline --no-f32-chain --no-any-length --no-parity"
 for rep in 1 2; do
 for extra in "--no-pcie" ""; do
   HPFW_PLAN_TIMING=1 timeout -k 10 300 python bench.py $COMMON $extra 2> >(grep "plan timing" >&2) | python3 -c "

@@ -4,7 +4,7 @@
 #   tools/sweep_env.sh HPFW_FWD_CHUNK 16 8 32 0
 cd "$(dirname "$0")/.."
 VAR=$1; shift
-ARGS="--steps 10 --warmup 3 --no-search --no-stream --no-learn --no-cpu-baseline --no-pcie --no-ffi --no-f32-chain --no-any-length --no-parity"
+ARGS="--full --steps 10 --warmup 3 --no-search --no-stream --no-learn --no-cpu-baseline --no-pcie --no-ffi --no-f32-chain --no-any-length --no-parity"
 for rep in 1 2; do
 for v in "$@"; do
   env $VAR=$v timeout -k 10 300 python bench.py $ARGS 2>/dev/null | python3 -c "
