@@ -8,6 +8,8 @@ from ._lib import (Gpu, HpfwError, COMBINER_CONFIG, HIT_DTYPE, VOTE_DTYPE, KERNE
                    plan_checksum, supported_length)
 from .collector import ParallelCollector  # noqa: F401
 from .liveid import LiveSongIdentification  # noqa: F401
+from .combiner import AudioCombiner  # noqa: F401
 
 __all__ = ["Gpu", "HpfwError", "HIT_DTYPE", "VOTE_DTYPE", "KERNEL_KINDS", "LIB_PATH", "lib", "merge_topk",
-           "plan_checksum", "supported_length", "ParallelCollector", "LiveSongIdentification"]
+           "plan_checksum", "supported_length", "ParallelCollector", "LiveSongIdentification",
+           "AudioCombiner"]

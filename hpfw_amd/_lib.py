@@ -14,6 +14,10 @@ LIB_PATH = os.environ.get("HPFW_GPU_LIB") or os.path.join(_HERE, "lib", "libhpfw
 
 HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("offset", "<i4"), ("pad", "<u4")])
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
+# hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
+COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
+ALIGN_DTYPE = np.dtype([("rec", "<u4"), ("peak", "<u4"), ("offset", "<i8")])
+NO_REC = 0xFFFFFFFF
 
 KERNEL_KINDS = ("fwd_rows", "fwd_cols", "cq_chirpz", "db", "project_mfma", "delta_pack",
                 "hamming_scan", "topk", "pcm_pairs", "fwd_span")
@@ -39,6 +43,9 @@ EXPORTS = (
     "hpfw_gpu_set_kernel_timing", "hpfw_gpu_get_kernel_timing", "hpfw_gpu_plan_checksum",
     "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
     "hpfw_gpu_hashprints_from_db", "hpfw_gpu_stage_delta_q",
+    "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
+    "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
+    "hpfw_gpu_combiner_find_device", "hpfw_gpu_combiner_align", "hpfw_gpu_combiner_align_device", "hpfw_gpu_wav_read_pcm16",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -146,6 +153,18 @@ def lib():
     L.hpfw_gpu_hashprints_from_db.argtypes = [vp, vp, i64, i64, vp, vp]
     L.hpfw_gpu_stage_delta_q.argtypes = [vp, vp, i64, i64, vp, vp, vp]
     L.hpfw_gpu_set_conventions.argtypes = [vp, u32]
+    L.hpfw_gpu_mel_cov_accumulate_pcm16_host.argtypes = [vp, vp, i64, i64]
+    L.hpfw_gpu_combiner_clear.argtypes = [vp]
+    L.hpfw_gpu_combiner_add.argtypes = [vp, vp, vp, i64]
+    L.hpfw_gpu_combiner_add_device.argtypes = [vp, vp, vp, i64, vp]
+    L.hpfw_gpu_combiner_size.argtypes = [vp]
+    L.hpfw_gpu_combiner_size.restype = i64
+    L.hpfw_gpu_combiner_get.argtypes = [vp, vp, vp, vp, i64]
+    L.hpfw_gpu_combiner_find.argtypes = [vp, vp, vp, vp, i64, vp]
+    L.hpfw_gpu_combiner_find_device.argtypes = [vp, vp, vp, vp, i64, vp, vp]
+    L.hpfw_gpu_combiner_align.argtypes = [vp, vp, vp, vp, i64, i32, vp]
+    L.hpfw_gpu_combiner_align_device.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
+    L.hpfw_gpu_wav_read_pcm16.argtypes = [ctypes.c_char_p, vp, i64, ctypes.POINTER(i64)]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -342,6 +361,64 @@ class Gpu:
         check(lib().hpfw_gpu_mel_hashprints_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], _hp(hp), stride, _hp(n)))
         return [hp[i, :n[i]].copy() for i in range(pcm.shape[0])]
 
+    def mel_cov_accumulate(self, pcm):
+        """the combiner's filter learning: Mel front end + covariance of HPFW_CONFIG_COMBINER frames, pcm [n_clips][n] host"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        check(lib().hpfw_gpu_mel_cov_accumulate_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0]))
+
+    # ---- AudioCombiner's inverted index (combiner.h:90-132) ----------------------------------
+    def combiner_clear(self):
+        check(lib().hpfw_gpu_combiner_clear(self._h))
+
+    def combiner_add(self, recordings):
+        """append recordings (a list of uint16 arrays), numbered on from combiner_size()"""
+        hp, off = _ragged(recordings, np.uint16)
+        check(lib().hpfw_gpu_combiner_add(self._h, _hp(hp), _hp(off), off.size - 1))
+
+    def combiner_add_dev(self, d_hp, offsets, stream=0):
+        off = np.ascontiguousarray(offsets, np.int64)
+        check(lib().hpfw_gpu_combiner_add_device(self._h, d_hp, _hp(off), off.size - 1, stream))
+
+    def combiner_size(self):
+        return int(lib().hpfw_gpu_combiner_size(self._h))
+
+    def combiner_get(self):
+        """(val_start int64 [65537], rec uint32 [postings], off uint32 [postings]) copied back from HBM"""
+        vs = np.zeros(65537, np.int64)
+        check(lib().hpfw_gpu_combiner_get(self._h, _hp(vs), None, None, 0))
+        n = int(vs[-1])
+        rec, off = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        check(lib().hpfw_gpu_combiner_get(self._h, _hp(vs), _hp(rec), _hp(off), n))
+        return vs, rec, off
+
+    def combiner_find(self, queries, exclude=None):
+        """AudioCombiner::find for every query (a list of uint16 arrays): COMBINE_DTYPE [n_q]; exclude: ids or -1"""
+        hp, off = _ragged(queries, np.uint16)
+        ex = _exclude(exclude, off.size - 1)
+        out = np.zeros(off.size - 1, COMBINE_DTYPE)
+        check(lib().hpfw_gpu_combiner_find(self._h, _hp(hp), _hp(off), _hp(ex), off.size - 1, _hp(out)))
+        return out
+
+    def combiner_find_dev(self, d_q, q_off, exclude, d_out, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        ex = _exclude(exclude, off.size - 1)
+        check(lib().hpfw_gpu_combiner_find_device(self._h, d_q, _hp(off), _hp(ex), off.size - 1, d_out, stream))
+
+    def combiner_align(self, queries, k, exclude=None):
+        """per query the k recordings with the highest per-offset peak: ALIGN_DTYPE [n_q][k]"""
+        hp, off = _ragged(queries, np.uint16)
+        ex = _exclude(exclude, off.size - 1)
+        out = np.zeros((off.size - 1, int(k)), ALIGN_DTYPE)
+        check(lib().hpfw_gpu_combiner_align(self._h, _hp(hp), _hp(off), _hp(ex), off.size - 1, int(k), _hp(out)))
+        return out
+
+    def combiner_align_dev(self, d_q, q_off, exclude, k, d_out, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        ex = _exclude(exclude, off.size - 1)
+        check(lib().hpfw_gpu_combiner_align_device(self._h, d_q, _hp(off), _hp(ex), off.size - 1, int(k), d_out, stream))
+
     # ---- filter learning ------------------------------------------------------------------
     def cov_reset(self):
         check(lib().hpfw_gpu_cov_reset(self._h))
@@ -461,6 +538,34 @@ class Gpu:
         launches = (ctypes.c_int * 16)()
         check(lib().hpfw_gpu_get_kernel_timing(self._h, names, ms, launches, ctypes.byref(n)))
         return {names[i].decode(): (float(ms[i]), int(launches[i])) for i in range(n.value)}
+
+
+def _ragged(arrays, dtype):
+    """a list of 1-D arrays -> (concatenation, offsets int64 [n + 1])"""
+    arrays = [np.ascontiguousarray(a, dtype).ravel() for a in arrays]
+    off = np.zeros(len(arrays) + 1, np.int64)
+    off[1:] = np.cumsum([a.size for a in arrays])
+    hp = np.concatenate(arrays) if arrays and off[-1] else np.zeros(1, dtype)
+    return np.ascontiguousarray(hp, dtype), off
+
+
+def _exclude(exclude, n):
+    if exclude is None:
+        return np.full(max(n, 1), -1, np.int32)
+    ex = np.ascontiguousarray(exclude, np.int32).ravel()
+    if ex.size != n:
+        raise ValueError("exclude needs one recording id (or -1) per query")
+    return ex if n else np.full(1, -1, np.int32)
+
+
+def wav_read(path):
+    """a WAV file as the live-id file entry points read it: int16 mono (stereo averaged), 44.1 kHz only"""
+    n = ctypes.c_int64(0)
+    p = os.fsencode(path)
+    check(lib().hpfw_gpu_wav_read_pcm16(p, None, 0, ctypes.byref(n)))
+    out = np.zeros(max(n.value, 1), np.int16)
+    check(lib().hpfw_gpu_wav_read_pcm16(p, _hp(out), out.size, ctypes.byref(n)))
+    return out[:n.value]
 
 
 def merge_topk(per_shard_hits, k):

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/hpfw_gpu.h"
+#include "combiner.h"
 #include "kernels.h"
 #include "plan.h"
 
@@ -326,6 +327,8 @@ struct hpfw_gpu {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     float k_ms[K_COUNT] = {0};
     int k_launches[K_COUNT] = {0};
+    // AudioCombiner's inverted index (k_combiner.hip), created on first use
+    std::unique_ptr<hpfw::Combiner> combiner;
 };
 
 namespace {
@@ -1151,6 +1154,7 @@ void hpfw_gpu_destroy(hpfw_gpu *h)
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
+    h->combiner.reset();
     delete h;
 }
 
@@ -1892,6 +1896,33 @@ int hpfw_gpu_mel_hashprints_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t 
     return rc;
 }
 
+int hpfw_gpu_mel_cov_accumulate_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips)
+{
+    if (!h || !pcm || n_clips < 0 || n_samples < 1) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_clips == 0) return 0;
+    const hpfw_handle_config cfg = HPFW_CONFIG_COMBINER;
+    const int64_t frames = hpfw::mel_frames(n_samples);
+    const size_t per = (size_t)hpfw::kMelBands * frames;
+    int16_t *d_pcm = nullptr;
+    float *d_s = nullptr;
+    int32_t *d_cols = nullptr;
+    int rc = 0;
+    if (hipMalloc((void **)&d_pcm, (size_t)n_clips * n_samples * 2) != hipSuccess || hipMalloc((void **)&d_s, (size_t)n_clips * per * 4) != hipSuccess ||
+        hipMalloc((void **)&d_cols, (size_t)n_clips * 4) != hipSuccess)
+        rc = fail(HPFW_E_NOMEM, "hipMalloc failed");
+    if (!rc && (hipMemcpy(d_pcm, pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemset(d_s, 0, (size_t)n_clips * per * 4) != hipSuccess))
+        rc = fail(HPFW_E_HIP, "H2D copy failed");
+    if (!rc) rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm, n_samples, n_clips, d_s, d_cols, nullptr);
+    if (!rc) rc = hpfw_gpu_cfg_cov_accumulate(h, &cfg, d_s, d_cols, n_clips, frames, nullptr);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
+    if (d_pcm) (void)hipFree(d_pcm);
+    if (d_s) (void)hipFree(d_s);
+    if (d_cols) (void)hipFree(d_cols);
+    return rc;
+}
+
 // ---- filter learning: preprocess() of the reference (parallel_collector.h:82-112) ---------------
 static int cov_prepare(hpfw_gpu *h, hipStream_t s)
 {
@@ -2284,6 +2315,125 @@ int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
     (void)hipFree(d_q);
     (void)hipFree(d_out);
     return rc;
+}
+
+// ---- AudioCombiner: exact-hash index + offset votes (k_combiner.hip) --------------------------------
+static hpfw::Combiner *combiner_of(hpfw_gpu *h)
+{
+    if (!h->combiner) h->combiner.reset(new hpfw::Combiner());
+    return h->combiner.get();
+}
+
+int hpfw_gpu_combiner_clear(hpfw_gpu *h)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    combiner_of(h)->clear();
+    return 0;
+}
+
+static int combiner_add_impl(hpfw_gpu *h, const uint16_t *hp, const int64_t *offsets, int64_t n_rec, bool dev, hipStream_t s)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    Ordered ordered(h, s);
+    std::string why;
+    const int rc = combiner_of(h)->add(hp, dev, offsets, n_rec, s, why);
+    return rc ? fail(rc, why) : 0;
+}
+
+int hpfw_gpu_combiner_add(hpfw_gpu *h, const uint16_t *hp, const int64_t *offsets, int64_t n_rec)
+{
+    return combiner_add_impl(h, hp, offsets, n_rec, false, nullptr);
+}
+
+int hpfw_gpu_combiner_add_device(hpfw_gpu *h, const uint16_t *d_hp, const int64_t *offsets, int64_t n_rec, void *stream)
+{
+    return combiner_add_impl(h, d_hp, offsets, n_rec, true, (hipStream_t)stream);
+}
+
+int64_t hpfw_gpu_combiner_size(hpfw_gpu *h) { return h && h->combiner ? h->combiner->size() : 0; }
+
+int hpfw_gpu_combiner_get(hpfw_gpu *h, int64_t *val_start, uint32_t *rec, uint32_t *off, int64_t cap)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    std::string why;
+    const int rc = combiner_of(h)->get(val_start, rec, off, cap, why);
+    return rc ? fail(rc, why) : 0;
+}
+
+static int combiner_search_device(hpfw_gpu *h, const uint16_t *d_q, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                  hpfw_combine_result *d_find, int k, hpfw_align_hit *d_align, hipStream_t s)
+{
+    if (!h || !q_off || n_q < 0 || (!d_find && !d_align)) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    Ordered ordered(h, s);
+    std::string why;
+    const int rc = combiner_of(h)->search(d_q, q_off, exclude, n_q, d_find, k, d_align, s, why);
+    return rc ? fail(rc, why) : 0;
+}
+
+// host buffers: queries in, results out, synchronises
+static int combiner_search_host(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                hpfw_combine_result *find_out, int k, hpfw_align_hit *align_out)
+{
+    if (!h || !q_off || n_q < 0 || (!find_out && !align_out)) return fail(HPFW_E_INVALID, "bad argument");
+    if (align_out && (k < 1 || k > 64)) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    const int64_t total = q_off[n_q] - q_off[0];
+    if (total < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+    if (total && !q_hp) return fail(HPFW_E_INVALID, "null queries");
+    const size_t out_bytes = find_out ? (size_t)n_q * sizeof(hpfw_combine_result) : (size_t)n_q * k * sizeof(hpfw_align_hit);
+    uint16_t *d_q = nullptr;
+    void *d_out = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_q, (size_t)std::max<int64_t>(total, 1) * 2));
+    if (hipMalloc(&d_out, out_bytes) != hipSuccess) {
+        (void)hipFree(d_q);
+        return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    }
+    int rc = 0;
+    std::vector<int64_t> rel((size_t)n_q + 1);
+    for (int64_t i = 0; i <= n_q; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    if (total && hipMemcpy(d_q, q_hp + q_off[0], (size_t)total * 2, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(HPFW_E_HIP, "H2D copy failed");
+    if (!rc)
+        rc = combiner_search_device(h, d_q, rel.data(), exclude, n_q, find_out ? (hpfw_combine_result *)d_out : nullptr, k,
+                                    find_out ? nullptr : (hpfw_align_hit *)d_out, nullptr);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
+    if (!rc && hipMemcpy(find_out ? (void *)find_out : (void *)align_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(HPFW_E_HIP, "D2H copy failed");
+    (void)hipFree(d_q);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int hpfw_gpu_combiner_find_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                  hpfw_combine_result *d_out, void *stream)
+{
+    if (!d_out) return fail(HPFW_E_INVALID, "null output");
+    return combiner_search_device(h, d_q_hp, q_off, exclude, n_q, d_out, 0, nullptr, (hipStream_t)stream);
+}
+
+int hpfw_gpu_combiner_find(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                           hpfw_combine_result *out)
+{
+    if (!out) return fail(HPFW_E_INVALID, "null output");
+    return combiner_search_host(h, q_hp, q_off, exclude, n_q, out, 0, nullptr);
+}
+
+int hpfw_gpu_combiner_align_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                   int k, hpfw_align_hit *d_out, void *stream)
+{
+    if (!d_out || k < 1 || k > 64) return fail(HPFW_E_INVALID, "null output or k outside 1..64");
+    return combiner_search_device(h, d_q_hp, q_off, exclude, n_q, nullptr, k, d_out, (hipStream_t)stream);
+}
+
+int hpfw_gpu_combiner_align(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q, int k,
+                            hpfw_align_hit *out)
+{
+    if (!out) return fail(HPFW_E_INVALID, "null output");
+    return combiner_search_host(h, q_hp, q_off, exclude, n_q, nullptr, k, out);
 }
 
 // ---- voting search (AnnStorage semantics, exact neighbours) ------------------------------------

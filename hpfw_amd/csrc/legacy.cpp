@@ -311,6 +311,29 @@ static bool read_clip(const std::string &path, std::vector<int16_t> &pcm, std::s
     }
 }
 
+extern "C" int hpfw_gpu_wav_read_pcm16(const char *path, int16_t *out, int64_t cap, int64_t *n)
+{
+    if (!path || !n) {
+        hpfw_internal_set_error("null argument");
+        return HPFW_E_INVALID;
+    }
+    *n = 0;
+    std::vector<int16_t> pcm;
+    std::string why;
+    if (!read_clip(path, pcm, why)) {
+        hpfw_internal_set_error(why.c_str());
+        return HPFW_E_IO;
+    }
+    *n = (int64_t)pcm.size();
+    if (!out) return 0;
+    if (cap < *n) {
+        hpfw_internal_set_error("buffer smaller than the file's samples");
+        return HPFW_E_INVALID;
+    }
+    std::copy(pcm.begin(), pcm.end(), out);
+    return 0;
+}
+
 static uint64_t *calc_hashprint_impl(hpfw_legacy_collector *c, const char *filename, int *size)
 {
     if (size) *size = 0;

@@ -186,6 +186,64 @@ int hpfw_gpu_cfg_learn_filters(hpfw_gpu *h, const hpfw_handle_config *cfg, float
 int hpfw_gpu_mel_hashprints_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
                                        uint16_t *hp, int64_t hp_stride, int32_t *n_hp);
 
+/* the combiner's filter learning from host PCM: the Mel front end above, then hpfw_gpu_cfg_cov_accumulate for
+ * HPFW_CONFIG_COMBINER (what hpfw_gpu_cov_accumulate_pcm16_host is for live-id).  Finish with
+ * hpfw_gpu_cfg_learn_filters(h, &combiner_config, ...). */
+int hpfw_gpu_mel_cov_accumulate_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips);
+
+/* ---- AudioCombiner: exact-hash inverted index + offset votes (combiner.h:90-132) ----------------------------
+ * Recordings are uint16 hashprints of HPFW_CONFIG_COMBINER, numbered 0, 1, ... in the order they are added.  The
+ * index is a CSR over the 65 536 values: val_start [65537] and postings (rec, off) in ascending global position
+ * (recording, offset) inside every value -- build_db (:90-97) with the recordings in add order.  An append rebuilds it.
+ *
+ * find (:100-132) walks the events of a query in stream order: frame c ascending, then the postings of Q[c] in index
+ * order, the query's own recording (`exclude`, -1 = none) skipped.  Event (j, d = c - o) has count = ++cnt[j][d]; it
+ * changes the result iff count > confidence: to {j, count, 1, d} when j differs from the result's recording, else to
+ * {j, count, confidence + 1, d}.  The result starts as {0xffffffff, 0, 0, 0}.  Computed on the device, bit-exact.
+ *
+ * align: for every recording j but the excluded one, peak = the most events on one offset d and offset = the smallest
+ * such d; the k best recordings per query by (peak desc, rec asc), recordings with peak 0 not listed (rec = 0xffffffff).
+ *
+ * Workspace: the per-query bin arrays (sum over j of C_q + L_j - 1 uint32) and the event chunks are bounded by
+ * HPFW_COMBINER_WORKSPACE_MB in the environment (default 1024, read at every call); a query whose bin array alone
+ * exceeds it fails with HPFW_E_INVALID.  Unlike the other device entry points, the combiner's wait for their stream
+ * once per pass of queries (the host sizes the event chunks from the pass's event total) and once per add (the CSR is
+ * rebuilt at once). */
+typedef struct {
+    uint32_t rec;        /* recording id, 0xffffffff = none */
+    uint32_t pad;
+    int64_t cnt;
+    int64_t confidence;
+    int64_t offset;      /* d = c - o */
+} hpfw_combine_result;
+typedef struct {
+    uint32_t rec;        /* 0xffffffff = padding */
+    uint32_t peak;
+    int64_t offset;
+} hpfw_align_hit;
+int hpfw_gpu_combiner_clear(hpfw_gpu *h);
+/* appends n_rec recordings: recording i is hp[offsets[i] .. offsets[i+1]) (host or device source) */
+int hpfw_gpu_combiner_add(hpfw_gpu *h, const uint16_t *hp, const int64_t *offsets, int64_t n_rec);
+int hpfw_gpu_combiner_add_device(hpfw_gpu *h, const uint16_t *d_hp, const int64_t *offsets, int64_t n_rec, void *stream);
+int64_t hpfw_gpu_combiner_size(hpfw_gpu *h); /* number of recordings */
+/* the index on the host: val_start [65537] always; rec / off [postings] when not NULL (cap = their capacity; the number
+ * of postings is val_start[65536]).  Synchronises. */
+int hpfw_gpu_combiner_get(hpfw_gpu *h, int64_t *val_start, uint32_t *rec, uint32_t *off, int64_t cap);
+/* query q is q_hp[q_off[q] .. q_off[q+1]); exclude [n_q] or NULL (= -1 for all).  Device variants: d_q_hp and d_out on
+ * the device, q_off and exclude on the host. */
+int hpfw_gpu_combiner_find(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                           hpfw_combine_result *out);
+int hpfw_gpu_combiner_find_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude,
+                                  int64_t n_q, hpfw_combine_result *d_out, void *stream);
+/* out [n_q][k], k <= 64 */
+int hpfw_gpu_combiner_align(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                            int k, hpfw_align_hit *out);
+int hpfw_gpu_combiner_align_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude,
+                                   int64_t n_q, int k, hpfw_align_hit *d_out, void *stream);
+/* a WAV file as the live-id file entry points read it: PCM16 mono, or stereo averaged (truncating) to mono, 44.1 kHz
+ * only (HPFW_E_IO otherwise).  *n = samples in the file; out receives them when cap >= *n (out may be NULL). */
+int hpfw_gpu_wav_read_pcm16(const char *path, int16_t *out, int64_t cap, int64_t *n);
+
 /* ---- filter learning: ParallelCollector::preprocess + calc_filters ------------------------
  * (parallel_collector.h:82-112, hashprint_handle.h:96-112).  The handle owns accum_cov
  * (2420 x 2420, parallel_collector.h:76): per clip, the covariance of its context frames (centred
