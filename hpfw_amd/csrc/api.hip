@@ -20,12 +20,18 @@
 
 #include "../../include/hpfw_gpu.h"
 #include "combiner.h"
+#include "hip_owned.h"
 #include "kernels.h"
 #include "plan.h"
 
 struct hpfw_gpu;
 
 namespace {
+
+using hpfw::DevBuf;
+using hpfw::Event;
+using hpfw::HostBuf;
+using hpfw::Stream;
 
 thread_local std::string g_err;
 
@@ -45,18 +51,17 @@ int fail(int code, const std::string &msg)
 thread_local size_t g_uploaded = 0; // bytes uploaded by upload() since get_plan last reset it
 
 template <class T>
-int upload(const std::vector<T> &v, const T **out, std::vector<void *> &owned)
+int upload(const std::vector<T> &v, const T **out, std::vector<DevBuf> &owned)
 {
-    void *d = nullptr;
     g_uploaded += v.size() * sizeof(T);
     if (v.empty()) {
         *out = nullptr;
         return 0;
     }
-    HIP_TRY(hipMalloc(&d, v.size() * sizeof(T)));
-    owned.push_back(d);
-    HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = reinterpret_cast<const T *>(d);
+    owned.emplace_back();
+    HIP_TRY(owned.back().alloc(v.size() * sizeof(T)));
+    HIP_TRY(hipMemcpy(owned.back().get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = owned.back().as<const T>();
     return 0;
 }
 
@@ -73,13 +78,13 @@ hpfw::RadixList to_radix(const std::vector<int> &r)
 // 4 MB chunks, large ones are blocks of their own, and an evicted plan's chunks and blocks go back to the pool for the next
 // length (a corpus of tracks brings a new length with every file: ~40 hipMalloc and, at eviction, as many hipFree per plan
 // cost more than generating the tables).
-void *pool_take(hpfw_gpu *h, size_t bytes);
-void pool_give(hpfw_gpu *h, void *p, size_t bytes);
+DevBuf pool_take(hpfw_gpu *h, size_t bytes);
+void pool_give(hpfw_gpu *h, DevBuf b);
 void pool_release(hpfw_gpu *h);
 
 struct DevPlan {
     hpfw_gpu *owner = nullptr;
-    std::vector<std::pair<void *, size_t>> blocks; // what this plan holds of the pool
+    std::vector<DevBuf> blocks; // what this plan holds of the pool, each block with its real size
     char *cur = nullptr;                           // the open chunk
     size_t left = 0;
     // small tables are written to a host image of the open chunk and go over in one copy per run of them (plan_flush):
@@ -98,7 +103,7 @@ struct DevPlan {
     uint64_t last_use = 0; // for the least-recently-used eviction in get_plan
     ~DevPlan()
     {
-        for (auto &b : blocks) pool_give(owner, b.first, b.second);
+        for (DevBuf &b : blocks) pool_give(owner, std::move(b));
     }
 };
 
@@ -140,20 +145,19 @@ int plan_alloc(DevPlan *dp, size_t bytes, void **out)
     PlanTimer t(&PlanTiming::alloc);
     bytes = (bytes + 255) / 256 * 256;
     if (bytes >= kPlanChunk / 4) { // a block of its own, in 64 KB steps (equal sizes recur: lengths near each other share n1 and n2)
-        const size_t size = (bytes + 65535) / 65536 * 65536;
-        void *p = pool_take(dp->owner, size);
-        if (!p) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
-        dp->blocks.emplace_back(p, size);
-        *out = p;
+        DevBuf b = pool_take(dp->owner, (bytes + 65535) / 65536 * 65536);
+        if (!b) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
+        *out = b.get();
+        dp->blocks.push_back(std::move(b));
         return 0;
     }
     if (dp->left < bytes) {
         int rc = plan_flush(dp);
         if (rc) return rc;
-        void *p = pool_take(dp->owner, kPlanChunk);
-        if (!p) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
-        dp->blocks.emplace_back(p, kPlanChunk);
-        dp->cur = dp->chunk_base = static_cast<char *>(p);
+        DevBuf b = pool_take(dp->owner, kPlanChunk);
+        if (!b) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
+        dp->cur = dp->chunk_base = b.as<char>();
+        dp->blocks.push_back(std::move(b));
         dp->left = kPlanChunk;
         dp->stage.resize(kPlanChunk);
     }
@@ -194,7 +198,13 @@ const char *const kKernelNames[K_COUNT] = {"fwd_rows", "fwd_cols", "cq_chirpz", 
 
 struct TimedLaunch {
     int kind;
-    hipEvent_t a, b;
+    Event a, b;
+};
+
+// the first HIP failure met by a destructor (Timed, a fan-out's join) during the call in progress (ordered_call)
+struct CallStatus {
+    int rc = 0;
+    std::string msg;
 };
 
 } // namespace
@@ -202,9 +212,12 @@ struct TimedLaunch {
 struct hpfw_gpu {
     int device = 0;
     bool has_filters = false;
-    float *d_fpack = nullptr;
-    void *d_fq_image = nullptr; // the filters' fixed-point digits (k_project_q.hip)
-    int projection = 1;         // 1: fixed point (S9q), 0: the f32 fma chain (S9); hpfw_gpu_set_projection
+    DevBuf d_fpack;
+    DevBuf d_fq_image; // the filters' fixed-point digits (k_project_q.hip)
+    int projection = 1; // 1: fixed point (S9q), 0: the f32 fma chain (S9); hpfw_gpu_set_projection
+    // free chunks and blocks of evicted plans, by size (declared before `plans`: a plan gives its blocks back when it goes)
+    std::multimap<size_t, DevBuf> dev_pool;
+    size_t dev_pool_bytes = 0;
     std::map<int64_t, std::unique_ptr<DevPlan>> plans; // one per clip length, least recently used evicted
     // host halves of plans prepared ahead by other threads (hpfw_gpu_prepare_length): a null entry is being built
     std::mutex host_mtx;
@@ -217,39 +230,31 @@ struct hpfw_gpu {
     // queued on this handle since (hpfw_internal_note_idle: the file collectors, once per window of files) -- such plans
     // are evicted without the device-wide wait that an eviction otherwise needs
     uint64_t idle_clock = 0;
-    std::multimap<size_t, void *> dev_pool; // free chunks and blocks of evicted plans, by size
-    size_t dev_pool_bytes = 0;
     unsigned conventions = 0; // hpfw_gpu_set_conventions: essentia conventions that cannot be checked offline
     // clips per pass: 2.5 GB of workspace at 30 s; every launch but the forward transform's chunks fills the 256 CUs many
     // times over, and what one stage leaves for the next (forward bins, dB terms: 2.3 MB per clip) is still in the caches
     // when it is read (1000 clips: 10.25 ms in one pass, 10.0 in four)
     int batch = 256;
-    // extraction workspace
-    size_t ws_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
-    // yp, x, mag, proj, wave maxima [clip][121][16], pairs, second planar buffer of the chirp-z forward transform
-    void *ws[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // extraction workspace: yp, x, mag, proj, wave maxima [clip][121][16], pairs, second planar buffer of the chirp-z
+    // forward transform
+    DevBuf ws[7];
     // index
-    uint64_t *d_db = nullptr;
-    size_t db_cap = 0;
+    DevBuf d_db; // uint64 hashprints
     std::vector<int64_t> db_off{0};
-    int64_t *d_db_off = nullptr;
-    size_t db_off_cap = 0;
+    DevBuf d_db_off;
     bool db_off_dirty = true;
     uint32_t clip_base = 0;
     // search scratch
-    uint64_t *d_best = nullptr;
-    size_t best_cap = 0;
-    int64_t *d_q_off = nullptr;
-    size_t q_off_cap = 0;
+    DevBuf d_best, d_q_off;
     // filter learning: accum_cov of ParallelCollector (parallel_collector.h:76), upper tiles only
-    float *d_cov = nullptr;
-    float *d_cov_ws = nullptr; // scratch of the covariance kernels
-    void *d_cqwork = nullptr;  // chirp-z bands too long for the LDS (k_cq_big.hip)
+    DevBuf d_cov;
+    DevBuf d_cov_ws;  // scratch of the covariance kernels
+    DevBuf d_cqwork;  // chirp-z bands too long for the LDS (k_cq_big.hip)
     // the size classes of the chirp-z stage run side by side (run_front): their workgroups differ in LDS footprint and
     // one class alone leaves part of every CU's LDS and issue slots unused
     static constexpr int kCqSide = 4;
-    hipStream_t cq_side[kCqSide] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t cq_fork = nullptr, cq_join[kCqSide] = {nullptr, nullptr, nullptr, nullptr};
+    Stream cq_side[kCqSide];
+    Event cq_fork, cq_join[kCqSide];
     int cq_concurrent = 1; // HPFW_CQ_SERIAL=1 in the environment at creation: one class after the other on the caller's stream
     // the forward transform of a large batch in chunks of fwd_chunk clips taken in turn by fwd_streams streams (the
     // caller's and side streams): column stage and row stage of a chunk back to back, so that the column stage's output
@@ -262,69 +267,55 @@ struct hpfw_gpu {
     // wait (the stream that first uses them waits for plan_ev): synchronous copies on the default stream waited behind
     // whatever shared its hardware queue -- after bench.py's host-buffer section that was the collector's extraction stream,
     // and a corpus of distinct lengths lost a fifth of its rate (tools/ffi_interaction.sh)
-    hipStream_t plan_stream = nullptr;
-    char *pin_ring = nullptr;
-    size_t pin_cap = 0, pin_off = 0;
-    // HPFW_BACK_OVERLAP=1: the back end (hashprints from dB terms: the int8 matrix pipe) of one pass beside the front end
-    // (transforms: vector ALU, LDS) of the next, on a stream of its own.  Off by default: the kernels slow each other by
-    // what the overlap would gain (9.95-10.03 against 9.70-9.92 ms per 1000 clips on one box)
-    int back_overlap = 0;
-    hipStream_t back_side = nullptr;
-    hipEvent_t back_fork = nullptr, back_join = nullptr;
+    Stream plan_stream;
+    HostBuf pin_ring;
+    size_t pin_off = 0;
     int bz_chunk = 32;  // the same for the chirp-z forward transform's three kernels (HPFW_BZ_CHUNK; 38.6 -> 39.6 k clips/s at 30 s)
-    void *d_topk_scratch = nullptr;
-    size_t topk_scratch_cap = 0;
+    DevBuf d_topk_scratch;
     // Mel front-end: tables (owned by mel_owned), workspaces
     bool mel_ready = false;
     hpfw::HostPlan mel_plan;
     hpfw::RowsArgs mel_rows;
     const float *d_mel_win = nullptr, *d_mel_cpack = nullptr;
-    std::vector<void *> mel_owned;
-    void *d_mel_work = nullptr, *d_mel_small = nullptr;
-    size_t mel_work_cap = 0, mel_small_cap = 0;
-    size_t cqwork_cap = 0;
-    size_t cov_ws_cap = 0;
-    void *d_qa = nullptr;   // queries expanded to fp4 for the matrix-core scan
-    size_t qa_cap = 0;
-    int *d_gk = nullptr;    // longest query of each group of 32
-    size_t gk_cap = 0;
+    std::vector<DevBuf> mel_owned;
+    DevBuf d_mel_work, d_mel_small;
+    DevBuf d_qa; // queries expanded to fp4 for the matrix-core scan
+    DevBuf d_gk; // longest query of each group of 32
     // staging of the host-buffer entry points: kept between calls (a one-file call is otherwise mostly
     // allocation and stream set-up)
-    void *stage_pcm[2] = {nullptr, nullptr};
-    size_t stage_pcm_cap[2] = {0, 0};
-    void *stage_hp = nullptr;
-    size_t stage_hp_cap = 0;
-    hipStream_t stage_copy = nullptr, stage_comp = nullptr;
-    hipEvent_t stage_copied[2] = {nullptr, nullptr}, stage_consumed[2] = {nullptr, nullptr};
-    float *d_clipmax = nullptr; // per-clip maximum magnitude (reference level of the dB conversion)
-    size_t clipmax_cap = 0;
-    int *d_cov_tiles = nullptr;
+    DevBuf stage_pcm[2];
+    DevBuf stage_hp;
+    Stream stage_copy, stage_comp;
+    Event stage_copied[2], stage_consumed[2];
+    DevBuf d_clipmax; // per-clip maximum magnitude (reference level of the dB conversion)
+    DevBuf d_cov_tiles;
     int64_t cov_files = 0;
     // HashprintHandle configurations other than the default (hpfw_gpu_cfg_*): filter operand images by config
-    std::map<std::vector<int>, float *> cfg_fpack;
-    float *d_cfg_proj = nullptr;
-    size_t cfg_proj_cap = 0;
+    std::map<std::vector<int>, DevBuf> cfg_fpack;
+    DevBuf d_cfg_proj;
     struct CfgCov {
-        float *d_accum = nullptr;
-        int *d_tiles = nullptr;
+        DevBuf d_accum;
+        DevBuf d_tiles;
         int64_t clips = 0;
     };
     std::map<std::vector<int>, CfgCov> cfg_cov; // accum_cov of other configurations, by (rows, context)
-    float *d_cfg_cov_ws = nullptr;
-    size_t cfg_cov_ws_cap = 0;
-    // ordering of consecutive entry points that were handed different streams (the workspaces are shared)
-    hipEvent_t order_ev = nullptr;
+    DevBuf d_cfg_cov_ws;
+    // ordering of consecutive entry points that were handed different streams (the workspaces are shared): the stream of
+    // the last call, and whether order_ev marks the end of its work (else the next call on another stream waits for that
+    // stream on the host)
+    Event order_ev;
     hipStream_t order_stream = nullptr;
-    bool order_valid = false;
+    enum { kOrderNone, kOrderEvent, kOrderSync } order = kOrderNone;
+    CallStatus call; // what Timed and the fan-outs of the call in progress report (ordered_call)
     // the tables a new length generates on the device (default stream) are awaited by the stream that first uses them
-    // (Ordered), not by the host: a caller on a stream of its own keeps preparing lengths while earlier files run
-    hipEvent_t plan_ev = nullptr;
+    // (ordered_call), not by the host: a caller on a stream of its own keeps preparing lengths while earlier files run
+    Event plan_ev;
     bool plan_ev_pending = false;
     // timing
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     unsigned timing_mask = 0;
     std::vector<TimedLaunch> timed;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<Event, Event>> ev_pool;
     float k_ms[K_COUNT] = {0};
     int k_launches[K_COUNT] = {0};
     // AudioCombiner's inverted index (k_combiner.hip), created on first use
@@ -342,44 +333,35 @@ hipError_t plan_h2d(hpfw_gpu *h, void *dst, const void *src, size_t bytes)
         ++g_plan_timing->copies;
         g_plan_timing->copied += bytes;
     }
-    if (!h->pin_ring) {
-        if (hipHostMalloc(reinterpret_cast<void **>(&h->pin_ring), kPinRing, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            h->pin_ring = nullptr;
-        } else {
-            h->pin_cap = kPinRing;
-        }
+    if (!h->pin_ring && h->pin_ring.alloc(kPinRing) != hipSuccess) (void)hipGetLastError();
+    const hipStream_t ps = h->plan_stream.get();
+    if (!h->pin_ring || bytes > h->pin_ring.capacity() / 2) { // (a table beyond the ring: the runtime stages it; rare -- clips of many minutes)
+        hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ps);
+        return e != hipSuccess ? e : hipStreamSynchronize(ps);
     }
-    if (!h->pin_ring || bytes > h->pin_cap / 2) { // (a table beyond the ring: the runtime stages it; rare -- clips of many minutes)
-        hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->plan_stream);
-        return e != hipSuccess ? e : hipStreamSynchronize(h->plan_stream);
-    }
-    if (h->pin_off + bytes > h->pin_cap) { // wrap: what was copied out of the ring before has to be gone
-        hipError_t e = hipStreamSynchronize(h->plan_stream);
+    if (h->pin_off + bytes > h->pin_ring.capacity()) { // wrap: what was copied out of the ring before has to be gone
+        hipError_t e = hipStreamSynchronize(ps);
         if (e != hipSuccess) return e;
         h->pin_off = 0;
     }
-    std::memcpy(h->pin_ring + h->pin_off, src, bytes);
-    hipError_t e = hipMemcpyAsync(dst, h->pin_ring + h->pin_off, bytes, hipMemcpyHostToDevice, h->plan_stream);
+    char *slot = h->pin_ring.as<char>() + h->pin_off;
+    std::memcpy(slot, src, bytes);
+    hipError_t e = hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, ps);
     h->pin_off += (bytes + 255) / 256 * 256;
     return e;
 }
 
-int ensure(void **p, size_t *cap, size_t need, hpfw_gpu *pool_owner = nullptr)
+// a workspace of at least `need` bytes (its contents are not kept when it grows)
+int ensure(DevBuf &b, size_t need, hpfw_gpu *pool_owner = nullptr)
 {
-    if (*cap >= need) return 0;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need) != hipSuccess && pool_owner) { // the handle's pool of table blocks may be holding what is missing
+    if (b.capacity() >= need) return 0;
+    hipError_t e = b.alloc(need);
+    if (e != hipSuccess && pool_owner) { // the handle's pool of table blocks may be holding what is missing
         (void)hipGetLastError();
         pool_release(pool_owner);
-    } else if (*p) {
-        *cap = need;
-        return 0;
+        e = b.alloc(need);
     }
-    HIP_TRY(hipMalloc(p, need));
-    *cap = need;
+    if (e != hipSuccess) return fail(HPFW_E_HIP, std::string("device memory for a workspace: ") + hipGetErrorString(e));
     return 0;
 }
 
@@ -391,36 +373,36 @@ int ensure(void **p, size_t *cap, size_t need, hpfw_gpu *pool_owner = nullptr)
 // whole pool back first.
 void pool_release(hpfw_gpu *h)
 {
-    for (auto &kv : h->dev_pool) (void)hipFree(kv.second);
     h->dev_pool.clear();
     h->dev_pool_bytes = 0;
 }
 
-void *pool_take(hpfw_gpu *h, size_t bytes)
+// a block of at least `bytes` (its capacity() is its real size), empty when there is no device memory for it
+DevBuf pool_take(hpfw_gpu *h, size_t bytes)
 {
     auto it = h->dev_pool.lower_bound(bytes);
     if (it != h->dev_pool.end() && it->first <= bytes + bytes / 4) {
-        void *p = it->second;
-        h->dev_pool_bytes -= it->first;      // (it comes back under the size asked for here: the label only ever shrinks)
+        DevBuf b = std::move(it->second);
+        h->dev_pool_bytes -= it->first;
         h->dev_pool.erase(it);
-        return p;
+        return b;
     }
-    void *d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) {
+    DevBuf b;
+    if (b.alloc(bytes) != hipSuccess) {
         (void)hipGetLastError();
         pool_release(h);
-        if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
+        (void)b.alloc(bytes);
     }
-    return d;
+    return b;
 }
 
-void pool_give(hpfw_gpu *h, void *p, size_t bytes)
+// (a block beyond the pool's bound is freed here)
+void pool_give(hpfw_gpu *h, DevBuf b)
 {
+    const size_t bytes = b.capacity();
     if (h && h->dev_pool_bytes + bytes <= ((size_t)4 << 30)) {
-        h->dev_pool.emplace(bytes, p);
+        h->dev_pool.emplace(bytes, std::move(b));
         h->dev_pool_bytes += bytes;
-    } else {
-        (void)hipFree(p);
     }
 }
 
@@ -429,51 +411,60 @@ void pool_give(hpfw_gpu *h, void *p, size_t bytes)
 // index itself ...) and only enqueues on the caller's stream.  Two calls on different streams (a torch
 // side stream and the null stream, or the private non-blocking streams of the *_host entry points) would
 // otherwise overlap on those buffers: each call first makes its stream wait for the event the previous
-// call recorded, and records its own when it has enqueued its work.
-struct Ordered {
-    hpfw_gpu *h;
-    hipStream_t s;
-    Ordered(hpfw_gpu *h_, hipStream_t s_) : h(h_), s(s_)
-    {
-        if (h->order_valid && h->order_stream != s) (void)hipStreamWaitEvent(s, h->order_ev, 0);
-        if (h->plan_ev_pending) {
-            (void)hipStreamWaitEvent(s, h->plan_ev, 0);
-            h->plan_ev_pending = false; // (later calls on other streams are ordered after this one)
-        }
-    }
-    ~Ordered()
-    {
-        if (hipEventRecord(h->order_ev, s) == hipSuccess) {
-            h->order_valid = true;
-            h->order_stream = s;
-        }
-    }
-};
+// call recorded, and records its own when it has enqueued its work.  A call whose record failed leaves no
+// event: the next call on another stream waits for its stream on the host.
+// ordered_call(h, s, body) returns body's status, else the first failure Timed or a fan-out's join reported
+// during it, else the record's.  A failed wait returns before anything is queued.
+int report(hpfw_gpu *h, hipError_t e, const char *what)
+{
+    if (e != hipSuccess && !h->call.rc) h->call = {HPFW_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
+    return e != hipSuccess;
+}
 
+template <class Body>
+int ordered_call(hpfw_gpu *h, hipStream_t s, Body &&body)
+{
+    if (h->order_stream != s) {
+        if (h->order == hpfw_gpu::kOrderEvent) HIP_TRY(hipStreamWaitEvent(s, h->order_ev.get(), 0));
+        if (h->order == hpfw_gpu::kOrderSync) HIP_TRY(hipStreamSynchronize(h->order_stream));
+    }
+    if (h->plan_ev_pending) {
+        HIP_TRY(hipStreamWaitEvent(s, h->plan_ev.get(), 0));
+        h->plan_ev_pending = false; // (later calls on other streams are ordered after this one)
+    }
+    CallStatus outer = std::exchange(h->call, CallStatus{}); // (a call made inside another's body)
+    int rc = body();
+    const hipError_t recorded = hipEventRecord(h->order_ev.get(), s);
+    h->order_stream = s;
+    h->order = recorded == hipSuccess ? hpfw_gpu::kOrderEvent : hpfw_gpu::kOrderSync;
+    CallStatus mine = std::exchange(h->call, std::move(outer));
+    if (!rc && mine.rc) rc = fail(mine.rc, mine.msg);
+    if (!rc && recorded != hipSuccess) rc = fail(HPFW_E_HIP, std::string("hipEventRecord: ") + hipGetErrorString(recorded));
+    return rc;
+}
+
+// the span of the launches in its scope, when h->timing_mask selects `kind`
 struct Timed {
     hpfw_gpu *h;
     int kind;
     hipStream_t s;
-    bool on;
-    hipEvent_t a = nullptr, b = nullptr;
-    Timed(hpfw_gpu *h_, int kind_, hipStream_t s_) : h(h_), kind(kind_), s(s_), on((h_->timing_mask >> kind_) & 1u)
+    bool on = false;
+    Event a, b;
+    Timed(hpfw_gpu *h_, int kind_, hipStream_t s_) : h(h_), kind(kind_), s(s_)
     {
-        if (!on) return;
+        if (!((h->timing_mask >> kind) & 1u)) return;
         if (h->ev_pool.empty()) {
-            (void)hipEventCreate(&a);
-            (void)hipEventCreate(&b);
+            if (report(h, a.create(hipEventDefault), "timing event") || report(h, b.create(hipEventDefault), "timing event")) return;
         } else {
-            a = h->ev_pool.back().first;
-            b = h->ev_pool.back().second;
+            a = std::move(h->ev_pool.back().first);
+            b = std::move(h->ev_pool.back().second);
             h->ev_pool.pop_back();
         }
-        (void)hipEventRecord(a, s);
+        on = !report(h, hipEventRecord(a.get(), s), "timing event record");
     }
     ~Timed()
     {
-        if (!on) return;
-        (void)hipEventRecord(b, s);
-        h->timed.push_back({kind, a, b});
+        if (on && !report(h, hipEventRecord(b.get(), s), "timing event record")) h->timed.push_back({kind, std::move(a), std::move(b)});
     }
 };
 
@@ -567,14 +558,14 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
         const cf *d_tw_n1 = nullptr;
         struct PoolTmp {
             hpfw_gpu *h;
-            std::vector<std::pair<void *, size_t>> v;
-            ~PoolTmp() { for (auto &b : v) pool_give(h, b.first, b.second); }
+            std::vector<DevBuf> v;
+            ~PoolTmp() { for (DevBuf &b : v) pool_give(h, std::move(b)); }
             void *take(size_t bytes)
             {
-                const size_t size = (bytes + 65535) / 65536 * 65536;
-                void *q = pool_take(h, size);
-                if (q) v.emplace_back(q, size);
-                return q;
+                DevBuf b = pool_take(h, (bytes + 65535) / 65536 * 65536);
+                if (!b) return nullptr;
+                v.push_back(std::move(b));
+                return v.back().get();
             }
         } tmp{h, {}};
         {
@@ -594,8 +585,8 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
                 *slot[i] = static_cast<const float *>(d);
             }
             if ((rc = plan_flush(dp.get()))) return rc; // the row transform's tables are used by the kernels below
-            hpfw::launch_bz_pack_stages(bz, d_tw_n1, const_cast<float *>(bz.apack1), const_cast<float *>(bz.apack3), h->plan_stream);
-            hpfw::launch_bz_pack_coefficients(p.n1, bz.k1lo, bz.k1n, d_tw_n1, bz.n_tiles2, const_cast<float *>(bz.apack2), h->plan_stream);
+            hpfw::launch_bz_pack_stages(bz, d_tw_n1, const_cast<float *>(bz.apack1), const_cast<float *>(bz.apack3), h->plan_stream.get());
+            hpfw::launch_bz_pack_coefficients(p.n1, bz.k1lo, bz.k1n, d_tw_n1, bz.n_tiles2, const_cast<float *>(bz.apack2), h->plan_stream.get());
         }
         // chirp, T_L, w[k] / L and Bhat are generated on the device (k_bluestein.hip): a corpus of
         // real recordings brings a new length with every file
@@ -613,7 +604,7 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
         }
         void *scratch = tmp.take(big_l * 8 + plane); // back to the pool with T_n1 when this block ends, after the synchronisation below
         if (!scratch) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
-        hpfw::launch_bz_make_tables(ra, bz, n, static_cast<float *>(scratch), static_cast<float *>(scratch) + 2 * big_l, h->plan_stream);
+        hpfw::launch_bz_make_tables(ra, bz, n, static_cast<float *>(scratch), static_cast<float *>(scratch) + 2 * big_l, h->plan_stream.get());
         // (no host wait: the temporaries go back to the pool, whose next user is ordered after these kernels on the handle's
         // table stream like every table generation and upload; the stream that extracts waits for the event recorded below)
         const hipError_t launched = hipGetLastError();
@@ -747,7 +738,7 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
             for (auto q = h->plans.begin(); q != h->plans.end(); ++q)
                 if (q->second->last_use < lru->second->last_use) lru = q;
             if (lru->second->last_use > h->idle_clock) {
-                (void)hipDeviceSynchronize();
+                HIP_TRY(hipDeviceSynchronize());
                 h->idle_clock = h->plan_clock;
                 goal = budget - budget / 4;
             }
@@ -772,13 +763,13 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
             wb.hann_den[j] = (int)hpfw::cq_hann_den(h->conventions, p.lg[j]);
             lg_max = std::max(lg_max, p.lg[j]);
         }
-        hpfw::launch_cq_windows(c, wb, p.big_m, lg_max, const_cast<cf *>(c.g), h->plan_stream);
-        if (c.g2) hpfw::launch_cq_windows_rows(c, p.n1, g2_max_entries, const_cast<cf *>(c.g2), h->plan_stream);
+        hpfw::launch_cq_windows(c, wb, p.big_m, lg_max, const_cast<cf *>(c.g), h->plan_stream.get());
+        if (c.g2) hpfw::launch_cq_windows_rows(c, p.n1, g2_max_entries, const_cast<cf *>(c.g2), h->plan_stream.get());
         const hipError_t launched = hipGetLastError();
         if (launched != hipSuccess) return fail(HPFW_E_HIP, std::string("constant-Q window tables: ") + hipGetErrorString(launched));
     }
-    // every table of the length is on its way on the table stream: whoever uses them first waits for this (Ordered)
-    HIP_TRY(hipEventRecord(h->plan_ev, h->plan_stream));
+    // every table of the length is on its way on the table stream: whoever uses them first waits for this (ordered_call)
+    HIP_TRY(hipEventRecord(h->plan_ev.get(), h->plan_stream.get()));
     h->plan_ev_pending = true;
     h->plan_bytes += dp->bytes;
     *out = dp.get();
@@ -812,7 +803,7 @@ int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns)
     size_t work = 0;
     for (const hpfw::CqClassDev &cd : dp->cls) work = std::max(work, hpfw::cq_big_work_bytes(cd, nb));
     if (work) {
-        int rc = ensure(&h->d_cqwork, &h->cqwork_cap, work);
+        int rc = ensure(h->d_cqwork, work);
         if (rc) return rc;
     }
     const size_t planar = p.bluestein ? hpfw::bz_plane_bytes(dp->bz, nb) : 0;
@@ -823,22 +814,61 @@ int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns)
                             (size_t)ns * 121 * hpfw::kCqMaxWaves * 4,
                             0, planar};
     for (int i = 0; i < 7; ++i) {
-        int rc = ensure(&h->ws[i], &h->ws_bytes[i], need[i], h);
+        int rc = ensure(h->ws[i], need[i], h);
         if (rc) return rc;
     }
-    return ensure((void **)&h->d_clipmax, &h->clipmax_cap, (size_t)ns * 4, h);
+    return ensure(h->d_clipmax, (size_t)ns * 4, h);
 }
 
-// the side streams and their events (chirp-z classes side by side, chunks of the forward transform in turn)
+// the side streams and their events (chirp-z classes side by side, chunks of the forward transform in turn).  The last
+// join event is made last: a set left incomplete by a failure is made anew by the next call.
 int ensure_side_streams(hpfw_gpu *h)
 {
-    if (h->cq_fork) return HPFW_OK;
-    bool ok = hipEventCreateWithFlags(&h->cq_fork, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < hpfw_gpu::kCqSide && ok; ++k)
-        ok = hipStreamCreateWithFlags(&h->cq_side[k], hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&h->cq_join[k], hipEventDisableTiming) == hipSuccess;
+    if (h->cq_join[hpfw_gpu::kCqSide - 1]) return HPFW_OK;
+    bool ok = h->cq_fork.create() == hipSuccess;
+    for (int k = 0; k < hpfw_gpu::kCqSide && ok; ++k) ok = h->cq_side[k].create() == hipSuccess && h->cq_join[k].create() == hipSuccess;
     return ok ? HPFW_OK : fail(HPFW_E_HIP, "side streams");
 }
+
+// One stage's work spread over lanes: lane 0 is the caller's stream s, lane k > 0 the side stream cq_side[k - 1].  fork(n)
+// makes lanes 1..n wait for what s holds; the destructor makes s wait for every side lane that lane() handed out, on
+// every exit, so that the next call never reuses the workspaces under work still queued on a side stream.  A failed
+// join is reported to the call (ordered_call) and waited for on the host.
+class Fanout {
+public:
+    Fanout(hpfw_gpu *h, hipStream_t s) : h_(h), s_(s) {}
+    Fanout(const Fanout &) = delete;
+    Fanout &operator=(const Fanout &) = delete;
+    ~Fanout()
+    {
+        for (int k = 0; k < hpfw_gpu::kCqSide; ++k) {
+            if (!(used_ >> k & 1u)) continue;
+            hipStream_t side = h_->cq_side[k].get();
+            hipEvent_t join = h_->cq_join[k].get();
+            if (report(h_, hipEventRecord(join, side), "side stream join") || report(h_, hipStreamWaitEvent(s_, join, 0), "side stream join"))
+                (void)hipStreamSynchronize(side);
+        }
+    }
+    int fork(int n)
+    {
+        int rc = ensure_side_streams(h_);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(h_->cq_fork.get(), s_));
+        for (int k = 0; k < n; ++k) HIP_TRY(hipStreamWaitEvent(h_->cq_side[k].get(), h_->cq_fork.get(), 0));
+        return 0;
+    }
+    hipStream_t lane(int k)
+    {
+        if (k == 0) return s_;
+        used_ |= 1u << (k - 1);
+        return h_->cq_side[k - 1].get();
+    }
+
+private:
+    hpfw_gpu *h_;
+    hipStream_t s_;
+    unsigned used_ = 0;
+};
 
 #if defined(HPFW_ROWS_SNAP) || defined(HPFW_ROWS_STAMPS)
 hpfw::cf *g_rows_snap = nullptr; // diagnosis builds: fft_rows.h HPFW_SNAP / HPFW_STAMP
@@ -848,24 +878,21 @@ hpfw::cf *g_rows_snap = nullptr; // diagnosis builds: fft_rows.h HPFW_SNAP / HPF
 int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf *x, hipStream_t s)
 {
     const hpfw::HostPlan &p = dp->hp;
-    float *yp = (float *)h->ws[0];
+    float *yp = h->ws[0].as<float>();
     int rc;
     if (p.bluestein) { // S15: the clip length has a prime factor above 7
-        float *other = (float *)h->ws[6];
+        float *other = h->ws[6].as<float>();
         if (h->bz_chunk > 0 && nb >= 6 * h->bz_chunk) {
             // in chunks taken in turn by the streams, as below: 24 MB per clip between the three kernels
             const int lanes = h->fwd_streams;
-            if ((rc = ensure_side_streams(h))) return rc;
-            if (lanes > 1) {
-                HIP_TRY(hipEventRecord(h->cq_fork, s));
-                for (int k = 0; k + 1 < lanes; ++k) HIP_TRY(hipStreamWaitEvent(h->cq_side[k], h->cq_fork, 0));
-            }
+            Fanout fan(h, s);
+            if (lanes > 1 && (rc = fan.fork(lanes - 1))) return rc;
             const int64_t region = (int64_t)(hpfw::bz_plane_bytes(dp->bz, h->bz_chunk) / sizeof(float));
             int i = 0;
             for (int c0 = 0; c0 < nb; c0 += h->bz_chunk, ++i) {
                 const int nc = std::min(nb - c0, h->bz_chunk);
                 const int lane = i % lanes;
-                hipStream_t st = lane ? h->cq_side[lane - 1] : s;
+                hipStream_t st = fan.lane(lane);
                 float *ya = yp + lane * region, *yb = other + lane * region;
                 {
                     Timed t(h, K_COLS, st);
@@ -879,10 +906,6 @@ int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf
                     Timed t(h, K_COLS, st);
                     hpfw::launch_bz_cols_last(dp->bz, yb, nc, x + (int64_t)c0 * dp->cq.xclip, st);
                 }
-            }
-            for (int k = 0; k + 1 < lanes; ++k) {
-                HIP_TRY(hipEventRecord(h->cq_join[k], h->cq_side[k]));
-                HIP_TRY(hipStreamWaitEvent(s, h->cq_join[k], 0));
             }
             return check_launch("bz_chunks");
         }
@@ -907,19 +930,16 @@ int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf
     cols.variant = h->cols_variant;
     if (h->fwd_chunk > 0 && nb >= 6 * h->fwd_chunk) {
         const int lanes = h->fwd_streams;
-        if ((rc = ensure_side_streams(h))) return rc;
-        if (lanes > 1) {
-            HIP_TRY(hipEventRecord(h->cq_fork, s));
-            for (int k = 0; k + 1 < lanes; ++k) HIP_TRY(hipStreamWaitEvent(h->cq_side[k], h->cq_fork, 0));
-        }
+        Fanout fan(h, s);
+        if (lanes > 1 && (rc = fan.fork(lanes - 1))) return rc;
         // a stream's chunks follow each other in order, so every stream has one region of z of its own
         const int64_t region = (int64_t)h->fwd_chunk * dp->rows_out.zclip;
         int i = 0;
         for (int c0 = 0; c0 < nb; c0 += h->fwd_chunk, ++i) {
             const int nc = std::min(nb - c0, h->fwd_chunk);
             const int lane = i % lanes;
-            hipStream_t st = lane ? h->cq_side[lane - 1] : s;
-            float *zr = (float *)h->ws[0] + lane * region;
+            hipStream_t st = fan.lane(lane);
+            float *zr = yp + lane * region;
             {
                 Timed t(h, K_COLS, st);
                 hpfw::launch_fwd_cols_q(cols, d_pcm + (int64_t)c0 * p.n, p.n, nc, zr, st);
@@ -929,15 +949,11 @@ int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf
                 hpfw::launch_fwd_rows2(dp->rows, dp->rows_out, zr, nc, x + (int64_t)c0 * dp->rows_out.n1 * dp->rows_out.q2w, st);
             }
         }
-        for (int k = 0; k + 1 < lanes; ++k) {
-            HIP_TRY(hipEventRecord(h->cq_join[k], h->cq_side[k]));
-            HIP_TRY(hipStreamWaitEvent(s, h->cq_join[k], 0));
-        }
         return check_launch("fwd_chunks");
     }
     {
         Timed t(h, K_COLS, s);
-        hpfw::launch_fwd_cols_q(cols, d_pcm, p.n, nb, (float *)h->ws[0], s); // pcm as it lies -> z [hq][Re, Im][n2]
+        hpfw::launch_fwd_cols_q(cols, d_pcm, p.n, nb, yp, s); // pcm as it lies -> z [hq][Re, Im][n2]
     }
     if ((rc = check_launch("fwd_cols"))) return rc;
     {
@@ -948,7 +964,7 @@ int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf
 #if defined(HPFW_ROWS_STAMPS)
         dp->rows.stamps = reinterpret_cast<long long *>(g_rows_snap);
 #endif
-        hpfw::launch_fwd_rows2(dp->rows, dp->rows_out, (const float *)h->ws[0], nb, x, s); // -> x [n1][q2w]
+        hpfw::launch_fwd_rows2(dp->rows, dp->rows_out, yp, nb, x, s); // -> x [n1][q2w]
     }
     return check_launch("fwd_rows");
 }
@@ -960,9 +976,10 @@ int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, 
 {
     using hpfw::cf;
     const hpfw::HostPlan &p = dp->hp;
-    cf *x = (cf *)h->ws[1];
-    float *mag = (float *)h->ws[2] + (size_t)slot * 121 * p.c;
-    float *mm = (float *)h->ws[4] + (size_t)slot * 121 * hpfw::kCqMaxWaves; // this pass's wave maxima
+    cf *x = h->ws[1].as<cf>();
+    float *mag = h->ws[2].as<float>() + (size_t)slot * 121 * p.c;
+    float *mm = h->ws[4].as<float>() + (size_t)slot * 121 * hpfw::kCqMaxWaves; // this pass's wave maxima
+    float *clipmax = h->d_clipmax.as<float>() + slot;
     int rc;
     if ((rc = run_forward(h, dp, d_pcm, nb, x, s))) return rc;
     {
@@ -974,34 +991,24 @@ int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, 
         for (const hpfw::CqClassDev &cd : dp->cls) n_lds += cd.outer ? 0 : 1;
         // (a handful of clips: the five launches are tens of microseconds each, and forking costs the host a dozen calls)
         const bool fork = h->cq_concurrent && n_lds > 1 && nb >= 4;
-        if (fork && (rc = ensure_side_streams(h))) return rc;
-        if (fork) {
-            HIP_TRY(hipEventRecord(h->cq_fork, s));
-            for (int k = 0; k < hpfw_gpu::kCqSide; ++k) HIP_TRY(hipStreamWaitEvent(h->cq_side[k], h->cq_fork, 0));
-        }
-        unsigned used = 0;
+        Fanout fan(h, s);
+        if (fork && (rc = fan.fork(hpfw_gpu::kCqSide))) return rc;
         int turn = 0;
         for (size_t ci = dp->cls.size(); ci-- > 0;) {
             const hpfw::CqClassDev &cd = dp->cls[ci];
             if (cd.outer) {
-                hpfw::launch_cq_big_class(dp->cq, cd, x, nb, (cf *)h->d_cqwork, mag, mm, true, s);
+                hpfw::launch_cq_big_class(dp->cq, cd, x, nb, h->d_cqwork.as<cf>(), mag, mm, true, s);
                 continue;
             }
             const int lane = fork ? turn++ % (hpfw_gpu::kCqSide + 1) : 0; // 0: the caller's stream
-            if (lane) used |= 1u << (lane - 1);
-            hpfw::launch_cq_class(dp->cq, cd, x, nb, mag, mm, true, lane ? h->cq_side[lane - 1] : s);
+            hpfw::launch_cq_class(dp->cq, cd, x, nb, mag, mm, true, fan.lane(lane));
         }
-        for (int k = 0; k < hpfw_gpu::kCqSide; ++k)
-            if (used >> k & 1u) {
-                HIP_TRY(hipEventRecord(h->cq_join[k], h->cq_side[k]));
-                HIP_TRY(hipStreamWaitEvent(s, h->cq_join[k], 0));
-            }
+        if ((rc = check_launch("cq_chirpz"))) return rc;
     }
-    if ((rc = check_launch("cq_chirpz"))) return rc;
     {
         Timed t(h, K_DB, s);
-        hpfw::launch_clipmax(mm, h->d_clipmax + slot, nb, s);
-        if (finish_db) hpfw::launch_db_finish(mag, h->d_clipmax + slot, nb, (int64_t)121 * p.c, s);
+        hpfw::launch_clipmax(mm, clipmax, nb, s);
+        if (finish_db) hpfw::launch_db_finish(mag, clipmax, nb, (int64_t)121 * p.c, s);
     }
     return check_launch("db");
 }
@@ -1010,19 +1017,19 @@ int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, 
 int run_back(hpfw_gpu *h, DevPlan *dp, int ns, uint64_t *d_hp, hipStream_t s)
 {
     const hpfw::HostPlan &p = dp->hp;
-    float *sdb = (float *)h->ws[2];
-    float *proj = (float *)h->ws[3];
+    const float *sdb = h->ws[2].as<float>();
     int rc;
     if (h->projection) { // S9q: reference level, clip, exact integer sums on the int8 matrix pipe, sign and pack in ONE kernel
         {
             Timed t(h, K_PROJECT, s);
-            hpfw::launch_hashprints_q(h->d_fq_image, sdb, h->d_clipmax, ns, p.c, d_hp, nullptr, s);
+            hpfw::launch_hashprints_q(h->d_fq_image.get(), sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s);
         }
         return check_launch("project");
     }
+    float *proj = h->ws[3].as<float>();
     {
         Timed t(h, K_PROJECT, s);
-        hpfw::launch_project(h->d_fpack, sdb, h->d_clipmax, ns, p.c, proj, s);
+        hpfw::launch_project(h->d_fpack.as<float>(), sdb, h->d_clipmax.as<float>(), ns, p.c, proj, s);
     }
     if ((rc = check_launch("project"))) return rc;
     {
@@ -1056,25 +1063,20 @@ int hpfw_gpu_create(int device, hpfw_gpu **out)
     HIP_TRY(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) return fail(HPFW_E_INVALID, "no such device");
     HIP_TRY(hipSetDevice(device));
-    auto *h = new hpfw_gpu();
+    auto h = std::make_unique<hpfw_gpu>();
     h->device = device;
     if (std::getenv("HPFW_CQ_SERIAL")) h->cq_concurrent = 0;
     if (const char *e = std::getenv("HPFW_FWD_CHUNK")) h->fwd_chunk = std::max(0, atoi(e));
     if (const char *e = std::getenv("HPFW_BZ_CHUNK")) h->bz_chunk = std::max(0, atoi(e));
     if (const char *e = std::getenv("HPFW_COLS_VARIANT")) h->cols_variant = atoi(e);
     if (std::getenv("HPFW_PLAN_TIMING")) h->plan_timing = std::make_unique<PlanTiming>();
-    if (const char *e = std::getenv("HPFW_BACK_OVERLAP")) h->back_overlap = atoi(e);
     if (const char *e = std::getenv("HPFW_FWD_STREAMS")) h->fwd_streams = std::min(hpfw_gpu::kCqSide + 1, std::max(1, atoi(e)));
     if (const char *e = std::getenv("HPFW_PROJECTION")) // "f32": handles start with the f32 fma chain (hpfw_gpu_set_projection(h, 0))
         h->projection = std::strcmp(e, "f32") == 0 ? 0 : 1;
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-        hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->plan_ev, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->plan_stream, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
+    if (h->ev0.create(hipEventDefault) != hipSuccess || h->ev1.create(hipEventDefault) != hipSuccess || h->order_ev.create() != hipSuccess ||
+        h->plan_ev.create() != hipSuccess || h->plan_stream.create() != hipSuccess)
         return fail(HPFW_E_HIP, "hipEventCreate failed");
-    }
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
@@ -1094,67 +1096,6 @@ void hpfw_gpu_destroy(hpfw_gpu *h)
                      t.upload * 1e3 / t.plans, t.copies, t.copied / 1e6 / t.plans, t.device_tables * 1e3 / t.plans, t.alloc * 1e3 / t.plans,
                      t.evict * 1e3 / t.plans);
     }
-    h->plans.clear();
-    h->plan_bytes = 0;
-    for (auto &kv : h->dev_pool) (void)hipFree(kv.second);
-    h->dev_pool.clear();
-    for (void *p : h->ws)
-        if (p) (void)hipFree(p);
-    if (h->d_fpack) (void)hipFree(h->d_fpack);
-    if (h->d_fq_image) (void)hipFree(h->d_fq_image);
-    if (h->d_cov) (void)hipFree(h->d_cov);
-    if (h->d_cov_ws) (void)hipFree(h->d_cov_ws);
-    if (h->d_cqwork) (void)hipFree(h->d_cqwork);
-    if (h->d_topk_scratch) (void)hipFree(h->d_topk_scratch);
-    for (void *q : h->mel_owned) (void)hipFree(q);
-    if (h->d_mel_work) (void)hipFree(h->d_mel_work);
-    if (h->d_mel_small) (void)hipFree(h->d_mel_small);
-    if (h->d_qa) (void)hipFree(h->d_qa);
-    if (h->d_gk) (void)hipFree(h->d_gk);
-    if (h->d_clipmax) (void)hipFree(h->d_clipmax);
-    for (int b = 0; b < 2; ++b) {
-        if (h->stage_pcm[b]) (void)hipFree(h->stage_pcm[b]);
-        if (h->stage_copied[b]) (void)hipEventDestroy(h->stage_copied[b]);
-        if (h->stage_consumed[b]) (void)hipEventDestroy(h->stage_consumed[b]);
-    }
-    if (h->stage_hp) (void)hipFree(h->stage_hp);
-    for (int k = 0; k < hpfw_gpu::kCqSide; ++k) {
-        if (h->cq_side[k]) (void)hipStreamDestroy(h->cq_side[k]);
-        if (h->cq_join[k]) (void)hipEventDestroy(h->cq_join[k]);
-    }
-    if (h->cq_fork) (void)hipEventDestroy(h->cq_fork);
-    if (h->back_side) (void)hipStreamDestroy(h->back_side);
-    if (h->back_fork) (void)hipEventDestroy(h->back_fork);
-    if (h->back_join) (void)hipEventDestroy(h->back_join);
-    if (h->stage_copy) (void)hipStreamDestroy(h->stage_copy);
-    if (h->stage_comp) (void)hipStreamDestroy(h->stage_comp);
-    if (h->d_cov_tiles) (void)hipFree(h->d_cov_tiles);
-    for (auto &kv : h->cfg_fpack) (void)hipFree(kv.second);
-    if (h->d_cfg_proj) (void)hipFree(h->d_cfg_proj);
-    for (auto &kv : h->cfg_cov) {
-        if (kv.second.d_accum) (void)hipFree(kv.second.d_accum);
-        if (kv.second.d_tiles) (void)hipFree(kv.second.d_tiles);
-    }
-    if (h->d_cfg_cov_ws) (void)hipFree(h->d_cfg_cov_ws);
-    if (h->d_db) (void)hipFree(h->d_db);
-    if (h->d_db_off) (void)hipFree(h->d_db_off);
-    if (h->d_best) (void)hipFree(h->d_best);
-    if (h->d_q_off) (void)hipFree(h->d_q_off);
-    for (auto &t : h->timed) {
-        (void)hipEventDestroy(t.a);
-        (void)hipEventDestroy(t.b);
-    }
-    for (auto &e : h->ev_pool) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    if (h->plan_ev) (void)hipEventDestroy(h->plan_ev);
-    if (h->plan_stream) (void)hipStreamDestroy(h->plan_stream);
-    if (h->pin_ring) (void)hipHostFree(h->pin_ring);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
-    h->combiner.reset();
     delete h;
 }
 
@@ -1164,12 +1105,12 @@ int hpfw_gpu_set_filters(hpfw_gpu *h, const float *f)
     HIP_TRY(hipSetDevice(h->device));
     std::vector<float> packed((size_t)hpfw::kFilters * hpfw::kFrame);
     hpfw::pack_filters_for_mfma(f, packed.data());
-    if (!h->d_fpack) HIP_TRY(hipMalloc((void **)&h->d_fpack, packed.size() * 4));
-    HIP_TRY(hipMemcpy(h->d_fpack, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    if (!h->d_fpack) HIP_TRY(h->d_fpack.alloc(packed.size() * 4));
+    HIP_TRY(hipMemcpy(h->d_fpack.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     std::vector<int8_t> image;
     hpfw::pack_filters_q(f, image);
-    if (!h->d_fq_image) HIP_TRY(hipMalloc(&h->d_fq_image, image.size()));
-    HIP_TRY(hipMemcpy(h->d_fq_image, image.data(), image.size(), hipMemcpyHostToDevice));
+    if (!h->d_fq_image) HIP_TRY(h->d_fq_image.alloc(image.size()));
+    HIP_TRY(hipMemcpy(h->d_fq_image.get(), image.data(), image.size(), hipMemcpyHostToDevice));
     h->has_filters = true;
     return 0;
 }
@@ -1192,21 +1133,22 @@ int hpfw_gpu_hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips,
     if (nhp <= 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    int rc;
-    const int nbmax = 256;
-    if (!h->projection && (rc = ensure(&h->ws[3], &h->ws_bytes[3], (size_t)nbmax * 64 * (size_t)nf * 4))) return rc;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        if (h->projection) {
-            hpfw::launch_hashprints_q(h->d_fq_image, d_db + c0 * 121 * c, nullptr, nb, (int)c, d_hp + c0 * nhp, nullptr, s);
-        } else {
-            hpfw::launch_project(h->d_fpack, d_db + c0 * 121 * c, nullptr, nb, (int)c, (float *)h->ws[3], s);
-            hpfw::launch_pack((const float *)h->ws[3], nb, (int)nf, d_hp + c0 * nhp, s);
+    return ordered_call(h, s, [&] {
+        int rc;
+        const int nbmax = 256;
+        if (!h->projection && (rc = ensure(h->ws[3], (size_t)nbmax * 64 * (size_t)nf * 4))) return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            if (h->projection) {
+                hpfw::launch_hashprints_q(h->d_fq_image.get(), d_db + c0 * 121 * c, nullptr, nb, (int)c, d_hp + c0 * nhp, nullptr, s);
+            } else {
+                hpfw::launch_project(h->d_fpack.as<float>(), d_db + c0 * 121 * c, nullptr, nb, (int)c, h->ws[3].as<float>(), s);
+                hpfw::launch_pack(h->ws[3].as<float>(), nb, (int)nf, d_hp + c0 * nhp, s);
+            }
+            if ((rc = check_launch("project"))) return rc;
         }
-        if ((rc = check_launch("project"))) return rc;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp, void *stream)
@@ -1218,15 +1160,15 @@ int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int6
     if (n_clips > 65535) return fail(HPFW_E_INVALID, "at most 65535 clips per call");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    int rc;
-    uint64_t *hp = d_hp;
-    if (!hp) { // the kernel always writes its hashprints
-        if ((rc = ensure(&h->ws[3], &h->ws_bytes[3], (size_t)n_clips * (size_t)nhp * 8))) return rc;
-        hp = (uint64_t *)h->ws[3];
-    }
-    hpfw::launch_hashprints_q(h->d_fq_image, d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s);
-    return check_launch("project");
+    return ordered_call(h, s, [&] {
+        uint64_t *hp = d_hp;
+        if (!hp) { // the kernel always writes its hashprints
+            if (int rc = ensure(h->ws[3], (size_t)n_clips * (size_t)nhp * 8)) return rc;
+            hp = h->ws[3].as<uint64_t>();
+        }
+        hpfw::launch_hashprints_q(h->d_fq_image.get(), d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s);
+        return check_launch("project");
+    });
 }
 
 int hpfw_gpu_geometry(hpfw_gpu *h, int64_t n_samples, hpfw_geometry *out)
@@ -1299,43 +1241,20 @@ int hpfw_gpu_extract_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples,
     if (rc) return rc;
     if (dp->hp.n_hp <= 0) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint");
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int nbmax = pass_clips(h, dp, n_clips);
-    const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
-    if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
-    // several passes and the fixed-point back end: the hashprints of pass i are computed on a stream of their own while the
-    // front end of pass i + 1 runs on the caller's (different pipes: matrix against vector ALU and LDS)
-    const bool overlap = h->back_overlap && h->projection && n_clips > nbmax;
-    if (overlap && !h->back_side) {
-        if (hipStreamCreateWithFlags(&h->back_side, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->back_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->back_join, hipEventDisableTiming) != hipSuccess)
-            return fail(HPFW_E_HIP, "back-end stream");
-    }
-    for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
-        const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
-        for (int c0 = 0; c0 < ns; c0 += nbmax) {
-            const int nb = std::min(nbmax, ns - c0);
-            rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s);
-            if (rc) return rc;
-            if (overlap) {
-                HIP_TRY(hipEventRecord(h->back_fork, s));
-                HIP_TRY(hipStreamWaitEvent(h->back_side, h->back_fork, 0));
-                Timed t(h, K_PROJECT, h->back_side);
-                hpfw::launch_hashprints_q(h->d_fq_image, (const float *)h->ws[2] + (size_t)c0 * 121 * dp->hp.c, h->d_clipmax + c0, nb, dp->hp.c,
-                                          d_hp + (s0 + c0) * dp->hp.n_hp, nullptr, h->back_side);
-                if ((rc = check_launch("project"))) return rc;
+    return ordered_call(h, s, [&] {
+        const int nbmax = pass_clips(h, dp, n_clips);
+        const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
+        if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
+        for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
+            const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
+            for (int c0 = 0; c0 < ns; c0 += nbmax) {
+                const int nb = std::min(nbmax, ns - c0);
+                if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
             }
+            if ((rc = run_back(h, dp, ns, d_hp + s0 * dp->hp.n_hp, s))) return rc;
         }
-        if (overlap) { // the caller's stream (and the next batch's passes, which write the same slots) behind the last back end
-            HIP_TRY(hipEventRecord(h->back_join, h->back_side));
-            HIP_TRY(hipStreamWaitEvent(s, h->back_join, 0));
-        } else {
-            rc = run_back(h, dp, ns, d_hp + s0 * dp->hp.n_hp, s);
-            if (rc) return rc;
-        }
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
@@ -1351,35 +1270,35 @@ int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_sampl
     // i + 1 runs under the kernels of chunk i (from pinned host memory; a pageable source is staged
     // by the runtime and overlaps only partly)
     const int64_t chunk = std::min<int64_t>(n_clips, std::max<int64_t>(1, (192ll << 20) / (n_samples * 2)));
-    if ((rc = ensure(&h->stage_hp, &h->stage_hp_cap, (size_t)n_clips * std::max<int64_t>(g.n_hp, 1) * 8))) return rc;
+    if ((rc = ensure(h->stage_hp, (size_t)n_clips * std::max<int64_t>(g.n_hp, 1) * 8))) return rc;
     for (int b = 0; b < 2; ++b) {
         if (b == 1 && chunk >= n_clips) break; // one chunk: one buffer
-        if ((rc = ensure(&h->stage_pcm[b], &h->stage_pcm_cap[b], (size_t)chunk * n_samples * 2))) return rc;
+        if ((rc = ensure(h->stage_pcm[b], (size_t)chunk * n_samples * 2))) return rc;
     }
-    if (!h->stage_copy) {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stage_copy, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&h->stage_comp, hipStreamNonBlocking));
+    if (!h->stage_consumed[1]) { // (made last: a set left incomplete by a failure is made anew by the next call)
+        HIP_TRY(h->stage_copy.create());
+        HIP_TRY(h->stage_comp.create());
         for (int b = 0; b < 2; ++b) {
-            HIP_TRY(hipEventCreateWithFlags(&h->stage_copied[b], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&h->stage_consumed[b], hipEventDisableTiming));
+            HIP_TRY(h->stage_copied[b].create());
+            HIP_TRY(h->stage_consumed[b].create());
         }
     }
-    hipStream_t s_copy = h->stage_copy, s_comp = h->stage_comp;
-    uint64_t *d_hp = (uint64_t *)h->stage_hp;
+    hipStream_t s_copy = h->stage_copy.get(), s_comp = h->stage_comp.get();
+    uint64_t *d_hp = h->stage_hp.as<uint64_t>();
     int64_t ci = 0;
     for (int64_t c0 = 0; !rc && c0 < n_clips; c0 += chunk, ++ci) {
         const int b = (int)(ci & 1);
         const int64_t cnt = std::min(chunk, n_clips - c0);
-        int16_t *d_pcm = (int16_t *)h->stage_pcm[b];
-        if (ci >= 2 && hipStreamWaitEvent(s_copy, h->stage_consumed[b], 0) != hipSuccess) rc = fail(HPFW_E_HIP, "event wait failed");
+        int16_t *d_pcm = h->stage_pcm[b].as<int16_t>();
+        hipEvent_t copied = h->stage_copied[b].get(), consumed = h->stage_consumed[b].get();
+        if (ci >= 2 && hipStreamWaitEvent(s_copy, consumed, 0) != hipSuccess) rc = fail(HPFW_E_HIP, "event wait failed");
         if (!rc && hipMemcpyAsync(d_pcm, pcm + c0 * n_samples, (size_t)cnt * n_samples * 2, hipMemcpyHostToDevice, s_copy) !=
                        hipSuccess)
             rc = fail(HPFW_E_HIP, "H2D copy failed");
-        if (!rc && (hipEventRecord(h->stage_copied[b], s_copy) != hipSuccess ||
-                    hipStreamWaitEvent(s_comp, h->stage_copied[b], 0) != hipSuccess))
+        if (!rc && (hipEventRecord(copied, s_copy) != hipSuccess || hipStreamWaitEvent(s_comp, copied, 0) != hipSuccess))
             rc = fail(HPFW_E_HIP, "event record failed");
         if (!rc) rc = hpfw_gpu_extract_pcm16(h, d_pcm, n_samples, cnt, d_hp + c0 * g.n_hp, s_comp);
-        if (!rc && hipEventRecord(h->stage_consumed[b], s_comp) != hipSuccess) rc = fail(HPFW_E_HIP, "event record failed");
+        if (!rc && hipEventRecord(consumed, s_comp) != hipSuccess) rc = fail(HPFW_E_HIP, "event record failed");
     }
     if (hipStreamSynchronize(s_copy) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "H2D copy failed");
     if (!rc && hipMemcpyAsync(hp, d_hp, (size_t)n_clips * g.n_hp * 8, hipMemcpyDeviceToHost, s_comp) != hipSuccess)
@@ -1427,8 +1346,8 @@ int hpfw_gpu_debug_set_rows_snap(void *d_snap)
 int hpfw_gpu_debug_workspace(hpfw_gpu *h, int which, void **d_ptr, size_t *bytes)
 {
     if (!h || which < 0 || which >= 7 || !d_ptr || !bytes) return fail(HPFW_E_INVALID, "bad argument");
-    *d_ptr = h->ws[which];
-    *bytes = h->ws_bytes[which];
+    *d_ptr = h->ws[which].get();
+    *bytes = h->ws[which].capacity();
     return 0;
 }
 
@@ -1440,7 +1359,7 @@ int hpfw_gpu_chirpz_table(hpfw_gpu *h, int64_t n_samples, int which, float *out,
     DevPlan *dp;
     int rc = get_plan(h, n_samples, &dp);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->plan_stream)); // the tables are generated on the handle's table stream
+    HIP_TRY(hipStreamSynchronize(h->plan_stream.get())); // the tables are generated on the handle's table stream
     if (which == 4) { // the constant-Q stage's windows (every length): bands concatenated
         *count = 2 * dp->hp.g_total;
         if (!out) return 0;
@@ -1479,17 +1398,18 @@ int hpfw_gpu_stage_spectrum(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples
     int rc = get_plan(h, n_samples, &dp);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int nbmax = pass_clips(h, dp, n_clips);
-    if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
-    const int64_t nk = dp->hp.kmax - dp->hp.kmin;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        if ((rc = run_forward(h, dp, d_pcm + c0 * n_samples, nb, (hpfw::cf *)h->ws[1], s))) return rc;
-        hpfw::launch_gather_bins(dp->cq, (const hpfw::cf *)h->ws[1], nb, (hpfw::cf *)d_x + c0 * nk, s); // natural order [kmin, kmax)
-        if ((rc = check_launch("gather_bins"))) return rc;
-    }
-    return 0;
+    return ordered_call(h, s, [&] {
+        const int nbmax = pass_clips(h, dp, n_clips);
+        if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
+        const int64_t nk = dp->hp.kmax - dp->hp.kmin;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            if ((rc = run_forward(h, dp, d_pcm + c0 * n_samples, nb, h->ws[1].as<hpfw::cf>(), s))) return rc;
+            hpfw::launch_gather_bins(dp->cq, h->ws[1].as<hpfw::cf>(), nb, (hpfw::cf *)d_x + c0 * nk, s); // natural order [kmin, kmax)
+            if ((rc = check_launch("gather_bins"))) return rc;
+        }
+        return 0;
+    });
 }
 
 int hpfw_gpu_stage_cqmag(hpfw_gpu *h, const float *d_x, int64_t n_samples, int64_t n_clips, float *d_mag,
@@ -1501,28 +1421,29 @@ int hpfw_gpu_stage_cqmag(hpfw_gpu *h, const float *d_x, int64_t n_samples, int64
     int rc = get_plan(h, n_samples, &dp);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int nbmax = pass_clips(h, dp, n_clips);
-    if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
-    const int64_t nk = dp->hp.kmax - dp->hp.kmin;
-    hpfw::CqPlanDev cq = dp->cq; // the caller's bins lie in natural order
-    cq.xn1 = 1;
-    cq.xw = 0;
-    cq.xq0 = dp->hp.kmin;
-    cq.xclip = nk;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        for (const hpfw::CqClassDev &cd : dp->cls) {
-            if (cd.outer)
-                hpfw::launch_cq_big_class(cq, cd, (const hpfw::cf *)d_x + c0 * nk, nb, (hpfw::cf *)h->d_cqwork,
-                                          d_mag + c0 * 121 * dp->hp.c, (float *)h->ws[4], false, s);
-            else
-                hpfw::launch_cq_class(cq, cd, (const hpfw::cf *)d_x + c0 * nk, nb,
-                                      d_mag + c0 * 121 * dp->hp.c, (float *)h->ws[4], false, s);
+    return ordered_call(h, s, [&] {
+        const int nbmax = pass_clips(h, dp, n_clips);
+        if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
+        const int64_t nk = dp->hp.kmax - dp->hp.kmin;
+        hpfw::CqPlanDev cq = dp->cq; // the caller's bins lie in natural order
+        cq.xn1 = 1;
+        cq.xw = 0;
+        cq.xq0 = dp->hp.kmin;
+        cq.xclip = nk;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            for (const hpfw::CqClassDev &cd : dp->cls) {
+                if (cd.outer)
+                    hpfw::launch_cq_big_class(cq, cd, (const hpfw::cf *)d_x + c0 * nk, nb, h->d_cqwork.as<hpfw::cf>(),
+                                              d_mag + c0 * 121 * dp->hp.c, h->ws[4].as<float>(), false, s);
+                else
+                    hpfw::launch_cq_class(cq, cd, (const hpfw::cf *)d_x + c0 * nk, nb,
+                                          d_mag + c0 * 121 * dp->hp.c, h->ws[4].as<float>(), false, s);
+            }
+            if ((rc = check_launch("cq_chirpz"))) return rc;
         }
-        if ((rc = check_launch("cq_chirpz"))) return rc;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int hpfw_gpu_stage_db(hpfw_gpu *h, const float *d_mag, int64_t n_clips, int64_t c, float *d_db, void *stream)
@@ -1530,19 +1451,20 @@ int hpfw_gpu_stage_db(hpfw_gpu *h, const float *d_mag, int64_t n_clips, int64_t 
     if (!h || !d_mag || !d_db || c <= 0) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    int rc;
-    const int64_t per = 121 * c;
-    const int nbmax = 1024;
-    if ((rc = ensure(&h->ws[4], &h->ws_bytes[4], (size_t)nbmax * 121 * hpfw::kCqMaxWaves * 4))) return rc;
-    if ((rc = ensure((void **)&h->d_clipmax, &h->clipmax_cap, (size_t)nbmax * 4))) return rc;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        hpfw::launch_magmax(d_mag + c0 * per, nb, (int)c, (float *)h->ws[4], s);
-        hpfw::launch_db(d_mag + c0 * per, (const float *)h->ws[4], h->d_clipmax, nb, per, d_db + c0 * per, s);
-        if ((rc = check_launch("db"))) return rc;
-    }
-    return 0;
+    return ordered_call(h, s, [&] {
+        int rc;
+        const int64_t per = 121 * c;
+        const int nbmax = 1024;
+        if ((rc = ensure(h->ws[4], (size_t)nbmax * 121 * hpfw::kCqMaxWaves * 4))) return rc;
+        if ((rc = ensure(h->d_clipmax, (size_t)nbmax * 4))) return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            hpfw::launch_magmax(d_mag + c0 * per, nb, (int)c, h->ws[4].as<float>(), s);
+            hpfw::launch_db(d_mag + c0 * per, h->ws[4].as<float>(), h->d_clipmax.as<float>(), nb, per, d_db + c0 * per, s);
+            if ((rc = check_launch("db"))) return rc;
+        }
+        return 0;
+    });
 }
 
 int hpfw_gpu_stage_project(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, float *d_proj,
@@ -1552,14 +1474,15 @@ int hpfw_gpu_stage_project(hpfw_gpu *h, const float *d_db, int64_t n_clips, int6
     if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters loaded: call hpfw_gpu_set_filters first");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int64_t nf = c - (hpfw::kCtx - 1);
-    for (int64_t c0 = 0; c0 < n_clips; c0 += 16384) {
-        const int nb = (int)std::min<int64_t>(16384, n_clips - c0);
-        Timed t(h, K_PROJECT, s);
-        hpfw::launch_project(h->d_fpack, d_db + c0 * 121 * c, nullptr, nb, (int)c, d_proj + c0 * 64 * nf, s);
-    }
-    return check_launch("project");
+    return ordered_call(h, s, [&] {
+        const int64_t nf = c - (hpfw::kCtx - 1);
+        for (int64_t c0 = 0; c0 < n_clips; c0 += 16384) {
+            const int nb = (int)std::min<int64_t>(16384, n_clips - c0);
+            Timed t(h, K_PROJECT, s);
+            hpfw::launch_project(h->d_fpack.as<float>(), d_db + c0 * 121 * c, nullptr, nb, (int)c, d_proj + c0 * 64 * nf, s);
+        }
+        return check_launch("project");
+    });
 }
 
 int hpfw_gpu_stage_pack(hpfw_gpu *h, const float *d_proj, int64_t n_clips, int64_t n_frames, uint64_t *d_hp,
@@ -1568,12 +1491,13 @@ int hpfw_gpu_stage_pack(hpfw_gpu *h, const float *d_proj, int64_t n_clips, int64
     if (!h || !d_proj || !d_hp || n_frames <= hpfw::kLag) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    for (int64_t c0 = 0; c0 < n_clips; c0 += 16384) {
-        const int nb = (int)std::min<int64_t>(16384, n_clips - c0);
-        hpfw::launch_pack(d_proj + c0 * 64 * n_frames, nb, (int)n_frames, d_hp + c0 * (n_frames - hpfw::kLag), s);
-    }
-    return check_launch("delta_pack");
+    return ordered_call(h, s, [&] {
+        for (int64_t c0 = 0; c0 < n_clips; c0 += 16384) {
+            const int nb = (int)std::min<int64_t>(16384, n_clips - c0);
+            hpfw::launch_pack(d_proj + c0 * 64 * n_frames, nb, (int)n_frames, d_hp + c0 * (n_frames - hpfw::kLag), s);
+        }
+        return check_launch("delta_pack");
+    });
 }
 
 // Hashprints of one cached dB spectrogram (collect_fingerprints over cache.get_spectros(),
@@ -1593,17 +1517,12 @@ int hpfw_gpu_extract_db_host(hpfw_gpu *h, const float *s_colmajor, int32_t rows,
     std::vector<float> binmajor((size_t)rows * cols);
     for (int32_t c = 0; c < cols; ++c)
         for (int32_t b = 0; b < rows; ++b) binmajor[(size_t)b * cols + c] = s_colmajor[(size_t)c * rows + b];
-    float *d_s = nullptr;
-    uint64_t *d_h = nullptr;
-    int rc = 0;
-    if (hipMalloc((void **)&d_s, binmajor.size() * 4) != hipSuccess || hipMalloc((void **)&d_h, (size_t)nh * 8) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "out of device memory");
-    if (!rc && hipMemcpy(d_s, binmajor.data(), binmajor.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) rc = hpfw_gpu_hashprints_from_db(h, d_s, 1, cols, d_h, nullptr);
-    if (!rc && hipMemcpy(hp, d_h, (size_t)nh * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HPFW_E_HIP, "D2H copy failed");
-    if (d_s) (void)hipFree(d_s);
-    if (d_h) (void)hipFree(d_h);
+    DevBuf d_s, d_h;
+    if (d_s.alloc(binmajor.size() * 4) != hipSuccess || d_h.alloc((size_t)nh * 8) != hipSuccess) return fail(HPFW_E_HIP, "out of device memory");
+    if (hipMemcpy(d_s.get(), binmajor.data(), binmajor.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_hashprints_from_db(h, d_s.as<float>(), 1, cols, d_h.as<uint64_t>(), nullptr);
+    if (!rc && hipMemcpy(hp, d_h.get(), (size_t)nh * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HPFW_E_HIP, "D2H copy failed");
     return rc;
 }
 
@@ -1613,6 +1532,7 @@ int64_t hpfw_gpu_mel_frames(int64_t n_samples) { return hpfw::mel_frames(n_sampl
 static int mel_prepare(hpfw_gpu *h)
 {
     if (h->mel_ready) return 0;
+    h->mel_owned.clear(); // (what an attempt that failed part-way uploaded)
     std::string why;
     if (!hpfw::build_frame_transform(hpfw::kMelFrame, h->mel_plan, why)) return fail(HPFW_E_UNSUPPORTED, why.c_str());
     const hpfw::HostPlan &p = h->mel_plan;
@@ -1650,23 +1570,24 @@ int hpfw_gpu_mel_spectrogram_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_
     int rc = mel_prepare(h);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int nf = hpfw::mel_frames(n_samples), n_blk = (int)((n_samples + hpfw::kMelHop - 1) / hpfw::kMelHop);
-    // clips per pass: the split spectra take 2 * 2208 floats per frame
-    const int64_t per_clip = (int64_t)hpfw::mel_work_bytes(n_samples, 1);
-    const int nbmax = (int)std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(n_clips, 1), ((int64_t)8 << 30) / per_clip));
-    if ((rc = ensure(&h->d_mel_work, &h->mel_work_cap, hpfw::mel_work_bytes(n_samples, nbmax)))) return rc;
-    if ((rc = ensure(&h->d_mel_small, &h->mel_small_cap, (size_t)nbmax * ((size_t)n_blk * 8 + (size_t)nf * 4 + 8)))) return rc;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        int64_t *blk = (int64_t *)h->d_mel_small;
-        int *pos = (int *)(blk + (size_t)nbmax * n_blk);
-        float *pmax = (float *)(pos + (size_t)nbmax * nf);
-        hpfw::launch_mel(h->mel_rows, h->d_mel_win, h->d_mel_cpack, d_pcm + c0 * n_samples, n_samples, nb, blk, pos,
-                         d_cols + c0, pmax, (float *)h->d_mel_work, d_out + c0 * hpfw::kMelBands * nf, s);
-        if ((rc = check_launch("mel"))) return rc;
-    }
-    return 0;
+    return ordered_call(h, s, [&] {
+        const int nf = hpfw::mel_frames(n_samples), n_blk = (int)((n_samples + hpfw::kMelHop - 1) / hpfw::kMelHop);
+        // clips per pass: the split spectra take 2 * 2208 floats per frame
+        const int64_t per_clip = (int64_t)hpfw::mel_work_bytes(n_samples, 1);
+        const int nbmax = (int)std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(n_clips, 1), ((int64_t)8 << 30) / per_clip));
+        if ((rc = ensure(h->d_mel_work, hpfw::mel_work_bytes(n_samples, nbmax)))) return rc;
+        if ((rc = ensure(h->d_mel_small, (size_t)nbmax * ((size_t)n_blk * 8 + (size_t)nf * 4 + 8)))) return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            int64_t *blk = h->d_mel_small.as<int64_t>();
+            int *pos = (int *)(blk + (size_t)nbmax * n_blk);
+            float *pmax = (float *)(pos + (size_t)nbmax * nf);
+            hpfw::launch_mel(h->mel_rows, h->d_mel_win, h->d_mel_cpack, d_pcm + c0 * n_samples, n_samples, nb, blk, pos,
+                             d_cols + c0, pmax, h->d_mel_work.as<float>(), d_out + c0 * hpfw::kMelBands * nf, s);
+            if ((rc = check_launch("mel"))) return rc;
+        }
+        return 0;
+    });
 }
 
 int hpfw_gpu_mel_spectrogram_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, float *out,
@@ -1676,23 +1597,17 @@ int hpfw_gpu_mel_spectrogram_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t
     HIP_TRY(hipSetDevice(h->device));
     if (n_clips == 0) return 0;
     const size_t per = (size_t)hpfw::kMelBands * hpfw::mel_frames(n_samples);
-    int16_t *d_pcm = nullptr;
-    float *d_out = nullptr;
-    int32_t *d_cols = nullptr;
-    int rc = 0;
-    if (hipMalloc((void **)&d_pcm, (size_t)n_clips * n_samples * 2) != hipSuccess ||
-        hipMalloc((void **)&d_out, (size_t)n_clips * per * 4) != hipSuccess || hipMalloc((void **)&d_cols, (size_t)n_clips * 4) != hipSuccess)
-        rc = fail(HPFW_E_NOMEM, "hipMalloc failed");
-    if (!rc && (hipMemcpy(d_pcm, pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemset(d_out, 0, (size_t)n_clips * per * 4) != hipSuccess))
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm, n_samples, n_clips, d_out, d_cols, nullptr);
-    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_out, (size_t)n_clips * per * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(cols, d_cols, (size_t)n_clips * 4, hipMemcpyDeviceToHost) != hipSuccess))
+    DevBuf d_pcm, d_out, d_cols;
+    if (d_pcm.alloc((size_t)n_clips * n_samples * 2) != hipSuccess || d_out.alloc((size_t)n_clips * per * 4) != hipSuccess ||
+        d_cols.alloc((size_t)n_clips * 4) != hipSuccess)
+        return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    if (hipMemcpy(d_pcm.get(), pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_out.get(), 0, (size_t)n_clips * per * 4) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm.as<int16_t>(), n_samples, n_clips, d_out.as<float>(), d_cols.as<int32_t>(), nullptr);
+    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_out.get(), (size_t)n_clips * per * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(cols, d_cols.get(), (size_t)n_clips * 4, hipMemcpyDeviceToHost) != hipSuccess))
         rc = fail(HPFW_E_HIP, "kernel execution or D2H copy failed");
-    if (d_pcm) (void)hipFree(d_pcm);
-    if (d_out) (void)hipFree(d_out);
-    if (d_cols) (void)hipFree(d_cols);
     return rc;
 }
 
@@ -1716,11 +1631,17 @@ int hpfw_gpu_cfg_set_filters(hpfw_gpu *h, const hpfw_handle_config *c, const flo
     HIP_TRY(hipSetDevice(h->device));
     std::vector<float> packed(hpfw::cfg_fpack_floats(c->rows, c->context, c->bits));
     hpfw::pack_cfg_filters(c->rows, c->context, c->bits, f, packed.data());
-    float *&d = h->cfg_fpack[{c->rows, c->context, c->bits}];
-    if (!d) HIP_TRY(hipMalloc((void **)&d, packed.size() * 4));
-    Ordered ordered(h, nullptr);
-    HIP_TRY(hipMemcpy(d, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-    return 0;
+    const std::vector<int> key{c->rows, c->context, c->bits};
+    auto it = h->cfg_fpack.find(key);
+    if (it == h->cfg_fpack.end()) { // (the configuration is known once its buffer exists)
+        DevBuf d;
+        HIP_TRY(d.alloc(packed.size() * 4));
+        it = h->cfg_fpack.emplace(key, std::move(d)).first;
+    }
+    return ordered_call(h, nullptr, [&] {
+        HIP_TRY(hipMemcpy(it->second.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+        return 0;
+    });
 }
 
 int hpfw_gpu_cfg_hashprints(hpfw_gpu *h, const hpfw_handle_config *c, const float *d_s, const int32_t *d_cols, int64_t n_clips,
@@ -1736,45 +1657,48 @@ int hpfw_gpu_cfg_hashprints(hpfw_gpu *h, const hpfw_handle_config *c, const floa
     if (n_clips == 0 || nhp <= 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const hpfw::CfgArgs a{c->rows, c->context, c->lag, c->bits, it->second};
-    // clips per pass: the projection scratch stays below 1 GiB
-    const int64_t per = (int64_t)c->bits * nf * 4;
-    const int64_t chunk = d_proj ? n_clips : std::max<int64_t>(1, std::min<int64_t>(n_clips, ((int64_t)1 << 30) / per));
-    if (!d_proj && (rc = ensure((void **)&h->d_cfg_proj, &h->cfg_proj_cap, (size_t)chunk * per))) return rc;
-    const size_t word = (size_t)c->bits / 8;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {
-        const int nb = (int)std::min<int64_t>(chunk, n_clips - c0);
-        float *pj = d_proj ? d_proj + c0 * c->bits * nf : h->d_cfg_proj;
-        const int *cols = d_cols ? d_cols + c0 : nullptr;
-        {
-            Timed t(h, K_PROJECT, s);
-            hpfw::launch_project_cfg(a, d_s + c0 * c->rows * stride, cols, nb, stride, pj, nf, s);
+    return ordered_call(h, s, [&] {
+        const hpfw::CfgArgs a{c->rows, c->context, c->lag, c->bits, it->second.as<float>()};
+        // clips per pass: the projection scratch stays below 1 GiB
+        const int64_t per = (int64_t)c->bits * nf * 4;
+        const int64_t chunk = d_proj ? n_clips : std::max<int64_t>(1, std::min<int64_t>(n_clips, ((int64_t)1 << 30) / per));
+        if (!d_proj && (rc = ensure(h->d_cfg_proj, (size_t)chunk * per))) return rc;
+        const size_t word = (size_t)c->bits / 8;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {
+            const int nb = (int)std::min<int64_t>(chunk, n_clips - c0);
+            float *pj = d_proj ? d_proj + c0 * c->bits * nf : h->d_cfg_proj.as<float>();
+            const int *cols = d_cols ? d_cols + c0 : nullptr;
+            {
+                Timed t(h, K_PROJECT, s);
+                hpfw::launch_project_cfg(a, d_s + c0 * c->rows * stride, cols, nb, stride, pj, nf, s);
+            }
+            if ((rc = check_launch("project_cfg"))) return rc;
+            {
+                Timed t(h, K_PACK, s);
+                hpfw::launch_pack_cfg(a, pj, cols, nb, stride, nf, (char *)d_hp + (size_t)c0 * hp_stride * word, hp_stride, s);
+            }
+            if ((rc = check_launch("pack_cfg"))) return rc;
         }
-        if ((rc = check_launch("project_cfg"))) return rc;
-        {
-            Timed t(h, K_PACK, s);
-            hpfw::launch_pack_cfg(a, pj, cols, nb, stride, nf, (char *)d_hp + (size_t)c0 * hp_stride * word, hp_stride, s);
-        }
-        if ((rc = check_launch("pack_cfg"))) return rc;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 static int cfg_cov_slot(hpfw_gpu *h, const hpfw_handle_config *c, hpfw_gpu::CfgCov **out)
 {
-    const int kt = c->rows * c->context;
-    hpfw_gpu::CfgCov &cc = h->cfg_cov[{c->rows, c->context}];
-    if (!cc.d_accum) {
-        HIP_TRY(hipMalloc((void **)&cc.d_accum, (size_t)kt * kt * 4));
-        HIP_TRY(hipMemset(cc.d_accum, 0, (size_t)kt * kt * 4));
+    const std::vector<int> key{c->rows, c->context};
+    auto it = h->cfg_cov.find(key);
+    if (it == h->cfg_cov.end()) { // (entered once complete)
+        const int kt = c->rows * c->context;
+        hpfw_gpu::CfgCov cc;
+        HIP_TRY(cc.d_accum.alloc((size_t)kt * kt * 4));
+        HIP_TRY(hipMemset(cc.d_accum.get(), 0, (size_t)kt * kt * 4));
         std::vector<int> xy((size_t)2 * hpfw::cov_cfg_tile_count(kt));
         hpfw::cov_cfg_tile_list(kt, xy.data());
-        HIP_TRY(hipMalloc((void **)&cc.d_tiles, xy.size() * 4));
-        HIP_TRY(hipMemcpy(cc.d_tiles, xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
-        cc.clips = 0;
+        HIP_TRY(cc.d_tiles.alloc(xy.size() * 4));
+        HIP_TRY(hipMemcpy(cc.d_tiles.get(), xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
+        it = h->cfg_cov.emplace(key, std::move(cc)).first;
     }
-    *out = &cc;
+    *out = &it->second;
     return 0;
 }
 
@@ -1786,11 +1710,12 @@ int hpfw_gpu_cfg_cov_reset(hpfw_gpu *h, const hpfw_handle_config *c)
     HIP_TRY(hipSetDevice(h->device));
     auto it = h->cfg_cov.find({c->rows, c->context});
     if (it == h->cfg_cov.end()) return 0;
-    Ordered ordered(h, nullptr);
-    const int kt = c->rows * c->context;
-    HIP_TRY(hipMemset(it->second.d_accum, 0, (size_t)kt * kt * 4));
-    it->second.clips = 0;
-    return 0;
+    return ordered_call(h, nullptr, [&] {
+        const int kt = c->rows * c->context;
+        HIP_TRY(hipMemset(it->second.d_accum.get(), 0, (size_t)kt * kt * 4));
+        it->second.clips = 0;
+        return 0;
+    });
 }
 
 int hpfw_gpu_cfg_cov_accumulate(hpfw_gpu *h, const hpfw_handle_config *c, const float *d_s, const int32_t *d_cols, int64_t n_clips,
@@ -1805,19 +1730,20 @@ int hpfw_gpu_cfg_cov_accumulate(hpfw_gpu *h, const hpfw_handle_config *c, const 
     hpfw_gpu::CfgCov *cc;
     if ((rc = cfg_cov_slot(h, c, &cc))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int64_t chunk = 512; // clips per pass: bounds the partial tiles and the per-clip sums
-    if ((rc = ensure((void **)&h->d_cfg_cov_ws, &h->cfg_cov_ws_cap,
-                     hpfw::cov_cfg_workspace_bytes(a, (int)std::min(chunk, std::max<int64_t>(n_clips, 1))))))
-        return rc;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {
-        const int nb = (int)std::min(chunk, n_clips - c0);
-        hpfw::launch_cov_cfg(a, d_s + c0 * c->rows * stride, d_cols ? d_cols + c0 : nullptr, nb, stride, cc->d_tiles,
-                             h->d_cfg_cov_ws, cc->d_accum, s);
-        if ((rc = check_launch("cov_cfg"))) return rc;
-    }
-    cc->clips += n_clips;
-    return 0;
+    return ordered_call(h, s, [&] {
+        const int64_t chunk = 512; // clips per pass: bounds the partial tiles and the per-clip sums
+        if ((rc = ensure(h->d_cfg_cov_ws,
+                         hpfw::cov_cfg_workspace_bytes(a, (int)std::min(chunk, std::max<int64_t>(n_clips, 1))))))
+            return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {
+            const int nb = (int)std::min(chunk, n_clips - c0);
+            hpfw::launch_cov_cfg(a, d_s + c0 * c->rows * stride, d_cols ? d_cols + c0 : nullptr, nb, stride, cc->d_tiles.as<int>(),
+                                 h->d_cfg_cov_ws.as<float>(), cc->d_accum.as<float>(), s);
+            if ((rc = check_launch("cov_cfg"))) return rc;
+        }
+        cc->clips += n_clips;
+        return 0;
+    });
 }
 
 int hpfw_gpu_cfg_cov_get(hpfw_gpu *h, const hpfw_handle_config *c, float *cov, int64_t *n_clips)
@@ -1834,7 +1760,7 @@ int hpfw_gpu_cfg_cov_get(hpfw_gpu *h, const hpfw_handle_config *c, float *cov, i
         return 0;
     }
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(cov, it->second.d_accum, nn * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cov, it->second.d_accum.get(), nn * 4, hipMemcpyDeviceToHost));
     if (n_clips) *n_clips = it->second.clips;
     return 0;
 }
@@ -1870,29 +1796,21 @@ int hpfw_gpu_mel_hashprints_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t 
     if (n_clips == 0) return 0;
     if (h->cfg_fpack.find({cfg.rows, cfg.context, cfg.bits}) == h->cfg_fpack.end())
         return fail(HPFW_E_NOFILTERS, "no filters for the combiner configuration: call hpfw_gpu_cfg_set_filters first");
-    int16_t *d_pcm = nullptr;
-    float *d_s = nullptr;
-    int32_t *d_cols = nullptr;
-    uint16_t *d_hp = nullptr;
     const size_t per = (size_t)hpfw::kMelBands * frames, hp_words = (size_t)n_clips * std::max<int64_t>(hp_stride, 1);
-    int rc = 0;
-    if (hipMalloc((void **)&d_pcm, (size_t)n_clips * n_samples * 2) != hipSuccess || hipMalloc((void **)&d_s, (size_t)n_clips * per * 4) != hipSuccess ||
-        hipMalloc((void **)&d_cols, (size_t)n_clips * 4) != hipSuccess || hipMalloc((void **)&d_hp, hp_words * 2) != hipSuccess)
-        rc = fail(HPFW_E_NOMEM, "hipMalloc failed");
-    if (!rc && (hipMemcpy(d_pcm, pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemset(d_s, 0, (size_t)n_clips * per * 4) != hipSuccess || hipMemset(d_hp, 0, hp_words * 2) != hipSuccess))
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm, n_samples, n_clips, d_s, d_cols, nullptr);
-    if (!rc) rc = hpfw_gpu_cfg_hashprints(h, &cfg, d_s, d_cols, n_clips, frames, d_hp, hp_stride, nullptr, nullptr);
+    DevBuf d_pcm, d_s, d_cols, d_hp;
+    if (d_pcm.alloc((size_t)n_clips * n_samples * 2) != hipSuccess || d_s.alloc((size_t)n_clips * per * 4) != hipSuccess ||
+        d_cols.alloc((size_t)n_clips * 4) != hipSuccess || d_hp.alloc(hp_words * 2) != hipSuccess)
+        return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    if (hipMemcpy(d_pcm.get(), pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_s.get(), 0, (size_t)n_clips * per * 4) != hipSuccess || hipMemset(d_hp.get(), 0, hp_words * 2) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm.as<int16_t>(), n_samples, n_clips, d_s.as<float>(), d_cols.as<int32_t>(), nullptr);
+    if (!rc) rc = hpfw_gpu_cfg_hashprints(h, &cfg, d_s.as<float>(), d_cols.as<int32_t>(), n_clips, frames, d_hp.get(), hp_stride, nullptr, nullptr);
     std::vector<int32_t> cols((size_t)n_clips);
-    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(hp, d_hp, hp_words * 2, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(cols.data(), d_cols, (size_t)n_clips * 4, hipMemcpyDeviceToHost) != hipSuccess))
+    if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(hp, d_hp.get(), hp_words * 2, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(cols.data(), d_cols.get(), (size_t)n_clips * 4, hipMemcpyDeviceToHost) != hipSuccess))
         rc = fail(HPFW_E_HIP, "kernel execution or D2H copy failed");
     for (int64_t i = 0; !rc && i < n_clips; ++i) n_hp[i] = std::max<int32_t>(cols[(size_t)i] - cfg.context + 1 - cfg.lag, 0);
-    if (d_pcm) (void)hipFree(d_pcm);
-    if (d_s) (void)hipFree(d_s);
-    if (d_cols) (void)hipFree(d_cols);
-    if (d_hp) (void)hipFree(d_hp);
     return rc;
 }
 
@@ -1904,38 +1822,37 @@ int hpfw_gpu_mel_cov_accumulate_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int6
     const hpfw_handle_config cfg = HPFW_CONFIG_COMBINER;
     const int64_t frames = hpfw::mel_frames(n_samples);
     const size_t per = (size_t)hpfw::kMelBands * frames;
-    int16_t *d_pcm = nullptr;
-    float *d_s = nullptr;
-    int32_t *d_cols = nullptr;
-    int rc = 0;
-    if (hipMalloc((void **)&d_pcm, (size_t)n_clips * n_samples * 2) != hipSuccess || hipMalloc((void **)&d_s, (size_t)n_clips * per * 4) != hipSuccess ||
-        hipMalloc((void **)&d_cols, (size_t)n_clips * 4) != hipSuccess)
-        rc = fail(HPFW_E_NOMEM, "hipMalloc failed");
-    if (!rc && (hipMemcpy(d_pcm, pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemset(d_s, 0, (size_t)n_clips * per * 4) != hipSuccess))
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm, n_samples, n_clips, d_s, d_cols, nullptr);
-    if (!rc) rc = hpfw_gpu_cfg_cov_accumulate(h, &cfg, d_s, d_cols, n_clips, frames, nullptr);
+    DevBuf d_pcm, d_s, d_cols;
+    if (d_pcm.alloc((size_t)n_clips * n_samples * 2) != hipSuccess || d_s.alloc((size_t)n_clips * per * 4) != hipSuccess ||
+        d_cols.alloc((size_t)n_clips * 4) != hipSuccess)
+        return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    if (hipMemcpy(d_pcm.get(), pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_s.get(), 0, (size_t)n_clips * per * 4) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_mel_spectrogram_pcm16(h, d_pcm.as<int16_t>(), n_samples, n_clips, d_s.as<float>(), d_cols.as<int32_t>(), nullptr);
+    if (!rc) rc = hpfw_gpu_cfg_cov_accumulate(h, &cfg, d_s.as<float>(), d_cols.as<int32_t>(), n_clips, frames, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    if (d_pcm) (void)hipFree(d_pcm);
-    if (d_s) (void)hipFree(d_s);
-    if (d_cols) (void)hipFree(d_cols);
     return rc;
 }
 
 // ---- filter learning: preprocess() of the reference (parallel_collector.h:82-112) ---------------
 static int cov_prepare(hpfw_gpu *h, hipStream_t s)
 {
+    // (each buffer is the handle's once it is filled)
     if (!h->d_cov) {
-        HIP_TRY(hipMalloc((void **)&h->d_cov, (size_t)hpfw::kFrame * hpfw::kFrame * 4));
-        HIP_TRY(hipMemsetAsync(h->d_cov, 0, (size_t)hpfw::kFrame * hpfw::kFrame * 4, s));
+        DevBuf cov;
+        HIP_TRY(cov.alloc((size_t)hpfw::kFrame * hpfw::kFrame * 4));
+        HIP_TRY(hipMemsetAsync(cov.get(), 0, (size_t)hpfw::kFrame * hpfw::kFrame * 4, s));
+        h->d_cov = std::move(cov);
         h->cov_files = 0;
     }
     if (!h->d_cov_tiles) {
         std::vector<int> xy((size_t)2 * hpfw::cov_tile_count());
         hpfw::cov_tile_list(xy.data());
-        HIP_TRY(hipMalloc((void **)&h->d_cov_tiles, xy.size() * 4));
-        HIP_TRY(hipMemcpy(h->d_cov_tiles, xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
+        DevBuf tiles;
+        HIP_TRY(tiles.alloc(xy.size() * 4));
+        HIP_TRY(hipMemcpy(tiles.get(), xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
+        h->d_cov_tiles = std::move(tiles);
     }
     return 0;
 }
@@ -1944,7 +1861,7 @@ int hpfw_gpu_cov_reset(hpfw_gpu *h)
 {
     if (!h) return fail(HPFW_E_INVALID, "null handle");
     HIP_TRY(hipSetDevice(h->device));
-    if (h->d_cov) HIP_TRY(hipMemset(h->d_cov, 0, (size_t)hpfw::kFrame * hpfw::kFrame * 4));
+    if (h->d_cov) HIP_TRY(hipMemset(h->d_cov.get(), 0, (size_t)hpfw::kFrame * hpfw::kFrame * 4));
     h->cov_files = 0;
     return 0;
 }
@@ -1954,20 +1871,21 @@ int hpfw_gpu_cov_accumulate_db(hpfw_gpu *h, const float *d_db, int64_t n_clips, 
     if (!h || !d_db || n_clips < 0 || c < hpfw::kCtx + 1) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    int rc = cov_prepare(h, s);
-    if (rc) return rc;
-    const int64_t chunk = 128; // clips per pass: bounds the workspace (Z, correction vectors, partial sums)
-    if ((rc = ensure((void **)&h->d_cov_ws, &h->cov_ws_cap,
-                     hpfw::cov_workspace_bytes((int)std::min(chunk, std::max<int64_t>(n_clips, 1)), (int)c))))
-        return rc;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {
-        const int nb = (int)std::min(chunk, n_clips - c0);
-        hpfw::launch_cov(d_db + c0 * 121 * c, nb, (int)c, h->d_cov_tiles, h->d_cov_ws, h->d_cov, s);
-        if ((rc = check_launch("covariance"))) return rc;
-    }
-    h->cov_files += n_clips;
-    return 0;
+    return ordered_call(h, s, [&] {
+        int rc = cov_prepare(h, s);
+        if (rc) return rc;
+        const int64_t chunk = 128; // clips per pass: bounds the workspace (Z, correction vectors, partial sums)
+        if ((rc = ensure(h->d_cov_ws,
+                         hpfw::cov_workspace_bytes((int)std::min(chunk, std::max<int64_t>(n_clips, 1)), (int)c))))
+            return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {
+            const int nb = (int)std::min(chunk, n_clips - c0);
+            hpfw::launch_cov(d_db + c0 * 121 * c, nb, (int)c, h->d_cov_tiles.as<int>(), h->d_cov_ws.as<float>(), h->d_cov.as<float>(), s);
+            if ((rc = check_launch("covariance"))) return rc;
+        }
+        h->cov_files += n_clips;
+        return 0;
+    });
 }
 
 int hpfw_gpu_stage_spectrogram(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, float *d_db,
@@ -1979,16 +1897,17 @@ int hpfw_gpu_stage_spectrogram(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samp
     int rc = get_plan(h, n_samples, &dp);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int nbmax = pass_clips(h, dp, n_clips);
-    if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
-    const size_t per = (size_t)121 * dp->hp.c;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        if ((rc = run_front(h, dp, d_pcm + c0 * n_samples, nb, 0, true, s))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_db + c0 * per, h->ws[2], (size_t)nb * per * 4, hipMemcpyDeviceToDevice, s));
-    }
-    return 0;
+    return ordered_call(h, s, [&] {
+        const int nbmax = pass_clips(h, dp, n_clips);
+        if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
+        const size_t per = (size_t)121 * dp->hp.c;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            if ((rc = run_front(h, dp, d_pcm + c0 * n_samples, nb, 0, true, s))) return rc;
+            HIP_TRY(hipMemcpyAsync(d_db + c0 * per, h->ws[2].get(), (size_t)nb * per * 4, hipMemcpyDeviceToDevice, s));
+        }
+        return 0;
+    });
 }
 
 int hpfw_gpu_cov_accumulate_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips,
@@ -2001,15 +1920,16 @@ int hpfw_gpu_cov_accumulate_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_s
     if (rc) return rc;
     if (dp->hp.n_frames < 2) return fail(HPFW_E_UNSUPPORTED, "clip too short for a covariance");
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    const int nbmax = pass_clips(h, dp, n_clips);
-    if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
-    for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-        const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-        if ((rc = run_front(h, dp, d_pcm + c0 * n_samples, nb, 0, true, s))) return rc;
-        if ((rc = hpfw_gpu_cov_accumulate_db(h, (const float *)h->ws[2], nb, dp->hp.c, stream))) return rc;
-    }
-    return 0;
+    return ordered_call(h, s, [&] {
+        const int nbmax = pass_clips(h, dp, n_clips);
+        if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            if ((rc = run_front(h, dp, d_pcm + c0 * n_samples, nb, 0, true, s))) return rc;
+            if ((rc = hpfw_gpu_cov_accumulate_db(h, h->ws[2].as<float>(), nb, dp->hp.c, stream))) return rc;
+        }
+        return 0;
+    });
 }
 
 int hpfw_gpu_cov_accumulate_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips)
@@ -2017,14 +1937,12 @@ int hpfw_gpu_cov_accumulate_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t 
     if (!h || !pcm || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     if (n_clips == 0) return 0;
-    int16_t *d_pcm = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_pcm, (size_t)n_clips * n_samples * 2));
-    int rc = 0;
-    if (hipMemcpy(d_pcm, pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) rc = hpfw_gpu_cov_accumulate_pcm16(h, d_pcm, n_samples, n_clips, nullptr);
+    DevBuf d_pcm;
+    HIP_TRY(d_pcm.alloc((size_t)n_clips * n_samples * 2));
+    if (hipMemcpy(d_pcm.get(), pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_cov_accumulate_pcm16(h, d_pcm.as<int16_t>(), n_samples, n_clips, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    (void)hipFree(d_pcm);
     return rc;
 }
 
@@ -2038,7 +1956,7 @@ int hpfw_gpu_cov_get(hpfw_gpu *h, float *cov, int64_t *n_files)
         std::memset(cov, 0, nn * 4);
     } else {
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(cov, h->d_cov, nn * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cov, h->d_cov.get(), nn * 4, hipMemcpyDeviceToHost));
         // the device holds tiles on or above the diagonal (128-wide); mirror them
         for (int r = 0; r < hpfw::kFrame; ++r)
             for (int c2 = 0; c2 < r; ++c2)
@@ -2054,7 +1972,7 @@ int hpfw_gpu_cov_set(hpfw_gpu *h, const float *cov, int64_t n_files)
     HIP_TRY(hipSetDevice(h->device));
     int rc = cov_prepare(h, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(h->d_cov, cov, (size_t)hpfw::kFrame * hpfw::kFrame * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_cov.get(), cov, (size_t)hpfw::kFrame * hpfw::kFrame * 4, hipMemcpyHostToDevice));
     h->cov_files = n_files;
     return 0;
 }
@@ -2066,7 +1984,7 @@ int hpfw_gpu_cov_device(hpfw_gpu *h, float **d_cov)
     int rc = cov_prepare(h, nullptr);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    *d_cov = h->d_cov;
+    *d_cov = h->d_cov.as<float>();
     return 0;
 }
 
@@ -2118,29 +2036,28 @@ static int index_add_impl(hpfw_gpu *h, const uint64_t *hp, const int64_t *offset
         if (offsets[i + 1] < offsets[i]) return fail(HPFW_E_INVALID, "offsets must be non-decreasing");
     const int64_t add = offsets[n_clips] - offsets[0];
     const int64_t have = h->db_off.back();
-    Ordered ordered(h, s);
-    if ((size_t)(have + add) > h->db_cap) {
-        size_t ncap = std::max<size_t>((size_t)(have + add), h->db_cap * 2);
-        ncap = std::max<size_t>(ncap, 1 << 16);
-        uint64_t *nd = nullptr;
-        HIP_TRY(hipMalloc((void **)&nd, ncap * 8));
-        // earlier appends may still be in flight on a non-blocking stream the null-stream copy below would
-        // not wait for, and scans may still be reading the old buffer: growing is rare (capacity doubles)
-        HIP_TRY(hipDeviceSynchronize());
-        if (have) HIP_TRY(hipMemcpy(nd, h->d_db, (size_t)have * 8, hipMemcpyDeviceToDevice));
-        if (h->d_db) HIP_TRY(hipFree(h->d_db));
-        h->d_db = nd;
-        h->db_cap = ncap;
-    }
-    if (add) {
-        if (dev)
-            HIP_TRY(hipMemcpyAsync(h->d_db + have, hp + offsets[0], (size_t)add * 8, hipMemcpyDeviceToDevice, s));
-        else
-            HIP_TRY(hipMemcpy(h->d_db + have, hp + offsets[0], (size_t)add * 8, hipMemcpyHostToDevice));
-    }
-    for (int64_t i = 0; i < n_clips; ++i) h->db_off.push_back(have + (offsets[i + 1] - offsets[0]));
-    h->db_off_dirty = true;
-    return 0;
+    return ordered_call(h, s, [&] {
+        const size_t need = (size_t)(have + add) * 8;
+        if (need > h->d_db.capacity()) {
+            DevBuf nd;
+            HIP_TRY(nd.alloc(std::max({need, h->d_db.capacity() * 2, (size_t)8 << 16})));
+            // earlier appends may still be in flight on a non-blocking stream the null-stream copy below would
+            // not wait for, and scans may still be reading the old buffer: growing is rare (capacity doubles)
+            HIP_TRY(hipDeviceSynchronize());
+            if (have) HIP_TRY(hipMemcpy(nd.get(), h->d_db.get(), (size_t)have * 8, hipMemcpyDeviceToDevice));
+            h->d_db = std::move(nd); // (the old buffer goes with nd)
+        }
+        uint64_t *dst = h->d_db.as<uint64_t>() + have;
+        if (add) {
+            if (dev)
+                HIP_TRY(hipMemcpyAsync(dst, hp + offsets[0], (size_t)add * 8, hipMemcpyDeviceToDevice, s));
+            else
+                HIP_TRY(hipMemcpy(dst, hp + offsets[0], (size_t)add * 8, hipMemcpyHostToDevice));
+        }
+        for (int64_t i = 0; i < n_clips; ++i) h->db_off.push_back(have + (offsets[i + 1] - offsets[0]));
+        h->db_off_dirty = true;
+        return 0;
+    });
 }
 
 int hpfw_gpu_index_add(hpfw_gpu *h, const uint64_t *hp, const int64_t *offsets, int64_t n_clips)
@@ -2168,7 +2085,7 @@ int hpfw_gpu_index_get(hpfw_gpu *h, int64_t *offsets, uint64_t *hp, int64_t hp_c
     if (hp_cap < total) return fail(HPFW_E_INVALID, "hashprint buffer too small for the index");
     if (total) {
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(hp, h->d_db, (size_t)total * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hp, h->d_db.get(), (size_t)total * 8, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -2186,106 +2103,107 @@ int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64
     if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Ordered ordered(h, s);
-    if (n_q == 0) return 0;
-    if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
-    const int64_t n_clips = (int64_t)h->db_off.size() - 1;
-    int rc;
-    if (n_clips == 0) { // nothing indexed: every slot is "none"
-        hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->clip_base, d_out, s);
-        return check_launch("topk");
-    }
-    if (h->db_off_dirty) {
-        if ((rc = ensure((void **)&h->d_db_off, &h->db_off_cap, h->db_off.size() * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_db_off, h->db_off.data(), h->db_off.size() * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        h->db_off_dirty = false;
-    }
-    int64_t k_max = 0;
-    for (int64_t i = 0; i < n_q; ++i) {
-        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-        k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
-    }
-    if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
-    if ((rc = ensure((void **)&h->d_q_off, &h->q_off_cap, (size_t)(n_q + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->d_q_off, q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
-    // queries are processed in groups so the (query, clip) table stays below 1 GiB
-    int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 27) / n_clips / 32 * 32);
-    qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
-    qgroup = std::min<int64_t>(qgroup, (int64_t)65535 * 8 / 32 * 32); // the scans put groups of 8 / 32 queries along gridDim.y
-    if ((rc = ensure((void **)&h->d_best, &h->best_cap, (size_t)qgroup * n_clips * 8))) return rc;
-    // The scan runs on the matrix cores (k_search_mfma.hip) unless the window does not fit the LDS
-    // (queries of several thousand hashprints) or HPFW_SEARCH_POPC asks for the xor/popcount kernel; fewer than
-    // 8 queries go one by one through the shifted-rows variant (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force
-    // the grouped / the shifted-rows kernel for any number of queries).
-    // A group of 32 queries is one MFMA tile: with fewer than 8 queries most of its rows would be padding
-    // and the popcount kernel (one workgroup per 8 queries) does less work.
-    const bool mfma = !std::getenv("HPFW_SEARCH_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024 &&
-                      k_max > 0 && (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
-    const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
-    int64_t n_max = 0;
-    for (int64_t i = 0; i < n_clips; ++i) n_max = std::max(n_max, h->db_off[i + 1] - h->db_off[i]);
-    if (mfma) {
-        if ((rc = ensure((void **)&h->d_qa, &h->qa_cap, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
-        if ((rc = ensure((void **)&h->d_gk, &h->gk_cap, (size_t)(qgroup / 32) * 8))) return rc;
-    }
-    std::vector<int> gk;
-    for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
-        const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
-        HIP_TRY(hipMemsetAsync(h->d_best, 0xff, (size_t)ng * n_clips * 8, s));
-        hpfw::SearchArgs a;
-        a.db = h->d_db;
-        a.db_off = h->d_db_off;
-        a.n_clips = (int)n_clips;
-        a.q = d_q_hp;
-        a.q_off = h->d_q_off + g0;
-        a.n_q = ng;
-        a.k_max = (int)k_max;
-        a.best = h->d_best;
-        const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !std::getenv("HPFW_SEARCH_POPC") && k_max > 0 && n_max > 0 &&
-                         hpfw::hamming_shift_lds_bytes((int)k_max) <= 160 * 1024;
-        if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
-            if ((rc = ensure((void **)&h->d_qa, &h->qa_cap, hpfw::hamming_shift_image_bytes((int)k_max)))) return rc;
-            Timed t(h, K_SCAN, s);
-            for (int i = 0; i < ng; ++i) {
-                const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
-                if (kq <= 0) continue;
-                hpfw::launch_hamming_shift(h->d_db, h->d_db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
-                                           d_q_hp + q_off[g0 + i], kq, h->d_qa, h->d_best + (size_t)i * n_clips, s);
-            }
-        } else if (mfma && n_max > 0) {
-            gk.assign((size_t)(ng + 31) / 32 * 2, 0); // per group: longest query, shortest non-empty query
-            int kmin_all = 0;
-            for (int i = 0; i < ng; ++i) {
-                const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
-                int &mx = gk[(size_t)i / 32 * 2], &mn = gk[(size_t)i / 32 * 2 + 1];
-                mx = std::max(mx, kq);
-                if (kq > 0) mn = mn == 0 ? kq : std::min(mn, kq);
-                if (kq > 0) kmin_all = kmin_all == 0 ? kq : std::min(kmin_all, kq);
-            }
-            HIP_TRY(hipMemcpyAsync(h->d_gk, gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
-            Timed t(h, K_SCAN, s);
-            hpfw::launch_expand_queries(d_q_hp, a.q_off, ng, kt_pad, h->d_qa, s);
-            // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
-            hpfw::launch_hamming_mfma(a, h->d_qa, kt_pad, h->d_gk, (int)std::max<int64_t>(n_max - std::min<int64_t>(kmin_all, n_max) + 1, 1), s);
-        } else {
-            Timed t(h, K_SCAN, s);
-            hpfw::launch_hamming_scan(a, s);
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
+        const int64_t n_clips = (int64_t)h->db_off.size() - 1;
+        int rc;
+        if (n_clips == 0) { // nothing indexed: every slot is "none"
+            hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->clip_base, d_out, s);
+            return check_launch("topk");
         }
-        if ((rc = check_launch("hamming_scan"))) return rc;
-        {
-            Timed t(h, K_TOPK, s);
-            if (n_clips >= 16384 && ng <= 64) { // one workgroup per query would crawl through the whole table
-                if ((rc = ensure(&h->d_topk_scratch, &h->topk_scratch_cap, hpfw::topk_scratch_bytes(ng, k)))) return rc;
-                hpfw::launch_topk_two_step(h->d_best, ng, (int)n_clips, k, h->clip_base, h->d_topk_scratch, d_out + g0 * k, s);
+        if (h->db_off_dirty) {
+            if ((rc = ensure(h->d_db_off, h->db_off.size() * 8))) return rc;
+            HIP_TRY(hipMemcpyAsync(h->d_db_off.get(), h->db_off.data(), h->db_off.size() * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            h->db_off_dirty = false;
+        }
+        int64_t k_max = 0;
+        for (int64_t i = 0; i < n_q; ++i) {
+            if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+            k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
+        }
+        if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+        if ((rc = ensure(h->d_q_off, (size_t)(n_q + 1) * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
+        // queries are processed in groups so the (query, clip) table stays below 1 GiB
+        int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 27) / n_clips / 32 * 32);
+        qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
+        qgroup = std::min<int64_t>(qgroup, (int64_t)65535 * 8 / 32 * 32); // the scans put groups of 8 / 32 queries along gridDim.y
+        if ((rc = ensure(h->d_best, (size_t)qgroup * n_clips * 8))) return rc;
+        // The scan runs on the matrix cores (k_search_mfma.hip) unless the window does not fit the LDS
+        // (queries of several thousand hashprints) or HPFW_SEARCH_POPC asks for the xor/popcount kernel; fewer than
+        // 8 queries go one by one through the shifted-rows variant (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force
+        // the grouped / the shifted-rows kernel for any number of queries).
+        // A group of 32 queries is one MFMA tile: with fewer than 8 queries most of its rows would be padding
+        // and the popcount kernel (one workgroup per 8 queries) does less work.
+        const bool mfma = !std::getenv("HPFW_SEARCH_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024 &&
+                          k_max > 0 && (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
+        const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
+        int64_t n_max = 0;
+        for (int64_t i = 0; i < n_clips; ++i) n_max = std::max(n_max, h->db_off[i + 1] - h->db_off[i]);
+        if (mfma) {
+            if ((rc = ensure(h->d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
+            if ((rc = ensure(h->d_gk, (size_t)(qgroup / 32) * 8))) return rc;
+        }
+        std::vector<int> gk;
+        for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
+            const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
+            HIP_TRY(hipMemsetAsync(h->d_best.get(), 0xff, (size_t)ng * n_clips * 8, s));
+            hpfw::SearchArgs a;
+            a.db = h->d_db.as<uint64_t>();
+            a.db_off = h->d_db_off.as<int64_t>();
+            a.n_clips = (int)n_clips;
+            a.q = d_q_hp;
+            a.q_off = h->d_q_off.as<int64_t>() + g0;
+            a.n_q = ng;
+            a.k_max = (int)k_max;
+            a.best = h->d_best.as<uint64_t>();
+            const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !std::getenv("HPFW_SEARCH_POPC") && k_max > 0 && n_max > 0 &&
+                             hpfw::hamming_shift_lds_bytes((int)k_max) <= 160 * 1024;
+            if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
+                if ((rc = ensure(h->d_qa, hpfw::hamming_shift_image_bytes((int)k_max)))) return rc;
+                Timed t(h, K_SCAN, s);
+                for (int i = 0; i < ng; ++i) {
+                    const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
+                    if (kq <= 0) continue;
+                    hpfw::launch_hamming_shift(a.db, a.db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
+                                               d_q_hp + q_off[g0 + i], kq, h->d_qa.get(), a.best + (size_t)i * n_clips, s);
+                }
+            } else if (mfma && n_max > 0) {
+                gk.assign((size_t)(ng + 31) / 32 * 2, 0); // per group: longest query, shortest non-empty query
+                int kmin_all = 0;
+                for (int i = 0; i < ng; ++i) {
+                    const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
+                    int &mx = gk[(size_t)i / 32 * 2], &mn = gk[(size_t)i / 32 * 2 + 1];
+                    mx = std::max(mx, kq);
+                    if (kq > 0) mn = mn == 0 ? kq : std::min(mn, kq);
+                    if (kq > 0) kmin_all = kmin_all == 0 ? kq : std::min(kmin_all, kq);
+                }
+                HIP_TRY(hipMemcpyAsync(h->d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_expand_queries(d_q_hp, a.q_off, ng, kt_pad, h->d_qa.get(), s);
+                // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
+                hpfw::launch_hamming_mfma(a, h->d_qa.get(), kt_pad, h->d_gk.as<int>(), (int)std::max<int64_t>(n_max - std::min<int64_t>(kmin_all, n_max) + 1, 1), s);
             } else {
-                hpfw::launch_topk(h->d_best, ng, (int)n_clips, k, h->clip_base, d_out + g0 * k, s);
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_hamming_scan(a, s);
             }
+            if ((rc = check_launch("hamming_scan"))) return rc;
+            {
+                Timed t(h, K_TOPK, s);
+                if (n_clips >= 16384 && ng <= 64) { // one workgroup per query would crawl through the whole table
+                    if ((rc = ensure(h->d_topk_scratch, hpfw::topk_scratch_bytes(ng, k)))) return rc;
+                    hpfw::launch_topk_two_step(a.best, ng, (int)n_clips, k, h->clip_base, h->d_topk_scratch.get(), d_out + g0 * k, s);
+                } else {
+                    hpfw::launch_topk(a.best, ng, (int)n_clips, k, h->clip_base, d_out + g0 * k, s);
+                }
+            }
+            if ((rc = check_launch("topk"))) return rc;
         }
-        if ((rc = check_launch("topk"))) return rc;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k,
@@ -2296,24 +2214,17 @@ int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
     const int64_t total = q_off[n_q] - q_off[0];
-    uint64_t *d_q = nullptr;
-    hpfw_hit *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_q, (size_t)std::max<int64_t>(total, 1) * 8));
-    if (hipMalloc((void **)&d_out, (size_t)n_q * k * sizeof(hpfw_hit)) != hipSuccess) {
-        (void)hipFree(d_q);
-        return fail(HPFW_E_NOMEM, "hipMalloc failed");
-    }
-    int rc = 0;
+    DevBuf d_q, d_out;
+    HIP_TRY(d_q.alloc((size_t)std::max<int64_t>(total, 1) * 8));
+    if (d_out.alloc((size_t)n_q * k * sizeof(hpfw_hit)) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
     std::vector<int64_t> rel((size_t)n_q + 1);
     for (int64_t i = 0; i <= n_q; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
-    if (total && hipMemcpy(d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) rc = hpfw_gpu_search_topk_device(h, d_q, rel.data(), n_q, k, d_out, nullptr);
+    if (total && hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_search_topk_device(h, d_q.as<uint64_t>(), rel.data(), n_q, k, d_out.as<hpfw_hit>(), nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    if (!rc && hipMemcpy(out, d_out, (size_t)n_q * k * sizeof(hpfw_hit), hipMemcpyDeviceToHost) != hipSuccess)
+    if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_q * k * sizeof(hpfw_hit), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(HPFW_E_HIP, "D2H copy failed");
-    (void)hipFree(d_q);
-    (void)hipFree(d_out);
     return rc;
 }
 
@@ -2335,10 +2246,11 @@ static int combiner_add_impl(hpfw_gpu *h, const uint16_t *hp, const int64_t *off
 {
     if (!h) return fail(HPFW_E_INVALID, "null handle");
     HIP_TRY(hipSetDevice(h->device));
-    Ordered ordered(h, s);
-    std::string why;
-    const int rc = combiner_of(h)->add(hp, dev, offsets, n_rec, s, why);
-    return rc ? fail(rc, why) : 0;
+    return ordered_call(h, s, [&] {
+        std::string why;
+        const int rc = combiner_of(h)->add(hp, dev, offsets, n_rec, s, why);
+        return rc ? fail(rc, why) : 0;
+    });
 }
 
 int hpfw_gpu_combiner_add(hpfw_gpu *h, const uint16_t *hp, const int64_t *offsets, int64_t n_rec)
@@ -2367,10 +2279,11 @@ static int combiner_search_device(hpfw_gpu *h, const uint16_t *d_q, const int64_
 {
     if (!h || !q_off || n_q < 0 || (!d_find && !d_align)) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    Ordered ordered(h, s);
-    std::string why;
-    const int rc = combiner_of(h)->search(d_q, q_off, exclude, n_q, d_find, k, d_align, s, why);
-    return rc ? fail(rc, why) : 0;
+    return ordered_call(h, s, [&] {
+        std::string why;
+        const int rc = combiner_of(h)->search(d_q, q_off, exclude, n_q, d_find, k, d_align, s, why);
+        return rc ? fail(rc, why) : 0;
+    });
 }
 
 // host buffers: queries in, results out, synchronises
@@ -2385,26 +2298,18 @@ static int combiner_search_host(hpfw_gpu *h, const uint16_t *q_hp, const int64_t
     if (total < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
     if (total && !q_hp) return fail(HPFW_E_INVALID, "null queries");
     const size_t out_bytes = find_out ? (size_t)n_q * sizeof(hpfw_combine_result) : (size_t)n_q * k * sizeof(hpfw_align_hit);
-    uint16_t *d_q = nullptr;
-    void *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_q, (size_t)std::max<int64_t>(total, 1) * 2));
-    if (hipMalloc(&d_out, out_bytes) != hipSuccess) {
-        (void)hipFree(d_q);
-        return fail(HPFW_E_NOMEM, "hipMalloc failed");
-    }
-    int rc = 0;
+    DevBuf d_q, d_out;
+    HIP_TRY(d_q.alloc((size_t)std::max<int64_t>(total, 1) * 2));
+    if (d_out.alloc(out_bytes) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
     std::vector<int64_t> rel((size_t)n_q + 1);
     for (int64_t i = 0; i <= n_q; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
-    if (total && hipMemcpy(d_q, q_hp + q_off[0], (size_t)total * 2, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc)
-        rc = combiner_search_device(h, d_q, rel.data(), exclude, n_q, find_out ? (hpfw_combine_result *)d_out : nullptr, k,
-                                    find_out ? nullptr : (hpfw_align_hit *)d_out, nullptr);
+    if (total && hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 2, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = combiner_search_device(h, d_q.as<uint16_t>(), rel.data(), exclude, n_q, find_out ? d_out.as<hpfw_combine_result>() : nullptr, k,
+                                    find_out ? nullptr : d_out.as<hpfw_align_hit>(), nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    if (!rc && hipMemcpy(find_out ? (void *)find_out : (void *)align_out, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!rc && hipMemcpy(find_out ? (void *)find_out : (void *)align_out, d_out.get(), out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(HPFW_E_HIP, "D2H copy failed");
-    (void)hipFree(d_q);
-    (void)hipFree(d_out);
     return rc;
 }
 
@@ -2461,48 +2366,37 @@ int knn_windows_impl(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, in
     if (n_win == 0 || n_max < kVoteWin) return 0;
     // one launch: groups of 32 windows along gridDim.y (at most 65535)
     if (n_win > (int64_t)65535 * 32) return fail(HPFW_E_UNSUPPORTED, "too many query windows in one call (limit 2097120)");
-    int rc;
-    Ordered ordered(h, nullptr);
-    if (h->db_off_dirty) {
-        if ((rc = ensure((void **)&h->d_db_off, &h->db_off_cap, h->db_off.size() * 8))) return rc;
-        HIP_TRY(hipMemcpy(h->d_db_off, h->db_off.data(), h->db_off.size() * 8, hipMemcpyHostToDevice));
-        h->db_off_dirty = false;
-    }
-    const int64_t total = q_off[n_q] - q_off[0];
-    const int kt_pad = hpfw::hamming_mfma_kt_pad(kVoteWin);
-    uint64_t *d_q = nullptr, *d_slots = nullptr;
-    int64_t *d_ws = nullptr;
-    void *d_qa = nullptr;
-    const size_t n_groups = (size_t)(n_win + 31) / 32;
-    if (hipMalloc((void **)&d_q, (size_t)total * 8) != hipSuccess || hipMalloc((void **)&d_ws, (size_t)n_win * 8) != hipSuccess ||
-        hipMalloc((void **)&d_slots, (size_t)n_win * 64) != hipSuccess || hipMalloc(&d_qa, n_groups * kt_pad * 1024) != hipSuccess)
-        rc = fail(HPFW_E_NOMEM, "hipMalloc failed");
-    else
-        rc = 0;
-    if (!rc && (hipMemcpy(d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_ws, w_start.data(), (size_t)n_win * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemset(d_slots, 0xff, (size_t)n_win * 64) != hipSuccess))
-        rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc) {
-        hpfw::launch_expand_windows(d_q, d_ws, (int)n_win, kVoteWin, kt_pad, d_qa, nullptr);
-        hpfw::launch_knn_windows(h->d_db, h->d_db_off, (int)n_clips, (int)(n_max - kVoteWin + 1), d_qa, kt_pad, (int)n_win,
-                                 kVoteWin, kVoteNn, d_slots, nullptr);
-        rc = check_launch("knn_windows");
-    }
-    std::vector<uint64_t> slots((size_t)n_win * 8);
-    if (!rc && hipMemcpy(slots.data(), d_slots, slots.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "kernel execution failed");
-    if (d_q) (void)hipFree(d_q);
-    if (d_ws) (void)hipFree(d_ws);
-    if (d_slots) (void)hipFree(d_slots);
-    if (d_qa) (void)hipFree(d_qa);
-    if (rc) return rc;
-    for (int64_t w = 0; w < n_win; ++w) { // the device keeps the 5 smallest keys unsorted
-        uint64_t *s5 = &slots[(size_t)w * 8];
-        std::sort(s5, s5 + kVoteNn);
-        for (int r = 0; r < kVoteNn; ++r) keys[(size_t)w * kVoteNn + r] = s5[r];
-    }
-    return 0;
+    return ordered_call(h, nullptr, [&] {
+        if (h->db_off_dirty) {
+            if (int rc = ensure(h->d_db_off, h->db_off.size() * 8)) return rc;
+            HIP_TRY(hipMemcpy(h->d_db_off.get(), h->db_off.data(), h->db_off.size() * 8, hipMemcpyHostToDevice));
+            h->db_off_dirty = false;
+        }
+        const int64_t total = q_off[n_q] - q_off[0];
+        const int kt_pad = hpfw::hamming_mfma_kt_pad(kVoteWin);
+        const size_t n_groups = (size_t)(n_win + 31) / 32;
+        DevBuf d_q, d_ws, d_slots, d_qa;
+        if (d_q.alloc((size_t)total * 8) != hipSuccess || d_ws.alloc((size_t)n_win * 8) != hipSuccess ||
+            d_slots.alloc((size_t)n_win * 64) != hipSuccess || d_qa.alloc(n_groups * kt_pad * 1024) != hipSuccess)
+            return fail(HPFW_E_NOMEM, "hipMalloc failed");
+        if (hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_ws.get(), w_start.data(), (size_t)n_win * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(d_slots.get(), 0xff, (size_t)n_win * 64) != hipSuccess)
+            return fail(HPFW_E_HIP, "H2D copy failed");
+        hpfw::launch_expand_windows(d_q.as<uint64_t>(), d_ws.as<int64_t>(), (int)n_win, kVoteWin, kt_pad, d_qa.get(), nullptr);
+        hpfw::launch_knn_windows(h->d_db.as<uint64_t>(), h->d_db_off.as<int64_t>(), (int)n_clips, (int)(n_max - kVoteWin + 1), d_qa.get(),
+                                 kt_pad, (int)n_win, kVoteWin, kVoteNn, d_slots.as<uint64_t>(), nullptr);
+        if (int rc = check_launch("knn_windows")) return rc;
+        std::vector<uint64_t> slots((size_t)n_win * 8);
+        if (hipMemcpy(slots.data(), d_slots.get(), slots.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(HPFW_E_HIP, "kernel execution failed");
+        for (int64_t w = 0; w < n_win; ++w) { // the device keeps the 5 smallest keys unsorted
+            uint64_t *s5 = &slots[(size_t)w * 8];
+            std::sort(s5, s5 + kVoteNn);
+            for (int r = 0; r < kVoteNn; ++r) keys[(size_t)w * kVoteNn + r] = s5[r];
+        }
+        return 0;
+    });
 }
 } // namespace
 
@@ -2579,16 +2473,16 @@ int hpfw_gpu_merge_topk(const hpfw_hit *in, int n_shards, int64_t n_q, int k, hp
 int hpfw_gpu_timer_start(hpfw_gpu *h, void *stream)
 {
     if (!h) return fail(HPFW_E_INVALID, "null handle");
-    HIP_TRY(hipEventRecord(h->ev0, (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(h->ev0.get(), (hipStream_t)stream));
     return 0;
 }
 
 int hpfw_gpu_timer_stop(hpfw_gpu *h, void *stream, float *ms)
 {
     if (!h || !ms) return fail(HPFW_E_INVALID, "null argument");
-    HIP_TRY(hipEventRecord(h->ev1, (hipStream_t)stream));
-    HIP_TRY(hipEventSynchronize(h->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
+    HIP_TRY(hipEventRecord(h->ev1.get(), (hipStream_t)stream));
+    HIP_TRY(hipEventSynchronize(h->ev1.get()));
+    HIP_TRY(hipEventElapsedTime(ms, h->ev0.get(), h->ev1.get()));
     return 0;
 }
 
@@ -2596,7 +2490,7 @@ int hpfw_gpu_set_kernel_timing(hpfw_gpu *h, int mask)
 {
     if (!h) return fail(HPFW_E_INVALID, "null handle");
     h->timing_mask = (unsigned)mask;
-    for (auto &t : h->timed) h->ev_pool.push_back({t.a, t.b});
+    for (TimedLaunch &t : h->timed) h->ev_pool.emplace_back(std::move(t.a), std::move(t.b));
     h->timed.clear();
     std::memset(h->k_ms, 0, sizeof(h->k_ms));
     std::memset(h->k_launches, 0, sizeof(h->k_launches));
@@ -2606,14 +2500,14 @@ int hpfw_gpu_set_kernel_timing(hpfw_gpu *h, int mask)
 int hpfw_gpu_get_kernel_timing(hpfw_gpu *h, const char **names, float *ms, int *launches, int *n)
 {
     if (!h || !names || !ms || !launches || !n) return fail(HPFW_E_INVALID, "null argument");
-    for (auto &t : h->timed) {
-        HIP_TRY(hipEventSynchronize(t.b));
+    for (const TimedLaunch &t : h->timed) {
+        HIP_TRY(hipEventSynchronize(t.b.get()));
         float e = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&e, t.a, t.b));
+        HIP_TRY(hipEventElapsedTime(&e, t.a.get(), t.b.get()));
         h->k_ms[t.kind] += e;
         h->k_launches[t.kind] += 1;
-        h->ev_pool.push_back({t.a, t.b});
     }
+    for (TimedLaunch &t : h->timed) h->ev_pool.emplace_back(std::move(t.a), std::move(t.b));
     h->timed.clear();
     const int cap = *n;
     int w = 0;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/hpfw_gpu.h"
+#include "hip_owned.h"
 
 namespace hpfw {
 
@@ -17,7 +18,6 @@ public:
     Combiner() = default;
     Combiner(const Combiner &) = delete;
     Combiner &operator=(const Combiner &) = delete;
-    ~Combiner();
 
     void clear();
     int64_t size() const { return (int64_t)rec_off_.size() - 1; }
@@ -29,22 +29,17 @@ public:
                int k, hpfw_align_hit *d_align, hipStream_t s, std::string &err);
 
 private:
-    struct Buf {
-        void *p = nullptr;
-        size_t cap = 0;
-    };
-    hipError_t grow(Buf &b, size_t bytes);
     int rebuild(hipStream_t s, std::string &err);
 
     std::vector<int64_t> rec_off_{0}; // recording j is positions [rec_off_[j], rec_off_[j+1])
     bool stale_ = false; // the device tables do not describe rec_off_ (a rebuild failed part-way)
-    Buf hp_;         // uint16 [positions]: every recording's hashprints back to back
-    Buf rec_off_d_;  // uint32 [n_rec + 1]
-    Buf val_start_;  // uint32 [65537]
-    Buf post_;       // uint2 (rec, off) [positions], ascending position inside every value
-    Buf sort_keys_, sort_vals_, sort_vals_out_, temp_; // build and search scratch
+    DevBuf hp_;         // uint16 [positions]: every recording's hashprints back to back
+    DevBuf rec_off_d_;  // uint32 [n_rec + 1]
+    DevBuf val_start_;  // uint32 [65537]
+    DevBuf post_;       // uint2 (rec, off) [positions], ascending position inside every value
+    DevBuf sort_keys_, sort_vals_, sort_vals_out_, temp_; // build and search scratch
     // search scratch
-    Buf q_tab_, fr_len_, fr_tab_, ev_keys_, ev_keys_s_, ev_vals_, ev_vals_s_, ev_rec_, ev_cnt_, bins_, peaks_;
+    DevBuf q_tab_, fr_len_, fr_tab_, ev_keys_, ev_keys_s_, ev_vals_, ev_vals_s_, ev_rec_, ev_cnt_, bins_, peaks_;
 };
 
 } // namespace hpfw

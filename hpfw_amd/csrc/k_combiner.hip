@@ -341,30 +341,10 @@ constexpr int64_t kMaxHashprints = 0x7fffffff; // the index sort takes an int it
 constexpr int64_t kMinChunk = (int64_t)1 << 16;
 constexpr int64_t kMaxBatch = 1024;         // queries per pass (bounds the peak table: kMaxBatch x n_rec)
 
+// a scratch buffer of at least `bytes` (256 at least: never a null one, which hipcub takes for a size query)
+hipError_t grow(DevBuf &b, size_t bytes) { return b.ensure(std::max<size_t>(bytes, 256)); }
+
 } // namespace
-
-Combiner::~Combiner()
-{
-    for (Buf *b : {&hp_, &rec_off_d_, &val_start_, &post_, &sort_keys_, &sort_vals_, &sort_vals_out_, &temp_, &q_tab_, &fr_len_,
-                   &fr_tab_, &ev_keys_, &ev_keys_s_, &ev_vals_, &ev_vals_s_, &ev_rec_, &ev_cnt_, &bins_, &peaks_})
-        if (b->p) (void)hipFree(b->p);
-}
-
-hipError_t Combiner::grow(Buf &b, size_t bytes)
-{
-    bytes = std::max<size_t>(bytes, 256);
-    if (b.cap >= bytes) return hipSuccess;
-    if (b.p) {
-        hipError_t e = hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        if (e != hipSuccess) return e;
-    }
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.cap = bytes;
-    else b.p = nullptr;
-    return e;
-}
 
 void Combiner::clear() { rec_off_.assign(1, 0); } // (the device tables are rebuilt by the next add)
 
@@ -385,22 +365,15 @@ int Combiner::add(const uint16_t *hp, bool device, const int64_t *offsets, int64
         err = "combiner index: more than 2^31 - 1 hashprints";
         return HPFW_E_INVALID;
     }
-    if ((size_t)(have + add) * 2 > hp_.cap) { // grow by doubling, keeping what is there
-        const size_t ncap = std::max<size_t>((size_t)(have + add) * 2, hp_.cap * 2);
-        void *nd = nullptr;
-        CB_TRY(hipMalloc(&nd, ncap));
+    if ((size_t)(have + add) * 2 > hp_.capacity()) { // grow by doubling, keeping what is there
+        DevBuf nd;
+        CB_TRY(nd.alloc(std::max<size_t>((size_t)(have + add) * 2, hp_.capacity() * 2)));
         hipError_t e = hipStreamSynchronize(s);
-        if (e == hipSuccess && have) e = hipMemcpy(nd, hp_.p, (size_t)have * 2, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(nd);
-            return hip_fail(e, "growing the combiner index", err);
-        }
-        void *old = hp_.p;
-        hp_.p = nd;
-        hp_.cap = ncap;
-        if (old) CB_TRY(hipFree(old));
+        if (e == hipSuccess && have) e = hipMemcpy(nd.get(), hp_.get(), (size_t)have * 2, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) return hip_fail(e, "growing the combiner index", err);
+        hp_ = std::move(nd); // (the old buffer goes with nd)
     }
-    uint16_t *dst = (uint16_t *)hp_.p + have;
+    uint16_t *dst = (uint16_t *)hp_.get() + have;
     if (add) {
         if (device) CB_TRY(hipMemcpyAsync(dst, hp + offsets[0], (size_t)add * 2, hipMemcpyDeviceToDevice, s));
         else CB_TRY(hipMemcpy(dst, hp + offsets[0], (size_t)add * 2, hipMemcpyHostToDevice));
@@ -423,22 +396,22 @@ int Combiner::rebuild(hipStream_t s, std::string &err)
     CB_TRY(grow(sort_keys_, (size_t)n * 2));
     CB_TRY(grow(sort_vals_, (size_t)n * 4));
     CB_TRY(grow(sort_vals_out_, (size_t)n * 4));
-    CB_TRY(hipMemcpyAsync(rec_off_d_.p, ro.data(), ro.size() * 4, hipMemcpyHostToDevice, s));
+    CB_TRY(hipMemcpyAsync(rec_off_d_.get(), ro.data(), ro.size() * 4, hipMemcpyHostToDevice, s));
     size_t tb = 0;
-    CB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint16_t *)hp_.p, (uint16_t *)sort_keys_.p,
-                                              (const uint32_t *)sort_vals_.p, (uint32_t *)sort_vals_out_.p, (int)n, 0, 16, s));
+    CB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint16_t *)hp_.get(), (uint16_t *)sort_keys_.get(),
+                                              (const uint32_t *)sort_vals_.get(), (uint32_t *)sort_vals_out_.get(), (int)n, 0, 16, s));
     CB_TRY(grow(temp_, tb));
     if (n) {
-        iota_kernel<<<grid_of(n), kThreads, 0, s>>>((uint32_t *)sort_vals_.p, n);
+        iota_kernel<<<grid_of(n), kThreads, 0, s>>>((uint32_t *)sort_vals_.get(), n);
         CB_LAUNCH("combiner iota");
-        tb = temp_.cap;
-        CB_TRY(hipcub::DeviceRadixSort::SortPairs(temp_.p, tb, (const uint16_t *)hp_.p, (uint16_t *)sort_keys_.p,
-                                                  (const uint32_t *)sort_vals_.p, (uint32_t *)sort_vals_out_.p, (int)n, 0, 16, s));
-        postings_kernel<<<grid_of(n), kThreads, 0, s>>>((const uint32_t *)sort_vals_out_.p, n, (const uint32_t *)rec_off_d_.p,
-                                                        n_rec, (uint2 *)post_.p);
+        tb = temp_.capacity();
+        CB_TRY(hipcub::DeviceRadixSort::SortPairs(temp_.get(), tb, (const uint16_t *)hp_.get(), (uint16_t *)sort_keys_.get(),
+                                                  (const uint32_t *)sort_vals_.get(), (uint32_t *)sort_vals_out_.get(), (int)n, 0, 16, s));
+        postings_kernel<<<grid_of(n), kThreads, 0, s>>>((const uint32_t *)sort_vals_out_.get(), n, (const uint32_t *)rec_off_d_.get(),
+                                                        n_rec, (uint2 *)post_.get());
         CB_LAUNCH("combiner postings");
     }
-    val_start_kernel<<<grid_of(65537), kThreads, 0, s>>>((const uint16_t *)sort_keys_.p, n, (uint32_t *)val_start_.p);
+    val_start_kernel<<<grid_of(65537), kThreads, 0, s>>>((const uint16_t *)sort_keys_.get(), n, (uint32_t *)val_start_.get());
     CB_LAUNCH("combiner val_start");
     // the host vector ro dies here: the copy above must have left it
     CB_TRY(hipStreamSynchronize(s));
@@ -454,7 +427,7 @@ int Combiner::get(int64_t *val_start, uint32_t *rec, uint32_t *off, int64_t cap,
         return HPFW_E_INVALID;
     }
     CB_TRY(hipDeviceSynchronize());
-    if (!val_start_.p || n == 0) { // nothing added since the last clear (the device tables are those of before)
+    if (!val_start_.get() || n == 0) { // nothing added since the last clear (the device tables are those of before)
         std::fill(val_start, val_start + 65537, 0);
         return 0;
     }
@@ -463,11 +436,11 @@ int Combiner::get(int64_t *val_start, uint32_t *rec, uint32_t *off, int64_t cap,
         if (rc) return rc;
     }
     std::vector<uint32_t> vs(65537);
-    CB_TRY(hipMemcpy(vs.data(), val_start_.p, 65537 * 4, hipMemcpyDeviceToHost));
+    CB_TRY(hipMemcpy(vs.data(), val_start_.get(), 65537 * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < 65537; ++i) val_start[i] = vs[(size_t)i];
     if ((rec || off) && n) {
         std::vector<uint32_t> p((size_t)n * 2);
-        CB_TRY(hipMemcpy(p.data(), post_.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+        CB_TRY(hipMemcpy(p.data(), post_.get(), (size_t)n * 8, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) {
             if (rec) rec[i] = p[(size_t)i * 2];
             if (off) off[i] = p[(size_t)i * 2 + 1];
@@ -544,18 +517,18 @@ int Combiner::search(const uint16_t *d_q, const int64_t *q_off, const int32_t *e
         CB_TRY(grow(fr_len_, (size_t)(nf + 1) * 8 * 2)); // lengths, then their exclusive scan
         CB_TRY(grow(fr_tab_, (size_t)std::max<int64_t>(nf, 1) * sizeof(FrameTab)));
         CB_TRY(grow(bins_, (size_t)std::max<uint64_t>(bins, 1) * 4));
-        CB_TRY(hipMemcpyAsync(q_tab_.p, qt.data(), qt.size() * sizeof(QueryTab), hipMemcpyHostToDevice, s));
-        CB_TRY(hipMemsetAsync(bins_.p, 0, (size_t)std::max<uint64_t>(bins, 1) * 4, s));
-        const QueryTab *d_qt = (const QueryTab *)q_tab_.p;
-        int64_t *len = (int64_t *)fr_len_.p, *ev_start = len + nf + 1;
-        frames_kernel<<<grid_of(nf + 1), kThreads, 0, s>>>(d_q, d_qt, nq, nf, (const uint32_t *)val_start_.p, (const uint2 *)post_.p,
-                                                           (FrameTab *)fr_tab_.p, len);
+        CB_TRY(hipMemcpyAsync(q_tab_.get(), qt.data(), qt.size() * sizeof(QueryTab), hipMemcpyHostToDevice, s));
+        CB_TRY(hipMemsetAsync(bins_.get(), 0, (size_t)std::max<uint64_t>(bins, 1) * 4, s));
+        const QueryTab *d_qt = (const QueryTab *)q_tab_.get();
+        int64_t *len = (int64_t *)fr_len_.get(), *ev_start = len + nf + 1;
+        frames_kernel<<<grid_of(nf + 1), kThreads, 0, s>>>(d_q, d_qt, nq, nf, (const uint32_t *)val_start_.get(), (const uint2 *)post_.get(),
+                                                           (FrameTab *)fr_tab_.get(), len);
         CB_LAUNCH("combiner frames");
         size_t tb = 0;
         CB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len, ev_start, nf + 1, s));
         CB_TRY(grow(temp_, tb));
-        tb = temp_.cap;
-        CB_TRY(hipcub::DeviceScan::ExclusiveSum(temp_.p, tb, len, ev_start, nf + 1, s));
+        tb = temp_.capacity();
+        CB_TRY(hipcub::DeviceScan::ExclusiveSum(temp_.get(), tb, len, ev_start, nf + 1, s));
         int64_t n_ev = 0;
         CB_TRY(hipMemcpyAsync(&n_ev, ev_start + nf, 8, hipMemcpyDeviceToHost, s));
         CB_TRY(hipStreamSynchronize(s));
@@ -571,34 +544,34 @@ int Combiner::search(const uint16_t *d_q, const int64_t *q_off, const int32_t *e
         CB_TRY(grow(ev_cnt_, (size_t)ec * 4));
         const int kb = bits_for(std::max<uint64_t>(bins, 1));
         tb = 0;
-        CB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)ev_keys_.p, (uint32_t *)ev_keys_s_.p,
-                                                  (const uint32_t *)ev_vals_.p, (uint32_t *)ev_vals_s_.p, (int)ec, 0, kb, s));
+        CB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)ev_keys_.get(), (uint32_t *)ev_keys_s_.get(),
+                                                  (const uint32_t *)ev_vals_.get(), (uint32_t *)ev_vals_s_.get(), (int)ec, 0, kb, s));
         CB_TRY(grow(temp_, tb));
-        uint32_t *keys = (uint32_t *)ev_keys_.p, *keys_s = (uint32_t *)ev_keys_s_.p, *vals = (uint32_t *)ev_vals_.p,
-                 *vals_s = (uint32_t *)ev_vals_s_.p, *cnt = (uint32_t *)ev_cnt_.p, *bin = (uint32_t *)bins_.p;
-        const uint32_t *rof = (const uint32_t *)rec_off_d_.p;
+        uint32_t *keys = (uint32_t *)ev_keys_.get(), *keys_s = (uint32_t *)ev_keys_s_.get(), *vals = (uint32_t *)ev_vals_.get(),
+                 *vals_s = (uint32_t *)ev_vals_s_.get(), *cnt = (uint32_t *)ev_cnt_.get(), *bin = (uint32_t *)bins_.get();
+        const uint32_t *rof = (const uint32_t *)rec_off_d_.get();
         for (int64_t e0 = 0; e0 < n_ev; e0 += chunk) {
             const int64_t m = std::min(chunk, n_ev - e0);
-            events_kernel<<<grid_of(m), kThreads, 0, s>>>(ev_start, nf, (const FrameTab *)fr_tab_.p, d_qt, (const uint2 *)post_.p, rof,
-                                                          e0, m, keys, (uint32_t *)ev_rec_.p, vals);
+            events_kernel<<<grid_of(m), kThreads, 0, s>>>(ev_start, nf, (const FrameTab *)fr_tab_.get(), d_qt, (const uint2 *)post_.get(), rof,
+                                                          e0, m, keys, (uint32_t *)ev_rec_.get(), vals);
             CB_LAUNCH("combiner events");
-            tb = temp_.cap;
-            CB_TRY(hipcub::DeviceRadixSort::SortPairs(temp_.p, tb, (const uint32_t *)keys, keys_s, (const uint32_t *)vals, vals_s,
+            tb = temp_.capacity();
+            CB_TRY(hipcub::DeviceRadixSort::SortPairs(temp_.get(), tb, (const uint32_t *)keys, keys_s, (const uint32_t *)vals, vals_s,
                                                       (int)m, 0, kb, s));
             counts_kernel<<<grid_of(m), kThreads, 0, s>>>(keys_s, vals_s, m, bin, cnt);
             CB_LAUNCH("combiner counts");
             carry_kernel<<<grid_of(m), kThreads, 0, s>>>(keys_s, vals_s, m, cnt, bin);
             CB_LAUNCH("combiner carry");
             if (d_find) {
-                rule_kernel<<<nq, 64, 0, s>>>(ev_start, d_qt, keys, (const uint32_t *)ev_rec_.p, cnt, e0, m, rof, d_find);
+                rule_kernel<<<nq, 64, 0, s>>>(ev_start, d_qt, keys, (const uint32_t *)ev_rec_.get(), cnt, e0, m, rof, d_find);
                 CB_LAUNCH("combiner rule");
             }
         }
         if (d_align && n_rec > 0) {
             CB_TRY(grow(peaks_, (size_t)nq * n_rec * 8));
-            peaks_kernel<<<(unsigned)(nq * n_rec), kThreads, 0, s>>>(d_qt, bin, rof, n_rec, (uint64_t *)peaks_.p);
+            peaks_kernel<<<(unsigned)(nq * n_rec), kThreads, 0, s>>>(d_qt, bin, rof, n_rec, (uint64_t *)peaks_.get());
             CB_LAUNCH("combiner peaks");
-            align_topk_kernel<<<nq, kThreads, 0, s>>>(d_qt, (const uint64_t *)peaks_.p, rof, n_rec, k, d_align);
+            align_topk_kernel<<<nq, kThreads, 0, s>>>(d_qt, (const uint64_t *)peaks_.get(), rof, n_rec, k, d_align);
             CB_LAUNCH("combiner align_topk");
         }
         // the next batch reuses the tables uploaded from host vectors above

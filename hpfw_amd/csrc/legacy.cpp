@@ -32,6 +32,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/hpfw_gpu.h"
+#include "hip_owned.h"
 #include "legacy_internal.h" // the extern "C" signatures multi.cpp sees, checked against the definitions below
 
 extern "C" void hpfw_internal_set_error(const char *msg); // api.hip: feeds hpfw_gpu_last_error()
@@ -186,34 +187,19 @@ struct hpfw_legacy_collector {
     // two pinned host arenas in turn: the files of the next window are read while this one is copied and extracted
     // (spare_db: the spectrogram buffer of the last group that was not kept, for the next one -- freeing and allocating
     // hundreds of MB of device memory per window stalls the reader threads, who share the address space)
-    void *spare_db = nullptr;
-    size_t spare_db_cap = 0;
+    hpfw::DevBuf spare_db;
     // hashprints of a whole window when nothing is learned or cached (calc_hashprints): device buffer and pinned host copy
-    void *d_hp_win = nullptr, *h_hp_win = nullptr;
-    size_t hp_win_cap = 0;
+    hpfw::DevBuf d_hp_win;
+    hpfw::HostBuf h_hp_win;
     // ... on a stream of the collector's own (non-blocking): the tables of the next file's length are generated and
     // uploaded through the default stream while the kernels of the previous file run
-    hipStream_t win_stream = nullptr;
+    hpfw::Stream win_stream;
     // pinned host copy of a group's spectrograms on their way to cache/spectros/ (grow-only)
-    void *h_spec = nullptr;
-    size_t h_spec_cap = 0;
-    void *arena[2] = {nullptr, nullptr};
-    size_t arena_cap[2] = {0, 0};
+    hpfw::HostBuf h_spec;
+    hpfw::HostBuf arena[2];
     // ... and two device copies in turn: window w + 1 is uploaded while the kernels of window w read theirs
-    void *d_arena_buf[2] = {nullptr, nullptr}, *d_arena = nullptr; // d_arena: the copy of the window in hand
-    size_t d_arena_cap[2] = {0, 0};
-    ~hpfw_legacy_collector()
-    {
-        for (void *a : arena)
-            if (a) (void)hipHostFree(a);
-        for (void *a : d_arena_buf)
-            if (a) (void)hipFree(a);
-        if (spare_db) (void)hipFree(spare_db);
-        if (win_stream) (void)hipStreamDestroy(win_stream);
-        if (h_spec) (void)hipHostFree(h_spec);
-        if (d_hp_win) (void)hipFree(d_hp_win);
-        if (h_hp_win) (void)hipHostFree(h_hp_win);
-    }
+    hpfw::DevBuf d_arena_buf[2];
+    void *d_arena = nullptr; // the copy of the window in hand
 };
 
 // the exported entry points: no exception leaves the C boundary (the reference's wrapper.cpp has no such
@@ -498,19 +484,11 @@ size_t read_window(hpfw_legacy_collector *c, int slot, const char **filenames, c
             bytes += (size_t)kv.first * 2;
         }
     }
-    if (bytes > c->arena_cap[slot]) {
-        if (c->arena[slot]) (void)hipHostFree(c->arena[slot]);
-        c->arena[slot] = nullptr;
-        c->arena_cap[slot] = 0;
-        const size_t want = std::max(bytes + bytes / 4, (size_t)64 << 20);
-        if (hipHostMalloc(&c->arena[slot], want, hipHostMallocDefault) != hipSuccess) {
-            c->arena[slot] = nullptr;
-            first_why = "prepare: out of pinned host memory";
-            for (WavProbe &w : probes)
-                if (w.fd >= 0) ::close(w.fd);
-            return 0;
-        }
-        c->arena_cap[slot] = want;
+    if (bytes > c->arena[slot].capacity() && c->arena[slot].alloc(std::max(bytes + bytes / 4, (size_t)64 << 20)) != hipSuccess) {
+        first_why = "prepare: out of pinned host memory";
+        for (WavProbe &w : probes)
+            if (w.fd >= 0) ::close(w.fd);
+        return 0;
     }
     run([&](int i) {
         WavProbe &w = probes[(size_t)i];
@@ -518,7 +496,7 @@ size_t read_window(hpfw_legacy_collector *c, int slot, const char **filenames, c
             if (w.fd >= 0) ::close(w.fd);
             return;
         }
-        int16_t *dst = reinterpret_cast<int16_t *>(static_cast<char *>(c->arena[slot]) + out[(size_t)i].arena_off);
+        int16_t *dst = reinterpret_cast<int16_t *>(c->arena[slot].as<char>() + out[(size_t)i].arena_off);
         bool ok = true;
         try {
             if (w.channels == 1) {
@@ -559,91 +537,51 @@ size_t read_window(hpfw_legacy_collector *c, int slot, const char **filenames, c
     return bytes; // (skipped files, parallel_collector.h:101-103: first_why holds the message)
 }
 
-struct DevMem {
-    void *p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem &) = delete;
-    DevMem &operator=(const DevMem &) = delete;
-    ~DevMem()
-    {
-        if (p) (void)hipFree(p);
-    }
-    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-};
-
 // the window's clips on the device: one copy of the arena (its layout is kept)
 bool upload_window(hpfw_legacy_collector *c, int slot, size_t bytes)
 {
-    if (bytes > c->d_arena_cap[slot]) {
-        if (c->d_arena_buf[slot]) (void)hipFree(c->d_arena_buf[slot]);
-        c->d_arena_buf[slot] = nullptr;
-        c->d_arena_cap[slot] = 0;
-        const size_t want = std::max(bytes + bytes / 4, (size_t)64 << 20);
-        if (hipMalloc(&c->d_arena_buf[slot], want) != hipSuccess) {
-            c->d_arena_buf[slot] = nullptr;
-            hpfw_internal_set_error("prepare: out of device memory");
-            return false;
-        }
-        c->d_arena_cap[slot] = want;
+    if (bytes > c->d_arena_buf[slot].capacity() && c->d_arena_buf[slot].alloc(std::max(bytes + bytes / 4, (size_t)64 << 20)) != hipSuccess) {
+        hpfw_internal_set_error("prepare: out of device memory");
+        return false;
     }
-    c->d_arena = c->d_arena_buf[slot];
-    return bytes == 0 || hipMemcpy(c->d_arena, c->arena[slot], bytes, hipMemcpyHostToDevice) == hipSuccess;
+    c->d_arena = c->d_arena_buf[slot].get();
+    return bytes == 0 || hipMemcpy(c->d_arena, c->arena[slot].get(), bytes, hipMemcpyHostToDevice) == hipSuccess;
 }
 
-// dB spectrograms [n][121][C] of n equally long clips of the window (device memory, caller frees); the clips lie side by
-// side in the device copy of the arena, the first at `first_off`
-// (the buffer comes from release_spectrograms' spare when that is large enough; *cap = its size)
-float *group_spectrograms(hpfw_legacy_collector *c, size_t first_off, size_t n, int64_t len, const hpfw_geometry &g, size_t *cap)
+// dB spectrograms [n][121][C] of n equally long clips of the window into d_db (empty on entry), which is
+// release_spectrograms' spare when that is large enough; the clips lie side by side in the device copy of the arena, the
+// first at `first_off`
+bool group_spectrograms(hpfw_legacy_collector *c, size_t first_off, size_t n, int64_t len, const hpfw_geometry &g, hpfw::DevBuf &d_db)
 {
-    float *d_db = nullptr;
     const size_t need = n * (size_t)121 * g.c * 4;
-    if (c->spare_db && c->spare_db_cap >= need) {
-        d_db = static_cast<float *>(c->spare_db);
-        *cap = c->spare_db_cap;
-        c->spare_db = nullptr;
-        c->spare_db_cap = 0;
-    } else if (hipMalloc((void **)&d_db, need) != hipSuccess) {
+    if (c->spare_db.capacity() >= need) {
+        d_db = std::move(c->spare_db);
+    } else if (d_db.alloc(need) != hipSuccess) {
         hpfw_internal_set_error("prepare: out of device memory");
-        return nullptr;
-    } else {
-        *cap = need;
+        return false;
     }
     const int16_t *d_pcm = reinterpret_cast<const int16_t *>(static_cast<const char *>(c->d_arena) + first_off);
     // (no synchronisation: what follows runs on the default stream too, and the copies to the host wait for it)
-    if (hpfw_gpu_stage_spectrogram(c->gpu, d_pcm, len, (int64_t)n, d_db, nullptr) != 0) {
-        (void)hipFree(d_db);
-        return nullptr;
-    }
-    return d_db;
+    return hpfw_gpu_stage_spectrogram(c->gpu, d_pcm, len, (int64_t)n, d_db.as<float>(), nullptr) == 0;
 }
 
 // a group's spectrogram buffer is done with: the larger of it and the spare stays for the next group
-void release_spectrograms(hpfw_legacy_collector *c, float *d_db, size_t cap)
+void release_spectrograms(hpfw_legacy_collector *c, hpfw::DevBuf d_db)
 {
-    if (cap > c->spare_db_cap) {
-        if (c->spare_db) (void)hipFree(c->spare_db);
-        c->spare_db = d_db;
-        c->spare_db_cap = cap;
-    } else {
-        (void)hipFree(d_db);
-    }
+    if (d_db.capacity() > c->spare_db.capacity()) c->spare_db = std::move(d_db);
 }
 
 // hashprints of n clips from their dB spectrograms: out[k] = new uint64_t[g.n_hp]
 // the collector's hashprint buffers (device, and pinned on the host) hold at least `bytes`
 bool ensure_hp_buffers(hpfw_legacy_collector *c, size_t bytes)
 {
-    if (bytes <= c->hp_win_cap) return true;
-    if (c->d_hp_win) (void)hipFree(c->d_hp_win);
-    if (c->h_hp_win) (void)hipHostFree(c->h_hp_win);
-    c->d_hp_win = c->h_hp_win = nullptr;
-    c->hp_win_cap = 0;
+    if (bytes <= c->d_hp_win.capacity() && bytes <= c->h_hp_win.capacity()) return true;
+    c->h_hp_win.reset(); // (both go before either is made again)
     const size_t want = std::max(bytes + bytes / 4, (size_t)8 << 20);
-    if (hipMalloc(&c->d_hp_win, want) != hipSuccess || hipHostMalloc(&c->h_hp_win, want, hipHostMallocDefault) != hipSuccess) {
+    if (c->d_hp_win.alloc(want) != hipSuccess || c->h_hp_win.alloc(want) != hipSuccess) {
         hpfw_internal_set_error("prepare: out of memory for the hashprints");
         return false;
     }
-    c->hp_win_cap = want;
     return true;
 }
 
@@ -652,14 +590,14 @@ bool group_hashprints(hpfw_legacy_collector *c, const float *d_db, size_t n, con
 {
     const size_t bytes = n * (size_t)g.n_hp * 8;
     if (!ensure_hp_buffers(c, bytes)) return false;
-    if (hpfw_gpu_hashprints_from_db(c->gpu, d_db, (int64_t)n, g.c, (uint64_t *)c->d_hp_win, nullptr) != 0) return false;
-    if (hipMemcpy(c->h_hp_win, c->d_hp_win, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (hpfw_gpu_hashprints_from_db(c->gpu, d_db, (int64_t)n, g.c, c->d_hp_win.as<uint64_t>(), nullptr) != 0) return false;
+    if (hipMemcpy(c->h_hp_win.get(), c->d_hp_win.get(), bytes, hipMemcpyDeviceToHost) != hipSuccess) {
         hpfw_internal_set_error("prepare: D2H copy failed");
         return false;
     }
     for (size_t k = 0; k < n; ++k) {
         out[k] = new uint64_t[(size_t)g.n_hp];
-        std::memcpy(out[k], static_cast<const uint64_t *>(c->h_hp_win) + k * (size_t)g.n_hp, (size_t)g.n_hp * 8);
+        std::memcpy(out[k], c->h_hp_win.as<const uint64_t>() + k * (size_t)g.n_hp, (size_t)g.n_hp * 8);
     }
     return true;
 }
@@ -667,7 +605,7 @@ bool group_hashprints(hpfw_legacy_collector *c, const float *d_db, size_t n, con
 struct KeptGroup {
     std::vector<int> files; // indices into the caller's list
     hpfw_geometry g;
-    float *d_db;
+    hpfw::DevBuf d_db;
 };
 
 } // namespace
@@ -753,7 +691,7 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
     auto finish = [&]() { // the results of the window whose kernels are in flight
         if (!pend.active) return;
         pend.active = false;
-        if (c->win_stream && hipStreamSynchronize(c->win_stream) != hipSuccess) {
+        if (c->win_stream && hipStreamSynchronize(c->win_stream.get()) != hipSuccess) {
             hpfw_internal_set_error("prepare: the window's kernels failed");
             pend.ok = false;
         } else if (c->win_stream) {
@@ -767,7 +705,7 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
             for (size_t q = 0; q < pt.pos.size(); ++q) {
                 const int id = files[pend.at + (size_t)pt.pos[q]];
                 uint64_t *out = new uint64_t[(size_t)pt.g.n_hp];
-                std::memcpy(out, static_cast<const uint64_t *>(c->h_hp_win) + pt.off + q * (size_t)pt.g.n_hp, (size_t)pt.g.n_hp * 8);
+                std::memcpy(out, c->h_hp_win.as<const uint64_t>() + pt.off + q * (size_t)pt.g.n_hp, (size_t)pt.g.n_hp * 8);
                 job.hp[(size_t)id] = out;
                 job.hp_size[(size_t)id] = (int)pt.g.n_hp;
             }
@@ -828,8 +766,7 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
             const size_t total = pend.total;
             bool ok = true;
             if (!ensure_hp_buffers(c, total * 8)) ok = false;
-            if (ok && !c->win_stream && hipStreamCreateWithFlags(&c->win_stream, hipStreamNonBlocking) != hipSuccess) {
-                c->win_stream = nullptr;
+            if (ok && !c->win_stream && c->win_stream.create() != hipSuccess) {
                 hpfw_internal_set_error("prepare: no stream");
                 ok = false;
             }
@@ -838,9 +775,9 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
                 Part &pt = pend.parts[k];
                 const int16_t *d_pcm = reinterpret_cast<const int16_t *>(static_cast<const char *>(c->d_arena) + clips[(size_t)pt.pos[0]].arena_off);
                 pt.done = hpfw_gpu_extract_pcm16(c->gpu, d_pcm, clips[(size_t)pt.pos[0]].n, (int64_t)pt.pos.size(),
-                                                 static_cast<uint64_t *>(c->d_hp_win) + pt.off, c->win_stream) == 0; // a failed group is skipped
+                                                 c->d_hp_win.as<uint64_t>() + pt.off, c->win_stream.get()) == 0; // a failed group is skipped
             }
-            if (ok && total > 0 && hipMemcpyAsync(c->h_hp_win, c->d_hp_win, total * 8, hipMemcpyDeviceToHost, c->win_stream) != hipSuccess) {
+            if (ok && total > 0 && hipMemcpyAsync(c->h_hp_win.get(), c->d_hp_win.get(), total * 8, hipMemcpyDeviceToHost, c->win_stream.get()) != hipSuccess) {
                 hpfw_internal_set_error("prepare: D2H copy failed");
                 ok = false;
             }
@@ -867,13 +804,8 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
                     hpfw_geometry g;
                     if (hpfw_gpu_geometry(c->gpu, kv.first, &g) == 0 && g.n_frames >= 2) total += pos.size() * (size_t)121 * g.c * 4;
                 }
-            if (total > c->h_spec_cap) { // (pinned: the copies run at the link's rate, not through the driver's staging)
-                if (c->h_spec) (void)hipHostFree(c->h_spec);
-                c->h_spec = nullptr;
-                c->h_spec_cap = 0;
-                if (hipHostMalloc(&c->h_spec, total + total / 8, hipHostMallocDefault) == hipSuccess) c->h_spec_cap = total + total / 8;
-                else c->h_spec = nullptr;
-            }
+            if (total > c->h_spec.capacity()) // (pinned: the copies run at the link's rate, not through the driver's staging)
+                (void)c->h_spec.alloc(total + total / 8);
         }
         for (auto &kv : by_len)
           for (const std::vector<int> &pos : kv.second) {
@@ -881,17 +813,16 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
             const int64_t len = kv.first;
             hpfw_geometry g;
             if (hpfw_gpu_geometry(c->gpu, len, &g) != 0 || g.n_frames < 2) continue; // skipped
-            size_t db_cap = 0;
-            float *d_db = group_spectrograms(c, clips[(size_t)pos[0]].arena_off, pos.size(), len, g, &db_cap);
-            if (!d_db) continue;
+            hpfw::DevBuf d_db;
+            if (!group_spectrograms(c, clips[(size_t)pos[0]].arena_off, pos.size(), len, g, d_db)) continue;
             std::vector<int> ids;
             for (int q : pos) ids.push_back(files[at + (size_t)q]);
             const size_t sz = pos.size() * (size_t)121 * g.c * 4;
             if (first && job.cache_spectros) {
                 // cache.set_spectro(filename, spectro) (parallel_collector.h:98-100): "it will also be needed
                 // when adding new tracks" -- a later prepare() recomputes every cached track's hashprints
-                if (c->h_spec && spec_used + sz <= c->h_spec_cap &&
-                    hipMemcpy(static_cast<char *>(c->h_spec) + spec_used, d_db, sz, hipMemcpyDeviceToHost) == hipSuccess) {
+                if (c->h_spec && spec_used + sz <= c->h_spec.capacity() &&
+                    hipMemcpy(c->h_spec.as<char>() + spec_used, d_db.get(), sz, hipMemcpyDeviceToHost) == hipSuccess) {
                     for (size_t k = 0; k < ids.size(); ++k)
                         spec_writes.push_back(SpecWrite{spectro_dir + std::filesystem::path(filenames[ids[k]]).stem().string(),
                                                         spec_used / 4 + k * (size_t)121 * g.c, (int32_t)g.c});
@@ -899,25 +830,25 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
                 }
             }
             if (first && job.learn) {
-                if (hpfw_gpu_cov_accumulate_db(c->gpu, d_db, (int64_t)pos.size(), g.c, nullptr) == 0) job.used += (int64_t)pos.size();
+                if (hpfw_gpu_cov_accumulate_db(c->gpu, d_db.as<float>(), (int64_t)pos.size(), g.c, nullptr) == 0) job.used += (int64_t)pos.size();
                 if (g.n_hp > 0 && job.kept_bytes + sz <= keep_budget) {
-                    job.kept.push_back(KeptGroup{ids, g, d_db});
+                    job.kept.push_back(KeptGroup{ids, g, std::move(d_db)});
                     job.kept_bytes += sz;
                     continue;
                 }
                 if (g.n_hp > 0) job.again.insert(job.again.end(), ids.begin(), ids.end());
             } else if (g.n_hp > 0) {
                 std::vector<uint64_t *> out(pos.size(), nullptr);
-                if (group_hashprints(c, d_db, pos.size(), g, out.data()))
+                if (group_hashprints(c, d_db.as<float>(), pos.size(), g, out.data()))
                     for (size_t k = 0; k < ids.size(); ++k) {
                         job.hp[(size_t)ids[k]] = out[k];
                         job.hp_size[(size_t)ids[k]] = (int)g.n_hp;
                     }
             }
-            release_spectrograms(c, d_db, db_cap); // (its next user is ordered after this group on the default stream; hipFree waits)
+            release_spectrograms(c, std::move(d_db)); // (its next user is ordered after this group on the default stream; hipFree waits)
         }
         if (!spec_writes.empty()) {
-            const float *host = static_cast<const float *>(c->h_spec);
+            const float *host = c->h_spec.as<const float>();
             host_team((int)spec_writes.size(), [&](int k) {
                 (void)save_spectro_cereal(spec_writes[(size_t)k].path, host + spec_writes[(size_t)k].off, spec_writes[(size_t)k].c);
             });
@@ -952,12 +883,11 @@ static void prepare_finish(hpfw_legacy_collector *c, const char **filenames, hpf
     (void)hipSetDevice(hpfw_gpu_device(c->gpu));
     for (KeptGroup &k : job.kept) {
         std::vector<uint64_t *> out(k.files.size(), nullptr);
-        if (ok && group_hashprints(c, k.d_db, k.files.size(), k.g, out.data()))
+        if (ok && group_hashprints(c, k.d_db.as<float>(), k.files.size(), k.g, out.data()))
             for (size_t q = 0; q < k.files.size(); ++q) {
                 job.hp[(size_t)k.files[q]] = out[q];
                 job.hp_size[(size_t)k.files[q]] = (int)k.g.n_hp;
             }
-        (void)hipFree(k.d_db);
     }
     job.kept.clear();
     if (ok && !job.again.empty()) {
@@ -1038,10 +968,10 @@ static void collect_cached(hpfw_legacy_collector *c, const std::vector<std::stri
                 for (int32_t col = 0; col < cols; ++col)
                     for (int32_t b = 0; b < HPFW_BINS; ++b) out[(size_t)b * cols + col] = cm[(size_t)col * HPFW_BINS + b];
             });
-            DevMem d_db;
+            hpfw::DevBuf d_db;
             std::vector<uint64_t *> out(pos.size(), nullptr);
-            if (!d_db.alloc(bm.size() * 4) || hipMemcpy(d_db.p, bm.data(), bm.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                !group_hashprints(c, (const float *)d_db.p, pos.size(), g, out.data()))
+            if (d_db.alloc(bm.size() * 4) != hipSuccess || hipMemcpy(d_db.get(), bm.data(), bm.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                !group_hashprints(c, d_db.as<float>(), pos.size(), g, out.data()))
                 continue;
             for (size_t k = 0; k < pos.size(); ++k) {
                 win_hp[(size_t)pos[k]] = out[k];
