@@ -46,6 +46,8 @@ EXPORTS = (
     "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
     "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
     "hpfw_gpu_combiner_find_device", "hpfw_gpu_combiner_align", "hpfw_gpu_combiner_align_device", "hpfw_gpu_wav_read_pcm16",
+    "hpfw_gpu_wav_read_pcm16_any", "hpfw_gpu_resample_length", "hpfw_gpu_resample_table", "hpfw_gpu_resample_pcm16",
+    "hpfw_gpu_resample_pcm16_host", "hpfw_gpu_collector_set_resample",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -165,6 +167,12 @@ def lib():
     L.hpfw_gpu_combiner_align.argtypes = [vp, vp, vp, vp, i64, i32, vp]
     L.hpfw_gpu_combiner_align_device.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
     L.hpfw_gpu_wav_read_pcm16.argtypes = [ctypes.c_char_p, vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_wav_read_pcm16_any.argtypes = [ctypes.c_char_p, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    L.hpfw_gpu_resample_length.argtypes = [i64, i32, ctypes.POINTER(i64)]
+    L.hpfw_gpu_resample_table.argtypes = [i32, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.hpfw_gpu_resample_pcm16.argtypes = [vp, vp, i64, i64, i32, vp, vp]
+    L.hpfw_gpu_resample_pcm16_host.argtypes = [vp, vp, i64, i64, i32, vp]
+    L.hpfw_gpu_collector_set_resample.argtypes = [vp, i32]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -255,6 +263,22 @@ class Gpu:
         hp = np.zeros((pcm.shape[0], g.n_hp), np.uint64)
         check(lib().hpfw_gpu_extract_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], _hp(hp)))
         return hp
+
+    # ---- sample-rate conversion to 44.1 kHz (k_resample.hip) --------------------------------
+    def resample_dev(self, d_in, n_in, n_clips, rate, d_out, stream=0):
+        """d_in int16 [n_clips][n_in] at `rate` -> d_out int16 [n_clips][resample_length(n_in, rate)] (device pointers)"""
+        check(lib().hpfw_gpu_resample_pcm16(self._h, d_in, int(n_in), int(n_clips), int(rate), d_out, stream))
+
+    def resample(self, pcm, rate):
+        """int16 [n] or [n_clips][n] at `rate` (8 000 .. 192 000 Hz) -> int16 at 44 100 Hz, same shape but the length"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        one = pcm.ndim == 1
+        if one:
+            pcm = pcm[None, :]
+        out = np.zeros((pcm.shape[0], resample_length(pcm.shape[1], rate)), np.int16)
+        if out.size:
+            check(lib().hpfw_gpu_resample_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], int(rate), _hp(out)))
+        return out[0] if one else out
 
     def set_projection(self, mode):
         """1 (default): fixed-point projection, exact integer sums (S9q); 0: the f32 fma chain (S9)"""
@@ -566,6 +590,33 @@ def wav_read(path):
     out = np.zeros(max(n.value, 1), np.int16)
     check(lib().hpfw_gpu_wav_read_pcm16(p, _hp(out), out.size, ctypes.byref(n)))
     return out[:n.value]
+
+
+def wav_read_any(path):
+    """a WAV file at its own rate: (int16 mono (stereo averaged, truncating), rate in Hz); not resampled"""
+    n, rate = ctypes.c_int64(0), ctypes.c_int32(0)
+    p = os.fsencode(path)
+    check(lib().hpfw_gpu_wav_read_pcm16_any(p, None, 0, ctypes.byref(n), ctypes.byref(rate)))
+    out = np.zeros(max(n.value, 1), np.int16)
+    check(lib().hpfw_gpu_wav_read_pcm16_any(p, _hp(out), out.size, ctypes.byref(n), ctypes.byref(rate)))
+    return out[:n.value], int(rate.value)
+
+
+def resample_length(n_in, rate):
+    """samples at 44.1 kHz of n_in samples at `rate`: ceil(n_in L / M)"""
+    n = ctypes.c_int64(0)
+    check(lib().hpfw_gpu_resample_length(int(n_in), int(rate), ctypes.byref(n)))
+    return int(n.value)
+
+
+def resample_table(rate):
+    """(L, M, taps int16 [L][T]) of the conversion from `rate` to 44.1 kHz (T = 0 at 44.1 kHz: the identity)"""
+    L, M, T = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().hpfw_gpu_resample_table(int(rate), None, 0, ctypes.byref(L), ctypes.byref(M), ctypes.byref(T)))
+    taps = np.zeros((L.value, T.value), np.int16)
+    if taps.size:
+        check(lib().hpfw_gpu_resample_table(int(rate), _hp(taps), taps.size, ctypes.byref(L), ctypes.byref(M), ctypes.byref(T)))
+    return int(L.value), int(M.value), taps
 
 
 def merge_topk(per_shard_hits, k):

@@ -10,11 +10,15 @@ from . import _lib
 
 
 class ParallelCollector:
-    def __init__(self):
+    def __init__(self, resample: bool = False):
+        """resample: accept WAV files at any rate in [8 000, 192 000] Hz and convert them to 44.1 kHz on the GPU
+        (hpfw_gpu_collector_set_resample); off, files at other rates are skipped as before"""
         self.__lib = _lib.lib()
         self.__collector = self.__lib.par_collector_new()
         if not self.__collector:
             raise _lib.HpfwError("par_collector_new failed: " + self.__lib.hpfw_gpu_last_error().decode())
+        if resample:
+            _lib.check(self.__lib.hpfw_gpu_collector_set_resample(self.__collector, 1))
 
     @staticmethod
     def _c_strings(filenames):

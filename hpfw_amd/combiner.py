@@ -32,8 +32,11 @@ class AlignHit(NamedTuple):
 
 
 class AudioCombiner:
-    def __init__(self, device: int = 0, filters: Optional[np.ndarray] = None):
+    def __init__(self, device: int = 0, filters: Optional[np.ndarray] = None, resample: bool = False):
+        """resample: prepare() reads WAV files at any rate in [8 000, 192 000] Hz and converts them to 44.1 kHz on the GPU
+        (off: 44.1 kHz only, as before)"""
         self._gpu = _lib.Gpu(device)
+        self._resample = resample
         self._has_filters = False
         self.names: List[str] = []
         self._hp: List[np.ndarray] = []
@@ -50,7 +53,7 @@ class AudioCombiner:
 
     def prepare(self, filenames: Sequence[str]) -> List[Tuple[str, np.ndarray]]:
         """(name, uint16 hashprints) per file, in the order given; learns the filters from these files if none are set"""
-        pcm = [_lib.wav_read(f) for f in filenames]
+        pcm = [self._read(f) for f in filenames]
         if not self._has_filters:
             cfg = _lib.COMBINER_CONFIG
             self._gpu.cfg_cov_reset(cfg)
@@ -60,6 +63,12 @@ class AudioCombiner:
             self._gpu.cfg_learn_filters(cfg)             # installs them
             self._has_filters = True
         return [(f, self._gpu.mel_hashprints(x)[0] if x.size else np.zeros(0, np.uint16)) for f, x in zip(filenames, pcm)]
+
+    def _read(self, filename):
+        if not self._resample:
+            return _lib.wav_read(filename)
+        x, rate = _lib.wav_read_any(filename)
+        return self._gpu.resample(x, rate) if rate != 44100 and x.size else x
 
     def build(self, pairs: Sequence[Tuple[str, np.ndarray]]):
         names = [name for name, _ in pairs]

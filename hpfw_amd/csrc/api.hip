@@ -320,6 +320,14 @@ struct hpfw_gpu {
     int k_launches[K_COUNT] = {0};
     // AudioCombiner's inverted index (k_combiner.hip), created on first use
     std::unique_ptr<hpfw::Combiner> combiner;
+    // sample-rate conversion (k_resample.hip): the device image of each rate's table, made on first use; staging of
+    // the host entry point
+    struct RsTable {
+        int32_t L = 0, M = 0, T = 0;
+        DevBuf d_taps;
+    };
+    std::map<int, RsTable> rs_tables;
+    DevBuf rs_in, rs_out;
 };
 
 namespace {
@@ -1609,6 +1617,96 @@ int hpfw_gpu_mel_spectrogram_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t
                 hipMemcpy(cols, d_cols.get(), (size_t)n_clips * 4, hipMemcpyDeviceToHost) != hipSuccess))
         rc = fail(HPFW_E_HIP, "kernel execution or D2H copy failed");
     return rc;
+}
+
+// ---- sample-rate conversion to 44.1 kHz (k_resample.hip) ------------------------
+static int rs_check_rate(int rate)
+{
+    if (rate < hpfw::kRsRateMin || rate > hpfw::kRsRateMax)
+        return fail(HPFW_E_INVALID, "sample rate " + std::to_string(rate) + " Hz outside [8000, 192000]");
+    return 0;
+}
+
+int hpfw_gpu_resample_length(int64_t n_in, int rate, int64_t *n_out)
+{
+    if (!n_out || n_in < 0) return fail(HPFW_E_INVALID, "bad argument");
+    int rc = rs_check_rate(rate);
+    if (rc) return rc;
+    int32_t L, M, H;
+    (void)hpfw::resample_ratio(rate, &L, &M, &H);
+    *n_out = hpfw::resample_out_length(n_in, L, M);
+    return 0;
+}
+
+int hpfw_gpu_resample_table(int rate, int16_t *taps, int64_t cap, int32_t *L, int32_t *M, int32_t *T)
+{
+    if (!L || !M || !T) return fail(HPFW_E_INVALID, "bad argument");
+    int rc = rs_check_rate(rate);
+    if (rc) return rc;
+    if (rate == hpfw::kRsRateOut) { // the identity: no filter
+        *L = *M = 1;
+        *T = 0;
+        return 0;
+    }
+    std::vector<int16_t> t;
+    if (!hpfw::resample_design(rate, t, L, M, T)) return fail(HPFW_E_INVALID, "resampling table out of range");
+    if (!taps) return 0;
+    if (cap < (int64_t)t.size()) return fail(HPFW_E_INVALID, "buffer smaller than the table");
+    std::copy(t.begin(), t.end(), taps);
+    return 0;
+}
+
+int hpfw_gpu_resample_pcm16(hpfw_gpu *h, const int16_t *d_in, int64_t n_in, int64_t n_clips, int rate, int16_t *d_out, void *stream)
+{
+    if (!h || n_in < 0 || n_clips < 0 || ((!d_in || !d_out) && n_in > 0 && n_clips > 0)) return fail(HPFW_E_INVALID, "bad argument");
+    int rc = rs_check_rate(rate);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    hpfw_gpu::RsTable *tab = nullptr;
+    if (rate != hpfw::kRsRateOut) {
+        hpfw_gpu::RsTable &t = h->rs_tables[rate];
+        if (!t.d_taps) { // once per rate (published only when complete)
+            std::vector<int16_t> taps;
+            int32_t L, M, T;
+            if (!hpfw::resample_design(rate, taps, &L, &M, &T)) return fail(HPFW_E_INVALID, "resampling table out of range");
+            const std::vector<int32_t> img = hpfw::resample_device_table(taps, L, T);
+            DevBuf d;
+            HIP_TRY(d.alloc(img.size() * 4));
+            HIP_TRY(hipMemcpy(d.get(), img.data(), img.size() * 4, hipMemcpyHostToDevice));
+            t.L = L;
+            t.M = M;
+            t.T = T;
+            t.d_taps = std::move(d);
+        }
+        tab = &t;
+    }
+    if (n_in == 0 || n_clips == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (!tab) { // 44.1 kHz: a plain copy
+            HIP_TRY(hipMemcpyAsync(d_out, d_in, (size_t)n_clips * n_in * 2, hipMemcpyDeviceToDevice, s));
+            return 0;
+        }
+        if (!hpfw::launch_resample(d_in, n_in, n_clips, tab->L, tab->M, tab->T, tab->d_taps.as<int32_t>(), d_out, s))
+            return fail(HPFW_E_INVALID, "resampling: the table and its input span exceed the LDS");
+        return check_launch("resample");
+    });
+}
+
+int hpfw_gpu_resample_pcm16_host(hpfw_gpu *h, const int16_t *in, int64_t n_in, int64_t n_clips, int rate, int16_t *out)
+{
+    if (!h || n_in < 0 || n_clips < 0 || ((!in || !out) && n_in > 0 && n_clips > 0)) return fail(HPFW_E_INVALID, "bad argument");
+    int64_t n_out = 0;
+    int rc = hpfw_gpu_resample_length(n_in, rate, &n_out);
+    if (rc) return rc;
+    if (n_in == 0 || n_clips == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if ((rc = ensure(h->rs_in, (size_t)n_clips * n_in * 2, h)) || (rc = ensure(h->rs_out, (size_t)n_clips * n_out * 2, h))) return rc;
+    HIP_TRY(hipMemcpy(h->rs_in.get(), in, (size_t)n_clips * n_in * 2, hipMemcpyHostToDevice));
+    if ((rc = hpfw_gpu_resample_pcm16(h, h->rs_in.as<int16_t>(), n_in, n_clips, rate, h->rs_out.as<int16_t>(), nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out, h->rs_out.get(), (size_t)n_clips * n_out * 2, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- HashprintHandle with other template arguments (hashprint_handle.h:50-64) -------------------------

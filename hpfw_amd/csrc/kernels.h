@@ -326,6 +326,19 @@ size_t topk_scratch_bytes(int n_q, int k);
 void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_scratch,
                           void *d_out, hipStream_t s);
 
+// sample-rate conversion to 44.1 kHz (k_resample.hip)
+constexpr int kRsRateOut = 44100, kRsRateMin = 8000, kRsRateMax = 192000;
+constexpr int kRsShift = 14; // taps in fixed point: every phase sums to 2^14
+// (L, M) = (44100, rate) / gcd and H (taps per phase T = 2 H); false outside [kRsRateMin, kRsRateMax]
+bool resample_ratio(int rate, int32_t *L, int32_t *M, int32_t *H);
+int64_t resample_out_length(int64_t n_in, int32_t L, int32_t M); // ceil(n_in L / M)
+// the [L][T] int16 table (host, float64); false for a rate outside the range
+bool resample_design(int rate, std::vector<int16_t> &taps, int32_t *L, int32_t *M, int32_t *T);
+int resample_row_words(int T);
+std::vector<int32_t> resample_device_table(const std::vector<int16_t> &taps, int32_t L, int32_t T);
+bool launch_resample(const int16_t *d_in, int64_t n_in, int64_t n_clips, int32_t L, int32_t M, int32_t T, const int32_t *d_taps,
+                     int16_t *d_out, hipStream_t s);
+
 // fail-loud launch check
 const char *last_launch_error();
 

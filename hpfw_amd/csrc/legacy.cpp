@@ -7,7 +7,8 @@
 //
 // Audio input: essentia MonoLoader (reference include/hpfw/spectrum/cqt.h:45-52) is replaced by a
 // RIFF/WAVE reader for PCM16 at 44.1 kHz (mono, or stereo averaged as MonoLoader's "mix" downmix);
-// other containers / rates are rejected (decode and resampling are outside the accelerated path).
+// other containers are rejected, and so are other rates unless the collector's resampling switch is on
+// (hpfw_gpu_collector_set_resample: any rate in [8 000, 192 000] Hz, converted to 44.1 kHz on the GPU).
 // Filters: read from / written to <cache>/filters.cereal in cereal's binary layout of an Eigen
 // matrix (reference include/hpfw/utils.h:84-90: int32 rows, int32 cols, column-major payload).
 #include <algorithm>
@@ -40,7 +41,14 @@ extern "C" void hpfw_internal_note_idle(hpfw_gpu *h);      // api.hip: every pla
 
 namespace {
 
-bool read_wav_pcm16_mono(const std::string &path, std::vector<int16_t> &out, std::string &why)
+// rate_any: NULL = 44.1 kHz only; else any rate in [8 000, 192 000] Hz is accepted and stored there
+bool rate_ok(uint32_t rate, const uint32_t *rate_any) { return rate_any ? rate >= 8000 && rate <= 192000 : rate == 44100; }
+const char *rate_msg(const uint32_t *rate_any)
+{
+    return rate_any ? ": only PCM16 mono/stereo at 8000..192000 Hz is supported" : ": only PCM16 mono/stereo at 44100 Hz is supported";
+}
+
+bool read_wav_pcm16_mono(const std::string &path, std::vector<int16_t> &out, std::string &why, uint32_t *rate_any = nullptr)
 {
     std::ifstream f(path, std::ios::binary);
     if (!f) {
@@ -74,10 +82,11 @@ bool read_wav_pcm16_mono(const std::string &path, std::vector<int16_t> &out, std
             if (sz & 1) f.seekg(1, std::ios::cur);
             have_fmt = true;
         } else if (!std::memcmp(id, "data", 4)) {
-            if (!have_fmt || fmt != 1 || bits != 16 || (channels != 1 && channels != 2) || rate != 44100) {
-                why = path + ": only PCM16 mono/stereo at 44100 Hz is supported";
+            if (!have_fmt || fmt != 1 || bits != 16 || (channels != 1 && channels != 2) || !rate_ok(rate, rate_any)) {
+                why = path + rate_msg(rate_any);
                 return false;
             }
+            if (rate_any) *rate_any = rate;
             // a streamed file may carry 0 or 0xffffffff as the size: trust the file's length instead
             const std::streamoff here = f.tellg();
             f.seekg(0, std::ios::end);
@@ -200,6 +209,10 @@ struct hpfw_legacy_collector {
     // ... and two device copies in turn: window w + 1 is uploaded while the kernels of window w read theirs
     hpfw::DevBuf d_arena_buf[2];
     void *d_arena = nullptr; // the copy of the window in hand
+    // hpfw_gpu_collector_set_resample: files at other rates than 44.1 kHz are converted on the device (grow-only staging
+    // of a group's 44.1 kHz clips, read by the extraction in place of the arena)
+    bool resample = false;
+    hpfw::DevBuf rs_stage;
 };
 
 // the exported entry points: no exception leaves the C boundary (the reference's wrapper.cpp has no such
@@ -287,10 +300,10 @@ void par_collector_save(hpfw_legacy_collector *c, const char *cache)
 
 // A file of any length: the reference hands the exact sample count to NSGConstantQ (cqt.h:54-55) and so does
 // this -- lengths with a prime factor above 7 take the chirp-z forward transform (k_bluestein.hip); nothing is padded.
-static bool read_clip(const std::string &path, std::vector<int16_t> &pcm, std::string &why)
+static bool read_clip(const std::string &path, std::vector<int16_t> &pcm, std::string &why, uint32_t *rate_any = nullptr)
 {
     try { // nothing may throw through the C boundary (or out of a reader thread): e.g. bad_alloc on a huge file
-        return read_wav_pcm16_mono(path, pcm, why);
+        return read_wav_pcm16_mono(path, pcm, why, rate_any);
     } catch (const std::exception &e) {
         why = path + ": " + e.what();
         return false;
@@ -320,15 +333,59 @@ extern "C" int hpfw_gpu_wav_read_pcm16(const char *path, int16_t *out, int64_t c
     return 0;
 }
 
+extern "C" int hpfw_gpu_wav_read_pcm16_any(const char *path, int16_t *out, int64_t cap, int64_t *n, int32_t *rate)
+{
+    if (!path || !n || !rate) {
+        hpfw_internal_set_error("null argument");
+        return HPFW_E_INVALID;
+    }
+    *n = 0;
+    *rate = 0;
+    std::vector<int16_t> pcm;
+    std::string why;
+    uint32_t r = 0;
+    if (!read_clip(path, pcm, why, &r)) {
+        hpfw_internal_set_error(why.c_str());
+        return HPFW_E_IO;
+    }
+    *n = (int64_t)pcm.size();
+    *rate = (int32_t)r;
+    if (!out) return 0;
+    if (cap < *n) {
+        hpfw_internal_set_error("buffer smaller than the file's samples");
+        return HPFW_E_INVALID;
+    }
+    std::copy(pcm.begin(), pcm.end(), out);
+    return 0;
+}
+
+extern "C" int hpfw_gpu_collector_set_resample(hpfw_legacy_collector *c, int on)
+{
+    if (!c) {
+        hpfw_internal_set_error("null collector");
+        return HPFW_E_INVALID;
+    }
+    c->resample = on != 0;
+    return 0;
+}
+
 static uint64_t *calc_hashprint_impl(hpfw_legacy_collector *c, const char *filename, int *size)
 {
     if (size) *size = 0;
     if (!c || !filename || !size) return nullptr;
     std::vector<int16_t> pcm;
     std::string why;
-    if (!read_clip(filename, pcm, why)) {
+    uint32_t rate = 44100;
+    if (!read_clip(filename, pcm, why, c->resample ? &rate : nullptr)) {
         hpfw_internal_set_error(why.c_str());
         return nullptr;
+    }
+    if (rate != 44100) { // converted on the device first
+        int64_t n_out = 0;
+        if (hpfw_gpu_resample_length((int64_t)pcm.size(), (int)rate, &n_out) != 0) return nullptr;
+        std::vector<int16_t> y((size_t)n_out);
+        if (hpfw_gpu_resample_pcm16_host(c->gpu, pcm.data(), (int64_t)pcm.size(), 1, (int)rate, y.data()) != 0) return nullptr;
+        pcm.swap(y);
     }
     hpfw_geometry g;
     if (hpfw_gpu_geometry(c->gpu, (int64_t)pcm.size(), &g) != 0) return nullptr;
@@ -356,10 +413,12 @@ struct WavProbe {
     int fd = -1;
     int64_t data_off = 0, frames = 0; // payload offset; samples per channel
     int channels = 0;
+    uint32_t rate = 44100;
     bool ok = false;
 };
 
-bool probe_wav(const std::string &path, WavProbe &w, std::string &why)
+// any_rate: accept every rate in [8 000, 192 000] Hz (else 44.1 kHz only)
+bool probe_wav(const std::string &path, WavProbe &w, std::string &why, bool any_rate)
 {
     w = WavProbe();
     const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
@@ -399,11 +458,13 @@ bool probe_wav(const std::string &path, WavProbe &w, std::string &why)
             if (fmt == 0xFFFE && sz >= 26) std::memcpy(&fmt, b + 24, 2); // WAVE_FORMAT_EXTENSIBLE: the sub-format's tag
             have_fmt = true;
         } else if (!std::memcmp(ch, "data", 4)) {
-            if (!have_fmt || fmt != 1 || bits != 16 || (channels != 1 && channels != 2) || rate != 44100) {
+            uint32_t any = 0;
+            if (!have_fmt || fmt != 1 || bits != 16 || (channels != 1 && channels != 2) || !rate_ok(rate, any_rate ? &any : nullptr)) {
                 ::close(fd);
-                why = path + ": only PCM16 mono/stereo at 44100 Hz is supported";
+                why = path + rate_msg(any_rate ? &any : nullptr);
                 return false;
             }
+            w.rate = rate;
             // a streamed file may carry 0 or 0xffffffff as the size: trust the file's length instead
             const int64_t left = fsize - (pos + 8);
             int64_t bytes = sz;
@@ -424,7 +485,9 @@ bool probe_wav(const std::string &path, WavProbe &w, std::string &why)
 
 struct Loaded {
     const int16_t *pcm = nullptr; // in the collector's pinned arena
-    int64_t n = 0;                // samples (mono)
+    int64_t n = 0;                // samples (mono) as read
+    uint32_t rate = 44100;        // their rate: other than 44.1 kHz only with the resampling switch on
+    int64_t n_out = 0;            // samples at 44.1 kHz
     size_t arena_off = 0;         // byte offset of the clip in the arena (the device copy has the same layout)
     bool ok = false;
 };
@@ -464,24 +527,33 @@ size_t read_window(hpfw_legacy_collector *c, int slot, const char **filenames, c
     run([&](int i) {
         std::string why;
         try {
-            if (!probe_wav(filenames[files[first + (size_t)i]], probes[(size_t)i], why)) fail(why);
-            else if (c->gpu) (void)hpfw_gpu_prepare_length(c->gpu, probes[(size_t)i].frames); // (too short: skipped later)
+            if (!probe_wav(filenames[files[first + (size_t)i]], probes[(size_t)i], why, c->resample)) {
+                fail(why);
+            } else if (c->gpu) { // the tables of the length the extraction will see (too short: skipped later)
+                int64_t n_out = probes[(size_t)i].frames;
+                if (probes[(size_t)i].rate != 44100) (void)hpfw_gpu_resample_length(n_out, (int)probes[(size_t)i].rate, &n_out);
+                (void)hpfw_gpu_prepare_length(c->gpu, n_out);
+            }
         } catch (const std::exception &e) {
             fail(std::string(filenames[files[first + (size_t)i]]) + ": " + e.what());
         }
     });
     const auto t_probe = std::chrono::steady_clock::now();
-    // slots: by length, then input order; every group starts 16-byte aligned
-    std::map<int64_t, std::vector<int>> by_len;
+    // slots: by (rate, length), then input order; every group starts 16-byte aligned
+    std::map<std::pair<uint32_t, int64_t>, std::vector<int>> by_len;
     for (int i = 0; i < count; ++i)
-        if (probes[(size_t)i].ok && probes[(size_t)i].frames > 0) by_len[probes[(size_t)i].frames].push_back(i);
+        if (probes[(size_t)i].ok && probes[(size_t)i].frames > 0) by_len[{probes[(size_t)i].rate, probes[(size_t)i].frames}].push_back(i);
     size_t bytes = 0;
     for (auto &kv : by_len) {
         bytes = (bytes + 15) / 16 * 16;
+        int64_t n_out = kv.first.second;
+        if (kv.first.first != 44100) (void)hpfw_gpu_resample_length(n_out, (int)kv.first.first, &n_out);
         for (int i : kv.second) {
             out[(size_t)i].arena_off = bytes;
-            out[(size_t)i].n = kv.first;
-            bytes += (size_t)kv.first * 2;
+            out[(size_t)i].n = kv.first.second;
+            out[(size_t)i].rate = kv.first.first;
+            out[(size_t)i].n_out = n_out;
+            bytes += (size_t)kv.first.second * 2;
         }
     }
     if (bytes > c->arena[slot].capacity() && c->arena[slot].alloc(std::max(bytes + bytes / 4, (size_t)64 << 20)) != hipSuccess) {
@@ -548,10 +620,23 @@ bool upload_window(hpfw_legacy_collector *c, int slot, size_t bytes)
     return bytes == 0 || hipMemcpy(c->d_arena, c->arena[slot].get(), bytes, hipMemcpyHostToDevice) == hipSuccess;
 }
 
-// dB spectrograms [n][121][C] of n equally long clips of the window into d_db (empty on entry), which is
-// release_spectrograms' spare when that is large enough; the clips lie side by side in the device copy of the arena, the
-// first at `first_off`
-bool group_spectrograms(hpfw_legacy_collector *c, size_t first_off, size_t n, int64_t len, const hpfw_geometry &g, hpfw::DevBuf &d_db)
+// the n clips of a group at 44.1 kHz on the device, side by side from `first`: the device copy of the arena itself, or, for
+// another rate, the collector's staging buffer after the conversion on stream s (NULL on failure)
+const int16_t *group_pcm(hpfw_legacy_collector *c, const Loaded &first, size_t n, hipStream_t s)
+{
+    const int16_t *d_in = reinterpret_cast<const int16_t *>(static_cast<const char *>(c->d_arena) + first.arena_off);
+    if (first.rate == 44100) return d_in;
+    if (c->rs_stage.ensure(n * (size_t)first.n_out * 2) != hipSuccess) {
+        hpfw_internal_set_error("prepare: out of device memory for the resampled clips");
+        return nullptr;
+    }
+    if (hpfw_gpu_resample_pcm16(c->gpu, d_in, first.n, (int64_t)n, (int)first.rate, c->rs_stage.as<int16_t>(), s) != 0) return nullptr;
+    return c->rs_stage.as<const int16_t>();
+}
+
+// dB spectrograms [n][121][C] of n equally long clips (side by side from d_pcm, on the device) into d_db (empty on entry),
+// which is release_spectrograms' spare when that is large enough
+bool group_spectrograms(hpfw_legacy_collector *c, const int16_t *d_pcm, size_t n, int64_t len, const hpfw_geometry &g, hpfw::DevBuf &d_db)
 {
     const size_t need = n * (size_t)121 * g.c * 4;
     if (c->spare_db.capacity() >= need) {
@@ -560,7 +645,6 @@ bool group_spectrograms(hpfw_legacy_collector *c, size_t first_off, size_t n, in
         hpfw_internal_set_error("prepare: out of device memory");
         return false;
     }
-    const int16_t *d_pcm = reinterpret_cast<const int16_t *>(static_cast<const char *>(c->d_arena) + first_off);
     // (no synchronisation: what follows runs on the default stream too, and the copies to the host wait for it)
     return hpfw_gpu_stage_spectrogram(c->gpu, d_pcm, len, (int64_t)n, d_db.as<float>(), nullptr) == 0;
 }
@@ -728,13 +812,13 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
         }
         finish(); // (the previous window's kernels ran under this upload)
         const auto t_2 = std::chrono::steady_clock::now();
-        // length -> positions in the window, in input order.  A group whose files were all read lies side by side in the
-        // arena; one with a failed read in its middle is cut into its contiguous runs
-        std::map<int64_t, std::vector<std::vector<int>>> by_len;
+        // (rate, length) -> positions in the window, in input order.  A group whose files were all read lies side by side in
+        // the arena; one with a failed read in its middle is cut into its contiguous runs
+        std::map<std::pair<uint32_t, int64_t>, std::vector<std::vector<int>>> by_len;
         {
-            std::map<int64_t, std::vector<int>> all;
+            std::map<std::pair<uint32_t, int64_t>, std::vector<int>> all;
             for (size_t i = 0; i < clips.size(); ++i)
-                if (clips[i].n > 0) all[clips[i].n].push_back((int)i);
+                if (clips[i].n > 0) all[{clips[i].rate, clips[i].n}].push_back((int)i);
             for (auto &kv : all) {
                 std::vector<int> run;
                 for (int i : kv.second) {
@@ -756,16 +840,23 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
             pend.total = 0;
             pend.at = at;
             pend.ok = true;
+            size_t stage = 0; // the resampled clips of the largest group at another rate (one buffer, reused in stream order)
             for (auto &kv : by_len)
                 for (const std::vector<int> &pos : kv.second) {
                     hpfw_geometry g;
-                    if (hpfw_gpu_geometry(c->gpu, kv.first, &g) != 0 || g.n_frames < 2 || g.n_hp <= 0) continue; // skipped
+                    const Loaded &l0 = clips[(size_t)pos[0]];
+                    if (hpfw_gpu_geometry(c->gpu, l0.n_out, &g) != 0 || g.n_frames < 2 || g.n_hp <= 0) continue; // skipped
                     pend.parts.push_back(Part{pos, g, pend.total, false});
                     pend.total += pos.size() * (size_t)g.n_hp;
+                    if (l0.rate != 44100) stage = std::max(stage, pos.size() * (size_t)l0.n_out * 2);
                 }
             const size_t total = pend.total;
             bool ok = true;
             if (!ensure_hp_buffers(c, total * 8)) ok = false;
+            if (ok && stage && c->rs_stage.ensure(stage) != hipSuccess) {
+                hpfw_internal_set_error("prepare: out of device memory for the resampled clips");
+                ok = false;
+            }
             if (ok && !c->win_stream && c->win_stream.create() != hipSuccess) {
                 hpfw_internal_set_error("prepare: no stream");
                 ok = false;
@@ -773,9 +864,10 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
             const auto t_enq = std::chrono::steady_clock::now();
             for (size_t k = 0; ok && k < pend.parts.size(); ++k) {
                 Part &pt = pend.parts[k];
-                const int16_t *d_pcm = reinterpret_cast<const int16_t *>(static_cast<const char *>(c->d_arena) + clips[(size_t)pt.pos[0]].arena_off);
-                pt.done = hpfw_gpu_extract_pcm16(c->gpu, d_pcm, clips[(size_t)pt.pos[0]].n, (int64_t)pt.pos.size(),
-                                                 c->d_hp_win.as<uint64_t>() + pt.off, c->win_stream.get()) == 0; // a failed group is skipped
+                const Loaded &l0 = clips[(size_t)pt.pos[0]];
+                const int16_t *d_pcm = group_pcm(c, l0, pt.pos.size(), c->win_stream.get());
+                pt.done = d_pcm && hpfw_gpu_extract_pcm16(c->gpu, d_pcm, l0.n_out, (int64_t)pt.pos.size(),
+                                                          c->d_hp_win.as<uint64_t>() + pt.off, c->win_stream.get()) == 0; // a failed group is skipped
             }
             if (ok && total > 0 && hipMemcpyAsync(c->h_hp_win.get(), c->d_hp_win.get(), total * 8, hipMemcpyDeviceToHost, c->win_stream.get()) != hipSuccess) {
                 hpfw_internal_set_error("prepare: D2H copy failed");
@@ -802,7 +894,7 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
             for (auto &kv : by_len)
                 for (const std::vector<int> &pos : kv.second) {
                     hpfw_geometry g;
-                    if (hpfw_gpu_geometry(c->gpu, kv.first, &g) == 0 && g.n_frames >= 2) total += pos.size() * (size_t)121 * g.c * 4;
+                    if (hpfw_gpu_geometry(c->gpu, clips[(size_t)pos[0]].n_out, &g) == 0 && g.n_frames >= 2) total += pos.size() * (size_t)121 * g.c * 4;
                 }
             if (total > c->h_spec.capacity()) // (pinned: the copies run at the link's rate, not through the driver's staging)
                 (void)c->h_spec.alloc(total + total / 8);
@@ -810,11 +902,12 @@ static void prepare_pass(hpfw_legacy_collector *c, const char **filenames, hpfw_
         for (auto &kv : by_len)
           for (const std::vector<int> &pos : kv.second) {
             if (direct) break;
-            const int64_t len = kv.first;
+            const int64_t len = clips[(size_t)pos[0]].n_out; // (at 44.1 kHz)
             hpfw_geometry g;
             if (hpfw_gpu_geometry(c->gpu, len, &g) != 0 || g.n_frames < 2) continue; // skipped
             hpfw::DevBuf d_db;
-            if (!group_spectrograms(c, clips[(size_t)pos[0]].arena_off, pos.size(), len, g, d_db)) continue;
+            const int16_t *d_pcm = group_pcm(c, clips[(size_t)pos[0]], pos.size(), nullptr);
+            if (!d_pcm || !group_spectrograms(c, d_pcm, pos.size(), len, g, d_db)) continue;
             std::vector<int> ids;
             for (int q : pos) ids.push_back(files[at + (size_t)q]);
             const size_t sz = pos.size() * (size_t)121 * g.c * 4;

@@ -18,6 +18,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/hpfw_gpu_multi.h"
+#include "../../include/hpfw_gpu_multi_resample.h"
 #include "legacy_internal.h"
 
 extern "C" void hpfw_internal_set_error(const char *msg); // libhpfw_gpu.so: feeds hpfw_gpu_last_error()
@@ -60,6 +61,7 @@ struct hpfw_gpu_group {
     int per_dev = 1; // shards on every device (uniform)
     int64_t n_clips = 0;
     std::string exchange;
+    bool resample = false; // hpfw_gpu_group_set_resample: applied to every shard collector, those made later included
 };
 
 namespace {
@@ -449,8 +451,17 @@ static int ensure_collectors(hpfw_gpu_group *g, const char *cache)
         // accum_cov.cereal carries the covariance of earlier runs (the reference keeps accumulating, cache.h:34-36,
         // live_song_id.h:23-29): it enters the sum once, through shard 0
         if (i > 0) (void)hpfw_gpu_cov_reset(hpfw_internal_collector_gpu(c));
+        (void)hpfw_gpu_collector_set_resample(c, g->resample);
         g->collectors.push_back(c);
     }
+    return 0;
+}
+
+int hpfw_gpu_group_set_resample(hpfw_gpu_group *g, int on)
+{
+    if (!g) return fail(HPFW_E_INVALID, "null group");
+    g->resample = on != 0;
+    for (hpfw_legacy_collector *c : g->collectors) (void)hpfw_gpu_collector_set_resample(c, g->resample);
     return 0;
 }
 

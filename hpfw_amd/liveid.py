@@ -16,8 +16,9 @@ from .collector import ParallelCollector
 
 
 class LiveSongIdentification:
-    def __init__(self, cache: str = "", device: int = 0):
-        self.collector = ParallelCollector()
+    def __init__(self, cache: str = "", device: int = 0, resample: bool = False):
+        """resample: index and search WAV files at any rate in [8 000, 192 000] Hz (ParallelCollector(resample=True))"""
+        self.collector = ParallelCollector(resample=resample)
         self.collector.load(cache)                       # the constructor loads the cache, live_song_id.h:24
         self._cache = cache
         self._gpu = _lib.Gpu(device)

@@ -19,6 +19,8 @@ EXPORTS = (
     "hpfw_gpu_group_cov_accumulate_pcm16", "hpfw_gpu_group_learn_filters",
     "hpfw_gpu_group_load", "hpfw_gpu_group_save", "hpfw_gpu_group_prepare", "hpfw_gpu_group_calc_hashprint",
 )
+# include/hpfw_gpu_multi_resample.h
+RESAMPLE_EXPORTS = ("hpfw_gpu_group_set_resample",)
 
 _multi = None
 
@@ -58,6 +60,7 @@ def lib():
     L.hpfw_gpu_group_prepare.restype = ctypes.POINTER(_lib.FilenameHashprintPair)
     L.hpfw_gpu_group_calc_hashprint.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
     L.hpfw_gpu_group_calc_hashprint.restype = ctypes.POINTER(ctypes.c_uint64)
+    L.hpfw_gpu_group_set_resample.argtypes = [vp, i32]
     _multi = L
     return L
 
@@ -161,6 +164,10 @@ class GpuGroup:
             out.append((a, res[i].filename.decode("utf-8")))
         _lib.lib().prepare_result_free(res, got)
         return out
+
+    def set_resample(self, on=True):
+        """files at any rate in [8 000, 192 000] Hz, converted to 44.1 kHz on the GPU (every shard, later ones too)"""
+        _lib.check(lib().hpfw_gpu_group_set_resample(self._g, int(bool(on))))
 
     def calc_hashprint(self, filename):
         size = ctypes.c_int(0)

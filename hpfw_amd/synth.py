@@ -83,11 +83,11 @@ def planted_queries(db, n_q, k, flip_bits=6, seed=SEED):
     return qs, cids, offs
 
 
-def write_wav(path, pcm, channels=1):
+def write_wav(path, pcm, channels=1, rate=SR):
     pcm = np.ascontiguousarray(pcm, np.int16)
     data = pcm.tobytes()
     with open(path, "wb") as f:
         f.write(b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE")
-        f.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, channels, SR, SR * 2 * channels, 2 * channels, 16))
+        f.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, channels, rate, rate * 2 * channels, 2 * channels, 16))
         f.write(b"data" + struct.pack("<I", len(data)))
         f.write(data)

@@ -45,6 +45,10 @@ public:
     GpuAudioCombiner(const GpuAudioCombiner &) = delete;
     GpuAudioCombiner &operator=(const GpuAudioCombiner &) = delete;
 
+    /// on: prepare() and the searches by file name read WAV files at any rate in [8 000, 192 000] Hz and convert them to
+    /// 44.1 kHz on the GPU (hpfw_gpu_resample_pcm16); off (the default): 44.1 kHz files only
+    void set_resample(bool on) { resample_ = on; }
+
     /// filters: Matrix<float, 16, 33 * 32> column-major (hpfw_gpu_cfg_set_filters)
     void set_filters(const float *filters_colmajor)
     {
@@ -162,6 +166,7 @@ private:
     hpfw_gpu *h_ = nullptr;
     hpfw_handle_config cfg_ = HPFW_CONFIG_COMBINER;
     bool has_filters_ = false;
+    bool resample_ = false;
     std::vector<FilenameFingerprintPair> pairs_;
     std::unordered_map<std::string, uint32_t> ids_;
     static inline uint16_t dummy_ = 0;
@@ -171,13 +176,25 @@ private:
         if (rc != 0) throw std::runtime_error(std::string("hpfw::GpuAudioCombiner: ") + hpfw_gpu_last_error());
     }
 
-    static std::vector<int16_t> read_wav(const std::string &path)
+    std::vector<int16_t> read_wav(const std::string &path)
     {
         int64_t n = 0;
-        check(hpfw_gpu_wav_read_pcm16(path.c_str(), nullptr, 0, &n));
+        if (!resample_) {
+            check(hpfw_gpu_wav_read_pcm16(path.c_str(), nullptr, 0, &n));
+            std::vector<int16_t> pcm((size_t)n);
+            check(hpfw_gpu_wav_read_pcm16(path.c_str(), pcm.data(), n, &n));
+            return pcm;
+        }
+        int32_t rate = 0;
+        check(hpfw_gpu_wav_read_pcm16_any(path.c_str(), nullptr, 0, &n, &rate));
         std::vector<int16_t> pcm((size_t)n);
-        check(hpfw_gpu_wav_read_pcm16(path.c_str(), pcm.data(), n, &n));
-        return pcm;
+        check(hpfw_gpu_wav_read_pcm16_any(path.c_str(), pcm.data(), n, &n, &rate));
+        if (rate == 44100 || pcm.empty()) return pcm;
+        int64_t n_out = 0;
+        check(hpfw_gpu_resample_length(n, rate, &n_out));
+        std::vector<int16_t> out((size_t)n_out);
+        check(hpfw_gpu_resample_pcm16_host(h_, pcm.data(), n, 1, rate, out.data()));
+        return out;
     }
 
     Hashprint hashprints(const std::vector<int16_t> &pcm)

@@ -6,7 +6,8 @@
 //
 // Same public surface: Hashprint, FilenameFingerprintPair, prepare(), calc_hashprint(), save(),
 // load().  Differences, all deliberate:
-//   - audio files must be PCM16 WAV at 44.1 kHz (decode/resample are outside the accelerated path);
+//   - audio files must be PCM16 WAV at 44.1 kHz, or at any rate in [8 000, 192 000] Hz after set_resample(true)
+//     (converted to 44.1 kHz on the GPU; compressed formats are not decoded);
 //   - prepare() learns the filters as the reference's preprocess() does (covariance of the frames
 //     of every file, 64 leading eigenvectors; parallel_collector.h:82-112) unless the environment
 //     variable HPFW_PREPARE_KEEP_FILTERS is set and filters were loaded; calc_hashprint() before any
@@ -82,6 +83,14 @@ public:
             out.push_back(res[i].hashprint ? Hashprint(res[i].hashprint, res[i].hashprint + res[i].hp_size) : Hashprint());
         prepare_result_free(res, (int)names.size());
         return out;
+    }
+
+    /// on: files at any rate in [8 000, 192 000] Hz are converted to 44.1 kHz on the GPU (not in the reference, whose
+    /// MonoLoader always resamples); off (the default): files at other rates than 44.1 kHz are skipped
+    void set_resample(bool on)
+    {
+        if (hpfw_gpu_collector_set_resample(c_, on ? 1 : 0) != 0)
+            throw std::runtime_error(std::string("hpfw::GpuCollector::set_resample: ") + hpfw_gpu_last_error());
     }
 
     void save() const { par_collector_save(c_, cache_.c_str()); } // parallel_collector.h:61-66

@@ -244,6 +244,25 @@ int hpfw_gpu_combiner_align_device(hpfw_gpu *h, const uint16_t *d_q_hp, const in
  * only (HPFW_E_IO otherwise).  *n = samples in the file; out receives them when cap >= *n (out may be NULL). */
 int hpfw_gpu_wav_read_pcm16(const char *path, int16_t *out, int64_t cap, int64_t *n);
 
+/* a WAV file at its own rate (8 000 .. 192 000 Hz): PCM16 mono, or stereo averaged (truncating) to mono, not resampled.
+ * *rate = the file's sample rate; other bit depths, more than two channels, non-PCM files and rates outside the range
+ * are HPFW_E_IO.  *n and out as hpfw_gpu_wav_read_pcm16. */
+int hpfw_gpu_wav_read_pcm16_any(const char *path, int16_t *out, int64_t cap, int64_t *n, int32_t *rate);
+
+/* ---- sample-rate conversion to 44.1 kHz (essentia MonoLoader's resampling, cqt.h:45-47, mel.h:42-44) -------------
+ * Polyphase windowed sinc in exact integer arithmetic: g = gcd(44100, rate), L = 44100 / g,
+ * M = rate / g; output m sits at input time m M / L and is clamp((sum_j x[floor(m M / L) - H + 1 + j] h[(m M) mod L][j]
+ * + 2^13) >> 14) over T = 2 H int16 taps per phase, x = 0 outside the clip.  n_out = ceil(n_in L / M).  44 100 Hz is
+ * a plain copy.  Rates outside [8 000, 192 000] are HPFW_E_INVALID. */
+int hpfw_gpu_resample_length(int64_t n_in, int rate, int64_t *n_out); /* host only */
+/* the [L][T] int16 table (host only; taps may be NULL to ask for L, M, T; cap = its capacity).  44 100 Hz: L = M = 1,
+ * T = 0. */
+int hpfw_gpu_resample_table(int rate, int16_t *taps, int64_t cap, int32_t *L, int32_t *M, int32_t *T);
+/* n_clips clips of n_in samples back to back -> d_out [n_clips][n_out] (device entry point) */
+int hpfw_gpu_resample_pcm16(hpfw_gpu *h, const int16_t *d_in, int64_t n_in, int64_t n_clips, int rate, int16_t *d_out,
+                            void *stream);
+int hpfw_gpu_resample_pcm16_host(hpfw_gpu *h, const int16_t *in, int64_t n_in, int64_t n_clips, int rate, int16_t *out);
+
 /* ---- filter learning: ParallelCollector::preprocess + calc_filters ------------------------
  * (parallel_collector.h:82-112, hashprint_handle.h:96-112).  The handle owns accum_cov
  * (2420 x 2420, parallel_collector.h:76): per clip, the covariance of its context frames (centred
@@ -406,6 +425,10 @@ FilenameHashprintPair *par_collector_calc_hashprints(hpfw_legacy_collector *coll
                                                      const char **filenames, int n);
 void prepare_result_free(FilenameHashprintPair *res, int got);          /* wrapper.hpp:36 */
 void calc_hashprint_result_free(uint64_t *hp);                          /* wrapper.hpp:38 */
+/* not in the reference's FFI: on != 0 makes the collector accept WAV files at any rate in [8 000, 192 000] Hz and
+ * resample them to 44.1 kHz on the GPU before the extraction (hpfw_gpu_resample_pcm16).  Off by default: files at
+ * other rates are skipped with a message, as before. */
+int hpfw_gpu_collector_set_resample(hpfw_legacy_collector *collector, int on);
 
 #ifdef __cplusplus
 }
