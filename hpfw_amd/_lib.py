@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HPFW_GPU_LIB") or os.path.join(_HERE, "lib", "libhpfw_gpu.so")
 
 HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("offset", "<i4"), ("pad", "<u4")])
+# hpfw_shift_hit: a hit of the transposed search and the index of its shift in the caller's list (-1 = none)
+SHIFT_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("offset", "<i4"), ("shift_index", "<i4")])
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
 # hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
 COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
@@ -48,6 +50,8 @@ EXPORTS = (
     "hpfw_gpu_combiner_find_device", "hpfw_gpu_combiner_align", "hpfw_gpu_combiner_align_device", "hpfw_gpu_wav_read_pcm16",
     "hpfw_gpu_wav_read_pcm16_any", "hpfw_gpu_resample_length", "hpfw_gpu_resample_table", "hpfw_gpu_resample_pcm16",
     "hpfw_gpu_resample_pcm16_host", "hpfw_gpu_collector_set_resample",
+    "hpfw_gpu_extract_transposed_pcm16", "hpfw_gpu_extract_transposed_pcm16_host", "hpfw_gpu_hashprints_from_db_transposed",
+    "hpfw_gpu_search_topk_transposed_device", "hpfw_gpu_search_topk_transposed",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -75,7 +79,16 @@ class FilenameHashprintPair(ctypes.Structure):
 
 
 class HpfwError(RuntimeError):
-    pass
+    """a failed library call; status is its hpfw_status (HPFW_E_*), None when the failure was not a library status"""
+
+    def __init__(self, msg, status=None):
+        super().__init__(msg)
+        self.status = status
+
+
+# hpfw_status values (include/hpfw_gpu.h)
+E_INVALID, E_UNSUPPORTED, E_NOFILTERS, E_HIP, E_NOMEM, E_IO = -1, -2, -3, -4, -5, -6
+MAX_SHIFTS, MAX_ABS_SHIFT = 64, 120
 
 
 _lib = None
@@ -173,6 +186,11 @@ def lib():
     L.hpfw_gpu_resample_pcm16.argtypes = [vp, vp, i64, i64, i32, vp, vp]
     L.hpfw_gpu_resample_pcm16_host.argtypes = [vp, vp, i64, i64, i32, vp]
     L.hpfw_gpu_collector_set_resample.argtypes = [vp, i32]
+    L.hpfw_gpu_extract_transposed_pcm16.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
+    L.hpfw_gpu_extract_transposed_pcm16_host.argtypes = [vp, vp, i64, i64, vp, i32, vp]
+    L.hpfw_gpu_hashprints_from_db_transposed.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
+    L.hpfw_gpu_search_topk_transposed_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    L.hpfw_gpu_search_topk_transposed.argtypes = [vp, vp, vp, i64, i32, i32, vp]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -196,7 +214,20 @@ def lib():
 
 def check(rc):
     if rc != 0:
-        raise HpfwError(f"hpfw_gpu error {rc}: {lib().hpfw_gpu_last_error().decode()}")
+        raise HpfwError(f"hpfw_gpu error {rc}: {lib().hpfw_gpu_last_error().decode()}", rc)
+
+
+def check_shifts(shifts):
+    """the bin shifts of a transposed query as the library accepts them: 1 to 64 distinct integers, |s| <= 120
+    (ValueError otherwise); returned as a list of int"""
+    out = [int(s) for s in shifts]
+    if not 1 <= len(out) <= MAX_SHIFTS:
+        raise ValueError(f"shifts: 1 to {MAX_SHIFTS} values, got {len(out)}")
+    if any(abs(s) > MAX_ABS_SHIFT for s in out):
+        raise ValueError(f"shifts: |s| <= {MAX_ABS_SHIFT}, got {out}")
+    if len(set(out)) != len(out):
+        raise ValueError(f"shifts: values must be distinct, got {out}")
+    return out
 
 
 def _hp(a):
@@ -263,6 +294,28 @@ class Gpu:
         hp = np.zeros((pcm.shape[0], g.n_hp), np.uint64)
         check(lib().hpfw_gpu_extract_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], _hp(hp)))
         return hp
+
+    # ---- transposed queries -------------------------------------------
+    def extract_transposed(self, pcm, shifts):
+        """pcm int16 [n] or [n_clips][n] -> uint64 [n_clips][len(shifts)][n_hp]: shift s hashes the dB spectrogram moved by
+        s bins (row b = row b + s, -80 dB outside); 24 bins per octave, so t semitones up is s = 2t"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        sh = np.ascontiguousarray(shifts, np.int32).ravel()
+        g = self.geometry(pcm.shape[1])
+        hp = np.zeros((pcm.shape[0], sh.size, max(g.n_hp, 0)), np.uint64)
+        check(lib().hpfw_gpu_extract_transposed_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], _hp(sh), sh.size,
+                                                           _hp(hp)))
+        return hp
+
+    def extract_transposed_dev(self, d_pcm, n_samples, n_clips, shifts, d_hp, stream=0):
+        sh = np.ascontiguousarray(shifts, np.int32).ravel()
+        check(lib().hpfw_gpu_extract_transposed_pcm16(self._h, d_pcm, n_samples, n_clips, _hp(sh), sh.size, d_hp, stream))
+
+    def hashprints_from_db_transposed_dev(self, d_db, n_clips, c, shifts, d_hp, stream=0):
+        sh = np.ascontiguousarray(shifts, np.int32).ravel()
+        check(lib().hpfw_gpu_hashprints_from_db_transposed(self._h, d_db, n_clips, c, _hp(sh), sh.size, d_hp, stream))
 
     # ---- sample-rate conversion to 44.1 kHz (k_resample.hip) --------------------------------
     def resample_dev(self, d_in, n_in, n_clips, rate, d_out, stream=0):
@@ -539,6 +592,21 @@ class Gpu:
         check(lib().hpfw_gpu_knn_windows(self._h, _hp(q), _hp(off), off.size - 1, _hp(keys), keys.size))
         return keys
 
+    def search_topk_transposed(self, q_hp, q_off, n_shifts, k):
+        """q_off [n_q * n_shifts + 1]: query set q * n_shifts + i is shift i of query q -> SHIFT_HIT_DTYPE [n_q][k]"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        if (off.size - 1) % n_shifts:
+            raise ValueError("q_off must hold n_q * n_shifts + 1 offsets")
+        out = np.zeros(((off.size - 1) // n_shifts, k), SHIFT_HIT_DTYPE)
+        check(lib().hpfw_gpu_search_topk_transposed(self._h, _hp(q), _hp(off), out.shape[0], int(n_shifts), int(k), _hp(out)))
+        return out
+
+    def search_topk_transposed_dev(self, d_q, q_off, n_shifts, k, d_out, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_search_topk_transposed_device(self._h, d_q, _hp(off), (off.size - 1) // n_shifts, int(n_shifts),
+                                                            int(k), d_out, stream))
+
     def search_topk_dev(self, d_q, q_off, k, d_out, stream=0):
         off = np.ascontiguousarray(q_off, np.int64)
         check(lib().hpfw_gpu_search_topk_device(self._h, d_q, _hp(off), off.size - 1, int(k), d_out, stream))
@@ -600,6 +668,14 @@ def wav_read_any(path):
     out = np.zeros(max(n.value, 1), np.int16)
     check(lib().hpfw_gpu_wav_read_pcm16_any(p, _hp(out), out.size, ctypes.byref(n), ctypes.byref(rate)))
     return out[:n.value], int(rate.value)
+
+
+def read_wav_44k(gpu, path, resample):
+    """a WAV file's PCM at 44.1 kHz: wav_read, or with `resample` wav_read_any converted on `gpu` (Gpu.resample)"""
+    if not resample:
+        return wav_read(path)
+    x, rate = wav_read_any(path)
+    return gpu.resample(x, rate) if rate != 44100 and x.size else x
 
 
 def resample_length(n_in, rate):

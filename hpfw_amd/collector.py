@@ -74,6 +74,12 @@ class ParallelCollector:
         self.__lib.prepare_result_free(hps, len(pyarr))
         return out
 
+    def gpu(self) -> "_lib.Gpu":
+        """a view of the collector's own handle, which holds the filters prepare() learned or load() read (not owned)"""
+        f = self.__lib.hpfw_internal_collector_gpu
+        f.argtypes, f.restype = [ctypes.c_void_p], ctypes.c_void_p
+        return _lib.Gpu.from_handle(f(self.__collector))
+
     def load(self, cache: str = ""):
         self.__lib.par_collector_load(self.__collector, cache.encode("utf-8"))
 

@@ -65,10 +65,7 @@ class AudioCombiner:
         return [(f, self._gpu.mel_hashprints(x)[0] if x.size else np.zeros(0, np.uint16)) for f, x in zip(filenames, pcm)]
 
     def _read(self, filename):
-        if not self._resample:
-            return _lib.wav_read(filename)
-        x, rate = _lib.wav_read_any(filename)
-        return self._gpu.resample(x, rate) if rate != 44100 and x.size else x
+        return _lib.read_wav_44k(self._gpu, filename, self._resample)
 
     def build(self, pairs: Sequence[Tuple[str, np.ndarray]]):
         names = [name for name, _ in pairs]

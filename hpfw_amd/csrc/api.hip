@@ -328,6 +328,11 @@ struct hpfw_gpu {
     };
     std::map<int, RsTable> rs_tables;
     DevBuf rs_in, rs_out;
+    // transposed queries (k_project_q.hip): the filter images of the shift list last used (cleared
+    // with the filters), the per-shift top-k lists of the search
+    DevBuf d_shift_images;
+    std::vector<int32_t> shift_images_of;
+    DevBuf d_shift_hits;
 };
 
 namespace {
@@ -1049,6 +1054,45 @@ int run_back(hpfw_gpu *h, DevPlan *dp, int ns, uint64_t *d_hp, hipStream_t s)
 
 constexpr int kBackBatch = 1024; // clips per projection launch: ~10^4 workgroups, a small launch tail
 
+// shifts of the transposed entry points: 1..64 distinct values, |s| <= 120 (checked before anything else)
+int check_shifts(const int32_t *shifts, int n_shifts)
+{
+    if (!shifts || n_shifts < 1 || n_shifts > hpfw::kMaxShifts) return fail(HPFW_E_INVALID, "shifts: 1 to 64 values");
+    for (int i = 0; i < n_shifts; ++i) {
+        if (shifts[i] < -(hpfw::kBins - 1) || shifts[i] > hpfw::kBins - 1) return fail(HPFW_E_INVALID, "shifts: |s| <= 120");
+        for (int j = 0; j < i; ++j)
+            if (shifts[j] == shifts[i]) return fail(HPFW_E_INVALID, "shifts: values must be distinct");
+    }
+    return 0;
+}
+
+// the shifted filter images of `shifts` on stream s (kept while the list and the filters stay the same)
+int shift_images(hpfw_gpu *h, const int32_t *shifts, int n_shifts, hipStream_t s)
+{
+    std::vector<int32_t> want(shifts, shifts + n_shifts);
+    if (want == h->shift_images_of) return 0;
+    h->shift_images_of.clear();
+    int rc;
+    if ((rc = ensure(h->d_shift_images, (size_t)n_shifts * hpfw::project_q_image_bytes()))) return rc;
+    hpfw::ShiftList sl{n_shifts, {}};
+    for (int i = 0; i < n_shifts; ++i) sl.s[i] = shifts[i];
+    hpfw::launch_shift_filter_images(h->d_fq_image.get(), sl, h->d_shift_images.get(), s);
+    if ((rc = check_launch("shift_filter_images"))) return rc;
+    h->shift_images_of = std::move(want);
+    return 0;
+}
+
+// the common checks of the transposed extraction entry points
+int check_transposed(hpfw_gpu *h, const int32_t *shifts, int n_shifts)
+{
+    int rc;
+    if ((rc = check_shifts(shifts, n_shifts))) return rc;
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    if (!h->projection) return fail(HPFW_E_INVALID, "transposed extraction needs projection mode 1 (fixed point)");
+    if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters: call hpfw_gpu_set_filters or hpfw_gpu_learn_filters first");
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -1119,6 +1163,7 @@ int hpfw_gpu_set_filters(hpfw_gpu *h, const float *f)
     hpfw::pack_filters_q(f, image);
     if (!h->d_fq_image) HIP_TRY(h->d_fq_image.alloc(image.size()));
     HIP_TRY(hipMemcpy(h->d_fq_image.get(), image.data(), image.size(), hipMemcpyHostToDevice));
+    h->shift_images_of.clear();
     h->has_filters = true;
     return 0;
 }
@@ -1176,6 +1221,31 @@ int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int6
         }
         hpfw::launch_hashprints_q(h->d_fq_image.get(), d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s);
         return check_launch("project");
+    });
+}
+
+int hpfw_gpu_hashprints_from_db_transposed(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, const int32_t *shifts,
+                                           int n_shifts, uint64_t *d_hp, void *stream)
+{
+    int rc = check_transposed(h, shifts, n_shifts);
+    if (rc) return rc;
+    if (!d_db || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    const int64_t nhp = c - (hpfw::kCtx - 1) - hpfw::kLag;
+    if (nhp <= 0 || n_clips == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        int rc;
+        if ((rc = shift_images(h, shifts, n_shifts, s))) return rc;
+        const int nbmax = 256;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            Timed t(h, K_PROJECT, s);
+            hpfw::launch_hashprints_q_shifted(h->d_shift_images.get(), n_shifts, d_db + c0 * 121 * c, nullptr, nb, (int)c,
+                                              d_hp + c0 * n_shifts * nhp, s);
+            if ((rc = check_launch("project"))) return rc;
+        }
+        return 0;
     });
 }
 
@@ -1263,6 +1333,62 @@ int hpfw_gpu_extract_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples,
         }
         return 0;
     });
+}
+
+int hpfw_gpu_extract_transposed_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts,
+                                      int n_shifts, uint64_t *d_hp, void *stream)
+{
+    int rc = check_transposed(h, shifts, n_shifts);
+    if (rc) return rc;
+    if (!d_pcm || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    DevPlan *dp;
+    if ((rc = get_plan(h, n_samples, &dp))) return rc;
+    if (dp->hp.n_hp <= 0) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint");
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if ((rc = shift_images(h, shifts, n_shifts, s))) return rc;
+        const int nbmax = pass_clips(h, dp, n_clips);
+        const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
+        if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
+        for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
+            const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
+            for (int c0 = 0; c0 < ns; c0 += nbmax) {
+                const int nb = std::min(nbmax, ns - c0);
+                if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
+            }
+            {
+                Timed t(h, K_PROJECT, s);
+                hpfw::launch_hashprints_q_shifted(h->d_shift_images.get(), n_shifts, h->ws[2].as<float>(), h->d_clipmax.as<float>(), ns,
+                                                  (int)dp->hp.c, d_hp + s0 * n_shifts * dp->hp.n_hp, s);
+            }
+            if ((rc = check_launch("project"))) return rc;
+        }
+        return 0;
+    });
+}
+
+int hpfw_gpu_extract_transposed_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts,
+                                           int n_shifts, uint64_t *hp)
+{
+    int rc = check_transposed(h, shifts, n_shifts);
+    if (rc) return rc;
+    if (!pcm || !hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hpfw_geometry g;
+    if ((rc = hpfw_gpu_geometry(h, n_samples, &g))) return rc;
+    if (n_clips == 0) return 0;
+    DevBuf d_pcm, d_hp;
+    if (d_pcm.alloc((size_t)n_clips * n_samples * 2) != hipSuccess || d_hp.alloc((size_t)n_clips * n_shifts * std::max<int64_t>(g.n_hp, 1) * 8) != hipSuccess)
+        return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    hipStream_t s = nullptr;
+    if (hipMemcpyAsync(d_pcm.get(), pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    rc = hpfw_gpu_extract_transposed_pcm16(h, d_pcm.as<int16_t>(), n_samples, n_clips, shifts, n_shifts, d_hp.as<uint64_t>(), s);
+    if (!rc && hipMemcpyAsync(hp, d_hp.get(), (size_t)n_clips * n_shifts * g.n_hp * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = fail(HPFW_E_HIP, "D2H copy failed");
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "kernel execution failed");
+    return rc;
 }
 
 int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
@@ -2322,6 +2448,49 @@ int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
     int rc = hpfw_gpu_search_topk_device(h, d_q.as<uint64_t>(), rel.data(), n_q, k, d_out.as<hpfw_hit>(), nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
     if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_q * k * sizeof(hpfw_hit), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(HPFW_E_HIP, "D2H copy failed");
+    return rc;
+}
+
+int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                           hpfw_shift_hit *d_out, void *stream)
+{
+    if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts)
+        return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        int rc;
+        // the per-shift lists: n_q * n_shifts queries in one pass of the existing scan, then one workgroup per query merges them
+        if ((rc = ensure(h->d_shift_hits, (size_t)n_q * n_shifts * k * sizeof(hpfw_hit)))) return rc;
+        if ((rc = hpfw_gpu_search_topk_device(h, d_q_hp, q_off, n_q * n_shifts, k, h->d_shift_hits.as<hpfw_hit>(), s))) return rc;
+        {
+            Timed t(h, K_TOPK, s);
+            hpfw::launch_topk_merge_shifts(h->d_shift_hits.get(), (int)n_q, n_shifts, k, d_out, s);
+        }
+        return check_launch("topk_merge_shifts");
+    });
+}
+
+int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                    hpfw_shift_hit *out)
+{
+    if (!h || !q_off || !out || n_q < 0 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts) return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    const int64_t nq = n_q * n_shifts, total = q_off[nq] - q_off[0];
+    DevBuf d_q, d_out;
+    HIP_TRY(d_q.alloc((size_t)std::max<int64_t>(total, 1) * 8));
+    if (d_out.alloc((size_t)n_q * k * sizeof(hpfw_shift_hit)) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    std::vector<int64_t> rel((size_t)nq + 1);
+    for (int64_t i = 0; i <= nq; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    if (total && hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = hpfw_gpu_search_topk_transposed_device(h, d_q.as<uint64_t>(), rel.data(), n_q, n_shifts, k, d_out.as<hpfw_shift_hit>(), nullptr);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
+    if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_q * k * sizeof(hpfw_shift_hit), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(HPFW_E_HIP, "D2H copy failed");
     return rc;
 }

@@ -258,6 +258,214 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
 #endif
 }
 
+// Transposed extraction: fq_image holds n_shifts digit images one after the other, image i the
+// filters moved by shift i along the bins (shift_filter_images_kernel).  The staging, the matrix loop and the epilogue are
+// those of hashprint_q_kernel above (see its comments); the slab is staged once and each image in turn runs the matrix
+// loop and the epilogue over it, hp [clip][shift][nhp].  A kernel of its own, so that the extraction's kernel stays as
+// it was compiled before.
+template <bool FROM_T>
+__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_shift_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
+                                                                         const float *__restrict__ tmax, int c, int nhp, int n_tiles_x,
+                                                                         int n_clips, int n_shifts, uint64_t *__restrict__ hp)
+{
+    unsigned char *slab = smem_raw;                                   // [chunk][column (pitch 160)][digit][16]
+    unsigned short *parts = reinterpret_cast<unsigned short *>(smem_raw + kQSlabBytes); // [hashprint][wave]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kg = lane >> 4, cl = lane & 15;  // this lane's group of 16 k' inside a step; its column (B) / filter (A) in a tile
+    // (clip, tile) in XCD-aware order, as hashprint_q_kernel
+    const unsigned per_xcd = (gridDim.x + 7) / 8;
+    const unsigned t = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
+    const int clip = t / n_tiles_x;
+    const int n0 = (t - clip * n_tiles_x) * kQTileN;
+    const float *S = sdb + (int64_t)clip * kBins * c;
+    const float ref = FROM_T ? tmax[clip] : 0.0f;
+    // the wave's filter digits of the first two steps are on their way while the slab is quantised
+    const v4i *img = fq_image + (size_t)wave * kQSteps * (kQStepBytes / 16) + lane;
+    v4i a[3][3]; // three register sets in turn: the loads of step s + 2 are issued before the products of step s
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        a[0][d] = img[d * 64];
+        a[1][d] = img[(kQStepBytes / 16) + d * 64];
+    }
+    // slab: one (chunk, column) unit = 16 bins of one column of Du, three digit planes.  The loads of a round (16 bins x
+    // the column and its partner 80 on) are all issued before the first value is quantised
+    constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
+#pragma unroll 1
+    for (int r0 = 0; r0 < kUnits; r0 += 2) {
+        float va[2][16], vb[2][16];
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int unit = tid + (r0 + rr) * kQThreads;
+            const int q = unit / kQCols, col = unit - q * kQCols;
+            const int gc = n0 + col;
+            const bool in = r0 + rr < kUnits && unit < kQChunks * kQCols && gc + kLag < c;
+            // every load issued from a valid address, zeroed afterwards (see hashprint_q_kernel)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int bin = 16 * q + e;
+                const bool ok = in && bin < kBins;
+                const unsigned idx = ok ? (unsigned)(bin * c + gc) : 0u; // (clip-relative: < 121 * c, 32 bits; S[0] and S[kLag] exist)
+                va[rr][e] = S[idx];
+                vb[rr][e] = S[idx + kLag];
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int unit = tid + (r0 + rr) * kQThreads;
+            const int q = unit / kQCols, col = unit - q * kQCols;
+            const bool in = r0 + rr < kUnits && unit < kQChunks * kQCols && n0 + col + kLag < c;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const bool ok = in && 16 * q + e < kBins;
+                va[rr][e] = ok ? va[rr][e] : 0.0f;
+                vb[rr][e] = ok ? vb[rr][e] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int unit = tid + (r0 + rr) * kQThreads;
+            if (r0 + rr >= kUnits || unit >= kQChunks * kQCols) break;
+            const int q = unit / kQCols, col = unit - q * kQCols;
+            unsigned w0[4] = {0, 0, 0, 0}, w1[4] = {0, 0, 0, 0}, w2[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                float xa = va[rr][e], xb = vb[rr][e];
+                if (FROM_T) {
+                    xa -= ref;
+                    xb -= ref;
+                }
+                // (values outside the slab's valid part were loaded as 0 on both sides: Du = 0, digits 0)
+                const unsigned d = q_digit_bytes(q_fixed(xa) - q_fixed(xb));
+                w0[e >> 2] |= (d & 255u) << (8 * (e & 3));
+                w1[e >> 2] |= ((d >> 8) & 255u) << (8 * (e & 3));
+                w2[e >> 2] |= ((d >> 16) & 255u) << (8 * (e & 3));
+            }
+            v4i *dst = reinterpret_cast<v4i *>(slab + (size_t)(q * kQPitch + col) * kQUnit);
+            dst[0] = v4i{(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3]};
+            dst[1] = v4i{(int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
+            dst[2] = v4i{(int)w2[0], (int)w2[1], (int)w2[2], (int)w2[3]};
+        }
+    }
+    __syncthreads(); // the only barrier before the epilogue: the slab is read-only from here on
+#pragma unroll 1
+    for (int sh = 0; sh < n_shifts; ++sh) {
+        if (sh > 0) { // the next image's first two steps (the slab stays)
+            img += (size_t)4 * kQSteps * kQStepBytes / 16;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                a[0][d] = img[d * 64];
+                a[1][d] = img[(kQStepBytes / 16) + d * 64];
+            }
+        }
+        // tiles of 16 hashprints that hold any (the last workgroup of a clip); the products of the others are skipped
+        const int n_tiles = min(8, (nhp - n0 + 15) / 16);
+        v4i acc[8][5];
+#pragma unroll
+        for (int f = 0; f < 8; ++f)
+#pragma unroll
+            for (int cls = 0; cls < 5; ++cls) acc[f][cls] = v4i{0, 0, 0, 0};
+        // B operand of (step, tile f): chunk 4 (s & 1) + kg, column 16 f + cl + (s >> 1)
+        const unsigned char *bl = slab + (size_t)(kg * kQPitch + cl) * kQUnit;
+        auto step = [&](int s, const v4i (&aw)[3]) {
+            const unsigned char *bs = bl + (size_t)((4 * (s & 1)) * kQPitch + (s >> 1)) * kQUnit;
+            // the operand reads of tile f + 1 are issued before the nine products of tile f
+            v4i nb0, nb1, nb2;
+            {
+                const v4i *bu = reinterpret_cast<const v4i *>(bs);
+                nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
+            }
+#pragma unroll
+            for (int f = 0; f < 8; ++f) {
+                if (f < n_tiles) {
+                    const v4i b0 = nb0, b1 = nb1, b2 = nb2;
+                    if (f + 1 < 8) { // (tile f + 1 of the slab exists whether or not it holds hashprints)
+                        const v4i *bu = reinterpret_cast<const v4i *>(bs + (size_t)(16 * (f + 1)) * kQUnit);
+                        nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
+                    }
+                    __builtin_amdgcn_sched_barrier(0); // (the scheduler would sink the reads back to where they are used)
+                    // filter digit i times spectrogram digit j goes to accumulator i + j
+                    acc[f][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b0, acc[f][0], 0, 0, 0);
+                    acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b1, acc[f][1], 0, 0, 0);
+                    acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b2, acc[f][2], 0, 0, 0);
+                    acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b2, acc[f][3], 0, 0, 0);
+                    acc[f][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b2, acc[f][4], 0, 0, 0);
+                    acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b0, acc[f][1], 0, 0, 0);
+                    acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b1, acc[f][2], 0, 0, 0);
+                    acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b1, acc[f][3], 0, 0, 0);
+                    acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b0, acc[f][2], 0, 0, 0);
+                }
+            }
+        };
+        auto load_a = [&](int s, v4i (&aw)[3]) {
+            if (s < kQSteps) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) aw[d] = img[(size_t)s * (kQStepBytes / 16) + d * 64];
+            }
+        };
+        if (n_tiles > 0) {
+#pragma unroll 1
+            for (int s = 0; s < kQSteps - 1; s += 3) { // 40 steps = 13 x 3 + 1
+                load_a(s + 2, a[2]);
+                step(s, a[0]);
+                load_a(s + 3, a[0]);
+                step(s + 1, a[1]);
+                load_a(s + 4, a[1]);
+                step(s + 2, a[2]);
+            }
+            step(kQSteps - 1, a[0]);
+        }
+        // S10q: D = sum_c acc_c 2^(8c); D layout of the 16x16 tile: column (hashprint) = lane & 15, row (filter) = 4 (lane >> 4) + reg
+#pragma unroll
+        for (int f = 0; f < 8; ++f) {
+            unsigned bits = 0; // this wave's 16 filters of hashprint n0 + 16 f + cl, filter 16 wave + row at bit 15 - row
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int row = 4 * kg + reg;
+                long long v = acc[f][4][reg];
+#pragma unroll
+                for (int cls = 3; cls >= 0; --cls) v = v * 256 + acc[f][cls][reg];
+                bits |= (unsigned)(v >= 0) << (15 - row);
+            }
+            // the four lanes of a column hold four filters each
+            bits |= (unsigned)__shfl_xor((int)bits, 16);
+            bits |= (unsigned)__shfl_xor((int)bits, 32);
+            if (kg == 0) parts[(16 * f + cl) * 4 + wave] = (unsigned short)bits;
+        }
+        __syncthreads();
+        if (tid < kQTileN && n0 + tid < nhp) {
+            const unsigned short *p = parts + tid * 4;
+            hp[((int64_t)clip * n_shifts + sh) * nhp + n0 + tid] = ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
+        }
+        __syncthreads(); // parts is written again by the next image's epilogue
+    }
+}
+
+// Image i (blockIdx.y) of the filters moved by shifts.s[i] bins: the byte of bin b holds the digit of fq[r][20 (b - s) + t]
+// taken from the unshifted image (so the row scale is the unshifted filter's), zero where b - s is not a bin.  One
+// thread per 16-byte unit [wave][step][digit][lane] of the image.
+__global__ __launch_bounds__(256) void shift_filter_images_kernel(const unsigned char *__restrict__ base, ShiftList shifts,
+                                                                  v4i *__restrict__ out)
+{
+    constexpr int kUnits = 4 * kQSteps * kQStepBytes / 16;
+    const int u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= kUnits) return;
+    const int s = shifts.s[blockIdx.y];
+    const int l = u & 63, i = (u >> 6) % 3, ws = u / 192;
+    const int step = ws % kQSteps, w = ws / kQSteps, t = step >> 1, p = step & 1;
+    unsigned wd[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int b = 64 * p + 16 * (l >> 4) + e, src = b - s;
+        if (b < kBins && src >= 0 && src < kBins) {
+            const unsigned char v = base[((size_t)w * kQSteps + 2 * t + (src >> 6)) * kQStepBytes + ((size_t)i * 64 + (l & 15) + 16 * ((src >> 4) & 3)) * 16 +
+                                         (src & 15)];
+            wd[e >> 2] |= (unsigned)v << (8 * (e & 3));
+        }
+    }
+    out[(size_t)blockIdx.y * kUnits + u] = v4i{(int)wd[0], (int)wd[1], (int)wd[2], (int)wd[3]};
+}
+
 // host: the filters' digits as the A operand of v_mfma_i32_16x16x64_i8, [wave][step s = 2 t + p][digit][lane][16 bytes]:
 // byte e of lane l = digit of fq[row = 16 wave + (l & 15)][k = 20 bin + t], bin = 64 p + 16 (l >> 4) + e (zero for bin >= 121)
 void pack_filters_q(const float *f, std::vector<int8_t> &image)
@@ -317,6 +525,38 @@ void launch_hashprints_q(const void *d_fq_image, const float *d_db, const float 
     else
         hipLaunchKernelGGL(hashprint_q_kernel<false>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_fq_image), d_db, d_tmax,
                            c, nhp, tiles, n_clips, d_hp, d_dbg);
+}
+
+void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s)
+{
+    constexpr int kUnits = 4 * kQSteps * kQStepBytes / 16;
+    hipLaunchKernelGGL(shift_filter_images_kernel, dim3((kUnits + 255) / 256, shifts.n), dim3(256), 0, s,
+                       static_cast<const unsigned char *>(d_fq_image), shifts, static_cast<v4i *>(d_images));
+}
+
+// the hashprints of n_shifts shifts of every clip, hp [n_clips][n_shifts][c - 99], from the images of
+// launch_shift_filter_images: one launch, the slab of a (clip, tile) staged once for all shifts
+void launch_hashprints_q_shifted(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c,
+                                 uint64_t *d_hp, hipStream_t s)
+{
+    static PerDeviceOnce attr_set;
+    if (attr_set.need()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hashprint_q_shift_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kQLdsBytes);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hashprint_q_shift_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kQLdsBytes);
+        attr_set.mark();
+    }
+    const int nhp = c - (kCtx - 1) - kLag;
+    if (nhp <= 0 || n_clips <= 0 || n_shifts <= 0) return;
+    const int tiles = (nhp + kQTileN - 1) / kQTileN;
+    const dim3 grid(8 * (unsigned)(((int64_t)tiles * n_clips + 7) / 8));
+    if (d_tmax)
+        hipLaunchKernelGGL(hashprint_q_shift_kernel<true>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db,
+                           d_tmax, c, nhp, tiles, n_clips, n_shifts, d_hp);
+    else
+        hipLaunchKernelGGL(hashprint_q_shift_kernel<false>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db,
+                           d_tmax, c, nhp, tiles, n_clips, n_shifts, d_hp);
 }
 
 } // namespace hpfw

@@ -278,6 +278,75 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t *__restr
     }
 }
 
+// Transposed search: query q's per-shift top-k lists in[q][shift][k] -> its k best clips, each with
+// its smallest (dist, shift index).  One workgroup per query, the n = S k <= 4096 candidates in LDS: sorted by (clip, dist,
+// candidate) the first entry of a clip is its best (a clip appears at most once per list, and the candidate index i =
+// shift k + rank orders equal distances by shift); the others are dropped and the rest sorted by (dist, clip).  dist < 2^20
+// (queries of at most 16 000 hashprints) and i < 2^12 make both keys 64 bits.  Exact: a clip missing from its best shift's
+// list has k clips ahead of it there, so it is not among the k best.
+struct ShiftHitDev {
+    uint32_t dist, clip;
+    int32_t offset, shift_index;
+};
+constexpr int kMergeMax = 64 * 64;
+
+__device__ void bitonic_sort_lds(uint64_t *key, int np, int tid)
+{
+    for (int size = 2; size <= np; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < np; i += 256) {
+                const int j = i ^ stride;
+                if (j > i) {
+                    const uint64_t a = key[i], b = key[j];
+                    if ((a > b) == ((i & size) == 0)) {
+                        key[i] = b;
+                        key[j] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+__global__ __launch_bounds__(256) void topk_merge_shifts_kernel(const HitDev *__restrict__ in, int n_shifts, int k,
+                                                                ShiftHitDev *__restrict__ out)
+{
+    __shared__ uint64_t key[kMergeMax];
+    const int tid = threadIdx.x, q = blockIdx.x, n = n_shifts * k;
+    int np = 1;
+    while (np < n) np <<= 1;
+    const HitDev *row = in + (int64_t)q * n;
+    for (int i = tid; i < np; i += 256)
+        key[i] = i < n && row[i].clip != 0xffffffffu ? ((uint64_t)row[i].clip << 32) | ((uint64_t)row[i].dist << 12) | (uint64_t)i : ~0ull;
+    __syncthreads();
+    bitonic_sort_lds(key, np, tid);
+    uint64_t mine[kMergeMax / 256];
+    for (int i = tid, r = 0; i < np; i += 256, ++r) {
+        const uint64_t v = key[i];
+        const bool first = v != ~0ull && (i == 0 || (key[i - 1] >> 32) != (v >> 32));
+        mine[r] = first ? ((uint64_t)row[v & 4095].dist << 44) | ((v >> 32) << 12) | (v & 4095) : ~0ull;
+    }
+    __syncthreads();
+    for (int i = tid, r = 0; i < np; i += 256, ++r) key[i] = mine[r];
+    __syncthreads();
+    bitonic_sort_lds(key, np, tid);
+    for (int t = tid; t < k; t += 256) {
+        const uint64_t v = t < np ? key[t] : ~0ull;
+        ShiftHitDev h{0xffffffffu, 0xffffffffu, 0, -1};
+        if (v != ~0ull) {
+            const int i = (int)(v & 4095);
+            h = {row[i].dist, row[i].clip, row[i].offset, i / k};
+        }
+        out[(int64_t)q * k + t] = h;
+    }
+}
+
+void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(topk_merge_shifts_kernel, dim3(n_q), dim3(256), 0, s, static_cast<const HitDev *>(d_in), n_shifts, k,
+                       static_cast<ShiftHitDev *>(d_out));
+}
+
 size_t topk_scratch_bytes(int n_q, int k) { return (size_t)n_q * kTkSlices * k * (sizeof(uint64_t) + sizeof(int32_t)); }
 
 void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_scratch,

@@ -245,6 +245,17 @@ size_t project_q_image_bytes();
 void pack_filters_q(const float *f_colmajor, std::vector<int8_t> &image);
 void launch_hashprints_q(const void *d_fq_image, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
                          long long *d_dbg, hipStream_t s);
+// transposed extraction: the digit images of the filters moved by each of shifts.s[0 .. n) bins
+// (d_images: n * project_q_image_bytes()), then the hashprints of every shift from one staging of each slab,
+// hp [n_clips][n_shifts][c - 99]
+constexpr int kMaxShifts = 64;
+struct ShiftList {
+    int n;
+    int s[kMaxShifts];
+};
+void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s);
+void launch_hashprints_q_shifted(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c,
+                                 uint64_t *d_hp, hipStream_t s);
 
 // ---- HashprintHandle with other template arguments (k_hashprint_cfg.hip) ----------------------------
 struct CfgArgs {
@@ -325,6 +336,9 @@ void launch_topk(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t c
 size_t topk_scratch_bytes(int n_q, int k);
 void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_scratch,
                           void *d_out, hipStream_t s);
+// per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
+// (dist, shift index), then the k best by (dist, clip)
+void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);
 
 // sample-rate conversion to 44.1 kHz (k_resample.hip)
 constexpr int kRsRateOut = 44100, kRsRateMin = 8000, kRsRateMax = 192000;

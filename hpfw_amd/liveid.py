@@ -7,7 +7,7 @@ search(files) = per query: calc_hashprint -> find -> report       live_song_id.h
 top(files, k) = the notebook's "ten best tracks" per query        liveid.ipynb cell 9
 """
 import os
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -19,6 +19,7 @@ class LiveSongIdentification:
     def __init__(self, cache: str = "", device: int = 0, resample: bool = False):
         """resample: index and search WAV files at any rate in [8 000, 192 000] Hz (ParallelCollector(resample=True))"""
         self.collector = ParallelCollector(resample=resample)
+        self._resample = resample
         self.collector.load(cache)                       # the constructor loads the cache, live_song_id.h:24
         self._cache = cache
         self._gpu = _lib.Gpu(device)
@@ -41,9 +42,13 @@ class LiveSongIdentification:
     def index(self, filenames: Sequence[str]):
         self.build(self.collector.prepare(list(filenames)))
 
-    def top(self, filenames: Sequence[str], k: int = 10):
+    def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None):
         """per query (label, [(distance, name, offset) x <= k]) ordered by (distance, position in the
-        database); None in place of the list for a file that yields no hashprint"""
+        database); None in place of the list for a file that yields no hashprint.  shifts: bin shifts of the query's
+        constant-Q spectrogram to search as well (t semitones above the indexed recording is
+        s = 2t): each clip's smallest distance over them, and every hit is (distance, name, offset, shift)"""
+        if shifts is not None:
+            return self._top_transposed(list(filenames), k, list(shifts))
         hps = self.collector.calc_hashprints(list(filenames))
         good = [i for i, (hp, _) in enumerate(hps) if hp is not None and hp.size]
         out = [(f, None) for f in filenames]
@@ -56,17 +61,50 @@ class LiveSongIdentification:
                                          for h in row if h["clip"] != 0xFFFFFFFF])
         return out
 
-    def search(self, filenames: Sequence[str]):
-        """prints what the reference prints (live_song_id.h:38,47-48,53); returns (wrong, accuracy)"""
+    def _top_transposed(self, filenames: List[str], k: int, shifts: List[int]):
+        shifts = _lib.check_shifts(shifts)
+        extractor = self.collector.gpu()                  # the collector's filters
+        if extractor.get_projection() != 1:
+            raise _lib.HpfwError("transposed search needs projection mode 1 (fixed point)", _lib.E_INVALID)
+        out = [(f, None) for f in filenames]
+        sets, good = [], []
+        for i, f in enumerate(filenames):
+            # a file that yields no hashprint gets None, as calc_hashprints gives it: unreadable or at another rate
+            # (HPFW_E_IO), empty, too short or too long (HPFW_E_UNSUPPORTED); every other failure is raised
+            try:
+                x = _lib.read_wav_44k(self._gpu, f, self._resample)
+                if x.size == 0:
+                    continue
+                sets.extend(extractor.extract_transposed(x, shifts)[0])
+            except _lib.HpfwError as e:
+                if e.status in (_lib.E_IO, _lib.E_UNSUPPORTED):
+                    continue
+                raise
+            good.append(i)
+        if good and self.names:
+            off = np.zeros(len(sets) + 1, np.int64)
+            np.cumsum([hp.size for hp in sets], out=off[1:])
+            hits = self._gpu.search_topk_transposed(np.concatenate(sets), off, len(shifts), k)
+            for row, i in zip(hits, good):
+                out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"]), shifts[int(h["shift_index"])])
+                                         for h in row if h["clip"] != 0xFFFFFFFF])
+        return out
+
+    def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None):
+        """prints what the reference prints (live_song_id.h:38,47-48,53); returns (wrong, accuracy).  With shifts the
+        line of a match also names its shift in bins"""
         wrong = 0
-        for label, best in self.top(filenames, 1):
+        for label, best in self.top(filenames, 1, shifts):
             print("=> Finding", label)
             if not best:
                 continue
-            dist, name, offset = best[0]
+            dist, name, offset = best[0][:3]
             if os.path.splitext(os.path.basename(name))[0] not in label:
                 wrong += 1
-            print(f"=> {name} {dist} {offset}\n")
+            if shifts is None:
+                print(f"=> {name} {dist} {offset}\n")
+            else:
+                print(f"=> {name} {dist} {offset} shift {best[0][3]}\n")
         acc = 1 - wrong / float(len(filenames)) if filenames else 1.0
         print(f"=> {wrong} {acc:g}")
         return wrong, acc

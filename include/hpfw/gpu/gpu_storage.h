@@ -77,6 +77,34 @@ public:
         return out;
     }
 
+    /// a query played in another key: per_shift[i] holds the query's hashprints under shift i
+    /// (hpfw::transposed_hashprints, include/hpfw/gpu/transposed.h); per clip the smallest distance over the shifts, ties
+    /// to the first shift; the k best clips by (distance, position in the database) with the index of their shift
+    struct ShiftResult {
+        std::string filename;
+        size_t cnt;
+        int64_t offset;
+        int shift_index;
+    };
+    auto find_topk_transposed(const std::vector<typename Collector::Hashprint> &per_shift, int k) const -> std::vector<ShiftResult>
+    {
+        std::vector<ShiftResult> out;
+        if (per_shift.empty() || names_.empty()) return out;
+        std::vector<uint64_t> all;
+        std::vector<int64_t> off{0};
+        for (const auto &hp : per_shift) {
+            all.insert(all.end(), hp.begin(), hp.end());
+            off.push_back((int64_t)all.size());
+        }
+        std::vector<hpfw_shift_hit> hits((size_t)k);
+        check(hpfw_gpu_search_topk_transposed(h_, all.empty() ? &dummy_ : all.data(), off.data(), 1, (int)per_shift.size(), k, hits.data()));
+        for (const hpfw_shift_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            out.push_back({names_[hit.clip], (size_t)hit.dist, (int64_t)hit.offset, (int)hit.shift_index});
+        }
+        return out;
+    }
+
     /// find() for many queries in one scan of the database (same result per query as find();
     /// an empty hashprint yields the empty result of storage.h:28)
     auto find_batch(const std::vector<typename Collector::Hashprint> &hps) const -> std::vector<SearchResult>

@@ -373,6 +373,33 @@ int hpfw_gpu_get_projection(hpfw_gpu *h);
 /* dB spectrograms [n_clips][121][c] (device, as hpfw_gpu_stage_spectrogram writes them) -> hashprints
  * [n_clips][c - 99] with the handle's filters and projection mode */
 int hpfw_gpu_hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, uint64_t *d_hp, void *stream);
+/* ---- transposed queries: a performance in another key.  shifts: host array of 1 to 64 distinct
+ * bin shifts, |s| <= 120 (24 bins per octave: t semitones up is s = +2t).  Shift s hashes the clip's dB spectrogram with
+ * row b replaced by row b + s, -80 dB where b + s is not a bin, in projection mode 1; shifts = {0} gives what extraction
+ * gives.  In projection mode 0, and for any other shifts argument, HPFW_E_INVALID.  d_hp [n_clips][n_shifts][n_hp]. */
+int hpfw_gpu_extract_transposed_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips,
+                                      const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream);
+/* host buffers, meant for query batches: device memory for all of pcm and hp is allocated per call, the copies are not
+ * chunked or overlapped (large batches: hpfw_gpu_extract_transposed_pcm16 on device buffers of the caller's) */
+int hpfw_gpu_extract_transposed_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
+                                           const int32_t *shifts, int n_shifts, uint64_t *hp);
+/* dB spectrograms [n_clips][121][c] (device) -> d_hp [n_clips][n_shifts][c - 99] */
+int hpfw_gpu_hashprints_from_db_transposed(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, const int32_t *shifts,
+                                           int n_shifts, uint64_t *d_hp, void *stream);
+/* one result of the transposed search: hpfw_hit and the index (in the caller's shift list) of the winning shift */
+typedef struct {
+    uint32_t dist;       /* smallest distance of the clip over all shifts   */
+    uint32_t clip;       /* as hpfw_hit; 0xffffffff = none                  */
+    int32_t offset;      /* first offset reaching dist in that shift        */
+    int32_t shift_index; /* smallest shift index reaching dist; -1 = none   */
+} hpfw_shift_hit;
+/* query set q * n_shifts + i (q_off [n_q * n_shifts + 1]) holds shift i of query q.  Per clip the smallest distance over
+ * the shifts, ties to the smallest shift index; the k best clips by (dist, clip), padded as hpfw_gpu_search_topk pads.
+ * k <= 64, n_shifts <= 64.  out [n_q][k]. */
+int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                           int n_shifts, int k, hpfw_shift_hit *d_out, void *stream);
+int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
+                                    int k, hpfw_shift_hit *out);
 /* parity checkpoint of mode 1: the exact integer sums D[r][i] = sum_k fq[r][k] (u[k][i] - u[k][i + 80]) whose signs are
  * the hashprint bits, d_delta [n_clips][64][c - 99] int64 (device); d_hp may be NULL.  Same kernel as extraction. */
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp,
