@@ -1026,8 +1026,9 @@ int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, 
     return check_launch("db");
 }
 
-// back end for ns clips: dB spectrograms of the S workspace -> hashprints
-int run_back(hpfw_gpu *h, DevPlan *dp, int ns, uint64_t *d_hp, hipStream_t s)
+// back end for ns clips: dB spectrograms of the S workspace -> hashprints [ns][max(n_shifts, 1)][n_hp] of the filter
+// images at `images` as launch_hashprints_q takes them (the f32 chain: the handle's filters, n_shifts = 0)
+int run_back(hpfw_gpu *h, DevPlan *dp, const void *images, int n_shifts, int ns, uint64_t *d_hp, hipStream_t s)
 {
     const hpfw::HostPlan &p = dp->hp;
     const float *sdb = h->ws[2].as<float>();
@@ -1035,7 +1036,7 @@ int run_back(hpfw_gpu *h, DevPlan *dp, int ns, uint64_t *d_hp, hipStream_t s)
     if (h->projection) { // S9q: reference level, clip, exact integer sums on the int8 matrix pipe, sign and pack in ONE kernel
         {
             Timed t(h, K_PROJECT, s);
-            hpfw::launch_hashprints_q(h->d_fq_image.get(), sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s);
+            hpfw::launch_hashprints_q(images, n_shifts, sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s);
         }
         return check_launch("project");
     }
@@ -1091,6 +1092,86 @@ int check_transposed(hpfw_gpu *h, const int32_t *shifts, int n_shifts)
     if (!h->projection) return fail(HPFW_E_INVALID, "transposed extraction needs projection mode 1 (fixed point)");
     if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters: call hpfw_gpu_set_filters or hpfw_gpu_learn_filters first");
     return 0;
+}
+
+// dB spectrograms [n_clips][121][c] (device) -> hashprints [n_clips][max(n_shifts, 1)][c - 99], 256 clips per launch, of
+// the handle's filters (n_shifts = 0) or of their images moved by each of shifts[0 .. n_shifts)
+int hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, const int32_t *shifts, int n_shifts, uint64_t *d_hp,
+                       hipStream_t s)
+{
+    const int64_t nf = c - (hpfw::kCtx - 1), nhp = nf - hpfw::kLag;
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, s, [&] {
+        int rc;
+        if (n_shifts && (rc = shift_images(h, shifts, n_shifts, s))) return rc;
+        const void *images = n_shifts ? h->d_shift_images.get() : h->d_fq_image.get();
+        const int nbmax = 256;
+        if (!h->projection && (rc = ensure(h->ws[3], (size_t)nbmax * 64 * (size_t)nf * 4))) return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            if (h->projection) {
+                Timed t(h, K_PROJECT, s);
+                hpfw::launch_hashprints_q(images, n_shifts, d_db + c0 * 121 * c, nullptr, nb, (int)c, d_hp + c0 * std::max(n_shifts, 1) * nhp,
+                                          nullptr, s);
+            } else {
+                hpfw::launch_project(h->d_fpack.as<float>(), d_db + c0 * 121 * c, nullptr, nb, (int)c, h->ws[3].as<float>(), s);
+                hpfw::launch_pack(h->ws[3].as<float>(), nb, (int)nf, d_hp + c0 * nhp, s);
+            }
+            if ((rc = check_launch("project"))) return rc;
+        }
+        return 0;
+    });
+}
+
+// PCM (device) -> hashprints [n_clips][max(n_shifts, 1)][n_hp] as hashprints_from_db: front ends of up to a pass of clips, back
+// ends of up to kBackBatch clips
+int extract_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts, int n_shifts,
+                  uint64_t *d_hp, void *stream)
+{
+    if (!h || !d_pcm || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters loaded: call hpfw_gpu_set_filters first");
+    HIP_TRY(hipSetDevice(h->device));
+    DevPlan *dp;
+    int rc = get_plan(h, n_samples, &dp);
+    if (rc) return rc;
+    if (dp->hp.n_hp <= 0) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint");
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_shifts && (rc = shift_images(h, shifts, n_shifts, s))) return rc;
+        const void *images = n_shifts ? h->d_shift_images.get() : h->d_fq_image.get();
+        const int nbmax = pass_clips(h, dp, n_clips);
+        const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
+        if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
+        for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
+            const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
+            for (int c0 = 0; c0 < ns; c0 += nbmax) {
+                const int nb = std::min(nbmax, ns - c0);
+                if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
+            }
+            if ((rc = run_back(h, dp, images, n_shifts, ns, d_hp + s0 * std::max(n_shifts, 1) * dp->hp.n_hp, s))) return rc;
+        }
+        return 0;
+    });
+}
+
+// the host round trip of a search: the hashprints of query sets [0, n_sets) uploaded, their offsets rebased to 0,
+// device(d_q, rel, d_out) queued on the null stream, the n_out hits it wrote downloaded
+template <class Hit, class Device>
+int search_round_trip(const uint64_t *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, Device device)
+{
+    const int64_t total = q_off[n_sets] - q_off[0];
+    DevBuf d_q, d_out;
+    HIP_TRY(d_q.alloc((size_t)std::max<int64_t>(total, 1) * 8));
+    if (d_out.alloc((size_t)n_out * sizeof(Hit)) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
+    std::vector<int64_t> rel((size_t)n_sets + 1);
+    for (int64_t i = 0; i <= n_sets; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    if (total && hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy failed");
+    int rc = device(d_q.as<uint64_t>(), rel.data(), d_out.as<Hit>());
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
+    if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_out * sizeof(Hit), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(HPFW_E_HIP, "D2H copy failed");
+    return rc;
 }
 
 } // namespace
@@ -1182,26 +1263,8 @@ int hpfw_gpu_hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips,
 {
     if (!h || !d_db || !d_hp) return fail(HPFW_E_INVALID, "null argument");
     if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters: call hpfw_gpu_set_filters or hpfw_gpu_learn_filters first");
-    const int64_t nf = c - (hpfw::kCtx - 1), nhp = nf - hpfw::kLag;
-    if (nhp <= 0) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    return ordered_call(h, s, [&] {
-        int rc;
-        const int nbmax = 256;
-        if (!h->projection && (rc = ensure(h->ws[3], (size_t)nbmax * 64 * (size_t)nf * 4))) return rc;
-        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-            if (h->projection) {
-                hpfw::launch_hashprints_q(h->d_fq_image.get(), d_db + c0 * 121 * c, nullptr, nb, (int)c, d_hp + c0 * nhp, nullptr, s);
-            } else {
-                hpfw::launch_project(h->d_fpack.as<float>(), d_db + c0 * 121 * c, nullptr, nb, (int)c, h->ws[3].as<float>(), s);
-                hpfw::launch_pack(h->ws[3].as<float>(), nb, (int)nf, d_hp + c0 * nhp, s);
-            }
-            if ((rc = check_launch("project"))) return rc;
-        }
-        return 0;
-    });
+    if (c - (hpfw::kCtx - 1) - hpfw::kLag <= 0) return 0;
+    return hashprints_from_db(h, d_db, n_clips, c, nullptr, 0, d_hp, (hipStream_t)stream);
 }
 
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp, void *stream)
@@ -1219,7 +1282,7 @@ int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int6
             if (int rc = ensure(h->ws[3], (size_t)n_clips * (size_t)nhp * 8)) return rc;
             hp = h->ws[3].as<uint64_t>();
         }
-        hpfw::launch_hashprints_q(h->d_fq_image.get(), d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s);
+        hpfw::launch_hashprints_q(h->d_fq_image.get(), 0, d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s);
         return check_launch("project");
     });
 }
@@ -1230,23 +1293,8 @@ int hpfw_gpu_hashprints_from_db_transposed(hpfw_gpu *h, const float *d_db, int64
     int rc = check_transposed(h, shifts, n_shifts);
     if (rc) return rc;
     if (!d_db || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
-    const int64_t nhp = c - (hpfw::kCtx - 1) - hpfw::kLag;
-    if (nhp <= 0 || n_clips == 0) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    return ordered_call(h, s, [&] {
-        int rc;
-        if ((rc = shift_images(h, shifts, n_shifts, s))) return rc;
-        const int nbmax = 256;
-        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
-            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
-            Timed t(h, K_PROJECT, s);
-            hpfw::launch_hashprints_q_shifted(h->d_shift_images.get(), n_shifts, d_db + c0 * 121 * c, nullptr, nb, (int)c,
-                                              d_hp + c0 * n_shifts * nhp, s);
-            if ((rc = check_launch("project"))) return rc;
-        }
-        return 0;
-    });
+    if (c - (hpfw::kCtx - 1) - hpfw::kLag <= 0 || n_clips == 0) return 0;
+    return hashprints_from_db(h, d_db, n_clips, c, shifts, n_shifts, d_hp, (hipStream_t)stream);
 }
 
 int hpfw_gpu_geometry(hpfw_gpu *h, int64_t n_samples, hpfw_geometry *out)
@@ -1311,88 +1359,19 @@ int hpfw_gpu_set_batch(hpfw_gpu *h, int clips)
 int hpfw_gpu_extract_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips,
                            uint64_t *d_hp, void *stream)
 {
-    if (!h || !d_pcm || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
-    if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters loaded: call hpfw_gpu_set_filters first");
-    HIP_TRY(hipSetDevice(h->device));
-    DevPlan *dp;
-    int rc = get_plan(h, n_samples, &dp);
-    if (rc) return rc;
-    if (dp->hp.n_hp <= 0) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint");
-    hipStream_t s = (hipStream_t)stream;
-    return ordered_call(h, s, [&] {
-        const int nbmax = pass_clips(h, dp, n_clips);
-        const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
-        if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
-        for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
-            const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
-            for (int c0 = 0; c0 < ns; c0 += nbmax) {
-                const int nb = std::min(nbmax, ns - c0);
-                if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
-            }
-            if ((rc = run_back(h, dp, ns, d_hp + s0 * dp->hp.n_hp, s))) return rc;
-        }
-        return 0;
-    });
+    return extract_pcm16(h, d_pcm, n_samples, n_clips, nullptr, 0, d_hp, stream);
 }
 
 int hpfw_gpu_extract_transposed_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts,
                                       int n_shifts, uint64_t *d_hp, void *stream)
 {
-    int rc = check_transposed(h, shifts, n_shifts);
-    if (rc) return rc;
-    if (!d_pcm || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    DevPlan *dp;
-    if ((rc = get_plan(h, n_samples, &dp))) return rc;
-    if (dp->hp.n_hp <= 0) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint");
-    hipStream_t s = (hipStream_t)stream;
-    return ordered_call(h, s, [&] {
-        if ((rc = shift_images(h, shifts, n_shifts, s))) return rc;
-        const int nbmax = pass_clips(h, dp, n_clips);
-        const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
-        if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
-        for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
-            const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
-            for (int c0 = 0; c0 < ns; c0 += nbmax) {
-                const int nb = std::min(nbmax, ns - c0);
-                if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
-            }
-            {
-                Timed t(h, K_PROJECT, s);
-                hpfw::launch_hashprints_q_shifted(h->d_shift_images.get(), n_shifts, h->ws[2].as<float>(), h->d_clipmax.as<float>(), ns,
-                                                  (int)dp->hp.c, d_hp + s0 * n_shifts * dp->hp.n_hp, s);
-            }
-            if ((rc = check_launch("project"))) return rc;
-        }
-        return 0;
-    });
+    if (int rc = check_transposed(h, shifts, n_shifts)) return rc;
+    return extract_pcm16(h, d_pcm, n_samples, n_clips, shifts, n_shifts, d_hp, stream);
 }
 
-int hpfw_gpu_extract_transposed_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts,
-                                           int n_shifts, uint64_t *hp)
-{
-    int rc = check_transposed(h, shifts, n_shifts);
-    if (rc) return rc;
-    if (!pcm || !hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    hpfw_geometry g;
-    if ((rc = hpfw_gpu_geometry(h, n_samples, &g))) return rc;
-    if (n_clips == 0) return 0;
-    DevBuf d_pcm, d_hp;
-    if (d_pcm.alloc((size_t)n_clips * n_samples * 2) != hipSuccess || d_hp.alloc((size_t)n_clips * n_shifts * std::max<int64_t>(g.n_hp, 1) * 8) != hipSuccess)
-        return fail(HPFW_E_NOMEM, "hipMalloc failed");
-    hipStream_t s = nullptr;
-    if (hipMemcpyAsync(d_pcm.get(), pcm, (size_t)n_clips * n_samples * 2, hipMemcpyHostToDevice, s) != hipSuccess)
-        return fail(HPFW_E_HIP, "H2D copy failed");
-    rc = hpfw_gpu_extract_transposed_pcm16(h, d_pcm.as<int16_t>(), n_samples, n_clips, shifts, n_shifts, d_hp.as<uint64_t>(), s);
-    if (!rc && hipMemcpyAsync(hp, d_hp.get(), (size_t)n_clips * n_shifts * g.n_hp * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "D2H copy failed");
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    return rc;
-}
-
-int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
-                                uint64_t *hp)
+// host PCM -> host hashprints [n_clips][max(n_shifts, 1)][n_hp], through extract_pcm16 (shifts as there)
+static int extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts, int n_shifts,
+                              uint64_t *hp)
 {
     if (!h || !pcm || !hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -1404,7 +1383,8 @@ int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_sampl
     // i + 1 runs under the kernels of chunk i (from pinned host memory; a pageable source is staged
     // by the runtime and overlaps only partly)
     const int64_t chunk = std::min<int64_t>(n_clips, std::max<int64_t>(1, (192ll << 20) / (n_samples * 2)));
-    if ((rc = ensure(h->stage_hp, (size_t)n_clips * std::max<int64_t>(g.n_hp, 1) * 8))) return rc;
+    const int64_t per_clip = std::max(n_shifts, 1) * g.n_hp;
+    if ((rc = ensure(h->stage_hp, (size_t)n_clips * std::max<int64_t>(per_clip, 1) * 8))) return rc;
     for (int b = 0; b < 2; ++b) {
         if (b == 1 && chunk >= n_clips) break; // one chunk: one buffer
         if ((rc = ensure(h->stage_pcm[b], (size_t)chunk * n_samples * 2))) return rc;
@@ -1431,14 +1411,26 @@ int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_sampl
             rc = fail(HPFW_E_HIP, "H2D copy failed");
         if (!rc && (hipEventRecord(copied, s_copy) != hipSuccess || hipStreamWaitEvent(s_comp, copied, 0) != hipSuccess))
             rc = fail(HPFW_E_HIP, "event record failed");
-        if (!rc) rc = hpfw_gpu_extract_pcm16(h, d_pcm, n_samples, cnt, d_hp + c0 * g.n_hp, s_comp);
+        if (!rc) rc = extract_pcm16(h, d_pcm, n_samples, cnt, shifts, n_shifts, d_hp + c0 * per_clip, s_comp);
         if (!rc && hipEventRecord(consumed, s_comp) != hipSuccess) rc = fail(HPFW_E_HIP, "event record failed");
     }
     if (hipStreamSynchronize(s_copy) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc && hipMemcpyAsync(hp, d_hp, (size_t)n_clips * g.n_hp * 8, hipMemcpyDeviceToHost, s_comp) != hipSuccess)
+    if (!rc && hipMemcpyAsync(hp, d_hp, (size_t)n_clips * per_clip * 8, hipMemcpyDeviceToHost, s_comp) != hipSuccess)
         rc = fail(HPFW_E_HIP, "D2H copy failed");
     if (hipStreamSynchronize(s_comp) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "kernel execution failed");
     return rc;
+}
+
+int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, uint64_t *hp)
+{
+    return extract_pcm16_host(h, pcm, n_samples, n_clips, nullptr, 0, hp);
+}
+
+int hpfw_gpu_extract_transposed_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts,
+                                           int n_shifts, uint64_t *hp)
+{
+    if (int rc = check_transposed(h, shifts, n_shifts)) return rc;
+    return extract_pcm16_host(h, pcm, n_samples, n_clips, shifts, n_shifts, hp);
 }
 
 // Host half of the tables of a clip length, built on the CALLING thread and kept for the next entry point that meets
@@ -2437,19 +2429,9 @@ int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
-    const int64_t total = q_off[n_q] - q_off[0];
-    DevBuf d_q, d_out;
-    HIP_TRY(d_q.alloc((size_t)std::max<int64_t>(total, 1) * 8));
-    if (d_out.alloc((size_t)n_q * k * sizeof(hpfw_hit)) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
-    std::vector<int64_t> rel((size_t)n_q + 1);
-    for (int64_t i = 0; i <= n_q; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
-    if (total && hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(HPFW_E_HIP, "H2D copy failed");
-    int rc = hpfw_gpu_search_topk_device(h, d_q.as<uint64_t>(), rel.data(), n_q, k, d_out.as<hpfw_hit>(), nullptr);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_q * k * sizeof(hpfw_hit), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "D2H copy failed");
-    return rc;
+    return search_round_trip(q_hp, q_off, n_q, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_hit *d_out) {
+        return hpfw_gpu_search_topk_device(h, d_q, rel, n_q, k, d_out, nullptr);
+    });
 }
 
 int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
@@ -2480,19 +2462,9 @@ int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
-    const int64_t nq = n_q * n_shifts, total = q_off[nq] - q_off[0];
-    DevBuf d_q, d_out;
-    HIP_TRY(d_q.alloc((size_t)std::max<int64_t>(total, 1) * 8));
-    if (d_out.alloc((size_t)n_q * k * sizeof(hpfw_shift_hit)) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
-    std::vector<int64_t> rel((size_t)nq + 1);
-    for (int64_t i = 0; i <= nq; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
-    if (total && hipMemcpy(d_q.get(), q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(HPFW_E_HIP, "H2D copy failed");
-    int rc = hpfw_gpu_search_topk_transposed_device(h, d_q.as<uint64_t>(), rel.data(), n_q, n_shifts, k, d_out.as<hpfw_shift_hit>(), nullptr);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_q * k * sizeof(hpfw_shift_hit), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "D2H copy failed");
-    return rc;
+    return search_round_trip(q_hp, q_off, n_q * n_shifts, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_shift_hit *d_out) {
+        return hpfw_gpu_search_topk_transposed_device(h, d_q, rel, n_q, n_shifts, k, d_out, nullptr);
+    });
 }
 
 // ---- AudioCombiner: exact-hash index + offset votes (k_combiner.hip) --------------------------------

@@ -58,11 +58,14 @@ __device__ __forceinline__ int q_fixed(float s)
 }
 
 // FROM_T: sdb holds the dB terms t written by the chirp-z kernel; S = max(t - tmax[clip], -80) (convert.h:12-15)
-// rides on the staging loads.  dbg (tests only, NULL in extraction): D as int64 [clip][64][nhp].
-template <bool FROM_T>
-__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
+// rides on the staging loads.  fq_images: filter digit images one after the other, the slab staged once and each image
+// in turn running the matrix loop and the epilogue over it, hp [clip][image][nhp]: SHIFTED = false, the extraction's one
+// image; SHIFTED = true, n_images shifted ones (shift_filter_images_kernel).  dbg (tests only, NULL
+// in extraction; SHIFTED = false): D as int64 [clip][64][nhp].
+template <bool FROM_T, bool SHIFTED>
+__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
                                                                    const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
-                                                                   uint64_t *__restrict__ hp, long long *__restrict__ dbg)
+                                                                   uint64_t *__restrict__ hp, long long *__restrict__ dbg, int n_images)
 {
     unsigned char *slab = smem_raw;                                   // [chunk][column (pitch 160)][digit][16]
     unsigned short *parts = reinterpret_cast<unsigned short *>(smem_raw + kQSlabBytes); // [hashprint][wave]
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
     const float *S = sdb + (int64_t)clip * kBins * c;
     const float ref = FROM_T ? tmax[clip] : 0.0f;
     // the wave's filter digits of the first two steps are on their way while the slab is quantised
-    const v4i *img = fq_image + (size_t)wave * kQSteps * (kQStepBytes / 16) + lane;
+    const v4i *img = fq_images + (size_t)wave * kQSteps * (kQStepBytes / 16) + lane;
     v4i a[3][3]; // three register sets in turn: the loads of step s + 2 are issued before the products of step s
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -162,195 +165,17 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
     Q_STAMP(2);
     // tiles of 16 hashprints that hold any (the last workgroup of a clip); the products of the others are skipped
     const int n_tiles = min(8, (nhp - n0 + 15) / 16);
-    v4i acc[8][5];
-#pragma unroll
-    for (int f = 0; f < 8; ++f)
-#pragma unroll
-        for (int cls = 0; cls < 5; ++cls) acc[f][cls] = v4i{0, 0, 0, 0};
     // B operand of (step, tile f): chunk 4 (s & 1) + kg, column 16 f + cl + (s >> 1)
     const unsigned char *bl = slab + (size_t)(kg * kQPitch + cl) * kQUnit;
-    auto step = [&](int s, const v4i (&aw)[3]) {
-        const unsigned char *bs = bl + (size_t)((4 * (s & 1)) * kQPitch + (s >> 1)) * kQUnit;
-        // the operand reads of tile f + 1 are issued BEFORE the nine products of tile f: read right where they are used, a
-        // wave alone on its SIMD left the matrix pipe idle for an LDS round trip per tile (tools/q_stamps.py: 46 k cycles of
-        // matrix instructions in a 69 k cycle loop)
-        v4i nb0, nb1, nb2;
-        {
-            const v4i *bu = reinterpret_cast<const v4i *>(bs);
-            nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
-        }
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            if (f < n_tiles) {
-                const v4i b0 = nb0, b1 = nb1, b2 = nb2;
-                if (f + 1 < 8) { // (tile f + 1 of the slab exists whether or not it holds hashprints)
-                    const v4i *bu = reinterpret_cast<const v4i *>(bs + (size_t)(16 * (f + 1)) * kQUnit);
-                    nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
-                }
-                __builtin_amdgcn_sched_barrier(0); // (the scheduler would sink the reads back to where they are used)
-                // filter digit i times spectrogram digit j goes to accumulator i + j
-                acc[f][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b0, acc[f][0], 0, 0, 0);
-                acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b1, acc[f][1], 0, 0, 0);
-                acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b2, acc[f][2], 0, 0, 0);
-                acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b2, acc[f][3], 0, 0, 0);
-                acc[f][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b2, acc[f][4], 0, 0, 0);
-                acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b0, acc[f][1], 0, 0, 0);
-                acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b1, acc[f][2], 0, 0, 0);
-                acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b1, acc[f][3], 0, 0, 0);
-                acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b0, acc[f][2], 0, 0, 0);
-            }
-        }
-    };
-    auto load_a = [&](int s, v4i (&aw)[3]) {
-        if (s < kQSteps) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) aw[d] = img[(size_t)s * (kQStepBytes / 16) + d * 64];
-        }
-    };
-    if (n_tiles > 0) {
+    // one trip per image over the same slab, the first two steps' digits of image im in a[0] and a[1].  The extraction's
+    // instance is compiled without a loop (the condition folds to false before any optimisation): with a loop, even of
+    // one trip known at compile time, the compiler allocated its registers differently (16 more waits for memory in
+    // <true, false>, 44 in <false, false>), and a run-time image count with dbg live across the loop spilled
+    int im = 0;
 #pragma unroll 1
-        for (int s = 0; s < kQSteps - 1; s += 3) { // 40 steps = 13 x 3 + 1
-            load_a(s + 2, a[2]);
-            step(s, a[0]);
-            load_a(s + 3, a[0]);
-            step(s + 1, a[1]);
-            load_a(s + 4, a[1]);
-            step(s + 2, a[2]);
-        }
-        step(kQSteps - 1, a[0]);
-    }
-    Q_STAMP(3);
-    // S10q: D = sum_c acc_c 2^(8c); D layout of the 16x16 tile: column (hashprint) = lane & 15, row (filter) = 4 (lane >> 4) + reg
-#pragma unroll
-    for (int f = 0; f < 8; ++f) {
-        const int n = n0 + 16 * f + cl;
-        (void)n;
-        unsigned bits = 0; // this wave's 16 filters of hashprint n, filter 16 wave + row at bit 15 - row
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int row = 4 * kg + reg;
-            long long v = acc[f][4][reg];
-#pragma unroll
-            for (int cls = 3; cls >= 0; --cls) v = v * 256 + acc[f][cls][reg];
-            bits |= (unsigned)(v >= 0) << (15 - row);
-#if !defined(HPFW_Q_STAMPS)
-            if (dbg && f < n_tiles && n < nhp) dbg[((int64_t)clip * kFilters + 16 * wave + row) * nhp + n] = v;
-#endif
-        }
-        // the four lanes of a column hold four filters each
-        bits |= (unsigned)__shfl_xor((int)bits, 16);
-        bits |= (unsigned)__shfl_xor((int)bits, 32);
-        if (kg == 0) parts[(16 * f + cl) * 4 + wave] = (unsigned short)bits;
-    }
-    Q_STAMP(4);
-    __syncthreads();
-    if (tid < kQTileN && n0 + tid < nhp) {
-        const unsigned short *p = parts + tid * 4;
-        hp[(int64_t)clip * nhp + n0 + tid] = ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
-    }
-#if defined(HPFW_Q_STAMPS)
-    Q_STAMP(5);
-    if (dbg && tid == 0) {
-        for (int k = 0; k < 6; ++k) dbg[(int64_t)t * 8 + k] = st[k];
-        dbg[(int64_t)t * 8 + 6] = __builtin_amdgcn_s_getreg((15 << 11) | 4); // HW_ID: wave, SIMD, CU, SH, SE
-        dbg[(int64_t)t * 8 + 7] = blockIdx.x;
-    }
-#endif
-}
-
-// Transposed extraction: fq_image holds n_shifts digit images one after the other, image i the
-// filters moved by shift i along the bins (shift_filter_images_kernel).  The staging, the matrix loop and the epilogue are
-// those of hashprint_q_kernel above (see its comments); the slab is staged once and each image in turn runs the matrix
-// loop and the epilogue over it, hp [clip][shift][nhp].  A kernel of its own, so that the extraction's kernel stays as
-// it was compiled before.
-template <bool FROM_T>
-__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_shift_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
-                                                                         const float *__restrict__ tmax, int c, int nhp, int n_tiles_x,
-                                                                         int n_clips, int n_shifts, uint64_t *__restrict__ hp)
-{
-    unsigned char *slab = smem_raw;                                   // [chunk][column (pitch 160)][digit][16]
-    unsigned short *parts = reinterpret_cast<unsigned short *>(smem_raw + kQSlabBytes); // [hashprint][wave]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kg = lane >> 4, cl = lane & 15;  // this lane's group of 16 k' inside a step; its column (B) / filter (A) in a tile
-    // (clip, tile) in XCD-aware order, as hashprint_q_kernel
-    const unsigned per_xcd = (gridDim.x + 7) / 8;
-    const unsigned t = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
-    const int clip = t / n_tiles_x;
-    const int n0 = (t - clip * n_tiles_x) * kQTileN;
-    const float *S = sdb + (int64_t)clip * kBins * c;
-    const float ref = FROM_T ? tmax[clip] : 0.0f;
-    // the wave's filter digits of the first two steps are on their way while the slab is quantised
-    const v4i *img = fq_image + (size_t)wave * kQSteps * (kQStepBytes / 16) + lane;
-    v4i a[3][3]; // three register sets in turn: the loads of step s + 2 are issued before the products of step s
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        a[0][d] = img[d * 64];
-        a[1][d] = img[(kQStepBytes / 16) + d * 64];
-    }
-    // slab: one (chunk, column) unit = 16 bins of one column of Du, three digit planes.  The loads of a round (16 bins x
-    // the column and its partner 80 on) are all issued before the first value is quantised
-    constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
-#pragma unroll 1
-    for (int r0 = 0; r0 < kUnits; r0 += 2) {
-        float va[2][16], vb[2][16];
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int unit = tid + (r0 + rr) * kQThreads;
-            const int q = unit / kQCols, col = unit - q * kQCols;
-            const int gc = n0 + col;
-            const bool in = r0 + rr < kUnits && unit < kQChunks * kQCols && gc + kLag < c;
-            // every load issued from a valid address, zeroed afterwards (see hashprint_q_kernel)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int bin = 16 * q + e;
-                const bool ok = in && bin < kBins;
-                const unsigned idx = ok ? (unsigned)(bin * c + gc) : 0u; // (clip-relative: < 121 * c, 32 bits; S[0] and S[kLag] exist)
-                va[rr][e] = S[idx];
-                vb[rr][e] = S[idx + kLag];
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int unit = tid + (r0 + rr) * kQThreads;
-            const int q = unit / kQCols, col = unit - q * kQCols;
-            const bool in = r0 + rr < kUnits && unit < kQChunks * kQCols && n0 + col + kLag < c;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const bool ok = in && 16 * q + e < kBins;
-                va[rr][e] = ok ? va[rr][e] : 0.0f;
-                vb[rr][e] = ok ? vb[rr][e] : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int unit = tid + (r0 + rr) * kQThreads;
-            if (r0 + rr >= kUnits || unit >= kQChunks * kQCols) break;
-            const int q = unit / kQCols, col = unit - q * kQCols;
-            unsigned w0[4] = {0, 0, 0, 0}, w1[4] = {0, 0, 0, 0}, w2[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float xa = va[rr][e], xb = vb[rr][e];
-                if (FROM_T) {
-                    xa -= ref;
-                    xb -= ref;
-                }
-                // (values outside the slab's valid part were loaded as 0 on both sides: Du = 0, digits 0)
-                const unsigned d = q_digit_bytes(q_fixed(xa) - q_fixed(xb));
-                w0[e >> 2] |= (d & 255u) << (8 * (e & 3));
-                w1[e >> 2] |= ((d >> 8) & 255u) << (8 * (e & 3));
-                w2[e >> 2] |= ((d >> 16) & 255u) << (8 * (e & 3));
-            }
-            v4i *dst = reinterpret_cast<v4i *>(slab + (size_t)(q * kQPitch + col) * kQUnit);
-            dst[0] = v4i{(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3]};
-            dst[1] = v4i{(int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
-            dst[2] = v4i{(int)w2[0], (int)w2[1], (int)w2[2], (int)w2[3]};
-        }
-    }
-    __syncthreads(); // the only barrier before the epilogue: the slab is read-only from here on
-#pragma unroll 1
-    for (int sh = 0; sh < n_shifts; ++sh) {
-        if (sh > 0) { // the next image's first two steps (the slab stays)
+    do {
+        if (SHIFTED && im > 0) {
+            __syncthreads(); // (parts is written again by this image's epilogue)
             img += (size_t)4 * kQSteps * kQStepBytes / 16;
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
@@ -358,18 +183,16 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_shift_kernel(const v
                 a[1][d] = img[(kQStepBytes / 16) + d * 64];
             }
         }
-        // tiles of 16 hashprints that hold any (the last workgroup of a clip); the products of the others are skipped
-        const int n_tiles = min(8, (nhp - n0 + 15) / 16);
         v4i acc[8][5];
 #pragma unroll
         for (int f = 0; f < 8; ++f)
 #pragma unroll
             for (int cls = 0; cls < 5; ++cls) acc[f][cls] = v4i{0, 0, 0, 0};
-        // B operand of (step, tile f): chunk 4 (s & 1) + kg, column 16 f + cl + (s >> 1)
-        const unsigned char *bl = slab + (size_t)(kg * kQPitch + cl) * kQUnit;
         auto step = [&](int s, const v4i (&aw)[3]) {
             const unsigned char *bs = bl + (size_t)((4 * (s & 1)) * kQPitch + (s >> 1)) * kQUnit;
-            // the operand reads of tile f + 1 are issued before the nine products of tile f
+            // the operand reads of tile f + 1 are issued BEFORE the nine products of tile f: read right where they are used, a
+            // wave alone on its SIMD left the matrix pipe idle for an LDS round trip per tile (tools/q_stamps.py: 46 k cycles of
+            // matrix instructions in a 69 k cycle loop)
             v4i nb0, nb1, nb2;
             {
                 const v4i *bu = reinterpret_cast<const v4i *>(bs);
@@ -415,10 +238,13 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_shift_kernel(const v
             }
             step(kQSteps - 1, a[0]);
         }
+        Q_STAMP(3);
         // S10q: D = sum_c acc_c 2^(8c); D layout of the 16x16 tile: column (hashprint) = lane & 15, row (filter) = 4 (lane >> 4) + reg
 #pragma unroll
         for (int f = 0; f < 8; ++f) {
-            unsigned bits = 0; // this wave's 16 filters of hashprint n0 + 16 f + cl, filter 16 wave + row at bit 15 - row
+            const int n = n0 + 16 * f + cl;
+            (void)n;
+            unsigned bits = 0; // this wave's 16 filters of hashprint n, filter 16 wave + row at bit 15 - row
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int row = 4 * kg + reg;
@@ -426,19 +252,31 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_shift_kernel(const v
 #pragma unroll
                 for (int cls = 3; cls >= 0; --cls) v = v * 256 + acc[f][cls][reg];
                 bits |= (unsigned)(v >= 0) << (15 - row);
+#if !defined(HPFW_Q_STAMPS)
+                if (!SHIFTED && dbg && f < n_tiles && n < nhp) dbg[((int64_t)clip * kFilters + 16 * wave + row) * nhp + n] = v;
+#endif
             }
             // the four lanes of a column hold four filters each
             bits |= (unsigned)__shfl_xor((int)bits, 16);
             bits |= (unsigned)__shfl_xor((int)bits, 32);
             if (kg == 0) parts[(16 * f + cl) * 4 + wave] = (unsigned short)bits;
         }
+        Q_STAMP(4);
         __syncthreads();
         if (tid < kQTileN && n0 + tid < nhp) {
             const unsigned short *p = parts + tid * 4;
-            hp[((int64_t)clip * n_shifts + sh) * nhp + n0 + tid] = ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
+            hp[((int64_t)clip * (SHIFTED ? n_images : 1) + im) * nhp + n0 + tid] =
+                ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
         }
-        __syncthreads(); // parts is written again by the next image's epilogue
+    } while (SHIFTED && ++im < n_images);
+#if defined(HPFW_Q_STAMPS)
+    Q_STAMP(5);
+    if (dbg && tid == 0) {
+        for (int k = 0; k < 6; ++k) dbg[(int64_t)t * 8 + k] = st[k];
+        dbg[(int64_t)t * 8 + 6] = __builtin_amdgcn_s_getreg((15 << 11) | 4); // HW_ID: wave, SIMD, CU, SH, SE
+        dbg[(int64_t)t * 8 + 7] = blockIdx.x;
     }
+#endif
 }
 
 // Image i (blockIdx.y) of the filters moved by shifts.s[i] bins: the byte of bin b holds the digit of fq[r][20 (b - s) + t]
@@ -500,31 +338,31 @@ extern "C" void hpfw_gpu_debug_set_q_stamps(void *d) { g_q_stamps = static_cast<
 
 size_t project_q_image_bytes() { return (size_t)4 * kQSteps * kQStepBytes; }
 
-// dB terms (d_tmax != NULL) or dB spectrograms -> hashprints [n_clips][c - 99]; d_dbg: NULL, or D [n_clips][64][c - 99] (tests)
-void launch_hashprints_q(const void *d_fq_image, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
+// dB terms (d_tmax != NULL) or dB spectrograms -> hashprints [n_clips][max(n_shifts, 1)][c - 99] of the filter images at
+// d_images: the unshifted one (n_shifts = 0), or n_shifts from launch_shift_filter_images.  One shift runs the image loop
+// too: 2.14 ms against 2.15 for the extraction's instance on 1000 x 30 s clips (profiles/transpose.json).  d_dbg: NULL,
+// or D [n_clips][64][c - 99] of the unshifted image (tests)
+void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
                          long long *d_dbg, hipStream_t s)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hashprint_q_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kQLdsBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hashprint_q_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kQLdsBytes);
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q_kernel<true, false>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false>),
+                              reinterpret_cast<const void *>(hashprint_q_kernel<true, true>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true>)})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes);
         attr_set.mark();
     }
     const int nhp = c - (kCtx - 1) - kLag;
-    if (nhp <= 0 || n_clips <= 0) return;
+    if (nhp <= 0 || n_clips <= 0 || n_shifts < 0) return;
 #if defined(HPFW_Q_STAMPS)
     if (!d_dbg) d_dbg = g_q_stamps; // (tools/q_stamps.py extract: the stamps of the extraction's own launches)
 #endif
     const int tiles = (nhp + kQTileN - 1) / kQTileN;
     const dim3 grid(8 * (unsigned)(((int64_t)tiles * n_clips + 7) / 8)); // one-dimensional, in XCD-aware order
-    if (d_tmax)
-        hipLaunchKernelGGL(hashprint_q_kernel<true>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_fq_image), d_db, d_tmax,
-                           c, nhp, tiles, n_clips, d_hp, d_dbg);
-    else
-        hipLaunchKernelGGL(hashprint_q_kernel<false>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_fq_image), d_db, d_tmax,
-                           c, nhp, tiles, n_clips, d_hp, d_dbg);
+    auto k = n_shifts > 0 ? (d_tmax ? hashprint_q_kernel<true, true> : hashprint_q_kernel<false, true>)
+                          : (d_tmax ? hashprint_q_kernel<true, false> : hashprint_q_kernel<false, false>);
+    hipLaunchKernelGGL(k, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
+                       d_hp, d_dbg, n_shifts);
 }
 
 void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s)
@@ -532,31 +370,6 @@ void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts,
     constexpr int kUnits = 4 * kQSteps * kQStepBytes / 16;
     hipLaunchKernelGGL(shift_filter_images_kernel, dim3((kUnits + 255) / 256, shifts.n), dim3(256), 0, s,
                        static_cast<const unsigned char *>(d_fq_image), shifts, static_cast<v4i *>(d_images));
-}
-
-// the hashprints of n_shifts shifts of every clip, hp [n_clips][n_shifts][c - 99], from the images of
-// launch_shift_filter_images: one launch, the slab of a (clip, tile) staged once for all shifts
-void launch_hashprints_q_shifted(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c,
-                                 uint64_t *d_hp, hipStream_t s)
-{
-    static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hashprint_q_shift_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kQLdsBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hashprint_q_shift_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kQLdsBytes);
-        attr_set.mark();
-    }
-    const int nhp = c - (kCtx - 1) - kLag;
-    if (nhp <= 0 || n_clips <= 0 || n_shifts <= 0) return;
-    const int tiles = (nhp + kQTileN - 1) / kQTileN;
-    const dim3 grid(8 * (unsigned)(((int64_t)tiles * n_clips + 7) / 8));
-    if (d_tmax)
-        hipLaunchKernelGGL(hashprint_q_shift_kernel<true>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db,
-                           d_tmax, c, nhp, tiles, n_clips, n_shifts, d_hp);
-    else
-        hipLaunchKernelGGL(hashprint_q_shift_kernel<false>, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db,
-                           d_tmax, c, nhp, tiles, n_clips, n_shifts, d_hp);
 }
 
 } // namespace hpfw

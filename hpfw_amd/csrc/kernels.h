@@ -240,22 +240,21 @@ void launch_project(const float *d_fpack, const float *d_db, const float *d_tmax
 void launch_pack(const float *d_proj, int n_clips, int nf, uint64_t *d_hp, hipStream_t s);
 // a4's reference level + a5..a8 in fixed point (k_project_q.hip): filter digits image; dB terms (d_tmax != NULL)
 // or dB spectrograms -> hashprints in one kernel, the lag-80 difference taken on the quantised spectrogram (exact integers).
-// d_dbg: NULL, or (tests) the integer sums D [n_clips][64][c - 99]
+// d_images: the unshifted filter digit image (n_shifts = 0) or n_shifts shifted ones (project_q_image_bytes() each),
+// hashprints [n_clips][max(n_shifts, 1)][c - 99], the slab of each (clip, tile) staged once for all images.  d_dbg: NULL,
+// or (tests, unshifted) the integer sums D [n_clips][64][c - 99]
 size_t project_q_image_bytes();
 void pack_filters_q(const float *f_colmajor, std::vector<int8_t> &image);
-void launch_hashprints_q(const void *d_fq_image, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
+void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
                          long long *d_dbg, hipStream_t s);
 // transposed extraction: the digit images of the filters moved by each of shifts.s[0 .. n) bins
-// (d_images: n * project_q_image_bytes()), then the hashprints of every shift from one staging of each slab,
-// hp [n_clips][n_shifts][c - 99]
+// (d_images: n * project_q_image_bytes()), for launch_hashprints_q
 constexpr int kMaxShifts = 64;
 struct ShiftList {
     int n;
     int s[kMaxShifts];
 };
 void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s);
-void launch_hashprints_q_shifted(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c,
-                                 uint64_t *d_hp, hipStream_t s);
 
 // ---- HashprintHandle with other template arguments (k_hashprint_cfg.hip) ----------------------------
 struct CfgArgs {

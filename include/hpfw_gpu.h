@@ -379,8 +379,7 @@ int hpfw_gpu_hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips,
  * gives.  In projection mode 0, and for any other shifts argument, HPFW_E_INVALID.  d_hp [n_clips][n_shifts][n_hp]. */
 int hpfw_gpu_extract_transposed_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips,
                                       const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream);
-/* host buffers, meant for query batches: device memory for all of pcm and hp is allocated per call, the copies are not
- * chunked or overlapped (large batches: hpfw_gpu_extract_transposed_pcm16 on device buffers of the caller's) */
+/* host buffers, as hpfw_gpu_extract_pcm16_host: copies in, runs, copies out, synchronises */
 int hpfw_gpu_extract_transposed_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
                                            const int32_t *shifts, int n_shifts, uint64_t *hp);
 /* dB spectrograms [n_clips][121][c] (device) -> d_hp [n_clips][n_shifts][c - 99] */
