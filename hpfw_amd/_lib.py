@@ -52,6 +52,8 @@ EXPORTS = (
     "hpfw_gpu_resample_pcm16_host", "hpfw_gpu_collector_set_resample",
     "hpfw_gpu_extract_transposed_pcm16", "hpfw_gpu_extract_transposed_pcm16_host", "hpfw_gpu_hashprints_from_db_transposed",
     "hpfw_gpu_search_topk_transposed_device", "hpfw_gpu_search_topk_transposed",
+    "hpfw_gpu_tempo_columns", "hpfw_gpu_hashprints_from_db_tempo", "hpfw_gpu_extract_tempo_pcm16",
+    "hpfw_gpu_extract_tempo_pcm16_host",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -89,6 +91,7 @@ class HpfwError(RuntimeError):
 # hpfw_status values (include/hpfw_gpu.h)
 E_INVALID, E_UNSUPPORTED, E_NOFILTERS, E_HIP, E_NOMEM, E_IO = -1, -2, -3, -4, -5, -6
 MAX_SHIFTS, MAX_ABS_SHIFT = 64, 120
+MAX_TEMPOS, MIN_TEMPO, MAX_TEMPO = 64, 0.5, 2.0
 
 
 _lib = None
@@ -191,6 +194,10 @@ def lib():
     L.hpfw_gpu_hashprints_from_db_transposed.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
     L.hpfw_gpu_search_topk_transposed_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     L.hpfw_gpu_search_topk_transposed.argtypes = [vp, vp, vp, i64, i32, i32, vp]
+    L.hpfw_gpu_tempo_columns.argtypes = [i64, vp, i32, ctypes.POINTER(i64)]
+    L.hpfw_gpu_hashprints_from_db_tempo.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp, vp]
+    L.hpfw_gpu_extract_tempo_pcm16.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp, vp]
+    L.hpfw_gpu_extract_tempo_pcm16_host.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -228,6 +235,42 @@ def check_shifts(shifts):
     if len(set(out)) != len(out):
         raise ValueError(f"shifts: values must be distinct, got {out}")
     return out
+
+
+def tempo_step(rho):
+    """rint(65536 / rho) of the float32 tempo rho: its step along the source in sixteenths of a column"""
+    return int(np.rint(65536.0 / float(np.float32(rho))))
+
+
+def check_tempos(tempos, n_shifts=0):
+    """the tempo factors of a tempo query as the library accepts them: 1 to 64 finite values in [0.5, 2] with distinct
+    steps, at most 64 variants together with n_shifts shifts (ValueError otherwise); returned as a list of float"""
+    out = [float(t) for t in np.asarray(tempos, np.float32).ravel()] if tempos is not None else []
+    if not 1 <= len(out) <= MAX_TEMPOS:
+        raise ValueError(f"tempos: 1 to {MAX_TEMPOS} values, got {len(out)}")
+    if not all(MIN_TEMPO <= t <= MAX_TEMPO for t in out):           # (NaN fails the comparison)
+        raise ValueError(f"tempos: finite values in [{MIN_TEMPO}, {MAX_TEMPO}], got {out}")
+    if len({tempo_step(t) for t in out}) != len(out):
+        raise ValueError(f"tempos: values must have distinct steps rint(65536 / tempo), got {out}")
+    if len(out) * max(int(n_shifts), 1) > MAX_SHIFTS:
+        raise ValueError(f"tempos x shifts: at most {MAX_SHIFTS} variants, got {len(out)} x {n_shifts}")
+    return out
+
+
+def tempo_columns(c, tempos):
+    """columns c_t every tempo variant of a clip of c spectrogram columns is cut to (hpfw_gpu_tempo_columns)"""
+    t = np.ascontiguousarray(tempos, np.float32).ravel()
+    out = ctypes.c_int64()
+    check(lib().hpfw_gpu_tempo_columns(int(c), _hp(t), t.size, ctypes.byref(out)))
+    return out.value
+
+
+def _shift_arg(shifts):
+    """(array kept alive, pointer, count) of an optional shift list: None is (NULL, 0)"""
+    if shifts is None:
+        return None, None, 0
+    sh = np.ascontiguousarray(shifts, np.int32).ravel()
+    return sh, _hp(sh), sh.size
 
 
 def _hp(a):
@@ -316,6 +359,34 @@ class Gpu:
     def hashprints_from_db_transposed_dev(self, d_db, n_clips, c, shifts, d_hp, stream=0):
         sh = np.ascontiguousarray(shifts, np.int32).ravel()
         check(lib().hpfw_gpu_hashprints_from_db_transposed(self._h, d_db, n_clips, c, _hp(sh), sh.size, d_hp, stream))
+
+    # ---- queries at another tempo -------------------------------------
+    def extract_tempo(self, pcm, tempos, shifts=None):
+        """pcm int16 [n] or [n_clips][n] -> uint64 [n_clips][V][n_hp_t], V = len(tempos) max(len(shifts), 1): variant
+        v = j max(len(shifts), 1) + i hashes the dB spectrogram rescaled to tempo j (column k shows query time k / tempo)
+        and moved by shift i; every variant is cut to tempo_columns(c, tempos) columns"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        t = np.ascontiguousarray(tempos, np.float32).ravel()
+        keep, sp, ns = _shift_arg(shifts)
+        check_tempos(t, ns)
+        g = self.geometry(pcm.shape[1])
+        nhp = tempo_columns(g.c, t) - 99
+        hp = np.zeros((pcm.shape[0], t.size * max(ns, 1), max(nhp, 0)), np.uint64)
+        check(lib().hpfw_gpu_extract_tempo_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], _hp(t), t.size, sp, ns,
+                                                      _hp(hp)))
+        return hp
+
+    def extract_tempo_dev(self, d_pcm, n_samples, n_clips, tempos, d_hp, shifts=None, stream=0):
+        t = np.ascontiguousarray(tempos, np.float32).ravel()
+        keep, sp, ns = _shift_arg(shifts)
+        check(lib().hpfw_gpu_extract_tempo_pcm16(self._h, d_pcm, n_samples, n_clips, _hp(t), t.size, sp, ns, d_hp, stream))
+
+    def hashprints_from_db_tempo_dev(self, d_db, n_clips, c, tempos, d_hp, shifts=None, stream=0):
+        t = np.ascontiguousarray(tempos, np.float32).ravel()
+        keep, sp, ns = _shift_arg(shifts)
+        check(lib().hpfw_gpu_hashprints_from_db_tempo(self._h, d_db, n_clips, c, _hp(t), t.size, sp, ns, d_hp, stream))
 
     # ---- sample-rate conversion to 44.1 kHz (k_resample.hip) --------------------------------
     def resample_dev(self, d_in, n_in, n_clips, rate, d_out, stream=0):

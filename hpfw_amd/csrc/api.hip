@@ -333,6 +333,9 @@ struct hpfw_gpu {
     DevBuf d_shift_images;
     std::vector<int32_t> shift_images_of;
     DevBuf d_shift_hits;
+    // queries at another tempo (k_tempo.hip): the time-scaled dB spectrograms of a sub-batch of
+    // (clip, tempo) pairs (kTempoBudget, or one pair where a pair is larger)
+    DevBuf d_tempo;
 };
 
 namespace {
@@ -1123,6 +1126,110 @@ int hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t 
     });
 }
 
+// ---- queries at another tempo ----
+// The time-scaled dB spectrograms of the (clip, tempo) pairs of one sub-batch live in h->d_tempo: at most this many bytes,
+// unless a single pair is larger (an 18-minute clip at tempo 2: 84 MB)
+constexpr size_t kTempoBudget = (size_t)256 << 20;
+
+// tempos of the tempo entry points: 1..64 finite values in [0.5, 2], distinct steps, n_tempos max(n_shifts, 1) <= 64
+int check_tempos(const float *tempos, int n_tempos, int n_shifts)
+{
+    if (!tempos || n_tempos < 1 || n_tempos > hpfw::kMaxTempos) return fail(HPFW_E_INVALID, "tempos: 1 to 64 values");
+    for (int i = 0; i < n_tempos; ++i) {
+        if (!(tempos[i] >= 0.5f && tempos[i] <= 2.0f)) return fail(HPFW_E_INVALID, "tempos: finite values in [0.5, 2]");
+        for (int j = 0; j < i; ++j)
+            if (hpfw::tempo_step(tempos[j]) == hpfw::tempo_step(tempos[i]))
+                return fail(HPFW_E_INVALID, "tempos: values must have distinct steps rint(65536 / tempo)");
+    }
+    if ((int64_t)n_tempos * std::max(n_shifts, 1) > hpfw::kMaxShifts) return fail(HPFW_E_INVALID, "tempos x shifts: at most 64 variants");
+    return 0;
+}
+
+// the common checks of the tempo entry points (all before the handle is used); *tl: the steps
+int check_tempo_call(hpfw_gpu *h, const float *tempos, int n_tempos, const int32_t *shifts, int n_shifts, hpfw::TempoList *tl)
+{
+    int rc;
+    if ((rc = check_tempos(tempos, n_tempos, n_shifts))) return rc;
+    if ((shifts || n_shifts) && (rc = check_shifts(shifts, n_shifts))) return rc;
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    if (!h->projection) return fail(HPFW_E_INVALID, "tempo extraction needs projection mode 1 (fixed point)");
+    if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters: call hpfw_gpu_set_filters or hpfw_gpu_learn_filters first");
+    tl->n = n_tempos;
+    for (int i = 0; i < n_tempos; ++i) tl->step[i] = hpfw::tempo_step(tempos[i]);
+    return 0;
+}
+
+// the common length of the tempo variants of a clip of c columns: the fewest columns any of the steps gives
+int64_t tempo_common_columns(int64_t c, const hpfw::TempoList &tl)
+{
+    int64_t ct = INT64_MAX;
+    for (int i = 0; i < tl.n; ++i) ct = std::min(ct, hpfw::tempo_columns(c, tl.step[i]));
+    return ct;
+}
+
+// dB spectrograms [nb][121][c] (device) -> hashprints [nb][tl.n][max(n_shifts, 1)][ct - 99]: the (clip, tempo) pairs in
+// sub-batches that fit h->d_tempo -- whole clips with all their tempos while one clip's fit, else runs of one clip's tempos
+// -- each scaled to ct columns and projected as launch_hashprints_q's clips; pair p's hashprints start at p max(n_shifts, 1)
+// (ct - 99)
+int tempo_back(hpfw_gpu *h, const void *images, int n_shifts, const float *d_db, int64_t nb, int64_t c, const hpfw::TempoList &tl,
+               int64_t ct, uint64_t *d_hp, hipStream_t s)
+{
+    const int64_t per_pair = (int64_t)std::max(n_shifts, 1) * (ct - (hpfw::kCtx - 1) - hpfw::kLag);
+    const size_t pair_bytes = (size_t)hpfw::kBins * ct * 4;
+    const int64_t pairs = std::max<int64_t>(1, (int64_t)(kTempoBudget / pair_bytes));
+    const int64_t cb = pairs >= tl.n ? std::min<int64_t>(pairs / tl.n, nb) : 1; // clips per sub-batch
+    const int tb = pairs >= tl.n ? tl.n : (int)pairs;                           // tempos per sub-batch
+    int rc;
+    if ((rc = ensure(h->d_tempo, (size_t)cb * tb * pair_bytes, h))) return rc;
+    float *scaled = h->d_tempo.as<float>();
+    for (int64_t c0 = 0; c0 < nb; c0 += cb) {
+        const int nc = (int)std::min(cb, nb - c0);
+        for (int j0 = 0; j0 < tl.n; j0 += tb) {
+            hpfw::TempoList sub{std::min(tb, tl.n - j0), {}};
+            for (int j = 0; j < sub.n; ++j) sub.step[j] = tl.step[j0 + j];
+            hpfw::launch_tempo_scale(d_db + c0 * hpfw::kBins * c, nc, c, sub, ct, scaled, s);
+            if ((rc = check_launch("tempo_scale"))) return rc;
+            {
+                Timed t(h, K_PROJECT, s);
+                hpfw::launch_hashprints_q(images, n_shifts, scaled, nullptr, nc * sub.n, (int)ct, d_hp + (c0 * tl.n + j0) * per_pair, nullptr, s);
+            }
+            if ((rc = check_launch("project"))) return rc;
+        }
+    }
+    return 0;
+}
+
+// PCM (device) -> hashprints [n_clips][n_tempos][max(n_shifts, 1)][ct - 99]: front ends as hpfw_gpu_stage_spectrogram runs them
+// (the dB spectrogram finished in the S workspace), then tempo_back on each pass
+int extract_tempo_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const float *tempos, int n_tempos,
+                        const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream)
+{
+    hpfw::TempoList tl;
+    int rc = check_tempo_call(h, tempos, n_tempos, shifts, n_shifts, &tl);
+    if (rc) return rc;
+    if (!d_pcm || !d_hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    DevPlan *dp;
+    if ((rc = get_plan(h, n_samples, &dp))) return rc;
+    const int64_t c = dp->hp.c, ct = tempo_common_columns(c, tl);
+    if (ct - (hpfw::kCtx - 1) - hpfw::kLag < 1) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint at the slowest tempo");
+    if (n_clips == 0) return 0;
+    const int64_t per_clip = (int64_t)tl.n * std::max(n_shifts, 1) * (ct - (hpfw::kCtx - 1) - hpfw::kLag);
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_shifts && (rc = shift_images(h, shifts, n_shifts, s))) return rc;
+        const void *images = n_shifts ? h->d_shift_images.get() : h->d_fq_image.get();
+        const int nbmax = pass_clips(h, dp, n_clips);
+        if ((rc = ensure_ws(h, dp, nbmax, nbmax))) return rc;
+        for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
+            const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
+            if ((rc = run_front(h, dp, d_pcm + c0 * n_samples, nb, 0, true, s))) return rc;
+            if ((rc = tempo_back(h, images, n_shifts, h->ws[2].as<float>(), nb, c, tl, ct, d_hp + c0 * per_clip, s))) return rc;
+        }
+        return 0;
+    });
+}
+
 // PCM (device) -> hashprints [n_clips][max(n_shifts, 1)][n_hp] as hashprints_from_db: front ends of up to a pass of clips, back
 // ends of up to kBackBatch clips
 int extract_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const int32_t *shifts, int n_shifts,
@@ -1171,6 +1278,54 @@ int search_round_trip(const uint64_t *q_hp, const int64_t *q_off, int64_t n_sets
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
     if (!rc && hipMemcpy(out, d_out.get(), (size_t)n_out * sizeof(Hit), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(HPFW_E_HIP, "D2H copy failed");
+    return rc;
+}
+
+// the host-buffer round trip of an extraction whose output is per_clip hashprints per clip: device(d_pcm, cnt, d_hp, stream)
+// extracts cnt clips
+template <class Device>
+int staged_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, int64_t per_clip, uint64_t *hp,
+                      Device device)
+{
+    int rc;
+    // uploads in chunks on a copy stream, two device buffers deep, so that the PCIe transfer of chunk
+    // i + 1 runs under the kernels of chunk i (from pinned host memory; a pageable source is staged
+    // by the runtime and overlaps only partly)
+    const int64_t chunk = std::min<int64_t>(n_clips, std::max<int64_t>(1, (192ll << 20) / (n_samples * 2)));
+    if ((rc = ensure(h->stage_hp, (size_t)n_clips * std::max<int64_t>(per_clip, 1) * 8))) return rc;
+    for (int b = 0; b < 2; ++b) {
+        if (b == 1 && chunk >= n_clips) break; // one chunk: one buffer
+        if ((rc = ensure(h->stage_pcm[b], (size_t)chunk * n_samples * 2))) return rc;
+    }
+    if (!h->stage_consumed[1]) { // (made last: a set left incomplete by a failure is made anew by the next call)
+        HIP_TRY(h->stage_copy.create());
+        HIP_TRY(h->stage_comp.create());
+        for (int b = 0; b < 2; ++b) {
+            HIP_TRY(h->stage_copied[b].create());
+            HIP_TRY(h->stage_consumed[b].create());
+        }
+    }
+    hipStream_t s_copy = h->stage_copy.get(), s_comp = h->stage_comp.get();
+    uint64_t *d_hp = h->stage_hp.as<uint64_t>();
+    int64_t ci = 0;
+    for (int64_t c0 = 0; !rc && c0 < n_clips; c0 += chunk, ++ci) {
+        const int b = (int)(ci & 1);
+        const int64_t cnt = std::min(chunk, n_clips - c0);
+        int16_t *d_pcm = h->stage_pcm[b].as<int16_t>();
+        hipEvent_t copied = h->stage_copied[b].get(), consumed = h->stage_consumed[b].get();
+        if (ci >= 2 && hipStreamWaitEvent(s_copy, consumed, 0) != hipSuccess) rc = fail(HPFW_E_HIP, "event wait failed");
+        if (!rc && hipMemcpyAsync(d_pcm, pcm + c0 * n_samples, (size_t)cnt * n_samples * 2, hipMemcpyHostToDevice, s_copy) !=
+                       hipSuccess)
+            rc = fail(HPFW_E_HIP, "H2D copy failed");
+        if (!rc && (hipEventRecord(copied, s_copy) != hipSuccess || hipStreamWaitEvent(s_comp, copied, 0) != hipSuccess))
+            rc = fail(HPFW_E_HIP, "event record failed");
+        if (!rc) rc = device(d_pcm, cnt, d_hp + c0 * per_clip, s_comp);
+        if (!rc && hipEventRecord(consumed, s_comp) != hipSuccess) rc = fail(HPFW_E_HIP, "event record failed");
+    }
+    if (hipStreamSynchronize(s_copy) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "H2D copy failed");
+    if (!rc && hipMemcpyAsync(hp, d_hp, (size_t)n_clips * per_clip * 8, hipMemcpyDeviceToHost, s_comp) != hipSuccess)
+        rc = fail(HPFW_E_HIP, "D2H copy failed");
+    if (hipStreamSynchronize(s_comp) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "kernel execution failed");
     return rc;
 }
 
@@ -1379,46 +1534,10 @@ static int extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples
     int rc = hpfw_gpu_geometry(h, n_samples, &g);
     if (rc) return rc;
     if (n_clips == 0) return 0;
-    // uploads in chunks on a copy stream, two device buffers deep, so that the PCIe transfer of chunk
-    // i + 1 runs under the kernels of chunk i (from pinned host memory; a pageable source is staged
-    // by the runtime and overlaps only partly)
-    const int64_t chunk = std::min<int64_t>(n_clips, std::max<int64_t>(1, (192ll << 20) / (n_samples * 2)));
-    const int64_t per_clip = std::max(n_shifts, 1) * g.n_hp;
-    if ((rc = ensure(h->stage_hp, (size_t)n_clips * std::max<int64_t>(per_clip, 1) * 8))) return rc;
-    for (int b = 0; b < 2; ++b) {
-        if (b == 1 && chunk >= n_clips) break; // one chunk: one buffer
-        if ((rc = ensure(h->stage_pcm[b], (size_t)chunk * n_samples * 2))) return rc;
-    }
-    if (!h->stage_consumed[1]) { // (made last: a set left incomplete by a failure is made anew by the next call)
-        HIP_TRY(h->stage_copy.create());
-        HIP_TRY(h->stage_comp.create());
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(h->stage_copied[b].create());
-            HIP_TRY(h->stage_consumed[b].create());
-        }
-    }
-    hipStream_t s_copy = h->stage_copy.get(), s_comp = h->stage_comp.get();
-    uint64_t *d_hp = h->stage_hp.as<uint64_t>();
-    int64_t ci = 0;
-    for (int64_t c0 = 0; !rc && c0 < n_clips; c0 += chunk, ++ci) {
-        const int b = (int)(ci & 1);
-        const int64_t cnt = std::min(chunk, n_clips - c0);
-        int16_t *d_pcm = h->stage_pcm[b].as<int16_t>();
-        hipEvent_t copied = h->stage_copied[b].get(), consumed = h->stage_consumed[b].get();
-        if (ci >= 2 && hipStreamWaitEvent(s_copy, consumed, 0) != hipSuccess) rc = fail(HPFW_E_HIP, "event wait failed");
-        if (!rc && hipMemcpyAsync(d_pcm, pcm + c0 * n_samples, (size_t)cnt * n_samples * 2, hipMemcpyHostToDevice, s_copy) !=
-                       hipSuccess)
-            rc = fail(HPFW_E_HIP, "H2D copy failed");
-        if (!rc && (hipEventRecord(copied, s_copy) != hipSuccess || hipStreamWaitEvent(s_comp, copied, 0) != hipSuccess))
-            rc = fail(HPFW_E_HIP, "event record failed");
-        if (!rc) rc = extract_pcm16(h, d_pcm, n_samples, cnt, shifts, n_shifts, d_hp + c0 * per_clip, s_comp);
-        if (!rc && hipEventRecord(consumed, s_comp) != hipSuccess) rc = fail(HPFW_E_HIP, "event record failed");
-    }
-    if (hipStreamSynchronize(s_copy) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "H2D copy failed");
-    if (!rc && hipMemcpyAsync(hp, d_hp, (size_t)n_clips * per_clip * 8, hipMemcpyDeviceToHost, s_comp) != hipSuccess)
-        rc = fail(HPFW_E_HIP, "D2H copy failed");
-    if (hipStreamSynchronize(s_comp) != hipSuccess && !rc) rc = fail(HPFW_E_HIP, "kernel execution failed");
-    return rc;
+    return staged_pcm16_host(h, pcm, n_samples, n_clips, std::max(n_shifts, 1) * g.n_hp, hp,
+                             [&](const int16_t *d_pcm, int64_t cnt, uint64_t *d_hp, hipStream_t st) {
+                                 return extract_pcm16(h, d_pcm, n_samples, cnt, shifts, n_shifts, d_hp, st);
+                             });
 }
 
 int hpfw_gpu_extract_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, uint64_t *hp)
@@ -1431,6 +1550,60 @@ int hpfw_gpu_extract_transposed_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int6
 {
     if (int rc = check_transposed(h, shifts, n_shifts)) return rc;
     return extract_pcm16_host(h, pcm, n_samples, n_clips, shifts, n_shifts, hp);
+}
+
+int hpfw_gpu_tempo_columns(int64_t c, const float *tempos, int n_tempos, int64_t *c_out)
+{
+    if (int rc = check_tempos(tempos, n_tempos, 0)) return rc;
+    if (c < 1 || !c_out) return fail(HPFW_E_INVALID, "bad argument");
+    hpfw::TempoList tl{n_tempos, {}};
+    for (int i = 0; i < n_tempos; ++i) tl.step[i] = hpfw::tempo_step(tempos[i]);
+    *c_out = tempo_common_columns(c, tl);
+    return 0;
+}
+
+int hpfw_gpu_hashprints_from_db_tempo(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, const float *tempos, int n_tempos,
+                                      const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream)
+{
+    hpfw::TempoList tl;
+    int rc = check_tempo_call(h, tempos, n_tempos, shifts, n_shifts, &tl);
+    if (rc) return rc;
+    if (!d_db || !d_hp || n_clips < 0 || c < 1) return fail(HPFW_E_INVALID, "bad argument");
+    const int64_t ct = tempo_common_columns(c, tl);
+    if (ct - (hpfw::kCtx - 1) - hpfw::kLag < 1) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint at the slowest tempo");
+    if (n_clips == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_shifts && (rc = shift_images(h, shifts, n_shifts, s))) return rc;
+        const void *images = n_shifts ? h->d_shift_images.get() : h->d_fq_image.get();
+        return tempo_back(h, images, n_shifts, d_db, n_clips, c, tl, ct, d_hp, s);
+    });
+}
+
+int hpfw_gpu_extract_tempo_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const float *tempos,
+                                 int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream)
+{
+    return extract_tempo_pcm16(h, d_pcm, n_samples, n_clips, tempos, n_tempos, shifts, n_shifts, d_hp, stream);
+}
+
+int hpfw_gpu_extract_tempo_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const float *tempos,
+                                      int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp)
+{
+    hpfw::TempoList tl;
+    int rc = check_tempo_call(h, tempos, n_tempos, shifts, n_shifts, &tl);
+    if (rc) return rc;
+    if (!pcm || !hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hpfw_geometry g;
+    if ((rc = hpfw_gpu_geometry(h, n_samples, &g))) return rc;
+    const int64_t nhp = tempo_common_columns(g.c, tl) - (hpfw::kCtx - 1) - hpfw::kLag;
+    if (nhp < 1) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint at the slowest tempo");
+    if (n_clips == 0) return 0;
+    return staged_pcm16_host(h, pcm, n_samples, n_clips, (int64_t)tl.n * std::max(n_shifts, 1) * nhp, hp,
+                             [&](const int16_t *d_pcm, int64_t cnt, uint64_t *d_hp, hipStream_t st) {
+                                 return extract_tempo_pcm16(h, d_pcm, n_samples, cnt, tempos, n_tempos, shifts, n_shifts, d_hp, st);
+                             });
 }
 
 // Host half of the tables of a clip length, built on the CALLING thread and kept for the next entry point that meets

@@ -1,6 +1,7 @@
 // kernels.h -- host-callable launchers of the gfx950 kernels (one per hot loop of the reference,
 // SURVEY.md section 2.1).  Each launcher only enqueues on `stream`.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <vector>
 #include <atomic>
@@ -255,6 +256,18 @@ struct ShiftList {
     int s[kMaxShifts];
 };
 void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s);
+// queries at another tempo (k_tempo.hip): tempo rho moves along the source by step = rint(65536 / rho)
+// sixteenths of a column per output column; a clip of c columns gives (c - 1) 65536 / step + 1 of them
+constexpr int kMaxTempos = 64;
+struct TempoList {
+    int n;
+    int32_t step[kMaxTempos];
+};
+inline int32_t tempo_step(float rho) { return (int32_t)std::rint(65536.0 / (double)rho); }
+inline int64_t tempo_columns(int64_t c, int32_t step) { return (c - 1) * 65536 / step + 1; }
+// db [n_clips][121][c] -> out [n_clips][tl.n][121][ct]: column k of tempo r interpolates source position k tl.step[r] / 65536
+// (ct <= tempo_columns(c, every step))
+void launch_tempo_scale(const float *d_db, int n_clips, int64_t c, const TempoList &tl, int64_t ct, float *d_out, hipStream_t s);
 
 // ---- HashprintHandle with other template arguments (k_hashprint_cfg.hip) ----------------------------
 struct CfgArgs {

@@ -42,11 +42,17 @@ class LiveSongIdentification:
     def index(self, filenames: Sequence[str]):
         self.build(self.collector.prepare(list(filenames)))
 
-    def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None):
+    def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None,
+            tempos: Optional[Sequence[float]] = None):
         """per query (label, [(distance, name, offset) x <= k]) ordered by (distance, position in the
         database); None in place of the list for a file that yields no hashprint.  shifts: bin shifts of the query's
         constant-Q spectrogram to search as well (t semitones above the indexed recording is
-        s = 2t): each clip's smallest distance over them, and every hit is (distance, name, offset, shift)"""
+        s = 2t): each clip's smallest distance over them, and every hit is (distance, name, offset, shift).  tempos:
+        tempo factors (query tempo / indexed tempo) to search, each combined with every shift:
+        every hit is (distance, name, offset, shift, tempo), shift 0 when shifts is None, offset in the indexed
+        recording; a query too short for the slowest tempo yields None"""
+        if tempos is not None:
+            return self._top_tempo(list(filenames), k, None if shifts is None else list(shifts), list(tempos))
         if shifts is not None:
             return self._top_transposed(list(filenames), k, list(shifts))
         hps = self.collector.calc_hashprints(list(filenames))
@@ -63,9 +69,27 @@ class LiveSongIdentification:
 
     def _top_transposed(self, filenames: List[str], k: int, shifts: List[int]):
         shifts = _lib.check_shifts(shifts)
+        return self._top_sets(filenames, k, len(shifts), lambda g, x: g.extract_transposed(x, shifts)[0],
+                              lambda h: (shifts[int(h["shift_index"])],), "transposed")
+
+    def _top_tempo(self, filenames: List[str], k: int, shifts: Optional[List[int]], tempos: List[float]):
+        if shifts is not None:
+            shifts = _lib.check_shifts(shifts)
+        n_s = len(shifts) if shifts else 1
+        _lib.check_tempos(tempos, 0 if shifts is None else len(shifts))
+
+        def decode(h):
+            j, i = divmod(int(h["shift_index"]), n_s)                 # variant v = j max(S, 1) + i
+            return (shifts[i] if shifts else 0, tempos[j])
+        return self._top_sets(filenames, k, len(tempos) * n_s, lambda g, x: g.extract_tempo(x, tempos, shifts)[0], decode,
+                              "tempo")
+
+    def _top_sets(self, filenames: List[str], k: int, n_sets: int, extract, decode, what: str):
+        """the search of n_sets hashprint sets per query (extract(gpu, pcm) -> [n_sets][n_hp]) merged per clip
+        (hpfw_gpu_search_topk_transposed); decode(hit) -> what a hit adds to (distance, name, offset)"""
         extractor = self.collector.gpu()                  # the collector's filters
         if extractor.get_projection() != 1:
-            raise _lib.HpfwError("transposed search needs projection mode 1 (fixed point)", _lib.E_INVALID)
+            raise _lib.HpfwError(f"{what} search needs projection mode 1 (fixed point)", _lib.E_INVALID)
         out = [(f, None) for f in filenames]
         sets, good = [], []
         for i, f in enumerate(filenames):
@@ -75,7 +99,7 @@ class LiveSongIdentification:
                 x = _lib.read_wav_44k(self._gpu, f, self._resample)
                 if x.size == 0:
                     continue
-                sets.extend(extractor.extract_transposed(x, shifts)[0])
+                sets.extend(extract(extractor, x))
             except _lib.HpfwError as e:
                 if e.status in (_lib.E_IO, _lib.E_UNSUPPORTED):
                     continue
@@ -84,24 +108,27 @@ class LiveSongIdentification:
         if good and self.names:
             off = np.zeros(len(sets) + 1, np.int64)
             np.cumsum([hp.size for hp in sets], out=off[1:])
-            hits = self._gpu.search_topk_transposed(np.concatenate(sets), off, len(shifts), k)
+            hits = self._gpu.search_topk_transposed(np.concatenate(sets), off, n_sets, k)
             for row, i in zip(hits, good):
-                out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"]), shifts[int(h["shift_index"])])
+                out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"])) + decode(h)
                                          for h in row if h["clip"] != 0xFFFFFFFF])
         return out
 
-    def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None):
+    def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None,
+               tempos: Optional[Sequence[float]] = None):
         """prints what the reference prints (live_song_id.h:38,47-48,53); returns (wrong, accuracy).  With shifts the
-        line of a match also names its shift in bins"""
+        line of a match also names its shift in bins, with tempos its shift and tempo"""
         wrong = 0
-        for label, best in self.top(filenames, 1, shifts):
+        for label, best in self.top(filenames, 1, shifts, tempos):
             print("=> Finding", label)
             if not best:
                 continue
             dist, name, offset = best[0][:3]
             if os.path.splitext(os.path.basename(name))[0] not in label:
                 wrong += 1
-            if shifts is None:
+            if tempos is not None:
+                print(f"=> {name} {dist} {offset} shift {best[0][3]} tempo {best[0][4]:g}\n")
+            elif shifts is None:
                 print(f"=> {name} {dist} {offset}\n")
             else:
                 print(f"=> {name} {dist} {offset} shift {best[0][3]}\n")

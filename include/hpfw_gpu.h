@@ -399,6 +399,28 @@ int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, 
                                            int n_shifts, int k, hpfw_shift_hit *d_out, void *stream);
 int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
                                     int k, hpfw_shift_hit *out);
+/* ---- queries at another tempo: a performance faster or slower than the indexed recording.
+ * tempos: host array of 1 to 64 finite factors in [0.5, 2] (query tempo / indexed tempo; 1.05 = played 5 % faster) whose
+ * steps rint(65536 / tempo) are distinct.  Tempo rho rescales the query's dB spectrogram S [121][C] onto the indexed time
+ * axis: column k interpolates S linearly at source column k step / 65536 (64-bit fixed point, exact products in double,
+ * one rounding to float).  Every tempo of a call is cut to the common length c_t = min over the tempos of
+ * floor((C - 1) 65536 / step) + 1 columns, so every variant has n_hp_t = c_t - 99 hashprints and the distances of
+ * different tempos are comparable; offsets are positions in the indexed recording.  shifts: NULL with n_shifts = 0 (no
+ * shift), or a list as the transposed entry points take it; variant v = j max(n_shifts, 1) + i is tempo j with shift i,
+ * n_tempos max(n_shifts, 1) <= 64.  tempos = {1.0} gives what extraction gives.  Projection mode 1 only; any other argument
+ * is HPFW_E_INVALID (checked before the handle is used), n_hp_t < 1 is HPFW_E_UNSUPPORTED.
+ * d_hp [n_clips][n_tempos][max(n_shifts, 1)][n_hp_t].  To search, pass the V = n_tempos max(n_shifts, 1) sets of each
+ * query to hpfw_gpu_search_topk_transposed(_device) with n_shifts = V: a hit's shift_index is then v. */
+/* c_t of a clip of c columns under a tempo list (no handle needed) */
+int hpfw_gpu_tempo_columns(int64_t c, const float *tempos, int n_tempos, int64_t *c_out);
+/* dB spectrograms [n_clips][121][c] (device, as hpfw_gpu_stage_spectrogram writes them) -> d_hp as above */
+int hpfw_gpu_hashprints_from_db_tempo(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, const float *tempos,
+                                      int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream);
+int hpfw_gpu_extract_tempo_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips, const float *tempos,
+                                 int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream);
+/* host buffers, as hpfw_gpu_extract_pcm16_host: copies in, runs, copies out, synchronises */
+int hpfw_gpu_extract_tempo_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const float *tempos,
+                                      int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp);
 /* parity checkpoint of mode 1: the exact integer sums D[r][i] = sum_k fq[r][k] (u[k][i] - u[k][i + 80]) whose signs are
  * the hashprint bits, d_delta [n_clips][64][c - 99] int64 (device); d_hp may be NULL.  Same kernel as extraction. */
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp,
