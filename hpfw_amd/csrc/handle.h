@@ -1,0 +1,331 @@
+// handle.h -- what the sources of the C-ABI declared in include/hpfw_gpu.h (handle.hip, plans.hip, extract.hip, learn.hip,
+// search.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
+// ParallelCollector::collect_fingerprints' parallel_for, reference
+// include/hpfw/core/parallel_collector.h:115-137) and MemoryStorage::build/find
+// (include/hpfw/audioproblems/live-song-id/storage.h:21-64).  All arithmetic is in the kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <condition_variable>
+#include <chrono>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/hpfw_gpu.h"
+#include "combiner.h"
+#include "hip_owned.h"
+#include "kernels.h"
+#include "legacy_internal.h" // hpfw_internal_set_error (handle.hip), hpfw_internal_note_idle (plans.hip)
+#include "plan.h"
+
+using hpfw::DevBuf, hpfw::Event, hpfw::HostBuf, hpfw::Stream;
+
+int fail(int code, const std::string &msg);
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(HPFW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+    } while (0)
+
+// Device memory of the per-length tables.  A plan takes its memory from the handle's pool: small tables are carved out of
+// 4 MB chunks, large ones are blocks of their own, and an evicted plan's chunks and blocks go back to the pool for the next
+// length (a corpus of tracks brings a new length with every file: ~40 hipMalloc and, at eviction, as many hipFree per plan
+// cost more than generating the tables).
+struct DevPlan {
+    hpfw_gpu *owner = nullptr;
+    std::vector<DevBuf> blocks; // what this plan holds of the pool, each block with its real size
+    char *cur = nullptr;                           // the open chunk
+    size_t left = 0;
+    // small tables are written to a host image of the open chunk and go over in one copy per run of them (plan_flush):
+    // some thirty-five synchronous copies of a few KB each cost more than the tables' bytes
+    char *chunk_base = nullptr;
+    std::vector<char> stage;
+    std::vector<std::pair<size_t, size_t>> staged; // (offset, bytes) written to the image, in order
+    hpfw::HostPlan hp;
+    hpfw::ColsQArgs cols;
+    hpfw::Rows2Out rows_out;
+    hpfw::RowsArgs rows;
+    hpfw::BzArgs bz; // clip lengths with a prime factor above 7 (hp.bluestein)
+    hpfw::CqPlanDev cq;
+    std::vector<hpfw::CqClassDev> cls;
+    size_t bytes = 0;      // device memory of the tables
+    uint64_t last_use = 0; // for the least-recently-used eviction in get_plan
+    ~DevPlan(); // (gives its blocks back to the handle's pool)
+};
+
+struct PlanTiming; // (plans.hip)
+
+enum KernelKind { K_ROWS = 0, K_COLS, K_CQ, K_DB, K_PROJECT, K_PACK, K_SCAN, K_TOPK, K_PAIRS, K_FWD, K_COUNT };
+
+struct TimedLaunch {
+    int kind;
+    Event a, b;
+};
+
+// the first HIP failure met by a destructor (Timed, a fan-out's join) during the call in progress (ordered_call)
+struct CallStatus {
+    int rc = 0;
+    std::string msg;
+};
+
+struct hpfw_gpu {
+    int device = 0;
+    bool has_filters = false;
+    DevBuf d_fpack;
+    DevBuf d_fq_image; // the filters' fixed-point digits (k_project_q.hip)
+    int projection = 1; // 1: fixed point (S9q), 0: the f32 fma chain (S9); hpfw_gpu_set_projection
+    // the tables of every clip length in use and the device memory they come from (plans.hip)
+    struct PlanCache {
+        PlanCache(); // (both in plans.hip, where PlanTiming is known; the destructor prints its report)
+        ~PlanCache();
+        // free chunks and blocks of evicted plans, by size (declared before `plans`: a plan gives its blocks back when it goes)
+        std::multimap<size_t, DevBuf> dev_pool;
+        size_t dev_pool_bytes = 0;
+        std::map<int64_t, std::unique_ptr<DevPlan>> plans; // one per clip length, least recently used evicted
+        // host halves of plans prepared ahead by other threads (hpfw_gpu_prepare_length): a null entry is being built
+        std::mutex host_mtx;
+        std::condition_variable host_cv;
+        std::map<int64_t, std::unique_ptr<hpfw::HostPlan>> host_ready;
+        std::set<int64_t> host_seen; // lengths being prepared, prepared, or resident on the device (not prepared again while they are)
+        size_t plan_bytes = 0;
+        uint64_t plan_clock = 0;
+        // plans last used at or before this value of plan_clock are known to be idle: the caller has waited for all the work it
+        // queued on this handle since (hpfw_internal_note_idle: the file collectors, once per window of files) -- such plans
+        // are evicted without the device-wide wait that an eviction otherwise needs
+        uint64_t idle_clock = 0;
+        std::unique_ptr<PlanTiming> plan_timing; // HPFW_PLAN_TIMING
+        // The tables of a new clip length go to the device on a stream of the handle's own, from a pinned ring, without a host
+        // wait (the stream that first uses them waits for plan_ev): synchronous copies on the default stream waited behind
+        // whatever shared its hardware queue -- after bench.py's host-buffer section that was the collector's extraction stream,
+        // and a corpus of distinct lengths lost a fifth of its rate (tools/ffi_interaction.sh)
+        Stream plan_stream;
+        HostBuf pin_ring;
+        size_t pin_off = 0;
+        // the tables a new length generates on the device (default stream) are awaited by the stream that first uses them
+        // (ordered_call), not by the host: a caller on a stream of its own keeps preparing lengths while earlier files run
+        Event plan_ev;
+        bool plan_ev_pending = false;
+    } cache;
+    unsigned conventions = 0; // hpfw_gpu_set_conventions: essentia conventions that cannot be checked offline
+    // clips per pass: 2.5 GB of workspace at 30 s; every launch but the forward transform's chunks fills the 256 CUs many
+    // times over, and what one stage leaves for the next (forward bins, dB terms: 2.3 MB per clip) is still in the caches
+    // when it is read (1000 clips: 10.25 ms in one pass, 10.0 in four)
+    int batch = 256;
+    // extraction workspace: yp, x, mag, proj, wave maxima [clip][121][16], pairs, second planar buffer of the chirp-z
+    // forward transform
+    DevBuf ws[7];
+    // the index and the scratch of its searches (search.hip)
+    struct Index {
+        DevBuf d_db; // uint64 hashprints
+        std::vector<int64_t> db_off{0};
+        DevBuf d_db_off;
+        bool db_off_dirty = true;
+        uint32_t clip_base = 0;
+        DevBuf d_best, d_q_off;
+        DevBuf d_qa; // queries expanded to fp4 for the matrix-core scan
+        DevBuf d_gk; // longest query of each group of 32
+        DevBuf d_topk_scratch;
+        DevBuf d_shift_hits; // the per-shift top-k lists of a transposed search
+    } index;
+    // filter learning (learn.hip)
+    struct Learn {
+        // accum_cov of ParallelCollector (parallel_collector.h:76), upper tiles only
+        DevBuf d_cov;
+        DevBuf d_cov_ws; // scratch of the covariance kernels
+        DevBuf d_cov_tiles;
+        int64_t cov_files = 0;
+        // HashprintHandle configurations other than the default (hpfw_gpu_cfg_*): filter operand images by config
+        std::map<std::vector<int>, DevBuf> cfg_fpack;
+        DevBuf d_cfg_proj;
+        struct CfgCov {
+            DevBuf d_accum;
+            DevBuf d_tiles;
+            int64_t clips = 0;
+        };
+        std::map<std::vector<int>, CfgCov> cfg_cov; // accum_cov of other configurations, by (rows, context)
+        DevBuf d_cfg_cov_ws;
+    } learn;
+    // Mel front-end (learn.hip): tables (owned by `owned`), workspaces
+    struct Mel {
+        bool ready = false;
+        hpfw::HostPlan plan;
+        hpfw::RowsArgs rows;
+        const float *d_win = nullptr, *d_cpack = nullptr;
+        std::vector<DevBuf> owned;
+        DevBuf d_work, d_small;
+    } mel;
+    DevBuf d_cqwork; // chirp-z bands too long for the LDS (k_cq_big.hip)
+    // the size classes of the chirp-z stage run side by side (run_front): their workgroups differ in LDS footprint and
+    // one class alone leaves part of every CU's LDS and issue slots unused
+    static constexpr int kCqSide = 4;
+    Stream cq_side[kCqSide];
+    Event cq_fork, cq_join[kCqSide];
+    int cq_concurrent = 1; // HPFW_CQ_SERIAL=1 in the environment at creation: one class after the other on the caller's stream
+    // the forward transform of a large batch in chunks of fwd_chunk clips taken in turn by fwd_streams streams (the
+    // caller's and side streams): column stage and row stage of a chunk back to back, so that the column stage's output
+    // (5.3 MB per clip) is read back out of the Infinity Cache instead of HBM.  HPFW_FWD_CHUNK (0: one launch per stage
+    // for the whole batch), HPFW_FWD_STREAMS (1..5) in the environment at creation
+    int fwd_chunk = 16, fwd_streams = 2;
+    int cols_variant = 0; // HPFW_COLS_VARIANT (tests, diagnosis): kernels.h ColsQArgs::variant
+    int bz_chunk = 32;  // the same for the chirp-z forward transform's three kernels (HPFW_BZ_CHUNK; 38.6 -> 39.6 k clips/s at 30 s)
+    // staging of the host-buffer entry points: kept between calls (a one-file call is otherwise mostly
+    // allocation and stream set-up)
+    DevBuf stage_pcm[2];
+    DevBuf stage_hp;
+    Stream stage_copy, stage_comp;
+    Event stage_copied[2], stage_consumed[2];
+    DevBuf d_clipmax; // per-clip maximum magnitude (reference level of the dB conversion)
+    // ordering of consecutive entry points that were handed different streams (the workspaces are shared): the stream of
+    // the last call, and whether order_ev marks the end of its work (else the next call on another stream waits for that
+    // stream on the host)
+    Event order_ev;
+    hipStream_t order_stream = nullptr;
+    enum { kOrderNone, kOrderEvent, kOrderSync } order = kOrderNone;
+    CallStatus call; // what Timed and the fan-outs of the call in progress report (ordered_call)
+    // timing
+    Event ev0, ev1;
+    unsigned timing_mask = 0;
+    std::vector<TimedLaunch> timed;
+    std::vector<std::pair<Event, Event>> ev_pool;
+    float k_ms[K_COUNT] = {0};
+    int k_launches[K_COUNT] = {0};
+    // AudioCombiner's inverted index (k_combiner.hip), created on first use
+    std::unique_ptr<hpfw::Combiner> combiner;
+    // sample-rate conversion (k_resample.hip, extract.hip): the device image of each rate's table, made on first use;
+    // staging of the host entry point
+    struct Resample {
+        struct Table {
+            int32_t L = 0, M = 0, T = 0;
+            DevBuf d_taps;
+        };
+        std::map<int, Table> tables;
+        DevBuf in, out;
+    } rs;
+    // transposed queries (k_project_q.hip): the filter images of the shift list last used (cleared
+    // with the filters)
+    DevBuf d_shift_images;
+    std::vector<int32_t> shift_images_of;
+    // queries at another tempo (k_tempo.hip): the time-scaled dB spectrograms of a sub-batch of
+    // (clip, tempo) pairs (kTempoBudget, or one pair where a pair is larger)
+    DevBuf d_tempo;
+};
+
+// a workspace of at least `need` bytes (its contents are not kept when it grows)
+int ensure(DevBuf &b, size_t need, hpfw_gpu *pool_owner = nullptr);
+
+// Every entry point of a handle works in the handle's shared workspaces (ws[], d_clipmax, d_best, d_qa, the
+// index itself ...) and only enqueues on the caller's stream.  Two calls on different streams (a torch
+// side stream and the null stream, or the private non-blocking streams of the *_host entry points) would
+// otherwise overlap on those buffers: each call first makes its stream wait for the event the previous
+// call recorded, and records its own when it has enqueued its work.  A call whose record failed leaves no
+// event: the next call on another stream waits for its stream on the host.
+// ordered_call(h, s, body) returns body's status, else the first failure Timed or a fan-out's join reported
+// during it, else the record's.  A failed wait returns before anything is queued.
+inline int report(hpfw_gpu *h, hipError_t e, const char *what)
+{
+    if (e != hipSuccess && !h->call.rc) h->call = {HPFW_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
+    return e != hipSuccess;
+}
+
+template <class Body>
+int ordered_call(hpfw_gpu *h, hipStream_t s, Body &&body)
+{
+    if (h->order_stream != s) {
+        if (h->order == hpfw_gpu::kOrderEvent) HIP_TRY(hipStreamWaitEvent(s, h->order_ev.get(), 0));
+        if (h->order == hpfw_gpu::kOrderSync) HIP_TRY(hipStreamSynchronize(h->order_stream));
+    }
+    if (h->cache.plan_ev_pending) {
+        HIP_TRY(hipStreamWaitEvent(s, h->cache.plan_ev.get(), 0));
+        h->cache.plan_ev_pending = false; // (later calls on other streams are ordered after this one)
+    }
+    CallStatus outer = std::exchange(h->call, CallStatus{}); // (a call made inside another's body)
+    int rc = body();
+    const hipError_t recorded = hipEventRecord(h->order_ev.get(), s);
+    h->order_stream = s;
+    h->order = recorded == hipSuccess ? hpfw_gpu::kOrderEvent : hpfw_gpu::kOrderSync;
+    CallStatus mine = std::exchange(h->call, std::move(outer));
+    if (!rc && mine.rc) rc = fail(mine.rc, mine.msg);
+    if (!rc && recorded != hipSuccess) rc = fail(HPFW_E_HIP, std::string("hipEventRecord: ") + hipGetErrorString(recorded));
+    return rc;
+}
+
+// the span of the launches in its scope, when h->timing_mask selects `kind`
+struct Timed {
+    hpfw_gpu *h;
+    int kind;
+    hipStream_t s;
+    bool on = false;
+    Event a, b;
+    Timed(hpfw_gpu *h_, int kind_, hipStream_t s_) : h(h_), kind(kind_), s(s_)
+    {
+        if (!((h->timing_mask >> kind) & 1u)) return;
+        if (h->ev_pool.empty()) {
+            if (report(h, a.create(hipEventDefault), "timing event") || report(h, b.create(hipEventDefault), "timing event")) return;
+        } else {
+            a = std::move(h->ev_pool.back().first);
+            b = std::move(h->ev_pool.back().second);
+            h->ev_pool.pop_back();
+        }
+        on = !report(h, hipEventRecord(a.get(), s), "timing event record");
+    }
+    ~Timed()
+    {
+        if (on && !report(h, hipEventRecord(b.get(), s), "timing event record")) h->timed.push_back({kind, std::move(a), std::move(b)});
+    }
+};
+
+inline int check_launch(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(HPFW_E_HIP, std::string("launch of ") + what + ": " + hipGetErrorString(e));
+    return 0;
+}
+
+// The device side of an entry point on host buffers (the null stream): take() allocates a buffer, uploads its input or
+// sets its bytes, and names the host buffer it goes back to; run() makes the call, waits for the whole device if asked,
+// and downloads (blocking copies).  Every step after a failure does nothing; the buffers are freed on every exit.  A failed
+// allocation is HPFW_E_NOMEM.
+struct HostTrip {
+    int rc = 0;
+    std::vector<std::pair<DevBuf, void *>> bufs; // (device buffer, host destination or null)
+    // `bytes` of device memory: a copy of host `src` when given, else every byte `fill` when fill >= 0
+    template <class T>
+    T *take(size_t bytes, const void *src = nullptr, int fill = -1, void *dst = nullptr)
+    {
+        DevBuf &b = bufs.emplace_back(DevBuf(), dst).first;
+        if (!rc && b.alloc(bytes) != hipSuccess) rc = fail(HPFW_E_NOMEM, "hipMalloc failed");
+        if (!rc && ((src && hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
+                    (fill >= 0 && hipMemset(b.get(), fill, bytes) != hipSuccess)))
+            rc = fail(HPFW_E_HIP, "H2D copy failed");
+        return b.as<T>();
+    }
+    template <class Call>
+    int run(bool wait, Call call)
+    {
+        if (!rc) rc = call();
+        if (!rc && wait && hipDeviceSynchronize() != hipSuccess) rc = fail(HPFW_E_HIP, "kernel execution failed");
+        for (auto &[b, dst] : bufs)
+            if (!rc && dst && hipMemcpy(dst, b.get(), b.capacity(), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HPFW_E_HIP, "D2H copy failed");
+        return rc;
+    }
+};
+
+// plans.hip
+int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out);
+hipError_t init_plans(hpfw_gpu *h); // the table stream and event, HPFW_PLAN_TIMING (at the handle's creation)
+void clear_plans(hpfw_gpu *h);      // every length's tables and host half (no work may be using them)
+// extract.hip
+int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips);
+int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns);
+int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, bool finish_db, hipStream_t s);
+

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void mel_db_kernel(const float *__restrict__ p
 
 int mel_frames(int64_t n) { return n <= 0 ? 0 : (int)((n + kMelHalf + kMelHop - 1) / kMelHop); }
 
-// workspace for n_clips clips: block sums, positions, counts are separate small buffers (see api.hip);
+// workspace for n_clips clips: block sums, positions, counts are separate small buffers (see learn.hip);
 // this is the size of the split spectra and the band powers
 size_t mel_work_bytes(int64_t n, int n_clips)
 {

@@ -36,9 +36,6 @@
 #include "hip_owned.h"
 #include "legacy_internal.h" // the extern "C" signatures multi.cpp sees, checked against the definitions below
 
-extern "C" void hpfw_internal_set_error(const char *msg); // api.hip: feeds hpfw_gpu_last_error()
-extern "C" void hpfw_internal_note_idle(hpfw_gpu *h);      // api.hip: every plan used so far is idle (evictable without a device wait)
-
 namespace {
 
 // rate_any: NULL = 44.1 kHz only; else any rate in [8 000, 192 000] Hz is accepted and stored there

@@ -6,6 +6,8 @@
 #include "../../include/hpfw_gpu.h"
 
 extern "C" {
+void hpfw_internal_set_error(const char *msg); // handle.hip: feeds hpfw_gpu_last_error()
+void hpfw_internal_note_idle(hpfw_gpu *h);      // plans.hip: every plan used so far is idle (evictable without a device wait)
 typedef struct hpfw_prepare_job hpfw_prepare_job;
 // a collector on `device` with `cache` loaded (filters.cereal, accum_cov.cereal; NULL / "" = "cache/")
 hpfw_legacy_collector *hpfw_internal_collector_on_device(int device, const char *cache);

@@ -21,8 +21,6 @@
 #include "../../include/hpfw_gpu_multi_resample.h"
 #include "legacy_internal.h"
 
-extern "C" void hpfw_internal_set_error(const char *msg); // libhpfw_gpu.so: feeds hpfw_gpu_last_error()
-
 namespace {
 
 int fail(int code, const std::string &msg)

@@ -1,0 +1,489 @@
+// search.hip -- the index of hashprints and its searches (top-k, transposed, voting), and AudioCombiner's exact-hash
+// index (k_combiner.hip).
+#include "handle.h"
+
+namespace {
+// the host round trip of a search: the hashprints (elements Q) of query sets [0, n_sets) uploaded, their offsets rebased
+// to 0, device(d_q, rel, d_out) queued on the null stream, the n_out hits it wrote downloaded
+template <class Q, class Hit, class Device>
+int search_round_trip(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, Device device)
+{
+    const int64_t total = q_off[n_sets] - q_off[0];
+    if (total < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+    if (total && !q_hp) return fail(HPFW_E_INVALID, "null queries");
+    std::vector<int64_t> rel((size_t)n_sets + 1);
+    for (int64_t i = 0; i <= n_sets; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    HostTrip t;
+    const Q *d_q = t.take<Q>((size_t)std::max<int64_t>(total, 1) * sizeof(Q), total ? q_hp + q_off[0] : nullptr);
+    Hit *d_out = t.take<Hit>((size_t)n_out * sizeof(Hit), nullptr, -1, out);
+    return t.run(true, [&] { return device(d_q, rel.data(), d_out); });
+}
+
+// the index's offsets to the device when they changed since the last upload: on s, which the host then waits for
+int upload_db_off(hpfw_gpu *h, hipStream_t s)
+{
+    if (!h->index.db_off_dirty) return 0;
+    if (int rc = ensure(h->index.d_db_off, h->index.db_off.size() * 8)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->index.d_db_off.get(), h->index.db_off.data(), h->index.db_off.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->index.db_off_dirty = false;
+    return 0;
+}
+} // namespace
+
+extern "C" {
+
+// ---- index + search ----------------------------------------------------------------------------
+int hpfw_gpu_index_clear(hpfw_gpu *h)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    h->index.db_off.assign(1, 0);
+    h->index.db_off_dirty = true;
+    return 0;
+}
+
+static int index_add_impl(hpfw_gpu *h, const uint64_t *hp, const int64_t *offsets, int64_t n_clips, bool dev,
+                          hipStream_t s)
+{
+    if (!h || !hp || !offsets || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(HPFW_E_INVALID, "offsets must be non-decreasing");
+    const int64_t add = offsets[n_clips] - offsets[0];
+    const int64_t have = h->index.db_off.back();
+    return ordered_call(h, s, [&] {
+        const size_t need = (size_t)(have + add) * 8;
+        if (need > h->index.d_db.capacity()) {
+            DevBuf nd;
+            HIP_TRY(nd.alloc(std::max({need, h->index.d_db.capacity() * 2, (size_t)8 << 16})));
+            // earlier appends may still be in flight on a non-blocking stream the null-stream copy below would
+            // not wait for, and scans may still be reading the old buffer: growing is rare (capacity doubles)
+            HIP_TRY(hipDeviceSynchronize());
+            if (have) HIP_TRY(hipMemcpy(nd.get(), h->index.d_db.get(), (size_t)have * 8, hipMemcpyDeviceToDevice));
+            h->index.d_db = std::move(nd); // (the old buffer goes with nd)
+        }
+        uint64_t *dst = h->index.d_db.as<uint64_t>() + have;
+        if (add) {
+            if (dev)
+                HIP_TRY(hipMemcpyAsync(dst, hp + offsets[0], (size_t)add * 8, hipMemcpyDeviceToDevice, s));
+            else
+                HIP_TRY(hipMemcpy(dst, hp + offsets[0], (size_t)add * 8, hipMemcpyHostToDevice));
+        }
+        for (int64_t i = 0; i < n_clips; ++i) h->index.db_off.push_back(have + (offsets[i + 1] - offsets[0]));
+        h->index.db_off_dirty = true;
+        return 0;
+    });
+}
+
+int hpfw_gpu_index_add(hpfw_gpu *h, const uint64_t *hp, const int64_t *offsets, int64_t n_clips)
+{
+    return index_add_impl(h, hp, offsets, n_clips, false, nullptr);
+}
+
+int hpfw_gpu_index_add_device(hpfw_gpu *h, const uint64_t *d_hp, const int64_t *offsets, int64_t n_clips,
+                              void *stream)
+{
+    return index_add_impl(h, d_hp, offsets, n_clips, true, (hipStream_t)stream);
+}
+
+int64_t hpfw_gpu_index_size(hpfw_gpu *h) { return h ? (int64_t)h->index.db_off.size() - 1 : 0; }
+
+// the index back on the host (MemoryStorage::save, storage.h:67-75, dumps the whole db):
+// offsets [n_clips + 1] always; hp [offsets[n_clips]] when hp != NULL and hp_cap is large enough
+int hpfw_gpu_index_get(hpfw_gpu *h, int64_t *offsets, uint64_t *hp, int64_t hp_cap)
+{
+    if (!h || !offsets) return fail(HPFW_E_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    std::memcpy(offsets, h->index.db_off.data(), h->index.db_off.size() * sizeof(int64_t));
+    if (!hp) return 0;
+    const int64_t total = h->index.db_off.back();
+    if (hp_cap < total) return fail(HPFW_E_INVALID, "hashprint buffer too small for the index");
+    if (total) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(hp, h->index.d_db.get(), (size_t)total * 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int hpfw_gpu_index_set_clip_base(hpfw_gpu *h, uint32_t base)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    h->index.clip_base = base;
+    return 0;
+}
+
+int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
+                                hpfw_hit *d_out, void *stream)
+{
+    if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
+        const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+        int rc;
+        if (n_clips == 0) { // nothing indexed: every slot is "none"
+            hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->index.clip_base, d_out, s);
+            return check_launch("topk");
+        }
+        if ((rc = upload_db_off(h, s))) return rc;
+        int64_t k_max = 0;
+        for (int64_t i = 0; i < n_q; ++i) {
+            if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+            k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
+        }
+        if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+        if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
+        // queries are processed in groups so the (query, clip) table stays below 1 GiB
+        int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 27) / n_clips / 32 * 32);
+        qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
+        qgroup = std::min<int64_t>(qgroup, (int64_t)65535 * 8 / 32 * 32); // the scans put groups of 8 / 32 queries along gridDim.y
+        if ((rc = ensure(h->index.d_best, (size_t)qgroup * n_clips * 8))) return rc;
+        // The scan runs on the matrix cores (k_search_mfma.hip) unless the window does not fit the LDS
+        // (queries of several thousand hashprints) or HPFW_SEARCH_POPC asks for the xor/popcount kernel; fewer than
+        // 8 queries go one by one through the shifted-rows variant (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force
+        // the grouped / the shifted-rows kernel for any number of queries).
+        // A group of 32 queries is one MFMA tile: with fewer than 8 queries most of its rows would be padding
+        // and the popcount kernel (one workgroup per 8 queries) does less work.
+        const bool mfma = !std::getenv("HPFW_SEARCH_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024 &&
+                          k_max > 0 && (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
+        const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
+        int64_t n_max = 0;
+        for (int64_t i = 0; i < n_clips; ++i) n_max = std::max(n_max, h->index.db_off[i + 1] - h->index.db_off[i]);
+        if (mfma) {
+            if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
+            if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 8))) return rc;
+        }
+        std::vector<int> gk;
+        for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
+            const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
+            HIP_TRY(hipMemsetAsync(h->index.d_best.get(), 0xff, (size_t)ng * n_clips * 8, s));
+            hpfw::SearchArgs a;
+            a.db = h->index.d_db.as<uint64_t>();
+            a.db_off = h->index.d_db_off.as<int64_t>();
+            a.n_clips = (int)n_clips;
+            a.q = d_q_hp;
+            a.q_off = h->index.d_q_off.as<int64_t>() + g0;
+            a.n_q = ng;
+            a.k_max = (int)k_max;
+            a.best = h->index.d_best.as<uint64_t>();
+            const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !std::getenv("HPFW_SEARCH_POPC") && k_max > 0 && n_max > 0 &&
+                             hpfw::hamming_shift_lds_bytes((int)k_max) <= 160 * 1024;
+            if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
+                if ((rc = ensure(h->index.d_qa, hpfw::hamming_shift_image_bytes((int)k_max)))) return rc;
+                Timed t(h, K_SCAN, s);
+                for (int i = 0; i < ng; ++i) {
+                    const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
+                    if (kq <= 0) continue;
+                    hpfw::launch_hamming_shift(a.db, a.db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
+                                               d_q_hp + q_off[g0 + i], kq, h->index.d_qa.get(), a.best + (size_t)i * n_clips, s);
+                }
+            } else if (mfma && n_max > 0) {
+                gk.assign((size_t)(ng + 31) / 32 * 2, 0); // per group: longest query, shortest non-empty query
+                int kmin_all = 0;
+                for (int i = 0; i < ng; ++i) {
+                    const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
+                    int &mx = gk[(size_t)i / 32 * 2], &mn = gk[(size_t)i / 32 * 2 + 1];
+                    mx = std::max(mx, kq);
+                    if (kq > 0) mn = mn == 0 ? kq : std::min(mn, kq);
+                    if (kq > 0) kmin_all = kmin_all == 0 ? kq : std::min(kmin_all, kq);
+                }
+                HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_expand_queries(d_q_hp, a.q_off, ng, kt_pad, h->index.d_qa.get(), s);
+                // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
+                hpfw::launch_hamming_mfma(a, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)std::max<int64_t>(n_max - std::min<int64_t>(kmin_all, n_max) + 1, 1), s);
+            } else {
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_hamming_scan(a, s);
+            }
+            if ((rc = check_launch("hamming_scan"))) return rc;
+            {
+                Timed t(h, K_TOPK, s);
+                if (n_clips >= 16384 && ng <= 64) { // one workgroup per query would crawl through the whole table
+                    if ((rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes(ng, k)))) return rc;
+                    hpfw::launch_topk_two_step(a.best, ng, (int)n_clips, k, h->index.clip_base, h->index.d_topk_scratch.get(), d_out + g0 * k, s);
+                } else {
+                    hpfw::launch_topk(a.best, ng, (int)n_clips, k, h->index.clip_base, d_out + g0 * k, s);
+                }
+            }
+            if ((rc = check_launch("topk"))) return rc;
+        }
+        return 0;
+    });
+}
+
+int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k,
+                         hpfw_hit *out)
+{
+    if (!h || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    return search_round_trip(q_hp, q_off, n_q, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_hit *d_out) {
+        return hpfw_gpu_search_topk_device(h, d_q, rel, n_q, k, d_out, nullptr);
+    });
+}
+
+int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                           hpfw_shift_hit *d_out, void *stream)
+{
+    if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts)
+        return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        int rc;
+        // the per-shift lists: n_q * n_shifts queries in one pass of the existing scan, then one workgroup per query merges them
+        if ((rc = ensure(h->index.d_shift_hits, (size_t)n_q * n_shifts * k * sizeof(hpfw_hit)))) return rc;
+        if ((rc = hpfw_gpu_search_topk_device(h, d_q_hp, q_off, n_q * n_shifts, k, h->index.d_shift_hits.as<hpfw_hit>(), s))) return rc;
+        {
+            Timed t(h, K_TOPK, s);
+            hpfw::launch_topk_merge_shifts(h->index.d_shift_hits.get(), (int)n_q, n_shifts, k, d_out, s);
+        }
+        return check_launch("topk_merge_shifts");
+    });
+}
+
+int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                    hpfw_shift_hit *out)
+{
+    if (!h || !q_off || !out || n_q < 0 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts) return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    return search_round_trip(q_hp, q_off, n_q * n_shifts, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_shift_hit *d_out) {
+        return hpfw_gpu_search_topk_transposed_device(h, d_q, rel, n_q, n_shifts, k, d_out, nullptr);
+    });
+}
+
+// ---- AudioCombiner: exact-hash index + offset votes (k_combiner.hip) --------------------------------
+static hpfw::Combiner *combiner_of(hpfw_gpu *h)
+{
+    if (!h->combiner) h->combiner.reset(new hpfw::Combiner());
+    return h->combiner.get();
+}
+
+int hpfw_gpu_combiner_clear(hpfw_gpu *h)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    combiner_of(h)->clear();
+    return 0;
+}
+
+static int combiner_add_impl(hpfw_gpu *h, const uint16_t *hp, const int64_t *offsets, int64_t n_rec, bool dev, hipStream_t s)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, s, [&] {
+        std::string why;
+        const int rc = combiner_of(h)->add(hp, dev, offsets, n_rec, s, why);
+        return rc ? fail(rc, why) : 0;
+    });
+}
+
+int hpfw_gpu_combiner_add(hpfw_gpu *h, const uint16_t *hp, const int64_t *offsets, int64_t n_rec)
+{
+    return combiner_add_impl(h, hp, offsets, n_rec, false, nullptr);
+}
+
+int hpfw_gpu_combiner_add_device(hpfw_gpu *h, const uint16_t *d_hp, const int64_t *offsets, int64_t n_rec, void *stream)
+{
+    return combiner_add_impl(h, d_hp, offsets, n_rec, true, (hipStream_t)stream);
+}
+
+int64_t hpfw_gpu_combiner_size(hpfw_gpu *h) { return h && h->combiner ? h->combiner->size() : 0; }
+
+int hpfw_gpu_combiner_get(hpfw_gpu *h, int64_t *val_start, uint32_t *rec, uint32_t *off, int64_t cap)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    std::string why;
+    const int rc = combiner_of(h)->get(val_start, rec, off, cap, why);
+    return rc ? fail(rc, why) : 0;
+}
+
+static int combiner_search_device(hpfw_gpu *h, const uint16_t *d_q, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                  hpfw_combine_result *d_find, int k, hpfw_align_hit *d_align, hipStream_t s)
+{
+    if (!h || !q_off || n_q < 0 || (!d_find && !d_align)) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, s, [&] {
+        std::string why;
+        const int rc = combiner_of(h)->search(d_q, q_off, exclude, n_q, d_find, k, d_align, s, why);
+        return rc ? fail(rc, why) : 0;
+    });
+}
+
+// host buffers: queries in, results out, synchronises
+static int combiner_search_host(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                hpfw_combine_result *find_out, int k, hpfw_align_hit *align_out)
+{
+    if (!h || !q_off || n_q < 0 || (!find_out && !align_out)) return fail(HPFW_E_INVALID, "bad argument");
+    if (align_out && (k < 1 || k > 64)) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    if (find_out)
+        return search_round_trip(q_hp, q_off, n_q, n_q, find_out, [&](const uint16_t *d_q, const int64_t *rel, hpfw_combine_result *d_out) {
+            return combiner_search_device(h, d_q, rel, exclude, n_q, d_out, k, nullptr, nullptr);
+        });
+    return search_round_trip(q_hp, q_off, n_q, n_q * k, align_out, [&](const uint16_t *d_q, const int64_t *rel, hpfw_align_hit *d_out) {
+        return combiner_search_device(h, d_q, rel, exclude, n_q, nullptr, k, d_out, nullptr);
+    });
+}
+
+int hpfw_gpu_combiner_find_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                  hpfw_combine_result *d_out, void *stream)
+{
+    if (!d_out) return fail(HPFW_E_INVALID, "null output");
+    return combiner_search_device(h, d_q_hp, q_off, exclude, n_q, d_out, 0, nullptr, (hipStream_t)stream);
+}
+
+int hpfw_gpu_combiner_find(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                           hpfw_combine_result *out)
+{
+    if (!out) return fail(HPFW_E_INVALID, "null output");
+    return combiner_search_host(h, q_hp, q_off, exclude, n_q, out, 0, nullptr);
+}
+
+int hpfw_gpu_combiner_align_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q,
+                                   int k, hpfw_align_hit *d_out, void *stream)
+{
+    if (!d_out || k < 1 || k > 64) return fail(HPFW_E_INVALID, "null output or k outside 1..64");
+    return combiner_search_device(h, d_q_hp, q_off, exclude, n_q, nullptr, k, d_out, (hipStream_t)stream);
+}
+
+int hpfw_gpu_combiner_align(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_off, const int32_t *exclude, int64_t n_q, int k,
+                            hpfw_align_hit *out)
+{
+    if (!out) return fail(HPFW_E_INVALID, "null output");
+    return combiner_search_host(h, q_hp, q_off, exclude, n_q, nullptr, k, out);
+}
+
+// ---- voting search (AnnStorage semantics, exact neighbours) ------------------------------------
+namespace {
+constexpr int kVoteWin = 64, kVoteNn = 5;
+
+// keys [n_win][5] of the windows of all queries, sorted per window; w_first[q] = first window of query q
+int knn_windows_impl(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, std::vector<uint64_t> &keys,
+                     std::vector<int64_t> &w_first)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    w_first.assign((size_t)n_q + 1, 0);
+    std::vector<int64_t> w_start;
+    for (int64_t q = 0; q < n_q; ++q) {
+        if (q_off[q + 1] < q_off[q]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        const int64_t k = q_off[q + 1] - q_off[q];
+        for (int64_t i = 0; i + kVoteWin <= k; ++i) w_start.push_back(q_off[q] - q_off[0] + i);
+        w_first[(size_t)q + 1] = (int64_t)w_start.size();
+    }
+    const int64_t n_win = (int64_t)w_start.size();
+    keys.assign((size_t)n_win * kVoteNn, ~0ull);
+    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+    int64_t n_max = 0;
+    for (int64_t i = 0; i < n_clips; ++i) n_max = std::max(n_max, h->index.db_off[i + 1] - h->index.db_off[i]);
+    if (n_win == 0 || n_max < kVoteWin) return 0;
+    // one launch: groups of 32 windows along gridDim.y (at most 65535)
+    if (n_win > (int64_t)65535 * 32) return fail(HPFW_E_UNSUPPORTED, "too many query windows in one call (limit 2097120)");
+    return ordered_call(h, nullptr, [&] {
+        if (int rc = upload_db_off(h, nullptr)) return rc;
+        const int64_t total = q_off[n_q] - q_off[0];
+        const int kt_pad = hpfw::hamming_mfma_kt_pad(kVoteWin);
+        const size_t n_groups = (size_t)(n_win + 31) / 32;
+        std::vector<uint64_t> slots((size_t)n_win * 8);
+        HostTrip t;
+        const uint64_t *d_q = t.take<uint64_t>((size_t)total * 8, q_hp + q_off[0]);
+        const int64_t *d_ws = t.take<int64_t>((size_t)n_win * 8, w_start.data());
+        uint64_t *d_slots = t.take<uint64_t>(slots.size() * 8, nullptr, 0xff, slots.data());
+        void *d_qa = t.take<void>(n_groups * kt_pad * 1024);
+        const int rc = t.run(false, [&] { // (the blocking copy of the slots waits for the kernels)
+            hpfw::launch_expand_windows(d_q, d_ws, (int)n_win, kVoteWin, kt_pad, d_qa, nullptr);
+            hpfw::launch_knn_windows(h->index.d_db.as<uint64_t>(), h->index.d_db_off.as<int64_t>(), (int)n_clips, (int)(n_max - kVoteWin + 1), d_qa,
+                                     kt_pad, (int)n_win, kVoteWin, kVoteNn, d_slots, nullptr);
+            return check_launch("knn_windows");
+        });
+        if (rc) return rc;
+        for (int64_t w = 0; w < n_win; ++w) { // the device keeps the 5 smallest keys unsorted
+            uint64_t *s5 = &slots[(size_t)w * 8];
+            std::sort(s5, s5 + kVoteNn);
+            for (int r = 0; r < kVoteNn; ++r) keys[(size_t)w * kVoteNn + r] = s5[r];
+        }
+        return 0;
+    });
+}
+} // namespace
+
+int hpfw_gpu_knn_windows(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, uint64_t *keys,
+                         int64_t keys_cap)
+{
+    if (!h || !q_hp || !q_off || !keys || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    std::vector<uint64_t> k;
+    std::vector<int64_t> wf;
+    int rc = knn_windows_impl(h, q_hp, q_off, n_q, k, wf);
+    if (rc) return rc;
+    if ((int64_t)k.size() > keys_cap) return fail(HPFW_E_INVALID, "keys buffer too small");
+    std::memcpy(keys, k.data(), k.size() * 8);
+    return 0;
+}
+
+int hpfw_gpu_search_votes(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, hpfw_vote *out)
+{
+    if (!h || !q_hp || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    std::vector<uint64_t> keys;
+    std::vector<int64_t> wf;
+    int rc = knn_windows_impl(h, q_hp, q_off, n_q, keys, wf);
+    if (rc) return rc;
+    struct Bucket {
+        int64_t clip, off;
+        float cnt;
+    };
+    std::vector<Bucket> buckets;
+    for (int64_t q = 0; q < n_q; ++q) {
+        hpfw_vote best = {0xffffffffu, 0, 0, 0.0f, 0.0f}; // annoy_storage.h:43
+        buckets.clear();
+        for (int64_t w = wf[(size_t)q]; w < wf[(size_t)q + 1]; ++w) {
+            const int64_t i = w - wf[(size_t)q];
+            for (int r = 0; r < kVoteNn; ++r) {
+                const uint64_t key = keys[(size_t)w * kVoteNn + r];
+                if (key == ~0ull) continue;
+                const uint64_t d = key >> 40;
+                const int64_t pos = (int64_t)(key & (((uint64_t)1 << 40) - 1));
+                const int64_t clip = (int64_t)(std::upper_bound(h->index.db_off.begin(), h->index.db_off.end(), pos) - h->index.db_off.begin()) - 1;
+                const int64_t off = i - (pos - h->index.db_off[(size_t)clip]);
+                size_t s = 0;
+                while (s < buckets.size() && !(buckets[s].clip == clip && buckets[s].off == off)) ++s;
+                if (s == buckets.size()) buckets.push_back({clip, off, 0.0f});
+                buckets[s].cnt = (float)((double)buckets[s].cnt + 1.0 / (double)(float)(d + 1)); // :53
+                if (buckets[s].cnt > best.cnt) {                                                  // :55-59
+                    best.clip = h->index.clip_base + (uint32_t)clip;
+                    best.offset = off;
+                    best.cnt = buckets[s].cnt;
+                }
+            }
+        }
+        out[q] = best;
+    }
+    return 0;
+}
+
+int hpfw_gpu_merge_topk(const hpfw_hit *in, int n_shards, int64_t n_q, int k, hpfw_hit *out)
+{
+    if (!in || !out || n_shards < 1 || n_q < 0 || k < 1) return fail(HPFW_E_INVALID, "bad argument");
+    std::vector<hpfw_hit> all((size_t)n_shards * k);
+    for (int64_t q = 0; q < n_q; ++q) {
+        for (int s = 0; s < n_shards; ++s)
+            for (int t = 0; t < k; ++t) all[(size_t)s * k + t] = in[((size_t)s * n_q + q) * k + t];
+        std::stable_sort(all.begin(), all.end(), [](const hpfw_hit &a, const hpfw_hit &b) {
+            if (a.dist != b.dist) return a.dist < b.dist;
+            return a.clip < b.clip;
+        });
+        for (int t = 0; t < k; ++t) out[(size_t)q * k + t] = all[(size_t)t];
+    }
+    return 0;
+}
+
+} // extern "C"

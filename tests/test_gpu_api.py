@@ -327,7 +327,7 @@ def test_python_liveid_and_notebook_example(wav_set, oracle, filters, tmp_path):
 
 def test_constant_q_classes_side_by_side_or_in_turn(torch_cuda, oracle, filters, monkeypatch):
     """the size classes of the constant-Q stage are launched on forked streams that join the caller's before the next stage
-    (api.hip run_front); HPFW_CQ_SERIAL=1 launches them one after the other: the same hashprints either way, on the null
+    (extract.hip run_front); HPFW_CQ_SERIAL=1 launches them one after the other: the same hashprints either way, on the null
     stream and on a side stream, with another call enqueued right behind on a third stream"""
     torch = torch_cuda
     clips = np.stack([synth.gen_clip(640 + i, 12.0) for i in range(5)])   # (fewer than four clips are never forked)
@@ -355,7 +355,7 @@ def test_constant_q_classes_side_by_side_or_in_turn(torch_cuda, oracle, filters,
 def test_forward_transform_in_chunks_on_streams_in_turn(torch_cuda, oracle, filters, monkeypatch):
     """a large batch goes through the forward transform in chunks of HPFW_FWD_CHUNK clips (default 16) that HPFW_FWD_STREAMS
     streams (default 2: the caller's and a side stream) take in turn, column stage and row stage of a chunk back to back
-    (api.hip run_forward: the column stage's output stays in the Infinity Cache); HPFW_FWD_CHUNK=0 runs one launch per
+    (extract.hip run_forward: the column stage's output stays in the Infinity Cache); HPFW_FWD_CHUNK=0 runs one launch per
     stage over the whole batch.  100 clips = six chunks of 16 and a ragged one of 4: the same hashprints whatever the
     chunking, on the null stream and on a side stream, with another call enqueued right behind on a third stream"""
     torch = torch_cuda
