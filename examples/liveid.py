@@ -1,10 +1,14 @@
 """The reference's notebook (examples/python/liveid.ipynb) on the GPU path:
 
     python examples/liveid.py --index originals/*.wav --search slices/*.wav [--dump dump.pkl]
+    python examples/liveid.py --index originals/*.wav --timeline concert.wav --min-score 10 [--tempos 0.96 1 1.04]
 
 prepare() -> pickle dump of [(hashprint array, name)] (cells 4-5) -> ten best tracks per query by the
 sliding Hamming scan (cell 9, here one batched scan in HBM instead of a process pool over Cython
-loops) -> share of queries whose best track is contained in the query's name (cells 11-12)."""
+loops) -> share of queries whose best track is contained in the query's name (cells 11-12).
+
+--timeline FILE (not in the notebook): the set list of one long recording, 5 s windows every 2.5 s, each segment with the
+score of its best window.  --min-score has no default: pick it from recordings you know."""
 import argparse
 import os
 import pickle
@@ -20,6 +24,10 @@ ap.add_argument("--load", help="pickle written by --dump (cell 6)")
 ap.add_argument("--dump", help="write prepare()'s result as a pickle (cell 5)")
 ap.add_argument("--search", nargs="*", default=[])
 ap.add_argument("--cache", default="")
+ap.add_argument("--timeline", help="a long recording: print the indexed songs it holds, with times")
+ap.add_argument("--min-score", type=float, help="required with --timeline")
+ap.add_argument("--shifts", nargs="*", type=int, help="bin shifts to search as well (--timeline)")
+ap.add_argument("--tempos", nargs="*", type=float, help="tempo factors to search as well (--timeline)")
 args = ap.parse_args()
 
 liveid = LiveSongIdentification(cache=args.cache)
@@ -32,6 +40,12 @@ if args.dump:
     with open(args.dump, "wb") as fp:
         pickle.dump(hashprints, fp)
 liveid.build(hashprints)
+if args.timeline:
+    if args.min_score is None:
+        ap.error("--timeline needs --min-score")
+    for start, end, name, score, offset, shift, tempo in liveid.timeline(args.timeline, args.min_score, shifts=args.shifts or None,
+                                                                         tempos=args.tempos or None):
+        print(f"{start:8.1f} s - {end:8.1f} s  {name}  score {score:.1f}  from {offset:.1f} s  shift {shift}  tempo {tempo:g}")
 ans = liveid.top(args.search, 10)
 for label, top in ans:
     print("Finding ", label)

@@ -20,6 +20,14 @@ VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt
 COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
 ALIGN_DTYPE = np.dtype([("rec", "<u4"), ("peak", "<u4"), ("offset", "<i8")])
 NO_REC = 0xFFFFFFFF
+# the timeline of a long recording: hpfw_dist_stats, hpfw_window_hit, hpfw_segment
+STATS_DTYPE = np.dtype([("sum", "<u8"), ("sum_sq", "<u8"), ("n", "<u4"), ("pad", "<u4")])
+WINDOW_HIT_DTYPE = np.dtype([("clip", "<u4"), ("offset", "<i4"), ("variant", "<i4"), ("pad", "<i4"), ("tempo", "<f8"),
+                             ("score", "<f8")])
+SEGMENT_DTYPE = np.dtype([("clip", "<u4"), ("n_strong", "<i4"), ("first", "<i8"), ("last", "<i8"), ("start", "<i8"),
+                          ("end", "<i8"), ("best_window", "<i8"), ("best_score", "<f8"), ("best_tempo", "<f8"),
+                          ("best_offset", "<i4"), ("best_variant", "<i4"), ("first_offset", "<i4"), ("pad", "<i4")])
+NO_CLIP = 0xFFFFFFFF
 
 KERNEL_KINDS = ("fwd_rows", "fwd_cols", "cq_chirpz", "db", "project_mfma", "delta_pack",
                 "hamming_scan", "topk", "pcm_pairs", "fwd_span")
@@ -54,6 +62,9 @@ EXPORTS = (
     "hpfw_gpu_search_topk_transposed_device", "hpfw_gpu_search_topk_transposed",
     "hpfw_gpu_tempo_columns", "hpfw_gpu_hashprints_from_db_tempo", "hpfw_gpu_extract_tempo_pcm16",
     "hpfw_gpu_extract_tempo_pcm16_host",
+    "hpfw_gpu_search_topk_scored_device", "hpfw_gpu_search_topk_scored", "hpfw_gpu_search_topk_transposed_scored_device",
+    "hpfw_gpu_search_topk_transposed_scored", "hpfw_gpu_hit_score", "hpfw_gpu_window_count", "hpfw_gpu_extract_windows_pcm16",
+    "hpfw_gpu_extract_windows_pcm16_host", "hpfw_gpu_timeline_segments",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -66,6 +77,16 @@ class HandleConfig(ctypes.Structure):
 
 
 COMBINER_CONFIG = (33, 32, 50, 16)      # combiner.h:12: HashPrint<uint16_t, MelSpectrogram<>, 32, 50>
+
+
+class TimelineParams(ctypes.Structure):
+    """hpfw_timeline_params: min_score is required; tol_cols 0, max_gap -1 and min_windows 0 ask for the defaults"""
+    _fields_ = [("min_score", ctypes.c_double), ("hop_cols", ctypes.c_double), ("tol_cols", ctypes.c_double),
+                ("win", ctypes.c_int64), ("hop", ctypes.c_int64), ("max_gap", ctypes.c_int32), ("min_windows", ctypes.c_int32)]
+
+
+class DistStats(ctypes.Structure):
+    _fields_ = [("sum", ctypes.c_uint64), ("sum_sq", ctypes.c_uint64), ("n", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
 class Geometry(ctypes.Structure):
@@ -198,6 +219,15 @@ def lib():
     L.hpfw_gpu_hashprints_from_db_tempo.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp, vp]
     L.hpfw_gpu_extract_tempo_pcm16.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp, vp]
     L.hpfw_gpu_extract_tempo_pcm16_host.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp]
+    L.hpfw_gpu_search_topk_scored_device.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
+    L.hpfw_gpu_search_topk_scored.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    L.hpfw_gpu_search_topk_transposed_scored_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
+    L.hpfw_gpu_search_topk_transposed_scored.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    L.hpfw_gpu_hit_score.argtypes = [u32, i32, ctypes.POINTER(DistStats), ctypes.POINTER(ctypes.c_double)]
+    L.hpfw_gpu_window_count.argtypes = [i64, i64, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_extract_windows_pcm16.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp, vp]
+    L.hpfw_gpu_extract_windows_pcm16_host.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp]
+    L.hpfw_gpu_timeline_segments.argtypes = [vp, i64, ctypes.POINTER(TimelineParams), vp, i64, ctypes.POINTER(i64)]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -263,6 +293,38 @@ def tempo_columns(c, tempos):
     out = ctypes.c_int64()
     check(lib().hpfw_gpu_tempo_columns(int(c), _hp(t), t.size, ctypes.byref(out)))
     return out.value
+
+
+def window_count(n_total, win, hop):
+    """windows [w hop, w hop + win) of a recording of n_total samples (hpfw_gpu_window_count)"""
+    n = ctypes.c_int64()
+    check(lib().hpfw_gpu_window_count(int(n_total), int(win), int(hop), ctypes.byref(n)))
+    return n.value
+
+
+def hit_score(dist, counted, stats):
+    """(mean of the other counted clips' distances - dist) / their standard deviation, from a STATS_DTYPE row
+    (hpfw_gpu_hit_score); NaN when the clip is not counted, n < 3 or the variance is 0"""
+    st = DistStats(int(stats["sum"]), int(stats["sum_sq"]), int(stats["n"]), 0)
+    out = ctypes.c_double()
+    check(lib().hpfw_gpu_hit_score(int(dist), int(bool(counted)), ctypes.byref(st), ctypes.byref(out)))
+    return out.value
+
+
+def timeline_segments(windows, min_score, hop_cols, win, hop, tol_cols=None, max_gap=1, min_windows=1):
+    """WINDOW_HIT_DTYPE [n_w] -> SEGMENT_DTYPE [n_seg] by the rule of include/hpfw_gpu.h (hpfw_gpu_timeline_segments);
+    tol_cols None = the default max(2, 0.08 hop_cols)"""
+    w = np.ascontiguousarray(windows, WINDOW_HIT_DTYPE).ravel()
+    p = TimelineParams(float(min_score), float(hop_cols), 0.0 if tol_cols is None else float(tol_cols), int(win), int(hop),
+                       int(max_gap), int(min_windows))
+    if tol_cols is not None and not tol_cols > 0:
+        raise ValueError("tol_cols must be positive")
+    if max_gap < 0 or min_windows < 1:
+        raise ValueError("max_gap >= 0 and min_windows >= 1")
+    out = np.zeros(max(w.size, 1), SEGMENT_DTYPE)
+    n = ctypes.c_int64()
+    check(lib().hpfw_gpu_timeline_segments(_hp(w) if w.size else None, w.size, ctypes.byref(p), _hp(out), out.size, ctypes.byref(n)))
+    return out[:n.value].copy()
 
 
 def _shift_arg(shifts):
@@ -387,6 +449,36 @@ class Gpu:
         t = np.ascontiguousarray(tempos, np.float32).ravel()
         keep, sp, ns = _shift_arg(shifts)
         check(lib().hpfw_gpu_hashprints_from_db_tempo(self._h, d_db, n_clips, c, _hp(t), t.size, sp, ns, d_hp, stream))
+
+    # ---- windows of one recording ---------------------------------------
+    def _windows_shape(self, n_total, win, hop, tempos, shifts):
+        """(n_w, sets per window, hashprints per set, tempo array, shift tuple) of extract_windows"""
+        t = None if tempos is None else np.ascontiguousarray(tempos, np.float32).ravel()
+        sh = _shift_arg(shifts)
+        n_w = window_count(n_total, win, hop)
+        g = self.geometry(win)
+        nhp = g.n_hp if t is None else tempo_columns(g.c, t) - 99
+        return n_w, (1 if t is None else t.size) * max(sh[2], 1), max(int(nhp), 0), t, sh
+
+    def extract_windows(self, pcm, win, hop, tempos=None, shifts=None):
+        """pcm int16 [n_total] (host), ONE recording of any length -> uint64 [n_w][n_hp] of windows [w hop, w hop + win), or
+        [n_w][V][n_hp_v] with shifts and / or tempos (as extract_transposed / extract_tempo on the windows copied out)"""
+        pcm = np.ascontiguousarray(pcm, np.int16).ravel()
+        n_w, sets, nhp, t, (keep, sp, ns) = self._windows_shape(pcm.size, win, hop, tempos, shifts)
+        hp = np.zeros((n_w, sets, nhp), np.uint64)
+        check(lib().hpfw_gpu_extract_windows_pcm16_host(self._h, _hp(pcm), pcm.size, int(win), int(hop),
+                                                        None if t is None else _hp(t), 0 if t is None else t.size, sp, ns,
+                                                        _hp(hp) if hp.size else None))
+        return hp if (tempos is not None or shifts is not None) else hp[:, 0, :]
+
+    def extract_windows_dev(self, d_pcm, n_total, win, hop, d_hp, tempos=None, shifts=None, stream=0):
+        t = None if tempos is None else np.ascontiguousarray(tempos, np.float32).ravel()
+        keep, sp, ns = _shift_arg(shifts)
+        check(lib().hpfw_gpu_extract_windows_pcm16(self._h, d_pcm, int(n_total), int(win), int(hop),
+                                                   None if t is None else _hp(t), 0 if t is None else t.size, sp, ns, d_hp, stream))
+
+    hit_score = staticmethod(hit_score)
+    timeline_segments = staticmethod(timeline_segments)
 
     # ---- sample-rate conversion to 44.1 kHz (k_resample.hip) --------------------------------
     def resample_dev(self, d_in, n_in, n_clips, rate, d_out, stream=0):
@@ -677,6 +769,45 @@ class Gpu:
         off = np.ascontiguousarray(q_off, np.int64)
         check(lib().hpfw_gpu_search_topk_transposed_device(self._h, d_q, _hp(off), (off.size - 1) // n_shifts, int(n_shifts),
                                                             int(k), d_out, stream))
+
+    # ---- scored search: the same hits and, per query row, the moments of the per-clip distances
+    def search_topk_scored(self, q_hp, q_off, k):
+        """(HIT_DTYPE [n_q][k] as search_topk, STATS_DTYPE [n_q])"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        out = np.zeros((off.size - 1, k), HIT_DTYPE)
+        stats = np.zeros(off.size - 1, STATS_DTYPE)
+        check(lib().hpfw_gpu_search_topk_scored(self._h, _hp(q), _hp(off), off.size - 1, int(k), _hp(out), _hp(stats)))
+        return out, stats
+
+    def search_topk_scored_dev(self, d_q, q_off, k, d_out, d_stats, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_search_topk_scored_device(self._h, d_q, _hp(off), off.size - 1, int(k), d_out, d_stats, stream))
+
+    def search_topk_transposed_scored(self, q_hp, q_off, n_shifts, k):
+        """(SHIFT_HIT_DTYPE [n_q][k] as search_topk_transposed, STATS_DTYPE [n_q][n_shifts]): a hit is scored against
+        stats[q][hit.shift_index]"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        if (off.size - 1) % n_shifts:
+            raise ValueError("q_off must hold n_q * n_shifts + 1 offsets")
+        n_q = (off.size - 1) // n_shifts
+        out = np.zeros((n_q, k), SHIFT_HIT_DTYPE)
+        stats = np.zeros((n_q, n_shifts), STATS_DTYPE)
+        check(lib().hpfw_gpu_search_topk_transposed_scored(self._h, _hp(q), _hp(off), n_q, int(n_shifts), int(k), _hp(out),
+                                                           _hp(stats)))
+        return out, stats
+
+    def search_topk_transposed_scored_dev(self, d_q, q_off, n_shifts, k, d_out, d_stats, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_search_topk_transposed_scored_device(self._h, d_q, _hp(off), (off.size - 1) // n_shifts, int(n_shifts),
+                                                                   int(k), d_out, d_stats, stream))
+
+    def index_offsets(self):
+        """the index's clip offsets int64 [n_clips + 1] (host copy; no hashprint is downloaded)"""
+        off = np.zeros(self.index_size() + 1, np.int64)
+        check(lib().hpfw_gpu_index_get(self._h, _hp(off), None, 0))
+        return off
 
     def search_topk_dev(self, d_q, q_off, k, d_out, stream=0):
         off = np.ascontiguousarray(q_off, np.int64)

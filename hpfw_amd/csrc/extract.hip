@@ -661,6 +661,85 @@ int hpfw_gpu_extract_tempo_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n
                              });
 }
 
+// ---- windows of one recording ----
+// the checks of the variant the arguments select (none, shifts, tempos with or without shifts), as that variant's own entry
+// points make them, then the windows; *per_window: hashprints per window
+static int check_windows_call(hpfw_gpu *h, int64_t n_total, int64_t win, int64_t hop, const float *tempos, int n_tempos,
+                              const int32_t *shifts, int n_shifts, int64_t *n_w, int64_t *per_window)
+{
+    int rc;
+    hpfw::TempoList tl;
+    if (tempos || n_tempos) {
+        if ((rc = check_tempo_call(h, tempos, n_tempos, shifts, n_shifts, &tl))) return rc;
+    } else if (shifts || n_shifts) {
+        if ((rc = check_transposed(h, shifts, n_shifts))) return rc;
+    } else {
+        if (!h) return fail(HPFW_E_INVALID, "null handle");
+        if ((rc = check_filters(h))) return rc;
+    }
+    if ((rc = hpfw_gpu_window_count(n_total, win, hop, n_w))) return rc;
+    hpfw_geometry g;
+    if ((rc = hpfw_gpu_geometry(h, win, &g))) return rc;
+    int64_t nhp = g.n_hp;
+    if (tempos) {
+        nhp = tempo_common_columns(g.c, tl) - (hpfw::kCtx - 1) - hpfw::kLag;
+        if (nhp < 1) return fail(HPFW_E_UNSUPPORTED, "clip too short to yield a hashprint at the slowest tempo");
+    }
+    *per_window = (int64_t)(tempos ? n_tempos : 1) * std::max(n_shifts, 1) * nhp;
+    return 0;
+}
+
+int hpfw_gpu_extract_windows_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_total, int64_t win, int64_t hop, const float *tempos,
+                                   int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *d_hp, void *stream)
+{
+    int64_t n_w, per_window;
+    int rc = check_windows_call(h, n_total, win, hop, tempos, n_tempos, shifts, n_shifts, &n_w, &per_window);
+    if (rc) return rc;
+    if (n_w == 0) return 0;
+    if (!d_pcm || !d_hp) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    DevPlan *dp;
+    if ((rc = get_plan(h, win, &dp))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        // a pass of windows gathered into clips back to back, then the pass through the extraction of clips
+        const int nbmax = pass_clips(h, dp, n_w);
+        if ((rc = ensure(h->d_windows, (size_t)nbmax * win * 2, h))) return rc;
+        int16_t *clips = h->d_windows.as<int16_t>();
+        for (int64_t w0 = 0; w0 < n_w; w0 += nbmax) {
+            const int64_t nb = std::min<int64_t>(nbmax, n_w - w0);
+            hpfw::launch_gather_windows(d_pcm + w0 * hop, hop, win, nb, clips, s);
+            if ((rc = check_launch("gather_windows"))) return rc;
+            uint64_t *dst = d_hp + w0 * per_window;
+            rc = tempos ? extract_tempo_pcm16(h, clips, win, nb, tempos, n_tempos, shifts, n_shifts, dst, s)
+                        : extract_pcm16(h, clips, win, nb, shifts, n_shifts, dst, s);
+            if (rc) return rc;
+        }
+        return 0;
+    });
+}
+
+// host buffers: the recording uploaded once, the hashprints of all windows downloaded, synchronises
+int hpfw_gpu_extract_windows_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_total, int64_t win, int64_t hop, const float *tempos,
+                                        int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp)
+{
+    int64_t n_w, per_window;
+    int rc = check_windows_call(h, n_total, win, hop, tempos, n_tempos, shifts, n_shifts, &n_w, &per_window);
+    if (rc) return rc;
+    if (n_w == 0) return 0;
+    if (!pcm || !hp) return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t used = (n_w - 1) * hop + win; // (the samples behind the last window are not needed)
+    if ((rc = ensure(h->stage_pcm[0], (size_t)used * 2))) return rc;
+    if ((rc = ensure(h->stage_hp, (size_t)n_w * per_window * 8))) return rc;
+    HIP_TRY(hipMemcpy(h->stage_pcm[0].get(), pcm, (size_t)used * 2, hipMemcpyHostToDevice));
+    if ((rc = hpfw_gpu_extract_windows_pcm16(h, h->stage_pcm[0].as<int16_t>(), used, win, hop, tempos, n_tempos, shifts, n_shifts,
+                                             h->stage_hp.as<uint64_t>(), nullptr)))
+        return rc;
+    HIP_TRY(hipMemcpy(hp, h->stage_hp.get(), (size_t)n_w * per_window * 8, hipMemcpyDeviceToHost)); // (waits for the null stream)
+    return 0;
+}
+
 #if defined(HPFW_ROWS_SNAP) || defined(HPFW_ROWS_STAMPS)
 int hpfw_gpu_debug_set_rows_snap(void *d_snap)
 {

@@ -218,6 +218,8 @@ struct hpfw_gpu {
     // queries at another tempo (k_tempo.hip): the time-scaled dB spectrograms of a sub-batch of
     // (clip, tempo) pairs (kTempoBudget, or one pair where a pair is larger)
     DevBuf d_tempo;
+    // windows of one recording (k_windows.hip): the windows of a pass gathered into clips back to back
+    DevBuf d_windows;
 };
 
 // a workspace of at least `need` bytes (its contents are not kept when it grows)

@@ -351,6 +351,12 @@ void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, u
 // per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
 // (dist, shift index), then the k best by (dist, clip)
 void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);
+// scored search (k_stats.hip): d_stats [n_q] (hpfw_dist_stats, zeroed by the caller) += per query row the
+// moments n, sum d, sum d^2 of d = best >> 32 over the clips with db_off[c + 1] - db_off[c] >= q_off[q + 1] - q_off[q] >= 1
+void launch_dist_stats(const uint64_t *d_best, const int64_t *d_db_off, const int64_t *d_q_off, int n_q, int n_clips, void *d_stats,
+                       hipStream_t s);
+// windows of one recording (k_windows.hip): window i of d_src is samples [i hop, i hop + win) -> d_dst [n_w][win]
+void launch_gather_windows(const int16_t *d_src, int64_t hop, int64_t win, int64_t n_w, int16_t *d_dst, hipStream_t s);
 
 // sample-rate conversion to 44.1 kHz (k_resample.hip)
 constexpr int kRsRateOut = 44100, kRsRateMin = 8000, kRsRateMax = 192000;

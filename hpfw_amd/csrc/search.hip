@@ -5,8 +5,10 @@
 namespace {
 // the host round trip of a search: the hashprints (elements Q) of query sets [0, n_sets) uploaded, their offsets rebased
 // to 0, device(d_q, rel, d_out) queued on the null stream, the n_out hits it wrote downloaded
+// (scored searches: the n_stats rows of moments the call wrote downloaded as well, device(d_q, rel, d_out, d_stats))
 template <class Q, class Hit, class Device>
-int search_round_trip(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, Device device)
+int search_round_trip_scored(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, int64_t n_stats,
+                             hpfw_dist_stats *stats, Device device)
 {
     const int64_t total = q_off[n_sets] - q_off[0];
     if (total < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
@@ -16,7 +18,15 @@ int search_round_trip(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64
     HostTrip t;
     const Q *d_q = t.take<Q>((size_t)std::max<int64_t>(total, 1) * sizeof(Q), total ? q_hp + q_off[0] : nullptr);
     Hit *d_out = t.take<Hit>((size_t)n_out * sizeof(Hit), nullptr, -1, out);
-    return t.run(true, [&] { return device(d_q, rel.data(), d_out); });
+    hpfw_dist_stats *d_stats = n_stats ? t.take<hpfw_dist_stats>((size_t)n_stats * sizeof(hpfw_dist_stats), nullptr, -1, stats) : nullptr;
+    return t.run(true, [&] { return device(d_q, rel.data(), d_out, d_stats); });
+}
+
+template <class Q, class Hit, class Device>
+int search_round_trip(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, Device device)
+{
+    return search_round_trip_scored(q_hp, q_off, n_sets, n_out, out, 0, nullptr,
+                                    [&](const Q *d_q, const int64_t *rel, Hit *d_out, hpfw_dist_stats *) { return device(d_q, rel, d_out); });
 }
 
 // the index's offsets to the device when they changed since the last upload: on s, which the host then waits for
@@ -112,17 +122,19 @@ int hpfw_gpu_index_set_clip_base(hpfw_gpu *h, uint32_t base)
     return 0;
 }
 
-int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
-                                hpfw_hit *d_out, void *stream)
+// the top-k search of n_q queries; d_stats: NULL, or [n_q] rows that receive the moments of the per-clip best distances
+// (k_stats.hip: one more reader of the table the scan wrote)
+static int search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *d_out,
+                              hpfw_dist_stats *d_stats, hipStream_t s)
 {
     if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
     return ordered_call(h, s, [&] {
         if (n_q == 0) return 0;
         if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
         const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
         int rc;
+        if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_q * sizeof(hpfw_dist_stats), s));
         if (n_clips == 0) { // nothing indexed: every slot is "none"
             hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->index.clip_base, d_out, s);
             return check_launch("topk");
@@ -134,6 +146,9 @@ int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64
             k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
         }
         if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+        // d <= 64 k_max: the sum of squares stays below 2^64 while n_clips k_max^2 4096 does
+        if (d_stats && (unsigned __int128)n_clips * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
+            return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
         if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
         HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
         // queries are processed in groups so the (query, clip) table stays below 1 GiB
@@ -211,36 +226,69 @@ int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64
                 }
             }
             if ((rc = check_launch("topk"))) return rc;
+            if (d_stats) {
+                Timed t(h, K_TOPK, s);
+                hpfw::launch_dist_stats(a.best, a.db_off, a.q_off, ng, (int)n_clips, d_stats + g0, s);
+            }
+            if (d_stats && (rc = check_launch("dist_stats"))) return rc;
         }
         return 0;
     });
 }
 
-int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k,
-                         hpfw_hit *out)
+int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
+                                hpfw_hit *d_out, void *stream)
+{
+    return search_topk_device(h, d_q_hp, q_off, n_q, k, d_out, nullptr, (hipStream_t)stream);
+}
+
+int hpfw_gpu_search_topk_scored_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *d_out,
+                                       hpfw_dist_stats *d_stats, void *stream)
+{
+    if (!d_stats) return fail(HPFW_E_INVALID, "null stats");
+    return search_topk_device(h, d_q_hp, q_off, n_q, k, d_out, d_stats, (hipStream_t)stream);
+}
+
+// host buffers: stats NULL (plain) or [n_q]
+static int search_topk_host(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out,
+                            hpfw_dist_stats *stats)
 {
     if (!h || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
-    return search_round_trip(q_hp, q_off, n_q, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_hit *d_out) {
-        return hpfw_gpu_search_topk_device(h, d_q, rel, n_q, k, d_out, nullptr);
-    });
+    return search_round_trip_scored(q_hp, q_off, n_q, n_q * k, out, stats ? n_q : 0, stats,
+                                    [&](const uint64_t *d_q, const int64_t *rel, hpfw_hit *d_out, hpfw_dist_stats *d_stats) {
+                                        return search_topk_device(h, d_q, rel, n_q, k, d_out, d_stats, nullptr);
+                                    });
 }
 
-int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
-                                           hpfw_shift_hit *d_out, void *stream)
+int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k,
+                         hpfw_hit *out)
+{
+    return search_topk_host(h, q_hp, q_off, n_q, k, out, nullptr);
+}
+
+int hpfw_gpu_search_topk_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out,
+                                hpfw_dist_stats *stats)
+{
+    if (!stats) return fail(HPFW_E_INVALID, "null stats");
+    return search_topk_host(h, q_hp, q_off, n_q, k, out, stats);
+}
+
+// d_stats: NULL, or [n_q][n_shifts] rows, one per query set
+static int search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                         hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats, hipStream_t s)
 {
     if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts)
         return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
     return ordered_call(h, s, [&] {
         if (n_q == 0) return 0;
         int rc;
         // the per-shift lists: n_q * n_shifts queries in one pass of the existing scan, then one workgroup per query merges them
         if ((rc = ensure(h->index.d_shift_hits, (size_t)n_q * n_shifts * k * sizeof(hpfw_hit)))) return rc;
-        if ((rc = hpfw_gpu_search_topk_device(h, d_q_hp, q_off, n_q * n_shifts, k, h->index.d_shift_hits.as<hpfw_hit>(), s))) return rc;
+        if ((rc = search_topk_device(h, d_q_hp, q_off, n_q * n_shifts, k, h->index.d_shift_hits.as<hpfw_hit>(), d_stats, s))) return rc;
         {
             Timed t(h, K_TOPK, s);
             hpfw::launch_topk_merge_shifts(h->index.d_shift_hits.get(), (int)n_q, n_shifts, k, d_out, s);
@@ -249,16 +297,43 @@ int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, 
     });
 }
 
-int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
-                                    hpfw_shift_hit *out)
+int hpfw_gpu_search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                           hpfw_shift_hit *d_out, void *stream)
+{
+    return search_topk_transposed_device(h, d_q_hp, q_off, n_q, n_shifts, k, d_out, nullptr, (hipStream_t)stream);
+}
+
+int hpfw_gpu_search_topk_transposed_scored_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
+                                                  int k, hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats, void *stream)
+{
+    if (!d_stats) return fail(HPFW_E_INVALID, "null stats");
+    return search_topk_transposed_device(h, d_q_hp, q_off, n_q, n_shifts, k, d_out, d_stats, (hipStream_t)stream);
+}
+
+static int search_topk_transposed_host(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                       hpfw_shift_hit *out, hpfw_dist_stats *stats)
 {
     if (!h || !q_off || !out || n_q < 0 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts) return fail(HPFW_E_INVALID, "bad argument");
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
-    return search_round_trip(q_hp, q_off, n_q * n_shifts, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_shift_hit *d_out) {
-        return hpfw_gpu_search_topk_transposed_device(h, d_q, rel, n_q, n_shifts, k, d_out, nullptr);
-    });
+    return search_round_trip_scored(q_hp, q_off, n_q * n_shifts, n_q * k, out, stats ? n_q * n_shifts : 0, stats,
+                                    [&](const uint64_t *d_q, const int64_t *rel, hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats) {
+                                        return search_topk_transposed_device(h, d_q, rel, n_q, n_shifts, k, d_out, d_stats, nullptr);
+                                    });
+}
+
+int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                    hpfw_shift_hit *out)
+{
+    return search_topk_transposed_host(h, q_hp, q_off, n_q, n_shifts, k, out, nullptr);
+}
+
+int hpfw_gpu_search_topk_transposed_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                           hpfw_shift_hit *out, hpfw_dist_stats *stats)
+{
+    if (!stats) return fail(HPFW_E_INVALID, "null stats");
+    return search_topk_transposed_host(h, q_hp, q_off, n_q, n_shifts, k, out, stats);
 }
 
 // ---- AudioCombiner: exact-hash index + offset votes (k_combiner.hip) --------------------------------

@@ -5,6 +5,7 @@
 index(files)  = storage.build(collector.prepare(files))           live_song_id.h:31-33
 search(files) = per query: calc_hashprint -> find -> report       live_song_id.h:35-54
 top(files, k) = the notebook's "ten best tracks" per query        liveid.ipynb cell 9
+timeline(file) = the songs of one long recording, window by window (not in the reference)
 """
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -113,6 +114,71 @@ class LiveSongIdentification:
                 out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"])) + decode(h)
                                          for h in row if h["clip"] != 0xFFFFFFFF])
         return out
+
+    def timeline(self, filename: str, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
+                 shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
+                 tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, windows: bool = False):
+        """the set list of one long recording: windows of window_s seconds every hop_s seconds, each
+        searched for its best clip and scored by how far that clip stands out from the others (hpfw_gpu_hit_score);
+        consecutive windows with score >= min_score that name the same clip at consistent offsets form a segment
+        (hpfw_gpu_timeline_segments; tol_cols None = max(2, 0.08 hop in columns)).
+        Returns [(start_s, end_s, name, score, offset_s, shift, tempo)]: the segment's extent in the recording, the score,
+        shift and tempo of its best window, and where in the indexed recording its first window starts.  windows=True:
+        (segments, [(clip index or None, name or None, distance, offset, score, shift, tempo) per window]).
+        An unreadable file or one shorter than a window gives []; every other failure raises."""
+        win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
+        if shifts is not None:
+            shifts = _lib.check_shifts(shifts)
+        if tempos is not None:
+            tempos = _lib.check_tempos(tempos, 0 if shifts is None else len(shifts))
+        n_s = len(shifts) if shifts else 1
+        n_sets = (len(tempos) if tempos else 1) * n_s
+        variants = shifts is not None or tempos is not None
+        extractor = self.collector.gpu()                  # the collector's filters
+        if variants and extractor.get_projection() != 1:
+            raise _lib.HpfwError("timeline with shifts or tempos needs projection mode 1 (fixed point)", _lib.E_INVALID)
+        empty = ([], []) if windows else []
+        _lib.window_count(0, win, hop)                     # (a bad window or hop raises whatever the file holds)
+        try:
+            x = _lib.read_wav_44k(self._gpu, filename, self._resample)
+        except _lib.HpfwError as e:
+            if e.status == _lib.E_IO:
+                return empty
+            raise
+        if _lib.window_count(x.size, win, hop) == 0:
+            return empty
+        hp = extractor.extract_windows(x, win, hop, tempos, shifts)
+        n_w, k_q = hp.shape[0], hp.shape[-1]
+        off = np.arange(n_w * n_sets + 1, dtype=np.int64) * k_q
+        if variants:
+            hits, stats = self._gpu.search_topk_transposed_scored(hp, off, n_sets, 1)
+        else:
+            hits, stats = self._gpu.search_topk_scored(hp, off, 1)
+        clip_len = np.diff(self._gpu.index_offsets())
+        rows = np.zeros(n_w, _lib.WINDOW_HIT_DTYPE)
+        per_window = []
+        for w in range(n_w):
+            h = hits[w, 0]
+            v = int(h["shift_index"]) if variants else 0
+            j, i = divmod(max(v, 0), n_s)                  # variant v = j max(S, 1) + i
+            shift, tempo = (shifts[i] if shifts else 0), (tempos[j] if tempos else 1.0)
+            if h["clip"] == _lib.NO_CLIP:
+                rows[w] = (_lib.NO_CLIP, 0, 0, 0, 1.0, np.nan)
+                per_window.append((None, None, None, None, float("nan"), 0, 1.0))
+                continue
+            clip = int(h["clip"])
+            score = _lib.hit_score(int(h["dist"]), clip_len[clip] >= k_q, stats[w, v] if variants else stats[w])
+            rows[w] = (clip, int(h["offset"]), v, 0, tempo, score)
+            per_window.append((clip, self.names[clip], int(h["dist"]), int(h["offset"]), score, shift, tempo))
+        m = self._gpu.geometry(win).m
+        col_s = 3.0 * win / m / 44100.0                    # one index column in seconds
+        segs = _lib.timeline_segments(rows, min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
+        out = []
+        for sg in segs:
+            bw = per_window[int(sg["best_window"])]
+            out.append((int(sg["start"]) / 44100.0, int(sg["end"]) / 44100.0, self.names[int(sg["clip"])], float(sg["best_score"]),
+                        int(sg["first_offset"]) * col_s, bw[5], bw[6]))
+        return (out, per_window) if windows else out
 
     def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None,
                tempos: Optional[Sequence[float]] = None):

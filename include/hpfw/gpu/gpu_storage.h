@@ -130,6 +130,9 @@ public:
     }
 
     size_t size() const { return names_.size(); }
+    /// the handle that holds the index and the names of its clips in index order (hpfw::timeline, timeline.h)
+    hpfw_gpu *handle() const { return h_; }
+    const std::vector<std::string> &names() const { return names_; }
 
     /// AnnStorage<Collector>::find (reference annoy_storage.h:41-63) with exact nearest neighbours in
     /// place of the Annoy forest: per query position the 5 nearest 64-hashprint windows vote

@@ -1,0 +1,115 @@
+// timeline.h -- the set list of one long recording: windows of the recording hashed on the extractor's
+// handle `h` (which holds the index's filters), each searched in a GpuStorage for its best clip and scored by how far that
+// clip stands out from the others (hpfw_gpu_hit_score), and the windows that name one clip at consistent offsets joined into
+// segments (hpfw_gpu_timeline_segments).  With tempos and / or shifts every window is searched under every variant, as
+// tempo.h / transposed.h describe them; projection mode 1 then.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <limits>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../hpfw_gpu.h"
+
+namespace hpfw {
+
+struct TimelineOptions {
+    double min_score = 0;          ///< REQUIRED, > 0: there is no default
+    int64_t win = 220500;          ///< window and hop in samples at 44.1 kHz; win must be a supported clip length
+    int64_t hop = 110250;
+    std::vector<float> tempos;     ///< empty: the recording's own tempo only
+    std::vector<int32_t> shifts;   ///< empty: the recording's own key only
+    double tol_cols = 0;           ///< 0: the default max(2, 0.08 hop in columns)
+    int max_gap = 1, min_windows = 1;
+};
+
+struct TimelineSegment {
+    std::string filename;          ///< the clip's name in the storage
+    uint32_t clip;
+    double start_s, end_s;         ///< the segment in the recording
+    double score;                  ///< of its best window, with that window's shift and tempo
+    double offset_s;               ///< where in the indexed recording the first window starts
+    int32_t shift;
+    float tempo;
+    hpfw_segment raw;
+};
+
+struct Timeline {
+    std::vector<hpfw_window_hit> windows; ///< the best hit of every window
+    std::vector<TimelineSegment> segments;
+};
+
+/// `path`: a 44.1 kHz PCM16 WAV file (hpfw_gpu_wav_read_pcm16).  A recording shorter than one window has no window and no
+/// segment; throws std::runtime_error with the library's message on failure.
+template <typename Storage>
+Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, const TimelineOptions &opt)
+{
+    auto fail = [](const char *what) { throw std::runtime_error(std::string("hpfw::timeline: ") + what + ": " + hpfw_gpu_last_error()); };
+    int64_t n = 0, n_w = 0;
+    if (hpfw_gpu_window_count(0, opt.win, opt.hop, &n_w) != 0) fail("windows");
+    if (hpfw_gpu_wav_read_pcm16(path.c_str(), nullptr, 0, &n) != 0) fail(path.c_str());
+    std::vector<int16_t> pcm((size_t)std::max<int64_t>(n, 1));
+    if (hpfw_gpu_wav_read_pcm16(path.c_str(), pcm.data(), n, &n) != 0) fail(path.c_str());
+    if (hpfw_gpu_window_count(n, opt.win, opt.hop, &n_w) != 0) fail("windows");
+    Timeline out;
+    if (n_w == 0) return out;
+    hpfw_geometry g;
+    if (hpfw_gpu_geometry(h, opt.win, &g) != 0) fail("geometry");
+    int64_t nhp = g.n_hp;
+    if (!opt.tempos.empty()) {
+        int64_t ct = 0;
+        if (hpfw_gpu_tempo_columns(g.c, opt.tempos.data(), (int)opt.tempos.size(), &ct) != 0) fail("tempos");
+        nhp = std::max<int64_t>(ct - 99, 0);
+    }
+    const int n_s = (int)std::max<size_t>(opt.shifts.size(), 1);
+    const int sets = (int)std::max<size_t>(opt.tempos.size(), 1) * n_s;
+    const bool variants = !opt.tempos.empty() || !opt.shifts.empty();
+    std::vector<uint64_t> hp((size_t)(n_w * sets * nhp));
+    if (hpfw_gpu_extract_windows_pcm16_host(h, pcm.data(), n, opt.win, opt.hop, opt.tempos.empty() ? nullptr : opt.tempos.data(),
+                                            (int)opt.tempos.size(), opt.shifts.empty() ? nullptr : opt.shifts.data(), (int)opt.shifts.size(),
+                                            hp.data()) != 0)
+        fail("extraction");
+    std::vector<int64_t> q_off((size_t)(n_w * sets) + 1);
+    for (size_t i = 0; i < q_off.size(); ++i) q_off[i] = (int64_t)i * nhp;
+    std::vector<hpfw_dist_stats> stats((size_t)(n_w * sets));
+    std::vector<hpfw_shift_hit> hits((size_t)n_w);
+    if (variants) {
+        if (hpfw_gpu_search_topk_transposed_scored(storage.handle(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data()) != 0)
+            fail("search");
+    } else {
+        std::vector<hpfw_hit> plain((size_t)n_w);
+        if (hpfw_gpu_search_topk_scored(storage.handle(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data()) != 0) fail("search");
+        for (int64_t w = 0; w < n_w; ++w) hits[(size_t)w] = {plain[(size_t)w].dist, plain[(size_t)w].clip, plain[(size_t)w].offset, 0};
+    }
+    std::vector<int64_t> db_off(storage.names().size() + 1, 0);
+    if (hpfw_gpu_index_get(storage.handle(), db_off.data(), nullptr, 0) != 0) fail("index");
+    out.windows.resize((size_t)n_w);
+    for (int64_t w = 0; w < n_w; ++w) {
+        const hpfw_shift_hit &hit = hits[(size_t)w];
+        hpfw_window_hit &x = out.windows[(size_t)w];
+        x = {hit.clip, hit.offset, std::max(hit.shift_index, 0), 0, 1.0, std::numeric_limits<double>::quiet_NaN()};
+        if (hit.clip == 0xffffffffu) continue;
+        if (!opt.tempos.empty()) x.tempo = opt.tempos[(size_t)(x.variant / n_s)];
+        const int counted = db_off[hit.clip + 1] - db_off[hit.clip] >= nhp;
+        if (hpfw_gpu_hit_score(hit.dist, counted, &stats[(size_t)(w * sets + x.variant)], &x.score) != 0) fail("score");
+    }
+    const hpfw_timeline_params p{opt.min_score, (double)opt.hop * (double)g.m / (3.0 * (double)opt.win), opt.tol_cols, opt.win, opt.hop,
+                                 opt.max_gap, opt.min_windows};
+    std::vector<hpfw_segment> segs((size_t)n_w);
+    int64_t n_seg = 0;
+    if (hpfw_gpu_timeline_segments(out.windows.data(), n_w, &p, segs.data(), n_w, &n_seg) != 0) fail("segments");
+    const double col_s = 3.0 * (double)opt.win / (double)g.m / 44100.0; // one index column in seconds
+    for (int64_t i = 0; i < n_seg; ++i) {
+        const hpfw_segment &s = segs[(size_t)i];
+        out.segments.push_back({storage.names()[s.clip], s.clip, (double)s.start / 44100.0, (double)s.end / 44100.0, s.best_score,
+                                s.first_offset * col_s, opt.shifts.empty() ? 0 : opt.shifts[(size_t)(s.best_variant % n_s)],
+                                (float)s.best_tempo, s});
+    }
+    return out;
+}
+
+} // namespace hpfw

@@ -426,6 +426,99 @@ int hpfw_gpu_extract_tempo_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp,
                            void *stream);
 
+/* ---- timeline of a long recording: scored search, windows of one recording, segments.
+ *
+ * Scored search.  The scan leaves, per query and clip, the clip's best distance d_c.  The scored entry points return the
+ * hits of their unscored counterparts, bit for bit, and per query row the exact integer moments of d_c over the COUNTED
+ * clips: those with n_c >= k_q >= 1 hashprints (k_q the query's length).  A shorter clip is compared over n_c < k_q
+ * hashprints (storage.h:37-39), so its distance is on another scale and it is left out.  n, sum d_c and sum d_c^2 do not
+ * depend on the order of summation: they are bitwise deterministic.  d_c <= 64 * 16000 < 2^20, so sum_sq is exact while
+ * n_clips * k_max^2 * 4096 < 2^64 (k_max the longest query of the call); beyond that the call is refused with
+ * HPFW_E_UNSUPPORTED before anything runs.  An empty index or an empty query gives n = 0.  The moments are additive over
+ * the shards of a sharded index. */
+typedef struct {
+    uint64_t sum, sum_sq; /* sum of d_c and of d_c^2 over the counted clips */
+    uint32_t n, pad;      /* number of counted clips                       */
+} hpfw_dist_stats;
+/* as hpfw_gpu_search_topk(_device); stats [n_q] (device pointer in the device form) */
+int hpfw_gpu_search_topk_scored_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
+                                       hpfw_hit *d_out, hpfw_dist_stats *d_stats, void *stream);
+int hpfw_gpu_search_topk_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out,
+                                hpfw_dist_stats *stats);
+/* as hpfw_gpu_search_topk_transposed(_device); stats [n_q][n_shifts], one row per variant set.  A merged hit's distance is its
+ * clip's best distance in the winning set, so the hit is scored against stats[q][shift_index]. */
+int hpfw_gpu_search_topk_transposed_scored_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                                  int n_shifts, int k, hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats,
+                                                  void *stream);
+int hpfw_gpu_search_topk_transposed_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
+                                           int k, hpfw_shift_hit *out, hpfw_dist_stats *stats);
+/* Host only: how far a hit of distance `dist` stands out from the other counted clips of its row.  counted: whether the
+ * hit's clip is counted (the caller knows the query's and the clip's lengths).  With n' = n - 1 the others have mean
+ * m = (sum - d) / n' and variance var = (n' (sum_sq - d^2) - (sum - d)^2) / n'^2 (numerators in exact 128-bit integers,
+ * converted to double once); *score = (m - d) / sqrt(var).  *score is NaN, with status OK, when counted == 0, n < 3 or
+ * var == 0.  Moments no set of distances can have (d > sum, d^2 > sum_sq, a negative variance) are HPFW_E_INVALID. */
+int hpfw_gpu_hit_score(uint32_t dist, int counted, const hpfw_dist_stats *s, double *score);
+
+/* Windows of ONE recording of n_total samples: window w is samples [w hop, w hop + win).  Host only:
+ * *n_w = (n_total - win) / hop + 1, 0 when n_total < win.  1 <= hop <= win, win a supported clip length
+ * (hpfw_gpu_supported_length(win) == win), n_total >= 0; anything else is HPFW_E_INVALID. */
+int hpfw_gpu_window_count(int64_t n_total, int64_t win, int64_t hop, int64_t *n_w);
+/* Hashprints of every window.  The recording may be of any length: only win has to be a clip length.  tempos == NULL and
+ * shifts == NULL (n_tempos = n_shifts = 0): d_hp [n_w][n_hp], what hpfw_gpu_extract_pcm16 gives for the windows copied out
+ * back to back, bit for bit, in either projection mode.  shifts only: d_hp [n_w][n_shifts][n_hp] as
+ * hpfw_gpu_extract_transposed_pcm16; tempos (with or without shifts): d_hp [n_w][V][n_hp_t] as
+ * hpfw_gpu_extract_tempo_pcm16; the argument checks and the requirement of projection mode 1 are theirs.  The windows are
+ * gathered on the device, a pass of clips (hpfw_gpu_set_batch) at a time, and each pass goes through the existing
+ * extraction.  The host form uploads the recording once. */
+int hpfw_gpu_extract_windows_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_total, int64_t win, int64_t hop,
+                                   const float *tempos, int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *d_hp,
+                                   void *stream);
+int hpfw_gpu_extract_windows_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_total, int64_t win, int64_t hop,
+                                        const float *tempos, int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp);
+
+/* Segments: a pure function of the per-window best hits, no device and no handle.
+ * Window w sits at t_w = w * hop_cols index columns, hop_cols = hop * M / (3 * win) in double with M from
+ * hpfw_gpu_geometry(win) (one column is 3 win / M samples).
+ * Rule.  A window is STRONG when it has a hit (clip != 0xffffffff) and score >= min_score; NaN is never strong.  The windows
+ * are scanned left to right.  The first strong window opens a segment.  With l the open segment's last accepted window, a
+ * later strong window w CONTINUES it when it names the same clip, w - l - 1 <= max_gap, and
+ *     fabs((o_w - o_l) - rho_l * (t_w - t_l)) <= tol_cols * (w - l)
+ * (o: offset, rho: tempo; evaluated in double exactly as written).  A strong window that does not continue the open segment
+ * closes it and opens a new one; a segment also closes once more than max_gap windows have passed since l without a
+ * continuation.  A closed segment is kept when it holds at least min_windows strong windows.  Segments come out in order
+ * of their first window. */
+typedef struct {
+    uint32_t clip;   /* the window's best clip; 0xffffffff = none                            */
+    int32_t offset;  /* its offset in index columns                                          */
+    int32_t variant; /* the variant (shift_index) that found it; 0 without variants          */
+    int32_t pad;
+    double tempo;    /* the variant's tempo factor rho; 1 without tempos                     */
+    double score;    /* hpfw_gpu_hit_score of the hit                                        */
+} hpfw_window_hit;
+typedef struct {
+    double min_score;    /* REQUIRED: > 0 (<= 0 or NaN is HPFW_E_INVALID); there is no default            */
+    double hop_cols;     /* > 0, finite                                                                   */
+    double tol_cols;     /* > 0; 0 = the default max(2, 0.08 hop_cols); negative or NaN is invalid        */
+    int64_t win, hop;    /* samples, 1 <= hop <= win: a segment's start = first * hop, end = last * hop + win */
+    int32_t max_gap;     /* >= 0; -1 = the default 1                                                      */
+    int32_t min_windows; /* >= 1; 0 = the default 1                                                       */
+} hpfw_timeline_params;
+typedef struct {
+    uint32_t clip;
+    int32_t n_strong;     /* strong windows accepted                                 */
+    int64_t first, last;  /* first and last accepted window                          */
+    int64_t start, end;   /* samples                                                 */
+    int64_t best_window;  /* the best-scoring accepted window, the earliest on ties  */
+    double best_score;    /* its score, offset, variant and tempo                    */
+    double best_tempo;
+    int32_t best_offset, best_variant;
+    int32_t first_offset; /* the offset at the first window                          */
+    int32_t pad;
+} hpfw_segment;
+/* *n_seg = the number of segments kept; the first min(*n_seg, cap) are written (out may be NULL when cap = 0) */
+int hpfw_gpu_timeline_segments(const hpfw_window_hit *w, int64_t n_w, const hpfw_timeline_params *p, hpfw_segment *out,
+                               int64_t cap, int64_t *n_seg);
+
 /* ---- table preparation ahead of time.  A corpus of real recordings brings a new clip length with almost every file,
  * and the host half of a length's tables (constant-Q windows and chirp spectra, twiddles) costs more than the
  * extraction of the file: 3 ms for 30 s, 15 ms for 3 minutes.  hpfw_gpu_prepare_length builds that half on the
