@@ -8,8 +8,10 @@
 //                conjugates).  int16 samples times 23-bit fixed-point twiddles: an exact integer sum, so it runs on
 //                v_mfma_i32_32x32x32_i8 as six digit products (samples: two bytes; twiddles: three balanced base-256
 //                digits) -- a dense [2 hq x n1] . [n1 x n2] contraction per clip that needs no summation order.  The
-//                epilogue rounds the integers ONCE to f32.
-//   fwd_rows2  : one workgroup per row q1: times the twiddles between the stages on the way in (formed from every fourth
+//                epilogue rounds the integers ONCE to f32.  Even n1 <= 224 (the 30 s clip: n1 = 210) evaluate the same sums
+//                split by the parity of k1 (fwd_cols_q4_kernel): rows q1 <= n1 / 4 on v_mfma_i32_16x16x64_i8, row
+//                n1 / 2 - q1 from the same two half sums -- half the products, the same integers, the same z bit for bit.
+//   fwd_rows2 : one workgroup per row q1: times the twiddles between the stages on the way in (formed from every fourth
 //                one, 13 KB per row instead of 50), FFT_n2 in LDS (fft_rows.h), of which only the outputs q2 that hold consumed
 //                bins (a tenth) are stored, for the row itself and, conjugated, for its mirror n1 - q1.
 // Nothing is re-laid-out on the way: the first kernel reads the PCM where the caller put it, the second writes the
@@ -26,9 +28,11 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 // ---- column stage ---------------------------------------------------------------------------------------------
-// Two kernels: n1 <= 224 (clips up to 32 s at n2 = 6300: all k1 of a column fit the registers of a lane) runs
-// fwd_cols_q3_kernel further down; longer clips run the kernel of this section, which stages the samples in LDS chunk
-// by chunk of 224 k1.  Digits, accumulators, image layout and epilogue are common.
+// Three kernels: n1 <= 224 (clips up to 32 s at n2 = 6300: all k1 of a column fit the registers of a lane) runs
+// fwd_cols_q4_kernel (even n1: the sum split by the parity of k1) or fwd_cols_q3_kernel (odd n1) further down; longer
+// clips run the kernel of this section, which stages the samples in LDS chunk by chunk of 224 k1.  Digits, accumulators,
+// image layout and epilogue are common to this kernel and fwd_cols_q3_kernel; the sample digits, the correction and the
+// layout of z to all three.
 //
 // One workgroup = 4 waves = 128 columns k2 of one clip x up to 7 row tiles (224 rows (Re, Im interleaved) = 112 q1);
 // a wave owns 32 columns.  K = k1 in chunks of 224 samples (7 matrix-instruction steps): the samples of the chunk sit
@@ -549,6 +553,297 @@ __global__ __launch_bounds__(64 * kCq3Waves, 3) void fwd_cols_q3_kernel(ColsQArg
 #endif
 }
 
+// ---- column stage, even n1 <= 224: the sum split by the parity of k1 -------------------------------------------
+// With n1 = 2 h the fixed-point twiddles obey wq[m + h] = -wq[m] and wq[n1 - m] = conj(wq[m]) exactly (checked on the
+// integers when the plan is built: plan.cpp, which also proves the line below), so with
+//   E[q1] = sum_m wq[(q1 2m) mod n1] x[2m],   O[q1] = sum_m wq[(q1 (2m + 1)) mod n1] x[2m + 1]
+//   G[q1] = E[q1] + O[q1],   G[h - q1] = conj(E[q1] - O[q1])
+// the rows q1 = 0 .. h / 2 give all of 0 .. h: half the digit products and half the twiddle digits for the SAME exact
+// integers, hence the same z bit for bit.  Tiles of 16 rows (8 q1, Re and Im interleaved) on v_mfma_i32_16x16x64_i8, a
+// wave still 32 columns = two column tiles; K = the samples of one parity in steps of 64 (h <= 112: two steps).  The
+// samples of both parities stay in registers (64 per lane); E is accumulated first and kept as its two paired sums,
+// then O; the four accumulators of a parity and column tile are 16 registers, so the kernel stays within 168 and
+// three workgroups share a CU as above.  Per parity |acc_0 + 2^8 acc_1| <= 112 2^14 (1 + 2 2^8) < 2^30 and
+// |acc_2 + 2^8 acc_3| likewise, so E + O and E - O stay below 2^31 in int32 -- for n1 <= 224 and no further.
+constexpr int kCq4Steps = 2;                                              // steps of 64 samples per parity
+constexpr int kCq4ABytes = 2 * kCq4Steps * 3 * 1024;                      // the digits of a row tile, both parities: 12 288
+constexpr int kCq4ScratchBytes = 2 * 4 * 32 * 16;                         // per wave: [plane][unit][slot][16 bytes]
+constexpr int cq4_lds_bytes(int waves) { return 2 * kCq4ABytes + waves * kCq4ScratchBytes + kCq3CorrRows * 8; }
+
+// slot of column c (0 .. 31) inside a unit of the wave's scratch: the operand reads (16 lanes = columns c3..c0 of one
+// column tile c4) meet 16 different slots mod 16, the staging writes (8 groups of four columns, c1 c0 fixed) 8 different mod 8
+__device__ __forceinline__ int cq4_slot(int c)
+{
+    return ((c >> 2) & 1) | (((c >> 3) & 1) << 1) | ((((c >> 4) ^ (c >> 1)) & 1) << 2) | ((c & 1) << 3) | (((c >> 1) & 1) << 4);
+}
+
+__device__ __forceinline__ void cq4_store_pair(unsigned char *sc, int c, int rq, unsigned r0, unsigned r1, unsigned r2, unsigned r3)
+{
+    const unsigned x01 = __builtin_amdgcn_perm(r1, r0, 0x05010400u), x23 = __builtin_amdgcn_perm(r3, r2, 0x05010400u);
+    const unsigned y01 = __builtin_amdgcn_perm(r1, r0, 0x07030602u), y23 = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
+    const int a0 = (rq >> 2) * 512 + cq4_slot(c) * 16 + 4 * (rq & 3), a1 = (rq >> 2) * 512 + cq4_slot(c + 1) * 16 + 4 * (rq & 3);
+    *reinterpret_cast<unsigned *>(sc + a0) = __builtin_amdgcn_perm(x23, x01, 0x05040100u);        // lo plane
+    *reinterpret_cast<unsigned *>(sc + 2048 + a0) = __builtin_amdgcn_perm(x23, x01, 0x07060302u); // hi plane
+    *reinterpret_cast<unsigned *>(sc + a1) = __builtin_amdgcn_perm(y23, y01, 0x05040100u);
+    *reinterpret_cast<unsigned *>(sc + 2048 + a1) = __builtin_amdgcn_perm(y23, y01, 0x07060302u);
+}
+
+// the samples of the wave's 32 columns into x[2 parity + step][column tile][plane]: as cq3_load_samples, but sample m
+// of parity p is PCM row 2 m + p, 64 of them (a lane: 4 columns x 2 x 4 consecutive m) pass the scratch at a time, and a
+// lane reads back the 16 m of unit lane >> 4 for its column of either column tile -- the B operand of the 16x16x64 instruction
+template <int LOADW, class F>
+__device__ __forceinline__ void cq4_load_samples(const ColsQArgs &a, const int16_t *__restrict__ clip_pcm, int cw0,
+                                                 unsigned char *sc, int lane, v4i (&x)[2 * kCq4Steps][2][2], F issued)
+{
+    const int cg = lane & 7, quad = lane >> 3;
+    const int row_last = a.n1 - 1, last = a.n2 - 1;
+    const int gc = cw0 + 4 * cg;
+    const char *base = reinterpret_cast<const char *>(clip_pcm);
+    const unsigned pitch = 2u * (unsigned)a.n2;
+    unsigned cb[4];
+    if (LOADW == 4) {
+        cb[0] = 2u * (unsigned)(gc + 3 <= last ? gc : last - 3);
+    } else if (LOADW == 2) {
+        cb[0] = 2u * (unsigned)(gc + 1 <= last ? gc : last - 1);
+        cb[1] = 2u * (unsigned)(gc + 3 <= last ? gc + 2 : last - 1);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cb[e] = 2u * (unsigned)(gc + e <= last ? gc + e : last);
+    }
+    // LOADW = 4: every load is issued before the first value is used; the narrower loads of odd shapes go 64 samples at a time
+    constexpr int kItems = 2 * kCq4Steps;
+    constexpr int kBatch = LOADW == 4 ? kItems : 1;
+    const int rd0 = (lane >> 4) * 512 + cq4_slot(lane & 15) * 16, rd1 = (lane >> 4) * 512 + cq4_slot(16 + (lane & 15)) * 16;
+#pragma unroll
+    for (int i0 = 0; i0 < kItems; i0 += kBatch) {
+    unsigned r[kBatch][8][2];
+#pragma unroll
+    for (int ib = 0; ib < kBatch; ++ib) {
+        const int par = (i0 + ib) / kCq4Steps, s = (i0 + ib) % kCq4Steps;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            int row = 2 * (64 * s + 32 * (i >> 2) + 4 * quad + (i & 3)) + par;
+            if (row > row_last) row = row_last;      // samples past n1 meet zero twiddle digits: any valid address
+            const unsigned ro = (unsigned)row * pitch;
+            if (LOADW == 4) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(base + (ro + cb[0]));
+                r[ib][i][0] = v.x;
+                r[ib][i][1] = v.y;
+            } else if (LOADW == 2) {
+                r[ib][i][0] = *reinterpret_cast<const unsigned *>(base + (ro + cb[0]));
+                r[ib][i][1] = *reinterpret_cast<const unsigned *>(base + (ro + cb[1]));
+            } else {
+                r[ib][i][0] = (unsigned)*reinterpret_cast<const unsigned short *>(base + (ro + cb[0])) |
+                              ((unsigned)*reinterpret_cast<const unsigned short *>(base + (ro + cb[1])) << 16);
+                r[ib][i][1] = (unsigned)*reinterpret_cast<const unsigned short *>(base + (ro + cb[2])) |
+                              ((unsigned)*reinterpret_cast<const unsigned short *>(base + (ro + cb[3])) << 16);
+            }
+        }
+    }
+    if (i0 == 0) issued();                         // what the caller wants in flight behind the first loads
+#pragma unroll
+    for (int ib = 0; ib < kBatch; ++ib) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            r[ib][i][0] ^= 0x00800080u;              // lo = (x & 255) - 128: the low bytes' top bits flipped
+            r[ib][i][1] ^= 0x00800080u;
+        }
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            cq4_store_pair(sc, 4 * cg, 8 * hf + quad, r[ib][4 * hf][0], r[ib][4 * hf + 1][0], r[ib][4 * hf + 2][0], r[ib][4 * hf + 3][0]);
+            cq4_store_pair(sc, 4 * cg + 2, 8 * hf + quad, r[ib][4 * hf][1], r[ib][4 * hf + 1][1], r[ib][4 * hf + 2][1], r[ib][4 * hf + 3][1]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own writes, in order before its reads
+        x[i0 + ib][0][0] = *reinterpret_cast<const v4i *>(sc + rd0);
+        x[i0 + ib][0][1] = *reinterpret_cast<const v4i *>(sc + 2048 + rd0);
+        x[i0 + ib][1][0] = *reinterpret_cast<const v4i *>(sc + rd1);
+        x[i0 + ib][1][1] = *reinterpret_cast<const v4i *>(sc + 2048 + rd1);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // read before the next 64 samples' writes land
+    }
+    }
+}
+
+// 4 x 4 transposition inside every quad of lanes (two exchange steps on the data-parallel-primitive path): lane 4 i + j
+// gives q[e] = row e of its column and ends up with row j of the columns of lanes 4 i .. 4 i + 3
+__device__ __forceinline__ void cq4_quad_transpose(float (&q)[4], int lane)
+{
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {     // lanes differing in bit 0 exchange registers differing in bit 0
+        const float send = (lane & 1) ? q[2 * pr] : q[2 * pr + 1];
+        const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));
+        if (lane & 1) q[2 * pr] = got; else q[2 * pr + 1] = got;
+    }
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {     // bit 1
+        const float send = (lane & 2) ? q[pr] : q[pr + 2];
+        const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, true));
+        if (lane & 2) q[pr] = got; else q[pr + 2] = got;
+    }
+}
+
+template <int LOADW, int kCq4Waves>                  // a wave = 32 columns
+__global__ __launch_bounds__(64 * kCq4Waves, 3) void fwd_cols_q4_kernel(ColsQArgs a, const int16_t *__restrict__ pcm, int64_t clip_samples,
+                                                                    float *__restrict__ z)
+{
+    constexpr int kCq4Cols = 32 * kCq4Waves;
+    unsigned char *abytes = smem_raw;                                       // [2 buffers][2 parities x ks2 steps][3 digits][64 lanes][16 bytes]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned char *sc = smem_raw + 2 * kCq4ABytes + wave * kCq4ScratchBytes;
+    // (clip, column block) pairs in contiguous runs per XCD, the column block fastest: as fwd_cols_q3_kernel
+    const int ncb = (a.n2 + kCq4Cols - 1) / kCq4Cols;
+    const unsigned per_xcd = (gridDim.x + 7) / 8;
+    const unsigned t = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (t >= (unsigned)(a.n_clips * ncb)) return;
+    const int cb = t % ncb, clip = t / ncb;
+    const int col0 = cb * kCq4Cols;
+    const int16_t *clip_pcm = pcm + (int64_t)clip * clip_samples;
+    const v4i *image = static_cast<const v4i *>(a.image2);
+    const int ks2 = a.ks2, pieces = 3 * 2 * ks2;     // <= 2 steps per parity: every sample of the columns is in registers
+    // the twiddle digits of row tile mt into buffer `buf`: at most 12 pieces of 1 KB, every wave its share
+    auto issue_a = [&](int mt, int buf) {
+        const v4i *src = image + (int64_t)mt * pieces * 64 + lane;
+#pragma unroll
+        for (int e = 0; e < (2 * kCq4Steps * 3 + kCq4Waves - 1) / kCq4Waves; ++e) {
+            const int p = wave + kCq4Waves * e;
+            if (p < pieces)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + p * 64),
+                                                 (__attribute__((address_space(3))) void *)(abytes + buf * kCq4ABytes + p * 1024),
+                                                 16, 0, 0);
+        }
+    };
+#ifdef HPFW_COLS_STAMPS
+    long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long tprev = __builtin_amdgcn_s_memtime();
+    auto stamp = [&](int k) {
+        const long long t = __builtin_amdgcn_s_memtime();
+        st[k] += t - tprev;
+        tprev = t;
+    };
+#endif
+    v4i x[2 * kCq4Steps][2][2];
+    // the samples first (they come from HBM), the first tile's digits (from L2) behind them
+    cq4_load_samples<LOADW>(a, clip_pcm, col0 + wave * 32, sc, lane, x, [&] { issue_a(0, 0); });
+    CQ_STAMP(0);
+    // D[tile row = output row][tile column = column]: a lane holds column 16 ct + (lane & 15) of the wave's 32 for either
+    // column tile ct, its register r tile row 4 u + r (u = lane >> 4), that is Re (r even) or Im (r odd) of q1 = 8 mt + 2 u + (r >> 1).
+    const int u = lane >> 4, nl = lane & 15;
+    const int hh = a.n1 >> 1, q1_last = hh >> 1;     // n1 = 2 hh; the rows q1 <= q1_last are computed, hh - q1 follow from them
+    const bool vec4 = (a.n2 & 3) == 0;               // columns then come in whole fours
+    static_assert(32 * kCq4Waves == kZBlock, "a workgroup's columns are one block of z");
+    float *zblk = z + (int64_t)clip * a.zclip + (int64_t)cb * 2 * a.hq * kZBlock + wave * 32;
+    const int rows_live = 2 * a.hq;
+    double *corr_lds = reinterpret_cast<double *>(smem_raw + 2 * kCq4ABytes + kCq4Waves * kCq4ScratchBytes);
+    for (int i = tid; i < kCq3CorrRows; i += 64 * kCq4Waves) corr_lds[i] = a.corr[i < rows_live ? i : rows_live - 1];
+    for (int mt = 0; mt < a.mt2; ++mt) {
+        // the tile's digits have landed for everybody and everybody is done with the other buffer: the FULL wait of
+        // fwd_cols_q3_kernel, for its reason
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        CQ_STAMP(1);
+        const v4i *wb = reinterpret_cast<const v4i *>(abytes + (mt & 1) * kCq4ABytes) + lane;
+        const v4i zero = v4i{0, 0, 0, 0};
+        v4i lo[2][2], hi[2][2];                      // [parity][column tile]: acc_0 + 2^8 acc_1, acc_2 + 2^8 acc_3
+#pragma unroll
+        for (int par = 0; par < 2; ++par) {
+            v4i acc[4][2];
+#pragma unroll
+            for (int s = 0; s < kCq4Steps; ++s) {
+                if (s == 0 || s < ks2) {
+                    // sample digit i (0 lo, 1 hi) times twiddle digit j goes to accumulator i + j
+                    const v4i *w = wb + (par * ks2 + s) * 3 * 64;
+                    const v4i w0 = w[0], w1 = w[64], w2 = w[128];
+                    const v4i(&xs)[2][2] = x[par * kCq4Steps + s];
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        acc[0][ct] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, xs[ct][0], s == 0 ? zero : acc[0][ct], 0, 0, 0);
+                        acc[1][ct] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, xs[ct][0], s == 0 ? zero : acc[1][ct], 0, 0, 0);
+                        acc[2][ct] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w2, xs[ct][0], s == 0 ? zero : acc[2][ct], 0, 0, 0);
+                        acc[3][ct] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w2, xs[ct][1], s == 0 ? zero : acc[3][ct], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        acc[1][ct] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, xs[ct][1], acc[1][ct], 0, 0, 0);
+                        acc[2][ct] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, xs[ct][1], acc[2][ct], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                lo[par][ct] = acc[0][ct] + (acc[1][ct] << 8);
+                hi[par][ct] = acc[2][ct] + (acc[3][ct] << 8);
+            }
+        }
+        CQ_STAMP(2);
+        // the next tile's digits, on their way under the conversion and the stores
+        if (mt + 1 < a.mt2) issue_a(mt + 1, (mt + 1) & 1);
+        asm volatile("" ::: "memory");
+        CQ_STAMP(4);
+        // G = 2^16 hi + lo + corr, exact in double, rounded once; row q1 from E + O, row hh - q1 from E - O with the Im row
+        // as the INTEGER O - E (a negated float zero would be stored as -0.0)
+        const int q1a = 8 * mt + 2 * u;              // registers 0, 1: q1a; 2, 3: q1a + 1
+        const double *cp = corr_lds + 16 * mt + 4 * u;
+        const double *cm0 = corr_lds + 2 * max(hh - q1a, 0), *cm1 = corr_lds + 2 * max(hh - q1a - 1, 0);
+        float gp[2][4], gm[2][4];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int el = lo[0][ct][r], eh = hi[0][ct][r], ol = lo[1][ct][r], oh = hi[1][ct][r];
+                gp[ct][r] = (float)(__builtin_fma((double)(eh + oh), 65536.0, (double)(el + ol)) + cp[r]);
+                const int ml = (r & 1) ? ol - el : el - ol, mh = (r & 1) ? oh - eh : eh - oh;
+                gm[ct][r] = (float)(__builtin_fma((double)mh, 65536.0, (double)ml) + (r < 2 ? cm0 : cm1)[r & 1]);
+            }
+        if (vec4) {
+            // per column tile the 4 x 4 exchange gives lane 4 i + j tile row 4 u + j, columns 4 i .. 4 i + 3 of the tile's
+            // sixteen; the halves of the wave then swap column tile 1 of the lower against column tile 0 of the upper, so
+            // that a store instruction covers eight rows x all 32 columns = eight whole 128-byte lines, 16 bytes per lane
+            const int j = lane & 3, col = 16 * (u >> 1) + (nl & ~3);
+            const bool c_ok = col0 + wave * 32 + col < a.n2;
+#pragma unroll
+            for (int sgn = 0; sgn < 2; ++sgn) {
+                float(&g)[2][4] = sgn ? gm : gp;
+                cq4_quad_transpose(g[0], lane);
+                cq4_quad_transpose(g[1], lane);
+                float sa[4], sb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, g[0][e]), __builtin_bit_cast(unsigned, g[1][e]), false, false);
+                    sa[e] = __builtin_bit_cast(float, (unsigned)sw[0]);
+                    sb[e] = __builtin_bit_cast(float, (unsigned)sw[1]);
+                }
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+                    const int tr = 8 * half + 4 * (u & 1) + j, q1 = 8 * mt + (tr >> 1);
+                    const int row = sgn ? 2 * (hh - q1) + (tr & 1) : 16 * mt + tr;
+                    // (hh even: row hh / 2 is reached by both formulas and written by the first)
+                    const bool live = q1 <= q1_last && (!sgn || 2 * q1 < hh);
+                    const float(&s4)[4] = half ? sb : sa;
+                    if (c_ok && live) *reinterpret_cast<float4 *>(zblk + row * kZBlock + col) = float4{s4[0], s4[1], s4[2], s4[3]};
+                }
+            }
+        } else {
+            const int c = col0 + wave * 32 + nl;
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int q1 = q1a + (r >> 1);
+                    if (c + 16 * ct < a.n2 && q1 <= q1_last) {
+                        zblk[(2 * q1 + (r & 1)) * kZBlock + 16 * ct + nl] = gp[ct][r];
+                        if (2 * q1 < hh) zblk[(2 * (hh - q1) + (r & 1)) * kZBlock + 16 * ct + nl] = gm[ct][r];
+                    }
+                }
+        }
+        CQ_STAMP(6);
+    }
+#ifdef HPFW_COLS_STAMPS
+    if (a.stamps && tid == 0) {
+        long long *o = a.stamps + (int64_t)blockIdx.x * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = st[k];
+    }
+#endif
+}
+
 #ifdef HPFW_COLS_STAMPS
 long long *g_cols_stamps = nullptr;
 extern "C" long long *hpfw_debug_cols_stamps() { return g_cols_stamps; }
@@ -595,6 +890,11 @@ static void launch_cols_q_t(ColsQArgs a, const int16_t *d_pcm, int64_t clip_samp
         // itself 2.63 -> 2.9 ms, the step within 0.6 %: DESIGN.md section 9)
         constexpr int kWaves = 4;
         const int ncb = (a.n2 + 32 * kWaves - 1) / (32 * kWaves);
+        if (a.image2 && !(a.variant & 2)) {        // even n1: the sum split by the parity of k1
+            hipLaunchKernelGGL((fwd_cols_q4_kernel<LOADW, kWaves>), dim3(8 * ((grid.x * ncb + 7) / 8)), dim3(64 * kWaves), cq4_lds_bytes(kWaves), s,
+                               a, d_pcm, clip_samples, d_z);
+            return;
+        }
         hipLaunchKernelGGL((fwd_cols_q3_kernel<LOADW, kWaves>), dim3(8 * ((grid.x * ncb + 7) / 8)), dim3(64 * kWaves), cq3_lds_bytes(kWaves), s,
                            a, d_pcm, clip_samples, d_z);
         return;

@@ -48,7 +48,10 @@ struct ColsQArgs {
     const double *corr;  // [2 hq]: what the samples' +128 digit offset adds to every element of a row
     long long *stamps;   // diagnostic builds (-DHPFW_COLS_STAMPS) only: per workgroup 8 cycle sums
     int n_clips;         // set by the launch of the register-resident kernel: its grid is one-dimensional
-    int variant;         // HPFW_COLS_VARIANT at handle creation (tests, diagnosis): 1 = the LDS-staged kernel for every n1
+    int variant;         // HPFW_COLS_VARIANT at handle creation (tests, diagnosis), bits: 1 = the LDS-staged kernel for every n1;
+                         // 2 = the un-split register-resident kernel for even n1 too
+    int mt2, ks2;        // even n1 <= 224, split by the parity of k1: 16-row tiles of the rows q1 <= n1 / 4; 64-sample steps per parity
+    const void *image2;  // ... and the twiddle digits as the 16x16x64 A operand [mt2][2 ks2][3][64][16 bytes] (null: not split)
     long long zclip;     // floats of z per clip: z is [clip][block of kZBlock columns][row 2 q1 + (Re: 0, Im: 1)][kZBlock] (round 4: a
                          // workgroup's stores of a tile are then ONE contiguous 16 KB instead of 32 pieces 25 KB apart)
 };

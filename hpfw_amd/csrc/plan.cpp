@@ -463,6 +463,46 @@ bool build_plan(int64_t n, HostPlan &p, std::string &why, bool geometry_only, bo
                             p.cols_image[((((size_t)mt * p.cols_ks + ks) * 3 + i) * 64 + l) * 16 + e] = (int8_t)d[i];
                     }
         });
+        // Even n1 = 2 h that fit the register-resident kernel: the sum over k1 splits by parity,
+        //   E[q1] = sum_m wq[(q1 2m) mod n1] x[2m],  O[q1] = sum_m wq[(q1 (2m + 1)) mod n1] x[2m + 1],  G[q1] = E[q1] + O[q1],
+        // and row h - q1 needs no twiddles of its own.  With a = (q1 k1) mod n1:
+        //   k1 = 2m:     (h - q1) k1 = h 2m - a     = -a      (mod n1)  ->  wq[n1 - a] =  conj(wq[a])      (wq[n1 - m] == conj(wq[m]))
+        //   k1 = 2m + 1: (h - q1) k1 = h 2m + h - a = h - a   (mod n1)  ->  wq[h - a]  = -wq[n1 - a] = -conj(wq[a])  (wq[m + h] == -wq[m])
+        // so G[h - q1] = conj(E[q1] - O[q1]): rows 0 .. h come from q1 = 0 .. h / 2 with half the products.  Both identities
+        // are checked on the INTEGER table below (S2's octant reduction gives them; were a rounding ever to break one, the
+        // un-split image above stays in use), and they hold digit for digit of the samples: the x above may be the digit sum
+        // 256 hi + lo, and what the +128 offset adds to row h - q1 is cols_corr of that row as it is -- the table's entry is
+        // 128 sum_k1 wq[((h - q1) k1) mod n1] whichever way the rest of the row is formed.
+        if (n1 % 2 == 0 && p.cols_ks <= 7) {
+            const int64_t h = n1 / 2;
+            bool symmetric = true;
+            for (int64_t m = 0; m < n1 && symmetric; ++m) {
+                const int32_t *w = &p.wq[(size_t)(2 * m)], *wh = &p.wq[(size_t)(2 * ((m + h) % n1))], *wc = &p.wq[(size_t)(2 * ((n1 - m) % n1))];
+                symmetric = wh[0] == -w[0] && wh[1] == -w[1] && wc[0] == w[0] && wc[1] == -w[1];
+            }
+            if (symmetric) {
+                const int64_t nq1 = h / 2 + 1;
+                p.cols2_mt = (int)((2 * nq1 + 15) / 16);
+                p.cols2_ks = (int)((h + 63) / 64);
+                // image [tile][step = parity * cols2_ks + s][digit][lane][16]: byte e of lane l = digit of
+                // W[row = 16 tile + (l & 15)][k1 = 2 m + parity], m = 64 s + 16 (l >> 4) + e; zero beyond q1 = h / 2 and m = h - 1
+                p.cols2_image.assign((size_t)p.cols2_mt * 2 * p.cols2_ks * 3 * 1024, 0);
+                parallel_rows(p.cols2_mt, [&](int64_t mt) {
+                    for (int64_t st = 0; st < 2 * p.cols2_ks; ++st)
+                        for (int l = 0; l < 64; ++l)
+                            for (int e = 0; e < 16; ++e) {
+                                const int64_t row = 16 * mt + (l & 15), q1 = row >> 1, par = st / p.cols2_ks;
+                                const int64_t m = 64 * (st % p.cols2_ks) + 16 * (l >> 4) + e, k1 = 2 * m + par;
+                                if (q1 >= nq1 || m >= h) continue;
+                                const int w = p.wq[(size_t)(2 * ((q1 * k1) % n1) + (row & 1))];
+                                const int d0 = ((w + 128) & 255) - 128, w1 = (w - d0) >> 8, d1 = ((w1 + 128) & 255) - 128, d2 = (w1 - d1) >> 8;
+                                const int d[3] = {d0, d1, d2};
+                                for (int i = 0; i < 3; ++i)
+                                    p.cols2_image[((((size_t)mt * 2 * p.cols2_ks + st) * 3 + i) * 64 + l) * 16 + e] = (int8_t)d[i];
+                            }
+                });
+            }
+        }
         const int64_t nq = (n2 + 3) / 4;
         p.ts_seed.resize((size_t)(hq * nq));
         p.ts_step.resize((size_t)(hq * 4));

@@ -45,6 +45,9 @@ struct HostPlan {
     std::vector<int32_t> wq;                // [n1][2]: rint(2^22 T_n1[m])
     std::vector<int8_t> cols_image;         // digits of wq as the matrix instruction's A operand (k_forward.hip)
     std::vector<double> cols_corr;          // [2 hq]: 128 sum_k1 wq[(q1 k1) mod n1] (Re, Im): the samples' +128 digit offset
+    // even n1 <= 224 whose wq has both symmetries (plan.cpp): the same sums split by the parity of k1, rows q1 <= n1 / 4 only
+    int cols2_mt = 0, cols2_ks = 0;         // 16-row tiles of those rows; 64-sample steps per parity
+    std::vector<int8_t> cols2_image;        // digits of wq as the A operand of the 16x16x64 instruction (empty: not split)
     // the twiddles between the stages, T_N[q1 k2] 2^-37, are formed by the row stage from every fourth one:
     // ts[q1][4 m + e] = ts_seed[q1][m] (e = 0), ts_seed[q1][m] * ts_step[q1][e] (S1; e = 1, 2, 3)
     std::vector<HostCf> ts_seed;            // [hq][ceil(n2 / 4)]: T_N[4 q1 m] 2^-37

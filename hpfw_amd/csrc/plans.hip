@@ -342,6 +342,12 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
         const int8_t *img = nullptr;
         if ((rc = upload(p.cols_image, &img, dp.get()))) return rc;
         ca.image = img;
+        if (!p.cols2_image.empty()) {
+            ca.mt2 = p.cols2_mt;
+            ca.ks2 = p.cols2_ks;
+            if ((rc = upload(p.cols2_image, &img, dp.get()))) return rc;
+            ca.image2 = img;
+        }
         if ((rc = upload(p.cols_corr, &ca.corr, dp.get()))) return rc;
         if ((rc = upload(p.ts_seed, reinterpret_cast<const hpfw::HostCf **>(&dp->rows_out.seed), dp.get()))) return rc;
         if ((rc = upload(p.ts_step, reinterpret_cast<const hpfw::HostCf **>(&dp->rows_out.step), dp.get()))) return rc;
@@ -428,6 +434,7 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
         std::vector<hpfw::HostCf>().swap(hp.tw_n1);
         std::vector<hpfw::HostCf>().swap(hp.ts_seed);
         std::vector<int8_t>().swap(hp.cols_image);
+        std::vector<int8_t>().swap(hp.cols2_image);
         std::vector<hpfw::HostCf>().swap(hp.g);
         for (hpfw::BluesteinClass &bc : hp.classes) {
             std::vector<hpfw::HostCf>().swap(bc.tw);
