@@ -51,7 +51,7 @@ EXPORTS = (
     "hpfw_gpu_cfg_set_filters", "hpfw_gpu_cfg_hashprints", "hpfw_gpu_mel_hashprints_pcm16_host",
     "hpfw_gpu_cfg_cov_reset", "hpfw_gpu_cfg_cov_accumulate", "hpfw_gpu_cfg_cov_get", "hpfw_gpu_cfg_learn_filters",
     "hpfw_gpu_set_kernel_timing", "hpfw_gpu_get_kernel_timing", "hpfw_gpu_plan_checksum",
-    "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
+    "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_plan_cols_tables", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
     "hpfw_gpu_hashprints_from_db", "hpfw_gpu_stage_delta_q",
     "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
     "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
@@ -184,6 +184,7 @@ def lib():
     L.hpfw_gpu_get_kernel_timing.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i32)]
     L.hpfw_gpu_plan_checksum.argtypes = [i64, vp]
     L.hpfw_gpu_plan_checksum_ex.argtypes = [i64, i32, u32, vp]
+    L.hpfw_gpu_plan_cols_tables.argtypes = [i64, vp, vp, vp, vp, vp]
     L.hpfw_gpu_chirpz_table.argtypes = [vp, i64, i32, vp, i64, vp]
     L.hpfw_gpu_debug_workspace.argtypes = [vp, i32, vp, vp]
     L.hpfw_gpu_prepare_length.argtypes = [vp, i64]
@@ -921,3 +922,21 @@ def plan_checksum(n_samples, conventions=0):
     if rc != 0:
         raise HpfwError(f"unsupported clip length {n_samples}")
     return out
+
+
+def plan_cols_tables(n_samples):
+    """the column stage's host tables of a 7-smooth clip length (hpfw_gpu_plan_cols_tables): a dict of n1, n2, hq, the
+    tile and step counts, wq int32 [n1][2], corr float64 [hq][2], image int8 [mt][ks][3][64][16] and image2 int8
+    [mt2][2 ks2][3][64][16] (None when the length does not take the parity-split kernel)"""
+    d = np.zeros(9, np.int32)
+    if lib().hpfw_gpu_plan_cols_tables(int(n_samples), _hp(d), None, None, None, None) != 0:
+        raise HpfwError(f"no column-stage tables for clip length {n_samples}")
+    n1, n2, hq, mt, ks, mt2, ks2, split = (int(v) for v in d[:8])
+    wq, corr = np.zeros((n1, 2), np.int32), np.zeros((hq, 2), np.float64)
+    image = np.zeros((mt, ks, 3, 64, 16), np.int8)
+    image2 = np.zeros((mt2, 2 * ks2, 3, 64, 16), np.int8) if split else None
+    check_rc = lib().hpfw_gpu_plan_cols_tables(int(n_samples), _hp(d), _hp(wq), _hp(corr), _hp(image),
+                                               _hp(image2) if split else None)
+    if check_rc != 0:
+        raise HpfwError(f"no column-stage tables for clip length {n_samples}")
+    return dict(n1=n1, n2=n2, hq=hq, mt=mt, ks=ks, mt2=mt2, ks2=ks2, wq=wq, corr=corr, image=image, image2=image2)

@@ -805,3 +805,21 @@ extern "C" int hpfw_gpu_plan_checksum_ex(int64_t n_samples, int force_bluestein,
     out8[7] = hv;
     return 0;
 }
+
+// host-only: the column stage's tables of a 7-smooth length, copied out for the CPU-side checks of the matrix-core
+// kernels' integer arithmetic.  dims9 = {n1, n2, hq, cols_mt, cols_ks, cols2_mt, cols2_ks, split image present, 0};
+// every other pointer may be null (sizes first, then the tables): wq [2 n1], corr [2 hq], image
+// [cols_mt cols_ks 3072], image2 [cols2_mt 2 cols2_ks 3072]
+extern "C" int hpfw_gpu_plan_cols_tables(int64_t n_samples, int32_t *dims9, int32_t *wq, double *corr, int8_t *image, int8_t *image2)
+{
+    hpfw::HostPlan p;
+    std::string why;
+    if (!dims9 || !hpfw::build_plan(n_samples, p, why, false, false, 0, false) || p.bluestein) return -2;
+    const int32_t d[9] = {p.n1, p.n2, p.hq, p.cols_mt, p.cols_ks, p.cols2_mt, p.cols2_ks, p.cols2_image.empty() ? 0 : 1, 0};
+    std::copy(d, d + 9, dims9);
+    if (wq) std::copy(p.wq.begin(), p.wq.end(), wq);
+    if (corr) std::copy(p.cols_corr.begin(), p.cols_corr.end(), corr);
+    if (image) std::copy(p.cols_image.begin(), p.cols_image.end(), image);
+    if (image2) std::copy(p.cols2_image.begin(), p.cols2_image.end(), image2);
+    return 0;
+}

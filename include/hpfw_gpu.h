@@ -360,6 +360,11 @@ int hpfw_gpu_get_kernel_timing(hpfw_gpu *h, const char **names, float *ms, int *
 int hpfw_gpu_plan_checksum(int64_t n_samples, uint64_t *out8);
 /* the same with the chirp-z forward transform forced and under given conventions (HPFW_CONV_*) */
 int hpfw_gpu_plan_checksum_ex(int64_t n_samples, int force_bluestein, unsigned conventions, uint64_t *out8);
+/* host-only: the column stage's tables for a 7-smooth n_samples, copied out.  dims9 = {n1, n2, hq = n1 / 2 + 1,
+ * cols_mt, cols_ks, cols2_mt, cols2_ks, 1 when the parity-split image exists, 0}.  Any other pointer may be NULL; otherwise
+ * wq [2 n1] (Re, Im of rint(2^22 T_n1[m])), corr [2 hq], image [cols_mt * cols_ks * 3072] and image2
+ * [cols2_mt * 2 * cols2_ks * 3072] bytes, the twiddle digits as the int8 matrix instructions read them. */
+int hpfw_gpu_plan_cols_tables(int64_t n_samples, int32_t *dims9, int32_t *wq, double *corr, int8_t *image, int8_t *image2);
 
 /* ---- the projection's arithmetic.  The reference multiplies filters and frames in f32 (an Eigen/MKL sgemm,
  * parallel_collector.h:57,127) and keeps only the sign of P[r,i] - P[r,i+80] (hashprint_handle.h:119-122).  mode 1
