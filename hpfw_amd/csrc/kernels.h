@@ -65,7 +65,10 @@ constexpr int kXsBatch = HPFW_XS_BATCH; // elements per thread whose loads are i
 struct XsView {
     const cf *base;
     int n1, w, q0;
-    unsigned long long magic; // ceil(2^40 / n1): k / n1 = (k magic) >> 40 for every k < 2^21, n1 <= 2^13
+    // ceil(2^40 / n1): k / n1 = (k magic) >> 40 for every k < 2^27, n1 <= 2^13.  With e = magic n1 - 2^40 < n1 the product is
+    // 2^40 (k / n1 + k e / (2^40 n1)), and the floor is that of k / n1 while k e < 2^40.  (Bins reach 2.7 M at the longest
+    // clip; the product stays below 2^64 because k / n1 < n2 / 2 < 2^12.)
+    unsigned long long magic;
     HPFW_DEVICE_MEMBER cf operator()(int k) const
     {
         if (n1 == 1) return base[k - q0];

@@ -94,8 +94,8 @@ def test_stages_bit_exact(gpu, torch_cuda, oracle, filters, seconds):
 
 @pytest.mark.parametrize("seconds", [2.0, 4.2, 7.0, 10.0, 12.5, 20.0, 45.0, 49.0, 60.0, 100.0, 180.0])
 def test_extract_other_lengths(gpu, oracle, filters, seconds):
-    """other clip lengths (different n1, chirp-z classes from 64 to 16384 points in LDS and, from 60 s on,
-    lengths up to 98304 points through global memory, the run-time group sequence when n2 is not 6300):
+    """other clip lengths (different n1, chirp-z classes from 384 to 16384 points in LDS and, from 60 s on,
+    lengths up to 65536 points through global memory, the run-time group sequence when n2 is not 6300):
     hashprints and the dB spectrogram stay bit-exact"""
     torch = pytest.importorskip("torch")
     clips = np.stack([synth.gen_clip(900 + i, seconds) for i in range(2 if seconds < 60 else 1)])

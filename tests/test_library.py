@@ -46,6 +46,20 @@ def test_plan_tables_identical_to_oracle(oracle, n):
     assert np.array_equal(hpfw_amd.plan_checksum(n), want)
 
 
+@pytest.mark.parametrize("n", [10584000, 54190080])
+def test_plan_tables_of_the_large_classes_identical_to_oracle(oracle, n):
+    """240 s and the longest clip the forward split admits (8064 x 6720): constant-Q classes 24576 .. 98304 and 131072 ..
+    524288, which run through global memory (k_cq_big.hip).  FNV-1a checksums of the geometry, the windows, every class's
+    length-p twiddle table and its chirp spectrum in the kernels' order (vrev) agree with the oracle's.  (The per-group
+    arrangement of those twiddles for a length-len0 block, plan.cpp append_group_twiddles, has no counterpart in the oracle:
+    tests/test_gpu_cq_sweep.py pins it through the magnitudes.)"""
+    want = np.zeros(8, np.uint64)
+    plan = oracle.Plan(n)
+    oracle.lib().hpfw_oracle_plan_checksum.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    oracle.lib().hpfw_oracle_plan_checksum(plan._h, want.ctypes.data_as(ctypes.c_void_p))
+    assert np.array_equal(hpfw_amd.plan_checksum(n), want)
+
+
 @pytest.mark.parametrize("n", [1323001, 352799, 99991, -220500])
 def test_chirpz_plan_tables_identical_to_oracle(oracle, n):
     """lengths with a prime factor above 7 (and, negative, a 7-smooth length forced down the same path): geometry,
