@@ -51,7 +51,7 @@ EXPORTS = (
     "hpfw_gpu_cfg_set_filters", "hpfw_gpu_cfg_hashprints", "hpfw_gpu_mel_hashprints_pcm16_host",
     "hpfw_gpu_cfg_cov_reset", "hpfw_gpu_cfg_cov_accumulate", "hpfw_gpu_cfg_cov_get", "hpfw_gpu_cfg_learn_filters",
     "hpfw_gpu_set_kernel_timing", "hpfw_gpu_get_kernel_timing", "hpfw_gpu_plan_checksum",
-    "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_plan_cols_tables", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
+    "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_plan_cols_tables", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_debug_db_term_sweep", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
     "hpfw_gpu_hashprints_from_db", "hpfw_gpu_stage_delta_q",
     "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
     "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
@@ -187,6 +187,7 @@ def lib():
     L.hpfw_gpu_plan_cols_tables.argtypes = [i64, vp, vp, vp, vp, vp]
     L.hpfw_gpu_chirpz_table.argtypes = [vp, i64, i32, vp, i64, vp]
     L.hpfw_gpu_debug_workspace.argtypes = [vp, i32, vp, vp]
+    L.hpfw_gpu_debug_db_term_sweep.argtypes = [u32, ctypes.c_uint64, vp]
     L.hpfw_gpu_prepare_length.argtypes = [vp, i64]
     L.hpfw_gpu_set_projection.argtypes = [vp, i32]
     L.hpfw_gpu_get_projection.argtypes = [vp]
@@ -922,6 +923,14 @@ def plan_checksum(n_samples, conventions=0):
     if rc != 0:
         raise HpfwError(f"unsupported clip length {n_samples}")
     return out
+
+
+def debug_db_term_sweep(first, count):
+    """(differing, fallbacks, first differing pattern or None) of the two evaluations of the dB term on the `count`
+    consecutive float bit patterns from `first` (hpfw_gpu_debug_db_term_sweep), on the current device"""
+    out = np.zeros(3, np.uint64)
+    check(lib().hpfw_gpu_debug_db_term_sweep(int(first), int(count), _hp(out)))
+    return int(out[0]), int(out[1]), (None if int(out[2]) == 2 ** 64 - 1 else int(out[2]))
 
 
 def plan_cols_tables(n_samples):

@@ -224,11 +224,11 @@ int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, 
         for (size_t ci = dp->cls.size(); ci-- > 0;) {
             const hpfw::CqClassDev &cd = dp->cls[ci];
             if (cd.outer) {
-                hpfw::launch_cq_big_class(dp->cq, cd, x, nb, h->d_cqwork.as<cf>(), mag, mm, true, s);
+                hpfw::launch_cq_big_class(dp->cq, cd, x, nb, h->d_cqwork.as<cf>(), mag, mm, h->db_fast ? hpfw::kDbFast : hpfw::kDbSpec, s);
                 continue;
             }
             const int lane = fork ? turn++ % (hpfw_gpu::kCqSide + 1) : 0; // 0: the caller's stream
-            hpfw::launch_cq_class(dp->cq, cd, x, nb, mag, mm, true, fan.lane(lane));
+            hpfw::launch_cq_class(dp->cq, cd, x, nb, mag, mm, h->db_fast ? hpfw::kDbFast : hpfw::kDbSpec, fan.lane(lane));
         }
         if ((rc = check_launch("cq_chirpz"))) return rc;
     }
@@ -756,6 +756,19 @@ int hpfw_gpu_debug_workspace(hpfw_gpu *h, int which, void **d_ptr, size_t *bytes
     return 0;
 }
 
+int hpfw_gpu_debug_db_term_sweep(uint32_t first, uint64_t count, uint64_t *out)
+{
+    if (!out || count > (1ull << 32) - first) return fail(HPFW_E_INVALID, "bad argument");
+    DevBuf d;
+    HIP_TRY(d.alloc(3 * sizeof(uint64_t)));
+    const uint64_t init[3] = {0, 0, ~0ull};
+    HIP_TRY(hipMemcpy(d.get(), init, sizeof(init), hipMemcpyHostToDevice));
+    hpfw::launch_db_term_sweep(first, count, d.as<unsigned long long>(), nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d.get(), sizeof(init), hipMemcpyDeviceToHost)); // (waits for the null stream)
+    return 0;
+}
+
 // ---- stages ----------------------------------------------------------------------------------
 int hpfw_gpu_stage_spectrum(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t n_clips,
                             float *d_x, void *stream)
@@ -803,10 +816,10 @@ int hpfw_gpu_stage_cqmag(hpfw_gpu *h, const float *d_x, int64_t n_samples, int64
             for (const hpfw::CqClassDev &cd : dp->cls) {
                 if (cd.outer)
                     hpfw::launch_cq_big_class(cq, cd, (const hpfw::cf *)d_x + c0 * nk, nb, h->d_cqwork.as<hpfw::cf>(),
-                                              d_mag + c0 * 121 * dp->hp.c, h->ws[4].as<float>(), false, s);
+                                              d_mag + c0 * 121 * dp->hp.c, h->ws[4].as<float>(), hpfw::kDbNone, s);
                 else
                     hpfw::launch_cq_class(cq, cd, (const hpfw::cf *)d_x + c0 * nk, nb,
-                                          d_mag + c0 * 121 * dp->hp.c, h->ws[4].as<float>(), false, s);
+                                          d_mag + c0 * 121 * dp->hp.c, h->ws[4].as<float>(), hpfw::kDbNone, s);
             }
             if ((rc = check_launch("cq_chirpz"))) return rc;
         }
@@ -828,7 +841,7 @@ int hpfw_gpu_stage_db(hpfw_gpu *h, const float *d_mag, int64_t n_clips, int64_t 
         for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
             const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
             hpfw::launch_magmax(d_mag + c0 * per, nb, (int)c, h->ws[4].as<float>(), s);
-            hpfw::launch_db(d_mag + c0 * per, h->ws[4].as<float>(), h->d_clipmax.as<float>(), nb, per, d_db + c0 * per, s);
+            hpfw::launch_db(d_mag + c0 * per, h->ws[4].as<float>(), h->d_clipmax.as<float>(), nb, per, d_db + c0 * per, h->db_fast, s);
             if ((rc = check_launch("db"))) return rc;
         }
         return 0;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void cq_big_dif_kernel(CqBigArgs a, CqPlanDev 
 
 // one inverse DIT radix-4 pass at sub-length len.  LAST (len == p): the outputs with index < c go to
 // the spectrogram as magnitudes or dB terms, nothing is written back.
-template <bool LAST, bool DBT>
+template <bool LAST, int DBT>
 __global__ __launch_bounds__(256) void cq_big_idit_kernel(CqBigArgs a, CqPlanDev cp, cf *__restrict__ work,
                                                           float *__restrict__ mag)
 {
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void cq_big_idit_kernel(CqBigArgs a, CqPlanDev
             const int i = i0 + s * quarter;
             if (i < cp.c) {
                 const float m = __builtin_sqrtf(__builtin_fmaf(v[s].r, v[s].r, v[s].i * v[s].i));
-                out[i] = DBT ? db_term(m * m) : m;
+                out[i] = DBT == kDbNone ? m : db_term<DBT == kDbFast>(m * m);
             }
         }
     } else {
@@ -162,7 +162,7 @@ size_t cq_big_work_bytes(const CqClassDev &cc, int n_clips)
 }
 
 void launch_cq_big_class(const CqPlanDev &cp, const CqClassDev &cc, const cf *d_x, int n_clips, cf *d_work, float *d_mag,
-                         float *d_wavemax, bool db_term_out, hipStream_t s)
+                         float *d_wavemax, int db_mode, hipStream_t s)
 {
     CqBigArgs a;
     a.p = cc.p;
@@ -188,11 +188,13 @@ void launch_cq_big_class(const CqPlanDev &cp, const CqClassDev &cc, const cf *d_
     for (int q = cc.outer - 1; q >= 0; --q, len *= 4) {
         a.len = len;
         if (q > 0)
-            hipLaunchKernelGGL((cq_big_idit_kernel<false, false>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
-        else if (db_term_out)
-            hipLaunchKernelGGL((cq_big_idit_kernel<true, true>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
+            hipLaunchKernelGGL((cq_big_idit_kernel<false, kDbNone>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
+        else if (db_mode == kDbFast)
+            hipLaunchKernelGGL((cq_big_idit_kernel<true, kDbFast>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
+        else if (db_mode == kDbSpec)
+            hipLaunchKernelGGL((cq_big_idit_kernel<true, kDbSpec>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
         else
-            hipLaunchKernelGGL((cq_big_idit_kernel<true, false>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
+            hipLaunchKernelGGL((cq_big_idit_kernel<true, kDbNone>), grid, dim3(256), 0, s, a, cp, d_work, d_mag);
     }
     hipLaunchKernelGGL(cq_big_max_kernel, dim3(cc.n_bands, n_clips), dim3(256), 0, s, d_mag, cp.c, cc.band, d_wavemax);
 }

@@ -197,6 +197,7 @@ __global__ __launch_bounds__(256) void mel_max_kernel(const float *__restrict__ 
 }
 
 // out[clip][band][pos[f]] = max(t(power) - t(pmax), -80)  (convert.h:7-16), kept frames only
+template <bool FAST>
 __global__ __launch_bounds__(256) void mel_db_kernel(const float *__restrict__ power, const int *__restrict__ pos,
                                                      const float *__restrict__ pmax, int n_frames, float *__restrict__ out)
 {
@@ -206,8 +207,8 @@ __global__ __launch_bounds__(256) void mel_db_kernel(const float *__restrict__ p
     const int band = (int)(i / n_frames), f = (int)(i - (int64_t)band * n_frames);
     const int c = pos[(int64_t)clip * n_frames + f];
     if (c < 0) return;
-    const float ref = db_term(pmax[clip]);
-    const float l = db_term(power[(int64_t)clip * kMelBands * n_frames + i]) - ref;
+    const float ref = db_term<FAST>(pmax[clip]);
+    const float l = db_term<FAST>(power[(int64_t)clip * kMelBands * n_frames + i]) - ref;
     out[((int64_t)clip * kMelBands + band) * n_frames + c] = l < -80.0f ? -80.0f : l;
 }
 
@@ -222,7 +223,7 @@ size_t mel_work_bytes(int64_t n, int n_clips)
 }
 
 void launch_mel(const RowsArgs &rows, const float *d_win, const float *d_cpack, const int16_t *d_pcm, int64_t n, int n_clips,
-                int64_t *d_blk, int *d_pos, int *d_count, float *d_pmax, float *d_work, float *d_out, hipStream_t s)
+                int64_t *d_blk, int *d_pos, int *d_count, float *d_pmax, float *d_work, float *d_out, bool db_fast, hipStream_t s)
 {
     const int nf = mel_frames(n), fp = (nf + 1) / 2 * 2, n_blk = (int)((n + kMelHop - 1) / kMelHop);
     float *y = d_work, *power = d_work + (size_t)n_clips * fp * 2 * kMelHpad;
@@ -238,8 +239,11 @@ void launch_mel(const RowsArgs &rows, const float *d_win, const float *d_cpack, 
                        rows, d_pcm, n, nf, fp, d_win, y);
     hipLaunchKernelGGL(mel_bands_kernel, dim3((nf + 127) / 128, n_clips), dim3(256), 0, s, y, d_cpack, nf, fp, power);
     hipLaunchKernelGGL(mel_max_kernel, dim3(n_clips), dim3(256), 0, s, power, d_pos, nf, d_pmax);
-    hipLaunchKernelGGL(mel_db_kernel, dim3((unsigned)(((int64_t)kMelBands * nf + 255) / 256), n_clips), dim3(256), 0, s, power,
-                       d_pos, d_pmax, nf, d_out);
+    const dim3 db_grid((unsigned)(((int64_t)kMelBands * nf + 255) / 256), n_clips);
+    if (db_fast)
+        hipLaunchKernelGGL(mel_db_kernel<true>, db_grid, dim3(256), 0, s, power, d_pos, d_pmax, nf, d_out);
+    else
+        hipLaunchKernelGGL(mel_db_kernel<false>, db_grid, dim3(256), 0, s, power, d_pos, d_pmax, nf, d_out);
 }
 
 } // namespace hpfw

@@ -222,13 +222,15 @@ void launch_bz_cols_last(const BzArgs &bz, const float *d_in, int n_clips, cf *d
 // band chirp-z transforms: x -> mag [n_clips][121][c]; also the maxima each wave saw,
 // d_wavemax [n_clips][121][kCqMaxWaves] (slots of absent waves are written as 0)
 constexpr int kCqMaxWaves = 16;
-// db_term_out: store t(m^2) = (float)(10 log10(max(m^2, 1e-10))) instead of the magnitude m
+// db_mode: store the magnitude m, or t(m^2) = (float)(10 log10(max(m^2, 1e-10))) instead, by the specified sequence of
+// DESIGN.md S8 alone or by db_term_fast (db_spec.h), which gives the same floats
+enum DbMode { kDbNone = 0, kDbSpec = 1, kDbFast = 2 };
 void launch_cq_class(const CqPlanDev &cp, const CqClassDev &cc, const cf *d_x, int n_clips,
-                     float *d_mag, float *d_wavemax, bool db_term_out, hipStream_t s);
+                     float *d_mag, float *d_wavemax, int db_mode, hipStream_t s);
 // the same for a class whose length exceeds the LDS (cc.outer > 0); d_work: cq_big_work_bytes(cc, n_clips)
 size_t cq_big_work_bytes(const CqClassDev &cc, int n_clips);
 void launch_cq_big_class(const CqPlanDev &cp, const CqClassDev &cc, const cf *d_x, int n_clips, cf *d_work, float *d_mag,
-                         float *d_wavemax, bool db_term_out, hipStream_t s);
+                         float *d_wavemax, int db_mode, hipStream_t s);
 // d_clipmax [n_clips] = the largest of each clip's wave maxima
 void launch_clipmax(const float *d_wavemax, float *d_clipmax, int n_clips, hipStream_t s);
 // dB terms -> dB spectrogram in place: S = max(t - t_max, -80)
@@ -237,7 +239,10 @@ void launch_db_finish(float *d_t, const float *d_clipmax, int n_clips, int64_t p
 void launch_magmax(const float *d_mag, int n_clips, int c, float *d_wavemax, hipStream_t s);
 // amplitude_to_db: d_clipmax [n_clips] receives the per-clip maximum of d_wavemax first
 void launch_db(const float *d_mag, const float *d_wavemax, float *d_clipmax, int n_clips, int64_t per_clip,
-               float *d_db, hipStream_t s);
+               float *d_db, bool fast, hipStream_t s);
+// (tests) db_term_fast against db_term_spec on the bit patterns first .. first + count - 1: d_out[0] += those that differ,
+// d_out[1] += those in 1e-10f <= p < inf that took the fallback, d_out[2] = min(d_out[2], first differing pattern)
+void launch_db_term_sweep(uint32_t first, uint64_t count, unsigned long long *d_out, hipStream_t s);
 // filters * frames on f32 MFMA: s_db [n_clips][121][c] -> proj [n_clips][64][c-19]
 // d_fpack: filters repacked by pack_filters_for_mfma().  d_tmax != NULL: s_db holds dB terms and
 // S = max(t - d_tmax[clip], -80) is applied while the slab is staged.
@@ -317,7 +322,7 @@ int mel_frames(int64_t n_samples);
 size_t mel_work_bytes(int64_t n_samples, int n_clips);
 // d_out [n_clips][33][frames] (kept columns at the front of every row), d_count [n_clips] their number
 void launch_mel(const RowsArgs &rows, const float *d_win, const float *d_cpack, const int16_t *d_pcm, int64_t n, int n_clips,
-                int64_t *d_blk, int *d_pos, int *d_count, float *d_pmax, float *d_work, float *d_out, hipStream_t s);
+                int64_t *d_blk, int *d_pos, int *d_count, float *d_pmax, float *d_work, float *d_out, bool db_fast, hipStream_t s);
 
 // ---- search ------------------------------------------------------------------------------
 struct SearchArgs {

@@ -104,7 +104,7 @@ int hpfw_gpu_mel_spectrogram_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_
             int *pos = (int *)(blk + (size_t)nbmax * n_blk);
             float *pmax = (float *)(pos + (size_t)nbmax * nf);
             hpfw::launch_mel(h->mel.rows, h->mel.d_win, h->mel.d_cpack, d_pcm + c0 * n_samples, n_samples, nb, blk, pos,
-                             d_cols + c0, pmax, h->mel.d_work.as<float>(), d_out + c0 * hpfw::kMelBands * nf, s);
+                             d_cols + c0, pmax, h->mel.d_work.as<float>(), d_out + c0 * hpfw::kMelBands * nf, h->db_fast, s);
             if ((rc = check_launch("mel"))) return rc;
         }
         return 0;

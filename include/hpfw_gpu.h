@@ -546,6 +546,12 @@ int hpfw_gpu_chirpz_table(hpfw_gpu *h, int64_t n_samples, int which, float *out,
  * the first stage that differs; not part of the reference's interface. */
 int hpfw_gpu_debug_workspace(hpfw_gpu *h, int which, void **d_ptr, size_t *bytes);
 
+/* ---- diagnostic: the two evaluations of the dB term (the specified sequence, and the table and short
+ * polynomial that stand in for it) on the `count` consecutive float bit patterns from `first`, on the current device.
+ * out[0] = patterns whose results differ (0 is the claim), out[1] = patterns in 1e-10f <= p < inf for which the fast
+ * evaluation was not certain and ran the specified sequence, out[2] = the first differing pattern (all ones: none). */
+int hpfw_gpu_debug_db_term_sweep(uint32_t first, uint64_t count, uint64_t out[3]);
+
 /* ---- legacy FFI: modules/python/parallel_collector_wrapper.hpp:12-38, same shapes --------- */
 typedef struct {
     char *filename;
