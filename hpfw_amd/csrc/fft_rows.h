@@ -222,14 +222,30 @@ HPFW_DEVICE void rows_last_compute(Lds &lds, const RowsArgs &a, const cf *__rest
     }
 }
 
-template <int R1, int R2, int N2C = 0, class Lds>
+// Out: which of the block's R = R1 R2 outputs f are stored, a compile-time list.  LastAll: every one (any consumer of
+// the whole spectrum: the Mel STFT, the chirp-z forward transform).  LastEdges: f in {0, 1, R - 2, R - 1} only -- the
+// forward transform's epilogue reads the window q2lo <= k2 < q2lo + q2w and its mirror n2 - 1 - k2, and when the plan
+// finds both inside [0, 2 nb) and [n2 - 2 nb, n2) (plan.h rows_last_edges_ok: the 30 s clip reads 4 of 20 outputs) no other
+// position of the LDS is ever read again.  rows_last_compute is inlined into the same function and its `out` is a
+// register array, so what the skipped outputs alone depend on -- for (5, 4): e[2][.], its twiddle products, three of four
+// outputs of each second-stage Dft<4>, 14 of 15 final products -- is never formed.  The operations behind the stored outputs
+// are the same ones in the same order (-ffp-contract=off; a codelet's outputs do not share roundings that the others
+// lack), so the stored values are the same bits.
+struct LastAll {
+    static constexpr bool keep(int, int) { return true; }
+};
+struct LastEdges {
+    static constexpr bool keep(int f, int r) { return f < 2 || f >= r - 2; }
+};
+template <int R1, int R2, int N2C = 0, class Out = LastAll, class Lds>
 HPFW_DEVICE void rows_last_store(Lds &lds, const RowsArgs &a, int tid, const cf *out)
 {
     const int nb = (N2C ? N2C : a.n2) / (R1 * R2);
     if (tid >= nb) return;
     const int k0 = a.kb_last[tid];
 #pragma unroll
-    for (int f = 0; f < R1 * R2; ++f) lds[k0 + f * nb] = out[f];
+    for (int f = 0; f < R1 * R2; ++f)
+        if (Out::keep(f, R1 * R2)) lds[k0 + f * nb] = out[f];
 }
 
 template <int R1, class Lds>
@@ -285,6 +301,7 @@ struct StaticGroups;
 template <>
 struct StaticGroups<> {
     static constexpr int kProduct = 1;
+    static constexpr int kLastPoints = 0;
     static bool matches(const RowGroups &, int g, int n) { return g == n; }
 };
 
@@ -294,6 +311,8 @@ template <int R1, int R2, int... Rest>
 struct StaticGroups<R1, R2, Rest...> {
     static constexpr bool kNatural = true;
     static constexpr int kProduct = R1 * R2 * StaticGroups<Rest...>::kProduct;
+    // points of the last group (its outputs f = 0 .. kLastPoints - 1 per block)
+    static constexpr int kLastPoints = sizeof...(Rest) == 0 ? R1 * R2 : StaticGroups<Rest...>::kLastPoints;
     // butterflies of the two-phase groups: n2 / (R1 R2) with n2 the product of ALL radices, so only
     // the complete list knows it; StaticGroups<...>::min_threads(n2) is used by the launcher
     static int min_threads(int n2)
@@ -311,7 +330,7 @@ struct StaticGroups<R1, R2, Rest...> {
         }
     }
     // N2 = the product of the whole list, LEN = the sub-length this group starts from: both known at compile time
-    template <int N2, int LEN, class Lds>
+    template <int N2, int LEN, class Out = LastAll, class Lds>
     HPFW_DEVICE_STATIC void run_from(Lds &lds, const RowsArgs &a, int nthreads, int g)
     {
         const cf *gt = a.gtw + a.groups.tw_off[g];
@@ -320,7 +339,7 @@ struct StaticGroups<R1, R2, Rest...> {
             HPFW_FOR_THREADS(tid, nthreads) { rows_last_compute<R1, R2, N2>(lds, a, gt, tid, HPFW_CARRY_AT(outv, R1 * R2, tid)); }
             HPFW_BARRIER();
             HPFW_STAMP(a, 5);
-            HPFW_FOR_THREADS(tid, nthreads) { rows_last_store<R1, R2, N2>(lds, a, tid, HPFW_CARRY_AT(outv, R1 * R2, tid)); }
+            HPFW_FOR_THREADS(tid, nthreads) { rows_last_store<R1, R2, N2, Out>(lds, a, tid, HPFW_CARRY_AT(outv, R1 * R2, tid)); }
             HPFW_BARRIER();
             HPFW_STAMP(a, 6);
             HPFW_SNAP(lds, a, g + 1, N2);
@@ -333,13 +352,13 @@ struct StaticGroups<R1, R2, Rest...> {
             HPFW_BARRIER();
             HPFW_STAMP(a, 4);
             HPFW_SNAP(lds, a, g + 1, N2);
-            StaticGroups<Rest...>::template run_from<N2, LEN / (R1 * R2)>(lds, a, nthreads, g + 1);
+            StaticGroups<Rest...>::template run_from<N2, LEN / (R1 * R2), Out>(lds, a, nthreads, g + 1);
         } else {
             HPFW_FOR_THREADS(tid, nthreads) { rows_group<R1, R2, N2, LEN>(lds, a, gt, LEN, tid, nthreads); }
             HPFW_BARRIER();
             HPFW_STAMP(a, 2);
             HPFW_SNAP(lds, a, g + 1, N2);
-            StaticGroups<Rest...>::template run_from<N2, LEN / (R1 * R2)>(lds, a, nthreads, g + 1);
+            StaticGroups<Rest...>::template run_from<N2, LEN / (R1 * R2), Out>(lds, a, nthreads, g + 1);
         }
     }
 #if !defined(HPFW_SIMT_EMU)
@@ -351,12 +370,12 @@ struct StaticGroups<R1, R2, Rest...> {
     {
         if constexpr (sizeof...(Rest) != 0) rows_group_fetch<R1, R2, N2, LEN>(a.gtw + a.groups.tw_off[g], threadIdx.x, mine);
     }
-    template <int N2, int LEN, class Lds>
+    template <int N2, int LEN, class Out = LastAll, class Lds>
     HPFW_DEVICE_STATIC void run_fetched(Lds &lds, const RowsArgs &a, int g, const Pairs &mine)
     {
         const int tid = threadIdx.x;
         if constexpr (sizeof...(Rest) == 0) {
-            run_from<N2, LEN>(lds, a, 0, g);          // (the last group's twiddles are the same for every butterfly: scalar loads)
+            run_from<N2, LEN, Out>(lds, a, 0, g);     // (the last group's twiddles are the same for every butterfly: scalar loads)
         } else if constexpr (sizeof...(Rest) == 2) {
             cf outv[R1 * R2];
             rows_group_pre<R1, R2, N2, LEN>(lds, tid, mine, outv);
@@ -366,7 +385,7 @@ struct StaticGroups<R1, R2, Rest...> {
             HPFW_BARRIER();
             HPFW_STAMP(a, 4);
             HPFW_SNAP(lds, a, g + 1, N2);
-            StaticGroups<Rest...>::template run_from<N2, LEN / (R1 * R2)>(lds, a, 0, g + 1);
+            StaticGroups<Rest...>::template run_from<N2, LEN / (R1 * R2), Out>(lds, a, 0, g + 1);
         } else {
             using Next = StaticGroups<Rest...>;
             rows_group_pre<R1, R2, N2, LEN>(lds, tid, mine, static_cast<cf *>(nullptr));
@@ -375,15 +394,15 @@ struct StaticGroups<R1, R2, Rest...> {
             HPFW_BARRIER();
             HPFW_STAMP(a, 2);
             HPFW_SNAP(lds, a, g + 1, N2);
-            Next::template run_fetched<N2, LEN / (R1 * R2)>(lds, a, g + 1, next);
+            Next::template run_fetched<N2, LEN / (R1 * R2), Out>(lds, a, g + 1, next);
         }
     }
 #endif
-    template <class Lds>
+    template <class Out = LastAll, class Lds>
     HPFW_DEVICE_STATIC void run(Lds &lds, const RowsArgs &a, int nthreads)
     {
         static_assert(sizeof...(Rest) >= 2, "the transposed layout needs a group before the last");
-        run_from<kProduct, kProduct>(lds, a, nthreads, 0); // the launcher checked a.n2 == kProduct (matches())
+        run_from<kProduct, kProduct, Out>(lds, a, nthreads, 0); // the launcher checked a.n2 == kProduct (matches())
     }
     static bool matches(const RowGroups &g, int i, int n)
     {
@@ -506,6 +525,9 @@ struct Rows2Out {
     long long zpitch;
     int zrow;
     long long zclip;
+    // host side only: the plan found the consumed windows inside the last group's outputs {0, 1, R - 2, R - 1} and the
+    // handle allows it (HPFW_PRUNE bit 0) -- launch_fwd_rows2 then takes the LastEdges instantiation
+    int last_edges;
 };
 
 struct alignas(16) f4 {
@@ -513,7 +535,9 @@ struct alignas(16) f4 {
 };
 
 // zre: the row's Re values in the blocked layout of Rows2Out (its Im values o.zrow floats on), the column stage's integers rounded to f32
-template <class Groups, class Lds>
+// Out: the last group's output policy (rows_last_store); anything but LastAll only with a compile-time sequence and a plan
+// whose windows it covers (launch_fwd_rows2)
+template <class Groups, class Out = LastAll, class Lds>
 HPFW_DEVICE void rows2_body(Lds &lds, const RowsArgs &a, int nthreads, const float *__restrict__ zre, int q1, const Rows2Out &o,
                             cf *__restrict__ xclip)
 {
@@ -579,14 +603,17 @@ HPFW_DEVICE void rows2_body(Lds &lds, const RowsArgs &a, int nthreads, const flo
         HPFW_BARRIER();
         HPFW_STAMP(a, 1);
         HPFW_SNAP(lds, a, 0, n2);
-        Groups::template run_fetched<Groups::kProduct, Groups::kProduct>(lds, a, 0, tw0);
+        Groups::template run_fetched<Groups::kProduct, Groups::kProduct, Out>(lds, a, 0, tw0);
     } else
 #endif
     {
         HPFW_BARRIER();
         HPFW_STAMP(a, 1);
         HPFW_SNAP(lds, a, 0, n2);
-        Groups::run(lds, a, nthreads);
+        if constexpr (Groups::kProduct != 0)
+            Groups::template run<Out>(lds, a, nthreads);
+        else
+            Groups::run(lds, a, nthreads);
     }
     const int *__restrict__ pos = a.pos_n2;
     constexpr bool kNat = Groups::kNatural;

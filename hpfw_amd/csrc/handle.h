@@ -177,6 +177,9 @@ struct hpfw_gpu {
     // for the whole batch), HPFW_FWD_STREAMS (1..5) in the environment at creation
     int fwd_chunk = 16, fwd_streams = 2;
     int cols_variant = 0; // HPFW_COLS_VARIANT (tests, diagnosis): kernels.h ColsQArgs::variant
+    // HPFW_PRUNE (tests, timing), a bit mask of what the transforms leave out because nothing reads it: 1 = the row stage's last-group
+    // outputs outside the consumed windows (fft_rows.h LastEdges, where the plan finds that they fit); 0: the kernels without it
+    unsigned prune = 1;
     bool db_fast = true;  // HPFW_DB_TERM=spec (tests, timing) clears it: dB terms by the specified sequence alone (db_spec.h)
     int bz_chunk = 32;  // the same for the chirp-z forward transform's three kernels (HPFW_BZ_CHUNK; 38.6 -> 39.6 k clips/s at 30 s)
     // staging of the host-buffer entry points: kept between calls (a one-file call is otherwise mostly

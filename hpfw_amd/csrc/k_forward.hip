@@ -857,7 +857,7 @@ constexpr int kFwdThreads = 512;
 #define HPFW_ROWS_WAVES 6 // waves per SIMD the compile-time sequence is held to (6: three workgroups per CU)
 #endif
 
-template <class Groups, int WAVES>
+template <class Groups, int WAVES, class Out = LastAll>
 __global__ __launch_bounds__(kFwdThreads, WAVES) void fwd_rows2_kernel(RowsArgs a, Rows2Out o, const float *__restrict__ z,
                                                                    cf *__restrict__ x)
 {
@@ -865,7 +865,7 @@ __global__ __launch_bounds__(kFwdThreads, WAVES) void fwd_rows2_kernel(RowsArgs 
     // clip is the fast grid index: workgroups resident at the same time run the same row, whose butterfly twiddles
     // they share in L2
     const int clip = blockIdx.x, q1 = blockIdx.y;
-    rows2_body<Groups>(lds, a, kFwdThreads, z + (int64_t)clip * o.zclip + (int64_t)2 * q1 * o.zrow, q1, o, x + (int64_t)clip * o.n1 * o.q2w);
+    rows2_body<Groups, Out>(lds, a, kFwdThreads, z + (int64_t)clip * o.zclip + (int64_t)2 * q1 * o.zrow, q1, o, x + (int64_t)clip * o.n1 * o.q2w);
 }
 
 __global__ __launch_bounds__(256) void gather_bins_kernel(CqPlanDev cp, const cf *__restrict__ x, cf *__restrict__ out)
@@ -927,17 +927,17 @@ void launch_fwd_cols_q(const ColsQArgs &a_in, const int16_t *d_pcm, int64_t clip
 
 size_t fwd_rows_lds_bytes(const RowsArgs &a) { return (size_t)a.n2 * sizeof(cf); }
 
-template <class Groups, int WAVES>
+template <class Groups, int WAVES, class Out = LastAll>
 static void launch_rows2_t(const RowsArgs &a, const Rows2Out &o, const float *d_z, int n_clips, cf *d_x, hipStream_t s)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fwd_rows2_kernel<Groups, WAVES>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fwd_rows2_kernel<Groups, WAVES, Out>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set.mark();
     }
     dim3 grid(n_clips, o.hq);
-    hipLaunchKernelGGL((fwd_rows2_kernel<Groups, WAVES>), grid, dim3(kFwdThreads), fwd_rows_lds_bytes(a), s, a, o, d_z, d_x);
+    hipLaunchKernelGGL((fwd_rows2_kernel<Groups, WAVES, Out>), grid, dim3(kFwdThreads), fwd_rows_lds_bytes(a), s, a, o, d_z, d_x);
 }
 
 void launch_fwd_rows2(const RowsArgs &a, const Rows2Out &o, const float *d_z, int n_clips, cf *d_x, hipStream_t s)
@@ -946,8 +946,14 @@ void launch_fwd_rows2(const RowsArgs &a, const Rows2Out &o, const float *d_z, in
     // the compile-time sequence runs its last two groups one butterfly per thread
     // (68 registers under the bound of six waves per SIMD: three workgroups share a CU, as the 50 KB of LDS allow --
     // 2.30 -> 2.18 ms per 1000 clips against the 82 registers and two workgroups the compiler settles on by itself)
-    if (Groups6300::matches_plan(a) && Groups6300::min_threads(a.n2) <= kFwdThreads)
-        launch_rows2_t<Groups6300, HPFW_ROWS_WAVES>(a, o, d_z, n_clips, d_x, s);
+    // o.last_edges: the consumed windows lie inside the last group's outputs {0, 1, 18, 19} (the plan checked it: plan.h
+    // rows_last_edges_ok) -- the instantiation that neither forms nor stores the other sixteen (fft_rows.h rows_last_store)
+    if (Groups6300::matches_plan(a) && Groups6300::min_threads(a.n2) <= kFwdThreads) {
+        if (o.last_edges)
+            launch_rows2_t<Groups6300, HPFW_ROWS_WAVES, LastEdges>(a, o, d_z, n_clips, d_x, s);
+        else
+            launch_rows2_t<Groups6300, HPFW_ROWS_WAVES>(a, o, d_z, n_clips, d_x, s);
+    }
     else
         launch_rows2_t<RuntimeGroups, 4>(a, o, d_z, n_clips, d_x, s);
 }

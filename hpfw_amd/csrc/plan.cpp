@@ -532,6 +532,7 @@ bool build_plan(int64_t n, HostPlan &p, std::string &why, bool geometry_only, bo
                         why = "internal: last-group output map";
                         return false;
                     }
+        if (!p.bluestein) p.rows_last_mask = rows_last_needed(p.kb_last.data(), nb, len, (int)n2, p.q2lo, p.q2w);
     }
     // ---- chirp-z classes ----
     p.g_off.assign(kBins, 0);

@@ -54,6 +54,7 @@ struct HostPlan {
     std::vector<HostCf> ts_step;            // [hq][4]: T_N[q1 e] (entry 0 unused)
     std::vector<int> pos_n2;
     std::vector<int> kb_last;               // last group's block b holds outputs kb_last[b] + (n2 / len) f
+    unsigned rows_last_mask = 0;            // outputs f of the last group that the consumed window or its mirror needs (bit f; S6 only)
     int start[121], lg[121], psize[121];
     std::vector<int64_t> g_off;             // [121]
     int64_t g_total = 0, big_m = 0;         // sum of lg; M (the longest band: every band's output length)
@@ -95,6 +96,28 @@ inline double cq_window_scale(unsigned conventions, int64_t big_m, int psize)
     return 1.0 / (((conventions & kConvNoIfftScale) ? 1.0 : (double)big_m) * (double)psize);
 }
 inline int64_t cq_hann_den(unsigned conventions, int64_t lg) { return (conventions & kConvHannPeriodic) ? lg : lg - 1; }
+
+// The last fused group of the row transform (r points per block, nb blocks; output f of block b is k2 = kb_last[b] + nb f)
+// and what the forward transform's epilogue reads of it: q2lo <= k2 < q2lo + q2w and the mirror n2 - 1 - k2.  The set of
+// f that some block needs, as a bit mask (r <= 32; 0 when r is larger: nothing may be skipped then) ...
+inline unsigned rows_last_needed(const int *kb_last, int nb, int r, int n2, int q2lo, int q2w)
+{
+    if (r > 32) return 0;
+    unsigned mask = 0;
+    for (int b = 0; b < nb; ++b)
+        for (int f = 0; f < r; ++f) {
+            const int k2 = kb_last[b] + nb * f, km = n2 - 1 - k2;
+            if ((k2 >= q2lo && k2 < q2lo + q2w) || (km >= q2lo && km < q2lo + q2w)) mask |= 1u << f;
+        }
+    return mask;
+}
+// ... and whether the kernel that stores only f in {0, 1, r - 2, r - 1} (fft_rows.h LastEdges) covers it
+inline bool rows_last_edges_ok(unsigned needed, int r)
+{
+    if (r < 4 || r > 32 || needed == 0) return false;
+    const unsigned edges = 3u | (3u << (r - 2));
+    return (needed & ~edges) == 0;
+}
 
 // the row transform alone for frames of n2 samples (STFT of the Mel front-end): radix, groups, rows_gtw,
 // pos_n2 of `out`, and tw_big = two rows of ones

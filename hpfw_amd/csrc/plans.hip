@@ -332,6 +332,10 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
     dp->rows_out = hpfw::Rows2Out{p.n1, p.hq, p.q2lo, p.q2w, nullptr, nullptr, (p.n2 + 3) / 4, 5 /* kZBlock / 4 = 2^5 pieces */,
                                   (long long)2 * p.hq * hpfw::kZBlock, hpfw::kZBlock, hpfw::z_floats_per_clip(p.hq, p.n2)};
     static_assert(hpfw::kZBlock == 128, "Rows2Out::zshift4 above");
+    // HPFW_PRUNE bit 0: the row stage leaves out the last group's outputs that neither consumed window reads, when those it needs
+    // are among the first and last two of a block
+    dp->rows_out.last_edges = (h->prune & 1u) && !p.bluestein && !p.groups.empty() &&
+                              hpfw::rows_last_edges_ok(p.rows_last_mask, p.groups.back().first * p.groups.back().second);
     if (!p.bluestein) {
         ca.n1 = p.n1;
         ca.n2 = p.n2;

@@ -77,6 +77,9 @@ typedef struct {
 const char *hpfw_gpu_last_error(void);
 const char *hpfw_gpu_version(void);
 
+/* Environment read when a handle is created (tests and timing; results are the same bits either way): HPFW_DB_TERM=spec --
+ * dB terms by the specified sequence alone; HPFW_PRUNE=<mask>, default 1 -- bit 0: the forward transform's row stage leaves
+ * out the outputs of its last pass that hold no consumed bin where the clip length allows it, 0: every output is formed. */
 int hpfw_gpu_create(int device, hpfw_gpu **out);
 void hpfw_gpu_destroy(hpfw_gpu *h);
 int hpfw_gpu_device(const hpfw_gpu *h); /* the device ordinal the handle was created on */
