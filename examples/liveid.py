@@ -28,9 +28,10 @@ ap.add_argument("--timeline", help="a long recording: print the indexed songs it
 ap.add_argument("--min-score", type=float, help="required with --timeline")
 ap.add_argument("--shifts", nargs="*", type=int, help="bin shifts to search as well (--timeline)")
 ap.add_argument("--tempos", nargs="*", type=float, help="tempo factors to search as well (--timeline)")
+ap.add_argument("--devices", nargs="*", type=int, help="shard the index over these devices, one ordinal per shard")
 args = ap.parse_args()
 
-liveid = LiveSongIdentification(cache=args.cache)
+liveid = LiveSongIdentification(cache=args.cache, devices=args.devices or None)
 if args.load:
     with open(args.load, "rb") as fp:
         hashprints = pickle.load(fp)

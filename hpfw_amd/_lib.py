@@ -65,6 +65,7 @@ EXPORTS = (
     "hpfw_gpu_search_topk_scored_device", "hpfw_gpu_search_topk_scored", "hpfw_gpu_search_topk_transposed_scored_device",
     "hpfw_gpu_search_topk_transposed_scored", "hpfw_gpu_hit_score", "hpfw_gpu_window_count", "hpfw_gpu_extract_windows_pcm16",
     "hpfw_gpu_extract_windows_pcm16_host", "hpfw_gpu_timeline_segments",
+    "hpfw_gpu_merge_topk_device", "hpfw_gpu_sum_stats_device", "hpfw_gpu_get_filters",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -134,6 +135,7 @@ def lib():
     L.hpfw_gpu_destroy.argtypes = [vp]
     L.hpfw_gpu_destroy.restype = None
     L.hpfw_gpu_set_filters.argtypes = [vp, vp]
+    L.hpfw_gpu_get_filters.argtypes = [vp, vp]
     L.hpfw_gpu_geometry.argtypes = [vp, i64, ctypes.POINTER(Geometry)]
     L.hpfw_gpu_extract_pcm16.argtypes = [vp, vp, i64, i64, vp, vp]
     L.hpfw_gpu_extract_pcm16_host.argtypes = [vp, vp, i64, i64, vp]
@@ -230,6 +232,8 @@ def lib():
     L.hpfw_gpu_extract_windows_pcm16.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp, vp]
     L.hpfw_gpu_extract_windows_pcm16_host.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp]
     L.hpfw_gpu_timeline_segments.argtypes = [vp, i64, ctypes.POINTER(TimelineParams), vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_merge_topk_device.argtypes = [vp, vp, i32, i64, i32, vp, vp]
+    L.hpfw_gpu_sum_stats_device.argtypes = [vp, vp, i32, i64, vp, vp]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -375,6 +379,12 @@ class Gpu:
         if f.size != 64 * 2420:
             raise ValueError("filters must hold 64 x 2420 floats (column-major)")
         check(lib().hpfw_gpu_set_filters(self._h, _hp(f)))
+
+    def get_filters(self):
+        """the filters the handle holds, float32 [64 * 2420] column-major (HPFW_E_NOFILTERS when none)"""
+        f = np.zeros(64 * 2420, np.float32)
+        check(lib().hpfw_gpu_get_filters(self._h, _hp(f)))
+        return f
 
     def geometry(self, n_samples):
         g = Geometry()
@@ -804,6 +814,15 @@ class Gpu:
         off = np.ascontiguousarray(q_off, np.int64)
         check(lib().hpfw_gpu_search_topk_transposed_scored_device(self._h, d_q, _hp(off), (off.size - 1) // n_shifts, int(n_shifts),
                                                                    int(k), d_out, d_stats, stream))
+
+    # ---- a sharded search's gathered results (k_merge.hip): device twins of merge_topk and of the sum of the moments
+    def merge_topk_dev(self, d_in, n_shards, n_q, k, d_out, stream=0):
+        """d_in [n_shards][n_q][k] of HIT_DTYPE or SHIFT_HIT_DTYPE records -> d_out [n_q][k] (device pointers)"""
+        check(lib().hpfw_gpu_merge_topk_device(self._h, d_in, int(n_shards), int(n_q), int(k), d_out, stream))
+
+    def sum_stats_dev(self, d_in, n_shards, rows, d_out, stream=0):
+        """d_out[r] = sum over shards of d_in[shard][r] (STATS_DTYPE rows, device pointers)"""
+        check(lib().hpfw_gpu_sum_stats_device(self._h, d_in, int(n_shards), int(rows), d_out, stream))
 
     def index_offsets(self):
         """the index's clip offsets int64 [n_clips + 1] (host copy; no hashprint is downloaded)"""

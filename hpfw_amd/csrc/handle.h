@@ -81,6 +81,7 @@ struct CallStatus {
 struct hpfw_gpu {
     int device = 0;
     bool has_filters = false;
+    std::vector<float> filters; // the filters as they were installed (hpfw_gpu_get_filters)
     DevBuf d_fpack;
     DevBuf d_fq_image; // the filters' fixed-point digits (k_project_q.hip)
     int projection = 1; // 1: fixed point (S9q), 0: the f32 fma chain (S9); hpfw_gpu_set_projection

@@ -71,7 +71,16 @@ int hpfw_gpu_set_filters(hpfw_gpu *h, const float *f)
     if (!h->d_fq_image) HIP_TRY(h->d_fq_image.alloc(image.size()));
     HIP_TRY(hipMemcpy(h->d_fq_image.get(), image.data(), image.size(), hipMemcpyHostToDevice));
     h->shift_images_of.clear();
+    h->filters.assign(f, f + (size_t)hpfw::kFilters * hpfw::kFrame);
     h->has_filters = true;
+    return 0;
+}
+
+int hpfw_gpu_get_filters(hpfw_gpu *h, float *out)
+{
+    if (!h || !out) return fail(HPFW_E_INVALID, "null argument");
+    if (!h->has_filters) return fail(HPFW_E_NOFILTERS, "no filters: call hpfw_gpu_set_filters or hpfw_gpu_learn_filters first");
+    std::memcpy(out, h->filters.data(), h->filters.size() * sizeof(float));
     return 0;
 }
 

@@ -366,6 +366,11 @@ void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, vo
 // moments n, sum d, sum d^2 of d = best >> 32 over the clips with db_off[c + 1] - db_off[c] >= q_off[q + 1] - q_off[q] >= 1
 void launch_dist_stats(const uint64_t *d_best, const int64_t *d_db_off, const int64_t *d_q_off, int n_q, int n_clips, void *d_stats,
                        hipStream_t s);
+// a sharded search's gathered results (k_merge.hip): per-shard top-k lists in [n_shards][n_q][k] of 16-byte
+// records keyed (dist, clip) (hpfw_hit or hpfw_shift_hit) -> out [n_q][k], as hpfw_gpu_merge_topk orders them; n_shards k <= 4096
+void launch_topk_merge_shards(const void *d_in, int n_shards, int64_t n_q, int k, void *d_out, hipStream_t s);
+// d_out[r] = sum over the shards of d_in[shard][r] (hpfw_dist_stats), r < rows
+void launch_sum_stats(const void *d_in, int n_shards, int64_t rows, void *d_out, hipStream_t s);
 // windows of one recording (k_windows.hip): window i of d_src is samples [i hop, i hop + win) -> d_dst [n_w][win]
 void launch_gather_windows(const int16_t *d_src, int64_t hop, int64_t win, int64_t n_w, int16_t *d_dst, hipStream_t s);
 

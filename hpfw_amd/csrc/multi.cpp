@@ -19,6 +19,7 @@
 
 #include "../../include/hpfw_gpu_multi.h"
 #include "../../include/hpfw_gpu_multi_resample.h"
+#include "../../include/hpfw_gpu_multi_search.h"
 #include "legacy_internal.h"
 
 namespace {
@@ -46,6 +47,10 @@ struct Dev {
     hipStream_t stream = nullptr;
     hpfw_hit *d_send = nullptr, *d_recv = nullptr;
     size_t send_cap = 0, recv_cap = 0;
+    // device 0 of a key, tempo or scored search: the merged hits and summed moments, and (several devices) the gathered
+    // regions packed shard after shard
+    void *d_merged = nullptr, *d_pack = nullptr;
+    size_t merged_cap = 0, pack_cap = 0;
     std::vector<int> shards;
 };
 
@@ -217,6 +222,8 @@ void hpfw_gpu_group_destroy(hpfw_gpu_group *g)
         if (d.comm) (void)ncclCommDestroy(d.comm);
         if (d.d_send) (void)hipFree(d.d_send);
         if (d.d_recv) (void)hipFree(d.d_recv);
+        if (d.d_merged) (void)hipFree(d.d_merged);
+        if (d.d_pack) (void)hipFree(d.d_pack);
         if (d.stream) (void)hipStreamDestroy(d.stream);
     }
     for (hpfw_legacy_collector *c : g->collectors) par_collector_del(c);
@@ -340,6 +347,181 @@ int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const in
         HIP_OK(hipStreamSynchronize(g->devs[(size_t)i].stream), "all-gather");
     }
     return hpfw_gpu_merge_topk(all.data(), n, n_q, k, out);
+}
+
+// ---- key, tempo and scored searches over the shards (include/hpfw_gpu_multi_search.h) --------
+namespace {
+
+// One body for the three searches: n_sets = 0 is the plain search (one query set per query, hpfw_hit), n_sets >= 1 the
+// transposed one (hpfw_shift_hit); stats non-null asks for the moments.  Every device's send buffer is
+// [local shard][n_q][k] hits, then [local shard][rows] moments; the gathered buffer holds one such region per device.
+int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_sets, int k, void *out,
+                 hpfw_dist_stats *stats)
+{
+    const bool transposed = n_sets > 0;
+    const int64_t rows = n_q * (transposed ? n_sets : 1); // query sets
+    const int64_t total = q_off[rows] - q_off[0];
+    if (total < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+    if (total > 0 && !q_hp) return fail(HPFW_E_INVALID, "null queries");
+    std::vector<int64_t> rel((size_t)rows + 1);
+    int64_t k_max = 0;
+    for (int64_t i = 0; i <= rows; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    for (int64_t i = 0; i < rows; ++i) {
+        if (rel[(size_t)i + 1] < rel[(size_t)i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        k_max = std::max(k_max, rel[(size_t)i + 1] - rel[(size_t)i]);
+    }
+    // the limits of the one-handle call on the unsharded index: a shard sees only its own block of clips, and the sum
+    // of the shards' rows must not wrap where the unsharded row would be refused
+    if (g->n_clips > 0 && k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    if (stats && (unsigned __int128)g->n_clips * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
+        return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
+    const int n = (int)g->shards.size(), m = (int)g->devs.size();
+    const size_t list = (size_t)n_q * k * sizeof(hpfw_hit);                  // bytes of hits per shard
+    const size_t srows = stats ? (size_t)rows * sizeof(hpfw_dist_stats) : 0; // bytes of moments per shard
+    const size_t hits_dev = list * g->per_dev, stats_dev = srows * g->per_dev;
+    const size_t send = (hits_dev + stats_dev + 15) / 16 * 16; // a device's region of the gathered buffer stays 16-byte aligned
+    for (Dev &d : g->devs) {
+        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
+        int rc = grow((void **)&d.d_send, &d.send_cap, send);
+        if (!rc) rc = grow((void **)&d.d_recv, &d.recv_cap, send * m);
+        if (rc) return rc;
+    }
+    Dev &d0 = g->devs[0];
+    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+    int rc = grow(&d0.d_merged, &d0.merged_cap, list + srows);
+    if (!rc && m > 1) rc = grow(&d0.d_pack, &d0.pack_cap, (hits_dev + stats_dev) * m);
+    if (rc) return rc;
+    // 1. every shard: replicated queries in, its own search into its slots of the device's send buffer
+    rc = per_shard(g, [&](int i) {
+        Shard &s = g->shards[(size_t)i];
+        Dev &d = g->devs[(size_t)s.dev_slot];
+        int r = grow((void **)&s.d_q, &s.q_cap, (size_t)std::max<int64_t>(total, 1) * 8);
+        if (r) return r;
+        if (total && hipMemcpyAsync(s.d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice, s.stream) != hipSuccess)
+            return fail(HPFW_E_HIP, "H2D copy of the queries failed");
+        char *base = reinterpret_cast<char *>(d.d_send);
+        void *hits = base + (size_t)s.local * list;
+        hpfw_dist_stats *st = stats ? reinterpret_cast<hpfw_dist_stats *>(base + hits_dev + (size_t)s.local * srows) : nullptr;
+        if (transposed)
+            r = st ? hpfw_gpu_search_topk_transposed_scored_device(s.h, s.d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, st, s.stream)
+                   : hpfw_gpu_search_topk_transposed_device(s.h, s.d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, s.stream);
+        else
+            r = st ? hpfw_gpu_search_topk_scored_device(s.h, s.d_q, rel.data(), n_q, k, (hpfw_hit *)hits, st, s.stream)
+                   : hpfw_gpu_search_topk_device(s.h, s.d_q, rel.data(), n_q, k, (hpfw_hit *)hits, s.stream);
+        if (r) return r;
+        if (hipEventRecord(s.done, s.stream) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
+        return 0;
+    });
+    if (rc) return rc;
+    // 2. the exchange step: one all-gather of a device's hits and moments
+    for (Dev &d : g->devs) {
+        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
+        for (int si : d.shards) HIP_OK(hipStreamWaitEvent(d.stream, g->shards[(size_t)si].done, 0), "hipStreamWaitEvent");
+    }
+    NCCL_OK(ncclGroupStart(), "ncclGroupStart");
+    for (Dev &d : g->devs) {
+        ncclResult_t r = ncclAllGather(d.d_send, d.d_recv, send, ncclUint8, d.comm, d.stream);
+        if (r != ncclSuccess) {
+            (void)ncclGroupEnd();
+            return fail(HPFW_E_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
+        }
+    }
+    NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
+    // 3. device 0 merges the n lists and sums the n rows where they lie; the host takes n_q k hits and the rows.
+    //    One device: its region is already in[shard][q][k] and in[shard][row]; several: the regions' halves are packed first.
+    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+    const char *recv = reinterpret_cast<const char *>(d0.d_recv);
+    const char *hits_in = recv, *stats_in = recv + hits_dev;
+    if (m > 1) {
+        char *pack = reinterpret_cast<char *>(d0.d_pack);
+        for (int i = 0; i < m; ++i) {
+            HIP_OK(hipMemcpyAsync(pack + (size_t)i * hits_dev, recv + (size_t)i * send, hits_dev, hipMemcpyDeviceToDevice, d0.stream),
+                   "packing the gathered lists");
+            if (stats_dev)
+                HIP_OK(hipMemcpyAsync(pack + (size_t)m * hits_dev + (size_t)i * stats_dev, recv + (size_t)i * send + hits_dev, stats_dev,
+                                      hipMemcpyDeviceToDevice, d0.stream),
+                       "packing the gathered moments");
+        }
+        hits_in = pack;
+        stats_in = pack + (size_t)m * hits_dev;
+    }
+    hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h;
+    char *merged = reinterpret_cast<char *>(d0.d_merged);
+    if ((rc = hpfw_gpu_merge_topk_device(h0, hits_in, n, n_q, k, merged, d0.stream))) return rc;
+    if (stats && (rc = hpfw_gpu_sum_stats_device(h0, reinterpret_cast<const hpfw_dist_stats *>(stats_in), n, rows,
+                                                 reinterpret_cast<hpfw_dist_stats *>(merged + list), d0.stream)))
+        return rc;
+    HIP_OK(hipMemcpyAsync(out, merged, list, hipMemcpyDeviceToHost, d0.stream), "D2H copy of the merged lists");
+    if (stats) HIP_OK(hipMemcpyAsync(stats, merged + list, srows, hipMemcpyDeviceToHost, d0.stream), "D2H copy of the moments");
+    for (int i = 0; i < m; ++i) {
+        HIP_OK(hipSetDevice(g->devs[(size_t)i].device), "hipSetDevice");
+        HIP_OK(hipStreamSynchronize(g->devs[(size_t)i].stream), "all-gather");
+    }
+    return 0;
+}
+
+// the argument checks of the one-handle functions, before the group or any device is touched
+int group_search_checked(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_sets, bool transposed,
+                         int k, void *out, hpfw_dist_stats *stats, bool scored)
+{
+    if (scored && !stats) return fail(HPFW_E_INVALID, "null stats");
+    if (transposed && (n_sets < 1 || n_sets > 64)) return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    if (!g || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    if (n_q == 0) return 0;
+    return group_search(g, q_hp, q_off, n_q, transposed ? n_sets : 0, k, out, scored ? stats : nullptr);
+}
+
+} // namespace
+
+int hpfw_gpu_group_search_topk_scored(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out,
+                                      hpfw_dist_stats *stats)
+{
+    return group_search_checked(g, q_hp, q_off, n_q, 0, false, k, out, stats, true);
+}
+
+int hpfw_gpu_group_search_topk_transposed(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                          hpfw_shift_hit *out)
+{
+    return group_search_checked(g, q_hp, q_off, n_q, n_shifts, true, k, out, nullptr, false);
+}
+
+int hpfw_gpu_group_search_topk_transposed_scored(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
+                                                 int k, hpfw_shift_hit *out, hpfw_dist_stats *stats)
+{
+    return group_search_checked(g, q_hp, q_off, n_q, n_shifts, true, k, out, stats, true);
+}
+
+int hpfw_gpu_group_extract_windows_pcm16(hpfw_gpu_group *g, const int16_t *pcm, int64_t n_total, int64_t win, int64_t hop,
+                                         const float *tempos, int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp)
+{
+    if (!g) return fail(HPFW_E_INVALID, "null group");
+    hpfw_gpu *h0 = g->shards[0].h;
+    // the one-handle call's checks (lists, projection mode, window and hop, a window too short for the slowest tempo), made
+    // once: over no samples it checks everything and extracts nothing
+    int rc = hpfw_gpu_extract_windows_pcm16_host(h0, nullptr, 0, win, hop, tempos, n_tempos, shifts, n_shifts, nullptr);
+    if (rc) return rc;
+    int64_t n_w = 0;
+    if ((rc = hpfw_gpu_window_count(n_total, win, hop, &n_w))) return rc;
+    if (n_w == 0) return 0;
+    if (!pcm || !hp) return fail(HPFW_E_INVALID, "bad argument");
+    hpfw_geometry geo;
+    if ((rc = hpfw_gpu_geometry(h0, win, &geo))) return rc;
+    int64_t n_hp = geo.n_hp;
+    if (tempos) {
+        int64_t c_t = 0;
+        if ((rc = hpfw_gpu_tempo_columns(geo.c, tempos, n_tempos, &c_t))) return rc;
+        n_hp = c_t - (HPFW_CONTEXT - 1) - HPFW_LAG;
+    }
+    const int64_t per_window = (int64_t)(tempos ? n_tempos : 1) * std::max(n_shifts, 1) * n_hp;
+    const int n = (int)g->shards.size();
+    return per_shard(g, [&](int i) {
+        int64_t lo, hi;
+        hpfw_gpu_shard_range(n_w, i, n, &lo, &hi);
+        if (hi == lo) return 0;
+        return hpfw_gpu_extract_windows_pcm16_host(g->shards[(size_t)i].h, pcm + lo * hop, (hi - 1 - lo) * hop + win, win, hop, tempos,
+                                                   n_tempos, shifts, n_shifts, hp + lo * per_window);
+    });
 }
 
 int hpfw_gpu_group_cov_reset(hpfw_gpu_group *g)

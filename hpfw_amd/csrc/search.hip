@@ -561,4 +561,46 @@ int hpfw_gpu_merge_topk(const hpfw_hit *in, int n_shards, int64_t n_q, int k, hp
     return 0;
 }
 
+// one kernel serves both kinds of hit: the key (dist, clip) is the first two words of either, the rest is payload
+static_assert(sizeof(hpfw_hit) == 16 && sizeof(hpfw_shift_hit) == 16, "the merge kernel moves 16-byte records");
+static_assert(offsetof(hpfw_hit, dist) == 0 && offsetof(hpfw_hit, clip) == 4 && offsetof(hpfw_shift_hit, dist) == 0 &&
+                  offsetof(hpfw_shift_hit, clip) == 4,
+              "the merge kernel reads the key (dist, clip) from the first two words");
+static_assert(sizeof(hpfw_dist_stats) == 24 && offsetof(hpfw_dist_stats, sum_sq) == 8 && offsetof(hpfw_dist_stats, n) == 16,
+              "the sum kernel reads rows of 24 bytes");
+
+int hpfw_gpu_merge_topk_device(hpfw_gpu *h, const void *d_in, int n_shards, int64_t n_q, int k, void *d_out, void *stream)
+{
+    if (!h || !d_in || !d_out || n_shards < 1 || n_shards > 64 || n_q < 0 || n_q > 0x7fffffff || ((uintptr_t)d_in | (uintptr_t)d_out) % 16)
+        return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        {
+            Timed t(h, K_TOPK, s);
+            hpfw::launch_topk_merge_shards(d_in, n_shards, n_q, k, d_out, s);
+        }
+        return check_launch("topk_merge_shards");
+    });
+}
+
+int hpfw_gpu_sum_stats_device(hpfw_gpu *h, const hpfw_dist_stats *d_in, int n_shards, int64_t rows, hpfw_dist_stats *d_out, void *stream)
+{
+    if (!h || !d_in || !d_out || n_shards < 1 || n_shards > 64 || rows < 0 || rows > (int64_t)0x7fffffff * 256 ||
+        ((uintptr_t)d_in | (uintptr_t)d_out) % 8)
+        return fail(HPFW_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    return ordered_call(h, s, [&] {
+        if (rows == 0) return 0;
+        {
+            Timed t(h, K_TOPK, s);
+            hpfw::launch_sum_stats(d_in, n_shards, rows, d_out, s);
+        }
+        return check_launch("sum_stats");
+    });
+}
+
 } // extern "C"

@@ -41,6 +41,29 @@ def allgather_topk(local_hits, k, group=None, device=None):
     return _lib.merge_topk(per_shard, k)
 
 
+def allgather_topk_scored(local_hits, local_stats, k, group=None, device=None):
+    """the scored search over ranks: local_hits as allgather_topk takes them (HIT_DTYPE, or
+    SHIFT_HIT_DTYPE of a transposed search: the same 16 bytes, merged by (dist, clip) all the same), local_stats the rank's
+    STATS_DTYPE rows of any shape.  Returns (merged hits, summed rows), identical on every rank.  The moments are exact
+    integers and additive over the shards: they travel as int64 and one all-reduce sums them; two's-complement wrap-around is
+    the uint64 sum."""
+    import torch
+    import torch.distributed as dist
+    dtype = np.asarray(local_hits).dtype if np.asarray(local_hits).dtype == _lib.SHIFT_HIT_DTYPE else _lib.HIT_DTYPE
+    merged = allgather_topk(np.ascontiguousarray(local_hits, dtype).view(_lib.HIT_DTYPE), k, group, device).view(dtype)
+    st = np.ascontiguousarray(local_stats, _lib.STATS_DTYPE)
+    m = np.stack([st["sum"].view(np.int64), st["sum_sq"].view(np.int64), st["n"].astype(np.int64)], -1)
+    t = torch.from_numpy(np.ascontiguousarray(m))
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, group=group)
+    m = t.cpu().numpy()
+    out = np.zeros(st.shape, _lib.STATS_DTYPE)
+    out["sum"], out["sum_sq"] = m[..., 0].view(np.uint64), m[..., 1].view(np.uint64)
+    out["n"] = (m[..., 2] & 0xFFFFFFFF).astype(np.uint32)
+    return merged, out
+
+
 def _all_gather_list(out, t, group):
     import torch.distributed as dist
     parts = [out[i] for i in range(out.shape[0])]

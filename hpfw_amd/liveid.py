@@ -16,14 +16,46 @@ from . import _lib
 from .collector import ParallelCollector
 
 
+class _ShardedIndex:
+    """what LiveSongIdentification asks of its index handle, over a hpfw_amd.multi.GpuGroup: the index sharded over the
+    given devices (one ordinal per shard), every search and its result as the one handle's"""
+
+    def __init__(self, devices):
+        from . import multi
+        self.group = multi.GpuGroup(devices)
+        self._first = _lib.Gpu.from_handle(self.group.handle(0))
+        for name in ("index_offsets", "search_topk", "search_topk_scored", "search_topk_transposed",
+                     "search_topk_transposed_scored"):
+            setattr(self, name, getattr(self.group, name))
+        self.geometry, self.resample = self._first.geometry, self._first.resample
+
+    def index_clear(self):
+        self.group.index_build(np.zeros(1, np.uint64), np.zeros(1, np.int64))
+
+    def index_add(self, hp, offsets):
+        self.group.index_build(hp, offsets)               # (build() clears first: the one add is the whole index)
+
+    def extract_windows(self, extractor, pcm, win, hop, tempos, shifts):
+        """the windows sharded over the group, under the filters and the projection mode of `extractor`"""
+        self.group.set_filters(extractor.get_filters())
+        for i in range(self.group.shards):
+            _lib.Gpu.from_handle(self.group.handle(i)).set_projection(extractor.get_projection())
+        return self.group.extract_windows(pcm, win, hop, tempos, shifts)
+
+    def close(self):
+        self.group.close()
+
+
 class LiveSongIdentification:
-    def __init__(self, cache: str = "", device: int = 0, resample: bool = False):
-        """resample: index and search WAV files at any rate in [8 000, 192 000] Hz (ParallelCollector(resample=True))"""
+    def __init__(self, cache: str = "", device: int = 0, resample: bool = False, devices: Optional[Sequence[int]] = None):
+        """resample: index and search WAV files at any rate in [8 000, 192 000] Hz (ParallelCollector(resample=True));
+        devices: one device ordinal per shard (an ordinal may repeat) -- the index is sharded over them and top(), search()
+        and timeline() give what they give on one device; None: one handle on `device`"""
         self.collector = ParallelCollector(resample=resample)
         self._resample = resample
         self.collector.load(cache)                       # the constructor loads the cache, live_song_id.h:24
         self._cache = cache
-        self._gpu = _lib.Gpu(device)
+        self._gpu = _lib.Gpu(device) if devices is None else _ShardedIndex(list(devices))
         self.names: List[str] = []
 
     def close(self):
@@ -147,7 +179,10 @@ class LiveSongIdentification:
             raise
         if _lib.window_count(x.size, win, hop) == 0:
             return empty
-        hp = extractor.extract_windows(x, win, hop, tempos, shifts)
+        if isinstance(self._gpu, _ShardedIndex):
+            hp = self._gpu.extract_windows(extractor, x, win, hop, tempos, shifts)
+        else:
+            hp = extractor.extract_windows(x, win, hop, tempos, shifts)
         n_w, k_q = hp.shape[0], hp.shape[-1]
         off = np.arange(n_w * n_sets + 1, dtype=np.int64) * k_q
         if variants:

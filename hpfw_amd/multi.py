@@ -21,6 +21,11 @@ EXPORTS = (
 )
 # include/hpfw_gpu_multi_resample.h
 RESAMPLE_EXPORTS = ("hpfw_gpu_group_set_resample",)
+# include/hpfw_gpu_multi_search.h
+SEARCH_EXPORTS = (
+    "hpfw_gpu_group_search_topk_scored", "hpfw_gpu_group_search_topk_transposed",
+    "hpfw_gpu_group_search_topk_transposed_scored", "hpfw_gpu_group_extract_windows_pcm16",
+)
 
 _multi = None
 
@@ -61,6 +66,10 @@ def lib():
     L.hpfw_gpu_group_calc_hashprint.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
     L.hpfw_gpu_group_calc_hashprint.restype = ctypes.POINTER(ctypes.c_uint64)
     L.hpfw_gpu_group_set_resample.argtypes = [vp, i32]
+    L.hpfw_gpu_group_search_topk_scored.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    L.hpfw_gpu_group_search_topk_transposed.argtypes = [vp, vp, vp, i64, i32, i32, vp]
+    L.hpfw_gpu_group_search_topk_transposed_scored.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    L.hpfw_gpu_group_extract_windows_pcm16.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp]
     _multi = L
     return L
 
@@ -76,6 +85,7 @@ class GpuGroup:
 
     def __init__(self, devices=None):
         self._g = ctypes.c_void_p()
+        self._offsets = np.zeros(1, np.int64)
         if devices is None:
             _lib.check(lib().hpfw_gpu_group_create_env(ctypes.byref(self._g)))
         else:
@@ -123,6 +133,11 @@ class GpuGroup:
         hp = np.ascontiguousarray(hp, np.uint64).ravel()
         off = np.ascontiguousarray(offsets, np.int64)
         _lib.check(lib().hpfw_gpu_group_index_build(self._g, _lib._hp(hp), _lib._hp(off), off.size - 1))
+        self._offsets = off - off[0]
+
+    def index_offsets(self):
+        """the clip offsets int64 [n_clips + 1] of the index as index_build last took it, from 0 (as Gpu.index_offsets)"""
+        return self._offsets.copy()
 
     def search_topk(self, q_hp, q_off, k):
         q = np.ascontiguousarray(q_hp, np.uint64).ravel()
@@ -130,6 +145,52 @@ class GpuGroup:
         out = np.zeros((off.size - 1, k), _lib.HIT_DTYPE)
         _lib.check(lib().hpfw_gpu_group_search_topk(self._g, _lib._hp(q), _lib._hp(off), off.size - 1, int(k), _lib._hp(out)))
         return out
+
+    # ---- key, tempo and scored searches, windows (include/hpfw_gpu_multi_search.h): what their Gpu namesakes return
+    def search_topk_scored(self, q_hp, q_off, k):
+        """(HIT_DTYPE [n_q][k], STATS_DTYPE [n_q])"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        out = np.zeros((off.size - 1, k), _lib.HIT_DTYPE)
+        stats = np.zeros(off.size - 1, _lib.STATS_DTYPE)
+        _lib.check(lib().hpfw_gpu_group_search_topk_scored(self._g, _lib._hp(q), _lib._hp(off), off.size - 1, int(k), _lib._hp(out),
+                                                           _lib._hp(stats)))
+        return out, stats
+
+    def _transposed(self, q_hp, q_off, n_shifts, k, scored):
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        if n_shifts < 1 or (off.size - 1) % n_shifts:
+            raise ValueError("q_off must hold n_q * n_shifts + 1 offsets")
+        n_q = (off.size - 1) // n_shifts
+        out = np.zeros((n_q, k), _lib.SHIFT_HIT_DTYPE)
+        if not scored:
+            _lib.check(lib().hpfw_gpu_group_search_topk_transposed(self._g, _lib._hp(q), _lib._hp(off), n_q, int(n_shifts), int(k),
+                                                                   _lib._hp(out)))
+            return out
+        stats = np.zeros((n_q, n_shifts), _lib.STATS_DTYPE)
+        _lib.check(lib().hpfw_gpu_group_search_topk_transposed_scored(self._g, _lib._hp(q), _lib._hp(off), n_q, int(n_shifts), int(k),
+                                                                      _lib._hp(out), _lib._hp(stats)))
+        return out, stats
+
+    def search_topk_transposed(self, q_hp, q_off, n_shifts, k):
+        """q_off [n_q * n_shifts + 1] -> SHIFT_HIT_DTYPE [n_q][k]"""
+        return self._transposed(q_hp, q_off, n_shifts, k, False)
+
+    def search_topk_transposed_scored(self, q_hp, q_off, n_shifts, k):
+        """(SHIFT_HIT_DTYPE [n_q][k], STATS_DTYPE [n_q][n_shifts])"""
+        return self._transposed(q_hp, q_off, n_shifts, k, True)
+
+    def extract_windows(self, pcm, win, hop, tempos=None, shifts=None):
+        """Gpu.extract_windows with the windows sharded: uint64 [n_w][n_hp], or [n_w][V][n_hp_v] with shifts and / or tempos"""
+        pcm = np.ascontiguousarray(pcm, np.int16).ravel()
+        shape = _lib.Gpu.from_handle(self.handle(0))._windows_shape(pcm.size, win, hop, tempos, shifts)
+        n_w, sets, nhp, t, (keep, sp, ns) = shape
+        hp = np.zeros((n_w, sets, nhp), np.uint64)
+        _lib.check(lib().hpfw_gpu_group_extract_windows_pcm16(self._g, _lib._hp(pcm), pcm.size, int(win), int(hop),
+                                                              None if t is None else _lib._hp(t), 0 if t is None else t.size, sp, ns,
+                                                              _lib._hp(hp) if hp.size else None))
+        return hp if (tempos is not None or shifts is not None) else hp[:, 0, :]
 
     def cov_reset(self):
         _lib.check(lib().hpfw_gpu_group_cov_reset(self._g))

@@ -8,6 +8,9 @@
 // are merged by (distance, track id): the answer is the one GpuStorage gives on the unsharded index, for any
 // number of shards.  Header-only; the work is done by libhpfw_gpu_multi.so (include/hpfw_gpu_multi.h).
 //
+// The finds of a query in another key or at another tempo (transposed.h, tempo.h) and the scored searches behind
+// hpfw::timeline (timeline.h) are here too, over include/hpfw_gpu_multi_search.h: same names and result types as GpuStorage's.
+//
 // Placement: HPFW_GPU_DEVICES="0,1,2,3,4,5,6,7" (one ordinal per shard; default: every visible device), or
 // the explicit constructor.
 #pragma once
@@ -19,6 +22,7 @@
 #include <vector>
 
 #include "../../hpfw_gpu_multi.h"
+#include "../../hpfw_gpu_multi_search.h"
 
 namespace hpfw::db {
 
@@ -53,6 +57,41 @@ public:
             off.push_back((int64_t)all.size());
         }
         check(hpfw_gpu_group_index_build(g_, all.empty() ? &dummy_ : all.data(), off.data(), (int64_t)names_.size()));
+        off_ = off;
+    }
+
+    /// the group that holds the shards, the names of the clips in index order and their offsets [size() + 1] (hpfw::timeline,
+    /// timeline.h, searches a sharded storage through these)
+    hpfw_gpu_group *group() const { return g_; }
+    const std::vector<std::string> &names() const { return names_; }
+    const std::vector<int64_t> &index_offsets() const { return off_; }
+
+    /// GpuStorage::find_topk_transposed over the shards: per_shift[i] holds the query's hashprints under variant i
+    /// (hpfw::transposed_hashprints, hpfw::tempo_hashprints); per clip the smallest distance over the variants, ties to the
+    /// first; the k best clips by (distance, position in the database) with the index of their variant
+    struct ShiftResult {
+        std::string filename;
+        size_t cnt;
+        int64_t offset;
+        int shift_index;
+    };
+    auto find_topk_transposed(const std::vector<typename Collector::Hashprint> &per_shift, int k) const -> std::vector<ShiftResult>
+    {
+        std::vector<ShiftResult> out;
+        if (per_shift.empty() || names_.empty()) return out;
+        std::vector<uint64_t> all;
+        std::vector<int64_t> off{0};
+        for (const auto &hp : per_shift) {
+            all.insert(all.end(), hp.begin(), hp.end());
+            off.push_back((int64_t)all.size());
+        }
+        std::vector<hpfw_shift_hit> hits((size_t)k);
+        check(hpfw_gpu_group_search_topk_transposed(g_, all.empty() ? &dummy_ : all.data(), off.data(), 1, (int)per_shift.size(), k, hits.data()));
+        for (const hpfw_shift_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            out.push_back({names_[hit.clip], (size_t)hit.dist, (int64_t)hit.offset, (int)hit.shift_index});
+        }
+        return out;
     }
 
     /// storage.h:27-64: the first strict minimum in database order
@@ -108,6 +147,7 @@ private:
     }
     hpfw_gpu_group *g_ = nullptr;
     std::vector<std::string> names_;
+    std::vector<int64_t> off_{0};
     mutable uint64_t dummy_ = 0;
 };
 

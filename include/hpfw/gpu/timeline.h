@@ -2,7 +2,9 @@
 // handle `h` (which holds the index's filters), each searched in a GpuStorage for its best clip and scored by how far that
 // clip stands out from the others (hpfw_gpu_hit_score), and the windows that name one clip at consistent offsets joined into
 // segments (hpfw_gpu_timeline_segments).  With tempos and / or shifts every window is searched under every variant, as
-// tempo.h / transposed.h describe them; projection mode 1 then.
+// tempo.h / transposed.h describe them; projection mode 1 then.  A ShardedGpuStorage (sharded_storage.h) in place of the
+// GpuStorage gives the same timeline from an index sharded over several devices: the windows are hashed on its shards under
+// h's filters and the searches are the group's (include/hpfw_gpu_multi_search.h).
 #pragma once
 
 #include <algorithm>
@@ -14,6 +16,7 @@
 #include <vector>
 
 #include "../../hpfw_gpu.h"
+#include "../../hpfw_gpu_multi_search.h" // (declarations only: a program that uses no sharded storage links libhpfw_gpu alone)
 
 namespace hpfw {
 
@@ -49,6 +52,7 @@ template <typename Storage>
 Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, const TimelineOptions &opt)
 {
     auto fail = [](const char *what) { throw std::runtime_error(std::string("hpfw::timeline: ") + what + ": " + hpfw_gpu_last_error()); };
+    constexpr bool sharded = requires { storage.group(); };
     int64_t n = 0, n_w = 0;
     if (hpfw_gpu_window_count(0, opt.win, opt.hop, &n_w) != 0) fail("windows");
     if (hpfw_gpu_wav_read_pcm16(path.c_str(), nullptr, 0, &n) != 0) fail(path.c_str());
@@ -69,24 +73,39 @@ Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, 
     const int sets = (int)std::max<size_t>(opt.tempos.size(), 1) * n_s;
     const bool variants = !opt.tempos.empty() || !opt.shifts.empty();
     std::vector<uint64_t> hp((size_t)(n_w * sets * nhp));
-    if (hpfw_gpu_extract_windows_pcm16_host(h, pcm.data(), n, opt.win, opt.hop, opt.tempos.empty() ? nullptr : opt.tempos.data(),
-                                            (int)opt.tempos.size(), opt.shifts.empty() ? nullptr : opt.shifts.data(), (int)opt.shifts.size(),
-                                            hp.data()) != 0)
+    const float *tempos = opt.tempos.empty() ? nullptr : opt.tempos.data();
+    const int32_t *shifts = opt.shifts.empty() ? nullptr : opt.shifts.data();
+    if constexpr (sharded) { // the shards hash the windows, under the extractor's filters and projection mode
+        std::vector<float> filters((size_t)HPFW_FILTERS * HPFW_FRAME_SIZE);
+        if (hpfw_gpu_get_filters(h, filters.data()) != 0 || hpfw_gpu_group_set_filters(storage.group(), filters.data()) != 0) fail("filters");
+        for (int i = 0; i < storage.shards(); ++i)
+            if (hpfw_gpu_set_projection(hpfw_gpu_group_handle(storage.group(), i), hpfw_gpu_get_projection(h)) != 0) fail("projection");
+        if (hpfw_gpu_group_extract_windows_pcm16(storage.group(), pcm.data(), n, opt.win, opt.hop, tempos, (int)opt.tempos.size(), shifts,
+                                                 (int)opt.shifts.size(), hp.data()) != 0)
+            fail("extraction");
+    } else if (hpfw_gpu_extract_windows_pcm16_host(h, pcm.data(), n, opt.win, opt.hop, tempos, (int)opt.tempos.size(), shifts,
+                                                   (int)opt.shifts.size(), hp.data()) != 0)
         fail("extraction");
     std::vector<int64_t> q_off((size_t)(n_w * sets) + 1);
     for (size_t i = 0; i < q_off.size(); ++i) q_off[i] = (int64_t)i * nhp;
     std::vector<hpfw_dist_stats> stats((size_t)(n_w * sets));
     std::vector<hpfw_shift_hit> hits((size_t)n_w);
-    if (variants) {
-        if (hpfw_gpu_search_topk_transposed_scored(storage.handle(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data()) != 0)
-            fail("search");
-    } else {
-        std::vector<hpfw_hit> plain((size_t)n_w);
-        if (hpfw_gpu_search_topk_scored(storage.handle(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data()) != 0) fail("search");
+    std::vector<hpfw_hit> plain(variants ? 0 : (size_t)n_w);
+    int rc;
+    if constexpr (sharded)
+        rc = variants ? hpfw_gpu_group_search_topk_transposed_scored(storage.group(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
+                      : hpfw_gpu_group_search_topk_scored(storage.group(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data());
+    else
+        rc = variants ? hpfw_gpu_search_topk_transposed_scored(storage.handle(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
+                      : hpfw_gpu_search_topk_scored(storage.handle(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data());
+    if (rc != 0) fail("search");
+    if (!variants)
         for (int64_t w = 0; w < n_w; ++w) hits[(size_t)w] = {plain[(size_t)w].dist, plain[(size_t)w].clip, plain[(size_t)w].offset, 0};
-    }
     std::vector<int64_t> db_off(storage.names().size() + 1, 0);
-    if (hpfw_gpu_index_get(storage.handle(), db_off.data(), nullptr, 0) != 0) fail("index");
+    if constexpr (sharded)
+        db_off = storage.index_offsets();
+    else if (hpfw_gpu_index_get(storage.handle(), db_off.data(), nullptr, 0) != 0)
+        fail("index");
     out.windows.resize((size_t)n_w);
     for (int64_t w = 0; w < n_w; ++w) {
         const hpfw_shift_hit &hit = hits[(size_t)w];

@@ -86,6 +86,8 @@ int hpfw_gpu_device(const hpfw_gpu *h); /* the device ordinal the handle was cre
 
 /* filters = ParallelCollector::filters (parallel_collector.h:77), host pointer, 64 x 2420 floats */
 int hpfw_gpu_set_filters(hpfw_gpu *h, const float *filters_colmajor);
+/* the filters the handle holds (set, learned, or read from a cache by its collector), same layout; HPFW_E_NOFILTERS when none */
+int hpfw_gpu_get_filters(hpfw_gpu *h, float *filters_colmajor_out);
 /* the sizes of a clip length (columns, frames, hashprints: cqt.h:66-73, hashprint_handle.h:79-93).  Host arithmetic only:
  * no table of the length is built or uploaded for the question; a length the extraction would refuse (a factor n2 beyond
  * the LDS) is refused here with the same status.  Like every entry point but hpfw_gpu_prepare_length it belongs to the one
@@ -466,6 +468,15 @@ int hpfw_gpu_search_topk_transposed_scored(hpfw_gpu *h, const uint64_t *q_hp, co
  * converted to double once); *score = (m - d) / sqrt(var).  *score is NaN, with status OK, when counted == 0, n < 3 or
  * var == 0.  Moments no set of distances can have (d > sum, d^2 > sum_sq, a negative variance) are HPFW_E_INVALID. */
 int hpfw_gpu_hit_score(uint32_t dist, int counted, const hpfw_dist_stats *s, double *score);
+/* What a sharded search does with the gathered per-shard results, on the device that holds them (include/hpfw_gpu_multi_search.h).
+ * device twin of hpfw_gpu_merge_topk: records are hpfw_hit or hpfw_shift_hit (same 16-byte layout, key (dist, clip)); d_in
+ * [n_shards][n_q][k] -> d_out [n_q][k], bit for bit what hpfw_gpu_merge_topk gives on the same bytes (records of equal key keep
+ * their input order, the words after the key travel with their record).  dist < 2^20, as every search returns it, but for
+ * the padding record dist = clip = 0xffffffff.  n_shards in 1..64, k in 1..64, 16-byte aligned pointers, d_out apart from d_in. */
+int hpfw_gpu_merge_topk_device(hpfw_gpu *h, const void *d_in, int n_shards, int64_t n_q, int k, void *d_out, void *stream);
+/* d_out[r] = sum over shards of d_in[shard][r], r < rows: sum and sum_sq modulo 2^64, n modulo 2^32, pad = 0 */
+int hpfw_gpu_sum_stats_device(hpfw_gpu *h, const hpfw_dist_stats *d_in, int n_shards, int64_t rows, hpfw_dist_stats *d_out,
+                              void *stream);
 
 /* Windows of ONE recording of n_total samples: window w is samples [w hop, w hop + win).  Host only:
  * *n_w = (n_total - win) / hop + 1, 0 when n_total < win.  1 <= hop <= win, win a supported clip length
