@@ -28,6 +28,8 @@ SEGMENT_DTYPE = np.dtype([("clip", "<u4"), ("n_strong", "<i4"), ("first", "<i8")
                           ("end", "<i8"), ("best_window", "<i8"), ("best_score", "<f8"), ("best_tempo", "<f8"),
                           ("best_offset", "<i4"), ("best_variant", "<i4"), ("first_offset", "<i4"), ("pad", "<i4")])
 NO_CLIP = 0xFFFFFFFF
+# live feeds: hpfw_stream_window
+STREAM_WINDOW_DTYPE = np.dtype([("feed", "<i4"), ("pad", "<i4"), ("window", "<i8")])
 
 KERNEL_KINDS = ("fwd_rows", "fwd_cols", "cq_chirpz", "db", "project_mfma", "delta_pack",
                 "hamming_scan", "topk", "pcm_pairs", "fwd_span")
@@ -66,6 +68,11 @@ EXPORTS = (
     "hpfw_gpu_search_topk_transposed_scored", "hpfw_gpu_hit_score", "hpfw_gpu_window_count", "hpfw_gpu_extract_windows_pcm16",
     "hpfw_gpu_extract_windows_pcm16_host", "hpfw_gpu_timeline_segments",
     "hpfw_gpu_merge_topk_device", "hpfw_gpu_sum_stats_device", "hpfw_gpu_get_filters",
+    "hpfw_gpu_streams_create", "hpfw_gpu_streams_destroy", "hpfw_gpu_streams_push", "hpfw_gpu_streams_push_device",
+    "hpfw_gpu_streams_room", "hpfw_gpu_streams_extract", "hpfw_gpu_streams_extract_host", "hpfw_gpu_streams_reset",
+    "hpfw_gpu_streams_info", "hpfw_gpu_timeline_tracker_create", "hpfw_gpu_timeline_tracker_destroy",
+    "hpfw_gpu_timeline_tracker_push", "hpfw_gpu_timeline_tracker_pop", "hpfw_gpu_timeline_tracker_open",
+    "hpfw_gpu_timeline_tracker_finish",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -84,6 +91,18 @@ class TimelineParams(ctypes.Structure):
     """hpfw_timeline_params: min_score is required; tol_cols 0, max_gap -1 and min_windows 0 ask for the defaults"""
     _fields_ = [("min_score", ctypes.c_double), ("hop_cols", ctypes.c_double), ("tol_cols", ctypes.c_double),
                 ("win", ctypes.c_int64), ("hop", ctypes.c_int64), ("max_gap", ctypes.c_int32), ("min_windows", ctypes.c_int32)]
+
+
+class StreamsParams(ctypes.Structure):
+    """hpfw_streams_params: capacity 0 asks for 2 win; tempos / shifts NULL and 0 for none"""
+    _fields_ = [("n_streams", ctypes.c_int32), ("n_tempos", ctypes.c_int32), ("n_shifts", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("win", ctypes.c_int64), ("hop", ctypes.c_int64), ("capacity", ctypes.c_int64), ("tempos", ctypes.c_void_p),
+                ("shifts", ctypes.c_void_p)]
+
+
+class StreamsInfo(ctypes.Structure):
+    _fields_ = [("per_window", ctypes.c_int64), ("win", ctypes.c_int64), ("hop", ctypes.c_int64), ("capacity", ctypes.c_int64),
+                ("n_streams", ctypes.c_int32), ("n_sets", ctypes.c_int32)]
 
 
 class DistStats(ctypes.Structure):
@@ -234,6 +253,23 @@ def lib():
     L.hpfw_gpu_timeline_segments.argtypes = [vp, i64, ctypes.POINTER(TimelineParams), vp, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_merge_topk_device.argtypes = [vp, vp, i32, i64, i32, vp, vp]
     L.hpfw_gpu_sum_stats_device.argtypes = [vp, vp, i32, i64, vp, vp]
+    L.hpfw_gpu_streams_create.argtypes = [vp, ctypes.POINTER(StreamsParams), ctypes.POINTER(vp)]
+    L.hpfw_gpu_streams_destroy.argtypes = [vp]
+    L.hpfw_gpu_streams_destroy.restype = None
+    L.hpfw_gpu_streams_push.argtypes = [vp, vp, vp, ctypes.POINTER(i64)]
+    L.hpfw_gpu_streams_push_device.argtypes = [vp, vp, vp, ctypes.POINTER(i64), vp]
+    L.hpfw_gpu_streams_room.argtypes = [vp, vp]
+    L.hpfw_gpu_streams_extract.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64), vp]
+    L.hpfw_gpu_streams_extract_host.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.hpfw_gpu_streams_reset.argtypes = [vp, i32]
+    L.hpfw_gpu_streams_info.argtypes = [vp, ctypes.POINTER(StreamsInfo), vp, vp]
+    L.hpfw_gpu_timeline_tracker_create.argtypes = [ctypes.POINTER(TimelineParams), ctypes.POINTER(vp)]
+    L.hpfw_gpu_timeline_tracker_destroy.argtypes = [vp]
+    L.hpfw_gpu_timeline_tracker_destroy.restype = None
+    L.hpfw_gpu_timeline_tracker_push.argtypes = [vp, vp, i64]
+    L.hpfw_gpu_timeline_tracker_pop.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_timeline_tracker_open.argtypes = [vp, vp, ctypes.POINTER(i32)]
+    L.hpfw_gpu_timeline_tracker_finish.argtypes = [vp]
     L.par_collector_new.restype = vp
     L.par_collector_del.argtypes = [vp]
     L.par_collector_del.restype = None
@@ -321,16 +357,69 @@ def timeline_segments(windows, min_score, hop_cols, win, hop, tol_cols=None, max
     """WINDOW_HIT_DTYPE [n_w] -> SEGMENT_DTYPE [n_seg] by the rule of include/hpfw_gpu.h (hpfw_gpu_timeline_segments);
     tol_cols None = the default max(2, 0.08 hop_cols)"""
     w = np.ascontiguousarray(windows, WINDOW_HIT_DTYPE).ravel()
-    p = TimelineParams(float(min_score), float(hop_cols), 0.0 if tol_cols is None else float(tol_cols), int(win), int(hop),
-                       int(max_gap), int(min_windows))
-    if tol_cols is not None and not tol_cols > 0:
-        raise ValueError("tol_cols must be positive")
-    if max_gap < 0 or min_windows < 1:
-        raise ValueError("max_gap >= 0 and min_windows >= 1")
+    p = _timeline_params(min_score, hop_cols, win, hop, tol_cols, max_gap, min_windows)
     out = np.zeros(max(w.size, 1), SEGMENT_DTYPE)
     n = ctypes.c_int64()
     check(lib().hpfw_gpu_timeline_segments(_hp(w) if w.size else None, w.size, ctypes.byref(p), _hp(out), out.size, ctypes.byref(n)))
     return out[:n.value].copy()
+
+
+def _timeline_params(min_score, hop_cols, win, hop, tol_cols, max_gap, min_windows):
+    if tol_cols is not None and not tol_cols > 0:
+        raise ValueError("tol_cols must be positive")
+    if max_gap < 0 or min_windows < 1:
+        raise ValueError("max_gap >= 0 and min_windows >= 1")
+    return TimelineParams(float(min_score), float(hop_cols), 0.0 if tol_cols is None else float(tol_cols), int(win), int(hop),
+                          int(max_gap), int(min_windows))
+
+
+class TimelineTracker:
+    """hpfw_gpu_timeline_segments as the windows arrive (hpfw_timeline_tracker): push() window rows,
+    pop() the segments nothing can continue any more, open() the one in progress, finish() at the end of the feed"""
+
+    def __init__(self, min_score, hop_cols, win, hop, tol_cols=None, max_gap=1, min_windows=1):
+        p = _timeline_params(min_score, hop_cols, win, hop, tol_cols, max_gap, min_windows)
+        self._t = ctypes.c_void_p()
+        check(lib().hpfw_gpu_timeline_tracker_create(ctypes.byref(p), ctypes.byref(self._t)))
+
+    def push(self, windows):
+        w = np.ascontiguousarray(windows, WINDOW_HIT_DTYPE).ravel()
+        check(lib().hpfw_gpu_timeline_tracker_push(self._t, _hp(w) if w.size else None, w.size))
+
+    def pop(self, cap=None):
+        """the closed segments not yet popped, oldest first (at most cap of them): SEGMENT_DTYPE [n]"""
+        got, left = [], (None if cap is None else int(cap))
+        chunk = np.zeros(16, SEGMENT_DTYPE)
+        n = ctypes.c_int64()
+        while left is None or left > 0:
+            want = chunk.size if left is None else min(chunk.size, left)
+            check(lib().hpfw_gpu_timeline_tracker_pop(self._t, _hp(chunk), want, ctypes.byref(n)))
+            got.append(chunk[:n.value].copy())
+            left = None if left is None else left - n.value
+            if n.value < want:
+                break
+        return np.concatenate(got) if got else np.zeros(0, SEGMENT_DTYPE)
+
+    def open(self):
+        """the segment in progress as it would close now (a SEGMENT_DTYPE record), or None"""
+        cur = np.zeros(1, SEGMENT_DTYPE)
+        has = ctypes.c_int(0)
+        check(lib().hpfw_gpu_timeline_tracker_open(self._t, _hp(cur), ctypes.byref(has)))
+        return cur[0] if has.value else None
+
+    def finish(self):
+        check(lib().hpfw_gpu_timeline_tracker_finish(self._t))
+
+    def close(self):
+        if getattr(self, "_t", None):
+            lib().hpfw_gpu_timeline_tracker_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:        # interpreter teardown
+            pass
 
 
 def _shift_arg(shifts):
@@ -491,6 +580,10 @@ class Gpu:
 
     hit_score = staticmethod(hit_score)
     timeline_segments = staticmethod(timeline_segments)
+
+    def streams(self, n_streams, win, hop, capacity=0, tempos=None, shifts=None):
+        """a set of live feeds on this handle: GpuStreams"""
+        return GpuStreams(self, n_streams, win, hop, capacity, tempos, shifts)
 
     # ---- sample-rate conversion to 44.1 kHz (k_resample.hip) --------------------------------
     def resample_dev(self, d_in, n_in, n_clips, rate, d_out, stream=0):
@@ -853,6 +946,101 @@ class Gpu:
         launches = (ctypes.c_int * 16)()
         check(lib().hpfw_gpu_get_kernel_timing(self._h, names, ms, launches, ctypes.byref(n)))
         return {names[i].decode(): (float(ms[i]), int(launches[i])) for i in range(n.value)}
+
+
+class GpuStreams:
+    """hpfw_gpu_streams: n_streams rings of `capacity` samples on a Gpu handle; push() appends chunks, extract() hashes the
+    windows [w hop, w hop + win) that have become complete, bit for bit what Gpu.extract_windows gives for the feed so far.
+    Close it before its Gpu."""
+
+    def __init__(self, gpu, n_streams, win, hop, capacity=0, tempos=None, shifts=None):
+        self._t = None if tempos is None else np.ascontiguousarray(tempos, np.float32).ravel()
+        self._sh = None if shifts is None else np.ascontiguousarray(shifts, np.int32).ravel()
+        p = StreamsParams(int(n_streams), 0 if self._t is None else self._t.size, 0 if self._sh is None else self._sh.size, 0, int(win),
+                          int(hop), int(capacity), None if self._t is None else _hp(self._t), None if self._sh is None else _hp(self._sh))
+        self._s = ctypes.c_void_p()
+        self._gpu = gpu                                   # (keeps the handle alive as long as the set)
+        check(lib().hpfw_gpu_streams_create(gpu._h, ctypes.byref(p), ctypes.byref(self._s)))
+        info = StreamsInfo()
+        check(lib().hpfw_gpu_streams_info(self._s, ctypes.byref(info), None, None))
+        self.n_streams, self.win, self.hop, self.capacity = info.n_streams, info.win, info.hop, info.capacity
+        self.per_window, self.n_sets = info.per_window, info.n_sets
+        self.variants = tempos is not None or shifts is not None
+
+    def close(self):
+        if getattr(self, "_s", None):
+            lib().hpfw_gpu_streams_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:        # interpreter teardown
+            pass
+
+    def _counts(self, counts):
+        c = np.ascontiguousarray(counts, np.int64).ravel()
+        if c.size != self.n_streams:
+            raise ValueError("one count per feed")
+        return c
+
+    def push(self, chunks):
+        """chunks: one int16 array or None per feed (host) -> the number of complete windows not yet handed out"""
+        if len(chunks) != self.n_streams:
+            raise ValueError("one chunk (or None) per feed")
+        parts = [np.zeros(0, np.int16) if c is None else np.ascontiguousarray(c, np.int16).ravel() for c in chunks]
+        counts = np.array([p.size for p in parts], np.int64)
+        pcm = np.concatenate(parts) if counts.sum() else np.zeros(1, np.int16)
+        n = ctypes.c_int64()
+        check(lib().hpfw_gpu_streams_push(self._s, _hp(pcm), _hp(counts), ctypes.byref(n)))
+        return n.value
+
+    def push_dev(self, d_pcm, counts, stream=0):
+        """d_pcm: the chunks concatenated in feed order (device pointer), counts [n_streams]"""
+        c = self._counts(counts)
+        n = ctypes.c_int64()
+        check(lib().hpfw_gpu_streams_push_device(self._s, d_pcm, _hp(c), ctypes.byref(n), stream))
+        return n.value
+
+    def room(self):
+        out = np.zeros(self.n_streams, np.int64)
+        check(lib().hpfw_gpu_streams_room(self._s, _hp(out)))
+        return out
+
+    def info(self):
+        """(samples received, windows handed out) per feed"""
+        n, e = np.zeros(self.n_streams, np.int64), np.zeros(self.n_streams, np.int64)
+        check(lib().hpfw_gpu_streams_info(self._s, None, _hp(n), _hp(e)))
+        return n, e
+
+    def ready(self):
+        n, e = self.info()
+        return int(sum(window_count(int(a), self.win, self.hop) - int(b) for a, b in zip(n, e)))
+
+    def _hp_shape(self, n):
+        return (n, self.n_sets, self.per_window // self.n_sets) if self.variants else (n, self.per_window)
+
+    def extract(self, cap=None, clips=False):
+        """hashes up to cap ready windows (None: all): (STREAM_WINDOW_DTYPE [n], uint64 [n][n_hp] or [n][V][n_hp_v]) and
+        with clips=True also their samples int16 [n][win]"""
+        cap = self.ready() if cap is None else min(int(cap), self.ready())
+        which = np.zeros(max(cap, 1), STREAM_WINDOW_DTYPE)
+        hp = np.zeros(max(cap, 1) * self.per_window, np.uint64)
+        pcm = np.zeros((max(cap, 1), self.win), np.int16) if clips else None
+        n = ctypes.c_int64()
+        check(lib().hpfw_gpu_streams_extract_host(self._s, cap, _hp(hp), None if pcm is None else _hp(pcm), _hp(which), ctypes.byref(n)))
+        out = (which[:n.value], hp[:n.value * self.per_window].reshape(self._hp_shape(n.value)))
+        return out + (pcm[:n.value],) if clips else out
+
+    def extract_dev(self, cap, d_hp, d_clips=0, stream=0):
+        """the device form: d_hp [cap][per_window] and d_clips (0 or [cap][win]) are device pointers -> STREAM_WINDOW_DTYPE [n]"""
+        which = np.zeros(max(int(cap), 1), STREAM_WINDOW_DTYPE)
+        n = ctypes.c_int64()
+        check(lib().hpfw_gpu_streams_extract(self._s, int(cap), d_hp, d_clips or None, _hp(which), ctypes.byref(n), stream))
+        return which[:n.value]
+
+    def reset(self, feed):
+        check(lib().hpfw_gpu_streams_reset(self._s, int(feed)))
 
 
 def _ragged(arrays, dtype):

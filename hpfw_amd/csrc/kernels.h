@@ -373,6 +373,18 @@ void launch_topk_merge_shards(const void *d_in, int n_shards, int64_t n_q, int k
 void launch_sum_stats(const void *d_in, int n_shards, int64_t rows, void *d_out, hipStream_t s);
 // windows of one recording (k_windows.hip): window i of d_src is samples [i hop, i hop + win) -> d_dst [n_w][win]
 void launch_gather_windows(const int16_t *d_src, int64_t hop, int64_t win, int64_t n_w, int16_t *d_dst, hipStream_t s);
+// live feeds (k_streams.hip): rings of `capacity` samples in one slab [n_streams][capacity]
+struct RingRun {
+    int64_t src, dst, count; // `count` staged samples from src + `src` to slab + `dst`: one run inside one ring
+};
+struct RingWindow {
+    int64_t base, start; // a window's ring at slab + base, its first sample at ring position start < capacity
+};
+// every run of one push in one launch; max_count: the longest run
+void launch_ring_append(const RingRun *d_runs, int n_runs, int64_t max_count, const int16_t *d_src, int16_t *d_slab, hipStream_t s);
+// window i of the pass: win samples from d_tab[i] on, modulo capacity -> d_dst [n_w][win]
+void launch_ring_gather_windows(const int16_t *d_slab, const RingWindow *d_tab, int64_t capacity, int64_t win, int64_t n_w, int16_t *d_dst,
+                                hipStream_t s);
 
 // sample-rate conversion to 44.1 kHz (k_resample.hip)
 constexpr int kRsRateOut = 44100, kRsRateMin = 8000, kRsRateMax = 192000;

@@ -1,8 +1,11 @@
 // timeline.cpp -- the host-only parts of the timeline of a long recording (include/hpfw_gpu.h): the
 // score of a hit from its row's integer moments, the number of windows of a recording, and the segments of a list of
-// per-window hits.  No device, no handle: every binding calls these, so the numbers are the same everywhere.
+// per-window hits, all at once or push by push.  No device, no handle: every binding calls these, so
+// the numbers are the same everywhere.
 #include <cmath>
 #include <cstdint>
+#include <deque>
+#include <functional>
 #include <limits>
 #include <string>
 
@@ -14,7 +17,86 @@ int fail(int code, const char *msg)
     hpfw_internal_set_error(msg);
     return code;
 }
+
+// the parameter checks of the segment rule, with their messages
+int check_params(const hpfw_timeline_params *p)
+{
+    if (!(p->min_score > 0)) return fail(HPFW_E_INVALID, "timeline: min_score is required and must be positive");
+    if (!(p->hop_cols > 0) || !std::isfinite(p->hop_cols)) return fail(HPFW_E_INVALID, "timeline: hop_cols must be positive and finite");
+    if (!(p->tol_cols >= 0)) return fail(HPFW_E_INVALID, "timeline: tol_cols must not be negative");
+    if (p->hop < 1 || p->hop > p->win) return fail(HPFW_E_INVALID, "timeline: 1 <= hop <= win");
+    if (p->max_gap < -1 || p->min_windows < 0) return fail(HPFW_E_INVALID, "timeline: max_gap >= 0 (-1: default), min_windows >= 1 (0: default)");
+    return 0;
+}
+
+// The rule of include/hpfw_gpu.h, one window at a time.  A segment is closed as soon as nothing can continue it: by a strong
+// window that does not continue it, or once window l + max_gap + 1 has passed without continuing it (l: its last accepted
+// window; a later window lies more than max_gap windows behind l).  Closing then instead of at the next strong window or at
+// the end of the list changes no segment: the whole list at once and the list push by push give the same bytes.
+struct Segmenter {
+    hpfw_timeline_params p;
+    double tol;
+    int64_t max_gap;
+    int min_windows;
+    std::function<void(const hpfw_segment &)> keep; // receives every closed segment of at least min_windows strong windows
+    bool open = false;
+    hpfw_segment seg{};
+    int64_t i = 0;    // the number of the next window
+    int64_t l = 0;    // the open segment's last accepted window, its offset and tempo
+    int32_t l_offset = 0;
+    double l_tempo = 1.0;
+
+    Segmenter(const hpfw_timeline_params &p_, std::function<void(const hpfw_segment &)> keep_)
+        : p(p_), tol(p_.tol_cols > 0 ? p_.tol_cols : std::fmax(2.0, 0.08 * p_.hop_cols)), max_gap(p_.max_gap < 0 ? 1 : p_.max_gap),
+          min_windows(p_.min_windows == 0 ? 1 : p_.min_windows), keep(std::move(keep_))
+    {
+    }
+    void close()
+    {
+        if (open && seg.n_strong >= min_windows) keep(seg);
+        open = false;
+    }
+    void step(const hpfw_window_hit &x)
+    {
+        if (x.clip != 0xffffffffu && x.score >= p.min_score) { // strong (a NaN score fails the comparison)
+            bool cont = false;
+            if (open && x.clip == seg.clip && i - l - 1 <= max_gap) {
+                const double t_w = (double)i * p.hop_cols, t_l = (double)l * p.hop_cols;
+                const double res = ((double)x.offset - (double)l_offset) - l_tempo * (t_w - t_l);
+                cont = std::fabs(res) <= tol * (double)(i - l);
+            }
+            if (cont) {
+                seg.last = i;
+                seg.end = i * p.hop + p.win;
+                ++seg.n_strong;
+                if (x.score > seg.best_score) {
+                    seg.best_window = i;
+                    seg.best_score = x.score;
+                    seg.best_tempo = x.tempo;
+                    seg.best_offset = x.offset;
+                    seg.best_variant = x.variant;
+                }
+            } else {
+                close();
+                open = true;
+                seg = hpfw_segment{x.clip, 1, i, i, i * p.hop, i * p.hop + p.win, i, x.score, x.tempo, x.offset, x.variant, x.offset, 0};
+            }
+            l = i;
+            l_offset = x.offset;
+            l_tempo = x.tempo;
+        } else if (open && i - l > max_gap) { // window l + max_gap + 1 did not continue it: no later one can
+            close();
+        }
+        ++i;
+    }
+};
 } // namespace
+
+struct hpfw_timeline_tracker {
+    std::deque<hpfw_segment> closed; // closed and kept, not yet popped
+    Segmenter sg;
+    explicit hpfw_timeline_tracker(const hpfw_timeline_params &p) : sg(p, [this](const hpfw_segment &s) { closed.push_back(s); }) {}
+};
 
 extern "C" {
 
@@ -49,55 +131,60 @@ int hpfw_gpu_timeline_segments(const hpfw_window_hit *w, int64_t n_w, const hpfw
                                int64_t *n_seg)
 {
     if (!p || !n_seg || n_w < 0 || cap < 0 || (n_w && !w) || (cap && !out)) return fail(HPFW_E_INVALID, "bad argument");
-    if (!(p->min_score > 0)) return fail(HPFW_E_INVALID, "timeline: min_score is required and must be positive");
-    if (!(p->hop_cols > 0) || !std::isfinite(p->hop_cols)) return fail(HPFW_E_INVALID, "timeline: hop_cols must be positive and finite");
-    if (!(p->tol_cols >= 0)) return fail(HPFW_E_INVALID, "timeline: tol_cols must not be negative");
-    if (p->hop < 1 || p->hop > p->win) return fail(HPFW_E_INVALID, "timeline: 1 <= hop <= win");
-    if (p->max_gap < -1 || p->min_windows < 0) return fail(HPFW_E_INVALID, "timeline: max_gap >= 0 (-1: default), min_windows >= 1 (0: default)");
-    const double tol = p->tol_cols > 0 ? p->tol_cols : std::fmax(2.0, 0.08 * p->hop_cols);
-    const int64_t max_gap = p->max_gap < 0 ? 1 : p->max_gap;
-    const int min_windows = p->min_windows == 0 ? 1 : p->min_windows;
-
+    if (int rc = check_params(p)) return rc;
     int64_t kept = 0;
-    bool open = false;
-    hpfw_segment seg{};
-    int64_t l = 0; // the open segment's last accepted window
-    auto close = [&] {
-        if (open && seg.n_strong >= min_windows) {
-            if (kept < cap) out[kept] = seg;
-            ++kept;
-        }
-        open = false;
-    };
-    for (int64_t i = 0; i < n_w; ++i) {
-        const hpfw_window_hit &x = w[i];
-        if (x.clip == 0xffffffffu || !(x.score >= p->min_score)) continue; // not strong (a NaN score fails the comparison)
-        bool cont = false;
-        if (open && x.clip == seg.clip && i - l - 1 <= max_gap) {
-            const double t_w = (double)i * p->hop_cols, t_l = (double)l * p->hop_cols;
-            const double res = ((double)x.offset - (double)w[l].offset) - w[l].tempo * (t_w - t_l);
-            cont = std::fabs(res) <= tol * (double)(i - l);
-        }
-        if (cont) {
-            seg.last = i;
-            seg.end = i * p->hop + p->win;
-            ++seg.n_strong;
-            if (x.score > seg.best_score) {
-                seg.best_window = i;
-                seg.best_score = x.score;
-                seg.best_tempo = x.tempo;
-                seg.best_offset = x.offset;
-                seg.best_variant = x.variant;
-            }
-        } else {
-            close();
-            open = true;
-            seg = hpfw_segment{x.clip, 1, i, i, i * p->hop, i * p->hop + p->win, i, x.score, x.tempo, x.offset, x.variant, x.offset, 0};
-        }
-        l = i;
-    }
-    close();
+    Segmenter sg(*p, [&](const hpfw_segment &seg) {
+        if (kept < cap) out[kept] = seg;
+        ++kept;
+    });
+    for (int64_t i = 0; i < n_w; ++i) sg.step(w[i]);
+    sg.close();
     *n_seg = kept;
+    return 0;
+}
+
+// ---- the same rule one push at a time ----
+int hpfw_gpu_timeline_tracker_create(const hpfw_timeline_params *p, hpfw_timeline_tracker **out)
+{
+    if (!p || !out) return fail(HPFW_E_INVALID, "bad argument");
+    if (int rc = check_params(p)) return rc;
+    *out = new hpfw_timeline_tracker(*p);
+    return 0;
+}
+
+void hpfw_gpu_timeline_tracker_destroy(hpfw_timeline_tracker *t) { delete t; }
+
+int hpfw_gpu_timeline_tracker_push(hpfw_timeline_tracker *t, const hpfw_window_hit *w, int64_t n_w)
+{
+    if (!t || n_w < 0 || (n_w && !w)) return fail(HPFW_E_INVALID, "bad argument");
+    for (int64_t i = 0; i < n_w; ++i) t->sg.step(w[i]);
+    return 0;
+}
+
+int hpfw_gpu_timeline_tracker_pop(hpfw_timeline_tracker *t, hpfw_segment *out, int64_t cap, int64_t *n)
+{
+    if (!t || !n || cap < 0 || (cap && !out)) return fail(HPFW_E_INVALID, "bad argument");
+    int64_t got = 0;
+    for (; got < cap && !t->closed.empty(); ++got) {
+        out[got] = t->closed.front();
+        t->closed.pop_front();
+    }
+    *n = got;
+    return 0;
+}
+
+int hpfw_gpu_timeline_tracker_open(hpfw_timeline_tracker *t, hpfw_segment *cur, int *has)
+{
+    if (!t || !cur || !has) return fail(HPFW_E_INVALID, "bad argument");
+    *has = t->sg.open ? 1 : 0;
+    if (t->sg.open) *cur = t->sg.seg;
+    return 0;
+}
+
+int hpfw_gpu_timeline_tracker_finish(hpfw_timeline_tracker *t)
+{
+    if (!t) return fail(HPFW_E_INVALID, "bad argument");
+    t->sg.close();
     return 0;
 }
 

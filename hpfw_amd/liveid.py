@@ -6,6 +6,7 @@ index(files)  = storage.build(collector.prepare(files))           live_song_id.h
 search(files) = per query: calc_hashprint -> find -> report       live_song_id.h:35-54
 top(files, k) = the notebook's "ten best tracks" per query        liveid.ipynb cell 9
 timeline(file) = the songs of one long recording, window by window (not in the reference)
+streams(n)     = the same for n feeds that are still running, as their samples arrive
 """
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -163,8 +164,6 @@ class LiveSongIdentification:
             shifts = _lib.check_shifts(shifts)
         if tempos is not None:
             tempos = _lib.check_tempos(tempos, 0 if shifts is None else len(shifts))
-        n_s = len(shifts) if shifts else 1
-        n_sets = (len(tempos) if tempos else 1) * n_s
         variants = shifts is not None or tempos is not None
         extractor = self.collector.gpu()                  # the collector's filters
         if variants and extractor.get_projection() != 1:
@@ -183,6 +182,19 @@ class LiveSongIdentification:
             hp = self._gpu.extract_windows(extractor, x, win, hop, tempos, shifts)
         else:
             hp = extractor.extract_windows(x, win, hop, tempos, shifts)
+        rows, per_window = self._search_windows(hp, shifts, tempos)
+        m = self._gpu.geometry(win).m
+        segs = _lib.timeline_segments(rows, min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
+        out = [self._segment_tuple(sg, *per_window[int(sg["best_window"])][5:], 3.0 * win / m / 44100.0) for sg in segs]
+        return (out, per_window) if windows else out
+
+    def _search_windows(self, hp, shifts, tempos):
+        """the scored search of the windows' hashprints hp [n_w][k_q] or, with variants, [n_w][n_sets][k_q] (shifts and tempos
+        as checked): (WINDOW_HIT_DTYPE [n_w] for the segment rule, [(clip index or None, name or None, distance, offset, score,
+        shift, tempo) per window]).  timeline() and LiveStreams.push() share it."""
+        variants = shifts is not None or tempos is not None
+        n_s = len(shifts) if shifts else 1
+        n_sets = (len(tempos) if tempos else 1) * n_s
         n_w, k_q = hp.shape[0], hp.shape[-1]
         off = np.arange(n_w * n_sets + 1, dtype=np.int64) * k_q
         if variants:
@@ -205,15 +217,28 @@ class LiveSongIdentification:
             score = _lib.hit_score(int(h["dist"]), clip_len[clip] >= k_q, stats[w, v] if variants else stats[w])
             rows[w] = (clip, int(h["offset"]), v, 0, tempo, score)
             per_window.append((clip, self.names[clip], int(h["dist"]), int(h["offset"]), score, shift, tempo))
-        m = self._gpu.geometry(win).m
-        col_s = 3.0 * win / m / 44100.0                    # one index column in seconds
-        segs = _lib.timeline_segments(rows, min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
-        out = []
-        for sg in segs:
-            bw = per_window[int(sg["best_window"])]
-            out.append((int(sg["start"]) / 44100.0, int(sg["end"]) / 44100.0, self.names[int(sg["clip"])], float(sg["best_score"]),
-                        int(sg["first_offset"]) * col_s, bw[5], bw[6]))
-        return (out, per_window) if windows else out
+        return rows, per_window
+
+    def _segment_tuple(self, sg, shift, tempo, col_s):
+        """a SEGMENT_DTYPE record as timeline() returns it; shift, tempo: those of its best window, col_s: one index column
+        in seconds"""
+        return (int(sg["start"]) / 44100.0, int(sg["end"]) / 44100.0, self.names[int(sg["clip"])], float(sg["best_score"]),
+                int(sg["first_offset"]) * col_s, shift, tempo)
+
+    def streams(self, n_streams: int, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
+                shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
+                tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, capacity_s: Optional[float] = None,
+                windows: bool = False, rate: int = 44100):
+        """the timelines of n_streams live feeds as their samples arrive (hpfw_amd.streams.LiveStreams):
+        per feed exactly what timeline() gives for a file that holds everything pushed to it.  Feeds are 44.1 kHz mono PCM16:
+        another rate is refused (HPFW_E_UNSUPPORTED), whatever the resample switch.  capacity_s: seconds of audio a feed's ring
+        holds (None: two windows)."""
+        from .streams import LiveStreams
+        if int(rate) != 44100:
+            raise _lib.HpfwError(f"live feeds are 44.1 kHz mono PCM16: a feed at {rate} Hz has to be converted before it is pushed",
+                                 _lib.E_UNSUPPORTED)
+        return LiveStreams(self, n_streams, min_score, window_s, hop_s, shifts, tempos, tol_cols, max_gap, min_windows, capacity_s,
+                           windows)
 
     def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None,
                tempos: Optional[Sequence[float]] = None):

@@ -1,0 +1,97 @@
+"""LiveStreams: the timelines of feeds that are still running.
+
+LiveSongIdentification.timeline() reads a finished file; LiveSongIdentification.streams() takes the samples of any number of
+feeds as they arrive.  Every window that has become complete is hashed in one extraction pass over all feeds (the rings and
+their two kernels: hpfw_gpu_streams_*, k_streams.hip), searched and scored as timeline() does it, and a segmenter per feed
+(hpfw_timeline_tracker) hands out each segment as soon as nothing can continue it.  A window is an independent clip, so what
+a feed yields is exactly timeline() of a file that holds everything pushed to it, however the samples were cut into chunks.
+
+Feeds are 44.1 kHz mono PCM16.  A feed at another rate has to be converted before it is pushed; converting it chunk by chunk
+needs the resampler's history carried across pushes, which is not done here.
+"""
+import numpy as np
+
+from . import _lib
+
+
+class LiveStreams:
+    def __init__(self, lsi, n_streams, min_score, window_s=5.0, hop_s=2.5, shifts=None, tempos=None, tol_cols=None, max_gap=1,
+                 min_windows=1, capacity_s=None, windows=False):
+        self._lsi = lsi
+        win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
+        self._shifts = None if shifts is None else _lib.check_shifts(shifts)
+        self._tempos = None if tempos is None else _lib.check_tempos(tempos, 0 if shifts is None else len(self._shifts))
+        self._windows = bool(windows)
+        self._gs = None
+        capacity = 0 if capacity_s is None else int(round(capacity_s * 44100))
+        extractor = lsi.collector.gpu()                   # the collector's filters
+        self._gs = extractor.streams(n_streams, win, hop, capacity, self._tempos, self._shifts)
+        m = lsi._gpu.geometry(win).m
+        self._col_s = 3.0 * win / m / 44100.0             # one index column in seconds
+        self._tracker_args = (min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
+        self._trackers = [_lib.TimelineTracker(*self._tracker_args) for _ in range(n_streams)]
+        self.n_streams, self.win, self.hop, self.capacity = n_streams, win, hop, self._gs.capacity
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        for t in getattr(self, "_trackers", []):
+            t.close()
+        if getattr(self, "_gs", None) is not None:
+            self._gs.close()
+            self._gs = None
+
+    def room(self):
+        """the samples every feed can take now"""
+        return self._gs.room()
+
+    def _variant(self, v):
+        n_s = len(self._shifts) if self._shifts else 1
+        j, i = divmod(max(int(v), 0), n_s)                # variant v = j max(S, 1) + i
+        return (self._shifts[i] if self._shifts else 0), (self._tempos[j] if self._tempos else 1.0)
+
+    def _tuple(self, sg):
+        return self._lsi._segment_tuple(sg, *self._variant(sg["best_variant"]), self._col_s)
+
+    def push(self, chunks):
+        """chunks: a list with one int16 array or None per feed, or {feed: array}.  Appends them, hashes and searches every
+        window that has become complete, and returns [(feed, segment)]: the segments these windows closed, as timeline()
+        returns them with start_s / end_s counted from the feed's start.  With windows=True at creation:
+        (segments, [(feed, window, per-window tuple of timeline(windows=True))])."""
+        if isinstance(chunks, dict):
+            if any(not 0 <= int(f) < self.n_streams for f in chunks):
+                raise ValueError("no such feed")
+            chunks = [chunks.get(f) for f in range(self.n_streams)]
+        segments, wins = [], []
+        if self._gs.push(chunks):
+            which, hp = self._gs.extract()
+            rows, per_window = self._lsi._search_windows(hp, self._shifts, self._tempos)
+            wins = [(int(w["feed"]), int(w["window"]), row) for w, row in zip(which, per_window)]
+            for feed in np.unique(which["feed"]):         # (ascending; a feed's windows are in order)
+                t = self._trackers[int(feed)]
+                t.push(rows[which["feed"] == feed])
+                segments += [(int(feed), self._tuple(sg)) for sg in t.pop()]
+        return (segments, wins) if self._windows else segments
+
+    def open(self):
+        """per feed the segment in progress as it would close now, whatever min_windows, or None"""
+        cur = [t.open() for t in self._trackers]
+        return [None if sg is None else self._tuple(sg) for sg in cur]
+
+    def finish(self, feed=None):
+        """closes the segment in progress of one feed, or of every feed, and returns [(feed, segment)] it released"""
+        out = []
+        for f in (range(self.n_streams) if feed is None else [int(feed)]):
+            self._trackers[f].finish()
+            out += [(f, self._tuple(sg)) for sg in self._trackers[f].pop()]
+        return out
+
+    def reset(self, feed):
+        """the feed starts again at sample 0 and window 0 (a feed that reconnects); its segment in progress is dropped"""
+        self._gs.reset(feed)
+        self._trackers[int(feed)].close()
+        self._trackers[int(feed)] = _lib.TimelineTracker(*self._tracker_args)

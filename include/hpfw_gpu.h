@@ -538,6 +538,79 @@ typedef struct {
 int hpfw_gpu_timeline_segments(const hpfw_window_hit *w, int64_t n_w, const hpfw_timeline_params *p, hpfw_segment *out,
                                int64_t cap, int64_t *n_seg);
 
+/* ---- live feeds: the timeline of feeds that are still running, as their samples arrive.
+ *
+ * A set of n_streams feeds on one handle, each a ring of `capacity` samples in device memory (44.1 kHz mono PCM16; another
+ * rate has to be converted before it is pushed).  n_i: the samples feed i has received, e_i: the windows of it already handed
+ * out.  Window w of a feed is its samples [w hop, w hop + win), as hpfw_gpu_window_count cuts a recording; the ring holds
+ * samples [e_i hop, n_i).
+ * CONTRACT.  The hashprints of window w of a feed equal, bit for bit, what hpfw_gpu_extract_windows_pcm16 gives for window w
+ * of everything pushed to that feed since its last reset, and the clips equal those samples: whatever the chunking, the
+ * other feeds, cap, and however often the ring has wrapped.
+ * A set works in its handle's workspaces: calls on it are ordered with every other call on the handle, it is used by one
+ * thread at a time, and it is destroyed before the handle. */
+typedef struct hpfw_gpu_streams hpfw_gpu_streams;
+typedef struct {
+    int32_t n_streams;     /* 1 .. 4096                                                                  */
+    int32_t n_tempos;      /* tempos / shifts as hpfw_gpu_extract_windows_pcm16 takes them: NULL and 0 for  */
+    int32_t n_shifts;      /* none; the lists are copied                                                 */
+    int32_t pad;
+    int64_t win, hop;      /* samples, as hpfw_gpu_window_count: 1 <= hop <= win, win a supported length  */
+    int64_t capacity;      /* samples per ring, >= win; 0 = 2 win                                        */
+    const float *tempos;
+    const int32_t *shifts;
+} hpfw_streams_params;
+typedef struct {
+    int32_t feed, pad;
+    int64_t window;
+} hpfw_stream_window;
+typedef struct {
+    int64_t per_window;    /* hashprints per window: [V][n_hp_v] flattened, as hpfw_gpu_extract_windows_pcm16 lays them out */
+    int64_t win, hop, capacity;
+    int32_t n_streams, n_sets; /* n_sets = V: max(n_tempos, 1) max(n_shifts, 1)                           */
+} hpfw_streams_info;
+/* Every check of hpfw_gpu_extract_windows_pcm16 with its messages (the lists first, then the handle, projection mode 1 for
+ * variants, the filters), after n_streams, win / hop and capacity.  Builds the tables of `win` and allocates the rings. */
+int hpfw_gpu_streams_create(hpfw_gpu *h, const hpfw_streams_params *p, hpfw_gpu_streams **out);
+void hpfw_gpu_streams_destroy(hpfw_gpu_streams *s);
+/* Appends counts[i] >= 0 samples to feed i, for every feed: pcm holds the chunks concatenated in feed order (host memory; the
+ * device form takes a device pointer and enqueues on `stream`).  One upload and one launch, however many feeds take part.
+ * A chunk that does not fit (n_i + counts[i] - e_i hop > capacity) makes the whole call HPFW_E_INVALID: nothing is appended
+ * to any feed and the message names the first such feed.  *n_ready (may be NULL): complete windows not yet handed out, over
+ * all feeds.  pcm may be NULL when every count is 0. */
+int hpfw_gpu_streams_push(hpfw_gpu_streams *s, const int16_t *pcm, const int64_t *counts, int64_t *n_ready);
+int hpfw_gpu_streams_push_device(hpfw_gpu_streams *s, const int16_t *d_pcm, const int64_t *counts, int64_t *n_ready, void *stream);
+/* room[i] = capacity - (n_i - e_i hop): the samples feed i can take now */
+int hpfw_gpu_streams_room(hpfw_gpu_streams *s, int64_t *room);
+/* Hashes up to cap >= 0 ready windows in order of (feed, window) ascending; the others stay ready.  *n: how many; which [*n]
+ * (host, room for min(cap, ready) entries) names them; d_hp [*n][per_window]; d_clips NULL or [*n][win], the windows' samples.
+ * The windows go through the extraction a pass of clips (hpfw_gpu_set_batch) at a time, one gather launch per pass.  The
+ * host form downloads and synchronises. */
+int hpfw_gpu_streams_extract(hpfw_gpu_streams *s, int64_t cap, uint64_t *d_hp, int16_t *d_clips, hpfw_stream_window *which, int64_t *n,
+                             void *stream);
+int hpfw_gpu_streams_extract_host(hpfw_gpu_streams *s, int64_t cap, uint64_t *hp, int16_t *clips, hpfw_stream_window *which, int64_t *n);
+/* feed `stream` starts again at sample 0 and window 0 (a feed that reconnects); its windows not yet handed out are dropped */
+int hpfw_gpu_streams_reset(hpfw_gpu_streams *s, int stream);
+/* info, received [n_streams] = n_i and extracted [n_streams] = e_i; each may be NULL */
+int hpfw_gpu_streams_info(hpfw_gpu_streams *s, hpfw_streams_info *info, int64_t *received, int64_t *extracted);
+
+/* Segments as the windows arrive: hpfw_gpu_timeline_segments one push at a time.  Host only, no handle.  Windows are numbered
+ * from 0 in push order; the parameter checks and messages are those of hpfw_gpu_timeline_segments.
+ * CONTRACT.  For any window list and any partition of it into pushes, the popped segments followed by those popped after
+ * _finish equal hpfw_gpu_timeline_segments on the whole list, byte for byte.
+ * A segment whose last accepted window is l is closed, and can be popped, after the push of the first window that shows that
+ * nothing continues it: a strong window that does not continue it, or window l + max_gap + 1 when that one does not. */
+typedef struct hpfw_timeline_tracker hpfw_timeline_tracker;
+int hpfw_gpu_timeline_tracker_create(const hpfw_timeline_params *p, hpfw_timeline_tracker **out);
+void hpfw_gpu_timeline_tracker_destroy(hpfw_timeline_tracker *t);
+int hpfw_gpu_timeline_tracker_push(hpfw_timeline_tracker *t, const hpfw_window_hit *w, int64_t n_w);
+/* takes up to cap closed and kept segments off the queue, oldest first; *n: how many were written */
+int hpfw_gpu_timeline_tracker_pop(hpfw_timeline_tracker *t, hpfw_segment *out, int64_t cap, int64_t *n);
+/* the segment in progress as it would close now, whatever min_windows; *has = 0 when none is open */
+int hpfw_gpu_timeline_tracker_open(hpfw_timeline_tracker *t, hpfw_segment *cur, int *has);
+/* closes the segment in progress (kept when it holds min_windows strong windows); the window numbering goes on */
+int hpfw_gpu_timeline_tracker_finish(hpfw_timeline_tracker *t);
+
 /* ---- table preparation ahead of time.  A corpus of real recordings brings a new clip length with almost every file,
  * and the host half of a length's tables (constant-Q windows and chirp spectra, twiddles) costs more than the
  * extraction of the file: 3 ms for 30 s, 15 ms for 3 minutes.  hpfw_gpu_prepare_length builds that half on the
