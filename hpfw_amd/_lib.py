@@ -54,7 +54,7 @@ EXPORTS = (
     "hpfw_gpu_cfg_cov_reset", "hpfw_gpu_cfg_cov_accumulate", "hpfw_gpu_cfg_cov_get", "hpfw_gpu_cfg_learn_filters",
     "hpfw_gpu_set_kernel_timing", "hpfw_gpu_get_kernel_timing", "hpfw_gpu_plan_checksum",
     "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_plan_cols_tables", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_debug_db_term_sweep", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
-    "hpfw_gpu_hashprints_from_db", "hpfw_gpu_stage_delta_q",
+    "hpfw_gpu_hashprints_from_db", "hpfw_gpu_stage_delta_q", "hpfw_gpu_debug_q_products",
     "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
     "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
     "hpfw_gpu_combiner_find_device", "hpfw_gpu_combiner_align", "hpfw_gpu_combiner_align_device", "hpfw_gpu_wav_read_pcm16",
@@ -214,6 +214,7 @@ def lib():
     L.hpfw_gpu_get_projection.argtypes = [vp]
     L.hpfw_gpu_hashprints_from_db.argtypes = [vp, vp, i64, i64, vp, vp]
     L.hpfw_gpu_stage_delta_q.argtypes = [vp, vp, i64, i64, vp, vp, vp]
+    L.hpfw_gpu_debug_q_products.argtypes = [vp, vp, vp, vp]
     L.hpfw_gpu_set_conventions.argtypes = [vp, u32]
     L.hpfw_gpu_mel_cov_accumulate_pcm16_host.argtypes = [vp, vp, i64, i64]
     L.hpfw_gpu_combiner_clear.argtypes = [vp]
@@ -614,6 +615,13 @@ class Gpu:
     def stage_delta_q_dev(self, d_db, n_clips, c, d_delta, d_hp=0, stream=0):
         """the exact integer sums of the fixed-point projection, int64 [n_clips][64][c - 99] (parity checkpoint)"""
         check(lib().hpfw_gpu_stage_delta_q(self._h, d_db, n_clips, c, d_delta, d_hp, stream))
+
+    def debug_q_products(self):
+        """(tiles, listed values, redone tiles) of the last six-product launch of this handle; waits for the device"""
+        v = (ctypes.c_int64 * 3)()
+        p = [ctypes.cast(ctypes.byref(v, 8 * i), ctypes.c_void_p) for i in range(3)]
+        check(lib().hpfw_gpu_debug_q_products(self._h, *p))
+        return int(v[0]), int(v[1]), int(v[2])
 
     def prepare_length(self, n_samples):
         """build the host half of the tables of a clip length on the calling thread (thread-safe; see hpfw_gpu.h)"""

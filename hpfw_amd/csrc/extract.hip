@@ -240,6 +240,18 @@ int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, 
     return check_launch("db");
 }
 
+int q_split(hpfw_gpu *h, int n_shifts, int64_t n_clips, int64_t c, hpfw::QSplit *qs, const hpfw::QSplit **use)
+{
+    *use = nullptr;
+    if (n_shifts || h->q_products != 6 || !h->projection) return 0;
+    const int64_t tiles = hpfw::project_q_tiles(n_clips, c);
+    if (tiles <= 0) return 0;
+    if (int rc = ensure(h->d_q_split, hpfw::project_q_split_bytes(tiles), h)) return rc;
+    *qs = {h->d_fq_thr.as<int32_t>(), h->d_q_split.get()};
+    *use = qs;
+    return 0;
+}
+
 namespace {
 // back end for ns clips: dB spectrograms of the S workspace -> hashprints [ns][max(n_shifts, 1)][n_hp] of the filter
 // images at `images` as launch_hashprints_q takes them (the f32 chain: the handle's filters, n_shifts = 0)
@@ -249,10 +261,14 @@ int run_back(hpfw_gpu *h, DevPlan *dp, const void *images, int n_shifts, int ns,
     const float *sdb = h->ws[2].as<float>();
     int rc;
     if (h->projection) { // S9q: reference level, clip, exact integer sums on the int8 matrix pipe, sign and pack in ONE kernel
+        hpfw::QSplit qs;
+        const hpfw::QSplit *split;
+        if ((rc = q_split(h, n_shifts, ns, p.c, &qs, &split))) return rc;
         {
             Timed t(h, K_PROJECT, s);
-            hpfw::launch_hashprints_q(images, n_shifts, sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s);
+            hpfw::launch_hashprints_q(images, n_shifts, sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s, split);
         }
+        if (split) h->q_last_tiles = hpfw::project_q_tiles(ns, p.c);
         return check_launch("project");
     }
     float *proj = h->ws[3].as<float>();
@@ -325,12 +341,16 @@ int hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t 
         const void *images = n_shifts ? h->d_shift_images.get() : h->d_fq_image.get();
         const int nbmax = 256;
         if (!h->projection && (rc = ensure(h->ws[3], (size_t)nbmax * 64 * (size_t)nf * 4))) return rc;
+        hpfw::QSplit qs;
+        const hpfw::QSplit *split;
+        if ((rc = q_split(h, n_shifts, std::min<int64_t>(nbmax, n_clips), c, &qs, &split))) return rc;
         for (int64_t c0 = 0; c0 < n_clips; c0 += nbmax) {
             const int nb = (int)std::min<int64_t>(nbmax, n_clips - c0);
             if (h->projection) {
                 Timed t(h, K_PROJECT, s);
                 hpfw::launch_hashprints_q(images, n_shifts, d_db + c0 * 121 * c, nullptr, nb, (int)c, d_hp + c0 * std::max(n_shifts, 1) * nhp,
-                                          nullptr, s);
+                                          nullptr, s, split);
+                if (split) h->q_last_tiles = hpfw::project_q_tiles(nb, c);
             } else {
                 hpfw::launch_project(h->d_fpack.as<float>(), d_db + c0 * 121 * c, nullptr, nb, (int)c, h->ws[3].as<float>(), s);
                 hpfw::launch_pack(h->ws[3].as<float>(), nb, (int)nf, d_hp + c0 * nhp, s);
@@ -534,6 +554,25 @@ int hpfw_gpu_hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips,
     if (int rc = check_filters(h)) return rc;
     if (c - (hpfw::kCtx - 1) - hpfw::kLag <= 0) return 0;
     return hashprints_from_db(h, d_db, n_clips, c, nullptr, 0, d_hp, (hipStream_t)stream);
+}
+
+// the six-product split's last launch on this handle (tests, profiles): its tiles, the open values listed in them and the
+// tiles redone with nine products.  Waits for the device.  All zero after a launch of the nine-product kernel
+int hpfw_gpu_debug_q_products(hpfw_gpu *h, int64_t *tiles, int64_t *listed, int64_t *redone)
+{
+    if (!h || !tiles || !listed || !redone) return fail(HPFW_E_INVALID, "null argument");
+    *tiles = *listed = *redone = 0;
+    if (h->q_products != 6 || h->q_last_tiles <= 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> counts((size_t)h->q_last_tiles);
+    HIP_TRY(hipMemcpy(counts.data(), h->d_q_split.get(), counts.size() * 4, hipMemcpyDeviceToHost));
+    *tiles = h->q_last_tiles;
+    for (uint32_t v : counts) {
+        if (v == 0xffffffffu) *redone += 1;
+        else *listed += v;
+    }
+    return 0;
 }
 
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp, void *stream)

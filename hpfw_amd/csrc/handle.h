@@ -84,6 +84,12 @@ struct hpfw_gpu {
     std::vector<float> filters; // the filters as they were installed (hpfw_gpu_get_filters)
     DevBuf d_fpack;
     DevBuf d_fq_image; // the filters' fixed-point digits (k_project_q.hip)
+    // the six-product split of the unshifted fixed-point extraction (k_project_q.hip): fq as int32 and the rows'
+    // thresholds; the tiles' counts and segments of open values of a launch; the tiles of the last launch (hpfw_gpu_debug_q_products).
+    // HPFW_Q_PRODUCTS=9 in the environment at creation: the nine-product kernel alone
+    DevBuf d_fq_thr, d_q_split;
+    int q_products = 6;
+    int64_t q_last_tiles = 0;
     int projection = 1; // 1: fixed point (S9q), 0: the f32 fma chain (S9); hpfw_gpu_set_projection
     // the tables of every clip length in use and the device memory they come from (plans.hip)
     struct PlanCache {
@@ -332,6 +338,9 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out);
 hipError_t init_plans(hpfw_gpu *h); // the table stream and event, HPFW_PLAN_TIMING (at the handle's creation)
 void clear_plans(hpfw_gpu *h);      // every length's tables and host half (no work may be using them)
 // extract.hip
+// what launch_hashprints_q takes as `split` for n_clips clips of c columns: the handle's split with its workspace, or NULL
+// where the call runs the nine-product kernel (shifted images, HPFW_Q_PRODUCTS=9)
+int q_split(hpfw_gpu *h, int n_shifts, int64_t n_clips, int64_t c, hpfw::QSplit *qs, const hpfw::QSplit **use);
 int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips);
 int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns);
 int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, bool finish_db, hipStream_t s);

@@ -23,8 +23,10 @@
 // 64 k', two steps ahead) -- nothing is exchanged between the waves in the main loop, so it has no barrier: the two
 // waves of a SIMD (two workgroups share a CU: 62 KB of LDS, 256 registers) interleave their matrix instructions freely,
 // and one workgroup's staging (loads, quantisation: vector ALU) and epilogue run under the other's products.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "kernels.h"
@@ -48,6 +50,11 @@ constexpr int kQStepBytes = 3 * 64 * 16;                      // a wave's filter
 constexpr int kQSteps = 2 * kCtx;                             // 40 steps of 64 k'
 constexpr int kQLdsBytes = kQSlabBytes + kQTileN * 4 * 2;     // + the waves' 16-bit parts of every hashprint: 62 464, two workgroups per CU
 constexpr float kQScale = 98304.0f;
+// six-product split: open values listed per tile of 128 hashprints, kQCap 16-bit entries (r << 7 | n - n0) each
+// (19 000 tiles of 1000 x 30 s clips: 4.9 MB of segments), kQRedo in place of a count above it
+constexpr int kQCap = 128;
+constexpr unsigned kQRedo = 0xffffffffu;
+constexpr int kQLdsBytes6 = kQLdsBytes + 16;                  // + the workgroup's count of open values
 
 // the three balanced base-256 digits of u as the three low bytes of one word (|u| < 2^23)
 __device__ __forceinline__ unsigned q_digit_bytes(int u) { return ((unsigned)u + 0x808080u) ^ 0x808080u; }
@@ -62,23 +69,32 @@ __device__ __forceinline__ int q_fixed(float s)
 // in turn running the matrix loop and the epilogue over it, hp [clip][image][nhp]: SHIFTED = false, the extraction's one
 // image; SHIFTED = true, n_images shifted ones (shift_filter_images_kernel).  dbg (tests only, NULL
 // in extraction; SHIFTED = false): D as int64 [clip][64][nhp].
-template <bool FROM_T, bool SHIFTED>
-__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
-                                                                   const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
-                                                                   uint64_t *__restrict__ hp, long long *__restrict__ dbg, int n_images)
+//
+// NP = 9: the nine digit products, D exactly.  NP = 6 (SHIFTED = false, no dbg): only the six products of weight >= 2^16.
+// With fq = a0 + 2^8 a1 + 2^16 a2 and Du = b0 + 2^8 b1 + 2^16 b2, D = 2^16 Dp + Dl where
+//   Dp = sum (a0 b2 + a1 b1 + a2 b0) + 2^8 sum (a1 b2 + a2 b1) + 2^16 sum a2 b2      (accumulators 2, 3, 4)
+//   Dl = sum a0 b0 + 2^8 sum (a0 b1 + a1 b0)                                          (accumulators 0, 1)
+// and every |b| <= 128, so |Dl| <= 128 S0_r + 2^8 128 (S0_r + S1_r) = Lmax_r with S0_r, S1_r the sums of |a0| and |a1| over
+// row r's 2420 taps.  Where 2^16 |Dp| > Lmax_r the sign of D is the sign of Dp (and D != 0); a row with Lmax_r = 0 has
+// D = 2^16 Dp exactly.  Else the value is OPEN: the bit from Dp >= 0 stands for the moment and hashprint_q_fixup_kernel
+// recomputes D.  thr[r] = floor(Lmax_r / 2^16), or -1 for Lmax_r = 0: open iff |Dp| <= thr[r] (pack_filters_q).  The
+// workgroup writes counts[t] = its number of open values and, up to kQCap of them, their entries to seg[t][..]; above
+// that counts[t] = kQRedo.  A slab of zero digits (silence, the -80 dB floor) has D = 0 everywhere: all bits one, count 0.
+template <bool FROM_T, bool SHIFTED, int NP>
+__device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
+                                                 const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, uint64_t *__restrict__ hp,
+                                                 long long *__restrict__ dbg, int n_images, const int *__restrict__ thr,
+                                                 unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
 {
+    static_assert(NP == 9 || (NP == 6 && !SHIFTED), "six products: the extraction's unshifted image only");
     unsigned char *slab = smem_raw;                                   // [chunk][column (pitch 160)][digit][16]
     unsigned short *parts = reinterpret_cast<unsigned short *>(smem_raw + kQSlabBytes); // [hashprint][wave]
+    unsigned *n_open = reinterpret_cast<unsigned *>(smem_raw + kQLdsBytes);             // (NP = 6)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kg = lane >> 4, cl = lane & 15;  // this lane's group of 16 k' inside a step; its column (B) / filter (A) in a tile
-    // Workgroups go to the eight XCDs in turn (id mod 8), each with an L2 of its own: an XCD takes a contiguous run of
-    // (clip, tile) pairs with the tile fastest, so that the 99 columns two neighbouring tiles share, and the columns a
-    // tile reads twice (as c and as c + 80), come from HBM once: 2.34 -> 1.19 MB per clip by the counters (1.17 algorithmic; profiles/r04_pmc.json)
-    const unsigned per_xcd = (gridDim.x + 7) / 8;
-    const unsigned t = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
     const int clip = t / n_tiles_x;
     const int n0 = (t - clip * n_tiles_x) * kQTileN;
+    if (NP == 6 && tid == 0) *n_open = 0; // (before the prologue barrier)
 #if defined(HPFW_Q_STAMPS)
     // diagnosis build (tools/q_stamps.py): s_memtime of wave 0 at the phase boundaries, written to dbg [workgroup][8]
     long long st[6];
@@ -100,6 +116,7 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
     // slab: one (chunk, column) unit = 16 bins of one column of Du, three digit planes.  The loads of a round (16 bins x
     // the column and its partner 80 on) are all issued before the first value is quantised
     constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
+    unsigned any_digit = 0; // (NP = 6) whether this thread stored a non-zero digit
 #pragma unroll 1
     for (int r0 = 0; r0 < kUnits; r0 += 2) {
         float va[2][16], vb[2][16];
@@ -158,10 +175,21 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
             dst[0] = v4i{(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3]};
             dst[1] = v4i{(int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
             dst[2] = v4i{(int)w2[0], (int)w2[1], (int)w2[2], (int)w2[3]};
+            if (NP == 6)
+                any_digit |= w0[0] | w0[1] | w0[2] | w0[3] | w1[0] | w1[1] | w1[2] | w1[3] | w2[0] | w2[1] | w2[2] | w2[3];
         }
     }
     Q_STAMP(1);
-    __syncthreads(); // the only barrier before the epilogue: the slab is read-only from here on
+    // the only barrier before the epilogue: the slab is read-only from here on
+    if (NP == 6) {
+        if (!__syncthreads_or((int)(any_digit != 0))) { // Du = 0 in the whole slab: D = 0, every bit one, nothing open
+            if (tid < kQTileN && n0 + tid < nhp) hp[(int64_t)clip * nhp + n0 + tid] = ~0ull;
+            if (tid == 0) counts[t] = 0;
+            return;
+        }
+    } else {
+        __syncthreads();
+    }
     Q_STAMP(2);
     // tiles of 16 hashprints that hold any (the last workgroup of a clip); the products of the others are skipped
     const int n_tiles = min(8, (nhp - n0 + 15) / 16);
@@ -208,12 +236,14 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
                     }
                     __builtin_amdgcn_sched_barrier(0); // (the scheduler would sink the reads back to where they are used)
                     // filter digit i times spectrogram digit j goes to accumulator i + j
-                    acc[f][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b0, acc[f][0], 0, 0, 0);
-                    acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b1, acc[f][1], 0, 0, 0);
+                    if (NP == 9) {
+                        acc[f][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b0, acc[f][0], 0, 0, 0);
+                        acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b1, acc[f][1], 0, 0, 0);
+                    }
                     acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b2, acc[f][2], 0, 0, 0);
                     acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b2, acc[f][3], 0, 0, 0);
                     acc[f][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b2, acc[f][4], 0, 0, 0);
-                    acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b0, acc[f][1], 0, 0, 0);
+                    if (NP == 9) acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b0, acc[f][1], 0, 0, 0);
                     acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b1, acc[f][2], 0, 0, 0);
                     acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b1, acc[f][3], 0, 0, 0);
                     acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b0, acc[f][2], 0, 0, 0);
@@ -240,6 +270,8 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
         }
         Q_STAMP(3);
         // S10q: D = sum_c acc_c 2^(8c); D layout of the 16x16 tile: column (hashprint) = lane & 15, row (filter) = 4 (lane >> 4) + reg
+        v4i th = v4i{-1, -1, -1, -1};
+        if (NP == 6) th = *reinterpret_cast<const v4i *>(thr + 16 * wave + 4 * kg);
 #pragma unroll
         for (int f = 0; f < 8; ++f) {
             const int n = n0 + 16 * f + cl;
@@ -250,8 +282,12 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
                 const int row = 4 * kg + reg;
                 long long v = acc[f][4][reg];
 #pragma unroll
-                for (int cls = 3; cls >= 0; --cls) v = v * 256 + acc[f][cls][reg];
+                for (int cls = 3; cls >= (NP == 9 ? 0 : 2); --cls) v = v * 256 + acc[f][cls][reg]; // (NP = 6: Dp)
                 bits |= (unsigned)(v >= 0) << (15 - row);
+                if (NP == 6 && f < n_tiles && n < nhp && (v < 0 ? -v : v) <= (long long)th[reg]) {
+                    const unsigned pos = atomicAdd(n_open, 1u);
+                    if (pos < (unsigned)kQCap) seg[(size_t)t * kQCap + pos] = (unsigned short)(((16 * wave + row) << 7) | (16 * f + cl));
+                }
 #if !defined(HPFW_Q_STAMPS)
                 if (!SHIFTED && dbg && f < n_tiles && n < nhp) dbg[((int64_t)clip * kFilters + 16 * wave + row) * nhp + n] = v;
 #endif
@@ -268,6 +304,7 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
             hp[((int64_t)clip * (SHIFTED ? n_images : 1) + im) * nhp + n0 + tid] =
                 ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
         }
+        if (NP == 6 && tid == 0) counts[t] = *n_open <= (unsigned)kQCap ? *n_open : kQRedo;
     } while (SHIFTED && ++im < n_images);
 #if defined(HPFW_Q_STAMPS)
     Q_STAMP(5);
@@ -277,6 +314,88 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
         dbg[(int64_t)t * 8 + 7] = blockIdx.x;
     }
 #endif
+}
+
+// Workgroups go to the eight XCDs in turn (id mod 8), each with an L2 of its own: an XCD takes a contiguous run of
+// (clip, tile) pairs with the tile fastest, so that the 99 columns two neighbouring tiles share, and the columns a
+// tile reads twice (as c and as c + 80), come from HBM once: 2.34 -> 1.19 MB per clip by the counters (1.17 algorithmic; profiles/r04_pmc.json)
+__device__ __forceinline__ unsigned q_tile_of_workgroup()
+{
+    const unsigned per_xcd = (gridDim.x + 7) / 8;
+    return (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+}
+
+template <bool FROM_T, bool SHIFTED>
+__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
+                                                                   const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
+                                                                   uint64_t *__restrict__ hp, long long *__restrict__ dbg, int n_images)
+{
+    const unsigned t = q_tile_of_workgroup();
+    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
+    hashprint_q_tile<FROM_T, SHIFTED, 9>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, dbg, n_images, nullptr, nullptr, nullptr);
+}
+
+// the six-product instantiation of the extraction's kernel (hashprint_q_tile): bits from Dp, the open values listed
+template <bool FROM_T>
+__global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
+                                                                    const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
+                                                                    uint64_t *__restrict__ hp, const int *__restrict__ thr,
+                                                                    unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
+{
+    const unsigned t = q_tile_of_workgroup();
+    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
+    hashprint_q_tile<FROM_T, false, 6>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, seg);
+}
+
+// The fix-up of a six-product launch, after it on the same stream: workgroups take the tiles in turn.  A tile with
+// listed open values: one wave per entry (r, n) forms D[r][n] = sum_k fq[r][k] Du[k / 20][n + k % 20] exactly in int64
+// -- fq32 [64][2420], Du from the dB terms as the staging quantises them -- and flips bit 63 - r of hp[n] where D >= 0
+// disagrees with it.  A tile marked kQRedo: the nine-product body over the whole tile.
+template <bool FROM_T>
+__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_fixup_kernel(const v4i *__restrict__ fq_image, const int *__restrict__ fq32,
+                                                                         const float *__restrict__ sdb, const float *__restrict__ tmax, int c,
+                                                                         int nhp, int n_tiles_x, int n_clips, uint64_t *__restrict__ hp,
+                                                                         const unsigned *__restrict__ counts,
+                                                                         const unsigned short *__restrict__ seg)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned total = (unsigned)(n_tiles_x * n_clips);
+    for (unsigned t = blockIdx.x; t < total; t += gridDim.x) {
+        const unsigned cnt = counts[t]; // (the same for the whole workgroup)
+        if (cnt == 0) continue;
+        if (cnt == kQRedo) {
+            __syncthreads(); // (the slab and parts of a tile redone before)
+            hashprint_q_tile<FROM_T, false, 9>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr, nullptr);
+            continue;
+        }
+        const int clip = t / n_tiles_x;
+        const int n0 = (t - clip * n_tiles_x) * kQTileN;
+        const float *S = sdb + (int64_t)clip * kBins * c;
+        const float ref = FROM_T ? tmax[clip] : 0.0f;
+        for (unsigned e = wave; e < cnt; e += kQThreads / 64) {
+            const unsigned entry = seg[(size_t)t * kQCap + e];
+            const int r = entry >> 7, n = n0 + (int)(entry & 127u); // (n < nhp: n + 19 + kLag < c)
+            const int *frow = fq32 + r * kFrame;
+            long long sum = 0;
+#pragma unroll 2
+            for (int k = lane; k < kFrame; k += 64) {
+                const int bin = k / kCtx, idx = bin * c + n + (k - bin * kCtx);
+                float xa = S[idx], xb = S[idx + kLag];
+                if (FROM_T) {
+                    xa -= ref;
+                    xb -= ref;
+                }
+                sum += (long long)frow[k] * (long long)(q_fixed(xa) - q_fixed(xb));
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+            if (lane == 0) {
+                unsigned long long *w = reinterpret_cast<unsigned long long *>(hp + (int64_t)clip * nhp + n);
+                const unsigned long long bit = 1ull << (63 - r);
+                if (((*w & bit) != 0) != (sum >= 0)) atomicXor(w, bit);
+            }
+        }
+    }
 }
 
 // Image i (blockIdx.y) of the filters moved by shifts.s[i] bins: the byte of bin b holds the digit of fq[r][20 (b - s) + t]
@@ -306,7 +425,10 @@ __global__ __launch_bounds__(256) void shift_filter_images_kernel(const unsigned
 
 // host: the filters' digits as the A operand of v_mfma_i32_16x16x64_i8, [wave][step s = 2 t + p][digit][lane][16 bytes]:
 // byte e of lane l = digit of fq[row = 16 wave + (l & 15)][k = 20 bin + t], bin = 64 p + 16 (l >> 4) + e (zero for bin >= 121)
-void pack_filters_q(const float *f, std::vector<int8_t> &image)
+// fq_thr, when given: fq as int32 [64][2420] (k = 20 bin + t), then the 64 thresholds of the six-product split: floor(Lmax_r /
+// 2^16) with Lmax_r = 128 (S0_r + 256 (S0_r + S1_r)), S0_r and S1_r the sums of |digit 0| and |digit 1| of row r's taps,
+// or -1 where Lmax_r = 0 (hashprint_q_tile)
+void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int32_t> *fq_thr)
 {
     std::vector<int32_t> fq((size_t)kFilters * kFrame);
     for (int r = 0; r < kFilters; ++r) {
@@ -314,6 +436,20 @@ void pack_filters_q(const float *f, std::vector<int8_t> &image)
         for (int k = 0; k < kFrame; ++k) m = std::fmax(m, std::fabs(f[(size_t)k * kFilters + r]));
         const int e = m > 0.0f ? 21 - std::ilogb(m) : 0;
         for (int k = 0; k < kFrame; ++k) fq[(size_t)r * kFrame + k] = (int32_t)std::rint(std::ldexp(f[(size_t)k * kFilters + r], e));
+    }
+    if (fq_thr) {
+        fq_thr->assign(fq.begin(), fq.end());
+        for (int r = 0; r < kFilters; ++r) {
+            int64_t s0 = 0, s1 = 0;
+            for (int k = 0; k < kFrame; ++k) {
+                const int u = fq[(size_t)r * kFrame + k];
+                const int d0 = ((u + 128) & 255) - 128, u1 = (u - d0) >> 8, d1 = ((u1 + 128) & 255) - 128;
+                s0 += std::abs(d0);
+                s1 += std::abs(d1);
+            }
+            const int64_t lmax = 128 * (s0 + 256 * (s0 + s1)); // <= 128 * 128 * 2420 * 513 < 2^35
+            fq_thr->push_back(lmax > 0 ? (int32_t)(lmax >> 16) : -1);
+        }
     }
     image.assign((size_t)4 * kQSteps * kQStepBytes, 0);
     for (int w = 0; w < 4; ++w)
@@ -337,19 +473,31 @@ extern "C" void hpfw_gpu_debug_set_q_stamps(void *d) { g_q_stamps = static_cast<
 #endif
 
 size_t project_q_image_bytes() { return (size_t)4 * kQSteps * kQStepBytes; }
+size_t project_q_split_bytes(int64_t tiles) { return (size_t)tiles * (4 + (size_t)kQCap * 2); }
+int64_t project_q_tiles(int64_t n_clips, int64_t c)
+{
+    const int64_t nhp = c - (kCtx - 1) - kLag;
+    return nhp > 0 ? n_clips * ((nhp + kQTileN - 1) / kQTileN) : 0;
+}
 
 // dB terms (d_tmax != NULL) or dB spectrograms -> hashprints [n_clips][max(n_shifts, 1)][c - 99] of the filter images at
 // d_images: the unshifted one (n_shifts = 0), or n_shifts from launch_shift_filter_images.  One shift runs the image loop
 // too: 2.14 ms against 2.15 for the extraction's instance on 1000 x 30 s clips (profiles/transpose.json).  d_dbg: NULL,
 // or D [n_clips][64][c - 99] of the unshifted image (tests)
+// split (n_shifts = 0, no d_dbg; else NULL): the six-product kernel and its fix-up instead of the nine-product kernel.
+// d_fq_thr: the device copy of pack_filters_q's fq_thr; d_work: project_q_split_bytes(project_q_tiles(n_clips, c)) bytes,
+// counts [tiles] then segments [tiles][kQCap]
 void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
-                         long long *d_dbg, hipStream_t s)
+                         long long *d_dbg, hipStream_t s, const QSplit *split)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
         for (const void *k : {reinterpret_cast<const void *>(hashprint_q_kernel<true, false>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false>),
                               reinterpret_cast<const void *>(hashprint_q_kernel<true, true>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes);
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_kernel<false>),
+                              reinterpret_cast<const void *>(hashprint_q_fixup_kernel<true>), reinterpret_cast<const void *>(hashprint_q_fixup_kernel<false>)})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6);
         attr_set.mark();
     }
     const int nhp = c - (kCtx - 1) - kLag;
@@ -359,6 +507,18 @@ void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, 
 #endif
     const int tiles = (nhp + kQTileN - 1) / kQTileN;
     const dim3 grid(8 * (unsigned)(((int64_t)tiles * n_clips + 7) / 8)); // one-dimensional, in XCD-aware order
+    if (split && n_shifts == 0 && !d_dbg) {
+        const int *fq32 = split->d_fq_thr, *thr = fq32 + (size_t)kFilters * kFrame;
+        unsigned *counts = static_cast<unsigned *>(split->d_work);
+        unsigned short *seg = reinterpret_cast<unsigned short *>(counts + (size_t)tiles * n_clips);
+        hipLaunchKernelGGL(d_tmax ? hashprint_q6_kernel<true> : hashprint_q6_kernel<false>, grid, dim3(kQThreads), kQLdsBytes6, s,
+                           static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, thr, counts, seg);
+        // eight workgroups per CU share the tiles: few enough that none is launched for nothing, enough to hide the loads
+        const unsigned fix = (unsigned)std::min<int64_t>((int64_t)tiles * n_clips, 2048);
+        hipLaunchKernelGGL(d_tmax ? hashprint_q_fixup_kernel<true> : hashprint_q_fixup_kernel<false>, dim3(fix), dim3(kQThreads), kQLdsBytes6, s,
+                           static_cast<const v4i *>(d_images), fq32, d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, counts, seg);
+        return;
+    }
     auto k = n_shifts > 0 ? (d_tmax ? hashprint_q_kernel<true, true> : hashprint_q_kernel<false, true>)
                           : (d_tmax ? hashprint_q_kernel<true, false> : hashprint_q_kernel<false, false>);
     hipLaunchKernelGGL(k, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,

@@ -432,9 +432,14 @@ int hpfw_gpu_extract_tempo_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_sa
 int hpfw_gpu_extract_tempo_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips, const float *tempos,
                                       int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp);
 /* parity checkpoint of mode 1: the exact integer sums D[r][i] = sum_k fq[r][k] (u[k][i] - u[k][i + 80]) whose signs are
- * the hashprint bits, d_delta [n_clips][64][c - 99] int64 (device); d_hp may be NULL.  Same kernel as extraction. */
+ * the hashprint bits, d_delta [n_clips][64][c - 99] int64 (device); d_hp may be NULL.  The nine-product kernel, which
+ * the extraction runs under HPFW_Q_PRODUCTS=9. */
 int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t c, int64_t *d_delta, uint64_t *d_hp,
                            void *stream);
+/* the six-product split (the default of mode 1's unshifted extraction; HPFW_Q_PRODUCTS=9 in the environment when the handle
+ * is created switches it off): of the last such launch on this handle, its tiles of 128 hashprints, the values listed
+ * for exact recomputation and the tiles redone with nine products.  Waits for the device; zeros without such a launch. */
+int hpfw_gpu_debug_q_products(hpfw_gpu *h, int64_t *tiles, int64_t *listed, int64_t *redone);
 
 /* ---- timeline of a long recording: scored search, windows of one recording, segments.
  *
