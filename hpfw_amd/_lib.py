@@ -70,7 +70,8 @@ EXPORTS = (
     "hpfw_gpu_merge_topk_device", "hpfw_gpu_sum_stats_device", "hpfw_gpu_get_filters",
     "hpfw_gpu_streams_create", "hpfw_gpu_streams_destroy", "hpfw_gpu_streams_push", "hpfw_gpu_streams_push_device",
     "hpfw_gpu_streams_room", "hpfw_gpu_streams_extract", "hpfw_gpu_streams_extract_host", "hpfw_gpu_streams_reset",
-    "hpfw_gpu_streams_info", "hpfw_gpu_timeline_tracker_create", "hpfw_gpu_timeline_tracker_destroy",
+    "hpfw_gpu_streams_info", "hpfw_gpu_streams_create_rates", "hpfw_gpu_streams_rates", "hpfw_gpu_streams_emitted",
+    "hpfw_gpu_timeline_tracker_create", "hpfw_gpu_timeline_tracker_destroy",
     "hpfw_gpu_timeline_tracker_push", "hpfw_gpu_timeline_tracker_pop", "hpfw_gpu_timeline_tracker_open",
     "hpfw_gpu_timeline_tracker_finish",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
@@ -255,6 +256,9 @@ def lib():
     L.hpfw_gpu_merge_topk_device.argtypes = [vp, vp, i32, i64, i32, vp, vp]
     L.hpfw_gpu_sum_stats_device.argtypes = [vp, vp, i32, i64, vp, vp]
     L.hpfw_gpu_streams_create.argtypes = [vp, ctypes.POINTER(StreamsParams), ctypes.POINTER(vp)]
+    L.hpfw_gpu_streams_create_rates.argtypes = [vp, ctypes.POINTER(StreamsParams), vp, ctypes.POINTER(vp)]
+    L.hpfw_gpu_streams_rates.argtypes = [vp, vp, vp]
+    L.hpfw_gpu_streams_emitted.argtypes = [i64, i32, ctypes.POINTER(i64)]
     L.hpfw_gpu_streams_destroy.argtypes = [vp]
     L.hpfw_gpu_streams_destroy.restype = None
     L.hpfw_gpu_streams_push.argtypes = [vp, vp, vp, ctypes.POINTER(i64)]
@@ -582,9 +586,10 @@ class Gpu:
     hit_score = staticmethod(hit_score)
     timeline_segments = staticmethod(timeline_segments)
 
-    def streams(self, n_streams, win, hop, capacity=0, tempos=None, shifts=None):
-        """a set of live feeds on this handle: GpuStreams"""
-        return GpuStreams(self, n_streams, win, hop, capacity, tempos, shifts)
+    def streams(self, n_streams, win, hop, capacity=0, tempos=None, shifts=None, rates=None):
+        """a set of live feeds on this handle: GpuStreams.  rates: the feeds' sample rate, one int for
+        all or one per feed (None: 44 100 Hz); win, hop and capacity are in 44.1 kHz samples whatever the rates"""
+        return GpuStreams(self, n_streams, win, hop, capacity, tempos, shifts, rates)
 
     # ---- sample-rate conversion to 44.1 kHz (k_resample.hip) --------------------------------
     def resample_dev(self, d_in, n_in, n_clips, rate, d_out, stream=0):
@@ -959,21 +964,36 @@ class Gpu:
 class GpuStreams:
     """hpfw_gpu_streams: n_streams rings of `capacity` samples on a Gpu handle; push() appends chunks, extract() hashes the
     windows [w hop, w hop + win) that have become complete, bit for bit what Gpu.extract_windows gives for the feed so far.
-    Close it before its Gpu."""
+    A feed at another rate than 44 100 Hz (rates) is converted chunk by chunk on its way into the ring: its ring holds the
+    first emitted() samples of Gpu.resample of everything pushed, and push, push_dev and room count in samples at the feed's
+    rate.  Close it before its Gpu."""
 
-    def __init__(self, gpu, n_streams, win, hop, capacity=0, tempos=None, shifts=None):
+    def __init__(self, gpu, n_streams, win, hop, capacity=0, tempos=None, shifts=None, rates=None):
         self._t = None if tempos is None else np.ascontiguousarray(tempos, np.float32).ravel()
         self._sh = None if shifts is None else np.ascontiguousarray(shifts, np.int32).ravel()
         p = StreamsParams(int(n_streams), 0 if self._t is None else self._t.size, 0 if self._sh is None else self._sh.size, 0, int(win),
                           int(hop), int(capacity), None if self._t is None else _hp(self._t), None if self._sh is None else _hp(self._sh))
         self._s = ctypes.c_void_p()
         self._gpu = gpu                                   # (keeps the handle alive as long as the set)
-        check(lib().hpfw_gpu_streams_create(gpu._h, ctypes.byref(p), ctypes.byref(self._s)))
+        if rates is not None:
+            rates = np.clip(np.asarray(rates, np.int64), -1, 2 ** 31 - 1).astype(np.int32)
+            rates = np.full(int(n_streams), rates, np.int32) if rates.ndim == 0 else np.ascontiguousarray(rates).ravel()
+            if rates.size != int(n_streams):
+                raise ValueError("one rate per feed")
+        check(lib().hpfw_gpu_streams_create_rates(gpu._h, ctypes.byref(p), None if rates is None else _hp(rates), ctypes.byref(self._s)))
         info = StreamsInfo()
         check(lib().hpfw_gpu_streams_info(self._s, ctypes.byref(info), None, None))
         self.n_streams, self.win, self.hop, self.capacity = info.n_streams, info.win, info.hop, info.capacity
         self.per_window, self.n_sets = info.per_window, info.n_sets
         self.variants = tempos is not None or shifts is not None
+        self.rates = np.zeros(self.n_streams, np.int32)
+        check(lib().hpfw_gpu_streams_rates(self._s, _hp(self.rates), None))
+
+    def emitted(self):
+        """per feed the 44.1 kHz samples its ring has received so far (the samples pushed, for a 44.1 kHz feed)"""
+        out = np.zeros(self.n_streams, np.int64)
+        check(lib().hpfw_gpu_streams_rates(self._s, None, _hp(out)))
+        return out
 
     def close(self):
         if getattr(self, "_s", None):
@@ -1011,6 +1031,7 @@ class GpuStreams:
         return n.value
 
     def room(self):
+        """the samples every feed can take now, at the feed's rate"""
         out = np.zeros(self.n_streams, np.int64)
         check(lib().hpfw_gpu_streams_room(self._s, _hp(out)))
         return out
@@ -1022,8 +1043,8 @@ class GpuStreams:
         return n, e
 
     def ready(self):
-        n, e = self.info()
-        return int(sum(window_count(int(a), self.win, self.hop) - int(b) for a, b in zip(n, e)))
+        e = self.info()[1]
+        return int(sum(window_count(int(a), self.win, self.hop) - int(b) for a, b in zip(self.emitted(), e)))
 
     def _hp_shape(self, n):
         return (n, self.n_sets, self.per_window // self.n_sets) if self.variants else (n, self.per_window)
@@ -1102,6 +1123,20 @@ def resample_length(n_in, rate):
     n = ctypes.c_int64(0)
     check(lib().hpfw_gpu_resample_length(int(n_in), int(rate), ctypes.byref(n)))
     return int(n.value)
+
+
+def streams_emitted(n_in, rate):
+    """the 44.1 kHz samples a live feed at `rate` has been given after n_in input samples (hpfw_gpu_streams_emitted)"""
+    n = ctypes.c_int64()
+    check(lib().hpfw_gpu_streams_emitted(int(n_in), int(rate), ctypes.byref(n)))
+    return n.value
+
+
+def streams_tail(rate):
+    """H of the filter of `rate` (T = 2 H taps per phase; 0 at 44 100 Hz): emitted(n + H) = resample_length(n)"""
+    L, M, T = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    check(lib().hpfw_gpu_resample_table(int(rate), None, 0, ctypes.byref(L), ctypes.byref(M), ctypes.byref(T)))
+    return T.value // 2
 
 
 def resample_table(rate):

@@ -980,6 +980,30 @@ int hpfw_gpu_resample_table(int rate, int16_t *taps, int64_t cap, int32_t *L, in
     return 0;
 }
 
+} // extern "C"
+
+int rs_table(hpfw_gpu *h, int rate, hpfw_gpu::Resample::Table **out)
+{
+    hpfw_gpu::Resample::Table &t = h->rs.tables[rate];
+    if (!t.d_taps) { // once per rate (published only when complete)
+        std::vector<int16_t> taps;
+        int32_t L, M, T;
+        if (!hpfw::resample_design(rate, taps, &L, &M, &T)) return fail(HPFW_E_INVALID, "resampling table out of range");
+        const std::vector<int32_t> img = hpfw::resample_device_table(taps, L, T);
+        DevBuf d;
+        HIP_TRY(d.alloc(img.size() * 4));
+        HIP_TRY(hipMemcpy(d.get(), img.data(), img.size() * 4, hipMemcpyHostToDevice));
+        t.L = L;
+        t.M = M;
+        t.T = T;
+        t.d_taps = std::move(d);
+    }
+    *out = &t;
+    return 0;
+}
+
+extern "C" {
+
 int hpfw_gpu_resample_pcm16(hpfw_gpu *h, const int16_t *d_in, int64_t n_in, int64_t n_clips, int rate, int16_t *d_out, void *stream)
 {
     if (!h || n_in < 0 || n_clips < 0 || ((!d_in || !d_out) && n_in > 0 && n_clips > 0)) return fail(HPFW_E_INVALID, "bad argument");
@@ -987,23 +1011,7 @@ int hpfw_gpu_resample_pcm16(hpfw_gpu *h, const int16_t *d_in, int64_t n_in, int6
     if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hpfw_gpu::Resample::Table *tab = nullptr;
-    if (rate != hpfw::kRsRateOut) {
-        hpfw_gpu::Resample::Table &t = h->rs.tables[rate];
-        if (!t.d_taps) { // once per rate (published only when complete)
-            std::vector<int16_t> taps;
-            int32_t L, M, T;
-            if (!hpfw::resample_design(rate, taps, &L, &M, &T)) return fail(HPFW_E_INVALID, "resampling table out of range");
-            const std::vector<int32_t> img = hpfw::resample_device_table(taps, L, T);
-            DevBuf d;
-            HIP_TRY(d.alloc(img.size() * 4));
-            HIP_TRY(hipMemcpy(d.get(), img.data(), img.size() * 4, hipMemcpyHostToDevice));
-            t.L = L;
-            t.M = M;
-            t.T = T;
-            t.d_taps = std::move(d);
-        }
-        tab = &t;
-    }
+    if (rate != hpfw::kRsRateOut && (rc = rs_table(h, rate, &tab))) return rc;
     if (n_in == 0 || n_clips == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     return ordered_call(h, s, [&] {

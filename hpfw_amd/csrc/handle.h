@@ -344,4 +344,6 @@ int q_split(hpfw_gpu *h, int n_shifts, int64_t n_clips, int64_t c, hpfw::QSplit 
 int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips);
 int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns);
 int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, bool finish_db, hipStream_t s);
+// the device image of the table of `rate` (not 44 100 Hz, inside the range), made and cached on first use; the device is set
+int rs_table(hpfw_gpu *h, int rate, hpfw_gpu::Resample::Table **out);
 

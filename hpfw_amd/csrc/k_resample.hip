@@ -8,24 +8,18 @@
 //                       lane l computes outputs l, l + 256, ... of the pass: T int16 products per output on
 //                       v_dot2_i32_i16, sample pairs realigned with v_alignbit_b32 when the first tap's sample is odd.
 //                       The taps live in LDS when they fit beside the samples (staged once per workgroup), else they
-//                       are read from device memory.
+//                       are read from device memory.  What it shares with the kernel of live feeds (the staging, one
+//                       output's products) is in resample_dev.h.
 #include <cmath>
 #include <algorithm>
 #include <numeric>
 
 #include "kernels.h"
+#include "resample_dev.h"
 
 namespace hpfw {
 
 namespace {
-
-constexpr int kRsThreads = 256;
-constexpr int kRsPerLane = 8;
-constexpr int kRsTile = kRsThreads * kRsPerLane; // outputs per pass
-constexpr int kRsPasses = 8;                      // passes per workgroup (the table is staged once for them)
-constexpr size_t kRsLdsMax = 64 * 1024;           // table + samples in LDS up to this
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 double bessel_i0(double x)
 {
@@ -117,39 +111,6 @@ struct RsArgs {
     uint32_t span_cap;     // int16 slots of the sample buffer in LDS
 };
 
-// samples [lo, lo + span) of clip x into s, zeros outside [0, n)
-__device__ void stage_span(const int16_t *__restrict__ x, int64_t n, int64_t lo, int span, int16_t *s)
-{
-    const int64_t g0 = lo < 0 ? 0 : lo, g1 = lo + span < n ? lo + span : n; // the part inside the clip
-    int64_t v0 = g1, nv = 0;                                               // 16-byte-aligned chunks [v0, v0 + 8 nv)
-    if (g0 < g1 && !((uintptr_t)(x + g0) & 1)) {
-        v0 = g0 + (int64_t)((16 - ((uintptr_t)(x + g0) & 15)) & 15) / 2;
-        nv = v0 < g1 ? (g1 - v0) / 8 : 0;
-    }
-    const int64_t v1 = v0 + 8 * nv;
-    for (int j = threadIdx.x; j < span; j += kRsThreads) {
-        const int64_t gi = lo + j;
-        if (gi < g0 || gi >= g1) s[j] = 0;
-        else if (gi < v0 || gi >= v1) s[j] = x[gi];
-    }
-    const int4 *xv = reinterpret_cast<const int4 *>(x + v0);
-    for (int64_t v = threadIdx.x; v < nv; v += kRsThreads) {
-        const int4 q = xv[v];
-        int16_t *d = s + (v0 - lo) + 8 * v;
-        const int w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            d[2 * i] = (int16_t)(w[i] & 0xffff);
-            d[2 * i + 1] = (int16_t)((uint32_t)w[i] >> 16);
-        }
-    }
-}
-
-__device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), acc, false);
-}
-
 template <bool kTabLds>
 __global__ __launch_bounds__(kRsThreads) void resample_kernel(RsArgs a)
 {
@@ -184,25 +145,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(RsArgs a)
         uint32_t k = t0 / a.L, p = t0 - k * a.L;
         for (int r = 0; r < kRsPerLane; ++r) {
             const int64_t m = m0 + threadIdx.x + (int64_t)r * kRsThreads;
-            if (m < a.n_out) {
-                const uint32_t *xs = sw + (k >> 1);
-                const uint32_t sh = (k & 1) * 16; // odd first sample: each pair straddles two words
-                const int4 *row = tab + (size_t)p * chunks;
-                int acc = 0;
-                uint32_t prev = xs[0];
-                for (int c = 0; c < chunks; ++c) {
-                    const int4 tv = row[c];
-                    const uint32_t w1 = xs[4 * c + 1], w2 = xs[4 * c + 2], w3 = xs[4 * c + 3], w4 = xs[4 * c + 4];
-                    acc = dot2(__builtin_amdgcn_alignbit(w1, prev, sh), (uint32_t)tv.x, acc);
-                    acc = dot2(__builtin_amdgcn_alignbit(w2, w1, sh), (uint32_t)tv.y, acc);
-                    acc = dot2(__builtin_amdgcn_alignbit(w3, w2, sh), (uint32_t)tv.z, acc);
-                    acc = dot2(__builtin_amdgcn_alignbit(w4, w3, sh), (uint32_t)tv.w, acc);
-                    prev = w4;
-                }
-                int v = (acc + (1 << (kRsShift - 1))) >> kRsShift;
-                v = v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
-                y[m] = (int16_t)v;
-            }
+            if (m < a.n_out) y[m] = rs_output(sw, k, tab + (size_t)p * chunks, chunks);
             k += a.step_q;
             p += a.step_r;
             if (p >= a.L) {
@@ -234,9 +177,7 @@ bool launch_resample(const int16_t *d_in, int64_t n_in, int64_t n_clips, int32_t
     const uint64_t step = (uint64_t)kRsThreads * (uint64_t)M;
     a.step_q = (uint32_t)(step / (uint64_t)L);
     a.step_r = (uint32_t)(step % (uint64_t)L);
-    // the span of a pass: floor(m_last M / L) - floor(m0 M / L) + 2 rw + 2 <= ((tile - 1) M + L - 1) / L + 2 rw + 2
-    const uint64_t span_max = ((uint64_t)(kRsTile - 1) * M + L - 1) / L + 2ull * a.rw + 2;
-    a.span_cap = (uint32_t)((span_max + 7) / 8 * 8);
+    a.span_cap = rs_span_cap(L, M, a.rw);
     const size_t sample_bytes = (size_t)a.span_cap * 2, tab_bytes = (size_t)L * a.rw * 4;
     const bool tab_lds = tab_bytes + sample_bytes <= kRsLdsMax;
     const size_t lds = sample_bytes + (tab_lds ? tab_bytes : 0);

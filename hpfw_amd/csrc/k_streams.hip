@@ -2,7 +2,8 @@
 // feed i lives at slab[i capacity + t mod capacity].  Two copies carry every sample of a feed: the chunks of one push go from
 // the staging buffer into their rings (ring_append_kernel), and the windows that have become complete go from the rings into
 // clips back to back (ring_gather_windows_kernel), exactly what gather_windows_kernel gives for a linear recording, so that the
-// extraction of clips runs unchanged behind it.
+// extraction of clips runs unchanged behind it.  (The chunks of a feed at another rate than 44.1 kHz take another way into their
+// ring: k_streams_resample.hip.)
 //
 // Both follow k_windows.hip: the destination is cut into chunks of 8 samples (16 bytes, aligned: slab and workspace come from
 // hipMalloc), a lane writes one chunk with one 16-byte store, and the 8 source samples are read through a 2-byte-aligned copy

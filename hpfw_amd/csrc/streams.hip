@@ -1,6 +1,7 @@
 // streams.hip -- live feeds (include/hpfw_gpu.h): the rings' bookkeeping on the host, the push of chunks
-// into them and the extraction of the windows that have become complete.  The samples move in k_streams.hip; the gathered
-// windows of a pass go through the extraction of clips as the windows of a recording do (extract.hip).
+// into them and the extraction of the windows that have become complete.  The samples move in k_streams.hip, those of feeds at
+// another rate than 44.1 kHz through k_streams_resample.hip (the planning of a push: streams_plan.cpp); the gathered windows of
+// a pass go through the extraction of clips as the windows of a recording do (extract.hip).
 #include "handle.h"
 
 struct hpfw_gpu_streams {
@@ -9,8 +10,12 @@ struct hpfw_gpu_streams {
     int64_t win = 0, hop = 0, capacity = 0, per_window = 0;
     std::vector<float> tempos;
     std::vector<int32_t> shifts;
-    std::vector<int64_t> received, extracted; // n_i, e_i
-    DevBuf slab;                              // [n_streams][capacity] int16
+    std::vector<hpfw::RingFeed> feeds; // per feed its rate, n_i, e_i and which of its two histories is current
+    DevBuf slab;                       // [n_streams][capacity] int16
+    // feeds at another rate than 44.1 kHz: per feed two buffers of T - 1 input samples, the current one holding the samples in
+    // front of the next chunk; a push reads it and writes the other (k_streams_resample.hip).  The tables live on the handle
+    DevBuf hist;
+    std::map<int, hpfw_gpu::Resample::Table *> tables;
     // One table per call goes to the device from pinned memory behind the call's other work: the runs of a push (with the
     // chunks behind them in the host form: one upload), the windows of an extraction.  table_ev marks the end of the copy
     // that last read the pinned buffer; the next call waits for it before it writes there.
@@ -25,10 +30,12 @@ namespace {
 
 int64_t windows_of(int64_t n, int64_t win, int64_t hop) { return n < win ? 0 : (n - win) / hop + 1; }
 
+int64_t emitted(const hpfw::RingFeed &f) { return hpfw::ring_emitted(f.n, f.L, f.M, f.H); }
+
 int64_t ready_windows(const hpfw_gpu_streams *s)
 {
     int64_t n = 0;
-    for (int i = 0; i < s->n_streams; ++i) n += windows_of(s->received[(size_t)i], s->win, s->hop) - s->extracted[(size_t)i];
+    for (const hpfw::RingFeed &f : s->feeds) n += windows_of(emitted(f), s->win, s->hop) - f.e;
     return n;
 }
 
@@ -56,42 +63,47 @@ int upload(hpfw_gpu_streams *s, size_t bytes, hipStream_t st)
 int push(hpfw_gpu_streams *s, const int16_t *pcm, bool host, const int64_t *counts, int64_t *n_ready, hipStream_t st)
 {
     if (!s || !counts) return fail(HPFW_E_INVALID, "null argument");
-    int64_t total = 0;
-    for (int i = 0; i < s->n_streams; ++i) {
+    for (int i = 0; i < s->n_streams; ++i)
         if (counts[i] < 0) return fail(HPFW_E_INVALID, "streams: counts must not be negative");
-        if (s->received[(size_t)i] + counts[i] - s->extracted[(size_t)i] * s->hop > s->capacity)
-            return fail(HPFW_E_INVALID, "streams: the chunk of feed " + std::to_string(i) + " does not fit its ring (" + std::to_string(counts[i]) +
-                                            " samples, room for " +
-                                            std::to_string(s->capacity - (s->received[(size_t)i] - s->extracted[(size_t)i] * s->hop)) + ")");
-        total += counts[i];
-    }
+    // the plan of the push (streams_plan.cpp): the runs of the 44.1 kHz feeds, and per other rate the runs of its feeds
+    hpfw::RingPushPlan plan;
+    const int bad = hpfw::ring_plan_push(s->feeds, counts, s->hop, s->capacity, &plan);
+    if (bad >= 0)
+        return fail(HPFW_E_INVALID, "streams: the chunk of feed " + std::to_string(bad) + " does not fit its ring (" + std::to_string(counts[bad]) +
+                                        " samples, room for " + std::to_string(hpfw::ring_room(s->feeds[(size_t)bad], s->hop, s->capacity)) + ")");
+    const int64_t total = plan.total;
     if (total && !pcm) return fail(HPFW_E_INVALID, "null argument");
     if (total) {
         hpfw_gpu *h = s->h;
         HIP_TRY(hipSetDevice(h->device));
-        // a chunk is one run of the slab, or two when it passes its ring's end
-        std::vector<hpfw::RingRun> runs;
-        int64_t src = 0, longest = 0;
-        for (int i = 0; i < s->n_streams; ++i) {
-            const int64_t cnt = counts[i], at = s->received[(size_t)i] % s->capacity, base = (int64_t)i * s->capacity;
-            const int64_t first = std::min(cnt, s->capacity - at);
-            if (first) runs.push_back({src, base + at, first});
-            if (cnt > first) runs.push_back({src + first, base, cnt - first});
-            longest = std::max(longest, std::max(first, cnt - first));
-            src += cnt;
-        }
-        const size_t tab = (runs.size() * sizeof(hpfw::RingRun) + 15) & ~(size_t)15, bytes = tab + (host ? (size_t)total * 2 : 0);
+        // the tables of both kinds of run, then the chunks (16-byte aligned) in the host form
+        const size_t copy_bytes = (plan.copy.size() * sizeof(hpfw::RingRun) + 15) & ~(size_t)15;
+        const size_t tab = copy_bytes + ((plan.rs.size() * sizeof(hpfw::RingRsRun) + 15) & ~(size_t)15), bytes = tab + (host ? (size_t)total * 2 : 0);
         if (int rc = stage(s, bytes)) return rc;
-        std::memcpy(s->pin.get(), runs.data(), runs.size() * sizeof(hpfw::RingRun));
+        std::memcpy(s->pin.get(), plan.copy.data(), plan.copy.size() * sizeof(hpfw::RingRun));
+        std::memcpy(s->pin.as<char>() + copy_bytes, plan.rs.data(), plan.rs.size() * sizeof(hpfw::RingRsRun));
         if (host) std::memcpy(s->pin.as<char>() + tab, pcm, (size_t)total * 2);
         const int16_t *d_src = host ? reinterpret_cast<const int16_t *>(s->d_stage.as<char>() + tab) : pcm;
+        const hpfw::RingRsRun *d_rs = reinterpret_cast<const hpfw::RingRsRun *>(s->d_stage.as<char>() + copy_bytes);
         int rc = ordered_call(h, st, [&] {
             if (int e = upload(s, bytes, st)) return e;
-            hpfw::launch_ring_append(s->d_stage.as<hpfw::RingRun>(), (int)runs.size(), longest, d_src, s->slab.as<int16_t>(), st);
-            return check_launch("ring_append");
+            hpfw::launch_ring_append(s->d_stage.as<hpfw::RingRun>(), (int)plan.copy.size(), plan.copy_longest, d_src, s->slab.as<int16_t>(), st);
+            if (int e = check_launch("ring_append")) return e;
+            for (const hpfw::RingPushPlan::Group &g : plan.groups) {
+                const hpfw_gpu::Resample::Table *t = s->tables.at(g.rate);
+                if (!hpfw::launch_ring_resample_append(d_rs + g.first, g.n, g.most, d_src, s->slab.as<int16_t>(), s->hist.as<int16_t>(), t->L, t->M,
+                                                       t->T, t->d_taps.as<int32_t>(), st))
+                    return fail(HPFW_E_INVALID, "resampling: the table and its input span exceed the LDS");
+                if (int e = check_launch("ring_resample_append")) return e;
+            }
+            return 0;
         });
-        if (rc) return rc;
-        for (int i = 0; i < s->n_streams; ++i) s->received[(size_t)i] += counts[i];
+        if (rc) return rc; // (no feed has advanced: what the launches wrote lies behind the rings' ends and in the histories not in use)
+        for (int i = 0; i < s->n_streams; ++i) {
+            hpfw::RingFeed &f = s->feeds[(size_t)i];
+            if (counts[i] && f.H) f.cur ^= 1;
+            f.n += counts[i];
+        }
     }
     if (n_ready) *n_ready = ready_windows(s);
     return 0;
@@ -103,8 +115,17 @@ extern "C" {
 
 int hpfw_gpu_streams_create(hpfw_gpu *h, const hpfw_streams_params *p, hpfw_gpu_streams **out)
 {
+    return hpfw_gpu_streams_create_rates(h, p, nullptr, out);
+}
+
+int hpfw_gpu_streams_create_rates(hpfw_gpu *h, const hpfw_streams_params *p, const int32_t *rates, hpfw_gpu_streams **out)
+{
     if (!p || !out) return fail(HPFW_E_INVALID, "null argument");
     if (p->n_streams < 1 || p->n_streams > 4096) return fail(HPFW_E_INVALID, "streams: n_streams must be 1 to 4096");
+    for (int i = 0; rates && i < p->n_streams; ++i)
+        if (rates[i] < hpfw::kRsRateMin || rates[i] > hpfw::kRsRateMax)
+            return fail(HPFW_E_UNSUPPORTED, "streams: the sample rate of feed " + std::to_string(i) + ", " + std::to_string(rates[i]) +
+                                                " Hz, is outside [8000, 192000]");
     int64_t none;
     int rc = hpfw_gpu_window_count(0, p->win, p->hop, &none);
     if (rc) return rc;
@@ -132,11 +153,23 @@ int hpfw_gpu_streams_create(hpfw_gpu *h, const hpfw_streams_params *p, hpfw_gpu_
     if (p->tempos) s->tempos.assign(p->tempos, p->tempos + p->n_tempos);
     if (p->shifts) s->shifts.assign(p->shifts, p->shifts + p->n_shifts);
     s->per_window = (int64_t)std::max<size_t>(s->tempos.size(), 1) * (int64_t)std::max<size_t>(s->shifts.size(), 1) * nhp;
-    s->received.assign((size_t)p->n_streams, 0);
-    s->extracted.assign((size_t)p->n_streams, 0);
+    s->feeds.assign((size_t)p->n_streams, hpfw::RingFeed());
+    int64_t hist_total = 0;
+    for (int i = 0; rates && i < p->n_streams; ++i) {
+        hpfw::RingFeed &f = s->feeds[(size_t)i];
+        if (rates[i] == hpfw::kRsRateOut) continue;
+        f.rate = rates[i];
+        (void)hpfw::resample_ratio(f.rate, &f.L, &f.M, &f.H);
+        f.hist = hist_total;
+        f.hist_len = (2 * (int64_t)f.H - 1 + 7) & ~(int64_t)7;
+        hist_total += 2 * f.hist_len;
+    }
     HIP_TRY(hipSetDevice(h->device));
     DevPlan *dp;
     if ((rc = get_plan(h, p->win, &dp))) return rc; // (the tables of win now: the first push is not the slow one)
+    for (const hpfw::RingFeed &f : s->feeds) // ... and those of every other rate
+        if (f.H && !s->tables.count(f.rate) && (rc = rs_table(h, f.rate, &s->tables[f.rate]))) return rc;
+    if (hist_total && s->hist.alloc((size_t)hist_total * 2) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
     if (s->slab.alloc((size_t)p->n_streams * (size_t)capacity * 2) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
     HIP_TRY(s->table_ev.create());
     *out = s.release();
@@ -166,7 +199,7 @@ int hpfw_gpu_streams_push_device(hpfw_gpu_streams *s, const int16_t *d_pcm, cons
 int hpfw_gpu_streams_room(hpfw_gpu_streams *s, int64_t *room)
 {
     if (!s || !room) return fail(HPFW_E_INVALID, "null argument");
-    for (int i = 0; i < s->n_streams; ++i) room[i] = s->capacity - (s->received[(size_t)i] - s->extracted[(size_t)i] * s->hop);
+    for (int i = 0; i < s->n_streams; ++i) room[i] = hpfw::ring_room(s->feeds[(size_t)i], s->hop, s->capacity);
     return 0;
 }
 
@@ -178,8 +211,8 @@ int hpfw_gpu_streams_extract(hpfw_gpu_streams *s, int64_t cap, uint64_t *d_hp, i
     // the windows of this call, in order of (feed, window)
     std::vector<hpfw_stream_window> take;
     for (int i = 0; i < s->n_streams && (int64_t)take.size() < cap; ++i) {
-        const int64_t have = windows_of(s->received[(size_t)i], s->win, s->hop);
-        for (int64_t w = s->extracted[(size_t)i]; w < have && (int64_t)take.size() < cap; ++w) take.push_back({i, 0, w});
+        const int64_t have = windows_of(emitted(s->feeds[(size_t)i]), s->win, s->hop);
+        for (int64_t w = s->feeds[(size_t)i].e; w < have && (int64_t)take.size() < cap; ++w) take.push_back({i, 0, w});
     }
     const int64_t n_w = (int64_t)take.size();
     if (n_w == 0) return 0;
@@ -219,7 +252,7 @@ int hpfw_gpu_streams_extract(hpfw_gpu_streams *s, int64_t cap, uint64_t *d_hp, i
         return 0;
     });
     if (rc) return rc; // (nothing was handed out: the windows stay ready)
-    for (const hpfw_stream_window &w : take) s->extracted[(size_t)w.feed] = w.window + 1;
+    for (const hpfw_stream_window &w : take) s->feeds[(size_t)w.feed].e = w.window + 1;
     std::copy(take.begin(), take.end(), which);
     *n = n_w;
     return 0;
@@ -248,8 +281,9 @@ int hpfw_gpu_streams_reset(hpfw_gpu_streams *s, int stream)
 {
     if (!s) return fail(HPFW_E_INVALID, "null argument");
     if (stream < 0 || stream >= s->n_streams) return fail(HPFW_E_INVALID, "streams: no such feed");
-    // (host bookkeeping only: what the ring holds is never read before it has been written again)
-    s->received[(size_t)stream] = s->extracted[(size_t)stream] = 0;
+    // (host bookkeeping only: what the ring holds is never read before it has been written again, and of the history of a feed
+    // at another rate only inputs at or behind the feed's first are read: none)
+    s->feeds[(size_t)stream].n = s->feeds[(size_t)stream].e = 0;
     return 0;
 }
 
@@ -259,8 +293,29 @@ int hpfw_gpu_streams_info(hpfw_gpu_streams *s, hpfw_streams_info *info, int64_t 
     if (info)
         *info = {s->per_window, s->win, s->hop, s->capacity, s->n_streams,
                  (int32_t)(std::max<size_t>(s->tempos.size(), 1) * std::max<size_t>(s->shifts.size(), 1))};
-    if (received) std::copy(s->received.begin(), s->received.end(), received);
-    if (extracted) std::copy(s->extracted.begin(), s->extracted.end(), extracted);
+    for (int i = 0; i < s->n_streams; ++i) {
+        if (received) received[i] = s->feeds[(size_t)i].n;
+        if (extracted) extracted[i] = s->feeds[(size_t)i].e;
+    }
+    return 0;
+}
+
+int hpfw_gpu_streams_rates(hpfw_gpu_streams *s, int32_t *rates, int64_t *n_emitted)
+{
+    if (!s) return fail(HPFW_E_INVALID, "null argument");
+    for (int i = 0; i < s->n_streams; ++i) {
+        if (rates) rates[i] = s->feeds[(size_t)i].rate;
+        if (n_emitted) n_emitted[i] = emitted(s->feeds[(size_t)i]);
+    }
+    return 0;
+}
+
+int hpfw_gpu_streams_emitted(int64_t n_in, int rate, int64_t *n_out)
+{
+    if (!n_out || n_in < 0) return fail(HPFW_E_INVALID, "bad argument");
+    int32_t L = 1, M = 1, H = 0;
+    if (!hpfw::resample_ratio(rate, &L, &M, &H)) return fail(HPFW_E_INVALID, "sample rate " + std::to_string(rate) + " Hz outside [8000, 192000]");
+    *n_out = rate == hpfw::kRsRateOut ? n_in : hpfw::ring_emitted(n_in, L, M, H);
     return 0;
 }
 

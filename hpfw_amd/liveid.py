@@ -228,17 +228,21 @@ class LiveSongIdentification:
     def streams(self, n_streams: int, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
                 shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
                 tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, capacity_s: Optional[float] = None,
-                windows: bool = False, rate: int = 44100):
+                windows: bool = False, rate=44100):
         """the timelines of n_streams live feeds as their samples arrive (hpfw_amd.streams.LiveStreams):
-        per feed exactly what timeline() gives for a file that holds everything pushed to it.  Feeds are 44.1 kHz mono PCM16:
-        another rate is refused (HPFW_E_UNSUPPORTED), whatever the resample switch.  capacity_s: seconds of audio a feed's ring
-        holds (None: two windows)."""
+        per feed exactly what timeline() gives for a file that holds everything pushed to it.  Feeds are mono PCM16.  rate: the
+        feeds' sample rate, one int for all or one per feed; another rate than 44 100 Hz is taken only by an identifier made with
+        resample=True, as files at other rates are (HPFW_E_UNSUPPORTED otherwise), and is converted chunk by chunk on the GPU:
+        the feed then yields what timeline() gives for a file at that rate, once H zero samples have been pushed behind its end
+        (LiveStreams.tail).  capacity_s: seconds of audio a feed's ring holds (None: two windows)."""
         from .streams import LiveStreams
-        if int(rate) != 44100:
-            raise _lib.HpfwError(f"live feeds are 44.1 kHz mono PCM16: a feed at {rate} Hz has to be converted before it is pushed",
+        rates = [int(rate)] * int(n_streams) if np.ndim(rate) == 0 else [int(r) for r in rate]
+        other = [r for r in rates if r != 44100]
+        if other and not self._resample:
+            raise _lib.HpfwError(f"live feeds are 44.1 kHz mono PCM16: a feed at {other[0]} Hz has to be converted before it is pushed",
                                  _lib.E_UNSUPPORTED)
         return LiveStreams(self, n_streams, min_score, window_s, hop_s, shifts, tempos, tol_cols, max_gap, min_windows, capacity_s,
-                           windows)
+                           windows, rates if other else None)
 
     def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None,
                tempos: Optional[Sequence[float]] = None):

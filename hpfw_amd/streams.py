@@ -6,8 +6,11 @@ their two kernels: hpfw_gpu_streams_*, k_streams.hip), searched and scored as ti
 (hpfw_timeline_tracker) hands out each segment as soon as nothing can continue it.  A window is an independent clip, so what
 a feed yields is exactly timeline() of a file that holds everything pushed to it, however the samples were cut into chunks.
 
-Feeds are 44.1 kHz mono PCM16.  A feed at another rate has to be converted before it is pushed; converting it chunk by chunk
-needs the resampler's history carried across pushes, which is not done here.
+Feeds are mono PCM16 at 44.1 kHz or, with rates=, at any integer rate in [8 000, 192 000] Hz.  A feed at another rate is
+converted to 44.1 kHz chunk by chunk on its way into its ring (k_streams_resample.hip), the resampler's history carried from
+push to push: the ring receives exactly the samples the conversion of the whole feed as one file gives, each as soon as the
+last input it reads has arrived, so that such a feed yields timeline() of a file at its rate.  The last H outputs of a feed
+that has ended wait for inputs that never come: tail(feed) zero samples pushed behind it bring them out.
 """
 import numpy as np
 
@@ -16,7 +19,7 @@ from . import _lib
 
 class LiveStreams:
     def __init__(self, lsi, n_streams, min_score, window_s=5.0, hop_s=2.5, shifts=None, tempos=None, tol_cols=None, max_gap=1,
-                 min_windows=1, capacity_s=None, windows=False):
+                 min_windows=1, capacity_s=None, windows=False, rates=None):
         self._lsi = lsi
         win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
         self._shifts = None if shifts is None else _lib.check_shifts(shifts)
@@ -25,12 +28,13 @@ class LiveStreams:
         self._gs = None
         capacity = 0 if capacity_s is None else int(round(capacity_s * 44100))
         extractor = lsi.collector.gpu()                   # the collector's filters
-        self._gs = extractor.streams(n_streams, win, hop, capacity, self._tempos, self._shifts)
+        self._gs = extractor.streams(n_streams, win, hop, capacity, self._tempos, self._shifts, rates)
         m = lsi._gpu.geometry(win).m
         self._col_s = 3.0 * win / m / 44100.0             # one index column in seconds
         self._tracker_args = (min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
         self._trackers = [_lib.TimelineTracker(*self._tracker_args) for _ in range(n_streams)]
         self.n_streams, self.win, self.hop, self.capacity = n_streams, win, hop, self._gs.capacity
+        self.rates = [int(r) for r in self._gs.rates]
 
     def __enter__(self):
         return self
@@ -46,8 +50,13 @@ class LiveStreams:
             self._gs = None
 
     def room(self):
-        """the samples every feed can take now"""
+        """the samples every feed can take now, at the feed's rate"""
         return self._gs.room()
+
+    def tail(self, feed):
+        """the zero samples to push behind a feed that has ended so that its last outputs come out: H of its rate's filter
+        (0 at 44.1 kHz).  With them the feed has given what a file of its samples gives."""
+        return _lib.streams_tail(self.rates[int(feed)])
 
     def _variant(self, v):
         n_s = len(self._shifts) if self._shifts else 1
@@ -58,7 +67,7 @@ class LiveStreams:
         return self._lsi._segment_tuple(sg, *self._variant(sg["best_variant"]), self._col_s)
 
     def push(self, chunks):
-        """chunks: a list with one int16 array or None per feed, or {feed: array}.  Appends them, hashes and searches every
+        """chunks: a list with one int16 array or None per feed (at the feed's rate), or {feed: array}.  Appends them, hashes and searches every
         window that has become complete, and returns [(feed, segment)]: the segments these windows closed, as timeline()
         returns them with start_s / end_s counted from the feed's start.  With windows=True at creation:
         (segments, [(feed, window, per-window tuple of timeline(windows=True))])."""

@@ -1,5 +1,6 @@
-// live_streams.h -- hpfw::LiveStreams: the timeline of feeds that are still running.  Chunks of 44.1 kHz
-// mono PCM16 are appended to any of n_streams feeds; every window that has become complete is hashed on the extractor's handle
+// live_streams.h -- hpfw::LiveStreams: the timeline of feeds that are still running.  Chunks of mono
+// PCM16 are appended to any of n_streams feeds (at 44.1 kHz, or with LiveStreamsOptions::resample at any rate in [8 000, 192 000]
+// Hz, converted chunk by chunk on the GPU exactly as a file at that rate is); every window that has become complete is hashed on the extractor's handle
 // `h` (which holds the index's filters) in one extraction pass over all feeds, searched in a GpuStorage or a ShardedGpuStorage
 // and scored exactly as hpfw::timeline (timeline.h) does it, and a segmenter per feed hands out each segment as soon as nothing
 // can continue it.  What a feed yields is, window for window and segment for segment, what hpfw::timeline yields for a file that
@@ -16,7 +17,9 @@ namespace hpfw {
 struct LiveStreamsOptions : TimelineOptions {
     int64_t capacity = 0;      ///< samples per feed's ring, >= win; 0: 2 win.  A push may not bring more than the ring has room for
     bool keep_windows = false; ///< windows() holds the best hit of every window of the last push
-    int rate = 44100;          ///< the feeds' sample rate: anything else is refused (convert before pushing)
+    int rate = 44100;          ///< the feeds' sample rate; another rate than 44 100 Hz needs `resample`
+    bool resample = false;     ///< take feeds at other rates, as GpuCollector's switch takes files (refused without it)
+    std::vector<int> rates;    ///< one rate per feed; empty: `rate` for all.  Chunks and LiveChunk::n count at the feed's rate
 };
 
 struct LiveChunk {
@@ -42,11 +45,15 @@ public:
     /// `storage` and `h` outlive the object; throws std::runtime_error with the library's message on failure
     LiveStreams(const Storage &storage, hpfw_gpu *h, int n_streams, const LiveStreamsOptions &opt) : storage_(storage), opt_(opt)
     {
-        if (opt.rate != 44100) throw std::runtime_error("hpfw::LiveStreams: feeds are 44.1 kHz mono PCM16");
+        std::vector<int32_t> rates(opt.rates.begin(), opt.rates.end());
+        if (rates.empty()) rates.assign((size_t)std::max(n_streams, 0), opt.rate);
+        if ((int)rates.size() != n_streams) throw std::runtime_error("hpfw::LiveStreams: one rate per feed");
+        for (int32_t r : rates)
+            if (r != 44100 && !opt.resample) throw std::runtime_error("hpfw::LiveStreams: feeds are 44.1 kHz mono PCM16");
         hpfw_streams_params p{n_streams, (int32_t)opt.tempos.size(), (int32_t)opt.shifts.size(), 0, opt.win, opt.hop, opt.capacity,
                               opt.tempos.empty() ? nullptr : opt.tempos.data(), opt.shifts.empty() ? nullptr : opt.shifts.data()};
         hpfw_gpu_streams *s = nullptr;
-        if (hpfw_gpu_streams_create(h, &p, &s) != 0) fail("create");
+        if (hpfw_gpu_streams_create_rates(h, &p, rates.empty() ? nullptr : rates.data(), &s) != 0) fail("create");
         s_.reset(s);
         if (hpfw_gpu_streams_info(s, &info_, nullptr, nullptr) != 0) fail("info");
         hpfw_geometry g;

@@ -545,13 +545,19 @@ int hpfw_gpu_timeline_segments(const hpfw_window_hit *w, int64_t n_w, const hpfw
 
 /* ---- live feeds: the timeline of feeds that are still running, as their samples arrive.
  *
- * A set of n_streams feeds on one handle, each a ring of `capacity` samples in device memory (44.1 kHz mono PCM16; another
- * rate has to be converted before it is pushed).  n_i: the samples feed i has received, e_i: the windows of it already handed
- * out.  Window w of a feed is its samples [w hop, w hop + win), as hpfw_gpu_window_count cuts a recording; the ring holds
- * samples [e_i hop, n_i).
+ * A set of n_streams feeds on one handle, each a ring of `capacity` samples in device memory.  A feed is mono PCM16 at 44.1 kHz
+ * or, in a set made by hpfw_gpu_streams_create_rates, at any integer rate fs in [8 000, 192 000] Hz: its chunks are converted to
+ * 44.1 kHz on their way into the ring.  n_i: the samples feed i has received (at its own rate), e_i: the windows of it already
+ * handed out.  y_i: the feed at 44.1 kHz.  For a 44.1 kHz feed y_i is what was pushed; for a feed at fs, with (L, M, T = 2 H) of
+ * hpfw_gpu_resample_table(fs), it is y_i[0 .. emitted(n_i)), the first emitted(n_i) = (n_i <= H ? 0 : ceil((n_i - H) L / M))
+ * samples of what hpfw_gpu_resample_pcm16 gives for everything pushed to the feed as one clip: output m reads the inputs up to
+ * floor(m M / L) + H and is given once they have arrived.  H zero samples pushed behind a feed that has ended bring out the
+ * rest: emitted(n + H) = hpfw_gpu_resample_length(n).  Window w of a feed is y_i[w hop, w hop + win), as hpfw_gpu_window_count
+ * cuts a recording; the ring holds y_i[e_i hop, emitted(n_i)).  win, hop and capacity are in 44.1 kHz samples.
  * CONTRACT.  The hashprints of window w of a feed equal, bit for bit, what hpfw_gpu_extract_windows_pcm16 gives for window w
- * of everything pushed to that feed since its last reset, and the clips equal those samples: whatever the chunking, the
- * other feeds, cap, and however often the ring has wrapped.
+ * of y_i -- everything pushed to that feed since its last reset, converted as one clip -- and the clips equal those samples:
+ * whatever the chunking (chunks of 0 samples, of 1 sample, of fewer than T), the other feeds and their rates, cap, and however
+ * often the ring has wrapped.
  * A set works in its handle's workspaces: calls on it are ordered with every other call on the handle, it is used by one
  * thread at a time, and it is destroyed before the handle. */
 typedef struct hpfw_gpu_streams hpfw_gpu_streams;
@@ -577,15 +583,22 @@ typedef struct {
 /* Every check of hpfw_gpu_extract_windows_pcm16 with its messages (the lists first, then the handle, projection mode 1 for
  * variants, the filters), after n_streams, win / hop and capacity.  Builds the tables of `win` and allocates the rings. */
 int hpfw_gpu_streams_create(hpfw_gpu *h, const hpfw_streams_params *p, hpfw_gpu_streams **out);
+/* The same with rates [n_streams], the sample rate of every feed; NULL: 44 100 Hz for all, which is hpfw_gpu_streams_create.  A
+ * rate outside [8 000, 192 000] is HPFW_E_UNSUPPORTED (after n_streams, before everything else: the handle is not used) and the
+ * message names the first such feed.  Also builds the conversion tables of every distinct rate (the cache of
+ * hpfw_gpu_resample_pcm16) and allocates per feed at another rate two histories of T - 1 input samples. */
+int hpfw_gpu_streams_create_rates(hpfw_gpu *h, const hpfw_streams_params *p, const int32_t *rates, hpfw_gpu_streams **out);
 void hpfw_gpu_streams_destroy(hpfw_gpu_streams *s);
 /* Appends counts[i] >= 0 samples to feed i, for every feed: pcm holds the chunks concatenated in feed order (host memory; the
- * device form takes a device pointer and enqueues on `stream`).  One upload and one launch, however many feeds take part.
- * A chunk that does not fit (n_i + counts[i] - e_i hop > capacity) makes the whole call HPFW_E_INVALID: nothing is appended
- * to any feed and the message names the first such feed.  *n_ready (may be NULL): complete windows not yet handed out, over
+ * device form takes a device pointer and enqueues on `stream`), each chunk counted in samples at its feed's rate.  One upload,
+ * one launch for the 44.1 kHz feeds that take part and one per other rate among those that do.
+ * A chunk that does not fit (counts[i] > room[i] below) makes the whole call HPFW_E_INVALID: nothing is appended to any feed, no
+ * history moves, and the message names the first such feed.  *n_ready (may be NULL): complete windows not yet handed out, over
  * all feeds.  pcm may be NULL when every count is 0. */
 int hpfw_gpu_streams_push(hpfw_gpu_streams *s, const int16_t *pcm, const int64_t *counts, int64_t *n_ready);
 int hpfw_gpu_streams_push_device(hpfw_gpu_streams *s, const int16_t *d_pcm, const int64_t *counts, int64_t *n_ready, void *stream);
-/* room[i] = capacity - (n_i - e_i hop): the samples feed i can take now */
+/* room[i]: the samples feed i can take now, at its own rate: H + floor((e_i hop + capacity) M / L) - n_i, the most it can hold
+ * while emitted <= e_i hop + capacity; at 44.1 kHz (L = M = 1, H = 0) that is capacity - (n_i - e_i hop) */
 int hpfw_gpu_streams_room(hpfw_gpu_streams *s, int64_t *room);
 /* Hashes up to cap >= 0 ready windows in order of (feed, window) ascending; the others stay ready.  *n: how many; which [*n]
  * (host, room for min(cap, ready) entries) names them; d_hp [*n][per_window]; d_clips NULL or [*n][win], the windows' samples.
@@ -596,8 +609,13 @@ int hpfw_gpu_streams_extract(hpfw_gpu_streams *s, int64_t cap, uint64_t *d_hp, i
 int hpfw_gpu_streams_extract_host(hpfw_gpu_streams *s, int64_t cap, uint64_t *hp, int16_t *clips, hpfw_stream_window *which, int64_t *n);
 /* feed `stream` starts again at sample 0 and window 0 (a feed that reconnects); its windows not yet handed out are dropped */
 int hpfw_gpu_streams_reset(hpfw_gpu_streams *s, int stream);
-/* info, received [n_streams] = n_i and extracted [n_streams] = e_i; each may be NULL */
+/* info, received [n_streams] = n_i (samples pushed, at the feed's rate) and extracted [n_streams] = e_i; each may be NULL */
 int hpfw_gpu_streams_info(hpfw_gpu_streams *s, hpfw_streams_info *info, int64_t *received, int64_t *extracted);
+/* rates [n_streams] and emitted [n_streams] = emitted(n_i), the 44.1 kHz samples each ring has received; each may be NULL */
+int hpfw_gpu_streams_rates(hpfw_gpu_streams *s, int32_t *rates, int64_t *emitted);
+/* *n_out = emitted(n_in) of a feed at `rate` (n_in itself at 44 100 Hz).  Host only, no handle; a rate outside the range or
+ * n_in < 0 is HPFW_E_INVALID, as for hpfw_gpu_resample_length. */
+int hpfw_gpu_streams_emitted(int64_t n_in, int rate, int64_t *n_out);
 
 /* Segments as the windows arrive: hpfw_gpu_timeline_segments one push at a time.  Host only, no handle.  Windows are numbered
  * from 0 in push order; the parameter checks and messages are those of hpfw_gpu_timeline_segments.
