@@ -20,6 +20,11 @@ VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt
 COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
 ALIGN_DTYPE = np.dtype([("rec", "<u4"), ("peak", "<u4"), ("offset", "<i8")])
 NO_REC = 0xFFFFFFFF
+# hpfw_xcorr_job / hpfw_xcorr_peak: the exact cross-correlation of PCM16
+XCORR_JOB_DTYPE = np.dtype([("a_off", "<i8"), ("a_len", "<i8"), ("b_off", "<i8"), ("b_len", "<i8"), ("p", "<i8"), ("q", "<i8"),
+                            ("len", "<i8"), ("radius", "<i4"), ("pad", "<i4")])
+XCORR_PEAK_DTYPE = np.dtype([("r", "<i8"), ("energy_a", "<i8"), ("energy_b", "<i8"), ("lag", "<i4"), ("pad", "<i4")])
+XCORR_MAX_LEN, XCORR_MAX_RADIUS = 1 << 22, 4096
 # the timeline of a long recording: hpfw_dist_stats, hpfw_window_hit, hpfw_segment
 STATS_DTYPE = np.dtype([("sum", "<u8"), ("sum_sq", "<u8"), ("n", "<u4"), ("pad", "<u4")])
 WINDOW_HIT_DTYPE = np.dtype([("clip", "<u4"), ("offset", "<i4"), ("variant", "<i4"), ("pad", "<i4"), ("tempo", "<f8"),
@@ -58,6 +63,7 @@ EXPORTS = (
     "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
     "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
     "hpfw_gpu_combiner_find_device", "hpfw_gpu_combiner_align", "hpfw_gpu_combiner_align_device", "hpfw_gpu_wav_read_pcm16",
+    "hpfw_gpu_xcorr_pcm16", "hpfw_gpu_xcorr_pcm16_host", "hpfw_gpu_mel_kept_frames_pcm16_host",
     "hpfw_gpu_wav_read_pcm16_any", "hpfw_gpu_resample_length", "hpfw_gpu_resample_table", "hpfw_gpu_resample_pcm16",
     "hpfw_gpu_resample_pcm16_host", "hpfw_gpu_collector_set_resample",
     "hpfw_gpu_extract_transposed_pcm16", "hpfw_gpu_extract_transposed_pcm16_host", "hpfw_gpu_hashprints_from_db_transposed",
@@ -228,6 +234,9 @@ def lib():
     L.hpfw_gpu_combiner_find_device.argtypes = [vp, vp, vp, vp, i64, vp, vp]
     L.hpfw_gpu_combiner_align.argtypes = [vp, vp, vp, vp, i64, i32, vp]
     L.hpfw_gpu_combiner_align_device.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
+    L.hpfw_gpu_xcorr_pcm16.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    L.hpfw_gpu_xcorr_pcm16_host.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.hpfw_gpu_mel_kept_frames_pcm16_host.argtypes = [vp, vp, i64, i64, vp, i64, vp]
     L.hpfw_gpu_wav_read_pcm16.argtypes = [ctypes.c_char_p, vp, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_wav_read_pcm16_any.argtypes = [ctypes.c_char_p, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     L.hpfw_gpu_resample_length.argtypes = [i64, i32, ctypes.POINTER(i64)]
@@ -776,6 +785,40 @@ class Gpu:
         off = np.ascontiguousarray(q_off, np.int64)
         ex = _exclude(exclude, off.size - 1)
         check(lib().hpfw_gpu_combiner_align_device(self._h, d_q, _hp(off), _hp(ex), off.size - 1, int(k), d_out, stream))
+
+    # ---- sample-accurate offsets ------------------------------------------
+    def xcorr(self, pcm, jobs, want_r=False):
+        """pcm int16 [n] (host), jobs XCORR_JOB_DTYPE [n_jobs] (operands are ranges of pcm) -> XCORR_PEAK_DTYPE [n_jobs], or
+        (peaks, list of int64 r [2 radius + 1] per job, lag -radius first) with want_r: exact int64 sums"""
+        pcm = np.ascontiguousarray(pcm, np.int16).ravel()
+        jobs = np.ascontiguousarray(jobs, XCORR_JOB_DTYPE).ravel()
+        peaks = np.zeros(jobs.size, XCORR_PEAK_DTYPE)
+        # (the library validates the jobs; r is sized from radii it would accept)
+        lags = 2 * np.clip(jobs["radius"].astype(np.int64), 0, XCORR_MAX_RADIUS) + 1
+        r = np.zeros(int(lags.sum()) if want_r else 0, np.int64)
+        check(lib().hpfw_gpu_xcorr_pcm16_host(self._h, _hp(pcm), pcm.size, _hp(jobs), jobs.size, _hp(r) if want_r else None,
+                                              _hp(peaks)))
+        if not want_r:
+            return peaks
+        off = np.concatenate([[0], np.cumsum(lags)])
+        return peaks, [r[off[i]:off[i + 1]] for i in range(jobs.size)]
+
+    def xcorr_dev(self, d_pcm, jobs, d_r, d_peaks, stream=0):
+        """device pointers (d_r 0 for none); jobs XCORR_JOB_DTYPE on the host"""
+        jobs = np.ascontiguousarray(jobs, XCORR_JOB_DTYPE).ravel()
+        check(lib().hpfw_gpu_xcorr_pcm16(self._h, d_pcm, _hp(jobs), jobs.size, d_r or None, d_peaks, stream))
+
+    def mel_kept_frames(self, pcm):
+        """pcm int16 [n] or [n_clips][n] (host) -> per clip the int32 frames its Mel columns came from (the silent frames are
+        dropped before hashing): column c is frame frames[c], centred on sample 441 * frames[c]"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        stride = max(int(lib().hpfw_gpu_mel_frames(pcm.shape[1])), 1)
+        frames = np.zeros((pcm.shape[0], stride), np.int32)
+        n = np.zeros(pcm.shape[0], np.int32)
+        check(lib().hpfw_gpu_mel_kept_frames_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], _hp(frames), stride, _hp(n)))
+        return [frames[i, :n[i]].copy() for i in range(pcm.shape[0])]
 
     # ---- filter learning ------------------------------------------------------------------
     def cov_reset(self):

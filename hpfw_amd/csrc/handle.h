@@ -212,6 +212,10 @@ struct hpfw_gpu {
     int k_launches[K_COUNT] = {0};
     // AudioCombiner's inverted index (k_combiner.hip), created on first use
     std::unique_ptr<hpfw::Combiner> combiner;
+    // exact cross-correlation (k_xcorr.hip, search.hip): the jobs and their parts on the device, r when the caller keeps none
+    struct Xcorr {
+        DevBuf d_tab, d_r;
+    } xcorr;
     // sample-rate conversion (k_resample.hip, extract.hip): the device image of each rate's table, made on first use;
     // staging of the host entry point
     struct Resample {

@@ -212,6 +212,19 @@ __global__ __launch_bounds__(256) void mel_db_kernel(const float *__restrict__ p
     out[((int64_t)clip * kMelBands + band) * n_frames + c] = l < -80.0f ? -80.0f : l;
 }
 
+// frames[clip][c] = the frame column c came from (pos inverted), -1 behind the kept columns
+__global__ __launch_bounds__(256) void mel_kept_frames_kernel(const int *__restrict__ pos, const int *__restrict__ count, int n_frames,
+                                                              int32_t *__restrict__ frames, int64_t stride)
+{
+    const int clip = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < stride && i >= count[clip]) frames[clip * stride + i] = -1;
+    if (i < n_frames) {
+        const int c = pos[(int64_t)clip * n_frames + i];
+        if (c >= 0) frames[clip * stride + c] = (int32_t)i;
+    }
+}
+
 int mel_frames(int64_t n) { return n <= 0 ? 0 : (int)((n + kMelHalf + kMelHop - 1) / kMelHop); }
 
 // workspace for n_clips clips: block sums, positions, counts are separate small buffers (see learn.hip);
@@ -220,6 +233,16 @@ size_t mel_work_bytes(int64_t n, int n_clips)
 {
     const int nf = mel_frames(n), fp = (nf + 1) / 2 * 2;
     return ((size_t)n_clips * fp * 2 * kMelHpad + (size_t)n_clips * kMelBands * nf) * sizeof(float);
+}
+
+void launch_mel_kept_frames(const int16_t *d_pcm, int64_t n, int n_clips, int64_t *d_blk, int *d_pos, int *d_count,
+                            int32_t *d_frames, int64_t stride, hipStream_t s)
+{
+    const int nf = mel_frames(n), n_blk = (int)((n + kMelHop - 1) / kMelHop);
+    hipLaunchKernelGGL(mel_blocksum_kernel, dim3((n_blk + 3) / 4, n_clips), dim3(256), 0, s, d_pcm, n, n_blk, d_blk);
+    hipLaunchKernelGGL(mel_keep_kernel, dim3(n_clips), dim3(256), 0, s, d_blk, n_blk, nf, d_pos, d_count);
+    hipLaunchKernelGGL(mel_kept_frames_kernel, dim3((unsigned)((stride + 255) / 256), n_clips), dim3(256), 0, s, d_pos, d_count, nf,
+                       d_frames, stride);
 }
 
 void launch_mel(const RowsArgs &rows, const float *d_win, const float *d_cpack, const int16_t *d_pcm, int64_t n, int n_clips,

@@ -8,10 +8,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/hpfw_gpu.h"
 #include "device_math.h"
 #include "fft_lds.h"
 #include "fft_rows.h"
 #include "streams_plan.h"
+#include "xcorr_plan.h"
 
 namespace hpfw {
 
@@ -334,6 +336,16 @@ size_t mel_work_bytes(int64_t n_samples, int n_clips);
 // d_out [n_clips][33][frames] (kept columns at the front of every row), d_count [n_clips] their number
 void launch_mel(const RowsArgs &rows, const float *d_win, const float *d_cpack, const int16_t *d_pcm, int64_t n, int n_clips,
                 int64_t *d_blk, int *d_pos, int *d_count, float *d_pmax, float *d_work, float *d_out, bool db_fast, hipStream_t s);
+// the silence test alone: d_frames [n_clips][stride] = the frame of every kept column (-1 behind them), d_count their number;
+// d_blk [n_clips][ceil(n / 441)], d_pos [n_clips][mel_frames(n)] scratch; stride >= mel_frames(n)
+void launch_mel_kept_frames(const int16_t *d_pcm, int64_t n, int n_clips, int64_t *d_blk, int *d_pos, int *d_count,
+                            int32_t *d_frames, int64_t stride, hipStream_t s);
+
+// ---- exact cross-correlation of PCM16 (k_xcorr.hip) ---------------------------------------------
+// (jobs and their parts: xcorr_plan.h) r of jobs [0, n_jobs) from the two item lists (either may be empty), then the
+// peaks when d_peaks is not null
+void launch_xcorr(const int16_t *d_pcm, const XcJob *d_jobs, int64_t n_jobs, const XcItem *d_mfma, int64_t n_mfma,
+                  const XcItem *d_valu, int64_t n_valu, int64_t *d_r, hpfw_xcorr_peak *d_peaks, hipStream_t s);
 
 // ---- search ------------------------------------------------------------------------------
 struct SearchArgs {

@@ -245,6 +245,41 @@ int hpfw_gpu_combiner_align(hpfw_gpu *h, const uint16_t *q_hp, const int64_t *q_
                             int k, hpfw_align_hit *out);
 int hpfw_gpu_combiner_align_device(hpfw_gpu *h, const uint16_t *d_q_hp, const int64_t *q_off, const int32_t *exclude,
                                    int64_t n_q, int k, hpfw_align_hit *d_out, void *stream);
+
+/* ---- sample-accurate offsets: exact windowed cross-correlation of PCM16 (k_xcorr.hip) ----
+ * Operands a and b of a job are ranges [a_off, a_off + a_len) and [b_off, b_off + b_len) of ONE int16 buffer.  For
+ * every lag l in [-radius, radius]
+ *     r[l] = sum over n in [0, len) of a[p + l + n] * b[q + n]
+ * with a read as 0 outside [0, a_len) and b[q .. q + len) inside b: exact int64 sums (|r| <= 2^52), no floating point
+ * and no summation order -- int8 digit products on the matrix cores (HPFW_XCORR=valu in the environment, read at every
+ * call: the plain integer kernel for every lag), 64-bit integer atomics between the parts of a job.
+ * peak: the lag with the largest |r| (ties: the smaller |lag|, then the negative lag), r there,
+ * energy_a = sum a[p + lag + n]^2 and energy_b = sum b[q + n]^2.
+ * HPFW_E_INVALID: len < 1 or > 2^22, radius < 0 or > 4096, q < 0 or q + len > b_len, a range outside the buffer (the
+ * device variant is not told the buffer's size: negative offsets and lengths only), |p| > 2^40, null pointers. */
+#define HPFW_XCORR_MAX_LEN (1 << 22)
+#define HPFW_XCORR_MAX_RADIUS 4096
+typedef struct {
+    int64_t a_off, a_len, b_off, b_len; /* operands: ranges of the pcm buffer */
+    int64_t p, q, len;                  /* as in the formula above */
+    int32_t radius, pad;
+} hpfw_xcorr_job;
+typedef struct {
+    int64_t r, energy_a, energy_b;
+    int32_t lag, pad;
+} hpfw_xcorr_peak;
+/* d_pcm, d_r (NULL, or [sum of 2 radius + 1], job after job, lag -radius first) and d_peaks [n_jobs] on the device,
+ * jobs on the host (read before the call returns).  The host variant takes n_pcm, uploads and synchronises. */
+int hpfw_gpu_xcorr_pcm16(hpfw_gpu *h, const int16_t *d_pcm, const hpfw_xcorr_job *jobs, int64_t n_jobs, int64_t *d_r,
+                         hpfw_xcorr_peak *d_peaks, void *stream);
+int hpfw_gpu_xcorr_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_pcm, const hpfw_xcorr_job *jobs, int64_t n_jobs,
+                              int64_t *r, hpfw_xcorr_peak *peaks);
+/* the frames the Mel front end keeps (it drops the frames essentia calls silent before anything is hashed): column c of
+ * clip i came from frame frames[i * stride + c], centred on sample 441 * frame; n_kept [n_clips] columns per clip, the
+ * rest of a row is -1.  stride >= hpfw_gpu_mel_frames(n_samples). */
+int hpfw_gpu_mel_kept_frames_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_samples, int64_t n_clips,
+                                        int32_t *frames, int64_t stride, int32_t *n_kept);
+
 /* a WAV file as the live-id file entry points read it: PCM16 mono, or stereo averaged (truncating) to mono, 44.1 kHz
  * only (HPFW_E_IO otherwise).  *n = samples in the file; out receives them when cap >= *n (out may be NULL). */
 int hpfw_gpu_wav_read_pcm16(const char *path, int16_t *out, int64_t cap, int64_t *n);
