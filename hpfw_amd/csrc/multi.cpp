@@ -6,12 +6,12 @@
 // per shard (each on its own device and stream, enqueued by its own host thread), ONE ncclAllGather of the
 // per-shard top-k lists over xGMI, one deterministic merge.  No torch, no Python: librccl and libamdhip64 only.
 #include <algorithm>
-#include <atomic>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
@@ -20,6 +20,7 @@
 #include "../../include/hpfw_gpu_multi.h"
 #include "../../include/hpfw_gpu_multi_resample.h"
 #include "../../include/hpfw_gpu_multi_search.h"
+#include "hip_owned.h"
 #include "legacy_internal.h"
 
 namespace {
@@ -30,41 +31,54 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
+// move-only owners of what has a C destroy call: a shard's handle, its collector, an RCCL communicator
+template <auto Destroy>
+struct Del {
+    template <class T>
+    void operator()(T *p) const { (void)Destroy(p); }
+};
+using GpuPtr = std::unique_ptr<hpfw_gpu, Del<hpfw_gpu_destroy>>;
+using CollectorPtr = std::unique_ptr<hpfw_legacy_collector, Del<par_collector_del>>;
+using Comm = std::unique_ptr<std::remove_pointer_t<ncclComm_t>, Del<ncclCommDestroy>>;
+
+// Members are destroyed in reverse order of declaration: a shard's buffer, event and stream go before its handle.
 struct Shard {
+    int device = 0;    // ordinal of its device
     int dev_slot = 0;  // index into hpfw_gpu_group::devs
     int local = 0;     // position among the shards of that device
-    hpfw_gpu *h = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    uint64_t *d_q = nullptr;
-    size_t q_cap = 0;
+    GpuPtr h;
+    hpfw::Stream stream;
+    hpfw::Event done;
+    hpfw::DevBuf d_q;
     int64_t lo = 0, hi = 0; // global clip ids of its block
 };
 
+// Reverse order of declaration again: the communicator goes before the device's buffers, the buffers before the stream.
 struct Dev {
     int device = 0;
-    ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;
-    hpfw_hit *d_send = nullptr, *d_recv = nullptr;
-    size_t send_cap = 0, recv_cap = 0;
-    // device 0 of a key, tempo or scored search: the merged hits and summed moments, and (several devices) the gathered
-    // regions packed shard after shard
-    void *d_merged = nullptr, *d_pack = nullptr;
-    size_t merged_cap = 0, pack_cap = 0;
     std::vector<int> shards;
+    hpfw::Stream stream;
+    // device 0 of a search: the merged hits and summed moments, and (several devices) the gathered regions packed shard
+    // after shard
+    hpfw::DevBuf d_pack, d_merged;
+    hpfw::DevBuf d_recv, d_send; // bytes: hits, then moments (group_search)
+    Comm comm;
 };
 
 } // namespace
 
+// The devices go first (reverse order of declaration), then the collectors, then the shards with their handles; the
+// destructor waits for every stream before any of that.  None of the frees needs its device to be the current one.
 struct hpfw_gpu_group {
-    std::vector<hpfw_legacy_collector *> collectors; // one per shard, created by the first load / prepare
-    std::string cache;
     std::vector<Shard> shards;
+    std::vector<CollectorPtr> collectors; // one per shard, created by the first load / prepare
     std::vector<Dev> devs;
+    std::string cache;
     int per_dev = 1; // shards on every device (uniform)
     int64_t n_clips = 0;
     std::string exchange;
     bool resample = false; // hpfw_gpu_group_set_resample: applied to every shard collector, those made later included
+    ~hpfw_gpu_group();
 };
 
 namespace {
@@ -80,15 +94,25 @@ namespace {
         if (r_ != ncclSuccess) return fail(HPFW_E_HIP, std::string(what) + ": " + ncclGetErrorString(r_));        \
     } while (0)
 
-int grow(void **p, size_t *cap, size_t need)
+int ensure(hpfw::DevBuf &b, size_t bytes)
 {
-    if (*cap >= need) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need) != hipSuccess) return fail(HPFW_E_NOMEM, "hipMalloc failed");
-    *cap = need;
-    return 0;
+    return b.ensure(bytes) == hipSuccess ? 0 : fail(HPFW_E_NOMEM, "device allocation failed");
+}
+
+// Waits for every shard stream and every device stream of the group, all of them whatever fails; the first failure is
+// returned and no message is set, so that the caller's earlier failure keeps its own.
+hipError_t drain(hpfw_gpu_group *g)
+{
+    hipError_t first = hipSuccess;
+    const auto wait = [&first](int device, const hpfw::Stream &s) {
+        if (!s) return;
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipStreamSynchronize(s.get());
+        if (first == hipSuccess) first = e;
+    };
+    for (const Shard &s : g->shards) wait(s.device, s.stream);
+    for (const Dev &d : g->devs) wait(d.device, d.stream);
+    return first;
 }
 
 // fn(shard index) on one host thread per shard; the first failure's code and message reach the caller's thread
@@ -99,7 +123,7 @@ int per_shard(hpfw_gpu_group *g, F fn)
     std::vector<int> rc((size_t)n, 0);
     std::vector<std::string> why((size_t)n);
     auto run = [&](int i) {
-        (void)hipSetDevice(g->devs[(size_t)g->shards[(size_t)i].dev_slot].device);
+        (void)hipSetDevice(g->shards[(size_t)i].device);
         rc[(size_t)i] = fn(i);
         if (rc[(size_t)i]) why[(size_t)i] = hpfw_gpu_last_error(); // thread-local in libhpfw_gpu.so
     };
@@ -116,7 +140,21 @@ int per_shard(hpfw_gpu_group *g, F fn)
     return 0;
 }
 
+// fn(shard index, lo, hi) on every shard whose block [lo, hi) of n_items items is not empty
+template <class F>
+int per_shard_range(hpfw_gpu_group *g, int64_t n_items, F fn)
+{
+    const int n = (int)g->shards.size();
+    return per_shard(g, [&](int i) {
+        int64_t lo, hi;
+        hpfw_gpu_shard_range(n_items, i, n, &lo, &hi);
+        return hi == lo ? 0 : fn(i, lo, hi);
+    });
+}
+
 } // namespace
+
+hpfw_gpu_group::~hpfw_gpu_group() { (void)drain(this); }
 
 extern "C" {
 
@@ -134,61 +172,42 @@ int hpfw_gpu_group_create(const int *devices, int n_shards, hpfw_gpu_group **out
     *out = nullptr;
     int n_dev = 0;
     HIP_OK(hipGetDeviceCount(&n_dev), "hipGetDeviceCount");
-    auto *g = new hpfw_gpu_group();
+    auto g = std::make_unique<hpfw_gpu_group>(); // a failure below takes down what was built so far
     g->shards.resize((size_t)n_shards);
     for (int i = 0; i < n_shards; ++i) {
         const int d = devices ? devices[i] : i;
-        if (d < 0 || d >= n_dev) {
-            hpfw_gpu_group_destroy(g);
-            return fail(HPFW_E_INVALID, "shard " + std::to_string(i) + ": no device " + std::to_string(d));
-        }
+        if (d < 0 || d >= n_dev) return fail(HPFW_E_INVALID, "shard " + std::to_string(i) + ": no device " + std::to_string(d));
         size_t slot = 0;
         while (slot < g->devs.size() && g->devs[slot].device != d) ++slot;
         if (slot == g->devs.size()) {
             g->devs.emplace_back();
             g->devs.back().device = d;
         }
+        g->shards[(size_t)i].device = d;
         g->shards[(size_t)i].dev_slot = (int)slot;
         g->shards[(size_t)i].local = (int)g->devs[slot].shards.size();
         g->devs[slot].shards.push_back(i);
     }
     g->per_dev = (int)g->devs[0].shards.size();
     for (const Dev &d : g->devs)
-        if ((int)d.shards.size() != g->per_dev) {
-            hpfw_gpu_group_destroy(g);
-            return fail(HPFW_E_INVALID, "every device must hold the same number of shards");
-        }
+        if ((int)d.shards.size() != g->per_dev) return fail(HPFW_E_INVALID, "every device must hold the same number of shards");
     for (Shard &s : g->shards) {
-        const int d = g->devs[(size_t)s.dev_slot].device;
-        if (hpfw_gpu_create(d, &s.h) != 0) {
-            hpfw_gpu_group_destroy(g);
-            return HPFW_E_HIP; // message set by hpfw_gpu_create
-        }
-        if (hipSetDevice(d) != hipSuccess || hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) {
-            hpfw_gpu_group_destroy(g);
+        hpfw_gpu *h = nullptr;
+        if (hpfw_gpu_create(s.device, &h) != 0) return HPFW_E_HIP; // message set by hpfw_gpu_create
+        s.h.reset(h);
+        if (hipSetDevice(s.device) != hipSuccess || s.stream.create() != hipSuccess || s.done.create() != hipSuccess)
             return fail(HPFW_E_HIP, "stream/event creation failed");
-        }
     }
     // one communicator per distinct device, all in this process (ncclCommInitAll); world size 1 is allowed
     std::vector<int> devlist;
     for (Dev &d : g->devs) devlist.push_back(d.device);
     std::vector<ncclComm_t> comms(devlist.size(), nullptr);
-    ncclResult_t r = ncclCommInitAll(comms.data(), (int)devlist.size(), devlist.data());
-    if (r != ncclSuccess) {
-        hpfw_gpu_group_destroy(g);
-        return fail(HPFW_E_HIP, std::string("ncclCommInitAll: ") + ncclGetErrorString(r));
-    }
-    for (size_t i = 0; i < g->devs.size(); ++i) {
-        g->devs[i].comm = comms[i];
-        if (hipSetDevice(g->devs[i].device) != hipSuccess ||
-            hipStreamCreateWithFlags(&g->devs[i].stream, hipStreamNonBlocking) != hipSuccess) {
-            hpfw_gpu_group_destroy(g);
-            return fail(HPFW_E_HIP, "stream creation failed");
-        }
-    }
+    NCCL_OK(ncclCommInitAll(comms.data(), (int)devlist.size(), devlist.data()), "ncclCommInitAll");
+    for (size_t i = 0; i < g->devs.size(); ++i) g->devs[i].comm = Comm(comms[i]);
+    for (Dev &d : g->devs)
+        if (hipSetDevice(d.device) != hipSuccess || d.stream.create() != hipSuccess) return fail(HPFW_E_HIP, "stream creation failed");
     g->exchange = g->per_dev == 1 ? "rccl" : "rccl+local";
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -213,36 +232,13 @@ int hpfw_gpu_group_create_env(hpfw_gpu_group **out)
     return hpfw_gpu_group_create(devs.data(), (int)devs.size(), out);
 }
 
-void hpfw_gpu_group_destroy(hpfw_gpu_group *g)
-{
-    if (!g) return;
-    for (Dev &d : g->devs) {
-        (void)hipSetDevice(d.device);
-        if (d.stream) (void)hipStreamSynchronize(d.stream);
-        if (d.comm) (void)ncclCommDestroy(d.comm);
-        if (d.d_send) (void)hipFree(d.d_send);
-        if (d.d_recv) (void)hipFree(d.d_recv);
-        if (d.d_merged) (void)hipFree(d.d_merged);
-        if (d.d_pack) (void)hipFree(d.d_pack);
-        if (d.stream) (void)hipStreamDestroy(d.stream);
-    }
-    for (hpfw_legacy_collector *c : g->collectors) par_collector_del(c);
-    for (Shard &s : g->shards) {
-        if (s.dev_slot < (int)g->devs.size()) (void)hipSetDevice(g->devs[(size_t)s.dev_slot].device);
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        if (s.d_q) (void)hipFree(s.d_q);
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        if (s.h) hpfw_gpu_destroy(s.h);
-    }
-    delete g;
-}
+void hpfw_gpu_group_destroy(hpfw_gpu_group *g) { delete g; } // the destructor drains, then the members go
 
 int hpfw_gpu_group_size(const hpfw_gpu_group *g) { return g ? (int)g->shards.size() : 0; }
 
 hpfw_gpu *hpfw_gpu_group_handle(hpfw_gpu_group *g, int shard)
 {
-    return g && shard >= 0 && shard < (int)g->shards.size() ? g->shards[(size_t)shard].h : nullptr;
+    return g && shard >= 0 && shard < (int)g->shards.size() ? g->shards[(size_t)shard].h.get() : nullptr;
 }
 
 const char *hpfw_gpu_group_exchange(const hpfw_gpu_group *g) { return g ? g->exchange.c_str() : ""; }
@@ -251,7 +247,7 @@ int hpfw_gpu_group_set_filters(hpfw_gpu_group *g, const float *f)
 {
     if (!g || !f) return fail(HPFW_E_INVALID, "null argument");
     for (Shard &s : g->shards) {
-        const int rc = hpfw_gpu_set_filters(s.h, f);
+        const int rc = hpfw_gpu_set_filters(s.h.get(), f);
         if (rc) return rc;
     }
     return 0;
@@ -261,14 +257,10 @@ int hpfw_gpu_group_extract_pcm16(hpfw_gpu_group *g, const int16_t *pcm, int64_t 
 {
     if (!g || !pcm || !hp || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
     hpfw_geometry geo;
-    int rc = hpfw_gpu_geometry(g->shards[0].h, n_samples, &geo);
+    int rc = hpfw_gpu_geometry(g->shards[0].h.get(), n_samples, &geo);
     if (rc) return rc;
-    const int n = (int)g->shards.size();
-    return per_shard(g, [&](int i) {
-        int64_t lo, hi;
-        hpfw_gpu_shard_range(n_clips, i, n, &lo, &hi);
-        if (hi == lo) return 0;
-        return hpfw_gpu_extract_pcm16_host(g->shards[(size_t)i].h, pcm + lo * n_samples, n_samples, hi - lo, hp + lo * geo.n_hp);
+    return per_shard_range(g, n_clips, [&](int i, int64_t lo, int64_t hi) {
+        return hpfw_gpu_extract_pcm16_host(g->shards[(size_t)i].h.get(), pcm + lo * n_samples, n_samples, hi - lo, hp + lo * geo.n_hp);
     });
 }
 
@@ -280,9 +272,9 @@ int hpfw_gpu_group_index_build(hpfw_gpu_group *g, const uint64_t *hp, const int6
     const int rc = per_shard(g, [&](int i) {
         Shard &s = g->shards[(size_t)i];
         hpfw_gpu_shard_range(n_clips, i, n, &s.lo, &s.hi);
-        int r = hpfw_gpu_index_clear(s.h);
-        if (!r) r = hpfw_gpu_index_set_clip_base(s.h, (uint32_t)s.lo);
-        if (!r && s.hi > s.lo) r = hpfw_gpu_index_add(s.h, hp, offsets + s.lo, s.hi - s.lo);
+        int r = hpfw_gpu_index_clear(s.h.get());
+        if (!r) r = hpfw_gpu_index_set_clip_base(s.h.get(), (uint32_t)s.lo);
+        if (!r && s.hi > s.lo) r = hpfw_gpu_index_add(s.h.get(), hp, offsets + s.lo, s.hi - s.lo);
         return r;
     });
     if (!rc) g->n_clips = n_clips;
@@ -291,68 +283,10 @@ int hpfw_gpu_group_index_build(hpfw_gpu_group *g, const uint64_t *hp, const int6
 
 int64_t hpfw_gpu_group_index_size(const hpfw_gpu_group *g) { return g ? g->n_clips : 0; }
 
-int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out)
-{
-    if (!g || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
-    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
-    if (n_q == 0) return 0;
-    const int64_t total = q_off[n_q] - q_off[0];
-    if (total > 0 && !q_hp) return fail(HPFW_E_INVALID, "null queries");
-    std::vector<int64_t> rel((size_t)n_q + 1);
-    for (int64_t i = 0; i <= n_q; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
-    const size_t list = (size_t)n_q * k; // hits per shard
-    const int n = (int)g->shards.size(), m = (int)g->devs.size();
-    for (Dev &d : g->devs) {
-        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-        int rc = grow((void **)&d.d_send, &d.send_cap, list * g->per_dev * sizeof(hpfw_hit));
-        if (!rc) rc = grow((void **)&d.d_recv, &d.recv_cap, list * n * sizeof(hpfw_hit));
-        if (rc) return rc;
-    }
-    // 1. every shard: replicated queries in, scan of its block, its own top-k (global clip ids) into its slot of
-    //    the device's send buffer
-    int rc = per_shard(g, [&](int i) {
-        Shard &s = g->shards[(size_t)i];
-        Dev &d = g->devs[(size_t)s.dev_slot];
-        int r = grow((void **)&s.d_q, &s.q_cap, (size_t)std::max<int64_t>(total, 1) * 8);
-        if (r) return r;
-        if (total && hipMemcpyAsync(s.d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice, s.stream) != hipSuccess)
-            return fail(HPFW_E_HIP, "H2D copy of the queries failed");
-        r = hpfw_gpu_search_topk_device(s.h, s.d_q, rel.data(), n_q, k, d.d_send + (size_t)s.local * list, s.stream);
-        if (r) return r;
-        if (hipEventRecord(s.done, s.stream) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
-        return 0;
-    });
-    if (rc) return rc;
-    // 2. the exchange step: one all-gather of per_dev x n_q x k x 16 bytes per device over xGMI
-    for (Dev &d : g->devs) {
-        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-        for (int si : d.shards) HIP_OK(hipStreamWaitEvent(d.stream, g->shards[(size_t)si].done, 0), "hipStreamWaitEvent");
-    }
-    NCCL_OK(ncclGroupStart(), "ncclGroupStart");
-    for (Dev &d : g->devs) {
-        ncclResult_t r = ncclAllGather(d.d_send, d.d_recv, list * g->per_dev * sizeof(hpfw_hit), ncclUint8, d.comm, d.stream);
-        if (r != ncclSuccess) {
-            (void)ncclGroupEnd();
-            return fail(HPFW_E_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
-        }
-    }
-    NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
-    // 3. every device now holds all n lists; the host takes device 0's copy and merges by (dist, clip)
-    std::vector<hpfw_hit> all(list * n);
-    HIP_OK(hipSetDevice(g->devs[0].device), "hipSetDevice");
-    HIP_OK(hipMemcpyAsync(all.data(), g->devs[0].d_recv, all.size() * sizeof(hpfw_hit), hipMemcpyDeviceToHost, g->devs[0].stream),
-           "D2H copy of the gathered lists");
-    for (int i = 0; i < m; ++i) {
-        HIP_OK(hipSetDevice(g->devs[(size_t)i].device), "hipSetDevice");
-        HIP_OK(hipStreamSynchronize(g->devs[(size_t)i].stream), "all-gather");
-    }
-    return hpfw_gpu_merge_topk(all.data(), n, n_q, k, out);
-}
-
-// ---- key, tempo and scored searches over the shards (include/hpfw_gpu_multi_search.h) --------
+// ---- the searches over the shards (include/hpfw_gpu_multi.h, include/hpfw_gpu_multi_search.h) ----
 namespace {
 
-// One body for the three searches: n_sets = 0 is the plain search (one query set per query, hpfw_hit), n_sets >= 1 the
+// One body for the four searches: n_sets = 0 is the plain search (one query set per query, hpfw_hit), n_sets >= 1 the
 // transposed one (hpfw_shift_hit); stats non-null asks for the moments.  Every device's send buffer is
 // [local shard][n_q][k] hits, then [local shard][rows] moments; the gathered buffer holds one such region per device.
 int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_sets, int k, void *out,
@@ -382,82 +316,97 @@ int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, 
     const size_t send = (hits_dev + stats_dev + 15) / 16 * 16; // a device's region of the gathered buffer stays 16-byte aligned
     for (Dev &d : g->devs) {
         HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-        int rc = grow((void **)&d.d_send, &d.send_cap, send);
-        if (!rc) rc = grow((void **)&d.d_recv, &d.recv_cap, send * m);
+        int rc = ensure(d.d_send, send);
+        if (!rc) rc = ensure(d.d_recv, send * m);
         if (rc) return rc;
     }
     Dev &d0 = g->devs[0];
     HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
-    int rc = grow(&d0.d_merged, &d0.merged_cap, list + srows);
-    if (!rc && m > 1) rc = grow(&d0.d_pack, &d0.pack_cap, (hits_dev + stats_dev) * m);
+    int rc = ensure(d0.d_merged, list + srows);
+    if (!rc && m > 1) rc = ensure(d0.d_pack, (hits_dev + stats_dev) * m);
     if (rc) return rc;
+
     // 1. every shard: replicated queries in, its own search into its slots of the device's send buffer
-    rc = per_shard(g, [&](int i) {
-        Shard &s = g->shards[(size_t)i];
-        Dev &d = g->devs[(size_t)s.dev_slot];
-        int r = grow((void **)&s.d_q, &s.q_cap, (size_t)std::max<int64_t>(total, 1) * 8);
-        if (r) return r;
-        if (total && hipMemcpyAsync(s.d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice, s.stream) != hipSuccess)
-            return fail(HPFW_E_HIP, "H2D copy of the queries failed");
-        char *base = reinterpret_cast<char *>(d.d_send);
-        void *hits = base + (size_t)s.local * list;
-        hpfw_dist_stats *st = stats ? reinterpret_cast<hpfw_dist_stats *>(base + hits_dev + (size_t)s.local * srows) : nullptr;
-        if (transposed)
-            r = st ? hpfw_gpu_search_topk_transposed_scored_device(s.h, s.d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, st, s.stream)
-                   : hpfw_gpu_search_topk_transposed_device(s.h, s.d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, s.stream);
-        else
-            r = st ? hpfw_gpu_search_topk_scored_device(s.h, s.d_q, rel.data(), n_q, k, (hpfw_hit *)hits, st, s.stream)
-                   : hpfw_gpu_search_topk_device(s.h, s.d_q, rel.data(), n_q, k, (hpfw_hit *)hits, s.stream);
-        if (r) return r;
-        if (hipEventRecord(s.done, s.stream) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
-        return 0;
-    });
-    if (rc) return rc;
+    const auto fan_out = [&]() {
+        return per_shard(g, [&](int i) {
+            Shard &s = g->shards[(size_t)i];
+            int r = ensure(s.d_q, (size_t)std::max<int64_t>(total, 1) * 8);
+            if (r) return r;
+            uint64_t *d_q = s.d_q.as<uint64_t>();
+            if (total && hipMemcpyAsync(d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice, s.stream.get()) != hipSuccess)
+                return fail(HPFW_E_HIP, "H2D copy of the queries failed");
+            char *base = g->devs[(size_t)s.dev_slot].d_send.as<char>();
+            void *hits = base + (size_t)s.local * list;
+            hpfw_dist_stats *st = stats ? reinterpret_cast<hpfw_dist_stats *>(base + hits_dev + (size_t)s.local * srows) : nullptr;
+            hpfw_gpu *h = s.h.get();
+            hipStream_t on = s.stream.get();
+            if (transposed)
+                r = st ? hpfw_gpu_search_topk_transposed_scored_device(h, d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, st, on)
+                       : hpfw_gpu_search_topk_transposed_device(h, d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, on);
+            else
+                r = st ? hpfw_gpu_search_topk_scored_device(h, d_q, rel.data(), n_q, k, (hpfw_hit *)hits, st, on)
+                       : hpfw_gpu_search_topk_device(h, d_q, rel.data(), n_q, k, (hpfw_hit *)hits, on);
+            if (r) return r;
+            if (hipEventRecord(s.done.get(), on) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
+            return 0;
+        });
+    };
     // 2. the exchange step: one all-gather of a device's hits and moments
-    for (Dev &d : g->devs) {
-        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-        for (int si : d.shards) HIP_OK(hipStreamWaitEvent(d.stream, g->shards[(size_t)si].done, 0), "hipStreamWaitEvent");
-    }
-    NCCL_OK(ncclGroupStart(), "ncclGroupStart");
-    for (Dev &d : g->devs) {
-        ncclResult_t r = ncclAllGather(d.d_send, d.d_recv, send, ncclUint8, d.comm, d.stream);
-        if (r != ncclSuccess) {
-            (void)ncclGroupEnd();
-            return fail(HPFW_E_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
+    const auto all_gather = [&]() {
+        for (Dev &d : g->devs) {
+            HIP_OK(hipSetDevice(d.device), "hipSetDevice");
+            for (int si : d.shards)
+                HIP_OK(hipStreamWaitEvent(d.stream.get(), g->shards[(size_t)si].done.get(), 0), "hipStreamWaitEvent");
         }
-    }
-    NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
+        NCCL_OK(ncclGroupStart(), "ncclGroupStart");
+        for (Dev &d : g->devs) {
+            ncclResult_t r = ncclAllGather(d.d_send.get(), d.d_recv.get(), send, ncclUint8, d.comm.get(), d.stream.get());
+            if (r != ncclSuccess) {
+                (void)ncclGroupEnd();
+                return fail(HPFW_E_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
+            }
+        }
+        NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
+        return 0;
+    };
     // 3. device 0 merges the n lists and sums the n rows where they lie; the host takes n_q k hits and the rows.
     //    One device: its region is already in[shard][q][k] and in[shard][row]; several: the regions' halves are packed first.
-    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
-    const char *recv = reinterpret_cast<const char *>(d0.d_recv);
-    const char *hits_in = recv, *stats_in = recv + hits_dev;
-    if (m > 1) {
-        char *pack = reinterpret_cast<char *>(d0.d_pack);
-        for (int i = 0; i < m; ++i) {
-            HIP_OK(hipMemcpyAsync(pack + (size_t)i * hits_dev, recv + (size_t)i * send, hits_dev, hipMemcpyDeviceToDevice, d0.stream),
-                   "packing the gathered lists");
-            if (stats_dev)
-                HIP_OK(hipMemcpyAsync(pack + (size_t)m * hits_dev + (size_t)i * stats_dev, recv + (size_t)i * send + hits_dev, stats_dev,
-                                      hipMemcpyDeviceToDevice, d0.stream),
-                       "packing the gathered moments");
+    const auto merge_and_fetch = [&]() {
+        hipStream_t on = d0.stream.get();
+        HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+        const char *recv = d0.d_recv.as<char>();
+        const char *hits_in = recv, *stats_in = recv + hits_dev;
+        if (m > 1) {
+            char *pack = d0.d_pack.as<char>();
+            for (int i = 0; i < m; ++i) {
+                HIP_OK(hipMemcpyAsync(pack + (size_t)i * hits_dev, recv + (size_t)i * send, hits_dev, hipMemcpyDeviceToDevice, on),
+                       "packing the gathered lists");
+                if (stats_dev)
+                    HIP_OK(hipMemcpyAsync(pack + (size_t)m * hits_dev + (size_t)i * stats_dev, recv + (size_t)i * send + hits_dev, stats_dev,
+                                          hipMemcpyDeviceToDevice, on),
+                           "packing the gathered moments");
+            }
+            hits_in = pack;
+            stats_in = pack + (size_t)m * hits_dev;
         }
-        hits_in = pack;
-        stats_in = pack + (size_t)m * hits_dev;
-    }
-    hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h;
-    char *merged = reinterpret_cast<char *>(d0.d_merged);
-    if ((rc = hpfw_gpu_merge_topk_device(h0, hits_in, n, n_q, k, merged, d0.stream))) return rc;
-    if (stats && (rc = hpfw_gpu_sum_stats_device(h0, reinterpret_cast<const hpfw_dist_stats *>(stats_in), n, rows,
-                                                 reinterpret_cast<hpfw_dist_stats *>(merged + list), d0.stream)))
-        return rc;
-    HIP_OK(hipMemcpyAsync(out, merged, list, hipMemcpyDeviceToHost, d0.stream), "D2H copy of the merged lists");
-    if (stats) HIP_OK(hipMemcpyAsync(stats, merged + list, srows, hipMemcpyDeviceToHost, d0.stream), "D2H copy of the moments");
-    for (int i = 0; i < m; ++i) {
-        HIP_OK(hipSetDevice(g->devs[(size_t)i].device), "hipSetDevice");
-        HIP_OK(hipStreamSynchronize(g->devs[(size_t)i].stream), "all-gather");
-    }
-    return 0;
+        hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h.get();
+        char *merged = d0.d_merged.as<char>();
+        int r = hpfw_gpu_merge_topk_device(h0, hits_in, n, n_q, k, merged, on);
+        if (!r && stats)
+            r = hpfw_gpu_sum_stats_device(h0, reinterpret_cast<const hpfw_dist_stats *>(stats_in), n, rows,
+                                          reinterpret_cast<hpfw_dist_stats *>(merged + list), on);
+        if (r) return r;
+        HIP_OK(hipMemcpyAsync(out, merged, list, hipMemcpyDeviceToHost, on), "D2H copy of the merged lists");
+        if (stats) HIP_OK(hipMemcpyAsync(stats, merged + list, srows, hipMemcpyDeviceToHost, on), "D2H copy of the moments");
+        return 0;
+    };
+    // From the first upload on, queued work reads rel and q_hp and writes out and stats: whichever step fails, the call
+    // returns only after every stream of the group has been waited for.  A failure of the wait is reported when nothing
+    // failed before it.
+    if (!(rc = fan_out()) && !(rc = all_gather())) rc = merge_and_fetch();
+    const hipError_t waited = drain(g);
+    if (!rc && waited != hipSuccess) rc = fail(HPFW_E_HIP, std::string("all-gather: ") + hipGetErrorString(waited));
+    return rc;
 }
 
 // the argument checks of the one-handle functions, before the group or any device is touched
@@ -473,6 +422,11 @@ int group_search_checked(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t 
 }
 
 } // namespace
+
+int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out)
+{
+    return group_search_checked(g, q_hp, q_off, n_q, 0, false, k, out, nullptr, false);
+}
 
 int hpfw_gpu_group_search_topk_scored(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out,
                                       hpfw_dist_stats *stats)
@@ -496,7 +450,7 @@ int hpfw_gpu_group_extract_windows_pcm16(hpfw_gpu_group *g, const int16_t *pcm, 
                                          const float *tempos, int n_tempos, const int32_t *shifts, int n_shifts, uint64_t *hp)
 {
     if (!g) return fail(HPFW_E_INVALID, "null group");
-    hpfw_gpu *h0 = g->shards[0].h;
+    hpfw_gpu *h0 = g->shards[0].h.get();
     // the one-handle call's checks (lists, projection mode, window and hop, a window too short for the slowest tempo), made
     // once: over no samples it checks everything and extracts nothing
     int rc = hpfw_gpu_extract_windows_pcm16_host(h0, nullptr, 0, win, hop, tempos, n_tempos, shifts, n_shifts, nullptr);
@@ -514,12 +468,8 @@ int hpfw_gpu_group_extract_windows_pcm16(hpfw_gpu_group *g, const int16_t *pcm, 
         n_hp = c_t - (HPFW_CONTEXT - 1) - HPFW_LAG;
     }
     const int64_t per_window = (int64_t)(tempos ? n_tempos : 1) * std::max(n_shifts, 1) * n_hp;
-    const int n = (int)g->shards.size();
-    return per_shard(g, [&](int i) {
-        int64_t lo, hi;
-        hpfw_gpu_shard_range(n_w, i, n, &lo, &hi);
-        if (hi == lo) return 0;
-        return hpfw_gpu_extract_windows_pcm16_host(g->shards[(size_t)i].h, pcm + lo * hop, (hi - 1 - lo) * hop + win, win, hop, tempos,
+    return per_shard_range(g, n_w, [&](int i, int64_t lo, int64_t hi) {
+        return hpfw_gpu_extract_windows_pcm16_host(g->shards[(size_t)i].h.get(), pcm + lo * hop, (hi - 1 - lo) * hop + win, win, hop, tempos,
                                                    n_tempos, shifts, n_shifts, hp + lo * per_window);
     });
 }
@@ -528,7 +478,7 @@ int hpfw_gpu_group_cov_reset(hpfw_gpu_group *g)
 {
     if (!g) return fail(HPFW_E_INVALID, "null group");
     for (Shard &s : g->shards) {
-        const int rc = hpfw_gpu_cov_reset(s.h);
+        const int rc = hpfw_gpu_cov_reset(s.h.get());
         if (rc) return rc;
     }
     return 0;
@@ -537,12 +487,8 @@ int hpfw_gpu_group_cov_reset(hpfw_gpu_group *g)
 int hpfw_gpu_group_cov_accumulate_pcm16(hpfw_gpu_group *g, const int16_t *pcm, int64_t n_samples, int64_t n_clips)
 {
     if (!g || !pcm || n_clips < 0) return fail(HPFW_E_INVALID, "bad argument");
-    const int n = (int)g->shards.size();
-    return per_shard(g, [&](int i) {
-        int64_t lo, hi;
-        hpfw_gpu_shard_range(n_clips, i, n, &lo, &hi);
-        if (hi == lo) return 0;
-        return hpfw_gpu_cov_accumulate_pcm16_host(g->shards[(size_t)i].h, pcm + lo * n_samples, n_samples, hi - lo);
+    return per_shard_range(g, n_clips, [&](int i, int64_t lo, int64_t hi) {
+        return hpfw_gpu_cov_accumulate_pcm16_host(g->shards[(size_t)i].h.get(), pcm + lo * n_samples, n_samples, hi - lo);
     });
 }
 
@@ -568,7 +514,7 @@ static int sum_covariances(hpfw_gpu_group *g, const std::vector<hpfw_gpu *> &hs,
         NCCL_OK(ncclGroupStart(), "ncclGroupStart");
         for (Dev &d : g->devs) {
             float *p = d_cov[(size_t)d.shards[0]];
-            ncclResult_t r = ncclAllReduce(p, p, nn, ncclFloat, ncclSum, d.comm, d.stream);
+            ncclResult_t r = ncclAllReduce(p, p, nn, ncclFloat, ncclSum, d.comm.get(), d.stream.get());
             if (r != ncclSuccess) {
                 (void)ncclGroupEnd();
                 return fail(HPFW_E_HIP, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
@@ -577,7 +523,7 @@ static int sum_covariances(hpfw_gpu_group *g, const std::vector<hpfw_gpu *> &hs,
         NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
         for (Dev &d : g->devs) {
             HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-            HIP_OK(hipStreamSynchronize(d.stream), "all-reduce");
+            HIP_OK(hipStreamSynchronize(d.stream.get()), "all-reduce");
         }
     } else {
         // shards that share a device: their matrices are summed on the host (RCCL has one rank per device)
@@ -598,19 +544,19 @@ int hpfw_gpu_group_learn_filters(hpfw_gpu_group *g, float *filters_out)
 {
     if (!g) return fail(HPFW_E_INVALID, "null group");
     std::vector<hpfw_gpu *> hs;
-    for (Shard &s : g->shards) hs.push_back(s.h);
+    for (Shard &s : g->shards) hs.push_back(s.h.get());
     int64_t files = 0;
     int rc = sum_covariances(g, hs, &files);
     if (rc) return rc;
     std::vector<float> f((size_t)HPFW_FILTERS * HPFW_FRAME_SIZE);
-    HIP_OK(hipSetDevice(g->devs[(size_t)g->shards[0].dev_slot].device), "hipSetDevice");
-    if ((rc = hpfw_gpu_learn_filters(g->shards[0].h, f.data()))) return rc;
+    HIP_OK(hipSetDevice(g->shards[0].device), "hipSetDevice");
+    if ((rc = hpfw_gpu_learn_filters(g->shards[0].h.get(), f.data()))) return rc;
     for (size_t i = 1; i < g->shards.size(); ++i)
-        if ((rc = hpfw_gpu_set_filters(g->shards[i].h, f.data()))) return rc;
+        if ((rc = hpfw_gpu_set_filters(g->shards[i].h.get(), f.data()))) return rc;
     // the reference keeps accumulating across calls (parallel_collector.h:93-97): the total stays on shard 0 only, so
     // that an accumulate + learn that follows adds every earlier file once and not once per shard
     for (size_t i = 1; i < g->shards.size(); ++i)
-        if ((rc = hpfw_gpu_cov_reset(g->shards[i].h))) return rc;
+        if ((rc = hpfw_gpu_cov_reset(g->shards[i].h.get()))) return rc;
     if (filters_out) std::memcpy(filters_out, f.data(), f.size() * 4);
     return 0;
 }
@@ -621,10 +567,8 @@ static int ensure_collectors(hpfw_gpu_group *g, const char *cache)
     if (cache && *cache) g->cache = cache;
     if (!g->collectors.empty()) return 0;
     for (size_t i = 0; i < g->shards.size(); ++i) {
-        const int dev = g->devs[(size_t)g->shards[i].dev_slot].device;
-        hpfw_legacy_collector *c = hpfw_internal_collector_on_device(dev, g->cache.c_str());
+        hpfw_legacy_collector *c = hpfw_internal_collector_on_device(g->shards[i].device, g->cache.c_str());
         if (!c) {
-            for (hpfw_legacy_collector *d : g->collectors) par_collector_del(d);
             g->collectors.clear();
             return HPFW_E_HIP; // message set by hpfw_gpu_create
         }
@@ -632,7 +576,7 @@ static int ensure_collectors(hpfw_gpu_group *g, const char *cache)
         // live_song_id.h:23-29): it enters the sum once, through shard 0
         if (i > 0) (void)hpfw_gpu_cov_reset(hpfw_internal_collector_gpu(c));
         (void)hpfw_gpu_collector_set_resample(c, g->resample);
-        g->collectors.push_back(c);
+        g->collectors.emplace_back(c);
     }
     return 0;
 }
@@ -641,7 +585,7 @@ int hpfw_gpu_group_set_resample(hpfw_gpu_group *g, int on)
 {
     if (!g) return fail(HPFW_E_INVALID, "null group");
     g->resample = on != 0;
-    for (hpfw_legacy_collector *c : g->collectors) (void)hpfw_gpu_collector_set_resample(c, g->resample);
+    for (auto &c : g->collectors) (void)hpfw_gpu_collector_set_resample(c.get(), g->resample);
     return 0;
 }
 
@@ -651,8 +595,8 @@ int hpfw_gpu_group_load(hpfw_gpu_group *g, const char *cache)
     if (!g->collectors.empty()) { // load again: every shard re-reads the cache
         if (cache && *cache) g->cache = cache;
         for (size_t i = 0; i < g->collectors.size(); ++i) {
-            par_collector_load(g->collectors[i], g->cache.c_str());
-            if (i > 0) (void)hpfw_gpu_cov_reset(hpfw_internal_collector_gpu(g->collectors[i]));
+            par_collector_load(g->collectors[i].get(), g->cache.c_str());
+            if (i > 0) (void)hpfw_gpu_cov_reset(hpfw_internal_collector_gpu(g->collectors[i].get()));
         }
         return 0;
     }
@@ -664,7 +608,7 @@ int hpfw_gpu_group_save(hpfw_gpu_group *g, const char *cache)
     if (!g) return fail(HPFW_E_INVALID, "null group");
     if (cache && *cache) g->cache = cache;
     if (g->collectors.empty()) return 0; // nothing loaded, nothing learned
-    par_collector_save(g->collectors[0], g->cache.c_str());
+    par_collector_save(g->collectors[0].get(), g->cache.c_str());
     return 0;
 }
 
@@ -683,7 +627,7 @@ FilenameHashprintPair *hpfw_gpu_group_prepare(hpfw_gpu_group *g, const char **fi
     for (int i = 0; i < ns; ++i) hpfw_gpu_shard_range(n, i, ns, &lo[(size_t)i], &hi[(size_t)i]);
     // 1. preprocess (parallel_collector.h:82-105) on every shard's block of files
     int rc = per_shard(g, [&](int i) {
-        jobs[(size_t)i] = hpfw_internal_prepare_accumulate(g->collectors[(size_t)i], filenames + lo[(size_t)i],
+        jobs[(size_t)i] = hpfw_internal_prepare_accumulate(g->collectors[(size_t)i].get(), filenames + lo[(size_t)i],
                                                            (int)(hi[(size_t)i] - lo[(size_t)i]), learn ? 1 : 0);
         return jobs[(size_t)i] ? 0 : (int)HPFW_E_NOMEM;
     });
@@ -691,16 +635,16 @@ FilenameHashprintPair *hpfw_gpu_group_prepare(hpfw_gpu_group *g, const char **fi
     bool ok = rc == 0;
     if (ok && learn) {
         std::vector<hpfw_gpu *> hs;
-        for (hpfw_legacy_collector *c : g->collectors) hs.push_back(hpfw_internal_collector_gpu(c));
+        for (auto &c : g->collectors) hs.push_back(hpfw_internal_collector_gpu(c.get()));
         int64_t files = 0, used = 0;
         for (hpfw_prepare_job *j : jobs) used += hpfw_internal_prepare_used(j);
         std::vector<float> f((size_t)HPFW_FILTERS * HPFW_FRAME_SIZE);
         ok = used > 0 && sum_covariances(g, hs, &files) == 0 && hipSetDevice(hpfw_gpu_device(hs[0])) == hipSuccess &&
              hpfw_gpu_learn_filters(hs[0], f.data()) == 0;
-        for (size_t i = 0; ok && i < g->collectors.size(); ++i) ok = hpfw_internal_collector_set_filters(g->collectors[i], f.data()) == 0;
+        for (size_t i = 0; ok && i < g->collectors.size(); ++i) ok = hpfw_internal_collector_set_filters(g->collectors[i].get(), f.data()) == 0;
         // the total stays on shard 0 only, so that the next prepare() adds every file once
         for (size_t i = 1; i < hs.size(); ++i) (void)hpfw_gpu_cov_reset(hs[i]);
-        if (ok) par_collector_save(g->collectors[0], g->cache.c_str());
+        if (ok) par_collector_save(g->collectors[0].get(), g->cache.c_str());
         if (used == 0) ok = true; // nothing readable: an empty result, as the single collector returns
     }
     // 3. collect_fingerprints (:115-137): every shard hashes its own files; shard 0 adds the older tracks of the cache
@@ -708,7 +652,7 @@ FilenameHashprintPair *hpfw_gpu_group_prepare(hpfw_gpu_group *g, const char **fi
     std::vector<int> part_n((size_t)ns, 0);
     (void)per_shard(g, [&](int i) {
         if (jobs[(size_t)i])
-            part[(size_t)i] = hpfw_internal_prepare_finish(g->collectors[(size_t)i], jobs[(size_t)i], filenames + lo[(size_t)i],
+            part[(size_t)i] = hpfw_internal_prepare_finish(g->collectors[(size_t)i].get(), jobs[(size_t)i], filenames + lo[(size_t)i],
                                                            (int)(hi[(size_t)i] - lo[(size_t)i]), ok ? 1 : 0, 0, &part_n[(size_t)i]);
         return 0;
     });
@@ -716,8 +660,8 @@ FilenameHashprintPair *hpfw_gpu_group_prepare(hpfw_gpu_group *g, const char **fi
     int cached_n = 0;
     if (ok && !std::getenv("HPFW_NO_SPECTRO_CACHE")) {
         // older tracks: an accumulate over zero files followed by a finish that walks the cache, told about all n names
-        hpfw_prepare_job *walk = hpfw_internal_prepare_accumulate(g->collectors[0], filenames, 0, 0);
-        if (walk) cached = hpfw_internal_prepare_finish_cached(g->collectors[0], walk, filenames, n, &cached_n);
+        hpfw_prepare_job *walk = hpfw_internal_prepare_accumulate(g->collectors[0].get(), filenames, 0, 0);
+        if (walk) cached = hpfw_internal_prepare_finish_cached(g->collectors[0].get(), walk, filenames, n, &cached_n);
     }
     if (!ok) {
         for (int i = 0; i < ns; ++i)
@@ -744,8 +688,8 @@ uint64_t *hpfw_gpu_group_calc_hashprint(hpfw_gpu_group *g, const char *filename,
 {
     if (size) *size = 0;
     if (!g || !filename || !size || ensure_collectors(g, nullptr)) return nullptr;
-    (void)hipSetDevice(g->devs[(size_t)g->shards[0].dev_slot].device);
-    return par_collector_calc_hashprint(g->collectors[0], filename, size);
+    (void)hipSetDevice(g->shards[0].device);
+    return par_collector_calc_hashprint(g->collectors[0].get(), filename, size);
 }
 
 } // extern "C"

@@ -139,39 +139,32 @@ class GpuGroup:
         """the clip offsets int64 [n_clips + 1] of the index as index_build last took it, from 0 (as Gpu.index_offsets)"""
         return self._offsets.copy()
 
-    def search_topk(self, q_hp, q_off, k):
+    def _search(self, fn, q_hp, q_off, n_q, extra, k, hit_dtype, stats_shape=None):
+        """contiguous queries and offsets in, fn(group, q, off, n_q, *extra, k, out[, stats]), out [n_q][k] (and the moments) back"""
         q = np.ascontiguousarray(q_hp, np.uint64).ravel()
         off = np.ascontiguousarray(q_off, np.int64)
-        out = np.zeros((off.size - 1, k), _lib.HIT_DTYPE)
-        _lib.check(lib().hpfw_gpu_group_search_topk(self._g, _lib._hp(q), _lib._hp(off), off.size - 1, int(k), _lib._hp(out)))
-        return out
+        out = np.zeros((n_q, k), hit_dtype)
+        stats = None if stats_shape is None else np.zeros(stats_shape, _lib.STATS_DTYPE)
+        tail = () if stats is None else (_lib._hp(stats),)
+        _lib.check(fn(self._g, _lib._hp(q), _lib._hp(off), n_q, *extra, int(k), _lib._hp(out), *tail))
+        return out if stats is None else (out, stats)
+
+    def search_topk(self, q_hp, q_off, k):
+        return self._search(lib().hpfw_gpu_group_search_topk, q_hp, q_off, np.size(q_off) - 1, (), k, _lib.HIT_DTYPE)
 
     # ---- key, tempo and scored searches, windows (include/hpfw_gpu_multi_search.h): what their Gpu namesakes return
     def search_topk_scored(self, q_hp, q_off, k):
         """(HIT_DTYPE [n_q][k], STATS_DTYPE [n_q])"""
-        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
-        off = np.ascontiguousarray(q_off, np.int64)
-        out = np.zeros((off.size - 1, k), _lib.HIT_DTYPE)
-        stats = np.zeros(off.size - 1, _lib.STATS_DTYPE)
-        _lib.check(lib().hpfw_gpu_group_search_topk_scored(self._g, _lib._hp(q), _lib._hp(off), off.size - 1, int(k), _lib._hp(out),
-                                                           _lib._hp(stats)))
-        return out, stats
+        n_q = np.size(q_off) - 1
+        return self._search(lib().hpfw_gpu_group_search_topk_scored, q_hp, q_off, n_q, (), k, _lib.HIT_DTYPE, n_q)
 
     def _transposed(self, q_hp, q_off, n_shifts, k, scored):
-        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
-        off = np.ascontiguousarray(q_off, np.int64)
-        if n_shifts < 1 or (off.size - 1) % n_shifts:
+        sets = np.size(q_off) - 1
+        if n_shifts < 1 or sets % n_shifts:
             raise ValueError("q_off must hold n_q * n_shifts + 1 offsets")
-        n_q = (off.size - 1) // n_shifts
-        out = np.zeros((n_q, k), _lib.SHIFT_HIT_DTYPE)
-        if not scored:
-            _lib.check(lib().hpfw_gpu_group_search_topk_transposed(self._g, _lib._hp(q), _lib._hp(off), n_q, int(n_shifts), int(k),
-                                                                   _lib._hp(out)))
-            return out
-        stats = np.zeros((n_q, n_shifts), _lib.STATS_DTYPE)
-        _lib.check(lib().hpfw_gpu_group_search_topk_transposed_scored(self._g, _lib._hp(q), _lib._hp(off), n_q, int(n_shifts), int(k),
-                                                                      _lib._hp(out), _lib._hp(stats)))
-        return out, stats
+        n_q = sets // n_shifts
+        fn = lib().hpfw_gpu_group_search_topk_transposed_scored if scored else lib().hpfw_gpu_group_search_topk_transposed
+        return self._search(fn, q_hp, q_off, n_q, (int(n_shifts),), k, _lib.SHIFT_HIT_DTYPE, (n_q, n_shifts) if scored else None)
 
     def search_topk_transposed(self, q_hp, q_off, n_shifts, k):
         """q_off [n_q * n_shifts + 1] -> SHIFT_HIT_DTYPE [n_q][k]"""

@@ -67,7 +67,7 @@ int64_t hpfw_gpu_group_index_size(const hpfw_gpu_group *g);
 void hpfw_gpu_shard_range(int64_t n_clips, int shard, int n_shards, int64_t *lo, int64_t *hi);
 
 /* MemoryStorage::find / the notebook's top-k (storage.h:27-64, liveid.ipynb cell 9) over the sharded index:
- * replicated queries -> per-shard scan + top-k -> ncclAllGather of the per-shard lists -> merge.
+ * replicated queries -> per-shard scan + top-k -> ncclAllGather of the per-shard lists -> merge on device 0.
  * out [n_q][k], ascending (dist, global clip id); identical to hpfw_gpu_search_topk on the unsharded index. */
 int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k,
                                hpfw_hit *out);

@@ -217,7 +217,7 @@ def _compare(g, gpu, oracle, n_clips, ks):
         ts, tstats = g.search_topk_transposed_scored(q_hp, q_off, V, k)
         assert ts.tobytes() == one_ts.tobytes() == one_t.tobytes() and tstats.tobytes() == one_tstats.tobytes(), (n_clips, k)
         assert tstats.shape == (len(sets) // V, V) and tstats.tobytes() == stats.tobytes()       # a variant's row is its plain row
-        assert np.array_equal(g.search_topk(q_hp, q_off, k), hits)                               # the unscored search, host merge
+        assert g.search_topk(q_hp, q_off, k).tobytes() == hits.tobytes()                         # the unscored search, the same body
         plain, moments, merged = _restated(oracle, n_clips, k)
         assert _rows(hits) == plain and _rows(ts, "shift_index") == merged, (n_clips, k)
         assert [(int(s["n"]), int(s["sum"]), int(s["sum_sq"])) for s in stats] == moments
@@ -238,12 +238,41 @@ def test_group_searches_equal_one_handle_and_oracle(torch_cuda, gpu, oracle, dev
         _compare(g, gpu, oracle, 206, (1, 10))
         g.index_build(db[:db_off[3]], db_off[:4])
         assert np.array_equal(g.index_offsets(), db_off[:4])
-        _compare(g, gpu, oracle, 3, (1, 10))
+        # 8 shards at k = 64: 512 candidates per query, almost all padding, whose order is what a merge can get wrong
+        _compare(g, gpu, oracle, 3, (1, 10, 64) if len(devices) == 8 else (1, 10))
         # one query alone, and no query at all
         one = g.search_topk_transposed_scored(q_hp[q_off[V]:q_off[2 * V]], q_off[V:2 * V + 1] - q_off[V], V, 4)
         assert np.array_equal(one[0], _one_handle(gpu, 3, 10)[2][0][1:2, :4])
         none_hits, none_stats = g.search_topk_scored(np.zeros(1, np.uint64), np.zeros(1, np.int64), 3)
         assert none_hits.shape == (0, 3) and none_stats.shape == (0,)
+    finally:
+        g.close()
+
+
+def test_group_lifecycle(torch_cuda):
+    """what the group owns comes and goes with it: (a) eight shards created and closed with nothing in between, every owner
+    destroyed empty; (b) three rounds of create, build, a plain and a transposed scored search, close, with equal results;
+    (c) a placement naming an ordinal that does not exist is refused after part of the group was built, and the next group
+    works"""
+    db, db_off, _, q_hp, q_off = _workload()
+    multi.GpuGroup([0] * 8).close()
+    rounds = []
+    for _ in range(3):
+        g = multi.GpuGroup([0, 0])
+        try:
+            g.index_build(db[:db_off[3]], db_off[:4])
+            ts, tstats = g.search_topk_transposed_scored(q_hp, q_off, V, 10)
+            rounds.append((g.search_topk(q_hp, q_off, 10).tobytes(), ts.tobytes(), tstats.tobytes()))
+        finally:
+            g.close()
+    assert rounds[0] == rounds[1] == rounds[2] and (np.frombuffer(rounds[0][0], _lib.HIT_DTYPE)["clip"] != NONE).any()
+    with pytest.raises(hpfw_amd.HpfwError, match="no device") as e:
+        multi.GpuGroup([0, _n_devices()])
+    assert e.value.status == _lib.E_INVALID
+    g = multi.GpuGroup([0, 0])
+    try:
+        g.index_build(db[:db_off[3]], db_off[:4])
+        assert g.search_topk(q_hp, q_off, 10).tobytes() == rounds[0][0]
     finally:
         g.close()
 

@@ -38,8 +38,8 @@ def _message():
 
 
 def test_bad_arguments_are_refused_before_any_device_is_used():
-    """there is no device here and no group: a bad k, a bad n_shifts and null stats are named by the messages of the one-handle
-    functions although the group is NULL, so they are checked before the group (and through it a device) is looked at; a NULL
+    """there is no device here and no group: a bad k (the plain search included), a bad n_shifts and null stats are named by the
+    messages of the one-handle functions although the group is NULL, so they are checked before the group (and through it a device) is looked at; a NULL
     group with good arguments is refused too"""
     M = multi.lib()
     q = np.zeros(8, np.uint64)
@@ -50,15 +50,18 @@ def test_bad_arguments_are_refused_before_any_device_is_used():
     scored = lambda k, st: M.hpfw_gpu_group_search_topk_scored(None, P(q), P(off), 4, k, P(hits), st)
     transposed = lambda ns, k: M.hpfw_gpu_group_search_topk_transposed(None, P(q), P(off), 2, ns, k, P(hits))
     both = lambda ns, k, st: M.hpfw_gpu_group_search_topk_transposed_scored(None, P(q), P(off), 2, ns, k, P(hits), st)
+    plain = lambda k: M.hpfw_gpu_group_search_topk(None, P(q), P(off), 4, k, P(hits))
     for k in (0, 65, -1):
         for rc in (scored(k, P(stats)), transposed(2, k), both(2, k, P(stats))):
             assert rc == E_INVALID and _message() == "k must be in 1..64", (k, _message())
+    for k in (0, 65):                                              # the plain search goes through the same checks
+        assert plain(k) == E_INVALID and _message() == "k must be in 1..64", (k, _message())
     for ns in (0, 65, -3):
         for rc in (transposed(ns, 3), both(ns, 3, P(stats))):
             assert rc == E_INVALID and _message() == "bad argument", (ns, _message())
     for rc in (scored(3, None), both(2, 3, None)):
         assert rc == E_INVALID and _message() == "null stats"
-    for rc in (scored(3, P(stats)), transposed(2, 3), both(2, 3, P(stats))):   # nothing wrong but the group
+    for rc in (plain(3), scored(3, P(stats)), transposed(2, 3), both(2, 3, P(stats))):   # nothing wrong but the group
         assert rc == E_INVALID and _message() == "bad argument"
     assert M.hpfw_gpu_group_extract_windows_pcm16(None, P(np.zeros(4, np.int16)), 4, 220500, 110250, None, 0, None, 0, P(q)) == E_INVALID
     # the two device entry points: the checks of the host merge, before the handle is used
