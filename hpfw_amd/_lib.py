@@ -58,7 +58,7 @@ EXPORTS = (
     "hpfw_gpu_cfg_set_filters", "hpfw_gpu_cfg_hashprints", "hpfw_gpu_mel_hashprints_pcm16_host",
     "hpfw_gpu_cfg_cov_reset", "hpfw_gpu_cfg_cov_accumulate", "hpfw_gpu_cfg_cov_get", "hpfw_gpu_cfg_learn_filters",
     "hpfw_gpu_set_kernel_timing", "hpfw_gpu_get_kernel_timing", "hpfw_gpu_plan_checksum",
-    "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_plan_cols_tables", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_debug_db_term_sweep", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
+    "hpfw_gpu_plan_checksum_ex", "hpfw_gpu_plan_cols_tables", "hpfw_gpu_plan_bz_shape", "hpfw_gpu_set_conventions", "hpfw_gpu_chirpz_table", "hpfw_gpu_debug_workspace", "hpfw_gpu_debug_db_term_sweep", "hpfw_gpu_prepare_length", "hpfw_gpu_set_projection", "hpfw_gpu_get_projection",
     "hpfw_gpu_hashprints_from_db", "hpfw_gpu_stage_delta_q", "hpfw_gpu_debug_q_products",
     "hpfw_gpu_mel_cov_accumulate_pcm16_host", "hpfw_gpu_combiner_clear", "hpfw_gpu_combiner_add",
     "hpfw_gpu_combiner_add_device", "hpfw_gpu_combiner_size", "hpfw_gpu_combiner_get", "hpfw_gpu_combiner_find",
@@ -213,6 +213,7 @@ def lib():
     L.hpfw_gpu_plan_checksum.argtypes = [i64, vp]
     L.hpfw_gpu_plan_checksum_ex.argtypes = [i64, i32, u32, vp]
     L.hpfw_gpu_plan_cols_tables.argtypes = [i64, vp, vp, vp, vp, vp]
+    L.hpfw_gpu_plan_bz_shape.argtypes = [i64, i32, vp]
     L.hpfw_gpu_chirpz_table.argtypes = [vp, i64, i32, vp, i64, vp]
     L.hpfw_gpu_debug_workspace.argtypes = [vp, i32, vp, vp]
     L.hpfw_gpu_debug_db_term_sweep.argtypes = [u32, ctypes.c_uint64, vp]
@@ -1242,3 +1243,17 @@ def plan_cols_tables(n_samples):
     if check_rc != 0:
         raise HpfwError(f"no column-stage tables for clip length {n_samples}")
     return dict(n1=n1, n2=n2, hq=hq, mt=mt, ks=ks, mt2=mt2, ks2=ks2, wq=wq, corr=corr, image=image, image2=image2)
+
+
+BZ_SHAPE_FIELDS = ("a", "n1", "L", "slack", "k1lo", "k1n", "need", "nt2", "n_tiles2", "step", "n_blocks", "n2", "n_tiles1",
+                   "kmin", "kmax")
+
+
+def plan_bz_shape(n_samples, force_bluestein=False):
+    """the shape of the chirp-z forward transform of a clip length (hpfw_gpu_plan_bz_shape, host only): a dict of a, n1 = 16 a,
+    L = n1 n2, slack = L - (n + (kmax - kmin) - 1), the consumed rows k1lo, k1n, their row tiles need, nt2, n_tiles2, the last
+    stage's step and n_blocks, n2, n_tiles1, kmin, kmax"""
+    d = np.zeros(len(BZ_SHAPE_FIELDS), np.int32)
+    if lib().hpfw_gpu_plan_bz_shape(int(n_samples), int(bool(force_bluestein)), _hp(d)) != 0:
+        raise HpfwError(f"no chirp-z forward transform for clip length {n_samples}")
+    return {k: int(v) for k, v in zip(BZ_SHAPE_FIELDS, d)}

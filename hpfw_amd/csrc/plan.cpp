@@ -280,6 +280,26 @@ static void parallel_rows(int64_t n, F fn)
 PlanSerial::PlanSerial() : before(g_plan_serial) { g_plan_serial = true; }
 PlanSerial::~PlanSerial() { g_plan_serial = before; }
 
+BzShape bz_shape(int n1, int n2, int kmin, int kmax)
+{
+    BzShape s;
+    s.a = n1 / 16;
+    s.n_tiles1 = (s.a + 15) / 16;
+    s.k1lo = kmin / n2;
+    s.k1n = (kmax - 1) / n2 - s.k1lo + 1;
+    s.need = (2 * s.k1n + 31) / 32;
+    s.nt2 = s.need < 3 ? s.need : 3;
+    s.n_tiles2 = (s.need + s.nt2 - 1) / s.nt2 * s.nt2;
+    // the second column stage walks the n1 residues in two register sets of `step` in turn, so in an even number of
+    // sets: of 16, 15 and 14 the step that pads n1 least (the larger one on a tie)
+    auto padded = [&](int step) { return ((n1 + step - 1) / step + 1) / 2 * 2 * step; };
+    s.step = 16;
+    for (int step : {15, 14})
+        if (padded(step) < padded(s.step)) s.step = step;
+    s.n_blocks = (n1 + s.step - 1) / s.step;
+    return s;
+}
+
 bool build_plan(int64_t n, HostPlan &p, std::string &why, bool geometry_only, bool force_bluestein, unsigned conv, bool host_windows)
 {
     if (n < 2) {
@@ -804,6 +824,21 @@ extern "C" int hpfw_gpu_plan_checksum_ex(int64_t n_samples, int force_bluestein,
     }
     out8[6] = ht;
     out8[7] = hv;
+    return 0;
+}
+
+// host-only: the shape of the chirp-z forward transform of a clip length (plan.h bz_shape), for the CPU-side checks of
+// which kernel classes a length runs.  out15 = {a, n1, L, slack, k1lo, k1n, need, nt2, n_tiles2, step, n_blocks, n2,
+// n_tiles1, kmin, kmax}; L = n1 n2, slack = L - (N + (kmax - kmin) - 1).  -2 when the length takes the mixed-radix transform.
+extern "C" int hpfw_gpu_plan_bz_shape(int64_t n_samples, int force_bluestein, int *out15)
+{
+    hpfw::HostPlan p;
+    std::string why;
+    if (!out15 || !hpfw::build_plan(n_samples, p, why, true, force_bluestein != 0) || !p.bluestein) return -2;
+    const hpfw::BzShape s = hpfw::bz_shape(p.n1, p.n2, p.kmin, p.kmax);
+    const int d[15] = {s.a, p.n1, (int)p.bz_l, (int)(p.bz_l - (n_samples + (p.kmax - p.kmin) - 1)), s.k1lo, s.k1n, s.need, s.nt2,
+                       s.n_tiles2, s.step, s.n_blocks, p.n2, s.n_tiles1, p.kmin, p.kmax};
+    std::copy(d, d + 15, out15);
     return 0;
 }
 

@@ -90,6 +90,15 @@ struct PlanSerial {
 // host_windows: build the constant-Q window table g on the host too (the product generates it on the device)
 bool build_plan(int64_t n_samples, HostPlan &out, std::string &why, bool geometry_only = false,
                 bool force_bluestein = false, unsigned conventions = 0, bool host_windows = true);
+// The shape of the chirp-z forward transform (S15) of a plan with n1 = 16 a rows of n2 points that consumes the bins
+// [kmin, kmax): what plans.hip sizes the coefficient images by and what k_bluestein.hip's launches choose their kernels by.
+struct BzShape {
+    int a, n_tiles1;           // n1 = 16 a; row tiles of 32 (16 outputs k_a each) of the first column stage's length-a transforms
+    int k1lo, k1n;             // rows k1lo .. k1lo + k1n - 1 of the second transform hold the consumed bins
+    int need, nt2, n_tiles2;   // row tiles of 32 that hold them; tiles per wave (at most 3); tiles of the image, a multiple of nt2
+    int step, n_blocks;        // bz_cols_kernel<1, step, nt2>: residues per register set, and the sets that hold n1 residues
+};
+BzShape bz_shape(int n1, int n2, int kmin, int kmax);
 // the two per-band constants of the window table (S5): shared by plan.cpp and the device generator's launch
 inline double cq_window_scale(unsigned conventions, int64_t big_m, int psize)
 {

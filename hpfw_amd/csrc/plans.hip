@@ -257,14 +257,14 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
         bz.n2pad = (p.n2 + 31) / 32 * 32;
         bz.kmin = p.kmin;
         bz.kmax = p.kmax;
-        bz.a = p.n1 / 16;
-        bz.n_tiles1 = (bz.a + 15) / 16;
-        bz.k1lo = p.kmin / p.n2;
-        bz.k1n = (p.kmax - 1) / p.n2 - bz.k1lo + 1;
         {
-            const int need = (2 * bz.k1n + 31) / 32; // row tiles of 32 that hold the consumed rows
-            bz.nt2 = need < 3 ? need : 3;
-            bz.n_tiles2 = (need + bz.nt2 - 1) / bz.nt2 * bz.nt2;
+            const hpfw::BzShape s = hpfw::bz_shape(p.n1, p.n2, p.kmin, p.kmax); // (plan.h)
+            bz.a = s.a;
+            bz.n_tiles1 = s.n_tiles1;
+            bz.k1lo = s.k1lo;
+            bz.k1n = s.k1n;
+            bz.nt2 = s.nt2;
+            bz.n_tiles2 = s.n_tiles2;
         }
         // coefficient images of the column transforms (the first one's two stages; the second one's rows that hold
         // consumed bins), packed on the device

@@ -405,6 +405,12 @@ int hpfw_gpu_plan_checksum_ex(int64_t n_samples, int force_bluestein, unsigned c
  * wq [2 n1] (Re, Im of rint(2^22 T_n1[m])), corr [2 hq], image [cols_mt * cols_ks * 3072] and image2
  * [cols2_mt * 2 * cols2_ks * 3072] bytes, the twiddle digits as the int8 matrix instructions read them. */
 int hpfw_gpu_plan_cols_tables(int64_t n_samples, int32_t *dims9, int32_t *wq, double *corr, int8_t *image, int8_t *image2);
+/* host-only: the shape of the chirp-z forward transform of n_samples (a length with a prime factor above 7, or
+ * any length with force_bluestein).  out15 = {a, n1 = 16 a, L = n1 n2, slack = L - (n_samples + (kmax - kmin) - 1), k1lo, k1n,
+ * need, nt2, n_tiles2, step, n_blocks, n2, n_tiles1, kmin, kmax}: the rows k1lo .. k1lo + k1n - 1 of the last stage hold the
+ * consumed bins, in `need` row tiles of 32, nt2 per wave, n_tiles2 in the coefficient image; that stage walks the n1 residues
+ * in n_blocks register sets of `step`.  -2 when the length takes the mixed-radix transform or is unsupported. */
+int hpfw_gpu_plan_bz_shape(int64_t n_samples, int force_bluestein, int *out15);
 
 /* ---- the projection's arithmetic.  The reference multiplies filters and frames in f32 (an Eigen/MKL sgemm,
  * parallel_collector.h:57,127) and keeps only the sign of P[r,i] - P[r,i+80] (hashprint_handle.h:119-122).  mode 1
