@@ -19,7 +19,6 @@ int64_t hpfw_internal_prepare_used(const hpfw_prepare_job *job); // files whose 
 // hashprints under the installed filters; consumes the job
 FilenameHashprintPair *hpfw_internal_prepare_finish(hpfw_legacy_collector *c, hpfw_prepare_job *job, const char **filenames, int n,
                                                     int ok, int with_cached, int *got);
-// every track of the cache except the n named files, sorted by name; consumes the job
-FilenameHashprintPair *hpfw_internal_prepare_finish_cached(hpfw_legacy_collector *c, hpfw_prepare_job *job, const char **filenames, int n,
-                                                           int *got);
+// every track of the cache except the n named files, sorted by name
+FilenameHashprintPair *hpfw_internal_prepare_finish_cached(hpfw_legacy_collector *c, const char **filenames, int n, int *got);
 }

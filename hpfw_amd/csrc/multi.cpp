@@ -658,11 +658,8 @@ FilenameHashprintPair *hpfw_gpu_group_prepare(hpfw_gpu_group *g, const char **fi
     });
     FilenameHashprintPair *cached = nullptr;
     int cached_n = 0;
-    if (ok && !std::getenv("HPFW_NO_SPECTRO_CACHE")) {
-        // older tracks: an accumulate over zero files followed by a finish that walks the cache, told about all n names
-        hpfw_prepare_job *walk = hpfw_internal_prepare_accumulate(g->collectors[0].get(), filenames, 0, 0);
-        if (walk) cached = hpfw_internal_prepare_finish_cached(g->collectors[0].get(), walk, filenames, n, &cached_n);
-    }
+    if (ok && !std::getenv("HPFW_NO_SPECTRO_CACHE")) // older tracks: a walk of the cache, told about all n names
+        cached = hpfw_internal_prepare_finish_cached(g->collectors[0].get(), filenames, n, &cached_n);
     if (!ok) {
         for (int i = 0; i < ns; ++i)
             if (part[(size_t)i]) prepare_result_free(part[(size_t)i], part_n[(size_t)i]);

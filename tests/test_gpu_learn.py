@@ -131,6 +131,34 @@ def test_legacy_prepare_mixed_lengths(torch_cuda, tmp_path, keep_gb, monkeypatch
     assert np.abs(cov - rawc).max() <= 2e-5 * np.abs(cov).max()
 
 
+def test_prepare_learning_and_caching_over_two_windows(torch_cuda, oracle, tmp_path):
+    """prepare() with learning and the spectrogram cache on over more files than one window holds (256): the second
+    window goes through the other pinned arena and the other device copy, and the pinned spectrogram buffer is used
+    again.  258 files of two lengths (2.0 s, and 7 samples less: a chirp-z length), so that each window holds two
+    groups; rolls of one clip keep the files cheap"""
+    base = synth.gen_clip(1400, 2.0)
+    paths, pcms = [], []
+    for i in range(258):
+        pcm = np.roll(base, 131 * i)[: base.size - 7 * (i & 1)]
+        p = str(tmp_path / f"w{i:03d}.wav")
+        synth.write_wav(p, pcm)
+        paths.append(p)
+        pcms.append(pcm)
+    cache = str(tmp_path / "cache") + "/"
+    pc = hpfw_amd.ParallelCollector()
+    pc.load(cache)
+    res = pc.prepare(paths)
+    assert [n for _, n in res] == [f"w{i:03d}" for i in range(258)]
+    for i in range(0, 258, 13):
+        assert np.array_equal(res[i][0], pc.calc_hashprint(paths[i])), i
+    raw = open(os.path.join(cache, "spectros", "w257"), "rb").read()
+    plan = oracle.Plan(pcms[257].size)
+    assert raw[:8] == np.array([121, plan.c], np.int32).tobytes() and len(raw) == 8 + 4 * 121 * plan.c
+    s_file = np.frombuffer(raw[8:], np.float32).reshape(plan.c, 121)
+    want = oracle.db(plan.cqmag(plan.spectrum(pcms[257])))
+    assert np.array_equal(s_file.T.view(np.uint32), want.view(np.uint32))
+
+
 def test_spectrogram_cache_and_incremental_indexing(torch_cuda, oracle, tmp_path):
     """f2: cache/spectros/<stem> (cache.h:30-33, utils.h:77-106) is written by prepare(), and a later prepare()
     -- a new collector, as a new process would hold -- returns hashprints for EVERY cached track under the

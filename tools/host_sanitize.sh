@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")/.."
 out=$(mktemp -d)
-src="tools/host_sanitize.cpp hpfw_amd/csrc/plan.cpp hpfw_amd/csrc/eigen_host.cpp"
+src="tools/host_sanitize.cpp hpfw_amd/csrc/plan.cpp hpfw_amd/csrc/eigen_host.cpp hpfw_amd/csrc/wav_file.cpp hpfw_amd/csrc/cache_files.cpp"
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Ihpfw_amd/csrc -Iinclude $src -o $out/asan -lpthread
 $out/asan
 g++ -std=c++17 -O1 -g -fsanitize=thread -Ihpfw_amd/csrc -Iinclude $src -o $out/tsan -lpthread
