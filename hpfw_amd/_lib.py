@@ -25,6 +25,9 @@ XCORR_JOB_DTYPE = np.dtype([("a_off", "<i8"), ("a_len", "<i8"), ("b_off", "<i8")
                             ("len", "<i8"), ("radius", "<i4"), ("pad", "<i4")])
 XCORR_PEAK_DTYPE = np.dtype([("r", "<i8"), ("energy_a", "<i8"), ("energy_b", "<i8"), ("lag", "<i4"), ("pad", "<i4")])
 XCORR_MAX_LEN, XCORR_MAX_RADIUS = 1 << 22, 4096
+# hpfw_warp_track: a track of the time warp and the mix
+WARP_TRACK_DTYPE = np.dtype([("src_off", "<i8"), ("src_len", "<i8"), ("i0", "<i8"), ("f0", "<i8"), ("d", "<i8"), ("gain", "<i4"),
+                             ("pad", "<i4")])
 # the timeline of a long recording: hpfw_dist_stats, hpfw_window_hit, hpfw_segment
 STATS_DTYPE = np.dtype([("sum", "<u8"), ("sum_sq", "<u8"), ("n", "<u4"), ("pad", "<u4")])
 WINDOW_HIT_DTYPE = np.dtype([("clip", "<u4"), ("offset", "<i4"), ("variant", "<i4"), ("pad", "<i4"), ("tempo", "<f8"),
@@ -66,6 +69,8 @@ EXPORTS = (
     "hpfw_gpu_xcorr_pcm16", "hpfw_gpu_xcorr_pcm16_host", "hpfw_gpu_mel_kept_frames_pcm16_host",
     "hpfw_gpu_wav_read_pcm16_any", "hpfw_gpu_resample_length", "hpfw_gpu_resample_table", "hpfw_gpu_resample_pcm16",
     "hpfw_gpu_resample_pcm16_host", "hpfw_gpu_collector_set_resample",
+    "hpfw_gpu_warp_table", "hpfw_gpu_warp_pcm16", "hpfw_gpu_warp_pcm16_host", "hpfw_gpu_mix_pcm16", "hpfw_gpu_mix_pcm16_host",
+    "hpfw_gpu_drift_anchors", "hpfw_gpu_drift_fit", "hpfw_gpu_time_map_q40", "hpfw_gpu_wav_write_pcm16",
     "hpfw_gpu_extract_transposed_pcm16", "hpfw_gpu_extract_transposed_pcm16_host", "hpfw_gpu_hashprints_from_db_transposed",
     "hpfw_gpu_search_topk_transposed_device", "hpfw_gpu_search_topk_transposed",
     "hpfw_gpu_tempo_columns", "hpfw_gpu_hashprints_from_db_tempo", "hpfw_gpu_extract_tempo_pcm16",
@@ -245,6 +250,17 @@ def lib():
     L.hpfw_gpu_resample_pcm16.argtypes = [vp, vp, i64, i64, i32, vp, vp]
     L.hpfw_gpu_resample_pcm16_host.argtypes = [vp, vp, i64, i64, i32, vp]
     L.hpfw_gpu_collector_set_resample.argtypes = [vp, i32]
+    L.hpfw_gpu_warp_table.argtypes = [vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.hpfw_gpu_warp_pcm16.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp]
+    L.hpfw_gpu_warp_pcm16_host.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
+    L.hpfw_gpu_mix_pcm16.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp]
+    L.hpfw_gpu_mix_pcm16_host.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
+    L.hpfw_gpu_drift_anchors.argtypes = [i64, i64, i64, i64, i64, i64, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                         ctypes.POINTER(i64)]
+    L.hpfw_gpu_drift_fit.argtypes = [vp, vp, i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                     ctypes.POINTER(ctypes.c_double)]
+    L.hpfw_gpu_time_map_q40.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.hpfw_gpu_wav_write_pcm16.argtypes = [ctypes.c_char_p, vp, i64, i32]
     L.hpfw_gpu_extract_transposed_pcm16.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
     L.hpfw_gpu_extract_transposed_pcm16_host.argtypes = [vp, vp, i64, i64, vp, i32, vp]
     L.hpfw_gpu_hashprints_from_db_transposed.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
@@ -616,6 +632,39 @@ class Gpu:
         if out.size:
             check(lib().hpfw_gpu_resample_pcm16_host(self._h, _hp(pcm), pcm.shape[1], pcm.shape[0], int(rate), _hp(out)))
         return out[0] if one else out
+
+    # ---- time warp and mix (k_warp.hip) ---------------------------------
+    warp_table = staticmethod(lambda: warp_table())
+
+    def _warp(self, pcm, tracks, m0, n_out, mix):
+        pcm = np.ascontiguousarray(pcm, np.int16).ravel()
+        tracks = np.ascontiguousarray(tracks, WARP_TRACK_DTYPE).ravel()
+        out = np.zeros(max(int(n_out), 0) if mix else (tracks.size, max(int(n_out), 0)), np.int16)
+        fn = lib().hpfw_gpu_mix_pcm16_host if mix else lib().hpfw_gpu_warp_pcm16_host
+        check(fn(self._h, _hp(pcm) if pcm.size else None, pcm.size, _hp(tracks) if tracks.size else None, tracks.size, int(m0), int(n_out),
+                 _hp(out) if out.size else None))
+        return out
+
+    def warp(self, pcm, tracks, m0, n_out):
+        """pcm int16 [n] (host), tracks WARP_TRACK_DTYPE (sources are ranges of pcm) -> int16 [n_tracks][n_out]: outputs
+        m0 .. m0 + n_out - 1 of every track, read at i0 + m + (f0 + m d) 2^-40; a negative gain negates"""
+        return self._warp(pcm, tracks, m0, n_out, False)
+
+    def mix(self, pcm, tracks, m0, n_out):
+        """-> int16 [n_out]: clamp((sum_k gain_k y_k + 2^14) >> 15) of the tracks' outputs, fused"""
+        return self._warp(pcm, tracks, m0, n_out, True)
+
+    def warp_dev(self, d_pcm, n_pcm, tracks, m0, n_out, d_out, stream=0):
+        """device pointers; tracks WARP_TRACK_DTYPE on the host; d_out int16 [n_tracks][n_out]"""
+        tracks = np.ascontiguousarray(tracks, WARP_TRACK_DTYPE).ravel()
+        check(lib().hpfw_gpu_warp_pcm16(self._h, d_pcm, int(n_pcm), _hp(tracks) if tracks.size else None, tracks.size, int(m0), int(n_out),
+                                        d_out, stream))
+
+    def mix_dev(self, d_pcm, n_pcm, tracks, m0, n_out, d_mix, stream=0):
+        """device pointers; d_mix int16 [n_out]"""
+        tracks = np.ascontiguousarray(tracks, WARP_TRACK_DTYPE).ravel()
+        check(lib().hpfw_gpu_mix_pcm16(self._h, d_pcm, int(n_pcm), _hp(tracks) if tracks.size else None, tracks.size, int(m0), int(n_out),
+                                       d_mix, stream))
 
     def set_projection(self, mode):
         """1 (default): fixed-point projection, exact integer sums (S9q); 0: the f32 fma chain (S9)"""
@@ -1191,6 +1240,50 @@ def resample_table(rate):
     if taps.size:
         check(lib().hpfw_gpu_resample_table(int(rate), _hp(taps), taps.size, ctypes.byref(L), ctypes.byref(M), ctypes.byref(T)))
     return int(L.value), int(M.value), taps
+
+
+def warp_table():
+    """taps int16 [P][T] of the time warp: row p the fractional delay p / P (hpfw_gpu_warp_table)"""
+    P, T = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().hpfw_gpu_warp_table(None, 0, ctypes.byref(P), ctypes.byref(T)))
+    taps = np.zeros((P.value, T.value), np.int16)
+    check(lib().hpfw_gpu_warp_table(_hp(taps), taps.size, ctypes.byref(P), ctypes.byref(T)))
+    return taps
+
+
+def drift_anchors(s_lo, s_hi, q, length, anchor_len, anchor_hop):
+    """(centre start, left starts going outward, right starts going outward) of a pair's anchors (hpfw_gpu_drift_anchors)"""
+    nl, nr, n = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    args = (int(s_lo), int(s_hi), int(q), int(length), int(anchor_len), int(anchor_hop))
+    check(lib().hpfw_gpu_drift_anchors(*args, None, 0, ctypes.byref(nl), ctypes.byref(nr), ctypes.byref(n)))
+    starts = np.zeros(n.value, np.int64)
+    check(lib().hpfw_gpu_drift_anchors(*args, _hp(starts), starts.size, ctypes.byref(nl), ctypes.byref(nr), ctypes.byref(n)))
+    return int(starts[0]), [int(v) for v in starts[1:1 + nl.value]], [int(v) for v in starts[1 + nl.value:]]
+
+
+def drift_fit(n, lag):
+    """(a, b, rms) of the Theil-Sen line lag ~ a + b n (hpfw_gpu_drift_fit; the centre anchor first)"""
+    n = np.ascontiguousarray(n, np.int64).ravel()
+    lag = np.ascontiguousarray(lag, np.int64).ravel()
+    if n.size != lag.size:
+        raise ValueError("drift_fit: one lag per position")
+    a, b, rms = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+    check(lib().hpfw_gpu_drift_fit(_hp(n) if n.size else None, _hp(lag) if n.size else None, n.size, ctypes.byref(a), ctypes.byref(b),
+                                   ctypes.byref(rms)))
+    return a.value, b.value, rms.value
+
+
+def time_map_q40(A, B):
+    """(i0, f0, d) of a source whose sample n sits at A + (1 + B) n of the output's timeline (hpfw_gpu_time_map_q40)"""
+    i0, f0, d = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().hpfw_gpu_time_map_q40(float(A), float(B), ctypes.byref(i0), ctypes.byref(f0), ctypes.byref(d)))
+    return i0.value, f0.value, d.value
+
+
+def wav_write(path, pcm, channels=1):
+    """int16 [n] (interleaved for 2 channels) as a 44.1 kHz PCM16 WAV file with a 44-byte header (hpfw_gpu_wav_write_pcm16)"""
+    pcm = np.ascontiguousarray(pcm, np.int16).ravel()
+    check(lib().hpfw_gpu_wav_write_pcm16(os.fsencode(path), _hp(pcm) if pcm.size else None, pcm.size, int(channels)))
 
 
 def merge_topk(per_shard_hits, k):

@@ -1,5 +1,5 @@
 // handle.h -- what the sources of the C-ABI declared in include/hpfw_gpu.h (handle.hip, plans.hip, extract.hip, learn.hip,
-// search.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
+// search.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
 // ParallelCollector::collect_fingerprints' parallel_for, reference
 // include/hpfw/core/parallel_collector.h:115-137) and MemoryStorage::build/find
 // (include/hpfw/audioproblems/live-song-id/storage.h:21-64).  All arithmetic is in the kernels.
@@ -226,6 +226,11 @@ struct hpfw_gpu {
         std::map<int, Table> tables;
         DevBuf in, out;
     } rs;
+    // time warp and mix (k_warp.hip, warp.hip): the device image of the table, made on first use; the tracks of the call in
+    // progress with their reach
+    struct Warp {
+        DevBuf d_taps, d_tracks;
+    } warp;
     // transposed queries (k_project_q.hip): the filter images of the shift list last used (cleared
     // with the filters)
     DevBuf d_shift_images;

@@ -421,6 +421,19 @@ std::vector<int32_t> resample_device_table(const std::vector<int16_t> &taps, int
 bool launch_resample(const int16_t *d_in, int64_t n_in, int64_t n_clips, int32_t L, int32_t M, int32_t T, const int32_t *d_taps,
                      int16_t *d_out, hipStream_t s);
 
+// time warp and mix of PCM16 (k_warp.hip; the constants and the host side: drift_plan.h)
+// a track as the kernels take it: hpfw_warp_track and the outputs [m_lo, m_hi] whose taps reach its source (warp_reach)
+struct WarpTrack {
+    int64_t src_off, src_len, i0, f0, d;
+    int32_t gain, pad;
+    int64_t m_lo, m_hi;
+};
+// the [4096][32] int16 table (host, float64): row p the fractional delay p / 4096, row 0 the unit impulse
+bool warp_design(std::vector<int16_t> &taps);
+// d_tab: resample_device_table's image of that table.  mix: d_out [n_out], the fused mix; else [n_tracks][n_out]
+void launch_warp(const int16_t *d_pcm, const WarpTrack *d_tracks, int64_t n_tracks, const int32_t *d_tab, int64_t m0, int64_t n_out, bool mix,
+                 int16_t *d_out, hipStream_t s);
+
 // fail-loud launch check
 const char *last_launch_error();
 

@@ -245,6 +245,18 @@ extern "C" int hpfw_gpu_wav_read_pcm16_any(const char *path, int16_t *out, int64
     return wav_read(path, out, cap, n, rate);
 }
 
+extern "C" int hpfw_gpu_wav_write_pcm16(const char *path, const int16_t *pcm, int64_t n, int channels)
+{
+    if (!path) {
+        hpfw_internal_set_error("null argument");
+        return HPFW_E_INVALID;
+    }
+    std::string why;
+    if (hpfw::write_wav_pcm16(path, pcm, n, channels, why)) return 0;
+    hpfw_internal_set_error(why.c_str());
+    return why.rfind("wav write:", 0) == 0 ? HPFW_E_INVALID : HPFW_E_IO;
+}
+
 extern "C" int hpfw_gpu_collector_set_resample(hpfw_legacy_collector *c, int on)
 {
     if (!c) {

@@ -122,4 +122,47 @@ bool read_wav_pcm16_mono(const std::string &path, std::vector<int16_t> &out, std
     return true;
 }
 
+bool write_wav_pcm16(const std::string &path, const int16_t *pcm, int64_t n, int channels, std::string &why)
+{
+    if ((channels != 1 && channels != 2) || n < 0 || n % channels || n > (INT64_C(0x7fffffff) - 36) / 2 || (n > 0 && !pcm)) {
+        why = "wav write: 1 or 2 channels, whole frames, less than 2^31 bytes";
+        return false;
+    }
+    const uint32_t bytes = (uint32_t)(n * 2), rate = 44100, riff = 36 + bytes, fmt_size = 16, byte_rate = rate * (uint32_t)channels * 2;
+    const uint16_t pcm_tag = 1, ch = (uint16_t)channels, align = (uint16_t)(channels * 2), bits = 16;
+    unsigned char hdr[44];
+    std::memcpy(hdr, "RIFF", 4);
+    std::memcpy(hdr + 4, &riff, 4);
+    std::memcpy(hdr + 8, "WAVEfmt ", 8);
+    std::memcpy(hdr + 16, &fmt_size, 4);
+    std::memcpy(hdr + 20, &pcm_tag, 2);
+    std::memcpy(hdr + 22, &ch, 2);
+    std::memcpy(hdr + 24, &rate, 4);
+    std::memcpy(hdr + 28, &byte_rate, 4);
+    std::memcpy(hdr + 32, &align, 2);
+    std::memcpy(hdr + 34, &bits, 2);
+    std::memcpy(hdr + 36, "data", 4);
+    std::memcpy(hdr + 40, &bytes, 4);
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    if (fd < 0) {
+        why = "cannot create " + path;
+        return false;
+    }
+    auto write_all = [&](const void *from, int64_t want) {
+        int64_t done = 0;
+        while (done < want) {
+            const ssize_t w = ::write(fd, static_cast<const char *>(from) + done, (size_t)(want - done));
+            if (w <= 0) break;
+            done += w;
+        }
+        return done == want;
+    };
+    const bool ok = write_all(hdr, 44) && write_all(pcm, (int64_t)bytes);
+    if (::close(fd) != 0 || !ok) {
+        why = path + ": short write";
+        return false;
+    }
+    return true;
+}
+
 } // namespace hpfw

@@ -33,4 +33,7 @@ bool read_mono(const WavProbe &w, int16_t *dst);
 // probe, resize, read_mono.  rate_any: NULL = 44.1 kHz only; else any rate in the range is accepted and stored there
 bool read_wav_pcm16_mono(const std::string &path, std::vector<int16_t> &out, std::string &why, uint32_t *rate_any = nullptr);
 
+// pcm [n] (interleaved when channels = 2) as a file with a 44-byte header: PCM16 at 44.1 kHz
+bool write_wav_pcm16(const std::string &path, const int16_t *pcm, int64_t n, int channels, std::string &why);
+
 } // namespace hpfw

@@ -303,6 +303,60 @@ int hpfw_gpu_resample_pcm16(hpfw_gpu *h, const int16_t *d_in, int64_t n_in, int6
                             void *stream);
 int hpfw_gpu_resample_pcm16_host(hpfw_gpu *h, const int16_t *in, int64_t n_in, int64_t n_clips, int rate, int16_t *out);
 
+/* ---- time warp and mix of PCM16: clock drift between recorders, and the event rendered (k_warp.hip, DESIGN.md
+ * section 16) ----
+ * A track is a range [src_off, src_off + src_len) of ONE int16 buffer, read at the affine position
+ * i0 + m + (f0 + m d) 2^-40 of output m.  For 0 <= m < 2^31, in exact integers:
+ *     u     = f0 + m d                          (int64)
+ *     ip    = i0 + m + (u >> 40)                (arithmetic shift: floor)
+ *     phase = (u & (2^40 - 1)) >> 28            (P = 4096 rows, truncated)
+ *     acc   = sum over j < T of x[ip - H + 1 + j] h[phase][j]        x = 0 outside [0, src_len); T = 2 H = 32; int32
+ *     y[m]  = clamp((acc + 2^13) >> 14, -32768, 32767)
+ * h is hpfw_gpu_warp_table's [P][T] int16 table in Q14: row p the windowed sinc of the fractional delay p / P, every row
+ * summing to 2^14 and row 0 the unit impulse, so that d = 0, f0 = 0 copies the source shifted by i0 bit for bit.
+ * HPFW_E_INVALID: a source range outside the buffer, |d| > 2^30 (977 ppm), f0 outside [0, 2^40), |i0| > 2^62,
+ * |gain| > 2^17, m0 < 0, n_out < 0, m0 + n_out > 2^31, null pointers. */
+typedef struct {
+    int64_t src_off, src_len; /* the source: a range of the pcm buffer */
+    int64_t i0, f0, d;        /* the time map */
+    int32_t gain, pad;        /* signed, Q15 */
+} hpfw_warp_track;
+/* the [P][T] int16 table (host only; taps may be NULL to ask for P and T; cap = its capacity) */
+int hpfw_gpu_warp_table(int16_t *taps, int64_t cap, int32_t *P, int32_t *T);
+/* outputs m0 .. m0 + n_out - 1 of every track -> d_out [n_tracks][n_out].  A negative gain negates the value before the
+ * clamp (+32768 becomes 32767); the size of the gain is not used.  d_pcm and d_out on the device, tracks on the host (read
+ * before the call returns).  The host variant uploads, synchronises and downloads. */
+int hpfw_gpu_warp_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_pcm, const hpfw_warp_track *tracks, int64_t n_tracks,
+                        int64_t m0, int64_t n_out, int16_t *d_out, void *stream);
+int hpfw_gpu_warp_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_pcm, const hpfw_warp_track *tracks, int64_t n_tracks,
+                             int64_t m0, int64_t n_out, int16_t *out);
+/* mix[m] = clamp((sum over the tracks of gain_k y_k[m] + 2^14) >> 15) -> d_mix [n_out], with y_k the clamped, un-negated
+ * value above and the sum in int64: no track is materialised, and the result equals the mix of materialised tracks bit for
+ * bit (integer sums have no order). */
+int hpfw_gpu_mix_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_pcm, const hpfw_warp_track *tracks, int64_t n_tracks,
+                       int64_t m0, int64_t n_out, int16_t *d_mix, void *stream);
+int hpfw_gpu_mix_pcm16_host(hpfw_gpu *h, const int16_t *pcm, int64_t n_pcm, const hpfw_warp_track *tracks, int64_t n_tracks,
+                            int64_t m0, int64_t n_out, int16_t *mix);
+/* Host only: the anchors of a pair.  [s_lo, s_hi) is the pair's overlap in the recording's samples, [q, q + len) the
+ * centre segment (len = min(anchor_len, overlap), as the refinement places it).  Further anchors of anchor_len samples start
+ * at q - t anchor_hop and q + t anchor_hop, t = 1, 2, ..., for as long as a whole anchor lies in the overlap; an overlap
+ * shorter than one anchor has the centre alone.  starts (NULL to count; cap = its capacity):
+ * [centre, left 1 .. *n_left, right 1 .. *n_right], *n = 1 + *n_left + *n_right. */
+int hpfw_gpu_drift_anchors(int64_t s_lo, int64_t s_hi, int64_t q, int64_t len, int64_t anchor_len, int64_t anchor_hop,
+                           int64_t *starts, int64_t cap, int32_t *n_left, int32_t *n_right, int64_t *n);
+/* Host only: the Theil-Sen line lag ~ a + b n.  b = the median of (lag_j - lag_i) / (n_j - n_i) over the pairs i < j in
+ * index order (pairs with equal n left out; the median of an even count is the mean of the two middle values), a = the
+ * median of lag_i - b n_i, rms = the root mean square of lag_i - (a + b n_i): float64 in exactly this order.  Fewer than 3
+ * points: b = 0 and a = lag[0] (callers put the centre anchor first); count = 0: all 0. */
+int hpfw_gpu_drift_fit(const int64_t *n, const int64_t *lag, int count, double *a, double *b, double *rms);
+/* Host only: the time map of a source whose sample n sits at t = A + (1 + B) n of the output's timeline: output m reads
+ * the source at (m - A) / (1 + B), and |i0 + m + (f0 + m d) 2^-40 - (m - A) / (1 + B)| <= 2^-40 + m 2^-41 samples.
+ * HPFW_E_INVALID: |1 / (1 + B) - 1| > 2^-10, |A| > 2^30. */
+int hpfw_gpu_time_map_q40(double A, double B, int64_t *i0, int64_t *f0, int64_t *d);
+/* pcm [n] int16 (n = frames x channels, interleaved) as a RIFF/WAVE file: a 44-byte header, PCM16, 44.1 kHz.  HPFW_E_IO
+ * when the file cannot be written; channels 1 or 2, n a multiple of channels and below 2^31 bytes. */
+int hpfw_gpu_wav_write_pcm16(const char *path, const int16_t *pcm, int64_t n, int channels);
+
 /* ---- filter learning: ParallelCollector::preprocess + calc_filters ------------------------
  * (parallel_collector.h:82-112, hashprint_handle.h:96-112).  The handle owns accum_cov
  * (2420 x 2420, parallel_collector.h:76): per clip, the covariance of its context frames (centred
