@@ -246,8 +246,8 @@ int q_split(hpfw_gpu *h, int n_shifts, int64_t n_clips, int64_t c, hpfw::QSplit 
     if (n_shifts || h->q_products != 6 || !h->projection) return 0;
     const int64_t tiles = hpfw::project_q_tiles(n_clips, c);
     if (tiles <= 0) return 0;
-    if (int rc = ensure(h->d_q_split, hpfw::project_q_split_bytes(tiles), h)) return rc;
-    *qs = {h->d_fq_thr.as<int32_t>(), h->d_q_split.get()};
+    if (int rc = ensure(h->d_q_split, hpfw::project_q_split_bytes(tiles, h->q_fixup_launch), h)) return rc;
+    *qs = {h->d_q_thr.as<int32_t>(), h->d_q_split.get(), h->q_fixup_launch ? h->d_fq32.as<int32_t>() : nullptr};
     *use = qs;
     return 0;
 }

@@ -23,6 +23,10 @@
 // 64 k', two steps ahead) -- nothing is exchanged between the waves in the main loop, so it has no barrier: the two
 // waves of a SIMD (two workgroups share a CU: 62 KB of LDS, 256 registers) interleave their matrix instructions freely,
 // and one workgroup's staging (loads, quantisation: vector ALU) and epilogue run under the other's products.
+//
+// The extraction's unshifted launches form only the six digit products of weight >= 2^16 (hashprint_q6_kernel) and settle
+// the few values whose sign those leave open in the same workgroup, from the digits still in its slab, before the
+// hashprints are stored: one launch, one pass over the spectrogram, hp written once (hashprint_q_tile, FUSED).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -51,10 +55,12 @@ constexpr int kQSteps = 2 * kCtx;                             // 40 steps of 64 
 constexpr int kQLdsBytes = kQSlabBytes + kQTileN * 4 * 2;     // + the waves' 16-bit parts of every hashprint: 62 464, two workgroups per CU
 constexpr float kQScale = 98304.0f;
 // six-product split: open values listed per tile of 128 hashprints, kQCap 16-bit entries (r << 7 | n - n0) each
-// (19 000 tiles of 1000 x 30 s clips: 4.9 MB of segments), kQRedo in place of a count above it
+// (in LDS; HPFW_Q_FIXUP=launch: in global segments, 4.9 MB for the 19 000 tiles of 1000 x 30 s clips), kQRedo in place of a
+// count above it
 constexpr int kQCap = 128;
 constexpr unsigned kQRedo = 0xffffffffu;
 constexpr int kQLdsBytes6 = kQLdsBytes + 16;                  // + the workgroup's count of open values
+constexpr int kQLdsBytes6f = kQLdsBytes6 + kQCap * 2;         // + its list of them (FUSED): 62 736, still two workgroups per CU
 
 // the three balanced base-256 digits of u as the three low bytes of one word (|u| < 2^23)
 __device__ __forceinline__ unsigned q_digit_bytes(int u) { return ((unsigned)u + 0x808080u) ^ 0x808080u; }
@@ -62,6 +68,47 @@ __device__ __forceinline__ unsigned q_digit_bytes(int u) { return ((unsigned)u +
 __device__ __forceinline__ int q_fixed(float s)
 {
     return (int)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(s, -80.0f), 0.0f) * kQScale);
+}
+
+// One wave forms D[r][n0 + nl] exactly from digits alone (r, nl the same in every lane).  The 2420 taps are 160 pairs of
+// 16-byte units, pair (s, g) = step s = 2 t + p of the matrix loop and its group g of 16 bins 64 p + 16 g + e:
+//   filter unit of digit i: the image's wave r >> 4, step s, lane (r & 15) + 16 g       (pack_filters_q's layout)
+//   slab unit of digit j:   chunk 4 p + g, column nl + t (<= 146), plane j               (the staging's layout)
+// both with zero bytes for bins >= 121.  A lane takes pairs lane, lane + 64 and, below lane 32, lane + 128; all its loads
+// are issued before the first product.  v_dot4c_i32_i8 products of weight 2^(8 (i + j)) share an int32 sum as in the
+// matrix loop (a lane's |sum| <= 3 * 3 * 16 * 128 * 128 < 2^22), D = sum_c acc_c 2^(8c) in int64, summed over the wave.
+__device__ __forceinline__ long long q_value_from_digits(const v4i *__restrict__ fq_image, const unsigned char *slab, int r, int nl, int lane)
+{
+    constexpr int kPairs = 4 * kQSteps; // 160
+    v4i fa[3][3], sb[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int pair = min(lane + 64 * k, kPairs - 1); // (k = 2 from lane 32 on: a valid address, the units zeroed below)
+        const int s = pair >> 2, g = pair & 3;
+        const v4i *fu = fq_image + ((size_t)(r >> 4) * kQSteps + s) * (kQStepBytes / 16) + (r & 15) + 16 * g;
+        const v4i *su = reinterpret_cast<const v4i *>(slab + (size_t)((4 * (s & 1) + g) * kQPitch + nl + (s >> 1)) * kQUnit);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            fa[k][d] = fu[d * 64];
+            sb[k][d] = su[d];
+        }
+    }
+    if (lane + 128 >= kPairs) sb[2][0] = sb[2][1] = sb[2][2] = v4i{0, 0, 0, 0};
+    int acc[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) acc[i + j] = __builtin_amdgcn_sdot4(fa[k][i][w], sb[k][j][w], acc[i + j], false);
+    long long v = acc[4];
+#pragma unroll
+    for (int cls = 3; cls >= 0; --cls) v = v * 256 + acc[cls];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
 }
 
 // FROM_T: sdb holds the dB terms t written by the chirp-z kernel; S = max(t - tmax[clip], -80) (convert.h:12-15)
@@ -76,20 +123,30 @@ __device__ __forceinline__ int q_fixed(float s)
 //   Dl = sum a0 b0 + 2^8 sum (a0 b1 + a1 b0)                                          (accumulators 0, 1)
 // and every |b| <= 128, so |Dl| <= 128 S0_r + 2^8 128 (S0_r + S1_r) = Lmax_r with S0_r, S1_r the sums of |a0| and |a1| over
 // row r's 2420 taps.  Where 2^16 |Dp| > Lmax_r the sign of D is the sign of Dp (and D != 0); a row with Lmax_r = 0 has
-// D = 2^16 Dp exactly.  Else the value is OPEN: the bit from Dp >= 0 stands for the moment and hashprint_q_fixup_kernel
-// recomputes D.  thr[r] = floor(Lmax_r / 2^16), or -1 for Lmax_r = 0: open iff |Dp| <= thr[r] (pack_filters_q).  The
-// workgroup writes counts[t] = its number of open values and, up to kQCap of them, their entries to seg[t][..]; above
-// that counts[t] = kQRedo.  A slab of zero digits (silence, the -80 dB floor) has D = 0 everywhere: all bits one, count 0.
-template <bool FROM_T, bool SHIFTED, int NP>
+// D = 2^16 Dp exactly.  Else the value is OPEN: the bit from Dp >= 0 stands for the moment and D is formed exactly.
+// thr[r] = floor(Lmax_r / 2^16), or -1 for Lmax_r = 0: open iff |Dp| <= thr[r] (pack_filters_q).  The workgroup writes
+// counts[t] = its number of open values, or kQRedo above kQCap; without FUSED (HPFW_Q_FIXUP=launch) also their entries,
+// up to kQCap, to seg[t][..] for hashprint_q_fixup_kernel.  A slab of zero digits (silence, the -80 dB floor) has D = 0
+// everywhere: all bits one, count 0.
+//
+// FUSED (NP = 6, the extraction's default): the workgroup settles its open values itself, before it packs.  The entries go
+// to a list in LDS; behind the barrier that ends the epilogue every wave takes each fourth entry, forms D from the digits
+// of the filter image and of the slab (q_value_from_digits) and flips the bit in `parts` where D >= 0 disagrees with it.
+// A workgroup with more than kQCap open values (near-stationary input) runs the nine-product body over its slab instead
+// (STAGED: the body entered behind the staging, the six-product accumulators dead by then).  hp is written once and final;
+// neither a second launch nor a second pass over the spectrogram follows.  counts[t] keeps its meaning.
+template <bool FROM_T, bool SHIFTED, int NP, bool FUSED = false, bool STAGED = false>
 __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
                                                  const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, uint64_t *__restrict__ hp,
                                                  long long *__restrict__ dbg, int n_images, const int *__restrict__ thr,
                                                  unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
 {
     static_assert(NP == 9 || (NP == 6 && !SHIFTED), "six products: the extraction's unshifted image only");
+    static_assert((!FUSED || NP == 6) && (!STAGED || (NP == 9 && !SHIFTED)), "FUSED: six products; STAGED: its nine-product redo");
     unsigned char *slab = smem_raw;                                   // [chunk][column (pitch 160)][digit][16]
     unsigned short *parts = reinterpret_cast<unsigned short *>(smem_raw + kQSlabBytes); // [hashprint][wave]
     unsigned *n_open = reinterpret_cast<unsigned *>(smem_raw + kQLdsBytes);             // (NP = 6)
+    unsigned short *list = reinterpret_cast<unsigned short *>(smem_raw + kQLdsBytes6);  // (FUSED) kQCap entries
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kg = lane >> 4, cl = lane & 15;  // this lane's group of 16 k' inside a step; its column (B) / filter (A) in a tile
     const int clip = t / n_tiles_x;
@@ -118,7 +175,7 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
     constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
     unsigned any_digit = 0; // (NP = 6) whether this thread stored a non-zero digit
 #pragma unroll 1
-    for (int r0 = 0; r0 < kUnits; r0 += 2) {
+    for (int r0 = STAGED ? kUnits : 0; r0 < kUnits; r0 += 2) { // (STAGED: the caller's slab stands, no trip)
         float va[2][16], vb[2][16];
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
@@ -181,7 +238,9 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
     }
     Q_STAMP(1);
     // the only barrier before the epilogue: the slab is read-only from here on
-    if (NP == 6) {
+    if (STAGED) {
+        // (the caller is behind this barrier and behind the one of its own epilogue)
+    } else if (NP == 6) {
         if (!__syncthreads_or((int)(any_digit != 0))) { // Du = 0 in the whole slab: D = 0, every bit one, nothing open
             if (tid < kQTileN && n0 + tid < nhp) hp[(int64_t)clip * nhp + n0 + tid] = ~0ull;
             if (tid == 0) counts[t] = 0;
@@ -286,7 +345,8 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
                 bits |= (unsigned)(v >= 0) << (15 - row);
                 if (NP == 6 && f < n_tiles && n < nhp && (v < 0 ? -v : v) <= (long long)th[reg]) {
                     const unsigned pos = atomicAdd(n_open, 1u);
-                    if (pos < (unsigned)kQCap) seg[(size_t)t * kQCap + pos] = (unsigned short)(((16 * wave + row) << 7) | (16 * f + cl));
+                    if (pos < (unsigned)kQCap)
+                        (FUSED ? list : seg + (size_t)t * kQCap)[pos] = (unsigned short)(((16 * wave + row) << 7) | (16 * f + cl));
                 }
 #if !defined(HPFW_Q_STAMPS)
                 if (!SHIFTED && dbg && f < n_tiles && n < nhp) dbg[((int64_t)clip * kFilters + 16 * wave + row) * nhp + n] = v;
@@ -299,6 +359,27 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
         }
         Q_STAMP(4);
         __syncthreads();
+        if (FUSED) {
+            const unsigned cnt = *n_open; // (the same for the whole workgroup; nothing adds to it behind the barrier)
+            if (cnt > (unsigned)kQCap) {
+                if (tid == 0) counts[t] = kQRedo;
+                hashprint_q_tile<FROM_T, false, 9, false, true>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr, nullptr);
+                return;
+            }
+            if (cnt > 0) {
+                for (unsigned e = (unsigned)__builtin_amdgcn_readfirstlane(wave); e < cnt; e += kQThreads / 64) {
+                    const int entry = __builtin_amdgcn_readfirstlane((int)list[e]);
+                    const int r = entry >> 7, nl = entry & 127;
+                    const long long d = q_value_from_digits(fq_images, slab, r, nl, lane);
+                    if (lane == 0) { // parts[nl * 4 + (r >> 4)], filter r at bit 15 - (r & 15) of it: two waves can meet in one word
+                        unsigned *w = reinterpret_cast<unsigned *>(parts) + nl * 2 + (r >> 5);
+                        const unsigned bit = 1u << (16 * ((r >> 4) & 1) + 15 - (r & 15));
+                        if (((*static_cast<volatile unsigned *>(w) & bit) != 0) != (d >= 0)) atomicXor(w, bit);
+                    }
+                }
+                __syncthreads();
+            }
+        }
         if (tid < kQTileN && n0 + tid < nhp) {
             const unsigned short *p = parts + tid * 4;
             hp[((int64_t)clip * (SHIFTED ? n_images : 1) + im) * nhp + n0 + tid] =
@@ -335,19 +416,33 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__
     hashprint_q_tile<FROM_T, SHIFTED, 9>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, dbg, n_images, nullptr, nullptr, nullptr);
 }
 
-// the six-product instantiation of the extraction's kernel (hashprint_q_tile): bits from Dp, the open values listed
+// the six-product instantiation of the extraction's kernel (hashprint_q_tile, FUSED): bits from Dp, the open values
+// settled from the slab before the hashprints are stored
 template <bool FROM_T>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
                                                                     const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
                                                                     uint64_t *__restrict__ hp, const int *__restrict__ thr,
-                                                                    unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
+                                                                    unsigned *__restrict__ counts)
+{
+    const unsigned t = q_tile_of_workgroup();
+    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
+    hashprint_q_tile<FROM_T, false, 6, true>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, nullptr);
+}
+
+// HPFW_Q_FIXUP=launch (kept to measure against): the six-product kernel that lists the open values in global segments for
+// hashprint_q_fixup_kernel
+template <bool FROM_T>
+__global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_listed_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
+                                                                           const float *__restrict__ tmax, int c, int nhp, int n_tiles_x,
+                                                                           int n_clips, uint64_t *__restrict__ hp, const int *__restrict__ thr,
+                                                                           unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
 {
     const unsigned t = q_tile_of_workgroup();
     if (t >= (unsigned)(n_tiles_x * n_clips)) return;
     hashprint_q_tile<FROM_T, false, 6>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, seg);
 }
 
-// The fix-up of a six-product launch, after it on the same stream: workgroups take the tiles in turn.  A tile with
+// The fix-up of a hashprint_q6_listed_kernel launch, after it on the same stream: workgroups take the tiles in turn.  A tile with
 // listed open values: one wave per entry (r, n) forms D[r][n] = sum_k fq[r][k] Du[k / 20][n + k % 20] exactly in int64
 // -- fq32 [64][2420], Du from the dB terms as the staging quantises them -- and flips bit 63 - r of hp[n] where D >= 0
 // disagrees with it.  A tile marked kQRedo: the nine-product body over the whole tile.
@@ -425,10 +520,10 @@ __global__ __launch_bounds__(256) void shift_filter_images_kernel(const unsigned
 
 // host: the filters' digits as the A operand of v_mfma_i32_16x16x64_i8, [wave][step s = 2 t + p][digit][lane][16 bytes]:
 // byte e of lane l = digit of fq[row = 16 wave + (l & 15)][k = 20 bin + t], bin = 64 p + 16 (l >> 4) + e (zero for bin >= 121)
-// fq_thr, when given: fq as int32 [64][2420] (k = 20 bin + t), then the 64 thresholds of the six-product split: floor(Lmax_r /
-// 2^16) with Lmax_r = 128 (S0_r + 256 (S0_r + S1_r)), S0_r and S1_r the sums of |digit 0| and |digit 1| of row r's taps,
-// or -1 where Lmax_r = 0 (hashprint_q_tile)
-void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int32_t> *fq_thr)
+// thr, when given: the 64 thresholds of the six-product split: floor(Lmax_r / 2^16) with Lmax_r = 128 (S0_r + 256 (S0_r +
+// S1_r)), S0_r and S1_r the sums of |digit 0| and |digit 1| of row r's taps, or -1 where Lmax_r = 0 (hashprint_q_tile).
+// fq32, when given (HPFW_Q_FIXUP=launch): fq as int32 [64][2420] (k = 20 bin + t)
+void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int32_t> *thr, std::vector<int32_t> *fq32)
 {
     std::vector<int32_t> fq((size_t)kFilters * kFrame);
     for (int r = 0; r < kFilters; ++r) {
@@ -437,8 +532,9 @@ void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int3
         const int e = m > 0.0f ? 21 - std::ilogb(m) : 0;
         for (int k = 0; k < kFrame; ++k) fq[(size_t)r * kFrame + k] = (int32_t)std::rint(std::ldexp(f[(size_t)k * kFilters + r], e));
     }
-    if (fq_thr) {
-        fq_thr->assign(fq.begin(), fq.end());
+    if (fq32) *fq32 = fq;
+    if (thr) {
+        thr->clear();
         for (int r = 0; r < kFilters; ++r) {
             int64_t s0 = 0, s1 = 0;
             for (int k = 0; k < kFrame; ++k) {
@@ -448,7 +544,7 @@ void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int3
                 s1 += std::abs(d1);
             }
             const int64_t lmax = 128 * (s0 + 256 * (s0 + s1)); // <= 128 * 128 * 2420 * 513 < 2^35
-            fq_thr->push_back(lmax > 0 ? (int32_t)(lmax >> 16) : -1);
+            thr->push_back(lmax > 0 ? (int32_t)(lmax >> 16) : -1);
         }
     }
     image.assign((size_t)4 * kQSteps * kQStepBytes, 0);
@@ -473,7 +569,7 @@ extern "C" void hpfw_gpu_debug_set_q_stamps(void *d) { g_q_stamps = static_cast<
 #endif
 
 size_t project_q_image_bytes() { return (size_t)4 * kQSteps * kQStepBytes; }
-size_t project_q_split_bytes(int64_t tiles) { return (size_t)tiles * (4 + (size_t)kQCap * 2); }
+size_t project_q_split_bytes(int64_t tiles, bool segments) { return (size_t)tiles * (4 + (segments ? (size_t)kQCap * 2 : 0)); }
 int64_t project_q_tiles(int64_t n_clips, int64_t c)
 {
     const int64_t nhp = c - (kCtx - 1) - kLag;
@@ -484,9 +580,10 @@ int64_t project_q_tiles(int64_t n_clips, int64_t c)
 // d_images: the unshifted one (n_shifts = 0), or n_shifts from launch_shift_filter_images.  One shift runs the image loop
 // too: 2.14 ms against 2.15 for the extraction's instance on 1000 x 30 s clips (profiles/transpose.json).  d_dbg: NULL,
 // or D [n_clips][64][c - 99] of the unshifted image (tests)
-// split (n_shifts = 0, no d_dbg; else NULL): the six-product kernel and its fix-up instead of the nine-product kernel.
-// d_fq_thr: the device copy of pack_filters_q's fq_thr; d_work: project_q_split_bytes(project_q_tiles(n_clips, c)) bytes,
-// counts [tiles] then segments [tiles][kQCap]
+// split (n_shifts = 0, no d_dbg; else NULL): the six-product kernel instead of the nine-product kernel.  d_thr: the device
+// copy of pack_filters_q's thresholds; d_work: project_q_split_bytes(project_q_tiles(n_clips, c), d_fq32 != NULL) bytes,
+// counts [tiles].  d_fq32 != NULL (HPFW_Q_FIXUP=launch): the listing kernel and the fix-up launch; d_work then holds the
+// segments [tiles][kQCap] behind the counts
 void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
                          long long *d_dbg, hipStream_t s, const QSplit *split)
 {
@@ -495,9 +592,11 @@ void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, 
         for (const void *k : {reinterpret_cast<const void *>(hashprint_q_kernel<true, false>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false>),
                               reinterpret_cast<const void *>(hashprint_q_kernel<true, true>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes);
-        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_kernel<false>),
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_listed_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_listed_kernel<false>),
                               reinterpret_cast<const void *>(hashprint_q_fixup_kernel<true>), reinterpret_cast<const void *>(hashprint_q_fixup_kernel<false>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6);
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_kernel<false>)})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6f);
         attr_set.mark();
     }
     const int nhp = c - (kCtx - 1) - kLag;
@@ -508,10 +607,15 @@ void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, 
     const int tiles = (nhp + kQTileN - 1) / kQTileN;
     const dim3 grid(8 * (unsigned)(((int64_t)tiles * n_clips + 7) / 8)); // one-dimensional, in XCD-aware order
     if (split && n_shifts == 0 && !d_dbg) {
-        const int *fq32 = split->d_fq_thr, *thr = fq32 + (size_t)kFilters * kFrame;
+        const int *fq32 = split->d_fq32, *thr = split->d_thr;
         unsigned *counts = static_cast<unsigned *>(split->d_work);
+        if (!fq32) {
+            hipLaunchKernelGGL(d_tmax ? hashprint_q6_kernel<true> : hashprint_q6_kernel<false>, grid, dim3(kQThreads), kQLdsBytes6f, s,
+                               static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, thr, counts);
+            return;
+        }
         unsigned short *seg = reinterpret_cast<unsigned short *>(counts + (size_t)tiles * n_clips);
-        hipLaunchKernelGGL(d_tmax ? hashprint_q6_kernel<true> : hashprint_q6_kernel<false>, grid, dim3(kQThreads), kQLdsBytes6, s,
+        hipLaunchKernelGGL(d_tmax ? hashprint_q6_listed_kernel<true> : hashprint_q6_listed_kernel<false>, grid, dim3(kQThreads), kQLdsBytes6, s,
                            static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, thr, counts, seg);
         // eight workgroups per CU share the tiles: few enough that none is launched for nothing, enough to hide the loads
         const unsigned fix = (unsigned)std::min<int64_t>((int64_t)tiles * n_clips, 2048);
