@@ -15,6 +15,11 @@ LIB_PATH = os.environ.get("HPFW_GPU_LIB") or os.path.join(_HERE, "lib", "libhpfw
 HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("offset", "<i4"), ("pad", "<u4")])
 # hpfw_shift_hit: a hit of the transposed search and the index of its shift in the caller's list (-1 = none)
 SHIFT_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("offset", "<i4"), ("shift_index", "<i4")])
+# hpfw_overlap_hit: a hit of the overlap search; padding: dist = clip = 0xffffffff, lag = overlap = 0
+OVERLAP_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("lag", "<i4"), ("overlap", "<u4")])
+# the lags of a (query, clip) pair are scanned in chunks of this many, the first at min_overlap - (the query's length; on the
+# matrix cores the longest of its group of 32) -- kOverlapChunk of csrc/kernels.h, for tests that plant matches on the seams
+OVERLAP_CHUNK = 1024
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
 # hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
 COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
@@ -85,6 +90,7 @@ EXPORTS = (
     "hpfw_gpu_timeline_tracker_create", "hpfw_gpu_timeline_tracker_destroy",
     "hpfw_gpu_timeline_tracker_push", "hpfw_gpu_timeline_tracker_pop", "hpfw_gpu_timeline_tracker_open",
     "hpfw_gpu_timeline_tracker_finish",
+    "hpfw_gpu_search_overlap_device", "hpfw_gpu_search_overlap",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -193,6 +199,8 @@ def lib():
     L.hpfw_gpu_search_topk_device.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.hpfw_gpu_search_topk.argtypes = [vp, vp, vp, i64, i32, vp]
     L.hpfw_gpu_merge_topk.argtypes = [vp, i32, i64, i32, vp]
+    L.hpfw_gpu_search_overlap_device.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp, vp]
+    L.hpfw_gpu_search_overlap.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp]
     L.hpfw_gpu_timer_start.argtypes = [vp, vp]
     L.hpfw_gpu_timer_stop.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.hpfw_gpu_stage_spectrogram.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -948,6 +956,33 @@ class Gpu:
         out = np.zeros((off.size - 1, k), HIT_DTYPE)
         check(lib().hpfw_gpu_search_topk(self._h, _hp(q), _hp(off), off.size - 1, int(k), _hp(out)))
         return out
+
+    # ---- overlap search: lags that overhang a clip's ends, rated per overlapping hashprint
+    @staticmethod
+    def _exclude(exclude, n_q):
+        if exclude is None:
+            return None
+        ex = np.ascontiguousarray(exclude, np.int32).ravel()
+        if ex.size != n_q:
+            raise ValueError("exclude must hold one clip index (or -1) per query")
+        return ex
+
+    def search_overlap(self, q_hp, q_off, k, min_overlap, exclude=None):
+        """OVERLAP_HIT_DTYPE [n_q][k] by the rule of include/hpfw_gpu.h; exclude: None or per query the clip (in add order)
+        to leave out, -1 for none"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        ex = self._exclude(exclude, off.size - 1)
+        out = np.zeros((off.size - 1, k), OVERLAP_HIT_DTYPE)
+        check(lib().hpfw_gpu_search_overlap(self._h, _hp(q), _hp(off), off.size - 1, None if ex is None else _hp(ex), int(min_overlap),
+                                            int(k), _hp(out)))
+        return out
+
+    def search_overlap_dev(self, d_q, q_off, k, min_overlap, d_out, exclude=None, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        ex = self._exclude(exclude, off.size - 1)
+        check(lib().hpfw_gpu_search_overlap_device(self._h, d_q, _hp(off), off.size - 1, None if ex is None else _hp(ex), int(min_overlap),
+                                                   int(k), d_out, stream))
 
     def search_votes(self, q_hp, q_off):
         """AnnStorage-style voting search with exact neighbours: VOTE_DTYPE [n_q]"""

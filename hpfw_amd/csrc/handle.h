@@ -146,6 +146,7 @@ struct hpfw_gpu {
         DevBuf d_gk; // longest query of each group of 32
         DevBuf d_topk_scratch;
         DevBuf d_shift_hits; // the per-shift top-k lists of a transposed search
+        DevBuf d_ov_tab, d_ov_exclude; // overlap search: the (query, clip, split) entries, the clips to skip
     } index;
     // filter learning (learn.hip)
     struct Learn {

@@ -384,6 +384,21 @@ void launch_topk(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t c
 size_t topk_scratch_bytes(int n_q, int k);
 void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_scratch,
                           void *d_out, hipStream_t s);
+// overlap search (k_search_overlap.hip): lags min_overlap - k .. n - min_overlap of every (query, clip),
+// rated by dist / overlap.  d_tab [n_q][n_clips][splits] of 16-byte entries {dist, overlap, lag, 0}, every byte preset to
+// 0xff; a clip's chunks of kOverlapChunk lags are dealt round robin to its `splits` workgroups.
+constexpr int kOverlapChunk = 1024;
+// the matrix-core scan: d_qa the image of launch_expand_queries, d_gk [group] the longest query of each group of 32,
+// k_max the longest query of the call (hamming_mfma_lds_bytes(k_max) <= 160 KB)
+void launch_overlap_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const int64_t *d_q_off, int n_q, const void *d_qa,
+                         int kt_pad, const int *d_gk, int k_max, int min_overlap, int splits, void *d_tab, hipStream_t s);
+// the same entries by xor/popcount, one workgroup per (query, clip, split)
+void launch_overlap_popc(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const uint64_t *d_q, const int64_t *d_q_off, int n_q,
+                         int min_overlap, int splits, void *d_tab, hipStream_t s);
+// folds the splits (in d_tab) and writes the k best clips of each query to d_out [n_q][k] (hpfw_overlap_hit);
+// d_exclude: NULL or [n_q] clips to skip (-1: none); n_clips == 0: padding records
+void launch_overlap_select(void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, int k, uint32_t clip_base, void *d_out,
+                           hipStream_t s);
 // per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
 // (dist, shift index), then the k best by (dist, clip)
 void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);

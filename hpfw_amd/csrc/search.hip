@@ -336,6 +336,126 @@ int hpfw_gpu_search_topk_transposed_scored(hpfw_gpu *h, const uint64_t *q_hp, co
     return search_topk_transposed_host(h, q_hp, q_off, n_q, n_shifts, k, out, stats);
 }
 
+// ---- overlap search (k_search_overlap.hip) ------------------------------------
+// what can be refused without the handle, before anything runs; *k_max: the longest query
+static int overlap_check(const void *h, const int64_t *q_off, int64_t n_q, const int32_t *exclude, int min_overlap, int k, const void *out,
+                         int64_t *k_max)
+{
+    if (!h || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    if (min_overlap < 1 || min_overlap > 16000) return fail(HPFW_E_INVALID, "min_overlap must be in 1..16000");
+    *k_max = 0;
+    for (int64_t i = 0; i < n_q; ++i) {
+        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        *k_max = std::max(*k_max, q_off[i + 1] - q_off[i]);
+    }
+    if (*k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    for (int64_t i = 0; exclude && i < n_q; ++i)
+        if (exclude[i] < -1) return fail(HPFW_E_INVALID, "exclude: an entry below -1 (query " + std::to_string(i) + ")");
+    return 0;
+}
+
+static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
+                                 int min_overlap, int k, hpfw_overlap_hit *d_out, hipStream_t s)
+{
+    int64_t k_max = 0;
+    if (int rc = overlap_check(h, q_off, n_q, exclude, min_overlap, k, d_out, &k_max)) return rc;
+    if (n_q > 0 && !d_q_hp) return fail(HPFW_E_INVALID, "null queries");
+    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+    for (int64_t i = 0; exclude && i < n_q; ++i)
+        if (exclude[i] >= n_clips) return fail(HPFW_E_INVALID, "exclude: an entry at or above the number of clips (query " + std::to_string(i) + ")");
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        int rc;
+        if (n_clips == 0) { // nothing indexed: every slot is "none"
+            for (int64_t g0 = 0; g0 < n_q; g0 += 1 << 20)
+                hpfw::launch_overlap_select(nullptr, (int)std::min<int64_t>(1 << 20, n_q - g0), 0, 1, nullptr, k, h->index.clip_base, d_out + g0 * k, s);
+            return check_launch("overlap_select");
+        }
+        if ((rc = upload_db_off(h, s))) return rc;
+        if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
+        if (exclude) {
+            if ((rc = ensure(h->index.d_ov_exclude, (size_t)n_q * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(h->index.d_ov_exclude.get(), exclude, (size_t)n_q * 4, hipMemcpyHostToDevice, s));
+        }
+        // The scan runs on the matrix cores unless the window does not fit the LDS (the bound of the plain search) or
+        // HPFW_OVERLAP_POPC asks for the xor/popcount kernel.
+        const bool mfma = !std::getenv("HPFW_OVERLAP_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024;
+        int64_t n_max = 0;
+        for (int64_t i = 0; i < n_clips; ++i) n_max = std::max(n_max, h->index.db_off[i + 1] - h->index.db_off[i]);
+        // A clip's lags come in chunks of 1024; with few (group, clip) pairs the chunks of a clip go to `splits` workgroups,
+        // each with an entry of its own (HPFW_OVERLAP_SPLITS: that many, for tests of either shape)
+        const int64_t chunks = std::max<int64_t>((n_max + k_max - 2 * min_overlap) / hpfw::kOverlapChunk + 1, 1);
+        const int64_t pairs = n_clips * (mfma ? (n_q + 31) / 32 : n_q);
+        int64_t splits = std::min<int64_t>({chunks, (2048 + pairs - 1) / pairs, 64});
+        if (const char *e = std::getenv("HPFW_OVERLAP_SPLITS")) splits = std::min<int64_t>(std::max(std::atoi(e), 1), 64);
+        // queries are processed in groups so the table stays below 1 GiB
+        int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 26) / (n_clips * splits) / 32 * 32);
+        qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
+        qgroup = std::min<int64_t>(qgroup, 65504); // the popcount kernel puts one query per gridDim.y
+        if ((int64_t)n_clips * splits > 0x7fffffff) return fail(HPFW_E_UNSUPPORTED, "overlap search: too many clips");
+        if ((rc = ensure(h->index.d_ov_tab, (size_t)qgroup * n_clips * splits * 16))) return rc;
+        const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
+        if (mfma) {
+            if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
+            if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 4))) return rc;
+        }
+        std::vector<int> gk;
+        for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
+            const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
+            HIP_TRY(hipMemsetAsync(h->index.d_ov_tab.get(), 0xff, (size_t)ng * n_clips * splits * 16, s));
+            const uint64_t *db = h->index.d_db.as<uint64_t>();
+            const int64_t *db_off = h->index.d_db_off.as<int64_t>(), *d_q_off = h->index.d_q_off.as<int64_t>() + g0;
+            if (mfma && k_max > 0) {
+                gk.assign((size_t)(ng + 31) / 32, 0);
+                for (int i = 0; i < ng; ++i) gk[(size_t)i / 32] = std::max(gk[(size_t)i / 32], (int)(q_off[g0 + i + 1] - q_off[g0 + i]));
+                HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_expand_queries(d_q_hp, d_q_off, ng, kt_pad, h->index.d_qa.get(), s);
+                hpfw::launch_overlap_mfma(db, db_off, (int)n_clips, d_q_off, ng, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)k_max,
+                                          min_overlap, (int)splits, h->index.d_ov_tab.get(), s);
+            } else if (k_max > 0) {
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_overlap_popc(db, db_off, (int)n_clips, d_q_hp, d_q_off, ng, min_overlap, (int)splits, h->index.d_ov_tab.get(), s);
+            }
+            if ((rc = check_launch("overlap scan"))) return rc;
+            {
+                Timed t(h, K_TOPK, s);
+                hpfw::launch_overlap_select(h->index.d_ov_tab.get(), ng, (int)n_clips, (int)splits,
+                                            exclude ? h->index.d_ov_exclude.as<int32_t>() + g0 : nullptr, k, h->index.clip_base, d_out + g0 * k, s);
+            }
+            if ((rc = check_launch("overlap_select"))) return rc;
+        }
+        if (exclude) HIP_TRY(hipStreamSynchronize(s)); // (the caller's array has been read)
+        return 0;
+    });
+}
+
+int hpfw_gpu_search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
+                                   int min_overlap, int k, hpfw_overlap_hit *d_out, void *stream)
+{
+    return search_overlap_device(h, d_q_hp, q_off, n_q, exclude, min_overlap, k, d_out, (hipStream_t)stream);
+}
+
+int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude, int min_overlap,
+                            int k, hpfw_overlap_hit *out)
+{
+    int64_t k_max = 0;
+    if (int rc = overlap_check(h, q_off, n_q, exclude, min_overlap, k, out, &k_max)) return rc;
+    if (n_q > 0 && q_off[n_q] > q_off[0] && !q_hp) return fail(HPFW_E_INVALID, "null queries");
+    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+    for (int64_t i = 0; exclude && i < n_q; ++i)
+        if (exclude[i] >= n_clips) return fail(HPFW_E_INVALID, "exclude: an entry at or above the number of clips (query " + std::to_string(i) + ")");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    return search_round_trip(q_hp, q_off, n_q, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_overlap_hit *d_out) {
+        return search_overlap_device(h, d_q, rel, n_q, exclude, min_overlap, k, d_out, nullptr);
+    });
+}
+
 // ---- AudioCombiner: exact-hash index + offset votes (k_combiner.hip) --------------------------------
 static hpfw::Combiner *combiner_of(hpfw_gpu *h)
 {

@@ -101,6 +101,26 @@ class LiveSongIdentification:
                                          for h in row if h["clip"] != 0xFFFFFFFF])
         return out
 
+    def top_overlap(self, filenames: Sequence[str], k: int, min_overlap: int):
+        """top() by the overlap search: the query may overhang either end of an indexed recording, and
+        clips are ordered by mismatching bits per overlapping hashprint over at least min_overlap hashprints (no default:
+        the caller decides).  Per query (label, [(distance, name, lag, overlap) x <= k]): query column 0 lies on column lag of
+        the recording (negative: the query begins before it does), overlap columns are compared.  None in place of the list
+        for a file that yields no hashprint.  An identifier made with devices= raises HPFW_E_UNSUPPORTED."""
+        if isinstance(self._gpu, _ShardedIndex):
+            raise _lib.HpfwError("the overlap search is not available on a sharded index", _lib.E_UNSUPPORTED)
+        hps = self.collector.calc_hashprints(list(filenames))
+        good = [i for i, (hp, _) in enumerate(hps) if hp is not None and hp.size]
+        out = [(f, None) for f in filenames]
+        if good and self.names:
+            off = np.zeros(len(good) + 1, np.int64)
+            np.cumsum([hps[i][0].size for i in good], out=off[1:])
+            hits = self._gpu.search_overlap(np.concatenate([hps[i][0] for i in good]), off, k, min_overlap)
+            for row, i in zip(hits, good):
+                out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["lag"]), int(h["overlap"]))
+                                         for h in row if h["clip"] != 0xFFFFFFFF])
+        return out
+
     def _top_transposed(self, filenames: List[str], k: int, shifts: List[int]):
         shifts = _lib.check_shifts(shifts)
         return self._top_sets(filenames, k, len(shifts), lambda g, x: g.extract_transposed(x, shifts)[0],

@@ -105,6 +105,30 @@ public:
         return out;
     }
 
+    /// the overlap search (hpfw_gpu_search_overlap): the query may overhang either end of a clip, and
+    /// clips are ordered by mismatching bits per overlapping hashprint over at least min_overlap hashprints (the caller's:
+    /// there is no default), then the larger overlap, then the position in the database.  Query position 0 lies on clip
+    /// position lag (negative: the query begins before the clip does).
+    struct OverlapResult {
+        std::string filename;
+        size_t cnt;     // mismatching bits over the overlap
+        int64_t lag;
+        size_t overlap; // hashprints compared
+    };
+    auto find_overlap(const typename Collector::Hashprint &hp, int k, int min_overlap) const -> std::vector<OverlapResult>
+    {
+        std::vector<OverlapResult> out;
+        if (hp.empty() || names_.empty()) return out;
+        const int64_t q_off[2] = {0, (int64_t)hp.size()};
+        std::vector<hpfw_overlap_hit> hits((size_t)k);
+        check(hpfw_gpu_search_overlap(h_, hp.data(), q_off, 1, nullptr, min_overlap, k, hits.data()));
+        for (const hpfw_overlap_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            out.push_back({names_[hit.clip], (size_t)hit.dist, (int64_t)hit.lag, (size_t)hit.overlap});
+        }
+        return out;
+    }
+
     /// find() for many queries in one scan of the database (same result per query as find();
     /// an empty hashprint yields the empty result of storage.h:28)
     auto find_batch(const std::vector<typename Collector::Hashprint> &hps) const -> std::vector<SearchResult>

@@ -436,6 +436,42 @@ int hpfw_gpu_knn_windows(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
  * -> out [n_q][k], ascending (dist, clip).  Host arrays. */
 int hpfw_gpu_merge_topk(const hpfw_hit *in, int n_shards, int64_t n_q, int k, hpfw_hit *out);
 
+/* ---- overlap search: the query may overhang either end of a clip, and alignments are rated per
+ * overlapping hashprint.  hpfw_gpu_search_topk slides the query inside the clip (offsets 0 .. n - k) and compares a clip
+ * shorter than the query over its own n hashprints at offset 0 (storage.h:37-39), which puts short clips on another scale
+ * and finds no window that begins before a clip does.  This search is a rule of its own beside it.
+ *
+ * Query q[0..k), 1 <= k <= 16000; clip r[0..n).  A lag d (signed) puts query position j on clip position d + j.
+ *   J(d) = { j : 0 <= j < k, 0 <= d + j < n },  L(d) = |J(d)| = min(k, n - d) - max(0, -d),
+ *   dist(d) = sum over j in J(d) of popcount(q[j] ^ r[d + j]).
+ * A lag is ADMISSIBLE when L(d) >= min_overlap.  min_overlap is the caller's, 1 <= min_overlap <= 16000, and has no
+ * default.  A clip with n < min_overlap or a query with k < min_overlap has no candidate.
+ * Candidates are ordered by (1) smaller dist / L as an exact rational -- dist1 L2 < dist2 L1, products below 2^34 --,
+ * (2) larger L, (3) smaller d.  A clip's candidate is its minimum in that order; the k <= 64 clips of a query are ordered
+ * by (1), (2), then the smaller clip id.  The order is computed in integers: no floating point takes part, and the result
+ * does not depend on how the work is scheduled.
+ * exclude: NULL, or [n_q] (host): per query the index, in add order (without clip_base), of a clip to leave out; -1 = none.
+ * With min_overlap = k and no clip shorter than the query the hits are hpfw_gpu_search_topk's (dist, clip, offset), with
+ * overlap = k.
+ * Refused before anything runs: null pointers, k outside 1..64, min_overlap outside 1..16000, decreasing q_off, an exclude
+ * entry below -1 or at or above the number of clips (HPFW_E_INVALID); a query above 16000 hashprints (HPFW_E_UNSUPPORTED).
+ * An empty index, a query without candidates and the slots past the last candidate give padding records.
+ * Environment (tests; the results are the same bytes): HPFW_OVERLAP_POPC -- the xor/popcount kernel for every query (it
+ * otherwise serves queries whose window does not fit the LDS); HPFW_OVERLAP_SPLITS=<1..64> -- workgroups per clip. */
+typedef struct {
+    uint32_t dist;    /* mismatching bits over the overlap                 */
+    uint32_t clip;    /* as hpfw_hit; 0xffffffff = none                    */
+    int32_t lag;      /* clip position of query position 0                 */
+    uint32_t overlap; /* L(lag)                                            */
+} hpfw_overlap_hit;
+/* padding: dist = clip = 0xffffffff, lag = overlap = 0 */
+/* d_q_hp, d_out [n_q][k] device; q_off, exclude host */
+int hpfw_gpu_search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                   const int32_t *exclude, int min_overlap, int k, hpfw_overlap_hit *d_out, void *stream);
+/* host convenience: copies queries in and hits out, synchronises */
+int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q,
+                            const int32_t *exclude, int min_overlap, int k, hpfw_overlap_hit *out);
+
 /* ---- events: time a region on `stream` with HIP events (bench.py uses these so that the
  * timing is taken on the stream the kernels run on) ---------------------------------------- */
 int hpfw_gpu_timer_start(hpfw_gpu *h, void *stream);
