@@ -28,6 +28,9 @@ ap.add_argument("--timeline", help="a long recording: print the indexed songs it
 ap.add_argument("--min-score", type=float, help="required with --timeline")
 ap.add_argument("--shifts", nargs="*", type=int, help="bin shifts to search as well (--timeline)")
 ap.add_argument("--tempos", nargs="*", type=float, help="tempo factors to search as well (--timeline)")
+ap.add_argument("--min-overlap", type=int, help="--timeline by the overlap rule over at least this many hashprints: song edges "
+                                                 "and indexed items shorter than a window (DESIGN.md section 18); not with "
+                                                 "--shifts, --tempos or --devices")
 ap.add_argument("--devices", nargs="*", type=int, help="shard the index over these devices, one ordinal per shard")
 args = ap.parse_args()
 
@@ -45,7 +48,7 @@ if args.timeline:
     if args.min_score is None:
         ap.error("--timeline needs --min-score")
     for start, end, name, score, offset, shift, tempo in liveid.timeline(args.timeline, args.min_score, shifts=args.shifts or None,
-                                                                         tempos=args.tempos or None):
+                                                                         tempos=args.tempos or None, min_overlap=args.min_overlap):
         print(f"{start:8.1f} s - {end:8.1f} s  {name}  score {score:.1f}  from {offset:.1f} s  shift {shift}  tempo {tempo:g}")
 ans = liveid.top(args.search, 10)
 for label, top in ans:

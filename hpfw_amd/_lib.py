@@ -91,6 +91,7 @@ EXPORTS = (
     "hpfw_gpu_timeline_tracker_push", "hpfw_gpu_timeline_tracker_pop", "hpfw_gpu_timeline_tracker_open",
     "hpfw_gpu_timeline_tracker_finish",
     "hpfw_gpu_search_overlap_device", "hpfw_gpu_search_overlap",
+    "hpfw_gpu_search_overlap_scored_device", "hpfw_gpu_search_overlap_scored", "hpfw_gpu_overlap_rate", "hpfw_gpu_overlap_extent",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -201,6 +202,10 @@ def lib():
     L.hpfw_gpu_merge_topk.argtypes = [vp, i32, i64, i32, vp]
     L.hpfw_gpu_search_overlap_device.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp, vp]
     L.hpfw_gpu_search_overlap.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp]
+    L.hpfw_gpu_search_overlap_scored_device.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp, vp, vp]
+    L.hpfw_gpu_search_overlap_scored.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp, vp]
+    L.hpfw_gpu_overlap_rate.argtypes = [u32, u32, ctypes.POINTER(u32)]
+    L.hpfw_gpu_overlap_extent.argtypes = [i32, i64, i64, i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.hpfw_gpu_timer_start.argtypes = [vp, vp]
     L.hpfw_gpu_timer_stop.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.hpfw_gpu_stage_spectrogram.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -390,6 +395,24 @@ def hit_score(dist, counted, stats):
     out = ctypes.c_double()
     check(lib().hpfw_gpu_hit_score(int(dist), int(bool(counted)), ctypes.byref(st), ctypes.byref(out)))
     return out.value
+
+
+OVERLAP_RATE_BITS = 10                                   # HPFW_OVERLAP_RATE_BITS
+
+
+def overlap_rate(dist, overlap):
+    """floor(dist 2^10 / overlap): the integer the scored overlap search takes its moments of (hpfw_gpu_overlap_rate)"""
+    out = ctypes.c_uint32()
+    check(lib().hpfw_gpu_overlap_rate(int(dist), int(overlap), ctypes.byref(out)))
+    return out.value
+
+
+def overlap_extent(lag, n_clip, k_q, span, win, m):
+    """(a, b): the samples [a, b) of a window of k_q hashprints that lie on the clip of n_clip hashprints it was found in at
+    lag `lag`; span: columns per hashprint (c - n_hp + 1 of the window's geometry), m: the geometry's m (hpfw_gpu_overlap_extent)"""
+    a, b = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().hpfw_gpu_overlap_extent(int(lag), int(n_clip), int(k_q), int(span), int(win), int(m), ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
 
 
 def timeline_segments(windows, min_score, hop_cols, win, hop, tol_cols=None, max_gap=1, min_windows=1):
@@ -983,6 +1006,24 @@ class Gpu:
         ex = self._exclude(exclude, off.size - 1)
         check(lib().hpfw_gpu_search_overlap_device(self._h, d_q, _hp(off), off.size - 1, None if ex is None else _hp(ex), int(min_overlap),
                                                    int(k), d_out, stream))
+
+    def search_overlap_scored(self, q_hp, q_off, k, min_overlap, exclude=None):
+        """(OVERLAP_HIT_DTYPE [n_q][k] as search_overlap, STATS_DTYPE [n_q]): the moments of overlap_rate(dist, overlap) over the
+        clips that have a candidate for the query, the excluded one left out"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        ex = self._exclude(exclude, off.size - 1)
+        out = np.zeros((off.size - 1, k), OVERLAP_HIT_DTYPE)
+        stats = np.zeros(off.size - 1, STATS_DTYPE)
+        check(lib().hpfw_gpu_search_overlap_scored(self._h, _hp(q), _hp(off), off.size - 1, None if ex is None else _hp(ex),
+                                                   int(min_overlap), int(k), _hp(out), _hp(stats)))
+        return out, stats
+
+    def search_overlap_scored_dev(self, d_q, q_off, k, min_overlap, d_out, d_stats, exclude=None, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        ex = self._exclude(exclude, off.size - 1)
+        check(lib().hpfw_gpu_search_overlap_scored_device(self._h, d_q, _hp(off), off.size - 1, None if ex is None else _hp(ex),
+                                                          int(min_overlap), int(k), d_out, d_stats, stream))
 
     def search_votes(self, q_hp, q_off):
         """AnnStorage-style voting search with exact neighbours: VOTE_DTYPE [n_q]"""

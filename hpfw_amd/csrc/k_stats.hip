@@ -1,4 +1,5 @@
-// k_stats.hip -- the scored search's second reader of the (query, clip) table.
+// k_stats.hip -- the scored searches' second readers of the (query, clip) tables: dist_stats_kernel for the plain search
+// (DESIGN.md section 13), overlap_stats_kernel for the overlap search (section 18, above its launch below).
 //
 // The scan leaves best[q][clip] = dist << 32 | offset; the top-k kernels pick the winners.  dist_stats_kernel reads the
 // same table once more and writes, per query row, the integer moments n, sum d, sum d^2 of the per-clip best distances
@@ -68,6 +69,60 @@ __global__ __launch_bounds__(kStThreads) void dist_stats_kernel(const uint64_t *
             atomicAdd(&stats[q].n, (uint32_t)n);
         }
     }
+}
+
+// The scored overlap search's second reader: the table of k_search_overlap.hip after
+// overlap_select_kernel has folded a clip's splits into its first entry {dist, L, lag, 0}.  Per query row the moments of
+// rate = floor(dist 2^10 / L) over the clips that have a candidate and are not the row's excluded clip.  dist <= 64 L and
+// L <= 16000: the numerator is below 2^30 (one 32-bit division), rate <= 2^16, and the sum of squares of fewer than 2^31
+// clips stays below 2^63 -- nothing can wrap.  Grid and reduction as dist_stats_kernel's.
+__global__ __launch_bounds__(kStThreads) void overlap_stats_kernel(const uint4 *__restrict__ tab, int n_clips, int splits,
+                                                                   const int32_t *__restrict__ exclude, int per,
+                                                                   DistStatsDev *__restrict__ stats)
+{
+    __shared__ unsigned long long red[3][kStThreads / 64];
+    const int tid = threadIdx.x, q = blockIdx.x;
+    const int c0 = blockIdx.y * per, c1 = min(n_clips, c0 + per);
+    const uint4 *row = tab + (int64_t)q * n_clips * splits;
+    const int ex = exclude ? exclude[q] : -1;
+    unsigned long long n = 0, sum = 0, sum_sq = 0;
+    for (int c = c0 + tid; c < c1; c += kStThreads) {
+        const uint4 e = row[(int64_t)c * splits];
+        if (e.x == 0xffffffffu || c == ex) continue; // no candidate (every byte still 0xff), or left out
+        const unsigned long long r = (e.x << kOverlapRateBits) / e.y;
+        n += 1;
+        sum += r;
+        sum_sq += r * r;
+    }
+    n = wave_sum_u64(n);
+    sum = wave_sum_u64(sum);
+    sum_sq = wave_sum_u64(sum_sq);
+    if ((tid & 63) == 0) {
+        red[0][tid >> 6] = n;
+        red[1][tid >> 6] = sum;
+        red[2][tid >> 6] = sum_sq;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kStThreads / 64; ++w) {
+            n += red[0][w];
+            sum += red[1][w];
+            sum_sq += red[2][w];
+        }
+        if (n) {
+            atomicAdd(&stats[q].sum, sum);
+            atomicAdd(&stats[q].sum_sq, sum_sq);
+            atomicAdd(&stats[q].n, (uint32_t)n);
+        }
+    }
+}
+
+void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, void *d_stats, hipStream_t s)
+{
+    const int slices = overlap_stats_slices(n_clips);
+    const int per = (n_clips + slices - 1) / slices;
+    hipLaunchKernelGGL(overlap_stats_kernel, dim3(n_q, slices), dim3(kStThreads), 0, s, static_cast<const uint4 *>(d_tab), n_clips, splits,
+                       d_exclude, per, static_cast<DistStatsDev *>(d_stats));
 }
 
 void launch_dist_stats(const uint64_t *d_best, const int64_t *d_db_off, const int64_t *d_q_off, int n_q, int n_clips, void *d_stats,

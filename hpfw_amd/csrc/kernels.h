@@ -399,6 +399,12 @@ void launch_overlap_popc(const uint64_t *d_db, const int64_t *d_db_off, int n_cl
 // d_exclude: NULL or [n_q] clips to skip (-1: none); n_clips == 0: padding records
 void launch_overlap_select(void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, int k, uint32_t clip_base, void *d_out,
                            hipStream_t s);
+// scored overlap search (k_stats.hip), after launch_overlap_select on the same d_tab: d_stats [n_q]
+// (hpfw_dist_stats, zeroed by the caller) += per query row the moments of floor(dist 2^kOverlapRateBits / overlap) over the
+// clips with a candidate but d_exclude's.  A row is cut into overlap_stats_slices(n_clips) workgroups.
+constexpr int kOverlapRateBits = HPFW_OVERLAP_RATE_BITS;
+inline int overlap_stats_slices(int n_clips) { return std::max(1, std::min(64, n_clips / 4096)); } // as launch_dist_stats cuts a row
+void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, void *d_stats, hipStream_t s);
 // per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
 // (dist, shift index), then the k best by (dist, clip)
 void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);

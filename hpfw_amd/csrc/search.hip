@@ -355,8 +355,9 @@ static int overlap_check(const void *h, const int64_t *q_off, int64_t n_q, const
     return 0;
 }
 
+// d_stats: NULL, or [n_q] rows that receive the moments of the per-clip rates (k_stats.hip: one more reader of the table)
 static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
-                                 int min_overlap, int k, hpfw_overlap_hit *d_out, hipStream_t s)
+                                 int min_overlap, int k, hpfw_overlap_hit *d_out, hpfw_dist_stats *d_stats, hipStream_t s)
 {
     int64_t k_max = 0;
     if (int rc = overlap_check(h, q_off, n_q, exclude, min_overlap, k, d_out, &k_max)) return rc;
@@ -368,6 +369,7 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
     return ordered_call(h, s, [&] {
         if (n_q == 0) return 0;
         int rc;
+        if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_q * sizeof(hpfw_dist_stats), s));
         if (n_clips == 0) { // nothing indexed: every slot is "none"
             for (int64_t g0 = 0; g0 < n_q; g0 += 1 << 20)
                 hpfw::launch_overlap_select(nullptr, (int)std::min<int64_t>(1 << 20, n_q - g0), 0, 1, nullptr, k, h->index.clip_base, d_out + g0 * k, s);
@@ -428,6 +430,12 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
                                             exclude ? h->index.d_ov_exclude.as<int32_t>() + g0 : nullptr, k, h->index.clip_base, d_out + g0 * k, s);
             }
             if ((rc = check_launch("overlap_select"))) return rc;
+            if (d_stats) { // (the select kernel has folded every clip's splits into its first entry)
+                Timed t(h, K_TOPK, s);
+                hpfw::launch_overlap_stats(h->index.d_ov_tab.get(), ng, (int)n_clips, (int)splits,
+                                           exclude ? h->index.d_ov_exclude.as<int32_t>() + g0 : nullptr, d_stats + g0, s);
+            }
+            if (d_stats && (rc = check_launch("overlap_stats"))) return rc;
         }
         if (exclude) HIP_TRY(hipStreamSynchronize(s)); // (the caller's array has been read)
         return 0;
@@ -437,11 +445,19 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
 int hpfw_gpu_search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
                                    int min_overlap, int k, hpfw_overlap_hit *d_out, void *stream)
 {
-    return search_overlap_device(h, d_q_hp, q_off, n_q, exclude, min_overlap, k, d_out, (hipStream_t)stream);
+    return search_overlap_device(h, d_q_hp, q_off, n_q, exclude, min_overlap, k, d_out, nullptr, (hipStream_t)stream);
 }
 
-int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude, int min_overlap,
-                            int k, hpfw_overlap_hit *out)
+int hpfw_gpu_search_overlap_scored_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
+                                          int min_overlap, int k, hpfw_overlap_hit *d_out, hpfw_dist_stats *d_stats, void *stream)
+{
+    if (!d_stats) return fail(HPFW_E_INVALID, "null stats");
+    return search_overlap_device(h, d_q_hp, q_off, n_q, exclude, min_overlap, k, d_out, d_stats, (hipStream_t)stream);
+}
+
+// host buffers: stats NULL (plain) or [n_q]
+static int search_overlap_host(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude, int min_overlap,
+                               int k, hpfw_overlap_hit *out, hpfw_dist_stats *stats)
 {
     int64_t k_max = 0;
     if (int rc = overlap_check(h, q_off, n_q, exclude, min_overlap, k, out, &k_max)) return rc;
@@ -451,9 +467,23 @@ int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_
         if (exclude[i] >= n_clips) return fail(HPFW_E_INVALID, "exclude: an entry at or above the number of clips (query " + std::to_string(i) + ")");
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
-    return search_round_trip(q_hp, q_off, n_q, n_q * k, out, [&](const uint64_t *d_q, const int64_t *rel, hpfw_overlap_hit *d_out) {
-        return search_overlap_device(h, d_q, rel, n_q, exclude, min_overlap, k, d_out, nullptr);
-    });
+    return search_round_trip_scored(q_hp, q_off, n_q, n_q * k, out, stats ? n_q : 0, stats,
+                                    [&](const uint64_t *d_q, const int64_t *rel, hpfw_overlap_hit *d_out, hpfw_dist_stats *d_stats) {
+                                        return search_overlap_device(h, d_q, rel, n_q, exclude, min_overlap, k, d_out, d_stats, nullptr);
+                                    });
+}
+
+int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude, int min_overlap,
+                            int k, hpfw_overlap_hit *out)
+{
+    return search_overlap_host(h, q_hp, q_off, n_q, exclude, min_overlap, k, out, nullptr);
+}
+
+int hpfw_gpu_search_overlap_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
+                                   int min_overlap, int k, hpfw_overlap_hit *out, hpfw_dist_stats *stats)
+{
+    if (!stats) return fail(HPFW_E_INVALID, "null stats");
+    return search_overlap_host(h, q_hp, q_off, n_q, exclude, min_overlap, k, out, stats);
 }
 
 // ---- AudioCombiner: exact-hash index + offset votes (k_combiner.hip) --------------------------------

@@ -2,6 +2,7 @@
 // score of a hit from its row's integer moments, the number of windows of a recording, and the segments of a list of
 // per-window hits, all at once or push by push.  No device, no handle: every binding calls these, so
 // the numbers are the same everywhere.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <deque>
@@ -114,6 +115,28 @@ int hpfw_gpu_hit_score(uint32_t dist, int counted, const hpfw_dist_stats *s, dou
     const __int128 mean_num = rest - np * (__int128)d; // n' (m - d)
     // (m - d) / sqrt(var) = (mean_num / n') / (sqrt(var_num) / n')
     *score = ((double)mean_num / (double)np) / (std::sqrt((double)var_num) / (double)np);
+    return 0;
+}
+
+int hpfw_gpu_overlap_rate(uint32_t dist, uint32_t overlap, uint32_t *rate)
+{
+    if (!rate) return fail(HPFW_E_INVALID, "null argument");
+    if (overlap == 0 || overlap > 16000) return fail(HPFW_E_INVALID, "overlap rate: overlap must be in 1..16000");
+    if (dist > 64 * overlap) return fail(HPFW_E_INVALID, "overlap rate: dist above 64 overlap");
+    *rate = (dist << HPFW_OVERLAP_RATE_BITS) / overlap; // below 2^30: the division the device does
+    return 0;
+}
+
+int hpfw_gpu_overlap_extent(int32_t lag, int64_t n_clip, int64_t k_q, int64_t span, int64_t win, int64_t m, int64_t *a, int64_t *b)
+{
+    if (!a || !b) return fail(HPFW_E_INVALID, "null argument");
+    if (n_clip < 1 || k_q < 1 || span < 1 || win < 1 || m < 1) return fail(HPFW_E_INVALID, "overlap extent: n_clip, k_q, span, win and m must be positive");
+    const int64_t d = lag;
+    if (std::min(k_q, n_clip - d) - std::max<int64_t>(0, -d) < 1) return fail(HPFW_E_INVALID, "overlap extent: the window and the clip share no hashprint at this lag");
+    const double col = 3.0 * (double)win / (double)m;
+    const int64_t a_cols = std::max<int64_t>(0, -d), b_cols = std::min(k_q + span - 1, n_clip + span - 1 - d);
+    *a = (int64_t)std::floor((double)a_cols * col + 0.5);
+    *b = std::min(win, (int64_t)std::floor((double)b_cols * col + 0.5));
     return 0;
 }
 

@@ -170,7 +170,8 @@ class LiveSongIdentification:
 
     def timeline(self, filename: str, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
                  shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
-                 tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, windows: bool = False):
+                 tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, windows: bool = False,
+                 min_overlap: Optional[int] = None):
         """the set list of one long recording: windows of window_s seconds every hop_s seconds, each
         searched for its best clip and scored by how far that clip stands out from the others (hpfw_gpu_hit_score);
         consecutive windows with score >= min_score that name the same clip at consistent offsets form a segment
@@ -178,8 +179,15 @@ class LiveSongIdentification:
         Returns [(start_s, end_s, name, score, offset_s, shift, tempo)]: the segment's extent in the recording, the score,
         shift and tempo of its best window, and where in the indexed recording its first window starts.  windows=True:
         (segments, [(clip index or None, name or None, distance, offset, score, shift, tempo) per window]).
-        An unreadable file or one shorter than a window gives []; every other failure raises."""
+        An unreadable file or one shorter than a window gives []; every other failure raises.
+        min_overlap=N: every window is searched by the overlap rule over at least N hashprints, so a
+        window that begins before a song does or runs past its end, and an indexed item shorter than the window, are found.
+        offset is then the lag (negative: the window begins before the clip does), the score is that of the hit's rate among
+        the rates of the other clips, start_s / end_s are trimmed to the part of the first and last window that lies on the
+        clip, offset_s is max(0, first lag) in seconds, and a window tuple carries the overlap as an eighth element.  Not
+        with shifts or tempos and not on an identifier made with devices= (HPFW_E_UNSUPPORTED)."""
         win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
+        self._check_min_overlap(min_overlap, shifts, tempos, win, hop)
         if shifts is not None:
             shifts = _lib.check_shifts(shifts)
         if tempos is not None:
@@ -202,16 +210,62 @@ class LiveSongIdentification:
             hp = self._gpu.extract_windows(extractor, x, win, hop, tempos, shifts)
         else:
             hp = extractor.extract_windows(x, win, hop, tempos, shifts)
-        rows, per_window = self._search_windows(hp, shifts, tempos)
+        rows, per_window = self._search_windows(hp, shifts, tempos, min_overlap)
         m = self._gpu.geometry(win).m
         segs = _lib.timeline_segments(rows, min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
-        out = [self._segment_tuple(sg, *per_window[int(sg["best_window"])][5:], 3.0 * win / m / 44100.0) for sg in segs]
+        out = [self._segment_tuple(sg, *per_window[int(sg["best_window"])][5:7], 3.0 * win / m / 44100.0,
+                                   None if min_overlap is None else
+                                   self._trim(sg, per_window[int(sg["first"])][3], per_window[int(sg["last"])][3], win, hop))
+               for sg in segs]
         return (out, per_window) if windows else out
 
-    def _search_windows(self, hp, shifts, tempos):
+    def _check_min_overlap(self, min_overlap, shifts, tempos, win, hop):
+        """what timeline() and streams() refuse of min_overlap, before anything runs on a device"""
+        if min_overlap is None:
+            return
+        if shifts is not None or tempos is not None:
+            raise _lib.HpfwError("min_overlap: the overlap rule has no shifts and no tempos", _lib.E_UNSUPPORTED)
+        if isinstance(self._gpu, _ShardedIndex):
+            raise _lib.HpfwError("the overlap search is not available on a sharded index", _lib.E_UNSUPPORTED)
+        _lib.window_count(0, win, hop)                     # (a bad window is refused as such)
+        n_hp = self._gpu.geometry(win).n_hp
+        if not 1 <= int(min_overlap) <= n_hp:
+            raise _lib.HpfwError(f"min_overlap must be in 1..{n_hp}, the hashprints of a window", _lib.E_INVALID)
+
+    def _search_windows_overlap(self, hp, min_overlap):
+        """_search_windows by the overlap rule: a window's record carries the lag as its offset, its
+        score is that of the hit's rate against the moments of the clips' rates, and its tuple ends with the overlap"""
+        n_w, k_q = hp.shape
+        hits, stats = self._gpu.search_overlap_scored(hp, np.arange(n_w + 1, dtype=np.int64) * k_q, 1, int(min_overlap))
+        rows = np.zeros(n_w, _lib.WINDOW_HIT_DTYPE)
+        per_window = []
+        for w in range(n_w):
+            h = hits[w, 0]
+            if h["clip"] == _lib.NO_CLIP:
+                rows[w] = (_lib.NO_CLIP, 0, 0, 0, 1.0, np.nan)
+                per_window.append((None, None, None, None, float("nan"), 0, 1.0, 0))
+                continue
+            clip, dist, lag, overlap = int(h["clip"]), int(h["dist"]), int(h["lag"]), int(h["overlap"])
+            score = _lib.hit_score(_lib.overlap_rate(dist, overlap), True, stats[w])
+            rows[w] = (clip, lag, 0, 0, 1.0, score)
+            per_window.append((clip, self.names[clip], dist, lag, score, 0, 1.0, overlap))
+        return rows, per_window
+
+    def _trim(self, sg, first_lag, last_lag, win, hop):
+        """(start, end, first lag) of a segment of windows searched by the overlap rule: the samples of its first and last
+        window that lie on the clip (hpfw_gpu_overlap_extent)"""
+        g = self._gpu.geometry(win)
+        n_clip = int(np.diff(self._gpu.index_offsets())[int(sg["clip"])])
+        a, _ = _lib.overlap_extent(first_lag, n_clip, g.n_hp, g.c - g.n_hp + 1, win, g.m)
+        _, b = _lib.overlap_extent(last_lag, n_clip, g.n_hp, g.c - g.n_hp + 1, win, g.m)
+        return int(sg["first"]) * hop + a, int(sg["last"]) * hop + b, int(first_lag)
+
+    def _search_windows(self, hp, shifts, tempos, min_overlap=None):
         """the scored search of the windows' hashprints hp [n_w][k_q] or, with variants, [n_w][n_sets][k_q] (shifts and tempos
         as checked): (WINDOW_HIT_DTYPE [n_w] for the segment rule, [(clip index or None, name or None, distance, offset, score,
-        shift, tempo) per window]).  timeline() and LiveStreams.push() share it."""
+        shift, tempo) per window]).  timeline() and LiveStreams.push() share it.  min_overlap: None, or the overlap rule."""
+        if min_overlap is not None:
+            return self._search_windows_overlap(hp, min_overlap)
         variants = shifts is not None or tempos is not None
         n_s = len(shifts) if shifts else 1
         n_sets = (len(tempos) if tempos else 1) * n_s
@@ -239,22 +293,25 @@ class LiveSongIdentification:
             per_window.append((clip, self.names[clip], int(h["dist"]), int(h["offset"]), score, shift, tempo))
         return rows, per_window
 
-    def _segment_tuple(self, sg, shift, tempo, col_s):
+    def _segment_tuple(self, sg, shift, tempo, col_s, trim=None):
         """a SEGMENT_DTYPE record as timeline() returns it; shift, tempo: those of its best window, col_s: one index column
-        in seconds"""
-        return (int(sg["start"]) / 44100.0, int(sg["end"]) / 44100.0, self.names[int(sg["clip"])], float(sg["best_score"]),
-                int(sg["first_offset"]) * col_s, shift, tempo)
+        in seconds; trim: None, or _trim() of a segment found by the overlap rule"""
+        start, end, first = (int(sg["start"]), int(sg["end"]), int(sg["first_offset"])) if trim is None else trim
+        if trim is not None:
+            first = max(first, 0)                          # a window that begins before the clip starts at the clip's start
+        return (start / 44100.0, end / 44100.0, self.names[int(sg["clip"])], float(sg["best_score"]), first * col_s, shift, tempo)
 
     def streams(self, n_streams: int, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
                 shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
                 tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, capacity_s: Optional[float] = None,
-                windows: bool = False, rate=44100):
+                windows: bool = False, rate=44100, min_overlap: Optional[int] = None):
         """the timelines of n_streams live feeds as their samples arrive (hpfw_amd.streams.LiveStreams):
         per feed exactly what timeline() gives for a file that holds everything pushed to it.  Feeds are mono PCM16.  rate: the
         feeds' sample rate, one int for all or one per feed; another rate than 44 100 Hz is taken only by an identifier made with
         resample=True, as files at other rates are (HPFW_E_UNSUPPORTED otherwise), and is converted chunk by chunk on the GPU:
         the feed then yields what timeline() gives for a file at that rate, once H zero samples have been pushed behind its end
-        (LiveStreams.tail).  capacity_s: seconds of audio a feed's ring holds (None: two windows)."""
+        (LiveStreams.tail).  capacity_s: seconds of audio a feed's ring holds (None: two windows).  min_overlap: as timeline()'s,
+        with its refusals."""
         from .streams import LiveStreams
         rates = [int(rate)] * int(n_streams) if np.ndim(rate) == 0 else [int(r) for r in rate]
         other = [r for r in rates if r != 44100]
@@ -262,7 +319,7 @@ class LiveSongIdentification:
             raise _lib.HpfwError(f"live feeds are 44.1 kHz mono PCM16: a feed at {other[0]} Hz has to be converted before it is pushed",
                                  _lib.E_UNSUPPORTED)
         return LiveStreams(self, n_streams, min_score, window_s, hop_s, shifts, tempos, tol_cols, max_gap, min_windows, capacity_s,
-                           windows, rates if other else None)
+                           windows, rates if other else None, min_overlap)
 
     def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None,
                tempos: Optional[Sequence[float]] = None):

@@ -19,9 +19,12 @@ from . import _lib
 
 class LiveStreams:
     def __init__(self, lsi, n_streams, min_score, window_s=5.0, hop_s=2.5, shifts=None, tempos=None, tol_cols=None, max_gap=1,
-                 min_windows=1, capacity_s=None, windows=False, rates=None):
+                 min_windows=1, capacity_s=None, windows=False, rates=None, min_overlap=None):
         self._lsi = lsi
         win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
+        lsi._check_min_overlap(min_overlap, shifts, tempos, win, hop)
+        self._min_overlap = min_overlap
+        self._lags = [{} for _ in range(n_streams)]       # overlap rule: per feed {window: lag} from the open segment's first on
         self._shifts = None if shifts is None else _lib.check_shifts(shifts)
         self._tempos = None if tempos is None else _lib.check_tempos(tempos, 0 if shifts is None else len(self._shifts))
         self._windows = bool(windows)
@@ -63,8 +66,19 @@ class LiveStreams:
         j, i = divmod(max(int(v), 0), n_s)                # variant v = j max(S, 1) + i
         return (self._shifts[i] if self._shifts else 0), (self._tempos[j] if self._tempos else 1.0)
 
-    def _tuple(self, sg):
-        return self._lsi._segment_tuple(sg, *self._variant(sg["best_variant"]), self._col_s)
+    def _tuple(self, sg, feed):
+        trim = None
+        if self._min_overlap is not None:                 # the extent of the first and last window on the clip
+            lags = self._lags[feed]
+            trim = self._lsi._trim(sg, lags[int(sg["first"])], lags[int(sg["last"])], self.win, self.hop)
+        return self._lsi._segment_tuple(sg, *self._variant(sg["best_variant"]), self._col_s, trim)
+
+    def _forget(self, feed, upto):
+        """drops the lags no segment can ask for any more: those before the open segment, or all up to window `upto`"""
+        cur = self._trackers[feed].open()
+        keep = upto + 1 if cur is None else int(cur["first"])
+        for w in [w for w in self._lags[feed] if w < keep]:
+            del self._lags[feed][w]
 
     def push(self, chunks):
         """chunks: a list with one int16 array or None per feed (at the feed's rate), or {feed: array}.  Appends them, hashes and searches every
@@ -78,25 +92,31 @@ class LiveStreams:
         segments, wins = [], []
         if self._gs.push(chunks):
             which, hp = self._gs.extract()
-            rows, per_window = self._lsi._search_windows(hp, self._shifts, self._tempos)
+            rows, per_window = self._lsi._search_windows(hp, self._shifts, self._tempos, self._min_overlap)
             wins = [(int(w["feed"]), int(w["window"]), row) for w, row in zip(which, per_window)]
+            if self._min_overlap is not None:
+                for f, w, row in wins:
+                    self._lags[f][w] = row[3]
             for feed in np.unique(which["feed"]):         # (ascending; a feed's windows are in order)
                 t = self._trackers[int(feed)]
                 t.push(rows[which["feed"] == feed])
-                segments += [(int(feed), self._tuple(sg)) for sg in t.pop()]
+                segments += [(int(feed), self._tuple(sg, int(feed))) for sg in t.pop()]
+                if self._min_overlap is not None:
+                    self._forget(int(feed), int(which["window"][which["feed"] == feed].max()))
         return (segments, wins) if self._windows else segments
 
     def open(self):
         """per feed the segment in progress as it would close now, whatever min_windows, or None"""
         cur = [t.open() for t in self._trackers]
-        return [None if sg is None else self._tuple(sg) for sg in cur]
+        return [None if sg is None else self._tuple(sg, f) for f, sg in enumerate(cur)]
 
     def finish(self, feed=None):
         """closes the segment in progress of one feed, or of every feed, and returns [(feed, segment)] it released"""
         out = []
         for f in (range(self.n_streams) if feed is None else [int(feed)]):
             self._trackers[f].finish()
-            out += [(f, self._tuple(sg)) for sg in self._trackers[f].pop()]
+            out += [(f, self._tuple(sg, f)) for sg in self._trackers[f].pop()]
+            self._lags[f].clear()
         return out
 
     def reset(self, feed):
@@ -104,3 +124,4 @@ class LiveStreams:
         self._gs.reset(feed)
         self._trackers[int(feed)].close()
         self._trackers[int(feed)] = _lib.TimelineTracker(*self._tracker_args)
+        self._lags[int(feed)].clear()

@@ -129,6 +129,35 @@ public:
         return out;
     }
 
+    /// find_overlap() with scores (hpfw_gpu_search_overlap_scored): the same hits, and per hit how far
+    /// its rate (mismatching bits per overlapping hashprint, in units of 2^-10) stands out from the rates of the other clips
+    /// that have a candidate: (their mean - the rate) / their standard deviation (hpfw_gpu_hit_score; NaN below three clips)
+    struct ScoredOverlapResult {
+        std::string filename;
+        size_t cnt;
+        int64_t lag;
+        size_t overlap;
+        double score;
+    };
+    auto find_overlap_scored(const typename Collector::Hashprint &hp, int k, int min_overlap) const -> std::vector<ScoredOverlapResult>
+    {
+        std::vector<ScoredOverlapResult> out;
+        if (hp.empty() || names_.empty()) return out;
+        const int64_t q_off[2] = {0, (int64_t)hp.size()};
+        std::vector<hpfw_overlap_hit> hits((size_t)k);
+        hpfw_dist_stats stats{};
+        check(hpfw_gpu_search_overlap_scored(h_, hp.data(), q_off, 1, nullptr, min_overlap, k, hits.data(), &stats));
+        for (const hpfw_overlap_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            uint32_t rate = 0;
+            double score = 0;
+            check(hpfw_gpu_overlap_rate(hit.dist, hit.overlap, &rate));
+            check(hpfw_gpu_hit_score(rate, 1, &stats, &score));
+            out.push_back({names_[hit.clip], (size_t)hit.dist, (int64_t)hit.lag, (size_t)hit.overlap, score});
+        }
+        return out;
+    }
+
     /// find() for many queries in one scan of the database (same result per query as find();
     /// an empty hashprint yields the empty result of storage.h:28)
     auto find_batch(const std::vector<typename Collector::Hashprint> &hps) const -> std::vector<SearchResult>

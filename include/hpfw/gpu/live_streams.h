@@ -7,6 +7,7 @@
 // holds everything pushed to the feed, however the samples were cut into chunks.
 #pragma once
 
+#include <map>
 #include <memory>
 #include <optional>
 
@@ -50,14 +51,17 @@ public:
         if ((int)rates.size() != n_streams) throw std::runtime_error("hpfw::LiveStreams: one rate per feed");
         for (int32_t r : rates)
             if (r != 44100 && !opt.resample) throw std::runtime_error("hpfw::LiveStreams: feeds are 44.1 kHz mono PCM16");
+        constexpr bool sharded = requires { storage.group(); };
+        if (hpfw_gpu_geometry(h, opt.win, &g_) != 0) fail("geometry");
+        detail::check_min_overlap(opt, sharded, g_.n_hp);
+        lags_.resize((size_t)std::max(n_streams, 0));
         hpfw_streams_params p{n_streams, (int32_t)opt.tempos.size(), (int32_t)opt.shifts.size(), 0, opt.win, opt.hop, opt.capacity,
                               opt.tempos.empty() ? nullptr : opt.tempos.data(), opt.shifts.empty() ? nullptr : opt.shifts.data()};
         hpfw_gpu_streams *s = nullptr;
         if (hpfw_gpu_streams_create_rates(h, &p, rates.empty() ? nullptr : rates.data(), &s) != 0) fail("create");
         s_.reset(s);
         if (hpfw_gpu_streams_info(s, &info_, nullptr, nullptr) != 0) fail("info");
-        hpfw_geometry g;
-        if (hpfw_gpu_geometry(h, opt.win, &g) != 0) fail("geometry");
+        const hpfw_geometry &g = g_;
         col_s_ = 3.0 * (double)opt.win / (double)g.m / 44100.0; // one index column in seconds
         tp_ = {opt.min_score, (double)opt.hop * (double)g.m / (3.0 * (double)opt.win), opt.tol_cols, opt.win, opt.hop, opt.max_gap, opt.min_windows};
         for (int i = 0; i < n_streams; ++i) trackers_.emplace_back(tracker());
@@ -87,12 +91,15 @@ public:
         std::vector<hpfw_stream_window> which((size_t)ready);
         int64_t n_w = 0;
         if (hpfw_gpu_streams_extract_host(s_.get(), ready, hp.data(), nullptr, which.data(), &n_w) != 0) fail("extraction");
+        constexpr bool sharded = requires { storage_.group(); };
+        if constexpr (!sharded) {
+            if (opt_.min_overlap > 0) return push_overlap(hp, which, n_w, nhp);
+        }
         std::vector<int64_t> q_off((size_t)(n_w * sets) + 1);
         for (size_t i = 0; i < q_off.size(); ++i) q_off[i] = (int64_t)i * nhp;
         std::vector<hpfw_dist_stats> stats((size_t)(n_w * sets));
         std::vector<hpfw_shift_hit> hits((size_t)n_w);
         std::vector<hpfw_hit> plain(variants ? 0 : (size_t)n_w);
-        constexpr bool sharded = requires { storage_.group(); };
         int rc;
         if constexpr (sharded)
             rc = variants ? hpfw_gpu_group_search_topk_transposed_scored(storage_.group(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
@@ -132,7 +139,7 @@ public:
         int has = 0;
         if (feed < 0 || feed >= info_.n_streams || hpfw_gpu_timeline_tracker_open(trackers_[(size_t)feed].get(), &cur, &has) != 0) fail("open");
         if (!has) return std::nullopt;
-        return named(cur);
+        return named(cur, feed);
     }
 
     /// closes the segment in progress of one feed, or of every feed (-1), and returns what that released
@@ -143,6 +150,7 @@ public:
             if (feed >= 0 && i != feed) continue;
             if (hpfw_gpu_timeline_tracker_finish(trackers_[(size_t)i].get()) != 0) fail("finish");
             pop(i, out);
+            lags_[(size_t)i].clear();
         }
         return out;
     }
@@ -152,6 +160,7 @@ public:
     {
         if (hpfw_gpu_streams_reset(s_.get(), feed) != 0) fail("reset");
         trackers_[(size_t)feed].reset(tracker());
+        lags_[(size_t)feed].clear();
     }
 
     const std::vector<LiveWindow> &windows() const { return windows_; }
@@ -167,11 +176,46 @@ private:
         return t;
     }
 
-    TimelineSegment named(const hpfw_segment &s) const
+    TimelineSegment named(const hpfw_segment &s, int feed) const
     {
         const int n_s = (int)std::max<size_t>(opt_.shifts.size(), 1);
-        return {storage_.names()[s.clip], s.clip, (double)s.start / 44100.0, (double)s.end / 44100.0, s.best_score, s.first_offset * col_s_,
-                opt_.shifts.empty() ? 0 : opt_.shifts[(size_t)(s.best_variant % n_s)], (float)s.best_tempo, s};
+        TimelineSegment seg{storage_.names()[s.clip], s.clip, (double)s.start / 44100.0, (double)s.end / 44100.0, s.best_score, s.first_offset * col_s_,
+                            opt_.shifts.empty() ? 0 : opt_.shifts[(size_t)(s.best_variant % n_s)], (float)s.best_tempo, s};
+        if constexpr (!requires { storage_.group(); }) {
+            if (opt_.min_overlap > 0) { // the part of the first and last window that lies on the clip
+                const auto &lags = lags_[(size_t)feed];
+                std::vector<int64_t> db_off(storage_.names().size() + 1, 0);
+                if (hpfw_gpu_index_get(storage_.handle(), db_off.data(), nullptr, 0) != 0) fail("index");
+                if (detail::trim_segment(seg, lags.at(s.first), lags.at(s.last), db_off[s.clip + 1] - db_off[s.clip], g_, opt_.win, opt_.hop) != 0)
+                    fail("extent");
+            }
+        }
+        return seg;
+    }
+
+    /// push() by the overlap rule (opt.min_overlap > 0): the lag of every window is kept, from the first window of the feed's
+    /// segment in progress on, for the extent of the segment that window may open or close
+    std::vector<LiveSegment> push_overlap(const std::vector<uint64_t> &hp, const std::vector<hpfw_stream_window> &which, int64_t n_w, int64_t nhp)
+    {
+        std::vector<hpfw_window_hit> x((size_t)n_w);
+        std::vector<uint32_t> overlaps((size_t)n_w);
+        if (detail::search_windows_overlap(storage_.handle(), hp.data(), n_w, nhp, opt_.min_overlap, x.data(), overlaps.data()) != 0) fail("search");
+        std::vector<LiveSegment> out;
+        for (int64_t w = 0; w < n_w; ++w) {
+            const int feed = which[(size_t)w].feed;
+            lags_[(size_t)feed][which[(size_t)w].window] = x[(size_t)w].offset;
+            if (opt_.keep_windows) windows_.push_back({feed, which[(size_t)w].window, x[(size_t)w]});
+            if (hpfw_gpu_timeline_tracker_push(trackers_[(size_t)feed].get(), &x[(size_t)w], 1) != 0) fail("tracker");
+            if (w + 1 == n_w || which[(size_t)w + 1].feed != feed) {
+                pop(feed, out);
+                hpfw_segment cur;
+                int has = 0;
+                if (hpfw_gpu_timeline_tracker_open(trackers_[(size_t)feed].get(), &cur, &has) != 0) fail("open");
+                auto &lags = lags_[(size_t)feed];
+                lags.erase(lags.begin(), has ? lags.lower_bound(cur.first) : lags.end());
+            }
+        }
+        return out;
     }
 
     void pop(int feed, std::vector<LiveSegment> &out)
@@ -179,7 +223,7 @@ private:
         hpfw_segment seg[8];
         for (int64_t n = 8; n == 8;) {
             if (hpfw_gpu_timeline_tracker_pop(trackers_[(size_t)feed].get(), seg, 8, &n) != 0) fail("pop");
-            for (int64_t i = 0; i < n; ++i) out.push_back({feed, named(seg[i])});
+            for (int64_t i = 0; i < n; ++i) out.push_back({feed, named(seg[i], feed)});
         }
     }
 
@@ -193,6 +237,8 @@ private:
     std::vector<std::unique_ptr<hpfw_timeline_tracker, Destroy>> trackers_;
     hpfw_streams_info info_{};
     hpfw_timeline_params tp_{};
+    hpfw_geometry g_{};
+    std::vector<std::map<int64_t, int32_t>> lags_; // min_overlap: per feed, window -> lag
     double col_s_ = 0;
     std::vector<int16_t> pcm_;
     std::vector<LiveWindow> windows_;

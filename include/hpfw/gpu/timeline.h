@@ -28,6 +28,8 @@ struct TimelineOptions {
     std::vector<int32_t> shifts;   ///< empty: the recording's own key only
     double tol_cols = 0;           ///< 0: the default max(2, 0.08 hop in columns)
     int max_gap = 1, min_windows = 1;
+    int min_overlap = 0;           ///< 0: the plain rule.  N > 0: every window is searched by the overlap rule over at least N
+                                   ///< hashprints; no tempos, no shifts, no sharded storage then
 };
 
 struct TimelineSegment {
@@ -42,9 +44,58 @@ struct TimelineSegment {
 };
 
 struct Timeline {
-    std::vector<hpfw_window_hit> windows; ///< the best hit of every window
+    std::vector<hpfw_window_hit> windows; ///< the best hit of every window (min_overlap: offset is the lag)
+    std::vector<uint32_t> overlaps;       ///< min_overlap: the hashprints every window's hit was compared over; empty otherwise
     std::vector<TimelineSegment> segments;
 };
+
+namespace detail {
+/// what min_overlap > 0 refuses, before anything runs on a device; nhp: the hashprints of a window
+inline void check_min_overlap(const TimelineOptions &opt, bool sharded, int64_t nhp)
+{
+    if (opt.min_overlap == 0) return;
+    if (!opt.tempos.empty() || !opt.shifts.empty()) throw std::runtime_error("hpfw: min_overlap: the overlap rule has no shifts and no tempos (HPFW_E_UNSUPPORTED)");
+    if (sharded) throw std::runtime_error("hpfw: min_overlap: the overlap search is not available on a sharded index (HPFW_E_UNSUPPORTED)");
+    if (opt.min_overlap < 1 || opt.min_overlap > nhp) throw std::runtime_error("hpfw: min_overlap must be in 1.." + std::to_string(nhp) + ", the hashprints of a window (HPFW_E_INVALID)");
+}
+
+/// the best hit of n_w windows of nhp hashprints each by the overlap rule, scored by its rate among the rates of the
+/// counted clips: x.offset is the lag; 0 on success (the library's status otherwise)
+inline int search_windows_overlap(hpfw_gpu *index, const uint64_t *hp, int64_t n_w, int64_t nhp, int min_overlap, hpfw_window_hit *x,
+                                  uint32_t *overlaps)
+{
+    std::vector<int64_t> q_off((size_t)n_w + 1);
+    for (size_t i = 0; i < q_off.size(); ++i) q_off[i] = (int64_t)i * nhp;
+    std::vector<hpfw_overlap_hit> hits((size_t)n_w);
+    std::vector<hpfw_dist_stats> stats((size_t)n_w);
+    if (int rc = hpfw_gpu_search_overlap_scored(index, hp, q_off.data(), n_w, nullptr, min_overlap, 1, hits.data(), stats.data())) return rc;
+    for (int64_t w = 0; w < n_w; ++w) {
+        const hpfw_overlap_hit &hit = hits[(size_t)w];
+        x[w] = {hit.clip, hit.lag, 0, 0, 1.0, std::numeric_limits<double>::quiet_NaN()};
+        overlaps[w] = hit.overlap;
+        if (hit.clip == 0xffffffffu) continue;
+        uint32_t rate = 0;
+        if (int rc = hpfw_gpu_overlap_rate(hit.dist, hit.overlap, &rate)) return rc;
+        if (int rc = hpfw_gpu_hit_score(rate, 1, &stats[(size_t)w], &x[w].score)) return rc;
+    }
+    return 0;
+}
+
+/// start_s, end_s and offset_s of a segment found by the overlap rule: the part of its first and last window that lies on
+/// the clip of n_clip hashprints (hpfw_gpu_overlap_extent); g: the window's geometry
+template <typename Segment>
+int trim_segment(Segment &seg, int32_t first_lag, int32_t last_lag, int64_t n_clip, const hpfw_geometry &g, int64_t win, int64_t hop)
+{
+    int64_t a = 0, b = 0, unused = 0;
+    const int64_t span = g.c - g.n_hp + 1;
+    if (int rc = hpfw_gpu_overlap_extent(first_lag, n_clip, g.n_hp, span, win, g.m, &a, &unused)) return rc;
+    if (int rc = hpfw_gpu_overlap_extent(last_lag, n_clip, g.n_hp, span, win, g.m, &unused, &b)) return rc;
+    seg.start_s = (double)(seg.raw.first * hop + a) / 44100.0;
+    seg.end_s = (double)(seg.raw.last * hop + b) / 44100.0;
+    seg.offset_s = (double)std::max(first_lag, 0) * (3.0 * (double)win / (double)g.m / 44100.0);
+    return 0;
+}
+} // namespace detail
 
 /// `path`: a 44.1 kHz PCM16 WAV file (hpfw_gpu_wav_read_pcm16).  A recording shorter than one window has no window and no
 /// segment; throws std::runtime_error with the library's message on failure.
@@ -55,14 +106,15 @@ Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, 
     constexpr bool sharded = requires { storage.group(); };
     int64_t n = 0, n_w = 0;
     if (hpfw_gpu_window_count(0, opt.win, opt.hop, &n_w) != 0) fail("windows");
+    hpfw_geometry g;
+    if (hpfw_gpu_geometry(h, opt.win, &g) != 0) fail("geometry");
+    detail::check_min_overlap(opt, sharded, g.n_hp);
     if (hpfw_gpu_wav_read_pcm16(path.c_str(), nullptr, 0, &n) != 0) fail(path.c_str());
     std::vector<int16_t> pcm((size_t)std::max<int64_t>(n, 1));
     if (hpfw_gpu_wav_read_pcm16(path.c_str(), pcm.data(), n, &n) != 0) fail(path.c_str());
     if (hpfw_gpu_window_count(n, opt.win, opt.hop, &n_w) != 0) fail("windows");
     Timeline out;
     if (n_w == 0) return out;
-    hpfw_geometry g;
-    if (hpfw_gpu_geometry(h, opt.win, &g) != 0) fail("geometry");
     int64_t nhp = g.n_hp;
     if (!opt.tempos.empty()) {
         int64_t ct = 0;
@@ -86,6 +138,30 @@ Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, 
     } else if (hpfw_gpu_extract_windows_pcm16_host(h, pcm.data(), n, opt.win, opt.hop, tempos, (int)opt.tempos.size(), shifts,
                                                    (int)opt.shifts.size(), hp.data()) != 0)
         fail("extraction");
+    const hpfw_timeline_params p{opt.min_score, (double)opt.hop * (double)g.m / (3.0 * (double)opt.win), opt.tol_cols, opt.win, opt.hop,
+                                 opt.max_gap, opt.min_windows};
+    const double col_s = 3.0 * (double)opt.win / (double)g.m / 44100.0; // one index column in seconds
+    std::vector<hpfw_segment> segs((size_t)n_w);
+    int64_t n_seg = 0;
+    if constexpr (!sharded) {
+        if (opt.min_overlap > 0) { // the overlap rule: lags in place of offsets, segments trimmed to the clip
+            out.windows.resize((size_t)n_w);
+            out.overlaps.resize((size_t)n_w);
+            if (detail::search_windows_overlap(storage.handle(), hp.data(), n_w, nhp, opt.min_overlap, out.windows.data(), out.overlaps.data()) != 0)
+                fail("search");
+            std::vector<int64_t> db_off(storage.names().size() + 1, 0);
+            if (hpfw_gpu_index_get(storage.handle(), db_off.data(), nullptr, 0) != 0) fail("index");
+            if (hpfw_gpu_timeline_segments(out.windows.data(), n_w, &p, segs.data(), n_w, &n_seg) != 0) fail("segments");
+            for (int64_t i = 0; i < n_seg; ++i) {
+                const hpfw_segment &s = segs[(size_t)i];
+                out.segments.push_back({storage.names()[s.clip], s.clip, 0.0, 0.0, s.best_score, 0.0, 0, (float)s.best_tempo, s});
+                if (detail::trim_segment(out.segments.back(), out.windows[(size_t)s.first].offset, out.windows[(size_t)s.last].offset,
+                                         db_off[s.clip + 1] - db_off[s.clip], g, opt.win, opt.hop) != 0)
+                    fail("extent");
+            }
+            return out;
+        }
+    }
     std::vector<int64_t> q_off((size_t)(n_w * sets) + 1);
     for (size_t i = 0; i < q_off.size(); ++i) q_off[i] = (int64_t)i * nhp;
     std::vector<hpfw_dist_stats> stats((size_t)(n_w * sets));
@@ -116,12 +192,7 @@ Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, 
         const int counted = db_off[hit.clip + 1] - db_off[hit.clip] >= nhp;
         if (hpfw_gpu_hit_score(hit.dist, counted, &stats[(size_t)(w * sets + x.variant)], &x.score) != 0) fail("score");
     }
-    const hpfw_timeline_params p{opt.min_score, (double)opt.hop * (double)g.m / (3.0 * (double)opt.win), opt.tol_cols, opt.win, opt.hop,
-                                 opt.max_gap, opt.min_windows};
-    std::vector<hpfw_segment> segs((size_t)n_w);
-    int64_t n_seg = 0;
     if (hpfw_gpu_timeline_segments(out.windows.data(), n_w, &p, segs.data(), n_w, &n_seg) != 0) fail("segments");
-    const double col_s = 3.0 * (double)opt.win / (double)g.m / 44100.0; // one index column in seconds
     for (int64_t i = 0; i < n_seg; ++i) {
         const hpfw_segment &s = segs[(size_t)i];
         out.segments.push_back({storage.names()[s.clip], s.clip, (double)s.start / 44100.0, (double)s.end / 44100.0, s.best_score,

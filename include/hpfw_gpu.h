@@ -676,6 +676,42 @@ typedef struct {
 int hpfw_gpu_timeline_segments(const hpfw_window_hit *w, int64_t n_w, const hpfw_timeline_params *p, hpfw_segment *out,
                                int64_t cap, int64_t *n_seg);
 
+/* ---- scored overlap search: how far a hit of hpfw_gpu_search_overlap stands out from the rest of
+ * the index, so that windows of a timeline can be searched by the overlap rule.
+ *
+ * A candidate (dist, L, lag) is ordered by the exact rational dist / L; for statistics it is mapped to one integer,
+ *     rate(dist, L) = floor(dist * 2^HPFW_OVERLAP_RATE_BITS / L),   L >= 1, dist <= 64 L.
+ * L <= 16000, so the numerator is below 2^30 and a 32-bit unsigned division is exact; rate <= 2^16.  The scored entry points
+ * return the hits of their unscored counterparts byte for byte and, per query row, the moments {sum, sum_sq, n} of rate_c
+ * over the COUNTED clips: those that have a candidate for the query (n_c >= min_overlap and k_q >= min_overlap) and are not
+ * the query's exclude entry.  rate^2 <= 2^32 and an index holds fewer than 2^31 clips, so sum_sq stays below 2^63 for every
+ * index the overlap search accepts: no call is refused because a sum could wrap.  The sums are integers, so they are bitwise
+ * deterministic for any number of splits, slices and query groups and for either scan kernel; no floating point runs on the
+ * device.  An empty index, an empty query and a query below min_overlap give n = 0.
+ * The score of a hit is hpfw_gpu_hit_score(rate(hit.dist, hit.overlap), 1, &stats[q], &score): a clip that is hit is counted.
+ * Refusals as hpfw_gpu_search_overlap's, and a null stats pointer (HPFW_E_INVALID). */
+#define HPFW_OVERLAP_RATE_BITS 10
+/* d_q_hp, d_out [n_q][k], d_stats [n_q] device; q_off, exclude host */
+int hpfw_gpu_search_overlap_scored_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                          const int32_t *exclude, int min_overlap, int k, hpfw_overlap_hit *d_out,
+                                          hpfw_dist_stats *d_stats, void *stream);
+int hpfw_gpu_search_overlap_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q,
+                                   const int32_t *exclude, int min_overlap, int k, hpfw_overlap_hit *out,
+                                   hpfw_dist_stats *stats);
+/* Host only: *rate = rate(dist, overlap).  overlap == 0, overlap > 16000 or dist > 64 overlap is HPFW_E_INVALID. */
+int hpfw_gpu_overlap_rate(uint32_t dist, uint32_t overlap, uint32_t *rate);
+/* Host only: the part of a window that lies on the clip it was found in, in samples of the window.  The window has k_q
+ * hashprints and was found at lag `lag` on a clip of n_clip hashprints; a hashprint spans `span` columns (S = c - n_hp + 1 of
+ * hpfw_gpu_geometry(win), 100 for the live-id configuration), and one column is col = 3 win / m samples (m of the same
+ * geometry).  In columns the window lies on the clip over
+ *     a_cols = max(0, -lag),   b_cols = min(k_q + span - 1, n_clip + span - 1 - lag),
+ * and *a = floor(a_cols col + 0.5), *b = min(win, floor(b_cols col + 0.5)), evaluated in double exactly as written.  For a
+ * hit inside the clip (0 <= lag <= n_clip - k_q) that is the whole window, [0, win).  A segment of windows searched by the
+ * overlap rule starts at first * hop + a(first window) and ends at last * hop + b(last window).
+ * n_clip, k_q, span, win or m below 1, or a lag at which window and clip share no hashprint, is HPFW_E_INVALID. */
+int hpfw_gpu_overlap_extent(int32_t lag, int64_t n_clip, int64_t k_q, int64_t span, int64_t win, int64_t m, int64_t *a,
+                            int64_t *b);
+
 /* ---- live feeds: the timeline of feeds that are still running, as their samples arrive.
  *
  * A set of n_streams feeds on one handle, each a ring of `capacity` samples in device memory.  A feed is mono PCM16 at 44.1 kHz
