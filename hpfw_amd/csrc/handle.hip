@@ -39,6 +39,7 @@ int hpfw_gpu_create(int device, hpfw_gpu **out)
     if (const char *e = std::getenv("HPFW_PRUNE")) h->prune = (unsigned)std::strtoul(e, nullptr, 0);
     if (const char *e = std::getenv("HPFW_Q_PRODUCTS")) h->q_products = atoi(e) == 9 ? 9 : 6;
     if (const char *e = std::getenv("HPFW_Q_FIXUP")) h->q_fixup_launch = std::strcmp(e, "launch") == 0;
+    if (const char *e = std::getenv("HPFW_Q_STAGING")) h->q_staging_classic = std::strcmp(e, "classic") == 0;
     if (const char *e = std::getenv("HPFW_DB_TERM")) h->db_fast = std::strcmp(e, "spec") != 0;
     if (const char *e = std::getenv("HPFW_FWD_STREAMS")) h->fwd_streams = std::min(hpfw_gpu::kCqSide + 1, std::max(1, atoi(e)));
     if (const char *e = std::getenv("HPFW_PROJECTION")) // "f32": handles start with the f32 fma chain (hpfw_gpu_set_projection(h, 0))

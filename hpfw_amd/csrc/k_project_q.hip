@@ -27,6 +27,14 @@
 // The extraction's unshifted launches form only the six digit products of weight >= 2^16 (hashprint_q6_kernel) and settle
 // the few values whose sign those leave open in the same workgroup, from the digits still in its slab, before the
 // hashprints are stored: one launch, one pass over the spectrogram, hp written once (hashprint_q_tile, FUSED).
+//
+// The slab is staged by chains: the 147 columns of Du need u of 227 columns, and a thread that holds u of column r, r + 80
+// and r + 160 forms Du[r] and Du[r + 80] from them, so every dB term is loaded and quantised once per workgroup (1816
+// column-units of 16 bins where a unit per slab column with its partner took 2352); the digit planes are gathered by
+// byte permutes, and a thread's five tasks keep the loads of two tasks in flight beyond the one it quantises.  Where a
+// clip's last tile is short, the short tiles of all clips are dispatched behind the full ones (q_tile_of_workgroup).
+// HPFW_Q_STAGING=classic at handle creation keeps the staging and the order as they were, to measure against
+// (CLASSIC; profiles/r10_q_staging.md).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -39,6 +47,7 @@ namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
+typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
@@ -65,9 +74,37 @@ constexpr int kQLdsBytes6f = kQLdsBytes6 + kQCap * 2;         // + its list of t
 // the three balanced base-256 digits of u as the three low bytes of one word (|u| < 2^23)
 __device__ __forceinline__ unsigned q_digit_bytes(int u) { return ((unsigned)u + 0x808080u) ^ 0x808080u; }
 
+#if defined(HPFW_Q_STAMPS)
+// diagnosis build (tools/q_stamps.py extract): where the extraction's six-product kernel, which has no dbg argument, leaves its stamps
+__device__ long long *g_q_stamps_dev = nullptr;
+#endif
+
 __device__ __forceinline__ int q_fixed(float s)
 {
     return (int)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(s, -80.0f), 0.0f) * kQScale);
+}
+
+// The staging's tasks ("one quantisation per dB term"): Du[col] = u[col] - u[col + 80], so the slab's 147 columns
+// need u of the 227 columns n0 .. n0 + 226, and these fall into 80 chains r, r + 80, r + 160 (r < 80; the third only for
+// r < 67).  A task = (half chunk qh: bins 8 qh .. 8 qh + 7, residue r): it loads and quantises its chain once and forms
+// Du[r] and, for r < 67, Du[r + 80] from it -- every (bin, column) is loaded and passed through q_fixed by exactly one
+// thread of the workgroup.  16 half chunks x 80 residues = 1280 tasks, five per thread, 24 loads each.
+constexpr int kQHeavy = kQCols - kLag;                        // 67 residues whose chain holds two slab columns
+constexpr int kQTasks = 2 * kQChunks * kLag / kQThreads;      // 5 tasks per thread
+constexpr int kQAhead = 2;                                    // tasks whose loads are in flight beyond the one being quantised
+static_assert(kQTasks * kQThreads == 2 * kQChunks * kLag && kQHeavy > 0 && kQHeavy <= kLag, "1280 tasks, five per thread");
+
+// Digit planes of four elements: w[e] = q_digit_bytes of element e (digit j in byte j).  Returns in p[j] the dword of plane
+// j, element e's digit in byte e.  v_perm_b32 takes bytes 0..3 of its selector's range from the SECOND operand, 4..7 from the first.
+__device__ __forceinline__ void q_planes(const unsigned (&w)[4], unsigned (&p)[3])
+{
+    const unsigned t01 = __builtin_amdgcn_perm(w[1], w[0], 0x05010400u); // [w0.b0, w1.b0, w0.b1, w1.b1]
+    const unsigned t23 = __builtin_amdgcn_perm(w[3], w[2], 0x05010400u);
+    const unsigned u01 = __builtin_amdgcn_perm(w[1], w[0], 0x0c0c0602u); // [w0.b2, w1.b2, 0, 0]
+    const unsigned u23 = __builtin_amdgcn_perm(w[3], w[2], 0x0c0c0602u);
+    p[0] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
+    p[1] = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+    p[2] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);
 }
 
 // One wave forms D[r][n0 + nl] exactly from digits alone (r, nl the same in every lane).  The 2420 taps are 160 pairs of
@@ -135,7 +172,7 @@ __device__ __forceinline__ long long q_value_from_digits(const v4i *__restrict__
 // A workgroup with more than kQCap open values (near-stationary input) runs the nine-product body over its slab instead
 // (STAGED: the body entered behind the staging, the six-product accumulators dead by then).  hp is written once and final;
 // neither a second launch nor a second pass over the spectrogram follows.  counts[t] keeps its meaning.
-template <bool FROM_T, bool SHIFTED, int NP, bool FUSED = false, bool STAGED = false>
+template <bool FROM_T, bool SHIFTED, int NP, bool CLASSIC, bool FUSED = false, bool STAGED = false>
 __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
                                                  const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, uint64_t *__restrict__ hp,
                                                  long long *__restrict__ dbg, int n_images, const int *__restrict__ thr,
@@ -170,12 +207,78 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
         a[0][d] = img[d * 64];
         a[1][d] = img[(kQStepBytes / 16) + d * 64];
     }
-    // slab: one (chunk, column) unit = 16 bins of one column of Du, three digit planes.  The loads of a round (16 bins x
-    // the column and its partner 80 on) are all issued before the first value is quantised
-    constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
     unsigned any_digit = 0; // (NP = 6) whether this thread stored a non-zero digit
+    if constexpr (!CLASSIC && !STAGED) { // (STAGED: the caller's slab stands)
+        // slab: a task's half unit = 8 bins of one column of Du, three digit planes of 8 bytes.  Every load is issued, from a valid
+        // 32-bit clip-relative index (S[0], S[kLag] exist), and what lies outside the valid part is zeroed afterwards (as in the
+        // classic staging below).  The loads of task i + kQAhead are issued before task i is quantised: a wave waits for
+        // memory once, at its first task, and the accumulators' registers, dead until the barrier, hold the values in flight
+        float x[kQTasks][3][8];
+        auto issue = [&](int i) {
+            const int task = tid + i * kQThreads, qh = task / kLag, r = task - qh * kLag;
+            const int gc = n0 + r;
+            const bool in0 = gc + kLag < c, in1 = r < kQHeavy && gc + 2 * kLag < c;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int bin = 8 * qh + e;
+                const unsigned at = (unsigned)(bin * c + gc); // (< 121 * c where it is used)
+                const unsigned i0 = in0 && bin < kBins ? at : 0u, i2 = in1 && bin < kBins ? at + 2 * kLag : 0u;
+                x[i][0][e] = S[i0];
+                x[i][1][e] = S[i0 + kLag];
+                x[i][2][e] = S[i2];
+            }
+        };
+        auto quantise = [&](int i) {
+            const int task = tid + i * kQThreads, qh = task / kLag, r = task - qh * kLag;
+            const int gc = n0 + r;
+            const bool in0 = gc + kLag < c, in1 = r < kQHeavy && gc + 2 * kLag < c;
+            unsigned wa[8], wb[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const bool okb = 8 * qh + e < kBins;
+                float x0 = x[i][0][e], x1 = x[i][1][e], x2 = x[i][2][e];
+                if (FROM_T) {
+                    x0 -= ref;
+                    x1 -= ref;
+                    x2 -= ref;
+                }
+                const int u0 = q_fixed(x0), u1 = q_fixed(x1), u2 = q_fixed(x2);
+                wa[e] = q_digit_bytes(in0 && okb ? u0 - u1 : 0);
+                wb[e] = q_digit_bytes(in1 && okb ? u1 - u2 : 0);
+            }
+            // the half unit's place: chunk qh >> 1, bytes 8 (qh & 1) .. + 7 of each plane
+            unsigned char *dst = slab + (size_t)((qh >> 1) * kQPitch + r) * kQUnit + 8 * (qh & 1);
+            auto store = [&](const unsigned (&w)[8], unsigned char *to) {
+                unsigned lo[3], hi[3];
+                q_planes({w[0], w[1], w[2], w[3]}, lo);
+                q_planes({w[4], w[5], w[6], w[7]}, hi);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) *reinterpret_cast<v2i *>(to + 16 * j) = v2i{(int)lo[j], (int)hi[j]};
+                if (NP == 6) any_digit |= lo[0] | lo[1] | lo[2] | hi[0] | hi[1] | hi[2];
+            };
+            // column r + 80 of a chain without a second slab column (r >= 67) is one of the pitch's 13 spare columns 147 .. 159,
+            // which nothing reads: its zero digits are stored there without a branch (inside one, the compiler moved the
+            // third column's loads into it too, with a wait for everything in flight)
+            static_assert(kLag + kLag <= kQPitch, "spare columns for the chains' unconditional second store");
+            store(wa, dst);
+            store(wb, dst + (size_t)kLag * kQUnit);
+        };
+#pragma unroll
+        for (int i = 0; i < kQAhead && i < kQTasks; ++i) issue(i);
+#pragma unroll
+        for (int i = 0; i < kQTasks; ++i) {
+            if (i + kQAhead < kQTasks) issue(i + kQAhead);
+            __builtin_amdgcn_sched_barrier(0); // (the loads stay above the quantisation they are to hide under)
+            quantise(i);
+        }
+    }
+    // The classic staging (HPFW_Q_STAGING=classic, kept to measure against; no trip otherwise): one (chunk, column) unit =
+    // 16 bins of one column of Du, three digit planes, from the column and its partner 80 on -- every column n0 + 80 ..
+    // n0 + 146 is loaded and quantised twice.  The loads of a round are all issued before the first value is quantised,
+    // and the three rounds follow one another
+    constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
 #pragma unroll 1
-    for (int r0 = STAGED ? kUnits : 0; r0 < kUnits; r0 += 2) { // (STAGED: the caller's slab stands, no trip)
+    for (int r0 = STAGED || !CLASSIC ? kUnits : 0; r0 < kUnits; r0 += 2) { // (STAGED: the caller's slab stands, no trip)
         float va[2][16], vb[2][16];
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
@@ -363,7 +466,8 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
             const unsigned cnt = *n_open; // (the same for the whole workgroup; nothing adds to it behind the barrier)
             if (cnt > (unsigned)kQCap) {
                 if (tid == 0) counts[t] = kQRedo;
-                hashprint_q_tile<FROM_T, false, 9, false, true>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr, nullptr);
+                hashprint_q_tile<FROM_T, false, 9, CLASSIC, false, true>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr,
+                                                                         nullptr);
                 return;
             }
             if (cnt > 0) {
@@ -389,10 +493,11 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
     } while (SHIFTED && ++im < n_images);
 #if defined(HPFW_Q_STAMPS)
     Q_STAMP(5);
-    if (dbg && tid == 0) {
-        for (int k = 0; k < 6; ++k) dbg[(int64_t)t * 8 + k] = st[k];
-        dbg[(int64_t)t * 8 + 6] = __builtin_amdgcn_s_getreg((15 << 11) | 4); // HW_ID: wave, SIMD, CU, SH, SE
-        dbg[(int64_t)t * 8 + 7] = blockIdx.x;
+    long long *stamps = dbg ? dbg : g_q_stamps_dev;
+    if (stamps && tid == 0 && !STAGED) {
+        for (int k = 0; k < 6; ++k) stamps[(int64_t)t * 8 + k] = st[k];
+        stamps[(int64_t)t * 8 + 6] = __builtin_amdgcn_s_getreg((15 << 11) | 4); // HW_ID: wave, SIMD, CU, SH, SE
+        stamps[(int64_t)t * 8 + 7] = blockIdx.x;
     }
 #endif
 }
@@ -400,52 +505,83 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
 // Workgroups go to the eight XCDs in turn (id mod 8), each with an L2 of its own: an XCD takes a contiguous run of
 // (clip, tile) pairs with the tile fastest, so that the 99 columns two neighbouring tiles share, and the columns a
 // tile reads twice (as c and as c + 80), come from HBM once: 2.34 -> 1.19 MB per clip by the counters (1.17 algorithmic; profiles/r04_pmc.json)
-__device__ __forceinline__ unsigned q_tile_of_workgroup()
+//
+// Short tiles last: where a clip's last tile holds fewer than eight tiles of 16 hashprints (n_hp = 2320: one of eight) its
+// workgroup stages a whole slab for a fraction of the matrix work, and a workgroup that starts in the launch's last
+// generation runs its whole life on a nearly empty chip.  The full tiles then come first, in the order above, and the
+// clips' short tiles after them, each XCD again with a contiguous run: the launch ends on short workgroups.  The
+// logical tile t = clip * n_tiles_x + tile (counts, seg, hp, dbg) does not change.  CLASSIC: the one order for all.
+constexpr unsigned kQNoTile = 0xffffffffu;
+__host__ __device__ inline bool q_short_last(int nhp, int n_tiles_x) { return nhp - (n_tiles_x - 1) * kQTileN <= kQTileN - 16; }
+__host__ __device__ inline unsigned q_round8(unsigned n) { return 8 * ((n + 7) / 8); }
+
+static unsigned q_grid(bool classic, int nhp, int n_tiles_x, int n_clips)
 {
-    const unsigned per_xcd = (gridDim.x + 7) / 8;
-    return (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (classic || !q_short_last(nhp, n_tiles_x)) return q_round8((unsigned)n_tiles_x * (unsigned)n_clips);
+    return q_round8((unsigned)(n_tiles_x - 1) * (unsigned)n_clips) + q_round8((unsigned)n_clips);
 }
 
-template <bool FROM_T, bool SHIFTED>
+template <bool CLASSIC>
+__device__ __forceinline__ unsigned q_tile_of_workgroup(int nhp, int n_tiles_x, int n_clips)
+{
+    unsigned b = blockIdx.x;
+    if (CLASSIC || !q_short_last(nhp, n_tiles_x)) {
+        const unsigned t = (b & 7) * (gridDim.x / 8) + (b >> 3);
+        return t < (unsigned)(n_tiles_x * n_clips) ? t : kQNoTile;
+    }
+    const unsigned full_x = (unsigned)(n_tiles_x - 1), n_full = full_x * (unsigned)n_clips, grid_full = q_round8(n_full);
+    if (b < grid_full) {
+        const unsigned j = (b & 7) * (grid_full / 8) + (b >> 3);
+        if (j >= n_full) return kQNoTile;
+        const unsigned clip = j / full_x;
+        return clip * (unsigned)n_tiles_x + (j - clip * full_x);
+    }
+    b -= grid_full; // (a multiple of 8: the XCD is b & 7 as before)
+    const unsigned j = (b & 7) * ((gridDim.x - grid_full) / 8) + (b >> 3);
+    return j < (unsigned)n_clips ? j * (unsigned)n_tiles_x + full_x : kQNoTile;
+}
+
+template <bool FROM_T, bool SHIFTED, bool CLASSIC>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
                                                                    const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
                                                                    uint64_t *__restrict__ hp, long long *__restrict__ dbg, int n_images)
 {
-    const unsigned t = q_tile_of_workgroup();
-    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
-    hashprint_q_tile<FROM_T, SHIFTED, 9>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, dbg, n_images, nullptr, nullptr, nullptr);
+    const unsigned t = q_tile_of_workgroup<CLASSIC>(nhp, n_tiles_x, n_clips);
+    if (t == kQNoTile) return;
+    hashprint_q_tile<FROM_T, SHIFTED, 9, CLASSIC>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, dbg, n_images, nullptr, nullptr, nullptr);
 }
 
 // the six-product instantiation of the extraction's kernel (hashprint_q_tile, FUSED): bits from Dp, the open values
 // settled from the slab before the hashprints are stored
-template <bool FROM_T>
+template <bool FROM_T, bool CLASSIC>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
                                                                     const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
                                                                     uint64_t *__restrict__ hp, const int *__restrict__ thr,
                                                                     unsigned *__restrict__ counts)
 {
-    const unsigned t = q_tile_of_workgroup();
-    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
-    hashprint_q_tile<FROM_T, false, 6, true>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, nullptr);
+    const unsigned t = q_tile_of_workgroup<CLASSIC>(nhp, n_tiles_x, n_clips);
+    if (t == kQNoTile) return;
+    hashprint_q_tile<FROM_T, false, 6, CLASSIC, true>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, nullptr);
 }
 
 // HPFW_Q_FIXUP=launch (kept to measure against): the six-product kernel that lists the open values in global segments for
 // hashprint_q_fixup_kernel
-template <bool FROM_T>
+template <bool FROM_T, bool CLASSIC>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_listed_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
                                                                            const float *__restrict__ tmax, int c, int nhp, int n_tiles_x,
                                                                            int n_clips, uint64_t *__restrict__ hp, const int *__restrict__ thr,
                                                                            unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
 {
-    const unsigned t = q_tile_of_workgroup();
-    if (t >= (unsigned)(n_tiles_x * n_clips)) return;
-    hashprint_q_tile<FROM_T, false, 6>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, seg);
+    const unsigned t = q_tile_of_workgroup<CLASSIC>(nhp, n_tiles_x, n_clips);
+    if (t == kQNoTile) return;
+    hashprint_q_tile<FROM_T, false, 6, CLASSIC>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, seg);
 }
 
 // The fix-up of a hashprint_q6_listed_kernel launch, after it on the same stream: workgroups take the tiles in turn.  A tile with
 // listed open values: one wave per entry (r, n) forms D[r][n] = sum_k fq[r][k] Du[k / 20][n + k % 20] exactly in int64
 // -- fq32 [64][2420], Du from the dB terms as the staging quantises them -- and flips bit 63 - r of hp[n] where D >= 0
-// disagrees with it.  A tile marked kQRedo: the nine-product body over the whole tile.
+// disagrees with it.  A tile marked kQRedo: the nine-product body over the whole tile, always with the classic staging (the
+// same slab): inside this loop the chains' values in flight did not fit the registers (49 spilled, 7 as it is).
 template <bool FROM_T>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_fixup_kernel(const v4i *__restrict__ fq_image, const int *__restrict__ fq32,
                                                                          const float *__restrict__ sdb, const float *__restrict__ tmax, int c,
@@ -460,7 +596,7 @@ __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_fixup_kernel(const v
         if (cnt == 0) continue;
         if (cnt == kQRedo) {
             __syncthreads(); // (the slab and parts of a tile redone before)
-            hashprint_q_tile<FROM_T, false, 9>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr, nullptr);
+            hashprint_q_tile<FROM_T, false, 9, true>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr, nullptr);
             continue;
         }
         const int clip = t / n_tiles_x;
@@ -565,7 +701,11 @@ void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int3
 
 #if defined(HPFW_Q_STAMPS)
 static long long *g_q_stamps = nullptr;
-extern "C" void hpfw_gpu_debug_set_q_stamps(void *d) { g_q_stamps = static_cast<long long *>(d); }
+extern "C" void hpfw_gpu_debug_set_q_stamps(void *d)
+{
+    g_q_stamps = static_cast<long long *>(d);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_q_stamps_dev), &g_q_stamps, sizeof(g_q_stamps));
+}
 #endif
 
 size_t project_q_image_bytes() { return (size_t)4 * kQSteps * kQStepBytes; }
@@ -584,49 +724,67 @@ int64_t project_q_tiles(int64_t n_clips, int64_t c)
 // copy of pack_filters_q's thresholds; d_work: project_q_split_bytes(project_q_tiles(n_clips, c), d_fq32 != NULL) bytes,
 // counts [tiles].  d_fq32 != NULL (HPFW_Q_FIXUP=launch): the listing kernel and the fix-up launch; d_work then holds the
 // segments [tiles][kQCap] behind the counts
-void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
-                         long long *d_dbg, hipStream_t s, const QSplit *split)
+template <bool CLASSIC>
+static void launch_hashprints_q_as(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
+                                   long long *d_dbg, hipStream_t s, const QSplit *split)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        for (const void *k : {reinterpret_cast<const void *>(hashprint_q_kernel<true, false>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false>),
-                              reinterpret_cast<const void *>(hashprint_q_kernel<true, true>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true>)})
+        for (const void *k :
+             {reinterpret_cast<const void *>(hashprint_q_kernel<true, false, CLASSIC>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false, CLASSIC>),
+              reinterpret_cast<const void *>(hashprint_q_kernel<true, true, CLASSIC>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true, CLASSIC>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes);
-        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_listed_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_listed_kernel<false>),
-                              reinterpret_cast<const void *>(hashprint_q_fixup_kernel<true>), reinterpret_cast<const void *>(hashprint_q_fixup_kernel<false>)})
+        for (const void *k :
+             {reinterpret_cast<const void *>(hashprint_q6_listed_kernel<true, CLASSIC>), reinterpret_cast<const void *>(hashprint_q6_listed_kernel<false, CLASSIC>),
+              reinterpret_cast<const void *>(hashprint_q_fixup_kernel<true>), reinterpret_cast<const void *>(hashprint_q_fixup_kernel<false>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6);
-        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_kernel<false>)})
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true, CLASSIC>), reinterpret_cast<const void *>(hashprint_q6_kernel<false, CLASSIC>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6f);
         attr_set.mark();
     }
     const int nhp = c - (kCtx - 1) - kLag;
     if (nhp <= 0 || n_clips <= 0 || n_shifts < 0) return;
 #if defined(HPFW_Q_STAMPS)
-    if (!d_dbg) d_dbg = g_q_stamps; // (tools/q_stamps.py extract: the stamps of the extraction's own launches)
+    // (tools/q_stamps.py extract: the stamps of the extraction's own launches; its six-product kernel finds them by g_q_stamps_dev)
+    if (!d_dbg && !(split && n_shifts == 0)) d_dbg = g_q_stamps;
 #endif
     const int tiles = (nhp + kQTileN - 1) / kQTileN;
-    const dim3 grid(8 * (unsigned)(((int64_t)tiles * n_clips + 7) / 8)); // one-dimensional, in XCD-aware order
+    const dim3 grid(q_grid(CLASSIC, nhp, tiles, n_clips)); // one-dimensional, in XCD-aware order (q_tile_of_workgroup)
     if (split && n_shifts == 0 && !d_dbg) {
         const int *fq32 = split->d_fq32, *thr = split->d_thr;
         unsigned *counts = static_cast<unsigned *>(split->d_work);
         if (!fq32) {
-            hipLaunchKernelGGL(d_tmax ? hashprint_q6_kernel<true> : hashprint_q6_kernel<false>, grid, dim3(kQThreads), kQLdsBytes6f, s,
-                               static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, thr, counts);
+            auto k6 = d_tmax ? hashprint_q6_kernel<true, CLASSIC> : hashprint_q6_kernel<false, CLASSIC>;
+            hipLaunchKernelGGL(k6, grid, dim3(kQThreads), kQLdsBytes6f, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
+                               d_hp, thr, counts);
             return;
         }
         unsigned short *seg = reinterpret_cast<unsigned short *>(counts + (size_t)tiles * n_clips);
-        hipLaunchKernelGGL(d_tmax ? hashprint_q6_listed_kernel<true> : hashprint_q6_listed_kernel<false>, grid, dim3(kQThreads), kQLdsBytes6, s,
-                           static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, thr, counts, seg);
+        auto k6 = d_tmax ? hashprint_q6_listed_kernel<true, CLASSIC> : hashprint_q6_listed_kernel<false, CLASSIC>;
+        hipLaunchKernelGGL(k6, grid, dim3(kQThreads), kQLdsBytes6, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
+                           d_hp, thr, counts, seg);
         // eight workgroups per CU share the tiles: few enough that none is launched for nothing, enough to hide the loads
         const unsigned fix = (unsigned)std::min<int64_t>((int64_t)tiles * n_clips, 2048);
-        hipLaunchKernelGGL(d_tmax ? hashprint_q_fixup_kernel<true> : hashprint_q_fixup_kernel<false>, dim3(fix), dim3(kQThreads), kQLdsBytes6, s,
-                           static_cast<const v4i *>(d_images), fq32, d_db, d_tmax, c, nhp, tiles, n_clips, d_hp, counts, seg);
+        auto kf = d_tmax ? hashprint_q_fixup_kernel<true> : hashprint_q_fixup_kernel<false>;
+        hipLaunchKernelGGL(kf, dim3(fix), dim3(kQThreads), kQLdsBytes6, s, static_cast<const v4i *>(d_images), fq32, d_db, d_tmax, c, nhp, tiles,
+                           n_clips, d_hp, counts, seg);
         return;
     }
-    auto k = n_shifts > 0 ? (d_tmax ? hashprint_q_kernel<true, true> : hashprint_q_kernel<false, true>)
-                          : (d_tmax ? hashprint_q_kernel<true, false> : hashprint_q_kernel<false, false>);
+    auto k = n_shifts > 0 ? (d_tmax ? hashprint_q_kernel<true, true, CLASSIC> : hashprint_q_kernel<false, true, CLASSIC>)
+                          : (d_tmax ? hashprint_q_kernel<true, false, CLASSIC> : hashprint_q_kernel<false, false, CLASSIC>);
     hipLaunchKernelGGL(k, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
                        d_hp, d_dbg, n_shifts);
+}
+
+// classic_staging (HPFW_Q_STAGING=classic at handle creation): the kernels with the staging and the workgroup order as they
+// were before the chains (hashprint_q_tile CLASSIC), kept to measure against; the slab and every result are the same
+void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
+                         long long *d_dbg, hipStream_t s, const QSplit *split, bool classic_staging)
+{
+    if (classic_staging)
+        launch_hashprints_q_as<true>(d_images, n_shifts, d_db, d_tmax, n_clips, c, d_hp, d_dbg, s, split);
+    else
+        launch_hashprints_q_as<false>(d_images, n_shifts, d_db, d_tmax, n_clips, c, d_hp, d_dbg, s, split);
 }
 
 void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s)

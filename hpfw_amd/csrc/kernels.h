@@ -273,7 +273,7 @@ size_t project_q_split_bytes(int64_t tiles, bool segments);
 int64_t project_q_tiles(int64_t n_clips, int64_t c);
 void pack_filters_q(const float *f_colmajor, std::vector<int8_t> &image, std::vector<int32_t> *thr = nullptr, std::vector<int32_t> *fq32 = nullptr);
 void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
-                         long long *d_dbg, hipStream_t s, const QSplit *split = nullptr);
+                         long long *d_dbg, hipStream_t s, const QSplit *split = nullptr, bool classic_staging = false);
 // transposed extraction: the digit images of the filters moved by each of shifts.s[0 .. n) bins
 // (d_images: n * project_q_image_bytes()), for launch_hashprints_q
 constexpr int kMaxShifts = 64;

@@ -1,7 +1,8 @@
 """q_stamps.py -- where a workgroup of hashprint_q_kernel spends its time (build: make OUT=../lib_qst EXTRA=-DHPFW_Q_STAMPS):
 s_memtime ticks (= shader cycles) of wave 0 at the phase boundaries, over the workgroups of one launch (dB spectrograms in).
     HPFW_GPU_LIB=hpfw_amd/lib_qst/libhpfw_gpu.so python tools/q_stamps.py [clips] [extract]
-"extract": the launches of a whole extraction (dB terms fresh from the chirp-z stage) instead of the dB-input entry point on
+"extract": the launches of a whole extraction (dB terms fresh from the chirp-z stage; its own kernel, the six-product one,
+which settles its open values behind the epilogue's barrier) instead of the dB-input entry point (nine products) on
 random values from HBM"""
 import os
 import sys
@@ -42,8 +43,8 @@ torch.cuda.synchronize()
 a = st.cpu().numpy()[: tiles * n_clips]
 d = np.diff(a[:, :6], axis=1).astype(np.float64)
 tot = (a[:, 5] - a[:, 0]).astype(np.float64)
-names = ["staging (loads, quantisation, LDS writes)", "barrier", "main loop (40 steps of 72 matrix instructions)", "epilogue (int64 sums, signs, shuffles)",
-         "barrier + store"]
+names = ["staging (loads, quantisation, LDS writes)", "barrier", "main loop (40 steps of 72 matrix instructions; extract: of 48)",
+         "epilogue (int64 sums, signs, shuffles)", "barrier + store (extract: + the open values settled)"]
 print(f"workgroups {a.shape[0]}; cycles per workgroup: median {np.median(tot):.0f}, mean {tot.mean():.0f}")
 for k, nm in enumerate(names):
     print(f"{nm:52s} median {np.median(d[:, k]):7.0f}  mean {d[:, k].mean():8.1f}  share {d[:, k].sum() / tot.sum():.3f}")
