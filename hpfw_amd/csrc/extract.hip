@@ -246,8 +246,8 @@ int q_split(hpfw_gpu *h, int n_shifts, int64_t n_clips, int64_t c, hpfw::QSplit 
     if (n_shifts || h->q_products != 6 || !h->projection) return 0;
     const int64_t tiles = hpfw::project_q_tiles(n_clips, c);
     if (tiles <= 0) return 0;
-    if (int rc = ensure(h->d_q_split, hpfw::project_q_split_bytes(tiles, h->q_fixup_launch), h)) return rc;
-    *qs = {h->d_q_thr.as<int32_t>(), h->d_q_split.get(), h->q_fixup_launch ? h->d_fq32.as<int32_t>() : nullptr};
+    if (int rc = ensure(h->d_q_split, hpfw::project_q_split_bytes(tiles), h)) return rc;
+    *qs = {h->d_q_thr.as<int32_t>(), h->d_q_split.get()};
     *use = qs;
     return 0;
 }
@@ -266,7 +266,7 @@ int run_back(hpfw_gpu *h, DevPlan *dp, const void *images, int n_shifts, int ns,
         if ((rc = q_split(h, n_shifts, ns, p.c, &qs, &split))) return rc;
         {
             Timed t(h, K_PROJECT, s);
-            hpfw::launch_hashprints_q(images, n_shifts, sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s, split, h->q_staging_classic);
+            hpfw::launch_hashprints_q(images, n_shifts, sdb, h->d_clipmax.as<float>(), ns, p.c, d_hp, nullptr, s, split);
         }
         if (split) h->q_last_tiles = hpfw::project_q_tiles(ns, p.c);
         return check_launch("project");
@@ -349,7 +349,7 @@ int hashprints_from_db(hpfw_gpu *h, const float *d_db, int64_t n_clips, int64_t 
             if (h->projection) {
                 Timed t(h, K_PROJECT, s);
                 hpfw::launch_hashprints_q(images, n_shifts, d_db + c0 * 121 * c, nullptr, nb, (int)c, d_hp + c0 * std::max(n_shifts, 1) * nhp,
-                                          nullptr, s, split, h->q_staging_classic);
+                                          nullptr, s, split);
                 if (split) h->q_last_tiles = hpfw::project_q_tiles(nb, c);
             } else {
                 hpfw::launch_project(h->d_fpack.as<float>(), d_db + c0 * 121 * c, nullptr, nb, (int)c, h->ws[3].as<float>(), s);
@@ -426,8 +426,7 @@ int tempo_back(hpfw_gpu *h, const void *images, int n_shifts, const float *d_db,
             if ((rc = check_launch("tempo_scale"))) return rc;
             {
                 Timed t(h, K_PROJECT, s);
-                hpfw::launch_hashprints_q(images, n_shifts, scaled, nullptr, nc * sub.n, (int)ct, d_hp + (c0 * tl.n + j0) * per_pair, nullptr, s, nullptr,
-                                          h->q_staging_classic);
+                hpfw::launch_hashprints_q(images, n_shifts, scaled, nullptr, nc * sub.n, (int)ct, d_hp + (c0 * tl.n + j0) * per_pair, nullptr, s);
             }
             if ((rc = check_launch("project"))) return rc;
         }
@@ -591,7 +590,7 @@ int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int6
             if (int rc = ensure(h->ws[3], (size_t)n_clips * (size_t)nhp * 8)) return rc;
             hp = h->ws[3].as<uint64_t>();
         }
-        hpfw::launch_hashprints_q(h->d_fq_image.get(), 0, d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s, nullptr, h->q_staging_classic);
+        hpfw::launch_hashprints_q(h->d_fq_image.get(), 0, d_db, nullptr, (int)n_clips, (int)c, hp, (long long *)d_delta, s);
         return check_launch("project");
     });
 }

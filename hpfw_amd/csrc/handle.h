@@ -86,14 +86,9 @@ struct hpfw_gpu {
     DevBuf d_fq_image; // the filters' fixed-point digits (k_project_q.hip)
     // the six-product split of the unshifted fixed-point extraction (k_project_q.hip): the rows' thresholds; the
     // tiles' counts of open values of a launch; the tiles of the last launch (hpfw_gpu_debug_q_products).
-    // HPFW_Q_PRODUCTS=9 in the environment at creation: the nine-product kernel alone.  HPFW_Q_FIXUP=launch: the open values
-    // listed and recomputed by a second launch (the form before the kernel settled them itself, kept to measure against); only
-    // then fq as int32 is on the device and d_q_split holds the segments too.  HPFW_Q_STAGING=classic: every fixed-point hashprint
-    // launch of the handle stages its slab and orders its workgroups as before the chains (k_project_q.hip CLASSIC; the same results)
-    DevBuf d_q_thr, d_fq32, d_q_split;
+    // HPFW_Q_PRODUCTS=9 in the environment at creation: the nine-product kernel alone.
+    DevBuf d_q_thr, d_q_split;
     int q_products = 6;
-    bool q_fixup_launch = false;
-    bool q_staging_classic = false;
     int64_t q_last_tiles = 0;
     int projection = 1; // 1: fixed point (S9q), 0: the f32 fma chain (S9); hpfw_gpu_set_projection
     // the tables of every clip length in use and the device memory they come from (plans.hip)

@@ -38,8 +38,6 @@ int hpfw_gpu_create(int device, hpfw_gpu **out)
     if (const char *e = std::getenv("HPFW_COLS_VARIANT")) h->cols_variant = atoi(e);
     if (const char *e = std::getenv("HPFW_PRUNE")) h->prune = (unsigned)std::strtoul(e, nullptr, 0);
     if (const char *e = std::getenv("HPFW_Q_PRODUCTS")) h->q_products = atoi(e) == 9 ? 9 : 6;
-    if (const char *e = std::getenv("HPFW_Q_FIXUP")) h->q_fixup_launch = std::strcmp(e, "launch") == 0;
-    if (const char *e = std::getenv("HPFW_Q_STAGING")) h->q_staging_classic = std::strcmp(e, "classic") == 0;
     if (const char *e = std::getenv("HPFW_DB_TERM")) h->db_fast = std::strcmp(e, "spec") != 0;
     if (const char *e = std::getenv("HPFW_FWD_STREAMS")) h->fwd_streams = std::min(hpfw_gpu::kCqSide + 1, std::max(1, atoi(e)));
     if (const char *e = std::getenv("HPFW_PROJECTION")) // "f32": handles start with the f32 fma chain (hpfw_gpu_set_projection(h, 0))
@@ -70,16 +68,12 @@ int hpfw_gpu_set_filters(hpfw_gpu *h, const float *f)
     if (!h->d_fpack) HIP_TRY(h->d_fpack.alloc(packed.size() * 4));
     HIP_TRY(hipMemcpy(h->d_fpack.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     std::vector<int8_t> image;
-    std::vector<int32_t> thr, fq32;
-    hpfw::pack_filters_q(f, image, &thr, h->q_fixup_launch ? &fq32 : nullptr);
+    std::vector<int32_t> thr;
+    hpfw::pack_filters_q(f, image, &thr);
     if (!h->d_fq_image) HIP_TRY(h->d_fq_image.alloc(image.size()));
     HIP_TRY(hipMemcpy(h->d_fq_image.get(), image.data(), image.size(), hipMemcpyHostToDevice));
     if (!h->d_q_thr) HIP_TRY(h->d_q_thr.alloc(thr.size() * 4));
     HIP_TRY(hipMemcpy(h->d_q_thr.get(), thr.data(), thr.size() * 4, hipMemcpyHostToDevice));
-    if (h->q_fixup_launch) {
-        if (!h->d_fq32) HIP_TRY(h->d_fq32.alloc(fq32.size() * 4));
-        HIP_TRY(hipMemcpy(h->d_fq32.get(), fq32.data(), fq32.size() * 4, hipMemcpyHostToDevice));
-    }
     h->shift_images_of.clear();
     h->filters.assign(f, f + (size_t)hpfw::kFilters * hpfw::kFrame);
     h->has_filters = true;

@@ -26,15 +26,17 @@
 //
 // The extraction's unshifted launches form only the six digit products of weight >= 2^16 (hashprint_q6_kernel) and settle
 // the few values whose sign those leave open in the same workgroup, from the digits still in its slab, before the
-// hashprints are stored: one launch, one pass over the spectrogram, hp written once (hashprint_q_tile, FUSED).
+// hashprints are stored: one launch, one pass over the spectrogram, hp written once.
+//
+// Every kernel here is hashprint_q_tile<FROM_T, SHIFTED, NP>, and a tile is its parts in this order: q_stage_slab (the digits
+// of Du into LDS), then per filter image q_matrix_loop<NP> (the digit products), q_epilogue<NP> (D, its sign bits, the open
+// values listed), for six products q_settle_open (the listed values from the slab), and q_pack.
 //
 // The slab is staged by chains: the 147 columns of Du need u of 227 columns, and a thread that holds u of column r, r + 80
 // and r + 160 forms Du[r] and Du[r + 80] from them, so every dB term is loaded and quantised once per workgroup (1816
 // column-units of 16 bins where a unit per slab column with its partner took 2352); the digit planes are gathered by
 // byte permutes, and a thread's five tasks keep the loads of two tasks in flight beyond the one it quantises.  Where a
 // clip's last tile is short, the short tiles of all clips are dispatched behind the full ones (q_tile_of_workgroup).
-// HPFW_Q_STAGING=classic at handle creation keeps the staging and the order as they were, to measure against
-// (CLASSIC; profiles/r10_q_staging.md).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -64,12 +66,11 @@ constexpr int kQSteps = 2 * kCtx;                             // 40 steps of 64 
 constexpr int kQLdsBytes = kQSlabBytes + kQTileN * 4 * 2;     // + the waves' 16-bit parts of every hashprint: 62 464, two workgroups per CU
 constexpr float kQScale = 98304.0f;
 // six-product split: open values listed per tile of 128 hashprints, kQCap 16-bit entries (r << 7 | n - n0) each
-// (in LDS; HPFW_Q_FIXUP=launch: in global segments, 4.9 MB for the 19 000 tiles of 1000 x 30 s clips), kQRedo in place of a
-// count above it
+// in LDS, kQRedo in place of a count above it
 constexpr int kQCap = 128;
 constexpr unsigned kQRedo = 0xffffffffu;
-constexpr int kQLdsBytes6 = kQLdsBytes + 16;                  // + the workgroup's count of open values
-constexpr int kQLdsBytes6f = kQLdsBytes6 + kQCap * 2;         // + its list of them (FUSED): 62 736, still two workgroups per CU
+constexpr int kQListAt = kQLdsBytes + 16;                     // behind the workgroup's count of open values:
+constexpr int kQLdsBytes6 = kQListAt + kQCap * 2;             // its list of them: 62 736, still two workgroups per CU
 
 // the three balanced base-256 digits of u as the three low bytes of one word (|u| < 2^23)
 __device__ __forceinline__ unsigned q_digit_bytes(int u) { return ((unsigned)u + 0x808080u) ^ 0x808080u; }
@@ -148,42 +149,261 @@ __device__ __forceinline__ long long q_value_from_digits(const v4i *__restrict__
     return v;
 }
 
-// FROM_T: sdb holds the dB terms t written by the chirp-z kernel; S = max(t - tmax[clip], -80) (convert.h:12-15)
-// rides on the staging loads.  fq_images: filter digit images one after the other, the slab staged once and each image
-// in turn running the matrix loop and the epilogue over it, hp [clip][image][nhp]: SHIFTED = false, the extraction's one
-// image; SHIFTED = true, n_images shifted ones (shift_filter_images_kernel).  dbg (tests only, NULL
-// in extraction; SHIFTED = false): D as int64 [clip][64][nhp].
+// ---- the parts of a tile, in the order hashprint_q_tile runs them.  tid, lane, wave, kg and cl are the tile's, handed
+// down: kg = lane >> 4, this lane's group of 16 k' inside a step, cl = lane & 15, its column (B) / filter (A) in a tile ----
+
+// The wave's filter digits of steps 0 and 1 of the image at img (this lane's unit of step 0) into the first two of the
+// matrix loop's three register sets
+__device__ __forceinline__ void q_load_first_steps(const v4i *img, v4i (&a)[3][3])
+{
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        a[0][d] = img[d * 64];
+        a[1][d] = img[(kQStepBytes / 16) + d * 64];
+    }
+}
+
+// Staging by chains: the digits of Du of the tile at column n0 of the clip at S [121][c] into the slab.  FROM_T: S holds dB
+// terms t and the spectrogram is max(t - ref, -80) (convert.h:12-15), the reference level riding on the loads.  NP = 6:
+// returns whether this thread stored a non-zero digit (the six-product kernel's shortcut for silence); else 0.
 //
-// NP = 9: the nine digit products, D exactly.  NP = 6 (SHIFTED = false, no dbg): only the six products of weight >= 2^16.
-// With fq = a0 + 2^8 a1 + 2^16 a2 and Du = b0 + 2^8 b1 + 2^16 b2, D = 2^16 Dp + Dl where
+// A task's half unit = 8 bins of one column of Du, three digit planes of 8 bytes.  EVERY load is issued, from a valid 32-bit
+// clip-relative index (S[0], S[kLag] exist), and what lies outside the valid part is zeroed afterwards: written as
+// `ok ? S[..] : 0` the loads sat in branches of their own, and the compiler, short of registers for so many merged values,
+// waited for all but one of the loads in flight after every fourth -- memory round trips in a row, and the staging took
+// as long as the matrix loop (tools/q_stamps.py: 69 k of a workgroup's 147 k cycles).  The loads of task i + kQAhead are
+// issued before task i is quantised: a wave waits for memory once, at its first task, and the accumulators' registers,
+// dead until the barrier, hold the values in flight
+template <bool FROM_T, int NP>
+__device__ __forceinline__ unsigned q_stage_slab(unsigned char *slab, const float *S, const float ref, const int n0, const int c, const int tid)
+{
+    unsigned any_digit = 0;
+    float x[kQTasks][3][8];
+    auto issue = [&](int i) {
+        const int task = tid + i * kQThreads, qh = task / kLag, r = task - qh * kLag;
+        const int gc = n0 + r;
+        const bool in0 = gc + kLag < c, in1 = r < kQHeavy && gc + 2 * kLag < c;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int bin = 8 * qh + e;
+            const unsigned at = (unsigned)(bin * c + gc); // (< 121 * c where it is used)
+            const unsigned i0 = in0 && bin < kBins ? at : 0u, i2 = in1 && bin < kBins ? at + 2 * kLag : 0u;
+            x[i][0][e] = S[i0];
+            x[i][1][e] = S[i0 + kLag];
+            x[i][2][e] = S[i2];
+        }
+    };
+    auto quantise = [&](int i) {
+        const int task = tid + i * kQThreads, qh = task / kLag, r = task - qh * kLag;
+        const int gc = n0 + r;
+        const bool in0 = gc + kLag < c, in1 = r < kQHeavy && gc + 2 * kLag < c;
+        unsigned wa[8], wb[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const bool okb = 8 * qh + e < kBins;
+            float x0 = x[i][0][e], x1 = x[i][1][e], x2 = x[i][2][e];
+            if (FROM_T) {
+                x0 -= ref;
+                x1 -= ref;
+                x2 -= ref;
+            }
+            const int u0 = q_fixed(x0), u1 = q_fixed(x1), u2 = q_fixed(x2);
+            wa[e] = q_digit_bytes(in0 && okb ? u0 - u1 : 0);
+            wb[e] = q_digit_bytes(in1 && okb ? u1 - u2 : 0);
+        }
+        // the half unit's place: chunk qh >> 1, bytes 8 (qh & 1) .. + 7 of each plane
+        unsigned char *dst = slab + (size_t)((qh >> 1) * kQPitch + r) * kQUnit + 8 * (qh & 1);
+        auto store = [&](const unsigned (&w)[8], unsigned char *to) {
+            unsigned lo[3], hi[3];
+            q_planes({w[0], w[1], w[2], w[3]}, lo);
+            q_planes({w[4], w[5], w[6], w[7]}, hi);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) *reinterpret_cast<v2i *>(to + 16 * j) = v2i{(int)lo[j], (int)hi[j]};
+            if (NP == 6) any_digit |= lo[0] | lo[1] | lo[2] | hi[0] | hi[1] | hi[2];
+        };
+        // column r + 80 of a chain without a second slab column (r >= 67) is one of the pitch's 13 spare columns 147 .. 159,
+        // which nothing reads: its zero digits are stored there without a branch (inside one, the compiler moved the
+        // third column's loads into it too, with a wait for everything in flight)
+        static_assert(kLag + kLag <= kQPitch, "spare columns for the chains' unconditional second store");
+        store(wa, dst);
+        store(wb, dst + (size_t)kLag * kQUnit);
+    };
+#pragma unroll
+    for (int i = 0; i < kQAhead && i < kQTasks; ++i) issue(i);
+#pragma unroll
+    for (int i = 0; i < kQTasks; ++i) {
+        if (i + kQAhead < kQTasks) issue(i + kQAhead);
+        __builtin_amdgcn_sched_barrier(0); // (the loads stay above the quantisation they are to hide under)
+        quantise(i);
+    }
+    return any_digit;
+}
+
+// The matrix loop: this wave's 16 filters of the image at img (steps 0 and 1 in a[0], a[1]) times the slab's columns, the
+// digit products of equal weight summed in acc[tile of 16 hashprints][weight].  NP = 9: all nine digit products; NP = 6: the
+// six of weight >= 2^16, accumulators 2 .. 4.  n_tiles: the tiles that hold hashprints; the products of the others are skipped
+template <int NP>
+__device__ __forceinline__ void q_matrix_loop(const v4i *img, v4i (&a)[3][3], const unsigned char *slab, const int kg, const int cl, const int n_tiles, v4i (&acc)[8][5])
+{
+    // B operand of (step, tile f): chunk 4 (s & 1) + kg, column 16 f + cl + (s >> 1)
+    const unsigned char *bl = slab + (size_t)(kg * kQPitch + cl) * kQUnit;
+#pragma unroll
+    for (int f = 0; f < 8; ++f)
+#pragma unroll
+        for (int cls = 0; cls < 5; ++cls) acc[f][cls] = v4i{0, 0, 0, 0};
+    auto step = [&](int s, const v4i (&aw)[3]) {
+        const unsigned char *bs = bl + (size_t)((4 * (s & 1)) * kQPitch + (s >> 1)) * kQUnit;
+        // the operand reads of tile f + 1 are issued BEFORE the nine products of tile f: read right where they are used, a
+        // wave alone on its SIMD left the matrix pipe idle for an LDS round trip per tile (tools/q_stamps.py: 46 k cycles of
+        // matrix instructions in a 69 k cycle loop)
+        v4i nb0, nb1, nb2;
+        {
+            const v4i *bu = reinterpret_cast<const v4i *>(bs);
+            nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
+        }
+#pragma unroll
+        for (int f = 0; f < 8; ++f) {
+            if (f < n_tiles) {
+                const v4i b0 = nb0, b1 = nb1, b2 = nb2;
+                if (f + 1 < 8) { // (tile f + 1 of the slab exists whether or not it holds hashprints)
+                    const v4i *bu = reinterpret_cast<const v4i *>(bs + (size_t)(16 * (f + 1)) * kQUnit);
+                    nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
+                }
+                __builtin_amdgcn_sched_barrier(0); // (the scheduler would sink the reads back to where they are used)
+                // filter digit i times spectrogram digit j goes to accumulator i + j
+                if (NP == 9) {
+                    acc[f][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b0, acc[f][0], 0, 0, 0);
+                    acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b1, acc[f][1], 0, 0, 0);
+                }
+                acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b2, acc[f][2], 0, 0, 0);
+                acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b2, acc[f][3], 0, 0, 0);
+                acc[f][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b2, acc[f][4], 0, 0, 0);
+                if (NP == 9) acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b0, acc[f][1], 0, 0, 0);
+                acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b1, acc[f][2], 0, 0, 0);
+                acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b1, acc[f][3], 0, 0, 0);
+                acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b0, acc[f][2], 0, 0, 0);
+            }
+        }
+    };
+    // three register sets in turn: the loads of step s + 2 are issued before the products of step s
+    auto load_a = [&](int s, v4i (&aw)[3]) {
+        if (s < kQSteps) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) aw[d] = img[(size_t)s * (kQStepBytes / 16) + d * 64];
+        }
+    };
+    if (n_tiles > 0) {
+#pragma unroll 1
+        for (int s = 0; s < kQSteps - 1; s += 3) { // 40 steps = 13 x 3 + 1
+            load_a(s + 2, a[2]);
+            step(s, a[0]);
+            load_a(s + 3, a[0]);
+            step(s + 1, a[1]);
+            load_a(s + 4, a[1]);
+            step(s + 2, a[2]);
+        }
+        step(kQSteps - 1, a[0]);
+    }
+}
+
+// The epilogue (S10q): D = sum_c acc_c 2^(8c), its sign bits to parts [hashprint][wave].  D layout of the 16x16 tile:
+// column (hashprint) = lane & 15, row (filter) = 4 (lane >> 4) + reg.  DBG: dbg may be given, D [clip][64][nhp] (tests; the unshifted nine-product kernel).
+// A flag of its own: with a pointer that is known to be NULL only once everything is inlined, the shifted kernels took two
+// registers more and the six-product kernels four (profiles/q_kernel_single_path.md).
+//
+// NP = 6: with fq = a0 + 2^8 a1 + 2^16 a2 and Du = b0 + 2^8 b1 + 2^16 b2, D = 2^16 Dp + Dl where
 //   Dp = sum (a0 b2 + a1 b1 + a2 b0) + 2^8 sum (a1 b2 + a2 b1) + 2^16 sum a2 b2      (accumulators 2, 3, 4)
 //   Dl = sum a0 b0 + 2^8 sum (a0 b1 + a1 b0)                                          (accumulators 0, 1)
 // and every |b| <= 128, so |Dl| <= 128 S0_r + 2^8 128 (S0_r + S1_r) = Lmax_r with S0_r, S1_r the sums of |a0| and |a1| over
 // row r's 2420 taps.  Where 2^16 |Dp| > Lmax_r the sign of D is the sign of Dp (and D != 0); a row with Lmax_r = 0 has
-// D = 2^16 Dp exactly.  Else the value is OPEN: the bit from Dp >= 0 stands for the moment and D is formed exactly.
-// thr[r] = floor(Lmax_r / 2^16), or -1 for Lmax_r = 0: open iff |Dp| <= thr[r] (pack_filters_q).  The workgroup writes
-// counts[t] = its number of open values, or kQRedo above kQCap; without FUSED (HPFW_Q_FIXUP=launch) also their entries,
-// up to kQCap, to seg[t][..] for hashprint_q_fixup_kernel.  A slab of zero digits (silence, the -80 dB floor) has D = 0
-// everywhere: all bits one, count 0.
+// D = 2^16 Dp exactly.  Else the value is OPEN: the bit from Dp >= 0 stands for the moment, and the value is counted in
+// *n_open and, up to kQCap of them, listed as (r << 7 | n - n0) for q_settle_open.  thr[r] = floor(Lmax_r / 2^16), or -1
+// for Lmax_r = 0: open iff |Dp| <= thr[r] (pack_filters_q)
+template <int NP, bool DBG>
+__device__ __forceinline__ void q_epilogue(const v4i (&acc)[8][5], const int clip, const int n0, const int nhp, const int n_tiles,
+                                           unsigned short *parts, const int *thr, unsigned *n_open, unsigned short *list,
+                                           long long *dbg, const int wave, const int kg, const int cl)
+{
+    v4i th = v4i{-1, -1, -1, -1};
+    if (NP == 6) th = *reinterpret_cast<const v4i *>(thr + 16 * wave + 4 * kg);
+#pragma unroll
+    for (int f = 0; f < 8; ++f) {
+        const int n = n0 + 16 * f + cl;
+        (void)n;
+        unsigned bits = 0; // this wave's 16 filters of hashprint n, filter 16 wave + row at bit 15 - row
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int row = 4 * kg + reg;
+            long long v = acc[f][4][reg];
+#pragma unroll
+            for (int cls = 3; cls >= (NP == 9 ? 0 : 2); --cls) v = v * 256 + acc[f][cls][reg]; // (NP = 6: Dp)
+            bits |= (unsigned)(v >= 0) << (15 - row);
+            if (NP == 6 && f < n_tiles && n < nhp && (v < 0 ? -v : v) <= (long long)th[reg]) {
+                const unsigned pos = atomicAdd(n_open, 1u);
+                if (pos < (unsigned)kQCap) list[pos] = (unsigned short)(((16 * wave + row) << 7) | (16 * f + cl));
+            }
+#if !defined(HPFW_Q_STAMPS)
+            if (DBG && dbg && f < n_tiles && n < nhp) dbg[((int64_t)clip * kFilters + 16 * wave + row) * nhp + n] = v;
+#endif
+        }
+        // the four lanes of a column hold four filters each
+        bits |= (unsigned)__shfl_xor((int)bits, 16);
+        bits |= (unsigned)__shfl_xor((int)bits, 32);
+        if (kg == 0) parts[(16 * f + cl) * 4 + wave] = (unsigned short)bits;
+    }
+}
+
+// Settling the cnt listed open values, behind the barrier that ends the epilogue: every wave takes each fourth entry,
+// forms D from the digits of the filter image and of the slab (q_value_from_digits) and flips the bit in `parts` where
+// D >= 0 disagrees with it
+__device__ __forceinline__ void q_settle_open(const v4i *fq_image, const unsigned char *slab, unsigned short *parts,
+                                              const unsigned short *list, const unsigned cnt, const int wave, const int lane)
+{
+    for (unsigned e = (unsigned)__builtin_amdgcn_readfirstlane(wave); e < cnt; e += kQThreads / 64) {
+        const int entry = __builtin_amdgcn_readfirstlane((int)list[e]);
+        const int r = entry >> 7, nl = entry & 127;
+        const long long d = q_value_from_digits(fq_image, slab, r, nl, lane);
+        if (lane == 0) { // parts[nl * 4 + (r >> 4)], filter r at bit 15 - (r & 15) of it: two waves can meet in one word
+            unsigned *w = reinterpret_cast<unsigned *>(parts) + nl * 2 + (r >> 5);
+            const unsigned bit = 1u << (16 * ((r >> 4) & 1) + 15 - (r & 15));
+            if (((*static_cast<volatile unsigned *>(w) & bit) != 0) != (d >= 0)) atomicXor(w, bit);
+        }
+    }
+}
+
+// The pack: the four waves' parts of the tile's hashprints n0 .. to hp[first + n0 ..] (first: where the clip's row of
+// this image begins), one 64-bit word each
+__device__ __forceinline__ void q_pack(const unsigned short *parts, uint64_t *hp, const int64_t first, const int n0, const int nhp, const int tid)
+{
+    if (tid < kQTileN && n0 + tid < nhp) {
+        const unsigned short *p = parts + tid * 4;
+        hp[first + n0 + tid] = ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
+    }
+}
+
+// One tile t = clip * n_tiles_x + tile of 128 hashprints: stage the slab, then per filter image the matrix loop, the
+// epilogue and the pack.  FROM_T: sdb holds the dB terms t written by the chirp-z kernel and tmax the clips' reference
+// levels (q_stage_slab).  fq_images: filter digit images one after the other, the slab staged once and each image in turn
+// running over it, hp [clip][image][nhp]: SHIFTED = false, the extraction's one image; SHIFTED = true, n_images shifted
+// ones (shift_filter_images_kernel).  dbg (tests only, NULL in extraction; SHIFTED = false): D as
+// int64 [clip][64][nhp].
 //
-// FUSED (NP = 6, the extraction's default): the workgroup settles its open values itself, before it packs.  The entries go
-// to a list in LDS; behind the barrier that ends the epilogue every wave takes each fourth entry, forms D from the digits
-// of the filter image and of the slab (q_value_from_digits) and flips the bit in `parts` where D >= 0 disagrees with it.
-// A workgroup with more than kQCap open values (near-stationary input) runs the nine-product body over its slab instead
-// (STAGED: the body entered behind the staging, the six-product accumulators dead by then).  hp is written once and final;
-// neither a second launch nor a second pass over the spectrogram follows.  counts[t] keeps its meaning.
-template <bool FROM_T, bool SHIFTED, int NP, bool CLASSIC, bool FUSED = false, bool STAGED = false>
+// NP = 9: the nine digit products, D exactly.  NP = 6 (hashprint_q6_kernel: the unshifted image, no dbg): the six products
+// of weight >= 2^16, and the workgroup settles the values whose sign those leave open itself, before it packs
+// (q_epilogue, q_settle_open).  A workgroup with more than kQCap open values (near-stationary input) runs the nine-product
+// matrix loop and epilogue over its slab instead, the six-product accumulators dead by then.  hp is written once and
+// final.  counts[t] = the tile's number of open values, or kQRedo above kQCap.  A slab of zero digits (silence, the -80 dB
+// floor) has D = 0 everywhere: all bits one, count 0, and no product is formed.
+template <bool FROM_T, bool SHIFTED, int NP>
 __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
                                                  const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, uint64_t *__restrict__ hp,
                                                  long long *__restrict__ dbg, int n_images, const int *__restrict__ thr,
-                                                 unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
+                                                 unsigned *__restrict__ counts)
 {
-    static_assert(NP == 9 || (NP == 6 && !SHIFTED), "six products: the extraction's unshifted image only");
-    static_assert((!FUSED || NP == 6) && (!STAGED || (NP == 9 && !SHIFTED)), "FUSED: six products; STAGED: its nine-product redo");
     unsigned char *slab = smem_raw;                                   // [chunk][column (pitch 160)][digit][16]
     unsigned short *parts = reinterpret_cast<unsigned short *>(smem_raw + kQSlabBytes); // [hashprint][wave]
     unsigned *n_open = reinterpret_cast<unsigned *>(smem_raw + kQLdsBytes);             // (NP = 6)
-    unsigned short *list = reinterpret_cast<unsigned short *>(smem_raw + kQLdsBytes6);  // (FUSED) kQCap entries
+    unsigned short *list = reinterpret_cast<unsigned short *>(smem_raw + kQListAt);     // (NP = 6) kQCap entries
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kg = lane >> 4, cl = lane & 15;  // this lane's group of 16 k' inside a step; its column (B) / filter (A) in a tile
     const int clip = t / n_tiles_x;
@@ -201,149 +421,12 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
     const float ref = FROM_T ? tmax[clip] : 0.0f;
     // the wave's filter digits of the first two steps are on their way while the slab is quantised
     const v4i *img = fq_images + (size_t)wave * kQSteps * (kQStepBytes / 16) + lane;
-    v4i a[3][3]; // three register sets in turn: the loads of step s + 2 are issued before the products of step s
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        a[0][d] = img[d * 64];
-        a[1][d] = img[(kQStepBytes / 16) + d * 64];
-    }
-    unsigned any_digit = 0; // (NP = 6) whether this thread stored a non-zero digit
-    if constexpr (!CLASSIC && !STAGED) { // (STAGED: the caller's slab stands)
-        // slab: a task's half unit = 8 bins of one column of Du, three digit planes of 8 bytes.  Every load is issued, from a valid
-        // 32-bit clip-relative index (S[0], S[kLag] exist), and what lies outside the valid part is zeroed afterwards (as in the
-        // classic staging below).  The loads of task i + kQAhead are issued before task i is quantised: a wave waits for
-        // memory once, at its first task, and the accumulators' registers, dead until the barrier, hold the values in flight
-        float x[kQTasks][3][8];
-        auto issue = [&](int i) {
-            const int task = tid + i * kQThreads, qh = task / kLag, r = task - qh * kLag;
-            const int gc = n0 + r;
-            const bool in0 = gc + kLag < c, in1 = r < kQHeavy && gc + 2 * kLag < c;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int bin = 8 * qh + e;
-                const unsigned at = (unsigned)(bin * c + gc); // (< 121 * c where it is used)
-                const unsigned i0 = in0 && bin < kBins ? at : 0u, i2 = in1 && bin < kBins ? at + 2 * kLag : 0u;
-                x[i][0][e] = S[i0];
-                x[i][1][e] = S[i0 + kLag];
-                x[i][2][e] = S[i2];
-            }
-        };
-        auto quantise = [&](int i) {
-            const int task = tid + i * kQThreads, qh = task / kLag, r = task - qh * kLag;
-            const int gc = n0 + r;
-            const bool in0 = gc + kLag < c, in1 = r < kQHeavy && gc + 2 * kLag < c;
-            unsigned wa[8], wb[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool okb = 8 * qh + e < kBins;
-                float x0 = x[i][0][e], x1 = x[i][1][e], x2 = x[i][2][e];
-                if (FROM_T) {
-                    x0 -= ref;
-                    x1 -= ref;
-                    x2 -= ref;
-                }
-                const int u0 = q_fixed(x0), u1 = q_fixed(x1), u2 = q_fixed(x2);
-                wa[e] = q_digit_bytes(in0 && okb ? u0 - u1 : 0);
-                wb[e] = q_digit_bytes(in1 && okb ? u1 - u2 : 0);
-            }
-            // the half unit's place: chunk qh >> 1, bytes 8 (qh & 1) .. + 7 of each plane
-            unsigned char *dst = slab + (size_t)((qh >> 1) * kQPitch + r) * kQUnit + 8 * (qh & 1);
-            auto store = [&](const unsigned (&w)[8], unsigned char *to) {
-                unsigned lo[3], hi[3];
-                q_planes({w[0], w[1], w[2], w[3]}, lo);
-                q_planes({w[4], w[5], w[6], w[7]}, hi);
-#pragma unroll
-                for (int j = 0; j < 3; ++j) *reinterpret_cast<v2i *>(to + 16 * j) = v2i{(int)lo[j], (int)hi[j]};
-                if (NP == 6) any_digit |= lo[0] | lo[1] | lo[2] | hi[0] | hi[1] | hi[2];
-            };
-            // column r + 80 of a chain without a second slab column (r >= 67) is one of the pitch's 13 spare columns 147 .. 159,
-            // which nothing reads: its zero digits are stored there without a branch (inside one, the compiler moved the
-            // third column's loads into it too, with a wait for everything in flight)
-            static_assert(kLag + kLag <= kQPitch, "spare columns for the chains' unconditional second store");
-            store(wa, dst);
-            store(wb, dst + (size_t)kLag * kQUnit);
-        };
-#pragma unroll
-        for (int i = 0; i < kQAhead && i < kQTasks; ++i) issue(i);
-#pragma unroll
-        for (int i = 0; i < kQTasks; ++i) {
-            if (i + kQAhead < kQTasks) issue(i + kQAhead);
-            __builtin_amdgcn_sched_barrier(0); // (the loads stay above the quantisation they are to hide under)
-            quantise(i);
-        }
-    }
-    // The classic staging (HPFW_Q_STAGING=classic, kept to measure against; no trip otherwise): one (chunk, column) unit =
-    // 16 bins of one column of Du, three digit planes, from the column and its partner 80 on -- every column n0 + 80 ..
-    // n0 + 146 is loaded and quantised twice.  The loads of a round are all issued before the first value is quantised,
-    // and the three rounds follow one another
-    constexpr int kUnits = (kQChunks * kQCols + kQThreads - 1) / kQThreads; // 5
-#pragma unroll 1
-    for (int r0 = STAGED || !CLASSIC ? kUnits : 0; r0 < kUnits; r0 += 2) { // (STAGED: the caller's slab stands, no trip)
-        float va[2][16], vb[2][16];
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int unit = tid + (r0 + rr) * kQThreads;
-            const int q = unit / kQCols, col = unit - q * kQCols;
-            const int gc = n0 + col;
-            const bool in = r0 + rr < kUnits && unit < kQChunks * kQCols && gc + kLag < c;
-            // EVERY load is issued, from a valid address, and what lies outside the slab is zeroed afterwards: written as
-            // `ok ? S[..] : 0` the loads sat in 64 branches of their own, and the compiler, short of registers for so many
-            // merged values, waited for all but one of the loads in flight after every fourth -- seven memory round trips
-            // in a row per round, 21 per workgroup: the staging took as long as the matrix loop (tools/q_stamps.py:
-            // 69 k of a workgroup's 147 k cycles)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int bin = 16 * q + e;
-                const bool ok = in && bin < kBins;
-                const unsigned idx = ok ? (unsigned)(bin * c + gc) : 0u; // (clip-relative: < 121 * c, 32 bits; S[0] and S[kLag] exist)
-                va[rr][e] = S[idx];
-                vb[rr][e] = S[idx + kLag];
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int unit = tid + (r0 + rr) * kQThreads;
-            const int q = unit / kQCols, col = unit - q * kQCols;
-            const bool in = r0 + rr < kUnits && unit < kQChunks * kQCols && n0 + col + kLag < c;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const bool ok = in && 16 * q + e < kBins;
-                va[rr][e] = ok ? va[rr][e] : 0.0f;
-                vb[rr][e] = ok ? vb[rr][e] : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int unit = tid + (r0 + rr) * kQThreads;
-            if (r0 + rr >= kUnits || unit >= kQChunks * kQCols) break;
-            const int q = unit / kQCols, col = unit - q * kQCols;
-            unsigned w0[4] = {0, 0, 0, 0}, w1[4] = {0, 0, 0, 0}, w2[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float xa = va[rr][e], xb = vb[rr][e];
-                if (FROM_T) {
-                    xa -= ref;
-                    xb -= ref;
-                }
-                // (values outside the slab's valid part were loaded as 0 on both sides: Du = 0, digits 0)
-                const unsigned d = q_digit_bytes(q_fixed(xa) - q_fixed(xb));
-                w0[e >> 2] |= (d & 255u) << (8 * (e & 3));
-                w1[e >> 2] |= ((d >> 8) & 255u) << (8 * (e & 3));
-                w2[e >> 2] |= ((d >> 16) & 255u) << (8 * (e & 3));
-            }
-            v4i *dst = reinterpret_cast<v4i *>(slab + (size_t)(q * kQPitch + col) * kQUnit);
-            dst[0] = v4i{(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3]};
-            dst[1] = v4i{(int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
-            dst[2] = v4i{(int)w2[0], (int)w2[1], (int)w2[2], (int)w2[3]};
-            if (NP == 6)
-                any_digit |= w0[0] | w0[1] | w0[2] | w0[3] | w1[0] | w1[1] | w1[2] | w1[3] | w2[0] | w2[1] | w2[2] | w2[3];
-        }
-    }
+    v4i a[3][3];
+    q_load_first_steps(img, a);
+    const unsigned any_digit = q_stage_slab<FROM_T, NP>(slab, S, ref, n0, c, tid);
     Q_STAMP(1);
     // the only barrier before the epilogue: the slab is read-only from here on
-    if (STAGED) {
-        // (the caller is behind this barrier and behind the one of its own epilogue)
-    } else if (NP == 6) {
+    if (NP == 6) {
         if (!__syncthreads_or((int)(any_digit != 0))) { // Du = 0 in the whole slab: D = 0, every bit one, nothing open
             if (tid < kQTileN && n0 + tid < nhp) hp[(int64_t)clip * nhp + n0 + tid] = ~0ull;
             if (tid == 0) counts[t] = 0;
@@ -353,10 +436,8 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
         __syncthreads();
     }
     Q_STAMP(2);
-    // tiles of 16 hashprints that hold any (the last workgroup of a clip); the products of the others are skipped
+    // tiles of 16 hashprints that hold any (the last workgroup of a clip)
     const int n_tiles = min(8, (nhp - n0 + 15) / 16);
-    // B operand of (step, tile f): chunk 4 (s & 1) + kg, column 16 f + cl + (s >> 1)
-    const unsigned char *bl = slab + (size_t)(kg * kQPitch + cl) * kQUnit;
     // one trip per image over the same slab, the first two steps' digits of image im in a[0] and a[1].  The extraction's
     // instance is compiled without a loop (the condition folds to false before any optimisation): with a loop, even of
     // one trip known at compile time, the compiler allocated its registers differently (16 more waits for memory in
@@ -367,134 +448,37 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
         if (SHIFTED && im > 0) {
             __syncthreads(); // (parts is written again by this image's epilogue)
             img += (size_t)4 * kQSteps * kQStepBytes / 16;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                a[0][d] = img[d * 64];
-                a[1][d] = img[(kQStepBytes / 16) + d * 64];
-            }
+            q_load_first_steps(img, a);
         }
         v4i acc[8][5];
-#pragma unroll
-        for (int f = 0; f < 8; ++f)
-#pragma unroll
-            for (int cls = 0; cls < 5; ++cls) acc[f][cls] = v4i{0, 0, 0, 0};
-        auto step = [&](int s, const v4i (&aw)[3]) {
-            const unsigned char *bs = bl + (size_t)((4 * (s & 1)) * kQPitch + (s >> 1)) * kQUnit;
-            // the operand reads of tile f + 1 are issued BEFORE the nine products of tile f: read right where they are used, a
-            // wave alone on its SIMD left the matrix pipe idle for an LDS round trip per tile (tools/q_stamps.py: 46 k cycles of
-            // matrix instructions in a 69 k cycle loop)
-            v4i nb0, nb1, nb2;
-            {
-                const v4i *bu = reinterpret_cast<const v4i *>(bs);
-                nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
-            }
-#pragma unroll
-            for (int f = 0; f < 8; ++f) {
-                if (f < n_tiles) {
-                    const v4i b0 = nb0, b1 = nb1, b2 = nb2;
-                    if (f + 1 < 8) { // (tile f + 1 of the slab exists whether or not it holds hashprints)
-                        const v4i *bu = reinterpret_cast<const v4i *>(bs + (size_t)(16 * (f + 1)) * kQUnit);
-                        nb0 = bu[0], nb1 = bu[1], nb2 = bu[2];
-                    }
-                    __builtin_amdgcn_sched_barrier(0); // (the scheduler would sink the reads back to where they are used)
-                    // filter digit i times spectrogram digit j goes to accumulator i + j
-                    if (NP == 9) {
-                        acc[f][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b0, acc[f][0], 0, 0, 0);
-                        acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b1, acc[f][1], 0, 0, 0);
-                    }
-                    acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[0], b2, acc[f][2], 0, 0, 0);
-                    acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b2, acc[f][3], 0, 0, 0);
-                    acc[f][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b2, acc[f][4], 0, 0, 0);
-                    if (NP == 9) acc[f][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b0, acc[f][1], 0, 0, 0);
-                    acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[1], b1, acc[f][2], 0, 0, 0);
-                    acc[f][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b1, acc[f][3], 0, 0, 0);
-                    acc[f][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[2], b0, acc[f][2], 0, 0, 0);
-                }
-            }
-        };
-        auto load_a = [&](int s, v4i (&aw)[3]) {
-            if (s < kQSteps) {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) aw[d] = img[(size_t)s * (kQStepBytes / 16) + d * 64];
-            }
-        };
-        if (n_tiles > 0) {
-#pragma unroll 1
-            for (int s = 0; s < kQSteps - 1; s += 3) { // 40 steps = 13 x 3 + 1
-                load_a(s + 2, a[2]);
-                step(s, a[0]);
-                load_a(s + 3, a[0]);
-                step(s + 1, a[1]);
-                load_a(s + 4, a[1]);
-                step(s + 2, a[2]);
-            }
-            step(kQSteps - 1, a[0]);
-        }
+        q_matrix_loop<NP>(img, a, slab, kg, cl, n_tiles, acc);
         Q_STAMP(3);
-        // S10q: D = sum_c acc_c 2^(8c); D layout of the 16x16 tile: column (hashprint) = lane & 15, row (filter) = 4 (lane >> 4) + reg
-        v4i th = v4i{-1, -1, -1, -1};
-        if (NP == 6) th = *reinterpret_cast<const v4i *>(thr + 16 * wave + 4 * kg);
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            const int n = n0 + 16 * f + cl;
-            (void)n;
-            unsigned bits = 0; // this wave's 16 filters of hashprint n, filter 16 wave + row at bit 15 - row
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int row = 4 * kg + reg;
-                long long v = acc[f][4][reg];
-#pragma unroll
-                for (int cls = 3; cls >= (NP == 9 ? 0 : 2); --cls) v = v * 256 + acc[f][cls][reg]; // (NP = 6: Dp)
-                bits |= (unsigned)(v >= 0) << (15 - row);
-                if (NP == 6 && f < n_tiles && n < nhp && (v < 0 ? -v : v) <= (long long)th[reg]) {
-                    const unsigned pos = atomicAdd(n_open, 1u);
-                    if (pos < (unsigned)kQCap)
-                        (FUSED ? list : seg + (size_t)t * kQCap)[pos] = (unsigned short)(((16 * wave + row) << 7) | (16 * f + cl));
-                }
-#if !defined(HPFW_Q_STAMPS)
-                if (!SHIFTED && dbg && f < n_tiles && n < nhp) dbg[((int64_t)clip * kFilters + 16 * wave + row) * nhp + n] = v;
-#endif
-            }
-            // the four lanes of a column hold four filters each
-            bits |= (unsigned)__shfl_xor((int)bits, 16);
-            bits |= (unsigned)__shfl_xor((int)bits, 32);
-            if (kg == 0) parts[(16 * f + cl) * 4 + wave] = (unsigned short)bits;
-        }
+        q_epilogue<NP, NP == 9 && !SHIFTED>(acc, clip, n0, nhp, n_tiles, parts, thr, n_open, list, dbg, wave, kg, cl);
         Q_STAMP(4);
         __syncthreads();
-        if (FUSED) {
+        if (NP == 6) {
             const unsigned cnt = *n_open; // (the same for the whole workgroup; nothing adds to it behind the barrier)
-            if (cnt > (unsigned)kQCap) {
+            if (cnt > (unsigned)kQCap) { // the redo: nine products over the slab as it stands
                 if (tid == 0) counts[t] = kQRedo;
-                hashprint_q_tile<FROM_T, false, 9, CLASSIC, false, true>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr,
-                                                                         nullptr);
+                q_load_first_steps(img, a);
+                q_matrix_loop<9>(img, a, slab, kg, cl, n_tiles, acc);
+                q_epilogue<9, false>(acc, clip, n0, nhp, n_tiles, parts, nullptr, nullptr, nullptr, nullptr, wave, kg, cl);
+                __syncthreads();
+                q_pack(parts, hp, (int64_t)clip * nhp, n0, nhp, tid);
                 return;
             }
             if (cnt > 0) {
-                for (unsigned e = (unsigned)__builtin_amdgcn_readfirstlane(wave); e < cnt; e += kQThreads / 64) {
-                    const int entry = __builtin_amdgcn_readfirstlane((int)list[e]);
-                    const int r = entry >> 7, nl = entry & 127;
-                    const long long d = q_value_from_digits(fq_images, slab, r, nl, lane);
-                    if (lane == 0) { // parts[nl * 4 + (r >> 4)], filter r at bit 15 - (r & 15) of it: two waves can meet in one word
-                        unsigned *w = reinterpret_cast<unsigned *>(parts) + nl * 2 + (r >> 5);
-                        const unsigned bit = 1u << (16 * ((r >> 4) & 1) + 15 - (r & 15));
-                        if (((*static_cast<volatile unsigned *>(w) & bit) != 0) != (d >= 0)) atomicXor(w, bit);
-                    }
-                }
+                q_settle_open(fq_images, slab, parts, list, cnt, wave, lane);
                 __syncthreads();
             }
         }
-        if (tid < kQTileN && n0 + tid < nhp) {
-            const unsigned short *p = parts + tid * 4;
-            hp[((int64_t)clip * (SHIFTED ? n_images : 1) + im) * nhp + n0 + tid] =
-                ((uint64_t)p[0] << 48) | ((uint64_t)p[1] << 32) | ((uint64_t)p[2] << 16) | (uint64_t)p[3];
-        }
+        q_pack(parts, hp, ((int64_t)clip * (SHIFTED ? n_images : 1) + im) * nhp, n0, nhp, tid);
         if (NP == 6 && tid == 0) counts[t] = *n_open <= (unsigned)kQCap ? *n_open : kQRedo;
     } while (SHIFTED && ++im < n_images);
 #if defined(HPFW_Q_STAMPS)
     Q_STAMP(5);
     long long *stamps = dbg ? dbg : g_q_stamps_dev;
-    if (stamps && tid == 0 && !STAGED) {
+    if (stamps && tid == 0) {
         for (int k = 0; k < 6; ++k) stamps[(int64_t)t * 8 + k] = st[k];
         stamps[(int64_t)t * 8 + 6] = __builtin_amdgcn_s_getreg((15 << 11) | 4); // HW_ID: wave, SIMD, CU, SH, SE
         stamps[(int64_t)t * 8 + 7] = blockIdx.x;
@@ -510,22 +494,21 @@ __device__ __forceinline__ void hashprint_q_tile(const unsigned t, const v4i *__
 // workgroup stages a whole slab for a fraction of the matrix work, and a workgroup that starts in the launch's last
 // generation runs its whole life on a nearly empty chip.  The full tiles then come first, in the order above, and the
 // clips' short tiles after them, each XCD again with a contiguous run: the launch ends on short workgroups.  The
-// logical tile t = clip * n_tiles_x + tile (counts, seg, hp, dbg) does not change.  CLASSIC: the one order for all.
+// logical tile t = clip * n_tiles_x + tile (counts, hp, dbg) does not change.
 constexpr unsigned kQNoTile = 0xffffffffu;
 __host__ __device__ inline bool q_short_last(int nhp, int n_tiles_x) { return nhp - (n_tiles_x - 1) * kQTileN <= kQTileN - 16; }
 __host__ __device__ inline unsigned q_round8(unsigned n) { return 8 * ((n + 7) / 8); }
 
-static unsigned q_grid(bool classic, int nhp, int n_tiles_x, int n_clips)
+static unsigned q_grid(int nhp, int n_tiles_x, int n_clips)
 {
-    if (classic || !q_short_last(nhp, n_tiles_x)) return q_round8((unsigned)n_tiles_x * (unsigned)n_clips);
+    if (!q_short_last(nhp, n_tiles_x)) return q_round8((unsigned)n_tiles_x * (unsigned)n_clips);
     return q_round8((unsigned)(n_tiles_x - 1) * (unsigned)n_clips) + q_round8((unsigned)n_clips);
 }
 
-template <bool CLASSIC>
 __device__ __forceinline__ unsigned q_tile_of_workgroup(int nhp, int n_tiles_x, int n_clips)
 {
     unsigned b = blockIdx.x;
-    if (CLASSIC || !q_short_last(nhp, n_tiles_x)) {
+    if (!q_short_last(nhp, n_tiles_x)) {
         const unsigned t = (b & 7) * (gridDim.x / 8) + (b >> 3);
         return t < (unsigned)(n_tiles_x * n_clips) ? t : kQNoTile;
     }
@@ -541,92 +524,27 @@ __device__ __forceinline__ unsigned q_tile_of_workgroup(int nhp, int n_tiles_x, 
     return j < (unsigned)n_clips ? j * (unsigned)n_tiles_x + full_x : kQNoTile;
 }
 
-template <bool FROM_T, bool SHIFTED, bool CLASSIC>
+template <bool FROM_T, bool SHIFTED>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q_kernel(const v4i *__restrict__ fq_images, const float *__restrict__ sdb,
                                                                    const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
                                                                    uint64_t *__restrict__ hp, long long *__restrict__ dbg, int n_images)
 {
-    const unsigned t = q_tile_of_workgroup<CLASSIC>(nhp, n_tiles_x, n_clips);
+    const unsigned t = q_tile_of_workgroup(nhp, n_tiles_x, n_clips);
     if (t == kQNoTile) return;
-    hashprint_q_tile<FROM_T, SHIFTED, 9, CLASSIC>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, dbg, n_images, nullptr, nullptr, nullptr);
+    hashprint_q_tile<FROM_T, SHIFTED, 9>(t, fq_images, sdb, tmax, c, nhp, n_tiles_x, hp, dbg, n_images, nullptr, nullptr);
 }
 
-// the six-product instantiation of the extraction's kernel (hashprint_q_tile, FUSED): bits from Dp, the open values
+// the six-product instantiation of the extraction's kernel (hashprint_q_tile, NP = 6): bits from Dp, the open values
 // settled from the slab before the hashprints are stored
-template <bool FROM_T, bool CLASSIC>
+template <bool FROM_T>
 __global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
                                                                     const float *__restrict__ tmax, int c, int nhp, int n_tiles_x, int n_clips,
                                                                     uint64_t *__restrict__ hp, const int *__restrict__ thr,
                                                                     unsigned *__restrict__ counts)
 {
-    const unsigned t = q_tile_of_workgroup<CLASSIC>(nhp, n_tiles_x, n_clips);
+    const unsigned t = q_tile_of_workgroup(nhp, n_tiles_x, n_clips);
     if (t == kQNoTile) return;
-    hashprint_q_tile<FROM_T, false, 6, CLASSIC, true>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, nullptr);
-}
-
-// HPFW_Q_FIXUP=launch (kept to measure against): the six-product kernel that lists the open values in global segments for
-// hashprint_q_fixup_kernel
-template <bool FROM_T, bool CLASSIC>
-__global__ __launch_bounds__(kQThreads, 2) void hashprint_q6_listed_kernel(const v4i *__restrict__ fq_image, const float *__restrict__ sdb,
-                                                                           const float *__restrict__ tmax, int c, int nhp, int n_tiles_x,
-                                                                           int n_clips, uint64_t *__restrict__ hp, const int *__restrict__ thr,
-                                                                           unsigned *__restrict__ counts, unsigned short *__restrict__ seg)
-{
-    const unsigned t = q_tile_of_workgroup<CLASSIC>(nhp, n_tiles_x, n_clips);
-    if (t == kQNoTile) return;
-    hashprint_q_tile<FROM_T, false, 6, CLASSIC>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts, seg);
-}
-
-// The fix-up of a hashprint_q6_listed_kernel launch, after it on the same stream: workgroups take the tiles in turn.  A tile with
-// listed open values: one wave per entry (r, n) forms D[r][n] = sum_k fq[r][k] Du[k / 20][n + k % 20] exactly in int64
-// -- fq32 [64][2420], Du from the dB terms as the staging quantises them -- and flips bit 63 - r of hp[n] where D >= 0
-// disagrees with it.  A tile marked kQRedo: the nine-product body over the whole tile, always with the classic staging (the
-// same slab): inside this loop the chains' values in flight did not fit the registers (49 spilled, 7 as it is).
-template <bool FROM_T>
-__global__ __launch_bounds__(kQThreads, 2) void hashprint_q_fixup_kernel(const v4i *__restrict__ fq_image, const int *__restrict__ fq32,
-                                                                         const float *__restrict__ sdb, const float *__restrict__ tmax, int c,
-                                                                         int nhp, int n_tiles_x, int n_clips, uint64_t *__restrict__ hp,
-                                                                         const unsigned *__restrict__ counts,
-                                                                         const unsigned short *__restrict__ seg)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned total = (unsigned)(n_tiles_x * n_clips);
-    for (unsigned t = blockIdx.x; t < total; t += gridDim.x) {
-        const unsigned cnt = counts[t]; // (the same for the whole workgroup)
-        if (cnt == 0) continue;
-        if (cnt == kQRedo) {
-            __syncthreads(); // (the slab and parts of a tile redone before)
-            hashprint_q_tile<FROM_T, false, 9, true>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, nullptr, nullptr, nullptr);
-            continue;
-        }
-        const int clip = t / n_tiles_x;
-        const int n0 = (t - clip * n_tiles_x) * kQTileN;
-        const float *S = sdb + (int64_t)clip * kBins * c;
-        const float ref = FROM_T ? tmax[clip] : 0.0f;
-        for (unsigned e = wave; e < cnt; e += kQThreads / 64) {
-            const unsigned entry = seg[(size_t)t * kQCap + e];
-            const int r = entry >> 7, n = n0 + (int)(entry & 127u); // (n < nhp: n + 19 + kLag < c)
-            const int *frow = fq32 + r * kFrame;
-            long long sum = 0;
-#pragma unroll 2
-            for (int k = lane; k < kFrame; k += 64) {
-                const int bin = k / kCtx, idx = bin * c + n + (k - bin * kCtx);
-                float xa = S[idx], xb = S[idx + kLag];
-                if (FROM_T) {
-                    xa -= ref;
-                    xb -= ref;
-                }
-                sum += (long long)frow[k] * (long long)(q_fixed(xa) - q_fixed(xb));
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-            if (lane == 0) {
-                unsigned long long *w = reinterpret_cast<unsigned long long *>(hp + (int64_t)clip * nhp + n);
-                const unsigned long long bit = 1ull << (63 - r);
-                if (((*w & bit) != 0) != (sum >= 0)) atomicXor(w, bit);
-            }
-        }
-    }
+    hashprint_q_tile<FROM_T, false, 6>(t, fq_image, sdb, tmax, c, nhp, n_tiles_x, hp, nullptr, 1, thr, counts);
 }
 
 // Image i (blockIdx.y) of the filters moved by shifts.s[i] bins: the byte of bin b holds the digit of fq[r][20 (b - s) + t]
@@ -657,9 +575,8 @@ __global__ __launch_bounds__(256) void shift_filter_images_kernel(const unsigned
 // host: the filters' digits as the A operand of v_mfma_i32_16x16x64_i8, [wave][step s = 2 t + p][digit][lane][16 bytes]:
 // byte e of lane l = digit of fq[row = 16 wave + (l & 15)][k = 20 bin + t], bin = 64 p + 16 (l >> 4) + e (zero for bin >= 121)
 // thr, when given: the 64 thresholds of the six-product split: floor(Lmax_r / 2^16) with Lmax_r = 128 (S0_r + 256 (S0_r +
-// S1_r)), S0_r and S1_r the sums of |digit 0| and |digit 1| of row r's taps, or -1 where Lmax_r = 0 (hashprint_q_tile).
-// fq32, when given (HPFW_Q_FIXUP=launch): fq as int32 [64][2420] (k = 20 bin + t)
-void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int32_t> *thr, std::vector<int32_t> *fq32)
+// S1_r)), S0_r and S1_r the sums of |digit 0| and |digit 1| of row r's taps, or -1 where Lmax_r = 0 (q_epilogue).
+void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int32_t> *thr)
 {
     std::vector<int32_t> fq((size_t)kFilters * kFrame);
     for (int r = 0; r < kFilters; ++r) {
@@ -668,7 +585,6 @@ void pack_filters_q(const float *f, std::vector<int8_t> &image, std::vector<int3
         const int e = m > 0.0f ? 21 - std::ilogb(m) : 0;
         for (int k = 0; k < kFrame; ++k) fq[(size_t)r * kFrame + k] = (int32_t)std::rint(std::ldexp(f[(size_t)k * kFilters + r], e));
     }
-    if (fq32) *fq32 = fq;
     if (thr) {
         thr->clear();
         for (int r = 0; r < kFilters; ++r) {
@@ -709,7 +625,7 @@ extern "C" void hpfw_gpu_debug_set_q_stamps(void *d)
 #endif
 
 size_t project_q_image_bytes() { return (size_t)4 * kQSteps * kQStepBytes; }
-size_t project_q_split_bytes(int64_t tiles, bool segments) { return (size_t)tiles * (4 + (segments ? (size_t)kQCap * 2 : 0)); }
+size_t project_q_split_bytes(int64_t tiles) { return (size_t)tiles * 4; }
 int64_t project_q_tiles(int64_t n_clips, int64_t c)
 {
     const int64_t nhp = c - (kCtx - 1) - kLag;
@@ -721,25 +637,17 @@ int64_t project_q_tiles(int64_t n_clips, int64_t c)
 // too: 2.14 ms against 2.15 for the extraction's instance on 1000 x 30 s clips (profiles/transpose.json).  d_dbg: NULL,
 // or D [n_clips][64][c - 99] of the unshifted image (tests)
 // split (n_shifts = 0, no d_dbg; else NULL): the six-product kernel instead of the nine-product kernel.  d_thr: the device
-// copy of pack_filters_q's thresholds; d_work: project_q_split_bytes(project_q_tiles(n_clips, c), d_fq32 != NULL) bytes,
-// counts [tiles].  d_fq32 != NULL (HPFW_Q_FIXUP=launch): the listing kernel and the fix-up launch; d_work then holds the
-// segments [tiles][kQCap] behind the counts
-template <bool CLASSIC>
-static void launch_hashprints_q_as(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
-                                   long long *d_dbg, hipStream_t s, const QSplit *split)
+// copy of pack_filters_q's thresholds; d_work: project_q_split_bytes(project_q_tiles(n_clips, c)) bytes, counts [tiles]
+void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
+                         long long *d_dbg, hipStream_t s, const QSplit *split)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        for (const void *k :
-             {reinterpret_cast<const void *>(hashprint_q_kernel<true, false, CLASSIC>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false, CLASSIC>),
-              reinterpret_cast<const void *>(hashprint_q_kernel<true, true, CLASSIC>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true, CLASSIC>)})
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q_kernel<true, false>), reinterpret_cast<const void *>(hashprint_q_kernel<false, false>),
+                              reinterpret_cast<const void *>(hashprint_q_kernel<true, true>), reinterpret_cast<const void *>(hashprint_q_kernel<false, true>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes);
-        for (const void *k :
-             {reinterpret_cast<const void *>(hashprint_q6_listed_kernel<true, CLASSIC>), reinterpret_cast<const void *>(hashprint_q6_listed_kernel<false, CLASSIC>),
-              reinterpret_cast<const void *>(hashprint_q_fixup_kernel<true>), reinterpret_cast<const void *>(hashprint_q_fixup_kernel<false>)})
+        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true>), reinterpret_cast<const void *>(hashprint_q6_kernel<false>)})
             (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6);
-        for (const void *k : {reinterpret_cast<const void *>(hashprint_q6_kernel<true, CLASSIC>), reinterpret_cast<const void *>(hashprint_q6_kernel<false, CLASSIC>)})
-            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes6f);
         attr_set.mark();
     }
     const int nhp = c - (kCtx - 1) - kLag;
@@ -749,42 +657,17 @@ static void launch_hashprints_q_as(const void *d_images, int n_shifts, const flo
     if (!d_dbg && !(split && n_shifts == 0)) d_dbg = g_q_stamps;
 #endif
     const int tiles = (nhp + kQTileN - 1) / kQTileN;
-    const dim3 grid(q_grid(CLASSIC, nhp, tiles, n_clips)); // one-dimensional, in XCD-aware order (q_tile_of_workgroup)
+    const dim3 grid(q_grid(nhp, tiles, n_clips)); // one-dimensional, in XCD-aware order (q_tile_of_workgroup)
     if (split && n_shifts == 0 && !d_dbg) {
-        const int *fq32 = split->d_fq32, *thr = split->d_thr;
-        unsigned *counts = static_cast<unsigned *>(split->d_work);
-        if (!fq32) {
-            auto k6 = d_tmax ? hashprint_q6_kernel<true, CLASSIC> : hashprint_q6_kernel<false, CLASSIC>;
-            hipLaunchKernelGGL(k6, grid, dim3(kQThreads), kQLdsBytes6f, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
-                               d_hp, thr, counts);
-            return;
-        }
-        unsigned short *seg = reinterpret_cast<unsigned short *>(counts + (size_t)tiles * n_clips);
-        auto k6 = d_tmax ? hashprint_q6_listed_kernel<true, CLASSIC> : hashprint_q6_listed_kernel<false, CLASSIC>;
-        hipLaunchKernelGGL(k6, grid, dim3(kQThreads), kQLdsBytes6, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
-                           d_hp, thr, counts, seg);
-        // eight workgroups per CU share the tiles: few enough that none is launched for nothing, enough to hide the loads
-        const unsigned fix = (unsigned)std::min<int64_t>((int64_t)tiles * n_clips, 2048);
-        auto kf = d_tmax ? hashprint_q_fixup_kernel<true> : hashprint_q_fixup_kernel<false>;
-        hipLaunchKernelGGL(kf, dim3(fix), dim3(kQThreads), kQLdsBytes6, s, static_cast<const v4i *>(d_images), fq32, d_db, d_tmax, c, nhp, tiles,
-                           n_clips, d_hp, counts, seg);
+        auto k6 = d_tmax ? hashprint_q6_kernel<true> : hashprint_q6_kernel<false>;
+        hipLaunchKernelGGL(k6, grid, dim3(kQThreads), kQLdsBytes6, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips, d_hp,
+                           split->d_thr, static_cast<unsigned *>(split->d_work));
         return;
     }
-    auto k = n_shifts > 0 ? (d_tmax ? hashprint_q_kernel<true, true, CLASSIC> : hashprint_q_kernel<false, true, CLASSIC>)
-                          : (d_tmax ? hashprint_q_kernel<true, false, CLASSIC> : hashprint_q_kernel<false, false, CLASSIC>);
+    auto k = n_shifts > 0 ? (d_tmax ? hashprint_q_kernel<true, true> : hashprint_q_kernel<false, true>)
+                          : (d_tmax ? hashprint_q_kernel<true, false> : hashprint_q_kernel<false, false>);
     hipLaunchKernelGGL(k, grid, dim3(kQThreads), kQLdsBytes, s, static_cast<const v4i *>(d_images), d_db, d_tmax, c, nhp, tiles, n_clips,
                        d_hp, d_dbg, n_shifts);
-}
-
-// classic_staging (HPFW_Q_STAGING=classic at handle creation): the kernels with the staging and the workgroup order as they
-// were before the chains (hashprint_q_tile CLASSIC), kept to measure against; the slab and every result are the same
-void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
-                         long long *d_dbg, hipStream_t s, const QSplit *split, bool classic_staging)
-{
-    if (classic_staging)
-        launch_hashprints_q_as<true>(d_images, n_shifts, d_db, d_tmax, n_clips, c, d_hp, d_dbg, s, split);
-    else
-        launch_hashprints_q_as<false>(d_images, n_shifts, d_db, d_tmax, n_clips, c, d_hp, d_dbg, s, split);
 }
 
 void launch_shift_filter_images(const void *d_fq_image, const ShiftList &shifts, void *d_images, hipStream_t s)

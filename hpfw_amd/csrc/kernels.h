@@ -262,18 +262,16 @@ size_t project_q_image_bytes();
 // The six-product split of the unshifted extraction (S9q): split != NULL, n_shifts = 0 and no d_dbg run the kernel that
 // forms only the digit products of weight >= 2^16 and settles the values whose sign those leave open from its own slab,
 // before it stores the hashprints.  d_thr: pack_filters_q's 64 thresholds; d_work: project_q_split_bytes(project_q_tiles(
-// n_clips, c), d_fq32 != NULL) bytes, the tiles' counts.  d_fq32 != NULL (HPFW_Q_FIXUP=launch, kept to measure against):
-// fq as int32 [64][2420]; the kernel lists the open values in segments behind the counts and a fix-up launch recomputes them
+// n_clips, c)) bytes, the tiles' counts
 struct QSplit {
     const int32_t *d_thr;
     void *d_work;
-    const int32_t *d_fq32;
 };
-size_t project_q_split_bytes(int64_t tiles, bool segments);
+size_t project_q_split_bytes(int64_t tiles);
 int64_t project_q_tiles(int64_t n_clips, int64_t c);
-void pack_filters_q(const float *f_colmajor, std::vector<int8_t> &image, std::vector<int32_t> *thr = nullptr, std::vector<int32_t> *fq32 = nullptr);
+void pack_filters_q(const float *f_colmajor, std::vector<int8_t> &image, std::vector<int32_t> *thr = nullptr);
 void launch_hashprints_q(const void *d_images, int n_shifts, const float *d_db, const float *d_tmax, int n_clips, int c, uint64_t *d_hp,
-                         long long *d_dbg, hipStream_t s, const QSplit *split = nullptr, bool classic_staging = false);
+                         long long *d_dbg, hipStream_t s, const QSplit *split = nullptr);
 // transposed extraction: the digit images of the filters moved by each of shifts.s[0 .. n) bins
 // (d_images: n * project_q_image_bytes()), for launch_hashprints_q
 constexpr int kMaxShifts = 64;

@@ -570,10 +570,7 @@ int hpfw_gpu_stage_delta_q(hpfw_gpu *h, const float *d_db, int64_t n_clips, int6
 /* the six-product split (the default of mode 1's unshifted extraction; HPFW_Q_PRODUCTS=9 in the environment when the handle
  * is created switches it off): of the last such launch on this handle, its tiles of 128 hashprints, the values listed
  * for exact recomputation and the tiles redone with nine products.  Waits for the device; zeros without such a launch.
- * The kernel settles the listed values and the redone tiles itself; HPFW_Q_FIXUP=launch in the environment at creation
- * keeps the earlier form, a second launch behind the kernel, to measure against.  HPFW_Q_STAGING=classic at creation
- * keeps, in every fixed-point hashprint launch of the handle, the slab staging and the workgroup order as they were before
- * the staging by chains; the results are the same. */
+ * The kernel settles the listed values and the redone tiles itself. */
 int hpfw_gpu_debug_q_products(hpfw_gpu *h, int64_t *tiles, int64_t *listed, int64_t *redone);
 
 /* ---- timeline of a long recording: scored search, windows of one recording, segments.

@@ -1,6 +1,5 @@
-"""The six-product hashprint kernel that settles its open values itself (k_project_q.hip FUSED):
-the default handle against a HPFW_Q_PRODUCTS=9 handle (the nine-product kernel), a HPFW_Q_FIXUP=launch handle (the open
-values listed and recomputed by a second launch) and the oracle.  Every case first shows on the CPU, with
+"""The six-product hashprint kernel that settles its open values itself (k_project_q.hip):
+the default handle against a HPFW_Q_PRODUCTS=9 handle (the nine-product kernel) and the oracle.  Every case first shows on the CPU, with
 q_products_ref.split, that its input reaches what it is about: bits that the list path has to flip, where in a tile they
 lie, tiles above the cap with wrong signs of Dp, the three tile states in one launch.
 
@@ -36,9 +35,9 @@ def handle(env, filt):
 
 
 @pytest.fixture(scope="module")
-def trio(torch_cuda, filters):
-    """(default: fused, nine products, six products with the fix-up launch)"""
-    gs = [handle(env, filters) for env in ({}, {"HPFW_Q_PRODUCTS": "9"}, {"HPFW_Q_FIXUP": "launch"})]
+def pair(torch_cuda, filters):
+    """(default: six products, the open values settled in the kernel; nine products)"""
+    gs = [handle(env, filters) for env in ({}, {"HPFW_Q_PRODUCTS": "9"})]
     yield gs
     for g in gs:
         g.close()
@@ -53,11 +52,10 @@ def from_db(torch, g, s):
     return hp.cpu().numpy().view(np.uint64)
 
 
-def all_agree(torch, trio, oracle, filt, s):
-    """hashprints of the default handle, equal to those of the other two handles and of the oracle"""
-    got = from_db(torch, trio[0], s)
-    assert np.array_equal(got, from_db(torch, trio[1], s)), "nine products"
-    assert np.array_equal(got, from_db(torch, trio[2], s)), "fix-up launch"
+def all_agree(torch, pair, oracle, filt, s):
+    """hashprints of the default handle, equal to those of the nine-product handle and of the oracle"""
+    got = from_db(torch, pair[0], s)
+    assert np.array_equal(got, from_db(torch, pair[1], s)), "nine products"
     for i in range(s.shape[0]):
         assert np.array_equal(got[i], oracle.hashprints_from_db(filt, s[i])), i
     return got
@@ -89,10 +87,9 @@ def cpu_view(oracle, filt, s):
     return clips, listed, redone
 
 
-def check_counts(trio, s, listed, redone):
+def check_counts(pair, s, listed, redone):
     tiles = s.shape[0] * ((s.shape[2] - 99 + ref.TILE - 1) // ref.TILE)
-    assert trio[0].debug_q_products() == (tiles, listed, redone)
-    assert trio[2].debug_q_products() == (tiles, listed, redone)
+    assert pair[0].debug_q_products() == (tiles, listed, redone)
 
 
 # clips per width: about one listed value in a hundred has to be flipped; a stretch of one hashprint opens 64 values and the
@@ -124,14 +121,14 @@ def list_path_input(c, seed):
 
 
 @pytest.mark.parametrize("c", (100, 227, 228, 355))
-def test_list_path_flips_bits(torch_cuda, trio, oracle, filters, c):
+def test_list_path_flips_bits(torch_cuda, pair, oracle, filters, c):
     s = list_path_input(c, LIST_SEEDS[c])
     clips, listed, redone = cpu_view(oracle, filters, s)
     counts = [k for _, _, cn, _ in clips for k in cn]
     assert redone == 0 and max(counts) <= ref.CAP and sum(1 for k in counts if k >= 1) >= len(clips)
     assert sum(int(w.sum()) for _, w, _, _ in clips) >= 8               # bits that stand wrong after the six products
-    all_agree(torch_cuda, trio, oracle, filters, s)
-    check_counts(trio, s, listed, redone)
+    all_agree(torch_cuda, pair, oracle, filters, s)
+    check_counts(pair, s, listed, redone)
 
 
 PLACE_CLIPS, PLACE_SEED = 36, 0
@@ -148,7 +145,7 @@ def placement_input(seed):
     return s
 
 
-def test_placement_of_open_values_in_a_tile(torch_cuda, trio, oracle, filters):
+def test_placement_of_open_values_in_a_tile(torch_cuda, pair, oracle, filters):
     s = placement_input(PLACE_SEED)
     clips, listed, redone = cpu_view(oracle, filters, s)
     assert redone == 0
@@ -164,11 +161,11 @@ def test_placement_of_open_values_in_a_tile(torch_cuda, trio, oracle, filters):
         assert both.any(), lo
     # ... and a word in which two bits flip
     assert (wrong[:, 0:32].sum(axis=1) >= 2).any() or (wrong[:, 32:64].sum(axis=1) >= 2).any()
-    all_agree(torch_cuda, trio, oracle, filters, s)
-    check_counts(trio, s, listed, redone)
+    all_agree(torch_cuda, pair, oracle, filters, s)
+    check_counts(pair, s, listed, redone)
 
 
-def test_above_the_cap_in_a_partial_and_in_a_full_tile(torch_cuda, trio, oracle, filters):
+def test_above_the_cap_in_a_partial_and_in_a_full_tile(torch_cuda, pair, oracle, filters):
     """one-digit Du everywhere, c = 240: 141 hashprints, a full tile and a last tile of 13 (n_tiles = 1) -- the widths 100,
     227, 228 and 355 have no partial tile of three or more hashprints, and a tile goes above the cap only from three on.
     Then 99 + 3 columns at c = 355: three hashprints, up to 192 open values in a full tile of otherwise uniform noise"""
@@ -178,8 +175,8 @@ def test_above_the_cap_in_a_partial_and_in_a_full_tile(torch_cuda, trio, oracle,
     assert redone == 4 and listed == 0
     for _, wrong, counts, _ in clips:
         assert min(counts) > ref.CAP and wrong[:, :128].any() and wrong[:, 128:].any()
-    all_agree(torch_cuda, trio, oracle, filters, s)
-    check_counts(trio, s, listed, redone)
+    all_agree(torch_cuda, pair, oracle, filters, s)
+    check_counts(pair, s, listed, redone)
 
     rng = np.random.default_rng(ABOVE_SEED)
     s = rng.uniform(-80, 0, (2, 121, 355)).astype(np.float32)
@@ -188,12 +185,12 @@ def test_above_the_cap_in_a_partial_and_in_a_full_tile(torch_cuda, trio, oracle,
     clips, listed, redone = cpu_view(oracle, filters, s)
     assert redone == 2 and clips[0][2][0] > ref.CAP and clips[1][2][1] > ref.CAP
     assert clips[0][1][:, 30:33].any() and clips[1][1][:, 150:153].any()           # a wrong sign of Dp in each redone tile
-    all_agree(torch_cuda, trio, oracle, filters, s)
-    check_counts(trio, s, listed, redone)
+    all_agree(torch_cuda, pair, oracle, filters, s)
+    check_counts(pair, s, listed, redone)
 
 
 
-def test_zero_listed_and_redone_tiles_in_one_clip(torch_cuda, trio, oracle, filters):
+def test_zero_listed_and_redone_tiles_in_one_clip(torch_cuda, pair, oracle, filters):
     """c = 483, three full tiles: the -80 dB floor under the first (Du = 0 in its slab), noise under the second, one-digit
     Du from column 255 on: the last hashprint of the second tile and all of the third"""
     rng = np.random.default_rng(MIXED_SEED)
@@ -205,12 +202,12 @@ def test_zero_listed_and_redone_tiles_in_one_clip(torch_cuda, trio, oracle, filt
         assert zero == [True, False, False] and 1 <= counts[1] <= ref.CAP < counts[2]
         assert wrong[:, 256:].any()
     assert sum(int(w[:, 128:256].sum()) for _, w, _, _ in clips) >= 1
-    got = all_agree(torch_cuda, trio, oracle, filters, s)
+    got = all_agree(torch_cuda, pair, oracle, filters, s)
     assert (got[:, :128] == np.uint64(2 ** 64 - 1)).all()
-    check_counts(trio, s, listed, redone)
+    check_counts(pair, s, listed, redone)
 
 
-def test_full_dynamic_range_from_the_spectrogram(torch_cuda, trio, oracle, filters):
+def test_full_dynamic_range_from_the_spectrogram(torch_cuda, pair, oracle, filters):
     """uniform -80 .. 0 dB without a reference level: differences up to 80 dB, all three digits of Du in use"""
     rng = np.random.default_rng(21)
     s = rng.uniform(-80, 0, (3, 121, 355)).astype(np.float32)
@@ -218,14 +215,14 @@ def test_full_dynamic_range_from_the_spectrogram(torch_cuda, trio, oracle, filte
     du = u[:, :, :-ref.LAG] - u[:, :, ref.LAG:]
     assert np.abs(du).max() > 75 * 98304 and all(np.abs(d).max() >= 100 for d in ref.digits(du))
     clips, listed, redone = cpu_view(oracle, filters, s)
-    all_agree(torch_cuda, trio, oracle, filters, s)
-    check_counts(trio, s, listed, redone)
+    all_agree(torch_cuda, pair, oracle, filters, s)
+    check_counts(pair, s, listed, redone)
 
 
-def test_end_to_end_from_pcm(torch_cuda, trio, oracle, filters):
+def test_end_to_end_from_pcm(torch_cuda, pair, oracle, filters):
     """2 s of synthetic audio through extract: the kernel's FROM_T instance, the reference level riding on the staging"""
     clip = synth.gen_clip(71, 2.0)[None]
     want = oracle.Plan(clip.shape[1]).extract(filters, clip[0])
-    for g in trio:
+    for g in pair:
         assert np.array_equal(g.extract(clip)[0], want)
-    assert trio[0].debug_q_products()[0] == (want.size + ref.TILE - 1) // ref.TILE
+    assert pair[0].debug_q_products()[0] == (want.size + ref.TILE - 1) // ref.TILE

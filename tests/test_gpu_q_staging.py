@@ -1,7 +1,6 @@
 """The hashprint kernel's slab staging by chains and its workgroup order (k_project_q.hip): the default
-handle against a HPFW_Q_STAGING=classic handle (the staging and the order as they were) and against q_products_ref, from
-seeded dB spectrograms through hashprints_from_db (the six-product kernel, fused) and stage_delta_q (the nine-product
-kernel, D as int64).  The slab is the same bytes in both forms, so everything is compared for equality."""
+handle against q_products_ref and the oracle, from seeded dB spectrograms through hashprints_from_db (the six-product
+kernel) and stage_delta_q (the nine-product kernel, D as int64).  Everything is integers: compared for equality."""
 import os
 import sys
 
@@ -17,24 +16,13 @@ from hpfw_amd import synth  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def handle(env, filt):
-    os.environ.update(env)
-    try:
-        g = hpfw_amd.Gpu(0)
-    finally:
-        for k in env:
-            os.environ.pop(k, None)
-    g.set_filters(filt)
-    return g
-
-
 @pytest.fixture(scope="module")
-def pair(torch_cuda, filters):
-    """(default: chains, short tiles last; classic)"""
-    gs = [handle(env, filters) for env in ({}, {"HPFW_Q_STAGING": "classic"})]
-    yield gs
-    for g in gs:
-        g.close()
+def g(torch_cuda, filters):
+    """a handle of its own with the default settings"""
+    g = hpfw_amd.Gpu(0)
+    g.set_filters(filters)
+    yield g
+    g.close()
 
 
 def run(torch, g, s):
@@ -50,11 +38,9 @@ def run(torch, g, s):
     return hp6.cpu().numpy().view(np.uint64), hp9.cpu().numpy().view(np.uint64), d.cpu().numpy()
 
 
-def check(torch, pair, oracle, filt, s):
-    """both handles equal each other and the reference; returns the reference's (listed, redone)"""
-    new, old = run(torch, pair[0], s), run(torch, pair[1], s)
-    for a, b, what in zip(new, old, ("hashprints, six products", "hashprints, nine products", "D")):
-        assert np.array_equal(a, b), what
+def check(torch, g, oracle, filt, s):
+    """the handle equals the reference; returns the reference's (listed, redone)"""
+    new = run(torch, g, s)
     listed = redone = 0
     for i in range(s.shape[0]):
         d, _, _, _, is_open, du = ref.split(oracle, filt, s[i])
@@ -64,24 +50,23 @@ def check(torch, pair, oracle, filt, s):
         a, b = ref.tile_states(is_open, du)
         listed, redone = listed + a, redone + b
     tiles = s.shape[0] * ((s.shape[2] - 99 + ref.TILE - 1) // ref.TILE)
-    for g in pair:                                                              # (the last six-product launch of either handle)
-        d_s = torch.from_numpy(np.ascontiguousarray(s)).cuda()
-        hp = torch.zeros((s.shape[0], s.shape[2] - 99), dtype=torch.int64, device="cuda")
-        g.hashprints_from_db_dev(d_s.data_ptr(), s.shape[0], s.shape[2], hp.data_ptr())
-        assert g.debug_q_products() == (tiles, listed, redone)
+    d_s = torch.from_numpy(np.ascontiguousarray(s)).cuda()                          # (the handle's last six-product launch)
+    hp = torch.zeros((s.shape[0], s.shape[2] - 99), dtype=torch.int64, device="cuda")
+    g.hashprints_from_db_dev(d_s.data_ptr(), s.shape[0], s.shape[2], hp.data_ptr())
+    assert g.debug_q_products() == (tiles, listed, redone)
     return listed, redone
 
 
 @pytest.mark.parametrize("n_hp", (1, 15, 16, 17, 127, 128, 129, 144, 2320))
-def test_widths(torch_cuda, pair, oracle, filters, n_hp):
+def test_widths(torch_cuda, g, oracle, filters, n_hp):
     """one tile, a short last tile (short tiles dispatched last), an exactly full last tile, the workload's shape"""
     c = n_hp + 99
     s = np.random.default_rng(1000 + n_hp).uniform(-80, 0, (2, 121, c)).astype(np.float32)
-    check(torch_cuda, pair, oracle, filters, s)
+    check(torch_cuda, g, oracle, filters, s)
 
 
 @pytest.mark.parametrize("floor", ("tile", "columns", "bin 120", "bin 0"))
-def test_the_floor(torch_cuda, pair, oracle, filters, floor):
+def test_the_floor(torch_cuda, g, oracle, filters, floor):
     """c = 371: two full tiles and a short one of 16.  The -80 dB floor under a whole tile's slab (the all-zero shortcut),
     in the single columns c - 81, c - 80 and c - 1 (the last column with a partner, the first and the last without one),
     in the highest and in the lowest bin"""
@@ -95,47 +80,43 @@ def test_the_floor(torch_cuda, pair, oracle, filters, floor):
         s[1][:, c - 80] = -80.0
     else:
         s[:, 120 if floor == "bin 120" else 0, :] = -80.0
-    new = run(torch_cuda, pair[0], s)
+    new = run(torch_cuda, g, s)
     if floor == "tile":
         ones = np.uint64(2 ** 64 - 1)
         assert (new[0][0, :128] == ones).all() and (new[0][1, 256:] == ones).all()
-    check(torch_cuda, pair, oracle, filters, s)
+    check(torch_cuda, g, oracle, filters, s)
 
 
-def test_tiles_above_the_cap_are_redone_alike(torch_cuda, pair, oracle, filters):
+def test_tiles_above_the_cap_are_redone_alike(torch_cuda, g, oracle, filters):
     """near-stationary input (every difference has one digit), c = 240: a full tile and a short one of 13, both above the
-    cap -- the nine-product redo over the slab as the chains left it (STAGED); then one such stretch in noise"""
+    cap -- the nine-product redo over the slab as the chains left it; then one such stretch in noise"""
     rng = np.random.default_rng(3)
     s = ((-40 * 98304 + rng.integers(0, 128, (2, 121, 240))) / 98304.0).astype(np.float32)
-    assert check(torch_cuda, pair, oracle, filters, s) == (0, 4)
+    assert check(torch_cuda, g, oracle, filters, s) == (0, 4)
     s = rng.uniform(-80, 0, (2, 121, 355)).astype(np.float32)
     s[0, :, 30:132] = ((-40 * 98304 + rng.integers(0, 128, (121, 102))) / 98304.0).astype(np.float32)
-    assert check(torch_cuda, pair, oracle, filters, s)[1] == 1
+    assert check(torch_cuda, g, oracle, filters, s)[1] == 1
 
 
-def test_transposed(torch_cuda, pair, oracle, filters):
+def test_transposed(torch_cuda, g, oracle, filters):
     """two shifted filter images over one slab (SHIFTED), a short last tile"""
     torch = torch_cuda
     c, shifts = 244, np.array([3, -2], np.int32)
     s = np.random.default_rng(6).uniform(-80, 0, (2, 121, c)).astype(np.float32)
-    out = []
-    for g in pair:
-        d_s = torch.from_numpy(s).cuda()
-        hp = torch.zeros((2, 2, c - 99), dtype=torch.int64, device="cuda")
-        g.hashprints_from_db_transposed_dev(d_s.data_ptr(), 2, c, shifts, hp.data_ptr())
-        torch.cuda.synchronize()
-        out.append(hp.cpu().numpy().view(np.uint64))
-    assert np.array_equal(out[0], out[1])
+    d_s = torch.from_numpy(s).cuda()
+    hp = torch.zeros((2, 2, c - 99), dtype=torch.int64, device="cuda")
+    g.hashprints_from_db_transposed_dev(d_s.data_ptr(), 2, c, shifts, hp.data_ptr())
+    torch.cuda.synchronize()
+    out = hp.cpu().numpy().view(np.uint64)
     for i in range(2):
         for j, sh in enumerate(shifts):
-            assert np.array_equal(out[0][i, j], oracle.hashprints_from_db(filters, transpose_ref.shift_db(s[i], int(sh)))), (i, sh)
+            assert np.array_equal(out[i, j], oracle.hashprints_from_db(filters, transpose_ref.shift_db(s[i], int(sh)))), (i, sh)
 
 
-def test_end_to_end_from_pcm(torch_cuda, pair, oracle, filters):
+def test_end_to_end_from_pcm(torch_cuda, g, oracle, filters):
     """two 2 s clips through extract: the dB terms' instance (the reference level rides on the chains' loads)"""
     clips = np.stack([synth.gen_clip(81 + i, 2.0) for i in range(2)])
     plan = oracle.Plan(clips.shape[1])
-    got = pair[0].extract(clips)
-    assert np.array_equal(got, pair[1].extract(clips))
+    got = g.extract(clips)
     for i in range(2):
         assert np.array_equal(got[i], plan.extract(filters, clips[i])), i
