@@ -92,6 +92,7 @@ EXPORTS = (
     "hpfw_gpu_timeline_tracker_finish",
     "hpfw_gpu_search_overlap_device", "hpfw_gpu_search_overlap",
     "hpfw_gpu_search_overlap_scored_device", "hpfw_gpu_search_overlap_scored", "hpfw_gpu_overlap_rate", "hpfw_gpu_overlap_extent",
+    "hpfw_gpu_knn_windows_device", "hpfw_gpu_vote_windows_device", "hpfw_gpu_search_votes_device", "hpfw_gpu_merge_knn_device",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -224,6 +225,10 @@ def lib():
     L.hpfw_gpu_supported_length.restype = i64
     L.hpfw_gpu_search_votes.argtypes = [vp, vp, vp, i64, vp]
     L.hpfw_gpu_knn_windows.argtypes = [vp, vp, vp, i64, vp, i64]
+    L.hpfw_gpu_knn_windows_device.argtypes = [vp, vp, vp, i64, vp, i64, vp]
+    L.hpfw_gpu_vote_windows_device.argtypes = [vp, vp, vp, i64, vp, i64, u32, vp, vp]
+    L.hpfw_gpu_search_votes_device.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.hpfw_gpu_merge_knn_device.argtypes = [vp, vp, vp, i32, i64, vp, vp]
     L.hpfw_gpu_index_get.argtypes = [vp, vp, vp, ctypes.c_int64]
     L.hpfw_gpu_extract_db_host.argtypes = [vp, vp, i32, i32, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.hpfw_gpu_set_kernel_timing.argtypes = [vp, i32]
@@ -1041,6 +1046,28 @@ class Gpu:
         keys = np.zeros((n_win, 5), np.uint64)
         check(lib().hpfw_gpu_knn_windows(self._h, _hp(q), _hp(off), off.size - 1, _hp(keys), keys.size))
         return keys
+
+    # ---- the voting search with device buffers: the tally runs on the device
+    def knn_windows_dev(self, d_q, q_off, d_keys, keys_cap, stream=0):
+        """d_keys [n_windows][5] uint64 on the device (keys_cap: its capacity in keys), ascending per window"""
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_knn_windows_device(self._h, d_q, _hp(off), off.size - 1, d_keys, int(keys_cap), stream))
+
+    def vote_windows_dev(self, d_keys, w_first, d_db_off, n_clips, d_out, clip_base=0, stream=0):
+        """the tally alone: w_first [n_q + 1] (host) the first window of each query in d_keys [..][5]; d_db_off int64
+        [n_clips + 1] and d_out VOTE_DTYPE [n_q] on the device"""
+        wf = np.ascontiguousarray(w_first, np.int64)
+        check(lib().hpfw_gpu_vote_windows_device(self._h, d_keys, _hp(wf), wf.size - 1, d_db_off, int(n_clips), int(clip_base), d_out, stream))
+
+    def search_votes_dev(self, d_q, q_off, d_out, stream=0):
+        """search_votes with the queries and d_out (VOTE_DTYPE [n_q]) on the device"""
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_search_votes_device(self._h, d_q, _hp(off), off.size - 1, d_out, stream))
+
+    def merge_knn_dev(self, d_in, pos_base, n_win, d_out, stream=0):
+        """d_in [n_shards][n_win][5] -> d_out [n_win][5]; pos_base [n_shards] (host): the hashprints in earlier shards"""
+        base = np.ascontiguousarray(pos_base, np.int64)
+        check(lib().hpfw_gpu_merge_knn_device(self._h, d_in, _hp(base), base.size, int(n_win), d_out, stream))
 
     def search_topk_transposed(self, q_hp, q_off, n_shifts, k):
         """q_off [n_q * n_shifts + 1]: query set q * n_shifts + i is shift i of query q -> SHIFT_HIT_DTYPE [n_q][k]"""

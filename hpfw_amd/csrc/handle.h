@@ -144,6 +144,9 @@ struct hpfw_gpu {
         DevBuf d_topk_scratch;
         DevBuf d_shift_hits; // the per-shift top-k lists of a transposed search
         DevBuf d_ov_tab, d_ov_exclude; // overlap search: the (query, clip, split) entries, the clips to skip
+        // voting search on the device: the workspaces of one group of windows, carved from one buffer;
+        // the first window and first hashprint of every query of the call
+        DevBuf d_votes_ws, d_votes_tab;
     } index;
     // filter learning (learn.hip)
     struct Learn {

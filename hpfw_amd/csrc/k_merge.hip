@@ -1,5 +1,6 @@
 // k_merge.hip -- what a sharded search does with the gathered per-shard results: the device twins of
-// hpfw_gpu_merge_topk and of the sum of the scored search's moments.
+// hpfw_gpu_merge_topk and of the sum of the scored search's moments, and the merge of the voting search's per-shard neighbour
+// lists (knn_merge_shards_kernel).
 //
 // topk_merge_shards_kernel: one workgroup per query.  Its n = n_shards k <= 4096 candidates in[shard][q][k] are 16-byte
 // records with the key (dist, clip) in their first two words; the other two words are payload (hpfw_hit: offset, pad;
@@ -80,6 +81,49 @@ __global__ __launch_bounds__(kMsThreads) void sum_stats_kernel(const MergeStatsD
         acc.n += v.n;
     }
     out[r] = acc;
+}
+
+// the per-shard neighbour lists of the voting search: one thread per window.  Shards are contiguous blocks of clips, so a key
+// with its shard's first position added is the key of the unsharded index, and the 5 smallest of the 5 n_shards keys, ties
+// included, are the unsharded list.
+struct KnnPosBase {
+    long long v[64];
+};
+
+__global__ __launch_bounds__(kMsThreads) void knn_merge_shards_kernel(const uint64_t *__restrict__ in, KnnPosBase base, int n_shards,
+                                                                      long long n_win, uint64_t *__restrict__ out)
+{
+    const long long w = (long long)blockIdx.x * kMsThreads + threadIdx.x;
+    if (w >= n_win) return;
+    uint64_t b0 = ~0ull, b1 = ~0ull, b2 = ~0ull, b3 = ~0ull, b4 = ~0ull;
+    for (int s = 0; s < n_shards; ++s) {
+        const uint64_t *row = in + ((long long)s * n_win + w) * 5;
+        const uint64_t add = (uint64_t)base.v[s];
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            uint64_t c = row[r], t;
+            if (c != ~0ull) c += add; // (the position field: below 2^40 with the base added)
+            if (c < b0) { t = b0; b0 = c; c = t; }
+            if (c < b1) { t = b1; b1 = c; c = t; }
+            if (c < b2) { t = b2; b2 = c; c = t; }
+            if (c < b3) { t = b3; b3 = c; c = t; }
+            if (c < b4) b4 = c;
+        }
+    }
+    uint64_t *o = out + w * 5;
+    o[0] = b0;
+    o[1] = b1;
+    o[2] = b2;
+    o[3] = b3;
+    o[4] = b4;
+}
+
+void launch_knn_merge_shards(const uint64_t *d_in, const int64_t *pos_base, int n_shards, int64_t n_win, uint64_t *d_out, hipStream_t s)
+{
+    KnnPosBase base = {};
+    for (int i = 0; i < n_shards && i < 64; ++i) base.v[i] = pos_base[i];
+    hipLaunchKernelGGL(knn_merge_shards_kernel, dim3((unsigned)((n_win + kMsThreads - 1) / kMsThreads)), dim3(kMsThreads), 0, s, d_in, base,
+                       n_shards, (long long)n_win, d_out);
 }
 
 void launch_topk_merge_shards(const void *d_in, int n_shards, int64_t n_q, int k, void *d_out, hipStream_t s)

@@ -415,6 +415,35 @@ void launch_dist_stats(const uint64_t *d_best, const int64_t *d_db_off, const in
 void launch_topk_merge_shards(const void *d_in, int n_shards, int64_t n_q, int k, void *d_out, hipStream_t s);
 // d_out[r] = sum over the shards of d_in[shard][r] (hpfw_dist_stats), r < rows
 void launch_sum_stats(const void *d_in, int n_shards, int64_t rows, void *d_out, hipStream_t s);
+// the same for the neighbour lists of the voting search: d_in [n_shards][n_win][5] keys (dist << 40 | position in the shard,
+// ascending, ~0 behind them), pos_base[shard] added to the position of every real key -> d_out [n_win][5], the 5 smallest
+// ascending; n_shards <= 64
+void launch_knn_merge_shards(const uint64_t *d_in, const int64_t *pos_base, int n_shards, int64_t n_win, uint64_t *d_out, hipStream_t s);
+// ---- the tally of the voting search (k_votes.hip) ----
+// d_w_start[w] = where window w_base + w begins in the query array: d_q_off[q] + (w_base + w - d_w_first[q]) for the query q
+// that holds it (d_w_first, d_q_off [n_q + 1], the first window of each query and its first hashprint)
+void launch_window_starts(const int64_t *d_w_first, const int64_t *d_q_off, int n_q, int64_t w_base, int64_t n_win, int64_t *d_w_start,
+                          hipStream_t s);
+// the slots [n_win][8] of launch_knn_windows -> d_keys [n_win][5] ascending
+void launch_sort_knn_slots(const void *d_slots, int64_t n_win, uint64_t *d_keys, hipStream_t s);
+// a group of n_q whole queries whose n_win windows begin at window w_base of the call
+struct VoteTallyArgs {
+    const uint64_t *keys;    // [n_win][5], the group's
+    const int64_t *w_first;  // [n_q + 1], the group's first entry first; window numbers of the call
+    int64_t w_base, n_win;
+    int n_q;
+    const int64_t *db_off;   // [n_clips + 1] (device)
+    int64_t n_clips;
+    uint32_t clip_base;
+    int64_t stride;          // the most windows any query of the call has (at least 1): more than every window index i
+    int ubits, qbits;        // a bucket's number stays below 2^ubits - 1, a query's below 2^qbits; ubits + qbits <= 64
+    uint64_t *sort_keys, *sorted_keys; // [n_win * 5] each
+    uint32_t *sort_vals, *sorted_vals;
+    float *post;             // [n_win * 5]: every event's bucket value after it
+    hpfw_vote *out;          // [n_q], the group's
+};
+size_t vote_sort_temp_bytes(int64_t n_ev, int bits); // of the sort of n_ev events by `bits` bits (0: the query failed)
+hipError_t launch_vote_tally(const VoteTallyArgs &a, void *d_temp, size_t temp_bytes, hipStream_t s);
 // windows of one recording (k_windows.hip): window i of d_src is samples [i hop, i hop + win) -> d_dst [n_w][win]
 void launch_gather_windows(const int16_t *d_src, int64_t hop, int64_t win, int64_t n_w, int16_t *d_dst, hipStream_t s);
 // live feeds (k_streams.hip): rings of `capacity` samples in one slab [n_streams][capacity]

@@ -20,6 +20,7 @@
 #include "../../include/hpfw_gpu_multi.h"
 #include "../../include/hpfw_gpu_multi_resample.h"
 #include "../../include/hpfw_gpu_multi_search.h"
+#include "../../include/hpfw_gpu_multi_votes.h"
 #include "hip_owned.h"
 #include "legacy_internal.h"
 
@@ -61,7 +62,8 @@ struct Dev {
     // device 0 of a search: the merged hits and summed moments, and (several devices) the gathered regions packed shard
     // after shard
     hpfw::DevBuf d_pack, d_merged;
-    hpfw::DevBuf d_recv, d_send; // bytes: hits, then moments (group_search)
+    hpfw::DevBuf d_recv, d_send; // bytes: hits, then moments (group_search); neighbour keys (group_search_votes)
+    hpfw::DevBuf d_db_off;       // device 0: hpfw_gpu_group::db_off
     Comm comm;
 };
 
@@ -76,6 +78,10 @@ struct hpfw_gpu_group {
     std::string cache;
     int per_dev = 1; // shards on every device (uniform)
     int64_t n_clips = 0;
+    // the clip offsets of the whole index from 0, as index_build took them, and their copy on device 0 (the tally of the voting
+    // search runs there against global positions); uploaded by the first voting search after a build
+    std::vector<int64_t> db_off{0};
+    bool db_off_dirty = true;
     std::string exchange;
     bool resample = false; // hpfw_gpu_group_set_resample: applied to every shard collector, those made later included
     ~hpfw_gpu_group();
@@ -277,7 +283,12 @@ int hpfw_gpu_group_index_build(hpfw_gpu_group *g, const uint64_t *hp, const int6
         if (!r && s.hi > s.lo) r = hpfw_gpu_index_add(s.h.get(), hp, offsets + s.lo, s.hi - s.lo);
         return r;
     });
-    if (!rc) g->n_clips = n_clips;
+    if (!rc) {
+        g->n_clips = n_clips;
+        g->db_off.resize((size_t)n_clips + 1);
+        for (int64_t i = 0; i <= n_clips; ++i) g->db_off[(size_t)i] = offsets[i] - offsets[0];
+        g->db_off_dirty = true;
+    }
     return rc;
 }
 
@@ -285,6 +296,36 @@ int64_t hpfw_gpu_group_index_size(const hpfw_gpu_group *g) { return g ? g->n_cli
 
 // ---- the searches over the shards (include/hpfw_gpu_multi.h, include/hpfw_gpu_multi_search.h) ----
 namespace {
+
+// a shard's copy of the replicated queries, queued on its stream: `total` hashprints from q_hp + first
+int upload_queries(Shard &s, const uint64_t *q_hp, int64_t first, int64_t total)
+{
+    if (int r = ensure(s.d_q, (size_t)std::max<int64_t>(total, 1) * 8)) return r;
+    if (total && hipMemcpyAsync(s.d_q.get(), q_hp + first, (size_t)total * 8, hipMemcpyHostToDevice, s.stream.get()) != hipSuccess)
+        return fail(HPFW_E_HIP, "H2D copy of the queries failed");
+    return 0;
+}
+
+// the exchange step of every search: each device's stream waits for its shards' work, then ONE all-gather of the devices'
+// send buffers (`send` bytes each) into every device's receive buffer
+int all_gather(hpfw_gpu_group *g, size_t send)
+{
+    for (Dev &d : g->devs) {
+        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
+        for (int si : d.shards)
+            HIP_OK(hipStreamWaitEvent(d.stream.get(), g->shards[(size_t)si].done.get(), 0), "hipStreamWaitEvent");
+    }
+    NCCL_OK(ncclGroupStart(), "ncclGroupStart");
+    for (Dev &d : g->devs) {
+        ncclResult_t r = ncclAllGather(d.d_send.get(), d.d_recv.get(), send, ncclUint8, d.comm.get(), d.stream.get());
+        if (r != ncclSuccess) {
+            (void)ncclGroupEnd();
+            return fail(HPFW_E_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
+        }
+    }
+    NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
+    return 0;
+}
 
 // One body for the four searches: n_sets = 0 is the plain search (one query set per query, hpfw_hit), n_sets >= 1 the
 // transposed one (hpfw_shift_hit); stats non-null asks for the moments.  Every device's send buffer is
@@ -330,11 +371,9 @@ int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, 
     const auto fan_out = [&]() {
         return per_shard(g, [&](int i) {
             Shard &s = g->shards[(size_t)i];
-            int r = ensure(s.d_q, (size_t)std::max<int64_t>(total, 1) * 8);
+            int r = upload_queries(s, q_hp, q_off[0], total);
             if (r) return r;
             uint64_t *d_q = s.d_q.as<uint64_t>();
-            if (total && hipMemcpyAsync(d_q, q_hp + q_off[0], (size_t)total * 8, hipMemcpyHostToDevice, s.stream.get()) != hipSuccess)
-                return fail(HPFW_E_HIP, "H2D copy of the queries failed");
             char *base = g->devs[(size_t)s.dev_slot].d_send.as<char>();
             void *hits = base + (size_t)s.local * list;
             hpfw_dist_stats *st = stats ? reinterpret_cast<hpfw_dist_stats *>(base + hits_dev + (size_t)s.local * srows) : nullptr;
@@ -351,24 +390,7 @@ int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, 
             return 0;
         });
     };
-    // 2. the exchange step: one all-gather of a device's hits and moments
-    const auto all_gather = [&]() {
-        for (Dev &d : g->devs) {
-            HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-            for (int si : d.shards)
-                HIP_OK(hipStreamWaitEvent(d.stream.get(), g->shards[(size_t)si].done.get(), 0), "hipStreamWaitEvent");
-        }
-        NCCL_OK(ncclGroupStart(), "ncclGroupStart");
-        for (Dev &d : g->devs) {
-            ncclResult_t r = ncclAllGather(d.d_send.get(), d.d_recv.get(), send, ncclUint8, d.comm.get(), d.stream.get());
-            if (r != ncclSuccess) {
-                (void)ncclGroupEnd();
-                return fail(HPFW_E_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
-            }
-        }
-        NCCL_OK(ncclGroupEnd(), "ncclGroupEnd");
-        return 0;
-    };
+    // 2. the exchange step: one all-gather of a device's hits and moments (all_gather)
     // 3. device 0 merges the n lists and sums the n rows where they lie; the host takes n_q k hits and the rows.
     //    One device: its region is already in[shard][q][k] and in[shard][row]; several: the regions' halves are packed first.
     const auto merge_and_fetch = [&]() {
@@ -403,7 +425,7 @@ int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, 
     // From the first upload on, queued work reads rel and q_hp and writes out and stats: whichever step fails, the call
     // returns only after every stream of the group has been waited for.  A failure of the wait is reported when nothing
     // failed before it.
-    if (!(rc = fan_out()) && !(rc = all_gather())) rc = merge_and_fetch();
+    if (!(rc = fan_out()) && !(rc = all_gather(g, send))) rc = merge_and_fetch();
     const hipError_t waited = drain(g);
     if (!rc && waited != hipSuccess) rc = fail(HPFW_E_HIP, std::string("all-gather: ") + hipGetErrorString(waited));
     return rc;
@@ -422,6 +444,94 @@ int group_search_checked(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t 
 }
 
 } // namespace
+
+// ---- the voting search over the shards (include/hpfw_gpu_multi_votes.h) ----
+// Replicated queries -> per shard the 5 nearest windows of every query window in its own block of clips -> ONE all-gather of
+// the key lists -> device 0: the lists merged with every shard's first position added (the unsharded list, ties included),
+// the tally against the whole index's offsets, n_q votes back.
+int hpfw_gpu_group_search_votes(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, hpfw_vote *out)
+{
+    if (!g || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    if (n_q == 0) return 0;
+    std::vector<int64_t> rel((size_t)n_q + 1), wf((size_t)n_q + 1, 0);
+    for (int64_t i = 0; i <= n_q; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    for (int64_t i = 0; i < n_q; ++i) {
+        const int64_t k = rel[(size_t)i + 1] - rel[(size_t)i];
+        if (k < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        wf[(size_t)i + 1] = wf[(size_t)i] + std::max<int64_t>(k - 63, 0);
+    }
+    const int64_t total = rel[(size_t)n_q], n_win = wf[(size_t)n_q];
+    if (total > 0 && !q_hp) return fail(HPFW_E_INVALID, "null queries");
+    const int n = (int)g->shards.size(), m = (int)g->devs.size();
+    const size_t list = (size_t)n_win * 5 * 8; // bytes of keys per shard
+    const size_t keys_dev = list * g->per_dev;
+    const size_t send = (std::max<size_t>(keys_dev, 16) + 15) / 16 * 16;
+    const size_t votes = (size_t)n_q * sizeof(hpfw_vote);
+    for (Dev &d : g->devs) {
+        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
+        int rc = ensure(d.d_send, send);
+        if (!rc) rc = ensure(d.d_recv, send * m);
+        if (rc) return rc;
+    }
+    Dev &d0 = g->devs[0];
+    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+    const size_t list_al = (list + 15) / 16 * 16;
+    int rc = ensure(d0.d_merged, list_al + votes);
+    if (!rc && m > 1) rc = ensure(d0.d_pack, std::max<size_t>(keys_dev * m, 16));
+    if (!rc) rc = ensure(d0.d_db_off, g->db_off.size() * 8);
+    if (rc) return rc;
+    std::vector<int64_t> pos_base((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        int64_t lo, hi;
+        hpfw_gpu_shard_range(g->n_clips, i, n, &lo, &hi);
+        pos_base[(size_t)i] = g->db_off[(size_t)lo];
+    }
+    const auto fan_out = [&]() {
+        return per_shard(g, [&](int i) {
+            Shard &s = g->shards[(size_t)i];
+            int r = upload_queries(s, q_hp, q_off[0], total);
+            if (r) return r;
+            uint64_t *keys = reinterpret_cast<uint64_t *>(g->devs[(size_t)s.dev_slot].d_send.as<char>() + (size_t)s.local * list);
+            hipStream_t on = s.stream.get();
+            if ((r = hpfw_gpu_knn_windows_device(s.h.get(), s.d_q.as<uint64_t>(), rel.data(), n_q, keys, n_win * 5, on))) return r;
+            if (hipEventRecord(s.done.get(), on) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
+            return 0;
+        });
+    };
+    const auto merge_and_fetch = [&]() {
+        hipStream_t on = d0.stream.get();
+        HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+        const char *keys_in = d0.d_recv.as<char>();
+        if (m > 1) { // several devices: the regions packed shard after shard
+            char *pack = d0.d_pack.as<char>();
+            for (int i = 0; i < m && keys_dev; ++i)
+                HIP_OK(hipMemcpyAsync(pack + (size_t)i * keys_dev, keys_in + (size_t)i * send, keys_dev, hipMemcpyDeviceToDevice, on),
+                       "packing the gathered lists");
+            keys_in = pack;
+        }
+        if (g->db_off_dirty) {
+            HIP_OK(hipMemcpyAsync(d0.d_db_off.get(), g->db_off.data(), g->db_off.size() * 8, hipMemcpyHostToDevice, on), "H2D copy of the offsets");
+            HIP_OK(hipStreamSynchronize(on), "H2D copy of the offsets");
+            g->db_off_dirty = false;
+        }
+        hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h.get();
+        char *merged = d0.d_merged.as<char>();
+        hpfw_vote *d_votes = reinterpret_cast<hpfw_vote *>(merged + list_al);
+        int r = hpfw_gpu_merge_knn_device(h0, reinterpret_cast<const uint64_t *>(keys_in), pos_base.data(), n, n_win,
+                                          reinterpret_cast<uint64_t *>(merged), on);
+        if (!r)
+            r = hpfw_gpu_vote_windows_device(h0, reinterpret_cast<const uint64_t *>(merged), wf.data(), n_q, d0.d_db_off.as<int64_t>(), g->n_clips,
+                                             0, d_votes, on);
+        if (r) return r;
+        HIP_OK(hipMemcpyAsync(out, d_votes, votes, hipMemcpyDeviceToHost, on), "D2H copy of the votes");
+        return 0;
+    };
+    // as group_search: whichever step fails, the call returns only after every stream of the group has been waited for
+    if (!(rc = fan_out()) && !(rc = all_gather(g, send))) rc = merge_and_fetch();
+    const hipError_t waited = drain(g);
+    if (!rc && waited != hipSuccess) rc = fail(HPFW_E_HIP, std::string("all-gather: ") + hipGetErrorString(waited));
+    return rc;
+}
 
 int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out)
 {

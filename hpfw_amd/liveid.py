@@ -5,6 +5,8 @@
 index(files)  = storage.build(collector.prepare(files))           live_song_id.h:31-33
 search(files) = per query: calc_hashprint -> find -> report       live_song_id.h:35-54
 top(files, k) = the notebook's "ten best tracks" per query        liveid.ipynb cell 9
+top_votes(files) = the reference's default storage, AnnStorage::find: per query the winning (track, offset) bucket of the
+                   votes of its 0.8 s windows (annoy_storage.h:41-63, exact neighbours)
 timeline(file) = the songs of one long recording, window by window (not in the reference)
 streams(n)     = the same for n feeds that are still running, as their samples arrive
 """
@@ -26,7 +28,7 @@ class _ShardedIndex:
         self.group = multi.GpuGroup(devices)
         self._first = _lib.Gpu.from_handle(self.group.handle(0))
         for name in ("index_offsets", "search_topk", "search_topk_scored", "search_topk_transposed",
-                     "search_topk_transposed_scored"):
+                     "search_topk_transposed_scored", "search_votes"):
             setattr(self, name, getattr(self.group, name))
         self.geometry, self.resample = self._first.geometry, self._first.resample
 
@@ -56,6 +58,7 @@ class LiveSongIdentification:
         self._resample = resample
         self.collector.load(cache)                       # the constructor loads the cache, live_song_id.h:24
         self._cache = cache
+        self._device = int(device)
         self._gpu = _lib.Gpu(device) if devices is None else _ShardedIndex(list(devices))
         self.names: List[str] = []
 
@@ -100,6 +103,35 @@ class LiveSongIdentification:
                 out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"]))
                                          for h in row if h["clip"] != 0xFFFFFFFF])
         return out
+
+    def top_votes(self, filenames: Sequence[str]):
+        """the reference's default search (AnnStorage::find, annoy_storage.h:41-63, with exact neighbours; DESIGN.md section
+        19): per query position the 5 nearest 64-hashprint windows of the index vote 1 / (distance + 1) for (track, offset),
+        and the first bucket to exceed the running maximum wins.  Per query (label, (cnt, name, offset)), offset the
+        reference's i - p in hashprints (query position minus position in the track: a query cut from column s of a track
+        gives -s); None in place of the tuple for a file that yields fewer than 64 hashprints, and when the index has no item"""
+        hps = self.collector.calc_hashprints(list(filenames))
+        good = [i for i, (hp, _) in enumerate(hps) if hp is not None and hp.size >= 64]
+        out = [(f, None) for f in filenames]
+        if good and self.names:
+            off = np.zeros(len(good) + 1, np.int64)
+            np.cumsum([hps[i][0].size for i in good], out=off[1:])
+            votes = self._votes(np.concatenate([hps[i][0] for i in good]), off)
+            for v, i in zip(votes, good):
+                if v["clip"] != _lib.NO_CLIP:
+                    out[i] = (filenames[i], (float(v["cnt"]), self.names[int(v["clip"])], int(v["offset"])))
+        return out
+
+    def _votes(self, q_hp, q_off):
+        """VOTE_DTYPE [n_q] by the device tally: the group's search on a sharded index, else the one handle's with the queries
+        and the votes in device buffers of this call"""
+        if isinstance(self._gpu, _ShardedIndex):
+            return self._gpu.search_votes(q_hp, q_off)
+        import torch
+        d_q = torch.from_numpy(np.ascontiguousarray(q_hp, np.uint64).view(np.int64)).to(f"cuda:{self._device}")
+        d_out = torch.zeros((q_off.size - 1) * _lib.VOTE_DTYPE.itemsize, dtype=torch.uint8, device=d_q.device)
+        self._gpu.search_votes_dev(d_q.data_ptr(), q_off, d_out.data_ptr(), torch.cuda.current_stream(d_q.device).cuda_stream)
+        return d_out.cpu().numpy().view(_lib.VOTE_DTYPE).copy()
 
     def top_overlap(self, filenames: Sequence[str], k: int, min_overlap: int):
         """top() by the overlap search: the query may overhang either end of an indexed recording, and

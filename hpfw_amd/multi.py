@@ -26,6 +26,8 @@ SEARCH_EXPORTS = (
     "hpfw_gpu_group_search_topk_scored", "hpfw_gpu_group_search_topk_transposed",
     "hpfw_gpu_group_search_topk_transposed_scored", "hpfw_gpu_group_extract_windows_pcm16",
 )
+# include/hpfw_gpu_multi_votes.h
+VOTES_EXPORTS = ("hpfw_gpu_group_search_votes",)
 
 _multi = None
 
@@ -70,6 +72,7 @@ def lib():
     L.hpfw_gpu_group_search_topk_transposed.argtypes = [vp, vp, vp, i64, i32, i32, vp]
     L.hpfw_gpu_group_search_topk_transposed_scored.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     L.hpfw_gpu_group_extract_windows_pcm16.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp]
+    L.hpfw_gpu_group_search_votes.argtypes = [vp, vp, vp, i64, vp]
     _multi = L
     return L
 
@@ -173,6 +176,14 @@ class GpuGroup:
     def search_topk_transposed_scored(self, q_hp, q_off, n_shifts, k):
         """(SHIFT_HIT_DTYPE [n_q][k], STATS_DTYPE [n_q][n_shifts])"""
         return self._transposed(q_hp, q_off, n_shifts, k, True)
+
+    def search_votes(self, q_hp, q_off):
+        """Gpu.search_votes over the shards (include/hpfw_gpu_multi_votes.h): VOTE_DTYPE [n_q]"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        out = np.zeros(off.size - 1, _lib.VOTE_DTYPE)
+        _lib.check(lib().hpfw_gpu_group_search_votes(self._g, _lib._hp(q), _lib._hp(off), off.size - 1, _lib._hp(out)))
+        return out
 
     def extract_windows(self, pcm, win, hop, tempos=None, shifts=None):
         """Gpu.extract_windows with the windows sharded: uint64 [n_w][n_hp], or [n_w][V][n_hp_v] with shifts and / or tempos"""

@@ -10,6 +10,7 @@
 //
 // The finds of a query in another key or at another tempo (transposed.h, tempo.h) and the scored searches behind
 // hpfw::timeline (timeline.h) are here too, over include/hpfw_gpu_multi_search.h: same names and result types as GpuStorage's.
+// So is the voting search (find_votes, include/hpfw_gpu_multi_votes.h).
 //
 // Placement: HPFW_GPU_DEVICES="0,1,2,3,4,5,6,7" (one ordinal per shard; default: every visible device), or
 // the explicit constructor.
@@ -23,6 +24,7 @@
 
 #include "../../hpfw_gpu_multi.h"
 #include "../../hpfw_gpu_multi_search.h"
+#include "../../hpfw_gpu_multi_votes.h"
 
 namespace hpfw::db {
 
@@ -138,6 +140,23 @@ public:
         for (size_t q = 0; q < which.size(); ++q)
             if (hits[q].clip != 0xffffffffu) out[which[q]] = {names_[hits[q].clip], (size_t)hits[q].dist, (int64_t)hits[q].offset};
         return out;
+    }
+
+    /// GpuStorage::find_votes over the shards (AnnStorage::find, annoy_storage.h:41-63, with exact neighbours): the
+    /// reference's {filename, cnt, offset} of the winning bucket, {"", 0, 0} when nothing votes
+    struct VoteResult { // annoy_storage.h:16-20
+        std::string filename;
+        float cnt;
+        int64_t offset;
+    };
+    auto find_votes(const typename Collector::Hashprint &hp) const -> VoteResult
+    {
+        if (hp.empty() || names_.empty()) return {"", 0.0f, 0};
+        const int64_t q_off[2] = {0, (int64_t)hp.size()};
+        hpfw_vote v;
+        check(hpfw_gpu_group_search_votes(g_, hp.data(), q_off, 1, &v));
+        if (v.clip == 0xffffffffu) return {"", 0.0f, 0};
+        return {names_[v.clip], v.cnt, v.offset};
     }
 
 private:

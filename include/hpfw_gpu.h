@@ -431,6 +431,33 @@ int hpfw_gpu_search_votes(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_of
  * ascending, ~0 where fewer exist; windows of all queries in order, n_windows = sum max(k - 63, 0) */
 int hpfw_gpu_knn_windows(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q,
                          uint64_t *keys, int64_t keys_cap);
+/* ---- the voting search with device buffers on a stream.  The tally runs on the device: events are
+ * grouped by bucket with a stable sort, every bucket's count is accumulated in the arithmetic above in window order, and the
+ * winner is the event earliest in stream order whose post-event count is the query's largest -- the result of the loop of
+ * hpfw_gpu_search_votes, bit for bit, whatever the scheduling.  Windows are processed in groups of whole queries whose
+ * workspaces stay within 256 MiB (HPFW_VOTES_GROUP_WINDOWS in the environment: fewer windows per group), so these calls
+ * have no limit on the windows of one call; the 256 MiB are an estimate, and one query with more windows than a group is
+ * processed alone, above it.  Bad arguments are refused before any device work.
+ * q_off indexes d_q_hp by ABSOLUTE offset: query q is d_q_hp[q_off[q] .. q_off[q+1]), as hpfw_gpu_search_topk_device takes it
+ * (the host functions above upload from q_off[0] on instead).
+ * Not fully asynchronous: every call uploads its small host tables (q_off, w_first) and WAITS for the caller's stream before
+ * it queues its kernels, so it returns with its work queued but cannot be captured into a graph. */
+/* keys [n_windows][5] on the device, ascending per window, positions in THIS handle's index; keys_cap in keys */
+int hpfw_gpu_knn_windows_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                uint64_t *d_keys, int64_t keys_cap, void *stream);
+/* the tally alone: window w of the call is d_keys[w][5]; w_first [n_q + 1] host, query q owns the windows
+ * [w_first[q], w_first[q + 1]); d_db_off [n_clips + 1] device; clip_base is added to the reported clip; d_out [n_q] */
+int hpfw_gpu_vote_windows_device(hpfw_gpu *h, const uint64_t *d_keys, const int64_t *w_first, int64_t n_q,
+                                 const int64_t *d_db_off, int64_t n_clips, uint32_t clip_base,
+                                 hpfw_vote *d_out, void *stream);
+/* knn + tally against the handle's index; d_q_hp and d_out [n_q] device, q_off host */
+int hpfw_gpu_search_votes_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                 hpfw_vote *d_out, void *stream);
+/* the per-shard neighbour lists of a sharded index merged: d_in [n_shards][n_win][5], pos_base [n_shards] host (the
+ * hashprints in earlier shards: non-negative, non-decreasing) is added to the position of every real key; d_out [n_win][5]
+ * the 5 smallest, ascending, ~0 behind them.  n_shards <= 64. */
+int hpfw_gpu_merge_knn_device(hpfw_gpu *h, const uint64_t *d_in, const int64_t *pos_base, int n_shards,
+                              int64_t n_win, uint64_t *d_out, void *stream);
 
 /* deterministic merge of per-shard top-k lists (e.g. after an all-gather): in [n_shards][n_q][k]
  * -> out [n_q][k], ascending (dist, clip).  Host arrays. */
