@@ -1,6 +1,6 @@
 // combiner.h -- AudioCombiner's exact-hash inverted index and offset-vote search (reference
 // include/hpfw/audioproblems/combiner/combiner.h:90-132) on the device: the index and the orchestration of
-// k_combiner.hip's kernels.  search.hip wraps it in the C-ABI (include/hpfw_gpu.h, hpfw_gpu_combiner_*).
+// k_combiner.hip's kernels.  combiner.hip wraps it in the C-ABI (include/hpfw_gpu.h, hpfw_gpu_combiner_*).
 #pragma once
 #include <cstdint>
 #include <string>

@@ -1,5 +1,5 @@
 // handle.h -- what the sources of the C-ABI declared in include/hpfw_gpu.h (handle.hip, plans.hip, extract.hip, learn.hip,
-// search.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
+// search.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
 // ParallelCollector::collect_fingerprints' parallel_for, reference
 // include/hpfw/core/parallel_collector.h:115-137) and MemoryStorage::build/find
 // (include/hpfw/audioproblems/live-song-id/storage.h:21-64).  All arithmetic is in the kernels.
@@ -131,7 +131,7 @@ struct hpfw_gpu {
     // extraction workspace: yp, x, mag, proj, wave maxima [clip][121][16], pairs, second planar buffer of the chirp-z
     // forward transform
     DevBuf ws[7];
-    // the index and the scratch of its searches (search.hip)
+    // the index and the scratch of its searches (search.hip, votes.hip)
     struct Index {
         DevBuf d_db; // uint64 hashprints
         std::vector<int64_t> db_off{0};
@@ -216,7 +216,7 @@ struct hpfw_gpu {
     int k_launches[K_COUNT] = {0};
     // AudioCombiner's inverted index (k_combiner.hip), created on first use
     std::unique_ptr<hpfw::Combiner> combiner;
-    // exact cross-correlation (k_xcorr.hip, search.hip): the jobs and their parts on the device, r when the caller keeps none
+    // exact cross-correlation (k_xcorr.hip, combiner.hip): the jobs and their parts on the device, r when the caller keeps none
     struct Xcorr {
         DevBuf d_tab, d_r;
     } xcorr;
@@ -345,6 +345,51 @@ struct HostTrip {
         return rc;
     }
 };
+
+// the host round trip of a search: the hashprints (elements Q) of query sets [0, n_sets) uploaded, their offsets rebased
+// to 0, device(d_q, rel, d_out) queued on the null stream, the n_out hits it wrote downloaded
+// (scored searches: the n_stats rows of moments the call wrote downloaded as well, device(d_q, rel, d_out, d_stats))
+template <class Q, class Hit, class Device>
+int search_round_trip_scored(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, int64_t n_stats,
+                             hpfw_dist_stats *stats, Device device)
+{
+    const int64_t total = q_off[n_sets] - q_off[0];
+    if (total < 0) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+    if (total && !q_hp) return fail(HPFW_E_INVALID, "null queries");
+    std::vector<int64_t> rel((size_t)n_sets + 1);
+    for (int64_t i = 0; i <= n_sets; ++i) rel[(size_t)i] = q_off[i] - q_off[0];
+    HostTrip t;
+    const Q *d_q = t.take<Q>((size_t)std::max<int64_t>(total, 1) * sizeof(Q), total ? q_hp + q_off[0] : nullptr);
+    Hit *d_out = t.take<Hit>((size_t)n_out * sizeof(Hit), nullptr, -1, out);
+    hpfw_dist_stats *d_stats = n_stats ? t.take<hpfw_dist_stats>((size_t)n_stats * sizeof(hpfw_dist_stats), nullptr, -1, stats) : nullptr;
+    return t.run(true, [&] { return device(d_q, rel.data(), d_out, d_stats); });
+}
+
+template <class Q, class Hit, class Device>
+int search_round_trip(const Q *q_hp, const int64_t *q_off, int64_t n_sets, int64_t n_out, Hit *out, Device device)
+{
+    return search_round_trip_scored(q_hp, q_off, n_sets, n_out, out, 0, nullptr,
+                                    [&](const Q *d_q, const int64_t *rel, Hit *d_out, hpfw_dist_stats *) { return device(d_q, rel, d_out); });
+}
+
+// the index's offsets to the device when they changed since the last upload: on s, which the host then waits for
+inline int upload_db_off(hpfw_gpu *h, hipStream_t s)
+{
+    if (!h->index.db_off_dirty) return 0;
+    if (int rc = ensure(h->index.d_db_off, h->index.db_off.size() * 8)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->index.d_db_off.get(), h->index.db_off.data(), h->index.db_off.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->index.db_off_dirty = false;
+    return 0;
+}
+
+// the hashprints of the index's longest clip
+inline int64_t index_longest_clip(const hpfw_gpu *h)
+{
+    int64_t n_max = 0;
+    for (size_t i = 0; i + 1 < h->index.db_off.size(); ++i) n_max = std::max(n_max, h->index.db_off[i + 1] - h->index.db_off[i]);
+    return n_max;
+}
 
 // plans.hip
 int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out);

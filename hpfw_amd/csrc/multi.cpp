@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -327,9 +328,77 @@ int all_gather(hpfw_gpu_group *g, size_t send)
     return 0;
 }
 
+// The skeleton of every search over the shards.  A shard writes one or two parts (part0, part1 bytes per shard; part1 may be
+// 0): a device's send buffer is [local shard] part 0, then [local shard] part 1, and the gathered buffer holds one such
+// region per device, 16-byte aligned.
+//   1. every shard, on its own stream: the replicated queries in (`total` hashprints from q_hp + first), then
+//      shard_call(shard, its slot of part 0, its slot of part 1);
+//   2. ONE all-gather of the devices' regions (all_gather);
+//   3. on device 0's stream: with several devices the regions' parts packed shard after shard, then
+//      finish(device 0, part 0 of all n shards, part 1 of all n shards, the stream), which queues what it makes of them in
+//      d_merged (`merged` bytes) and the copy back to the host.
+// From the first upload on, queued work reads and writes the caller's host arrays: whichever step fails, the call returns only
+// after every stream of the group has been waited for.  A failure of the wait is reported when nothing failed before it.
+using ShardCall = std::function<int(Shard &, void *, void *)>;
+using Finish = std::function<int(Dev &, const char *, const char *, hipStream_t)>;
+static int exchange(hpfw_gpu_group *g, const uint64_t *q_hp, int64_t first, int64_t total, size_t part0, size_t part1, size_t merged,
+                    const ShardCall &shard_call, const Finish &finish)
+{
+    const int m = (int)g->devs.size();
+    const size_t dev0 = part0 * g->per_dev, dev1 = part1 * g->per_dev;
+    const size_t send = (std::max<size_t>(dev0 + dev1, 16) + 15) / 16 * 16;
+    for (Dev &d : g->devs) {
+        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
+        int rc = ensure(d.d_send, send);
+        if (!rc) rc = ensure(d.d_recv, send * m);
+        if (rc) return rc;
+    }
+    Dev &d0 = g->devs[0];
+    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+    int rc = ensure(d0.d_merged, merged);
+    if (!rc && m > 1) rc = ensure(d0.d_pack, std::max<size_t>((dev0 + dev1) * m, 16));
+    if (rc) return rc;
+    const auto fan_out = [&]() {
+        return per_shard(g, [&](int i) {
+            Shard &s = g->shards[(size_t)i];
+            if (int r = upload_queries(s, q_hp, first, total)) return r;
+            char *base = g->devs[(size_t)s.dev_slot].d_send.as<char>();
+            if (int r = shard_call(s, base + (size_t)s.local * part0, base + dev0 + (size_t)s.local * part1)) return r;
+            if (hipEventRecord(s.done.get(), s.stream.get()) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
+            return 0;
+        });
+    };
+    // one device: its region is already [shard] part 0, [shard] part 1
+    const auto pack_and_finish = [&]() {
+        hipStream_t on = d0.stream.get();
+        HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
+        const char *recv = d0.d_recv.as<char>();
+        const char *in0 = recv, *in1 = recv + dev0;
+        if (m > 1) {
+            char *pack = d0.d_pack.as<char>();
+            for (int i = 0; i < m; ++i) {
+                if (dev0)
+                    HIP_OK(hipMemcpyAsync(pack + (size_t)i * dev0, recv + (size_t)i * send, dev0, hipMemcpyDeviceToDevice, on),
+                           "packing the gathered lists");
+                if (dev1)
+                    HIP_OK(hipMemcpyAsync(pack + (size_t)m * dev0 + (size_t)i * dev1, recv + (size_t)i * send + dev0, dev1,
+                                          hipMemcpyDeviceToDevice, on),
+                           "packing the gathered moments");
+            }
+            in0 = pack;
+            in1 = pack + (size_t)m * dev0;
+        }
+        return finish(d0, in0, in1, on);
+    };
+    if (!(rc = fan_out()) && !(rc = all_gather(g, send))) rc = pack_and_finish();
+    const hipError_t waited = drain(g);
+    if (!rc && waited != hipSuccess) rc = fail(HPFW_E_HIP, std::string("all-gather: ") + hipGetErrorString(waited));
+    return rc;
+}
+
 // One body for the four searches: n_sets = 0 is the plain search (one query set per query, hpfw_hit), n_sets >= 1 the
-// transposed one (hpfw_shift_hit); stats non-null asks for the moments.  Every device's send buffer is
-// [local shard][n_q][k] hits, then [local shard][rows] moments; the gathered buffer holds one such region per device.
+// transposed one (hpfw_shift_hit); stats non-null asks for the moments.  A shard's parts are its [n_q][k] hits and its
+// [rows] moments; device 0 merges the n lists and sums the n rows, and the host takes n_q k hits and the rows.
 int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_sets, int k, void *out,
                  hpfw_dist_stats *stats)
 {
@@ -350,85 +419,34 @@ int group_search(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, 
     if (g->n_clips > 0 && k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
     if (stats && (unsigned __int128)g->n_clips * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
         return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
-    const int n = (int)g->shards.size(), m = (int)g->devs.size();
+    const int n = (int)g->shards.size();
     const size_t list = (size_t)n_q * k * sizeof(hpfw_hit);                  // bytes of hits per shard
     const size_t srows = stats ? (size_t)rows * sizeof(hpfw_dist_stats) : 0; // bytes of moments per shard
-    const size_t hits_dev = list * g->per_dev, stats_dev = srows * g->per_dev;
-    const size_t send = (hits_dev + stats_dev + 15) / 16 * 16; // a device's region of the gathered buffer stays 16-byte aligned
-    for (Dev &d : g->devs) {
-        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-        int rc = ensure(d.d_send, send);
-        if (!rc) rc = ensure(d.d_recv, send * m);
-        if (rc) return rc;
-    }
-    Dev &d0 = g->devs[0];
-    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
-    int rc = ensure(d0.d_merged, list + srows);
-    if (!rc && m > 1) rc = ensure(d0.d_pack, (hits_dev + stats_dev) * m);
-    if (rc) return rc;
-
-    // 1. every shard: replicated queries in, its own search into its slots of the device's send buffer
-    const auto fan_out = [&]() {
-        return per_shard(g, [&](int i) {
-            Shard &s = g->shards[(size_t)i];
-            int r = upload_queries(s, q_hp, q_off[0], total);
-            if (r) return r;
+    return exchange(
+        g, q_hp, q_off[0], total, list, srows, list + srows,
+        [&](Shard &s, void *hits, void *moments) {
             uint64_t *d_q = s.d_q.as<uint64_t>();
-            char *base = g->devs[(size_t)s.dev_slot].d_send.as<char>();
-            void *hits = base + (size_t)s.local * list;
-            hpfw_dist_stats *st = stats ? reinterpret_cast<hpfw_dist_stats *>(base + hits_dev + (size_t)s.local * srows) : nullptr;
+            hpfw_dist_stats *st = stats ? static_cast<hpfw_dist_stats *>(moments) : nullptr;
             hpfw_gpu *h = s.h.get();
             hipStream_t on = s.stream.get();
             if (transposed)
-                r = st ? hpfw_gpu_search_topk_transposed_scored_device(h, d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, st, on)
-                       : hpfw_gpu_search_topk_transposed_device(h, d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, on);
-            else
-                r = st ? hpfw_gpu_search_topk_scored_device(h, d_q, rel.data(), n_q, k, (hpfw_hit *)hits, st, on)
-                       : hpfw_gpu_search_topk_device(h, d_q, rel.data(), n_q, k, (hpfw_hit *)hits, on);
+                return st ? hpfw_gpu_search_topk_transposed_scored_device(h, d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, st, on)
+                          : hpfw_gpu_search_topk_transposed_device(h, d_q, rel.data(), n_q, n_sets, k, (hpfw_shift_hit *)hits, on);
+            return st ? hpfw_gpu_search_topk_scored_device(h, d_q, rel.data(), n_q, k, (hpfw_hit *)hits, st, on)
+                      : hpfw_gpu_search_topk_device(h, d_q, rel.data(), n_q, k, (hpfw_hit *)hits, on);
+        },
+        [&](Dev &d0, const char *hits_in, const char *stats_in, hipStream_t on) {
+            hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h.get();
+            char *merged = d0.d_merged.as<char>();
+            int r = hpfw_gpu_merge_topk_device(h0, hits_in, n, n_q, k, merged, on);
+            if (!r && stats)
+                r = hpfw_gpu_sum_stats_device(h0, reinterpret_cast<const hpfw_dist_stats *>(stats_in), n, rows,
+                                              reinterpret_cast<hpfw_dist_stats *>(merged + list), on);
             if (r) return r;
-            if (hipEventRecord(s.done.get(), on) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
+            HIP_OK(hipMemcpyAsync(out, merged, list, hipMemcpyDeviceToHost, on), "D2H copy of the merged lists");
+            if (stats) HIP_OK(hipMemcpyAsync(stats, merged + list, srows, hipMemcpyDeviceToHost, on), "D2H copy of the moments");
             return 0;
         });
-    };
-    // 2. the exchange step: one all-gather of a device's hits and moments (all_gather)
-    // 3. device 0 merges the n lists and sums the n rows where they lie; the host takes n_q k hits and the rows.
-    //    One device: its region is already in[shard][q][k] and in[shard][row]; several: the regions' halves are packed first.
-    const auto merge_and_fetch = [&]() {
-        hipStream_t on = d0.stream.get();
-        HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
-        const char *recv = d0.d_recv.as<char>();
-        const char *hits_in = recv, *stats_in = recv + hits_dev;
-        if (m > 1) {
-            char *pack = d0.d_pack.as<char>();
-            for (int i = 0; i < m; ++i) {
-                HIP_OK(hipMemcpyAsync(pack + (size_t)i * hits_dev, recv + (size_t)i * send, hits_dev, hipMemcpyDeviceToDevice, on),
-                       "packing the gathered lists");
-                if (stats_dev)
-                    HIP_OK(hipMemcpyAsync(pack + (size_t)m * hits_dev + (size_t)i * stats_dev, recv + (size_t)i * send + hits_dev, stats_dev,
-                                          hipMemcpyDeviceToDevice, on),
-                           "packing the gathered moments");
-            }
-            hits_in = pack;
-            stats_in = pack + (size_t)m * hits_dev;
-        }
-        hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h.get();
-        char *merged = d0.d_merged.as<char>();
-        int r = hpfw_gpu_merge_topk_device(h0, hits_in, n, n_q, k, merged, on);
-        if (!r && stats)
-            r = hpfw_gpu_sum_stats_device(h0, reinterpret_cast<const hpfw_dist_stats *>(stats_in), n, rows,
-                                          reinterpret_cast<hpfw_dist_stats *>(merged + list), on);
-        if (r) return r;
-        HIP_OK(hipMemcpyAsync(out, merged, list, hipMemcpyDeviceToHost, on), "D2H copy of the merged lists");
-        if (stats) HIP_OK(hipMemcpyAsync(stats, merged + list, srows, hipMemcpyDeviceToHost, on), "D2H copy of the moments");
-        return 0;
-    };
-    // From the first upload on, queued work reads rel and q_hp and writes out and stats: whichever step fails, the call
-    // returns only after every stream of the group has been waited for.  A failure of the wait is reported when nothing
-    // failed before it.
-    if (!(rc = fan_out()) && !(rc = all_gather(g, send))) rc = merge_and_fetch();
-    const hipError_t waited = drain(g);
-    if (!rc && waited != hipSuccess) rc = fail(HPFW_E_HIP, std::string("all-gather: ") + hipGetErrorString(waited));
-    return rc;
 }
 
 // the argument checks of the one-handle functions, before the group or any device is touched
@@ -462,75 +480,41 @@ int hpfw_gpu_group_search_votes(hpfw_gpu_group *g, const uint64_t *q_hp, const i
     }
     const int64_t total = rel[(size_t)n_q], n_win = wf[(size_t)n_q];
     if (total > 0 && !q_hp) return fail(HPFW_E_INVALID, "null queries");
-    const int n = (int)g->shards.size(), m = (int)g->devs.size();
+    const int n = (int)g->shards.size();
     const size_t list = (size_t)n_win * 5 * 8; // bytes of keys per shard
-    const size_t keys_dev = list * g->per_dev;
-    const size_t send = (std::max<size_t>(keys_dev, 16) + 15) / 16 * 16;
-    const size_t votes = (size_t)n_q * sizeof(hpfw_vote);
-    for (Dev &d : g->devs) {
-        HIP_OK(hipSetDevice(d.device), "hipSetDevice");
-        int rc = ensure(d.d_send, send);
-        if (!rc) rc = ensure(d.d_recv, send * m);
-        if (rc) return rc;
-    }
-    Dev &d0 = g->devs[0];
-    HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
-    const size_t list_al = (list + 15) / 16 * 16;
-    int rc = ensure(d0.d_merged, list_al + votes);
-    if (!rc && m > 1) rc = ensure(d0.d_pack, std::max<size_t>(keys_dev * m, 16));
-    if (!rc) rc = ensure(d0.d_db_off, g->db_off.size() * 8);
-    if (rc) return rc;
+    const size_t list_al = (list + 15) / 16 * 16, votes = (size_t)n_q * sizeof(hpfw_vote);
+    HIP_OK(hipSetDevice(g->devs[0].device), "hipSetDevice");
+    if (int rc = ensure(g->devs[0].d_db_off, g->db_off.size() * 8)) return rc;
     std::vector<int64_t> pos_base((size_t)n);
     for (int i = 0; i < n; ++i) {
         int64_t lo, hi;
         hpfw_gpu_shard_range(g->n_clips, i, n, &lo, &hi);
         pos_base[(size_t)i] = g->db_off[(size_t)lo];
     }
-    const auto fan_out = [&]() {
-        return per_shard(g, [&](int i) {
-            Shard &s = g->shards[(size_t)i];
-            int r = upload_queries(s, q_hp, q_off[0], total);
+    return exchange(
+        g, q_hp, q_off[0], total, list, 0, list_al + votes,
+        [&](Shard &s, void *keys, void *) {
+            return hpfw_gpu_knn_windows_device(s.h.get(), s.d_q.as<uint64_t>(), rel.data(), n_q, static_cast<uint64_t *>(keys), n_win * 5,
+                                               s.stream.get());
+        },
+        [&](Dev &d0, const char *keys_in, const char *, hipStream_t on) {
+            if (g->db_off_dirty) {
+                HIP_OK(hipMemcpyAsync(d0.d_db_off.get(), g->db_off.data(), g->db_off.size() * 8, hipMemcpyHostToDevice, on), "H2D copy of the offsets");
+                HIP_OK(hipStreamSynchronize(on), "H2D copy of the offsets");
+                g->db_off_dirty = false;
+            }
+            hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h.get();
+            char *merged = d0.d_merged.as<char>();
+            hpfw_vote *d_votes = reinterpret_cast<hpfw_vote *>(merged + list_al);
+            int r = hpfw_gpu_merge_knn_device(h0, reinterpret_cast<const uint64_t *>(keys_in), pos_base.data(), n, n_win,
+                                              reinterpret_cast<uint64_t *>(merged), on);
+            if (!r)
+                r = hpfw_gpu_vote_windows_device(h0, reinterpret_cast<const uint64_t *>(merged), wf.data(), n_q, d0.d_db_off.as<int64_t>(), g->n_clips,
+                                                 0, d_votes, on);
             if (r) return r;
-            uint64_t *keys = reinterpret_cast<uint64_t *>(g->devs[(size_t)s.dev_slot].d_send.as<char>() + (size_t)s.local * list);
-            hipStream_t on = s.stream.get();
-            if ((r = hpfw_gpu_knn_windows_device(s.h.get(), s.d_q.as<uint64_t>(), rel.data(), n_q, keys, n_win * 5, on))) return r;
-            if (hipEventRecord(s.done.get(), on) != hipSuccess) return fail(HPFW_E_HIP, "event record failed");
+            HIP_OK(hipMemcpyAsync(out, d_votes, votes, hipMemcpyDeviceToHost, on), "D2H copy of the votes");
             return 0;
         });
-    };
-    const auto merge_and_fetch = [&]() {
-        hipStream_t on = d0.stream.get();
-        HIP_OK(hipSetDevice(d0.device), "hipSetDevice");
-        const char *keys_in = d0.d_recv.as<char>();
-        if (m > 1) { // several devices: the regions packed shard after shard
-            char *pack = d0.d_pack.as<char>();
-            for (int i = 0; i < m && keys_dev; ++i)
-                HIP_OK(hipMemcpyAsync(pack + (size_t)i * keys_dev, keys_in + (size_t)i * send, keys_dev, hipMemcpyDeviceToDevice, on),
-                       "packing the gathered lists");
-            keys_in = pack;
-        }
-        if (g->db_off_dirty) {
-            HIP_OK(hipMemcpyAsync(d0.d_db_off.get(), g->db_off.data(), g->db_off.size() * 8, hipMemcpyHostToDevice, on), "H2D copy of the offsets");
-            HIP_OK(hipStreamSynchronize(on), "H2D copy of the offsets");
-            g->db_off_dirty = false;
-        }
-        hpfw_gpu *h0 = g->shards[(size_t)d0.shards[0]].h.get();
-        char *merged = d0.d_merged.as<char>();
-        hpfw_vote *d_votes = reinterpret_cast<hpfw_vote *>(merged + list_al);
-        int r = hpfw_gpu_merge_knn_device(h0, reinterpret_cast<const uint64_t *>(keys_in), pos_base.data(), n, n_win,
-                                          reinterpret_cast<uint64_t *>(merged), on);
-        if (!r)
-            r = hpfw_gpu_vote_windows_device(h0, reinterpret_cast<const uint64_t *>(merged), wf.data(), n_q, d0.d_db_off.as<int64_t>(), g->n_clips,
-                                             0, d_votes, on);
-        if (r) return r;
-        HIP_OK(hipMemcpyAsync(out, d_votes, votes, hipMemcpyDeviceToHost, on), "D2H copy of the votes");
-        return 0;
-    };
-    // as group_search: whichever step fails, the call returns only after every stream of the group has been waited for
-    if (!(rc = fan_out()) && !(rc = all_gather(g, send))) rc = merge_and_fetch();
-    const hipError_t waited = drain(g);
-    if (!rc && waited != hipSuccess) rc = fail(HPFW_E_HIP, std::string("all-gather: ") + hipGetErrorString(waited));
-    return rc;
 }
 
 int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out)

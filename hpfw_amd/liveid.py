@@ -58,7 +58,6 @@ class LiveSongIdentification:
         self._resample = resample
         self.collector.load(cache)                       # the constructor loads the cache, live_song_id.h:24
         self._cache = cache
-        self._device = int(device)
         self._gpu = _lib.Gpu(device) if devices is None else _ShardedIndex(list(devices))
         self.names: List[str] = []
 
@@ -123,15 +122,8 @@ class LiveSongIdentification:
         return out
 
     def _votes(self, q_hp, q_off):
-        """VOTE_DTYPE [n_q] by the device tally: the group's search on a sharded index, else the one handle's with the queries
-        and the votes in device buffers of this call"""
-        if isinstance(self._gpu, _ShardedIndex):
-            return self._gpu.search_votes(q_hp, q_off)
-        import torch
-        d_q = torch.from_numpy(np.ascontiguousarray(q_hp, np.uint64).view(np.int64)).to(f"cuda:{self._device}")
-        d_out = torch.zeros((q_off.size - 1) * _lib.VOTE_DTYPE.itemsize, dtype=torch.uint8, device=d_q.device)
-        self._gpu.search_votes_dev(d_q.data_ptr(), q_off, d_out.data_ptr(), torch.cuda.current_stream(d_q.device).cuda_stream)
-        return d_out.cpu().numpy().view(_lib.VOTE_DTYPE).copy()
+        """VOTE_DTYPE [n_q] by the device tally, on one handle as on a sharded index"""
+        return self._gpu.search_votes(q_hp, q_off)
 
     def top_overlap(self, filenames: Sequence[str], k: int, min_overlap: int):
         """top() by the overlap search: the query may overhang either end of an indexed recording, and

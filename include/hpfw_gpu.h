@@ -417,7 +417,13 @@ int hpfw_gpu_search_topk(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
  * nearest in Hamming distance over the 4096 bits, by (distance, position in the database), vote
  * cnt[clip][i - p] += 1 / (d + 1) (float accumulator, :53); the first bucket to exceed the running
  * maximum wins (:55-59).  Host arrays; out[n_q]; clip = 0xffffffff when the query has no window or the
- * index no item. */
+ * index no item.
+ * The two host functions are round trips over hpfw_gpu_search_votes_device and hpfw_gpu_knn_windows_device below on the
+ * null stream: the queries are uploaded from q_off[0] on, the offsets rebased, the result downloaded.  Null h, q_hp, q_off,
+ * out / keys, n_q < 0, a decreasing q_off and too small a keys_cap are refused (HPFW_E_INVALID) before any device work.
+ * Their limits are the device calls': windows are processed in groups of about 256 MiB of workspace, so a call may hold any
+ * number of windows, and ONE QUERY may hold at most 2 097 120 (HPFW_E_UNSUPPORTED).  (Earlier versions refused more than
+ * 2 097 120 windows in one call; every call they accepted is accepted, with the same answer.) */
 typedef struct {
     uint32_t clip;
     uint32_t pad;
@@ -433,8 +439,8 @@ int hpfw_gpu_knn_windows(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off
                          uint64_t *keys, int64_t keys_cap);
 /* ---- the voting search with device buffers on a stream.  The tally runs on the device: events are
  * grouped by bucket with a stable sort, every bucket's count is accumulated in the arithmetic above in window order, and the
- * winner is the event earliest in stream order whose post-event count is the query's largest -- the result of the loop of
- * hpfw_gpu_search_votes, bit for bit, whatever the scheduling.  Windows are processed in groups of whole queries whose
+ * winner is the event earliest in stream order whose post-event count is the query's largest -- the result of the reference's
+ * sequential loop (annoy_storage.h:47-60), bit for bit, whatever the scheduling.  Windows are processed in groups of whole queries whose
  * workspaces stay within 256 MiB (HPFW_VOTES_GROUP_WINDOWS in the environment: fewer windows per group), so these calls
  * have no limit on the windows of one call; the 256 MiB are an estimate, and one query with more windows than a group is
  * processed alone, above it.  Bad arguments are refused before any device work.

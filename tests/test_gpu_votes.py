@@ -1,5 +1,5 @@
 """GPU tests of the voting search's device tally: the tally alone on the fixture of tests/votes_ref.py,
-the sorted neighbour keys, the search against the unchanged host function and the oracle, the shard merge, the search over a
+the sorted neighbour keys, the search against the host function (a round trip over it) and the oracle, the shard merge, the search over a
 sharded index, LiveSongIdentification.top_votes end to end, and the C++ facades.  Byte for byte unless stated."""
 import os
 import subprocess
@@ -188,6 +188,33 @@ def test_search_equals_the_host_function_and_the_oracle(gpu, oracle, torch_cuda,
     assert (want["clip"] != NO_CLIP).sum() >= 4 and (want["clip"] == NO_CLIP).any()
     if case == "workload":
         assert [(int(v["clip"]), int(v["offset"])) for v in got[:3]] == [(3, -700), (4, -2000), (0, -50)]
+
+
+def _offset_case():
+    """clips of 130, 64, 63 and 0 hashprints; a query buffer whose first 17 hashprints belong to no query, then 100 hashprints
+    cut from clip 0 at position 20 with 5 bit flips each, a copy of clip 1, 10 random hashprints and a query of none"""
+    rng = np.random.default_rng(77)
+    clips = [_rand(rng, n) for n in (130, 64, 63, 0)]
+    qs = [_flipped(rng, clips[0][20:120], 5), clips[1].copy(), _rand(rng, 10), _rand(rng, 0)]
+    return clips, qs, np.concatenate([_rand(rng, 17)] + qs), np.array([17, 117, 181, 191, 191], np.int64)
+
+
+@pytest.mark.parametrize("group", [None, 16], ids=["default-groups", "groups-of-16"])
+def test_host_calls_take_the_queries_from_q_off_0(gpu, oracle, torch_cuda, monkeypatch, group):
+    """the host functions upload from q_off[0] on and rebase the offsets: ragged queries behind 17 unused hashprints give the
+    oracle's keys and votes, and search_votes_dev on the same absolute offsets the same bytes; with groups of 16 windows the
+    first query's 37 windows are a group of their own"""
+    clips, qs, q_hp, q_off = _offset_case()
+    _index(gpu, clips)
+    want_keys, votes = _reference(oracle, "offset", clips, qs)
+    want = _vote_records(votes)
+    assert [(int(v["clip"]), int(v["offset"])) for v in want[:2]] == [(0, -20), (1, 0)] and np.all(want["clip"][2:] == NO_CLIP)
+    assert want_keys.shape == (37 + 1, 5)
+    if group is not None:
+        monkeypatch.setenv("HPFW_VOTES_GROUP_WINDOWS", str(group))
+    assert np.array_equal(gpu.knn_windows(q_hp, q_off), want_keys)
+    assert gpu.search_votes(q_hp, q_off).tobytes() == want.tobytes()
+    assert _search_dev(torch_cuda, gpu, q_hp, q_off).tobytes() == want.tobytes()
 
 
 def test_search_edge_cases(gpu, torch_cuda):
@@ -391,7 +418,7 @@ int main(int argc, char **argv)
 
 
 def test_cpp_find_votes_on_both_storages(tmp_path, filters, torch_cuda):
-    """GpuStorage::find_votes (the host tally) and ShardedGpuStorage{0, 0}::find_votes (the device tally over two shards) print
+    """GpuStorage::find_votes (the host function on one handle) and ShardedGpuStorage{0, 0}::find_votes (two shards) print
     the same name, count and offset for the end-to-end queries"""
     _, song_files, query_files = _songs_and_queries(tmp_path)
     src, exe = tmp_path / "votes.cpp", str(tmp_path / "votes")

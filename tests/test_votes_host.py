@@ -67,8 +67,21 @@ def test_bad_arguments_are_refused_without_a_device():
     def merge(h=one, d_in=one, base=np.array([0, 5], np.int64), n_shards=2, n_win=4, out=one):
         return L.hpfw_gpu_merge_knn_device(h, d_in, None if base is None else _p(base), n_shards, n_win, out, None)
 
+    # the host functions: round trips over the device calls, every refusal before the first of them
+    def knn_host(h=one, q=one, q_off=off, n_q=2, keys=one, cap=70):
+        return L.hpfw_gpu_knn_windows(h, q, None if q_off is None else _p(q_off), n_q, keys, cap)
+
+    def search_host(h=one, q=one, q_off=off, n_q=2, out=one):
+        return L.hpfw_gpu_search_votes(h, q, None if q_off is None else _p(q_off), n_q, out)
+
     bad = "bad argument"
-    for call, want in ((lambda: knn(h=None), bad), (lambda: knn(q=None), bad), (lambda: knn(q_off=None), bad), (lambda: knn(keys=None), bad), (lambda: knn(n_q=-1), bad),
+    for call, want in ((lambda: knn_host(h=None), bad), (lambda: knn_host(q=None), bad), (lambda: knn_host(q_off=None), bad),
+                     (lambda: knn_host(keys=None), bad), (lambda: knn_host(n_q=-1), bad),
+                     (lambda: knn_host(q_off=down), "q_off must be non-decreasing"), (lambda: knn_host(cap=69), "keys buffer too small"),
+                     (lambda: search_host(h=None), bad), (lambda: search_host(q=None), bad), (lambda: search_host(q_off=None), bad),
+                     (lambda: search_host(out=None), bad), (lambda: search_host(n_q=-1), bad),
+                     (lambda: search_host(q_off=down), "q_off must be non-decreasing"),
+                     (lambda: knn(h=None), bad), (lambda: knn(q=None), bad), (lambda: knn(q_off=None), bad), (lambda: knn(keys=None), bad), (lambda: knn(n_q=-1), bad),
                      (lambda: knn(cap=-1), bad), (lambda: knn(q_off=down), "q_off must be non-decreasing"), (lambda: knn(cap=69), "keys buffer too small"),
                      (lambda: tally(h=None), bad), (lambda: tally(keys=None), bad), (lambda: tally(w_first=None), bad), (lambda: tally(db_off=None), bad),
                      (lambda: tally(out=None), bad), (lambda: tally(n_q=-1), bad), (lambda: tally(n_clips=-1), bad),

@@ -1,17 +1,19 @@
-"""Times the voting search with the tally on the device (k_votes.hip) against the unchanged host
-function on one MI355X.
+"""Times the two entry points of the voting search (votes.hip, k_votes.hip) of one build on one MI355X:
+the host entry point, a round trip over the device entry point, and the device entry point itself.  To compare two builds,
+run fresh processes in turn: [HPFW_GPU_LIB=other/libhpfw_gpu.so] python tools/time_votes.py ...
 
   search   the index of BASELINE.json configs[2] (10 000 clips of 30 s = 2 320 hashprints, random hashprints); the queries of
            --workload: 304 = 1 000 queries of 304 hashprints (241 windows each), 2320 = 64 queries of 2 320 (2 257 windows
-           each).  hpfw_gpu_search_votes (host arrays in and out, the tally a host loop) and hpfw_gpu_search_votes_device plus
-           the copy of the votes to the host, ALTERNATED in one process; host wall clock around both, since the old one takes no
-           stream (the queries of the new one are on the device already, as they are behind an extraction); one warm-up round,
-           --reps rounds: medians with min and max, and whether the two gave the same bytes
-  kernel   --reps + 1 calls of the new path alone, for `rocprofv3 --kernel-trace --stats` in a run of its own; --stats FILE
+           each).  hpfw_gpu_search_votes (host arrays in and out) and hpfw_gpu_search_votes_device plus the copy of the votes
+           to the host, ALTERNATED in one process (--calls host or --calls device: that one alone); host wall clock around
+           both, since the host entry point takes no stream (the queries of the device entry point are on the device already,
+           as they are behind an extraction); one warm-up round, --reps rounds: medians with min and max, and whether the two
+           gave the same bytes
+  kernel   --reps + 1 calls of the device entry point alone, for `rocprofv3 --kernel-trace --stats` in a run of its own; --stats FILE
            then reads rocprofv3's output (the rocpd SQLite database, or kernel_stats.csv with `-f csv`) and adds the device time
            per call of the neighbour scan and of the tally to --out
 
-    python tools/time_votes.py [--parts search] [--workload 304] [--reps 9] [--out profiles/votes.json]
+    python tools/time_votes.py [--parts search] [--workload 304] [--reps 9] [--calls host,device] [--out profiles/votes.json]
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/time_votes.py --parts kernel --workload 304 [--out ...]
     python tools/time_votes.py --stats DIR/run_results.db --workload 304 [--out ...]     (no GPU: merges into --out)
 
@@ -19,6 +21,7 @@ Prints one JSON line per part and merges the parts into --out.
 """
 import argparse
 import csv
+import hashlib
 import json
 import os
 import re
@@ -50,18 +53,18 @@ def _setup(torch, g, workload):
     d_out = torch.zeros(n_q * 24, dtype=torch.uint8, device="cuda")
     s = torch.cuda.current_stream()
 
-    def old():
+    def host():
         return g.search_votes(q, q_off).tobytes()
 
-    def new():
+    def device():
         g.search_votes_dev(d_q.data_ptr(), q_off, d_out.data_ptr(), s.cuda_stream)
         return d_out.cpu().numpy().tobytes()              # (the copy waits for the stream)
-    return {"host_tally": old, "device_tally": new}, (n_q, k_q)
+    return {"host_entry": host, "device_entry": device}, (n_q, k_q)
 
 
-def part_search(torch, g, reps, workload):
+def part_search(torch, g, reps, workload, which=("host", "device")):
     calls, (n_q, k_q) = _setup(torch, g, workload)
-    names = list(calls)
+    names = [name for name in calls if name.split("_")[0] in which]
     ms, same = {name: [] for name in names}, True
     for r in range(reps + 1):
         got = {}
@@ -73,24 +76,26 @@ def part_search(torch, g, reps, workload):
             if r:
                 ms[name].append((t1 - t0) * 1e3)
             print(f"round {r} {name}: {(t1 - t0) * 1e3:.1f} ms", file=sys.stderr, flush=True)
-        same = same and got["host_tally"] == got["device_tally"]
+        same = same and len(set(got.values())) == 1
     g.index_clear()
-    out = {"workload": f"{n_q} queries of {k_q} hashprints ({n_q * (k_q - 63)} windows) against {N_IDX} clips of {PER}; the two calls "
-                       f"alternated in one process, host wall clock, {reps} rounds after one warm-up round",
-           "same_bytes": same}
+    out = {"workload": f"{n_q} queries of {k_q} hashprints ({n_q * (k_q - 63)} windows) against {N_IDX} clips of {PER}; "
+                       f"{' and '.join(names)} in turn in one process, host wall clock, {reps} rounds after one warm-up round",
+           "same_bytes": same, "sha": hashlib.sha256(got[names[0]]).hexdigest()[:16]}
     for name in names:
         out[name + "_ms"] = round(float(np.median(ms[name])), 2)
         out[name + "_min_max_ms"] = [round(min(ms[name]), 2), round(max(ms[name]), 2)]
-    ratio = [y / x for x, y in zip(ms["host_tally"], ms["device_tally"])]
-    out["device_over_host"] = round(float(np.median(ratio)), 4)
-    out["device_over_host_min_max"] = [round(min(ratio), 4), round(max(ratio), 4)]
+        out[name + "_all_ms"] = [round(x, 2) for x in ms[name]]
+    if len(names) == 2:
+        ratio = [y / x for x, y in zip(ms["host_entry"], ms["device_entry"])]
+        out["device_over_host"] = round(float(np.median(ratio)), 4)
+        out["device_over_host_min_max"] = [round(min(ratio), 4), round(max(ratio), 4)]
     return out
 
 
 def part_kernel(torch, g, reps, workload):
     calls, _ = _setup(torch, g, workload)
     for _ in range(reps + 1):
-        calls["device_tally"]()
+        calls["device_entry"]()
     torch.cuda.synchronize()
     g.index_clear()
     return {"calls": reps + 1}
@@ -132,6 +137,7 @@ def main():
     ap.add_argument("--parts", default="search")
     ap.add_argument("--workload", default="304", choices=sorted(WORKLOADS))
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--calls", default="host,device", help="the entry points the search part times: host, device or host,device")
     ap.add_argument("--stats", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "votes.json"))
     args = ap.parse_args()
@@ -139,7 +145,7 @@ def main():
     if os.path.exists(args.out) and os.path.getsize(args.out):
         with open(args.out) as f:
             rec = json.load(f)
-    rec["what"] = "the voting search: the tally on the device against the host loop, one MI355X (DESIGN.md section 19; tools/time_votes.py)"
+    rec["what"] = "the voting search: its host and its device entry point, one MI355X (DESIGN.md section 19; tools/time_votes.py)"
     if args.stats is not None:
         rec["kernels_" + args.workload] = merge_stats(args.stats, rec, args.workload)
         print(json.dumps(rec["kernels_" + args.workload]))
@@ -148,7 +154,8 @@ def main():
         import hpfw_amd
         g = hpfw_amd.Gpu(0)
         for part in args.parts.split(","):
-            res = {"search": part_search, "kernel": part_kernel}[part](torch, g, args.reps, args.workload)
+            extra = (tuple(args.calls.split(",")),) if part == "search" else ()
+            res = {"search": part_search, "kernel": part_kernel}[part](torch, g, args.reps, args.workload, *extra)
             rec[{"search": "search_", "kernel": "kernel_run_"}[part] + args.workload] = res
             print(json.dumps({part: res}), flush=True)
         g.close()
