@@ -20,6 +20,11 @@ OVERLAP_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("lag", "<i4"), 
 # the lags of a (query, clip) pair are scanned in chunks of this many, the first at min_overlap - (the query's length; on the
 # matrix cores the longest of its group of 32) -- kOverlapChunk of csrc/kernels.h, for tests that plant matches on the seams
 OVERLAP_CHUNK = 1024
+# hpfw_dtw_hit: a hit of the warped search; padding: dist = clip = 0xffffffff, start = end = 0
+DTW_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("start", "<i4"), ("end", "<i4")])
+DTW_MAX_PATH_CELLS = 1 << 31                             # the path call's cap on K n
+# the pairs kernel: a lane holds DTW_STRIP columns, a wave's pass DTW_BLOCK; a wider clip runs in blocks (hpfw_gpu_dtw_geometry)
+DTW_STRIP, DTW_BLOCK = 8, 512
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
 # hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
 COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
@@ -93,6 +98,8 @@ EXPORTS = (
     "hpfw_gpu_search_overlap_device", "hpfw_gpu_search_overlap",
     "hpfw_gpu_search_overlap_scored_device", "hpfw_gpu_search_overlap_scored", "hpfw_gpu_overlap_rate", "hpfw_gpu_overlap_extent",
     "hpfw_gpu_knn_windows_device", "hpfw_gpu_vote_windows_device", "hpfw_gpu_search_votes_device", "hpfw_gpu_merge_knn_device",
+    "hpfw_gpu_dtw_pairs_device", "hpfw_gpu_dtw_pairs", "hpfw_gpu_search_dtw_device", "hpfw_gpu_search_dtw",
+    "hpfw_gpu_dtw_path_device", "hpfw_gpu_dtw_path", "hpfw_gpu_dtw_geometry",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -207,6 +214,13 @@ def lib():
     L.hpfw_gpu_search_overlap_scored.argtypes = [vp, vp, vp, i64, vp, i32, i32, vp, vp]
     L.hpfw_gpu_overlap_rate.argtypes = [u32, u32, ctypes.POINTER(u32)]
     L.hpfw_gpu_overlap_extent.argtypes = [i32, i64, i64, i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.hpfw_gpu_dtw_pairs_device.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
+    L.hpfw_gpu_dtw_pairs.argtypes = [vp, vp, vp, i64, vp, i64, vp]
+    L.hpfw_gpu_search_dtw_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    L.hpfw_gpu_search_dtw.argtypes = [vp, vp, vp, i64, i32, i32, vp]
+    L.hpfw_gpu_dtw_path_device.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.hpfw_gpu_dtw_path.argtypes = [vp, vp, i64, i32, vp, vp]
+    L.hpfw_gpu_dtw_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.hpfw_gpu_timer_start.argtypes = [vp, vp]
     L.hpfw_gpu_timer_stop.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.hpfw_gpu_stage_spectrogram.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -1029,6 +1043,54 @@ class Gpu:
         ex = self._exclude(exclude, off.size - 1)
         check(lib().hpfw_gpu_search_overlap_scored_device(self._h, d_q, _hp(off), off.size - 1, None if ex is None else _hp(ex),
                                                           int(min_overlap), int(k), d_out, d_stats, stream))
+
+    # ---- warped search: subsequence DTW over hashprints, distance and path
+    @staticmethod
+    def _pairs(pairs):
+        p = np.ascontiguousarray(pairs, np.int32)
+        if p.size and (p.ndim != 2 or p.shape[1] != 2):
+            raise ValueError("pairs must be [n_pairs][2]: (query index, clip index)")
+        return p.reshape(-1, 2)
+
+    def dtw_pairs(self, q_hp, q_off, pairs):
+        """DTW_HIT_DTYPE [n_pairs] by the rule of include/hpfw_gpu.h: pairs [n_pairs][2] of (query index, clip index in add
+        order, without the clip base); the hit names the clip as the pair does, a pair without a candidate gives padding"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        p = self._pairs(pairs)
+        out = np.zeros(p.shape[0], DTW_HIT_DTYPE)
+        check(lib().hpfw_gpu_dtw_pairs(self._h, _hp(q), _hp(off), off.size - 1, _hp(p), p.shape[0], _hp(out)))
+        return out
+
+    def dtw_pairs_dev(self, d_q, q_off, pairs, d_out, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        p = self._pairs(pairs)
+        check(lib().hpfw_gpu_dtw_pairs_device(self._h, d_q, _hp(off), off.size - 1, _hp(p), p.shape[0], d_out, stream))
+
+    def search_dtw(self, q_hp, q_off, k, candidates):
+        """DTW_HIT_DTYPE [n_q][k], the k best clips by (dist, clip).  candidates (no default): 0 = every clip of the index is
+        warped against every query; k..64 = the plain search's that many best clips of each query are re-ranked"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        out = np.zeros((off.size - 1, k), DTW_HIT_DTYPE)
+        check(lib().hpfw_gpu_search_dtw(self._h, _hp(q), _hp(off), off.size - 1, int(candidates), int(k), _hp(out)))
+        return out
+
+    def search_dtw_dev(self, d_q, q_off, k, candidates, d_out, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_search_dtw_device(self._h, d_q, _hp(off), off.size - 1, int(candidates), int(k), d_out, stream))
+
+    def dtw_path(self, q_hp, clip):
+        """(hit DTW_HIT_DTYPE scalar, path int32 [K]): the column of clip `clip` (add order) every query hashprint lies on;
+        no candidate: the padding record and -1 everywhere"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        path = np.full(max(q.size, 1), -1, np.int32)
+        hit = np.zeros(1, DTW_HIT_DTYPE)
+        check(lib().hpfw_gpu_dtw_path(self._h, _hp(q) if q.size else None, q.size, int(clip), _hp(path), _hp(hit)))
+        return hit[0], path[:q.size]
+
+    def dtw_path_dev(self, d_q, k_q, clip, d_path, d_hit, stream=0):
+        check(lib().hpfw_gpu_dtw_path_device(self._h, d_q, int(k_q), int(clip), d_path, d_hit, stream))
 
     def search_votes(self, q_hp, q_off):
         """AnnStorage-style voting search with exact neighbours: VOTE_DTYPE [n_q]"""

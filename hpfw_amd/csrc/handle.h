@@ -1,5 +1,5 @@
 // handle.h -- what the sources of the C-ABI declared in include/hpfw_gpu.h (handle.hip, plans.hip, extract.hip, learn.hip,
-// search.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
+// search.hip, dtw.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
 // ParallelCollector::collect_fingerprints' parallel_for, reference
 // include/hpfw/core/parallel_collector.h:115-137) and MemoryStorage::build/find
 // (include/hpfw/audioproblems/live-song-id/storage.h:21-64).  All arithmetic is in the kernels.
@@ -147,6 +147,9 @@ struct hpfw_gpu {
         // voting search on the device: the workspaces of one group of windows, carved from one buffer;
         // the first window and first hashprint of every query of the call
         DevBuf d_votes_ws, d_votes_tab;
+        // warped search (dtw.hip): the queries' offsets, the caller's pairs, the boundary rows of the
+        // workgroups, the pairs' hits, the top lists (the plain search's candidates, launch_topk's hits), a path's choices
+        DevBuf d_dtw_q_off, d_dtw_pairs, d_dtw_bnd, d_dtw_hits, d_dtw_top, d_dtw_choices;
     } index;
     // filter learning (learn.hip)
     struct Learn {

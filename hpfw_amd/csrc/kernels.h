@@ -419,6 +419,37 @@ void launch_sum_stats(const void *d_in, int n_shards, int64_t rows, void *d_out,
 // ascending, ~0 behind them), pos_base[shard] added to the position of every real key -> d_out [n_win][5], the 5 smallest
 // ascending; n_shards <= 64
 void launch_knn_merge_shards(const uint64_t *d_in, const int64_t *pos_base, int n_shards, int64_t n_win, uint64_t *d_out, hipStream_t s);
+// ---- warped search (k_dtw.hip): subsequence DTW of a query over a clip, one wave per pair ----
+constexpr int kDtwStrip = 8;               // columns a lane holds in registers
+constexpr int kDtwBlock = 64 * kDtwStrip;  // columns of one pass of the wave; a wider clip runs in blocks from left to right
+constexpr int64_t kDtwPathCells = (int64_t)1 << 31; // the path call records 2 bits per cell: 512 MiB at this many
+struct DtwArgs {
+    const uint64_t *db;      // the index
+    const int64_t *db_off;   // [n_clips + 1] (device)
+    const uint64_t *q;       // concatenated queries (device)
+    const int64_t *q_off;    // [n_q + 1] (device)
+    int64_t q_first;         // added to a pair's query where the pairs are not the caller's list
+    // pair p is (pairs[2 p], pairs[2 p + 1]); else (p / per_q, clip of the hpfw_hit cand[p] less clip_base, or none for a
+    // padding record); else (p / per_q, p % per_q)
+    const int32_t *pairs;
+    const void *cand;
+    int64_t per_q;
+    uint32_t clip_base;
+    int64_t n_pairs;
+    int k_max;               // the longest query: rows of a workgroup's part of bnd
+    uint4 *bnd;              // [workgroups][k_max]: the last two columns of the block before, for every row
+    uint16_t *choices;       // path form (one pair): [k][blocks][64] the choices of a lane's strip, 2 bits per cell
+    void *out;               // hpfw_dtw_hit [n_pairs], clip as the pair names it; a pair without a candidate: padding
+    uint64_t *table;         // NULL, or [n_pairs]: dist << 32 | start for launch_topk, ~0 without a candidate
+};
+// `slots` workgroups of one wave take the pairs in turn
+void launch_dtw_pairs(const DtwArgs &a, int slots, bool path, hipStream_t s);
+// the path [k_q] of the pair whose hit and choices the path form left (no candidate: -1 everywhere)
+void launch_dtw_backtrack(const uint16_t *d_choices, int k_q, int n_blocks, const void *d_hit, int32_t *d_path, hipStream_t s);
+// d_top [n_q][k]: launch_topk's hits of the table of per_q pairs per query -> d_out [n_q][k] (hpfw_dtw_hit)
+void launch_dtw_finish(const void *d_top, const void *d_pairs, int64_t n_q, int k, int64_t per_q, uint32_t clip_base, void *d_out, hipStream_t s);
+// the k best by (dist, clip) of each query's per_q <= 64 pairs -> d_out [n_q][k], clip_base added
+void launch_dtw_rank(const void *d_pairs, int64_t n_q, int per_q, int k, uint32_t clip_base, void *d_out, hipStream_t s);
 // ---- the tally of the voting search (k_votes.hip) ----
 // d_w_start[w] = where window w_base + w begins in the query array: d_q_off[q] + (w_base + w - d_w_first[q]) for the query q
 // that holds it (d_w_first, d_q_off [n_q + 1], the first window of each query and its first hashprint)

@@ -145,6 +145,51 @@ class LiveSongIdentification:
                                          for h in row if h["clip"] != 0xFFFFFFFF])
         return out
 
+    def _no_shards(self, what):
+        if isinstance(self._gpu, _ShardedIndex):
+            raise _lib.HpfwError(f"{what} is not available on a sharded index", _lib.E_UNSUPPORTED)
+
+    def top_warped(self, filenames: Sequence[str], k: int, candidates: int):
+        """top() by the warped search: the query may run faster or slower than the indexed recording
+        inside the window (local slope 1/2 .. 2), distances on top()'s scale.  candidates has no default: 0 warps every
+        indexed recording against every query, k..64 re-ranks that many best recordings of the plain search.  Per query
+        (label, [(distance, name, start, end) x <= k]): the query's first hashprint lies on column start of the recording and
+        its last on column end.  None in place of the list for a file that yields no hashprint.  No shifts, no tempos
+        (Gpu.dtw_pairs takes any hashprints a caller extracts); an identifier made with devices= raises HPFW_E_UNSUPPORTED."""
+        self._no_shards("the warped search")
+        hps = self.collector.calc_hashprints(list(filenames))
+        good = [i for i, (hp, _) in enumerate(hps) if hp is not None and hp.size]
+        out = [(f, None) for f in filenames]
+        if good and self.names:
+            off = np.zeros(len(good) + 1, np.int64)
+            np.cumsum([hps[i][0].size for i in good], out=off[1:])
+            hits = self._gpu.search_dtw(np.concatenate([hps[i][0] for i in good]), off, k, candidates)
+            for row, i in zip(hits, good):
+                out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["start"]), int(h["end"]))
+                                         for h in row if h["clip"] != _lib.NO_CLIP])
+        return out
+
+    def warp_path(self, filename: str, name: str):
+        """(distance, columns): columns int32, the column of the indexed recording `name` every hashprint of the query file
+        lies on (DESIGN.md section 20).  None for a file that yields no hashprint or a recording too short for the query;
+        an unknown name raises KeyError; an identifier made with devices= raises HPFW_E_UNSUPPORTED."""
+        self._no_shards("the warped path")
+        if name not in self.names:
+            raise KeyError(name)
+        hp = self.collector.calc_hashprints([filename])[0][0]
+        if hp is None or not hp.size:
+            return None
+        hit, path = self._gpu.dtw_path(hp, self.names.index(name))
+        if hit["clip"] == _lib.NO_CLIP:
+            return None
+        return int(hit["dist"]), path
+
+    def columns_to_seconds(self, columns, window_s: float = 5.0):
+        """columns of an indexed recording (warp_path, the offsets of top()) in seconds, by the conversion timeline() uses for
+        its offsets: one column is 3 win / m samples of the geometry of a window of window_s seconds"""
+        win = int(round(window_s * 44100))
+        return np.asarray(columns, np.float64) * (3.0 * win / self._gpu.geometry(win).m / 44100.0)
+
     def _top_transposed(self, filenames: List[str], k: int, shifts: List[int]):
         shifts = _lib.check_shifts(shifts)
         return self._top_sets(filenames, k, len(shifts), lambda g, x: g.extract_transposed(x, shifts)[0],

@@ -129,6 +129,47 @@ public:
         return out;
     }
 
+    /// the warped search (hpfw_gpu_search_dtw): the query may run faster or slower than the recording
+    /// inside the window (local slope 1/2 .. 2).  candidates is the caller's (there is no default): 0 warps every clip of the
+    /// index, k..64 re-ranks that many best clips of the plain search.  Query hashprint 0 lies on column start of the
+    /// recording and the last one on column end.
+    struct WarpedResult {
+        std::string filename;
+        size_t cnt;    // mismatching bits along the path
+        int64_t start;
+        int64_t end;
+    };
+    auto find_warped(const typename Collector::Hashprint &hp, int k, int candidates) const -> std::vector<WarpedResult>
+    {
+        std::vector<WarpedResult> out;
+        if (hp.empty() || names_.empty()) return out;
+        const int64_t q_off[2] = {0, (int64_t)hp.size()};
+        std::vector<hpfw_dtw_hit> hits((size_t)k);
+        check(hpfw_gpu_search_dtw(h_, hp.data(), q_off, 1, candidates, k, hits.data()));
+        for (const hpfw_dtw_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            out.push_back({names_[hit.clip], (size_t)hit.dist, (int64_t)hit.start, (int64_t)hit.end});
+        }
+        return out;
+    }
+
+    /// the column of recording `clip` (position in the database) every hashprint of the query lies on, and the distance
+    /// along that path; nullopt when the recording is too short for the query (fewer than hp.size() / 2 + 1 columns)
+    struct WarpPath {
+        size_t cnt;
+        std::vector<int32_t> columns;
+    };
+    auto warp_path(const typename Collector::Hashprint &hp, size_t clip) const -> std::optional<WarpPath>
+    {
+        if (hp.empty() || clip >= names_.size()) return std::nullopt;
+        WarpPath out{0, std::vector<int32_t>(hp.size())};
+        hpfw_dtw_hit hit;
+        check(hpfw_gpu_dtw_path(h_, hp.data(), (int64_t)hp.size(), (int32_t)clip, out.columns.data(), &hit));
+        if (hit.clip == 0xffffffffu) return std::nullopt;
+        out.cnt = hit.dist;
+        return out;
+    }
+
     /// find_overlap() with scores (hpfw_gpu_search_overlap_scored): the same hits, and per hit how far
     /// its rate (mismatching bits per overlapping hashprint, in units of 2^-10) stands out from the rates of the other clips
     /// that have a candidate: (their mean - the rate) / their standard deviation (hpfw_gpu_hit_score; NaN below three clips)

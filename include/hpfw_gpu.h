@@ -505,6 +505,58 @@ int hpfw_gpu_search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const in
 int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q,
                             const int32_t *exclude, int min_overlap, int k, hpfw_overlap_hit *out);
 
+/* ---- warped search: subsequence DTW over hashprints.  Every other search lines a query up with a
+ * clip rigidly (query position j on clip position offset + j); this one lets the query run faster or slower than the clip
+ * inside the window, and tells which clip column every query hashprint lies on.  Exact integers throughout.
+ *
+ * Query q[0..K), 1 <= K <= 16000; clip r[0..n), n >= 1; c(i, j) = popcount(q[i] ^ r[j]).
+ * Row 0 starts anywhere for free: D(0, j) = c(0, j), S(0, j) = j.  For i >= 1 a cell takes the smallest of
+ *   A: D(i-1, j-1) + c(i, j)                 both advance by one
+ *   B: D(i-1, j-2) + c(i, j)                 the clip skips a column (the query runs faster)
+ *   C: D(i-2, j-1) + c(i-1, j) + c(i, j)     rows i-1 and i both lie on column j (the query runs slower); i >= 2
+ * each valid only where its predecessor exists and is reachable; ties go to the first of A, B, C; S(i, j) is the S of the
+ * chosen predecessor; a cell without a valid candidate is unreachable.  Every query hashprint is charged once, at the
+ * column it lies on, so distances are on hpfw_gpu_search_topk's scale, and the all-A path is the rigid alignment: for
+ * n >= K the warped distance of a clip is never above the plain search's.  The local slope stays within 1/2 .. 2.
+ * Per (query, clip): dist = min_j D(K-1, j), end = the smallest j reaching it, start = S(K-1, end).  A clip has a
+ * candidate iff n >= K / 2 + 1 (integer division); an empty query has none.  A query's clips are ordered by (dist, clip).
+ * The path of a pair is path[0..K), the clip column of every query row, walked back from (K-1, end) along the choices (a C
+ * step gives rows i-1 and i the same column): path[0] = start, path[K-1] = end, increments in {0, 1, 2} with a 0 only
+ * directly after a 1, and the sum of c(i, path[i]) is dist.
+ * Refused before any device work: null pointers, n_q < 0, n_pairs < 0, a decreasing q_off, k outside 1..64, candidates
+ * outside {0} and [k, 64], a negative pair or clip index (HPFW_E_INVALID); a query above 16000 hashprints, a path of more
+ * than 2^31 cells (K n; its choices take 2 bits each) (HPFW_E_UNSUPPORTED).  A pair or clip index at or above the number of
+ * queries or clips is HPFW_E_INVALID.  The sharded index (hpfw_gpu_multi.h) has no warped search. */
+typedef struct {
+    uint32_t dist;  /* mismatching bits along the path                        */
+    uint32_t clip;  /* 0xffffffff = none                                      */
+    int32_t start;  /* clip column of query hashprint 0                       */
+    int32_t end;    /* clip column of the query's last hashprint              */
+} hpfw_dtw_hit;
+/* padding: dist = clip = 0xffffffff, start = end = 0 */
+/* pairs [n_pairs][2] (host): (query index, clip index in add order, without clip_base); d_out [n_pairs]: one hit per pair, clip
+ * as the pair names it, the padding record for a pair without a candidate.  d_q_hp, d_out device; q_off, pairs host */
+int hpfw_gpu_dtw_pairs_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *pairs,
+                              int64_t n_pairs, hpfw_dtw_hit *d_out, void *stream);
+int hpfw_gpu_dtw_pairs(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, const int32_t *pairs,
+                       int64_t n_pairs, hpfw_dtw_hit *out);
+/* d_out [n_q][k], 1 <= k <= 64: the k best clips of every query by (dist, clip), clip_base added as in hpfw_hit, padding
+ * records behind the last candidate.  candidates (no default in any binding: the caller decides) = 0: every clip of the index
+ * is a pair of every query; k <= candidates <= 64: the pairs of a query are its hpfw_gpu_search_topk hits for k = candidates,
+ * re-ranked by the rule exactly as it stands. */
+int hpfw_gpu_search_dtw_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int candidates, int k,
+                               hpfw_dtw_hit *d_out, void *stream);
+int hpfw_gpu_search_dtw(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int candidates, int k,
+                        hpfw_dtw_hit *out);
+/* one query of k_q hashprints against clip `clip` (add order, without clip_base): d_path [k_q] and the pair's hit (clip as
+ * given); no candidate: the padding record and -1 in every entry of the path */
+int hpfw_gpu_dtw_path_device(hpfw_gpu *h, const uint64_t *d_q_hp, int64_t k_q, int32_t clip, int32_t *d_path,
+                             hpfw_dtw_hit *d_hit, void *stream);
+int hpfw_gpu_dtw_path(hpfw_gpu *h, const uint64_t *q_hp, int64_t k_q, int32_t clip, int32_t *path, hpfw_dtw_hit *hit);
+/* Host only (tests): the columns a lane of the pairs kernel holds and the columns of one pass of its wave -- the widths at
+ * which a clip crosses into the next lane and the next block */
+int hpfw_gpu_dtw_geometry(int32_t *strip, int32_t *block);
+
 /* ---- events: time a region on `stream` with HIP events (bench.py uses these so that the
  * timing is taken on the stream the kernels run on) ---------------------------------------- */
 int hpfw_gpu_timer_start(hpfw_gpu *h, void *stream);
