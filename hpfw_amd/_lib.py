@@ -25,6 +25,8 @@ DTW_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("start", "<i4"), ("
 DTW_MAX_PATH_CELLS = 1 << 31                             # the path call's cap on K n
 # the pairs kernel: a lane holds DTW_STRIP columns, a wave's pass DTW_BLOCK; a wider clip runs in blocks (hpfw_gpu_dtw_geometry)
 DTW_STRIP, DTW_BLOCK = 8, 512
+# hpfw_index_move: a piece of the plan of a removal from the index
+INDEX_MOVE_DTYPE = np.dtype([("dst", "<i8"), ("src", "<i8"), ("len", "<i8"), ("chunk", "<i8"), ("staged", "<i4"), ("pad", "<i4")])
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
 # hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
 COMBINE_DTYPE = np.dtype([("rec", "<u4"), ("pad", "<u4"), ("cnt", "<i8"), ("confidence", "<i8"), ("offset", "<i8")])
@@ -100,6 +102,8 @@ EXPORTS = (
     "hpfw_gpu_knn_windows_device", "hpfw_gpu_vote_windows_device", "hpfw_gpu_search_votes_device", "hpfw_gpu_merge_knn_device",
     "hpfw_gpu_dtw_pairs_device", "hpfw_gpu_dtw_pairs", "hpfw_gpu_search_dtw_device", "hpfw_gpu_search_dtw",
     "hpfw_gpu_dtw_path_device", "hpfw_gpu_dtw_path", "hpfw_gpu_dtw_geometry",
+    "hpfw_gpu_index_remove", "hpfw_gpu_index_reserve", "hpfw_gpu_index_capacity", "hpfw_gpu_index_remove_plan",
+    "hpfw_gpu_index_remove_geometry",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -221,6 +225,12 @@ def lib():
     L.hpfw_gpu_dtw_path_device.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.hpfw_gpu_dtw_path.argtypes = [vp, vp, i64, i32, vp, vp]
     L.hpfw_gpu_dtw_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.hpfw_gpu_index_remove.argtypes = [vp, vp, i64, vp]
+    L.hpfw_gpu_index_reserve.argtypes = [vp, i64]
+    L.hpfw_gpu_index_capacity.argtypes = [vp]
+    L.hpfw_gpu_index_capacity.restype = i64
+    L.hpfw_gpu_index_remove_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_index_remove_geometry.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.hpfw_gpu_timer_start.argtypes = [vp, vp]
     L.hpfw_gpu_timer_stop.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.hpfw_gpu_stage_spectrogram.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -991,6 +1001,19 @@ class Gpu:
 
     def index_set_clip_base(self, base):
         check(lib().hpfw_gpu_index_set_clip_base(self._h, int(base)))
+
+    # ---- index maintenance
+    def index_remove(self, clips, stream=0):
+        """the clips named (ids in add order, without the clip base) become empty and the others' hashprints close up in
+        place; ids, index_size() and index_capacity() stay.  Enqueues on stream, ordered with every other call."""
+        ids = np.ascontiguousarray(clips, np.int64).ravel()
+        check(lib().hpfw_gpu_index_remove(self._h, _hp(ids) if ids.size else None, ids.size, stream))
+
+    def index_reserve(self, n_hashprints):
+        check(lib().hpfw_gpu_index_reserve(self._h, int(n_hashprints)))
+
+    def index_capacity(self):
+        return int(lib().hpfw_gpu_index_capacity(self._h))
 
     def search_topk(self, q_hp, q_off, k):
         q = np.ascontiguousarray(q_hp, np.uint64).ravel()

@@ -150,6 +150,12 @@ struct hpfw_gpu {
         // warped search (dtw.hip): the queries' offsets, the caller's pairs, the boundary rows of the
         // workgroups, the pairs' hits, the top lists (the plain search's candidates, launch_topk's hits), a path's choices
         DevBuf d_dtw_q_off, d_dtw_pairs, d_dtw_bnd, d_dtw_hits, d_dtw_top, d_dtw_choices;
+        // removal in place (k_index.hip): the staging buffer of one chunk; the moves of the last
+        // removal on the device and the host copy their upload reads, which moves_ev says has been read
+        DevBuf d_stage, d_moves;
+        std::vector<hpfw_index_move> moves;
+        Event moves_ev;
+        bool moves_pending = false;
     } index;
     // filter learning (learn.hip)
     struct Learn {

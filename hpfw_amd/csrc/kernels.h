@@ -12,6 +12,7 @@
 #include "device_math.h"
 #include "fft_lds.h"
 #include "fft_rows.h"
+#include "index_plan.h"
 #include "streams_plan.h"
 #include "xcorr_plan.h"
 
@@ -450,6 +451,13 @@ void launch_dtw_backtrack(const uint16_t *d_choices, int k_q, int n_blocks, cons
 void launch_dtw_finish(const void *d_top, const void *d_pairs, int64_t n_q, int k, int64_t per_q, uint32_t clip_base, void *d_out, hipStream_t s);
 // the k best by (dist, clip) of each query's per_q <= 64 pairs -> d_out [n_q][k], clip_base added
 void launch_dtw_rank(const void *d_pairs, int64_t n_q, int per_q, int k, uint32_t clip_base, void *d_out, hipStream_t s);
+// ---- removal from the index in place (k_index.hip; kIndexTile and the plan: index_plan.h) ----
+// d_out[e - out_shift] = d_in[src + (e - dst)] of the piece that holds e, for e in [lo, hi): the n_moves pieces cover [lo, hi)
+// without a gap, ascending; out_shift even, d_out and d_in 16-byte aligned
+void launch_index_gather(uint64_t *d_out, int64_t out_shift, const uint64_t *d_in, const hpfw_index_move *d_moves, int64_t n_moves, int64_t lo,
+                         int64_t hi, hipStream_t s);
+// d_out[e] = d_in[e - in_shift] for e in [lo, hi); in_shift even
+void launch_index_copy(uint64_t *d_out, const uint64_t *d_in, int64_t in_shift, int64_t lo, int64_t hi, hipStream_t s);
 // ---- the tally of the voting search (k_votes.hip) ----
 // d_w_start[w] = where window w_base + w begins in the query array: d_q_off[q] + (w_base + w - d_w_first[q]) for the query q
 // that holds it (d_w_first, d_q_off [n_q + 1], the first window of each query and its first hashprint)

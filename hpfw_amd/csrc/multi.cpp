@@ -21,8 +21,10 @@
 #include "../../include/hpfw_gpu_multi.h"
 #include "../../include/hpfw_gpu_multi_resample.h"
 #include "../../include/hpfw_gpu_multi_search.h"
+#include "../../include/hpfw_gpu_multi_index.h"
 #include "../../include/hpfw_gpu_multi_votes.h"
 #include "hip_owned.h"
+#include "index_plan.h"
 #include "legacy_internal.h"
 
 namespace {
@@ -515,6 +517,37 @@ int hpfw_gpu_group_search_votes(hpfw_gpu_group *g, const uint64_t *q_hp, const i
             HIP_OK(hipMemcpyAsync(out, d_votes, votes, hipMemcpyDeviceToHost, on), "D2H copy of the votes");
             return 0;
         });
+}
+
+// ---- removal from the sharded index (include/hpfw_gpu_multi_index.h) ----
+// Global ids are checked against the group's clip count, routed to the shard whose range holds them and handed to
+// hpfw_gpu_index_remove as local ids on the shard's stream; the group's own offsets follow the same rule.  No collective.
+int hpfw_gpu_group_index_remove(hpfw_gpu_group *g, const int64_t *clips, int64_t n)
+{
+    if (!g) return fail(HPFW_E_INVALID, "null group");
+    if (n < 0) return fail(HPFW_E_INVALID, "n must not be negative");
+    if (n > 0 && !clips) return fail(HPFW_E_INVALID, "null clips");
+    for (int64_t i = 0; i < n; ++i)
+        if (clips[i] < 0 || clips[i] >= g->n_clips)
+            return fail(HPFW_E_INVALID, "group_index_remove: clip " + std::to_string(clips[i]) + " outside [0, " + std::to_string(g->n_clips) + ")");
+    if (n == 0) return 0;
+    std::vector<int64_t> ids(clips, clips + n);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    std::vector<int64_t> new_off(g->db_off.size());
+    if (!hpfw::index_remove_plan(g->db_off.data(), g->n_clips, ids.data(), (int64_t)ids.size(), 1, new_off.data(), nullptr))
+        return fail(HPFW_E_INVALID, "group_index_remove: no plan");
+    const int rc = per_shard(g, [&](int i) {
+        Shard &s = g->shards[(size_t)i];
+        std::vector<int64_t> local;
+        for (auto it = std::lower_bound(ids.begin(), ids.end(), s.lo); it != ids.end() && *it < s.hi; ++it) local.push_back(*it - s.lo);
+        return local.empty() ? 0 : hpfw_gpu_index_remove(s.h.get(), local.data(), (int64_t)local.size(), s.stream.get());
+    });
+    if (!rc) {
+        g->db_off = std::move(new_off);
+        g->db_off_dirty = true;
+    }
+    return rc;
 }
 
 int hpfw_gpu_group_search_topk(hpfw_gpu_group *g, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *out)

@@ -13,6 +13,21 @@ int hpfw_gpu_index_clear(hpfw_gpu *h)
     return 0;
 }
 
+// the index's hashprints into a buffer of `bytes` (more than the capacity)
+static int index_regrow(hpfw_gpu *h, size_t bytes)
+{
+    const int64_t have = h->index.db_off.back();
+    DevBuf nd;
+    HIP_TRY(nd.alloc(bytes));
+    // earlier appends may still be in flight on a non-blocking stream the null-stream copy below would
+    // not wait for, and scans may still be reading the old buffer: growing is rare (capacity doubles, or
+    // hpfw_gpu_index_reserve sizes the buffer once)
+    HIP_TRY(hipDeviceSynchronize());
+    if (have) HIP_TRY(hipMemcpy(nd.get(), h->index.d_db.get(), (size_t)have * 8, hipMemcpyDeviceToDevice));
+    h->index.d_db = std::move(nd); // (the old buffer goes with nd)
+    return 0;
+}
+
 static int index_add_impl(hpfw_gpu *h, const uint64_t *hp, const int64_t *offsets, int64_t n_clips, bool dev,
                           hipStream_t s)
 {
@@ -24,15 +39,8 @@ static int index_add_impl(hpfw_gpu *h, const uint64_t *hp, const int64_t *offset
     const int64_t have = h->index.db_off.back();
     return ordered_call(h, s, [&] {
         const size_t need = (size_t)(have + add) * 8;
-        if (need > h->index.d_db.capacity()) {
-            DevBuf nd;
-            HIP_TRY(nd.alloc(std::max({need, h->index.d_db.capacity() * 2, (size_t)8 << 16})));
-            // earlier appends may still be in flight on a non-blocking stream the null-stream copy below would
-            // not wait for, and scans may still be reading the old buffer: growing is rare (capacity doubles)
-            HIP_TRY(hipDeviceSynchronize());
-            if (have) HIP_TRY(hipMemcpy(nd.get(), h->index.d_db.get(), (size_t)have * 8, hipMemcpyDeviceToDevice));
-            h->index.d_db = std::move(nd); // (the old buffer goes with nd)
-        }
+        if (need > h->index.d_db.capacity())
+            if (int rc = index_regrow(h, std::max({need, h->index.d_db.capacity() * 2, (size_t)8 << 16}))) return rc;
         uint64_t *dst = h->index.d_db.as<uint64_t>() + have;
         if (add) {
             if (dev)
@@ -80,6 +88,123 @@ int hpfw_gpu_index_set_clip_base(hpfw_gpu *h, uint32_t base)
 {
     if (!h) return fail(HPFW_E_INVALID, "null handle");
     h->index.clip_base = base;
+    return 0;
+}
+
+// ---- removal in place (the plan and its order: index_plan.h, the kernels: k_index.hip) ----
+// hashprints of a chunk: HPFW_INDEX_STAGE_KB (tests), HPFW_INDEX_STAGE_MB, else the default; read at every call
+static int64_t index_chunk()
+{
+    for (const auto &[name, unit] : {std::pair<const char *, int64_t>{"HPFW_INDEX_STAGE_KB", 1024}, {"HPFW_INDEX_STAGE_MB", (int64_t)1 << 20}}) {
+        const char *e = std::getenv(name);
+        if (!e || !*e) continue;
+        const long long v = std::atoll(e);
+        if (v >= 1 && v <= ((long long)1 << 20)) return std::max<int64_t>((int64_t)v * unit / 8, 1);
+    }
+    return hpfw::kIndexChunkDefault;
+}
+
+int hpfw_gpu_index_remove(hpfw_gpu *h, const int64_t *clips, int64_t n, void *stream)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    if (n < 0) return fail(HPFW_E_INVALID, "n must not be negative");
+    if (n > 0 && !clips) return fail(HPFW_E_INVALID, "null clips");
+    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+    for (int64_t i = 0; i < n; ++i)
+        if (clips[i] < 0 || clips[i] >= n_clips)
+            return fail(HPFW_E_INVALID, "index_remove: clip " + std::to_string(clips[i]) + " outside [0, " + std::to_string(n_clips) + ")");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int64_t> ids(clips, clips + n);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const int64_t chunk = index_chunk();
+    std::vector<int64_t> new_off(h->index.db_off.size());
+    std::vector<hpfw_index_move> moves;
+    if (!hpfw::index_remove_plan(h->index.db_off.data(), n_clips, ids.data(), (int64_t)ids.size(), chunk, new_off.data(), &moves))
+        return fail(HPFW_E_INVALID, "index_remove: no plan");
+    if (new_off == h->index.db_off) return 0; // (every clip named was empty)
+    HIP_TRY(hipSetDevice(h->device));
+    // everything that can be refused is refused here, while the index is as it was
+    bool staged = false;
+    for (const hpfw_index_move &m : moves) staged = staged || m.staged;
+    const size_t stage_bytes = (size_t)(chunk + 2) * 8; // (a chunk that begins at an odd hashprint waits one word in)
+    if (staged && h->index.d_stage.capacity() < stage_bytes && h->index.d_stage.alloc(stage_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(HPFW_E_INVALID, "index_remove: no staging buffer of " + std::to_string(stage_bytes) + " bytes (HPFW_INDEX_STAGE_MB)");
+    }
+    if (!moves.empty()) {
+        if (h->index.d_moves.capacity() < moves.size() * sizeof(hpfw_index_move) &&
+            h->index.d_moves.alloc(std::max(moves.size() * sizeof(hpfw_index_move) * 2, (size_t)1 << 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(HPFW_E_INVALID, "index_remove: no device memory for the moves");
+        }
+        if (!h->index.moves_ev && h->index.moves_ev.create() != hipSuccess) return fail(HPFW_E_HIP, "index_remove: event");
+        // the upload of the removal before may still be reading the host copy this one replaces
+        if (h->index.moves_pending) HIP_TRY(hipEventSynchronize(h->index.moves_ev.get()));
+        h->index.moves_pending = false;
+    }
+    return ordered_call(h, s, [&] {
+        uint64_t *db = h->index.d_db.as<uint64_t>();
+        if (!moves.empty()) {
+            h->index.moves = std::move(moves);
+            const std::vector<hpfw_index_move> &mv = h->index.moves;
+            const hpfw_index_move *d_mv = h->index.d_moves.as<hpfw_index_move>();
+            HIP_TRY(hipMemcpyAsync(h->index.d_moves.get(), mv.data(), mv.size() * sizeof(hpfw_index_move), hipMemcpyHostToDevice, s));
+            h->index.moves_pending = hipEventRecord(h->index.moves_ev.get(), s) == hipSuccess;
+            if (!h->index.moves_pending) HIP_TRY(hipStreamSynchronize(s));
+            for (size_t i = 0; i < mv.size();) { // chunk after chunk, in launch order
+                size_t j = i;
+                while (j < mv.size() && mv[j].chunk == mv[i].chunk) ++j;
+                const int64_t lo = mv[i].dst, hi = mv[j - 1].dst + mv[j - 1].len;
+                if (mv[i].staged) {
+                    uint64_t *stage = h->index.d_stage.as<uint64_t>();
+                    const int64_t base = lo & ~(int64_t)1;
+                    hpfw::launch_index_gather(stage, base, db, d_mv + i, (int64_t)(j - i), lo, hi, s);
+                    hpfw::launch_index_copy(db, stage, base, lo, hi, s);
+                } else {
+                    hpfw::launch_index_gather(db, 0, db, d_mv + i, (int64_t)(j - i), lo, hi, s);
+                }
+                i = j;
+            }
+            if (int rc = check_launch("index_remove")) return rc;
+        }
+        h->index.db_off = std::move(new_off);
+        h->index.db_off_dirty = true;
+        return 0;
+    });
+}
+
+int hpfw_gpu_index_reserve(hpfw_gpu *h, int64_t n_hashprints)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    if (n_hashprints < 0 || n_hashprints > ((int64_t)1 << 58)) return fail(HPFW_E_INVALID, "index_reserve: n_hashprints outside 0 .. 2^58");
+    if ((size_t)n_hashprints * 8 <= h->index.d_db.capacity()) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, nullptr, [&] { return index_regrow(h, (size_t)n_hashprints * 8); });
+}
+
+int64_t hpfw_gpu_index_capacity(hpfw_gpu *h) { return h ? (int64_t)(h->index.d_db.capacity() / 8) : 0; }
+
+int hpfw_gpu_index_remove_plan(const int64_t *offsets, int64_t n_clips, const int64_t *removed, int64_t n_removed, int64_t chunk,
+                               int64_t *new_offsets, hpfw_index_move *moves, int64_t moves_cap, int64_t *n_moves)
+{
+    if (!offsets || !new_offsets || !n_moves) return fail(HPFW_E_INVALID, "null argument");
+    std::vector<hpfw_index_move> mv;
+    if (!hpfw::index_remove_plan(offsets, n_clips, removed, n_removed, chunk, new_offsets, &mv))
+        return fail(HPFW_E_INVALID, "index_remove_plan: offsets must not decrease, removed must ascend strictly inside [0, n_clips), chunk >= 1");
+    *n_moves = (int64_t)mv.size();
+    if (!moves) return 0;
+    if (moves_cap < *n_moves) return fail(HPFW_E_INVALID, "index_remove_plan: moves_cap below the number of pieces");
+    std::copy(mv.begin(), mv.end(), moves);
+    return 0;
+}
+
+int hpfw_gpu_index_remove_geometry(int64_t *tile, int64_t *chunk)
+{
+    if (!tile || !chunk) return fail(HPFW_E_INVALID, "null argument");
+    *tile = hpfw::kIndexTile;
+    *chunk = hpfw::kIndexChunkDefault;
     return 0;
 }
 

@@ -27,7 +27,7 @@ class _ShardedIndex:
         from . import multi
         self.group = multi.GpuGroup(devices)
         self._first = _lib.Gpu.from_handle(self.group.handle(0))
-        for name in ("index_offsets", "search_topk", "search_topk_scored", "search_topk_transposed",
+        for name in ("index_offsets", "index_remove", "search_topk", "search_topk_scored", "search_topk_transposed",
                      "search_topk_transposed_scored", "search_votes"):
             setattr(self, name, getattr(self.group, name))
         self.geometry, self.resample = self._first.geometry, self._first.resample
@@ -60,6 +60,8 @@ class LiveSongIdentification:
         self._cache = cache
         self._gpu = _lib.Gpu(device) if devices is None else _ShardedIndex(list(devices))
         self.names: List[str] = []
+        self._removed = set()                            # slots of self.names whose recording was removed
+        self._added_len: List[int] = []                  # per slot the hashprints the recording had when it was added
 
     def close(self):
         self.collector.save(self._cache)                 # the destructor saves it, live_song_id.h:28
@@ -68,6 +70,8 @@ class LiveSongIdentification:
     def build(self, hashprints: Sequence[Tuple[np.ndarray, str]]):
         """MemoryStorage::build (storage.h:21-25) from prepare()'s (array, name) pairs"""
         self.names = [name for _, name in hashprints]
+        self._removed = set()                            # a fresh index forgets all removals
+        self._added_len = [int(hp.size) for hp, _ in hashprints]
         self._gpu.index_clear()
         if self.names:
             off = np.zeros(len(hashprints) + 1, np.int64)
@@ -77,6 +81,45 @@ class LiveSongIdentification:
 
     def index(self, filenames: Sequence[str]):
         self.build(self.collector.prepare(list(filenames)))
+
+    # ---- index maintenance: slots of self.names are ids and stay; a removed recording's slot is empty
+    def live_names(self) -> List[str]:
+        """the recordings that remain, in slot order"""
+        removed = getattr(self, "_removed", ())
+        return [name for i, name in enumerate(self.names) if i not in removed]
+
+    def _live_slots(self, name):
+        removed = getattr(self, "_removed", ())
+        return [i for i, n in enumerate(self.names) if n == name and i not in removed]
+
+    def remove(self, names: Sequence[str]) -> int:
+        """removes the recordings named from the index in place, on one device and with devices=: every live slot carrying one
+        of the names goes, self.names keeps its length, and no search names them afterwards; returns the slots removed.  An
+        unknown or already removed name raises KeyError before anything changes; a name may repeat in the list."""
+        slots = []
+        for name in dict.fromkeys(names):
+            live = self._live_slots(name)
+            if not live:
+                raise KeyError(name)
+            slots += live
+        if slots:
+            self._gpu.index_remove(slots)
+            self._removed.update(slots)
+        return len(slots)
+
+    def add(self, filenames: Sequence[str]) -> int:
+        """appends the recordings of the files to the index: their hashprints by collector.calc_hashprints under the filters
+        in force (nothing is re-learned), their stems behind self.names; returns the recordings added.  A file that yields no
+        hashprint is left out.  An identifier made with devices= raises HPFW_E_UNSUPPORTED: a sharded index is rebuilt."""
+        self._no_shards("adding to the index")
+        pairs = [(hp, name) for hp, name in self.collector.calc_hashprints(list(filenames)) if hp is not None and hp.size]
+        if pairs:
+            off = np.zeros(len(pairs) + 1, np.int64)
+            np.cumsum([hp.size for hp, _ in pairs], out=off[1:])
+            self._gpu.index_add(np.concatenate([hp for hp, _ in pairs]), off)
+            self.names += [name for _, name in pairs]
+            self._added_len += [int(hp.size) for hp, _ in pairs]
+        return len(pairs)
 
     def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None,
             tempos: Optional[Sequence[float]] = None):
@@ -174,12 +217,13 @@ class LiveSongIdentification:
         lies on (DESIGN.md section 20).  None for a file that yields no hashprint or a recording too short for the query;
         an unknown name raises KeyError; an identifier made with devices= raises HPFW_E_UNSUPPORTED."""
         self._no_shards("the warped path")
-        if name not in self.names:
+        live = self._live_slots(name)                      # (a removed name is unknown)
+        if not live:
             raise KeyError(name)
         hp = self.collector.calc_hashprints([filename])[0][0]
         if hp is None or not hp.size:
             return None
-        hit, path = self._gpu.dtw_path(hp, self.names.index(name))
+        hit, path = self._gpu.dtw_path(hp, live[0])
         if hit["clip"] == _lib.NO_CLIP:
             return None
         return int(hit["dist"]), path
@@ -324,7 +368,10 @@ class LiveSongIdentification:
         """(start, end, first lag) of a segment of windows searched by the overlap rule: the samples of its first and last
         window that lie on the clip (hpfw_gpu_overlap_extent)"""
         g = self._gpu.geometry(win)
-        n_clip = int(np.diff(self._gpu.index_offsets())[int(sg["clip"])])
+        # the clip's length as it was added: a segment open on a recording that has been removed since ends as it would have
+        # ended had the feed stopped matching (DESIGN.md section 21)
+        added, clip = getattr(self, "_added_len", ()), int(sg["clip"])
+        n_clip = added[clip] if clip < len(added) else int(np.diff(self._gpu.index_offsets())[clip])
         a, _ = _lib.overlap_extent(first_lag, n_clip, g.n_hp, g.c - g.n_hp + 1, win, g.m)
         _, b = _lib.overlap_extent(last_lag, n_clip, g.n_hp, g.c - g.n_hp + 1, win, g.m)
         return int(sg["first"]) * hop + a, int(sg["last"]) * hop + b, int(first_lag)

@@ -28,6 +28,8 @@ SEARCH_EXPORTS = (
 )
 # include/hpfw_gpu_multi_votes.h
 VOTES_EXPORTS = ("hpfw_gpu_group_search_votes",)
+# include/hpfw_gpu_multi_index.h
+INDEX_EXPORTS = ("hpfw_gpu_group_index_remove",)
 
 _multi = None
 
@@ -73,6 +75,7 @@ def lib():
     L.hpfw_gpu_group_search_topk_transposed_scored.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     L.hpfw_gpu_group_extract_windows_pcm16.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp]
     L.hpfw_gpu_group_search_votes.argtypes = [vp, vp, vp, i64, vp]
+    L.hpfw_gpu_group_index_remove.argtypes = [vp, vp, i64]
     _multi = L
     return L
 
@@ -139,8 +142,18 @@ class GpuGroup:
         self._offsets = off - off[0]
 
     def index_offsets(self):
-        """the clip offsets int64 [n_clips + 1] of the index as index_build last took it, from 0 (as Gpu.index_offsets)"""
+        """the clip offsets int64 [n_clips + 1] of the index as index_build last took it and index_remove left it, from 0 (as
+        Gpu.index_offsets)"""
         return self._offsets.copy()
+
+    def index_remove(self, clips):
+        """the clips named (global ids) become empty on the shards that hold them; ids and the shards' ranges stay (DESIGN.md
+        section 21).  Adding to a sharded index is not offered: rebuild with index_build."""
+        ids = np.ascontiguousarray(clips, np.int64).ravel()
+        _lib.check(lib().hpfw_gpu_group_index_remove(self._g, _lib._hp(ids) if ids.size else None, ids.size))
+        lengths = np.diff(self._offsets)
+        lengths[ids] = 0
+        self._offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
 
     def _search(self, fn, q_hp, q_off, n_q, extra, k, hit_dtype, stats_shape=None):
         """contiguous queries and offsets in, fn(group, q, off, n_q, *extra, k, out[, stats]), out [n_q][k] (and the moments) back"""

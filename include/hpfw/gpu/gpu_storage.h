@@ -53,6 +53,67 @@ public:
         }
         check(hpfw_gpu_index_clear(h_));
         if (!names_.empty()) check(hpfw_gpu_index_add(h_, all.empty() ? &dummy_ : all.data(), off.data(), (int64_t)names_.size()));
+        removed_.assign(names_.size(), 0); // a fresh index forgets all removals
+        added_len_.clear();
+        for (size_t i = 0; i + 1 < off.size(); ++i) added_len_.push_back(off[i + 1] - off[i]);
+    }
+
+    /// index maintenance (hpfw_gpu_index_remove): the recordings named leave the index in place.  Slots
+    /// are ids: names() and size() keep counting them, live() counts the recordings that remain, and no search names a removed
+    /// one.  Every live slot carrying one of the names goes; returns the number removed.  A name that is unknown (or already
+    /// removed) throws std::out_of_range before anything changes.
+    auto remove(const std::vector<std::string> &names) -> size_t
+    {
+        std::vector<int64_t> ids;
+        for (const std::string &name : names) {
+            bool found = false;
+            for (size_t i = 0; i < names_.size(); ++i)
+                if (!removed_[i] && names_[i] == name) {
+                    ids.push_back((int64_t)i);
+                    found = true;
+                }
+            if (!found) throw std::out_of_range("hpfw::db::GpuStorage: no recording " + name);
+        }
+        if (ids.empty()) return 0;
+        check(hpfw_gpu_index_remove(h_, ids.data(), (int64_t)ids.size(), nullptr));
+        size_t n = 0;
+        for (int64_t i : ids) { // (a name may repeat in the list)
+            n += !removed_[(size_t)i];
+            removed_[(size_t)i] = 1;
+        }
+        return n;
+    }
+
+    /// appends a range of Collector::FilenameFingerprintPair behind the index (hpfw_gpu_index_add): the new recordings take
+    /// the slots size(), size() + 1, ... and use the room removals freed before anything is allocated
+    template <typename Range>
+    void add(Range &&hashprints)
+    {
+        std::vector<std::string> names;
+        std::vector<uint64_t> all;
+        std::vector<int64_t> off{0};
+        for (auto &p : hashprints) {
+            names.push_back(p.filename);
+            all.insert(all.end(), p.fingerprint.begin(), p.fingerprint.end());
+            off.push_back((int64_t)all.size());
+        }
+        if (names.empty()) return;
+        check(hpfw_gpu_index_add(h_, all.empty() ? &dummy_ : all.data(), off.data(), (int64_t)names.size()));
+        names_.insert(names_.end(), names.begin(), names.end());
+        removed_.resize(names_.size(), 0);
+        for (size_t i = 0; i + 1 < off.size(); ++i) added_len_.push_back(off[i + 1] - off[i]);
+    }
+
+    /// the hashprints slot `clip` had when its recording was added, removed since or not (hpfw::LiveStreams trims a segment
+    /// by it)
+    int64_t added_length(size_t clip) const { return added_len_.at(clip); }
+
+    /// the recordings that remain (size() counts slots)
+    size_t live() const
+    {
+        size_t n = 0;
+        for (char r : removed_) n += !r;
+        return n;
     }
 
     /// storage.h:27-64
@@ -262,8 +323,9 @@ public:
         check(hpfw_gpu_index_get(h_, off.data(), all.empty() ? &dummy_ : all.data(), (int64_t)all.size()));
         std::ofstream os(dump_name, std::ios::binary);
         if (!os) throw std::runtime_error("hpfw::db::GpuStorage: cannot write " + dump_name);
-        put(os, (uint64_t)names_.size());
+        put(os, (uint64_t)live()); // the live recordings only: the dump loads compact
         for (size_t i = 0; i < names_.size(); ++i) {
+            if (removed_[i]) continue;
             put(os, (uint64_t)names_[i].size());
             os.write(names_[i].data(), (std::streamsize)names_[i].size());
             const uint64_t n = (uint64_t)(off[i + 1] - off[i]);
@@ -315,6 +377,8 @@ private:
     }
     hpfw_gpu *h_ = nullptr;
     std::vector<std::string> names_;
+    std::vector<char> removed_; // per slot: its recording was removed
+    std::vector<int64_t> added_len_; // per slot: its hashprints when it was added
     mutable uint64_t dummy_ = 0;
 };
 

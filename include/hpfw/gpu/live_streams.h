@@ -184,9 +184,9 @@ private:
         if constexpr (!requires { storage_.group(); }) {
             if (opt_.min_overlap > 0) { // the part of the first and last window that lies on the clip
                 const auto &lags = lags_[(size_t)feed];
-                std::vector<int64_t> db_off(storage_.names().size() + 1, 0);
-                if (hpfw_gpu_index_get(storage_.handle(), db_off.data(), nullptr, 0) != 0) fail("index");
-                if (detail::trim_segment(seg, lags.at(s.first), lags.at(s.last), db_off[s.clip + 1] - db_off[s.clip], g_, opt_.win, opt_.hop) != 0)
+                // the clip's length as it was added: a segment open on a recording removed since (GpuStorage::remove) ends as
+                // it would have ended had the feed stopped matching
+                if (detail::trim_segment(seg, lags.at(s.first), lags.at(s.last), storage_.added_length(s.clip), g_, opt_.win, opt_.hop) != 0)
                     fail("extent");
             }
         }

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../hpfw_gpu_multi.h"
+#include "../../hpfw_gpu_multi_index.h"
 #include "../../hpfw_gpu_multi_search.h"
 #include "../../hpfw_gpu_multi_votes.h"
 
@@ -60,6 +61,44 @@ public:
         }
         check(hpfw_gpu_group_index_build(g_, all.empty() ? &dummy_ : all.data(), off.data(), (int64_t)names_.size()));
         off_ = off;
+        removed_.assign(names_.size(), 0); // a fresh index forgets all removals
+    }
+
+    /// GpuStorage::remove over the shards (hpfw_gpu_group_index_remove): the recordings named leave
+    /// their shards in place; slots are ids, so names() and size() keep counting them and live() counts what remains.  A
+    /// name that is unknown (or already removed) throws std::out_of_range before anything changes.  There is no add():
+    /// a sharded index is rebuilt (include/hpfw_gpu_multi_index.h).
+    auto remove(const std::vector<std::string> &names) -> size_t
+    {
+        std::vector<int64_t> ids;
+        for (const std::string &name : names) {
+            bool found = false;
+            for (size_t i = 0; i < names_.size(); ++i)
+                if (!removed_[i] && names_[i] == name) {
+                    ids.push_back((int64_t)i);
+                    found = true;
+                }
+            if (!found) throw std::out_of_range("hpfw::db::ShardedGpuStorage: no recording " + name);
+        }
+        if (ids.empty()) return 0;
+        check(hpfw_gpu_group_index_remove(g_, ids.data(), (int64_t)ids.size()));
+        size_t n = 0;
+        for (int64_t i : ids) { // (a name may repeat in the list)
+            n += !removed_[(size_t)i];
+            removed_[(size_t)i] = 1;
+        }
+        std::vector<int64_t> off(off_.size(), 0);
+        for (size_t i = 0; i < names_.size(); ++i) off[i + 1] = off[i] + (removed_[i] ? 0 : off_[i + 1] - off_[i]);
+        off_ = off;
+        return n;
+    }
+
+    /// the recordings that remain (size() counts slots)
+    size_t live() const
+    {
+        size_t n = 0;
+        for (char r : removed_) n += !r;
+        return n;
     }
 
     /// the group that holds the shards, the names of the clips in index order and their offsets [size() + 1] (hpfw::timeline,
@@ -167,6 +206,7 @@ private:
     hpfw_gpu_group *g_ = nullptr;
     std::vector<std::string> names_;
     std::vector<int64_t> off_{0};
+    std::vector<char> removed_; // per slot: its recording was removed
     mutable uint64_t dummy_ = 0;
 };
 

@@ -402,6 +402,37 @@ int64_t hpfw_gpu_index_size(hpfw_gpu *h); /* number of clips */
 int hpfw_gpu_index_get(hpfw_gpu *h, int64_t *offsets, uint64_t *hp, int64_t hp_cap);
 /* added to every reported clip id (rank's first global clip id when the index is sharded) */
 int hpfw_gpu_index_set_clip_base(hpfw_gpu *h, uint32_t clip_base);
+/* Index maintenance.  Removal keeps every id: the clips named become empty, the hashprints of the
+ * others close up in place, in order, and hpfw_gpu_index_get returns byte for byte what index_clear + index_add of the same
+ * clips with the removed ones empty would have built -- so every search answers as on that index.  hpfw_gpu_index_size,
+ * the clip base and the buffer's capacity do not change; a later index_add appends behind the last hashprint with ids
+ * size, size + 1, ... and uses the freed room before anything is allocated.
+ * clips [n]: ids in add order without the clip base, host, read before the call returns, in any order; a repeated id and an
+ * id of an empty clip are no-ops.  Refused before anything changes (HPFW_E_INVALID): an id outside [0, size), n < 0, a null
+ * list with n > 0, and a staging buffer that cannot be allocated (HPFW_INDEX_STAGE_MB, read at the call; default 128).
+ * Enqueues on stream, ordered with every other entry point of the handle: a search enqueued before the call, on any stream,
+ * sees the old index, one enqueued after it the new one, without the caller synchronising; no device-wide synchronisation.
+ * The device memory it needs beyond the index is the staging buffer and the list of moves. */
+int hpfw_gpu_index_remove(hpfw_gpu *h, const int64_t *clips, int64_t n, void *stream);
+/* room for n_hashprints without a later reallocation; never shrinks */
+int hpfw_gpu_index_reserve(hpfw_gpu *h, int64_t n_hashprints);
+int64_t hpfw_gpu_index_capacity(hpfw_gpu *h); /* in hashprints */
+/* host-only: the plan of a removal (hpfw_amd/csrc/index_plan.h).  A move piece copies len hashprints from src to dst
+ * (dst < src); pieces are listed chunk after chunk with adjacent ascending destinations; a chunk whose sources meet its own
+ * destinations is staged (read whole into the staging buffer, then written), every other is direct. */
+typedef struct {
+    int64_t dst, src, len;
+    int64_t chunk;  /* the chunk's number, from 0 */
+    int32_t staged; /* 1: the chunk goes through the staging buffer */
+    int32_t pad;
+} hpfw_index_move;
+/* offsets [n_clips + 1]; removed [n_removed] strictly ascending ids; chunk >= 1 hashprints; new_offsets [n_clips + 1];
+ * moves [moves_cap] (NULL to count); *n_moves the number of pieces.  HPFW_E_INVALID for arguments outside these conditions
+ * and for a moves_cap below *n_moves. */
+int hpfw_gpu_index_remove_plan(const int64_t *offsets, int64_t n_clips, const int64_t *removed, int64_t n_removed, int64_t chunk,
+                               int64_t *new_offsets, hpfw_index_move *moves, int64_t moves_cap, int64_t *n_moves);
+/* host-only: the hashprints of the destination one workgroup takes, and the default chunk in hashprints */
+int hpfw_gpu_index_remove_geometry(int64_t *tile, int64_t *chunk);
 
 /* top-k clips per query, ascending (dist, clip): query q is q_hp[q_off[q] .. q_off[q+1]).
  * d_q_hp device; q_off host; d_out device [n_q][k].  k <= 64. */

@@ -12,9 +12,10 @@
  * Replicated queries -> per-shard hpfw_gpu_knn_windows_device -> ONE ncclAllGather of the per-shard key lists -> on device 0
  * hpfw_gpu_merge_knn_device and hpfw_gpu_vote_windows_device against the offsets of the whole index (kept on device 0,
  * uploaded by the first voting search after a build) -> one copy of n_q votes back.
- * The tally reads the offsets hpfw_gpu_group_index_build recorded: the index has to be built through it.  Clips added to or
- * removed from a shard's own handle (hpfw_gpu_group_handle) afterwards are not known to the group, and the votes would be
- * counted against stale offsets without an error.  A group holds at most 64 shards (hpfw_gpu_group_create), which is also
+ * The tally reads the offsets hpfw_gpu_group_index_build recorded and hpfw_gpu_group_index_remove
+ * (include/hpfw_gpu_multi_index.h) keeps up to date: the index has to be built through the one and maintained through the
+ * other.  Clips added to or removed from a shard's own handle (hpfw_gpu_group_handle) are not known to the group, and the
+ * votes would be counted against stale offsets without an error.  A group holds at most 64 shards (hpfw_gpu_group_create), which is also
  * what hpfw_gpu_merge_knn_device takes.
  * All pointers are HOST pointers.
  */
