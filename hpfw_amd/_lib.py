@@ -26,6 +26,8 @@ DTW_MAX_PATH_CELLS = 1 << 31                             # the path call's cap o
 # the pairs kernel: a lane holds DTW_STRIP columns, a wave's pass DTW_BLOCK; a wider clip runs in blocks (hpfw_gpu_dtw_geometry)
 DTW_STRIP, DTW_BLOCK = 8, 512
 # hpfw_index_move: a piece of the plan of a removal from the index
+# hpfw_dup_pair: a pair of the catalogue self-join: clips a < b, position 0 of a on position lag of b
+DUP_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("dist", "<u4"), ("overlap", "<u4"), ("lag", "<i4"), ("pad", "<u4")])
 INDEX_MOVE_DTYPE = np.dtype([("dst", "<i8"), ("src", "<i8"), ("len", "<i8"), ("chunk", "<i8"), ("staged", "<i4"), ("pad", "<i4")])
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
 # hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
@@ -104,6 +106,7 @@ EXPORTS = (
     "hpfw_gpu_dtw_path_device", "hpfw_gpu_dtw_path", "hpfw_gpu_dtw_geometry",
     "hpfw_gpu_index_remove", "hpfw_gpu_index_reserve", "hpfw_gpu_index_capacity", "hpfw_gpu_index_remove_plan",
     "hpfw_gpu_index_remove_geometry",
+    "hpfw_gpu_index_selfjoin_device", "hpfw_gpu_index_selfjoin", "hpfw_gpu_selfjoin_geometry",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -231,6 +234,9 @@ def lib():
     L.hpfw_gpu_index_capacity.restype = i64
     L.hpfw_gpu_index_remove_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_index_remove_geometry.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.hpfw_gpu_index_selfjoin_device.argtypes = [vp, i32, i32, i32, vp, i64, vp, vp]
+    L.hpfw_gpu_index_selfjoin.argtypes = [vp, i32, i32, i32, vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_selfjoin_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.hpfw_gpu_timer_start.argtypes = [vp, vp]
     L.hpfw_gpu_timer_stop.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.hpfw_gpu_stage_spectrogram.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -427,6 +433,14 @@ def hit_score(dist, counted, stats):
 
 
 OVERLAP_RATE_BITS = 10                                   # HPFW_OVERLAP_RATE_BITS
+
+
+def selfjoin_geometry():
+    """(slice, chunk) of the catalogue self-join: positions of a staged per pass, lags of b per workgroup pass
+    (hpfw_gpu_selfjoin_geometry)"""
+    sl, ch = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().hpfw_gpu_selfjoin_geometry(ctypes.byref(sl), ctypes.byref(ch)))
+    return int(sl.value), int(ch.value)
 
 
 def overlap_rate(dist, overlap):
@@ -1014,6 +1028,26 @@ class Gpu:
 
     def index_capacity(self):
         return int(lib().hpfw_gpu_index_capacity(self._h))
+
+    # ---- catalogue self-join: the recordings of the index that duplicate or contain each other
+    def index_selfjoin(self, min_overlap, rate_num, rate_den, cap=1024):
+        """DUP_PAIR_DTYPE [n]: every pair of clips a < b whose best lag by the overlap rule, over at least min_overlap
+        hashprints, has dist * rate_den <= rate_num * overlap, in ascending (a, b) (include/hpfw_gpu.h).  Neither min_overlap
+        nor the threshold has a default.  cap: the pairs the first call has room for; the buffer grows to the count and the call
+        repeats while the count exceeds it."""
+        cap = max(int(cap), 0)
+        while True:
+            out = np.zeros(cap, DUP_PAIR_DTYPE)
+            count = ctypes.c_int64(0)
+            check(lib().hpfw_gpu_index_selfjoin(self._h, int(min_overlap), int(rate_num), int(rate_den), _hp(out), cap, ctypes.byref(count)))
+            if count.value <= cap:
+                return out[:count.value].copy()
+            cap = int(count.value)
+
+    def index_selfjoin_dev(self, min_overlap, rate_num, rate_den, d_out, cap, d_count, stream=0):
+        """device pointers: d_out DUP_PAIR_DTYPE [cap] (0 with cap = 0) receives the first cap pairs, d_count (int64) their
+        total number, which may exceed cap"""
+        check(lib().hpfw_gpu_index_selfjoin_device(self._h, int(min_overlap), int(rate_num), int(rate_den), d_out, int(cap), d_count, stream))
 
     def search_topk(self, q_hp, q_off, k):
         q = np.ascontiguousarray(q_hp, np.uint64).ravel()

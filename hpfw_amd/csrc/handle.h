@@ -1,5 +1,5 @@
 // handle.h -- what the sources of the C-ABI declared in include/hpfw_gpu.h (handle.hip, plans.hip, extract.hip, learn.hip,
-// search.hip, dtw.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
+// search.hip, selfjoin.hip, dtw.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
 // ParallelCollector::collect_fingerprints' parallel_for, reference
 // include/hpfw/core/parallel_collector.h:115-137) and MemoryStorage::build/find
 // (include/hpfw/audioproblems/live-song-id/storage.h:21-64).  All arithmetic is in the kernels.
@@ -144,6 +144,9 @@ struct hpfw_gpu {
         DevBuf d_topk_scratch;
         DevBuf d_shift_hits; // the per-shift top-k lists of a transposed search
         DevBuf d_ov_tab, d_ov_exclude; // overlap search: the (query, clip, split) entries, the clips to skip
+        // self-join (selfjoin.hip): the (row, clip, split) entries of a pass, its rows' counts and first
+        // positions, the passes' numbering of their (row group, clip) pairs
+        DevBuf d_sj_tab, d_sj_rows, d_sj_pairs;
         // voting search on the device: the workspaces of one group of windows, carved from one buffer;
         // the first window and first hashprint of every query of the call
         DevBuf d_votes_ws, d_votes_tab;

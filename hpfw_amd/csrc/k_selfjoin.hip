@@ -1,0 +1,490 @@
+// k_selfjoin.hip -- the join of the index with itself (include/hpfw_gpu.h): for clips a < b the best lag
+// of a against b by the overlap rule of section 17, and every pair under the caller's threshold.
+//
+// Clip a takes the query's part and b the clip's: lag d puts position j of a on position d + j of b, L(d) =
+// min(n_a, n_b - d) - max(0, -d), dist(d) = sum popcount(a[j] ^ b[d + j]); candidates with L >= min_overlap are ordered by
+// dist / L as an exact rational (cross-multiplied in 64 bits: dist <= 2^24, L < 2^18), then larger L, then smaller d.
+//
+// (a) selfjoin_mfma_kernel descends from overlap_mfma_kernel (k_search_overlap.hip): a workgroup = 32 rows (clips a of one
+// row group) x 1024 lags of one b per chunk, fp4 +-1 operands, fp4 0 outside either recording, accumulator 64 L - 2 dist.
+// Both operands are read from the index where it lies and expanded while they are staged.  The rows are walked in SLICES of
+// kSjSlice positions: per slice the 32 rows' hashprints and the kSjChunk + kSjSlice positions of b that the chunk's lags put
+// under them go to the LDS, and the accumulators stay in registers across slices -- the LDS does not depend on a
+// recording's length.  Slices that lie wholly before b's start or past its end are not staged.
+// (b) selfjoin_popc_kernel computes the same by xor/popcount (HPFW_SELFJOIN_POPC): the second opinion on the device.
+//
+// Work is launched for b above a group's first row only: workgroup p / splits of a pass is pair p of pair_first's prefix.
+// Rows with a >= b (the triangle cuts through a group) and rows below min_overlap are masked.  Both kernels write one
+// 16-byte entry {dist, L, lag, 0} per (row, b, split) with ordinary stores, as section 17 does.  selfjoin_count_kernel folds
+// the splits and counts a row's pairs under the threshold, selfjoin_offsets_kernel turns the counts into positions, and
+// selfjoin_write_kernel writes the pairs in (a, b) order: no atomics, nothing depends on the order workgroups run in.
+#include "kernels.h"
+
+namespace hpfw {
+
+extern __shared__ __align__(16) unsigned char smem_raw[];
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+namespace {
+constexpr int kSjThreads = 512;                            // 8 waves
+constexpr int kSjTiles = 4;                                // lag tiles of 32 per wave
+constexpr int kSjWaveLags = 32 * kSjTiles;                 // 128
+constexpr int kSjWin = kSelfjoinChunk + kSelfjoinSlice;    // positions of b staged per slice (one spare)
+constexpr int kSjBLoads = (kSjWin + kSjThreads - 1) / kSjThreads; // positions of b per thread and slice
+static_assert(kSjWaveLags * (kSjThreads / 64) == kSelfjoinChunk, "kernels.h states the chunk");
+static_assert(kSelfjoinSlice == 32 && kSjThreads == 512, "stage_a deals 32 positions x 32 rows to 512 threads, two each");
+static_assert(kSelfjoinChunk == 1024, "a candidate's lag inside the chunk takes 10 bits");
+
+constexpr unsigned kSjNoDist = 1u << 25;                   // above every distance (64 L <= 2^24); with L = 1 above every rate
+constexpr unsigned kSjLMax = (unsigned)kSelfjoinMaxLen;    // 2^18 - 1
+
+// 8 bits -> 8 E2M1 nibbles, bit i in nibble i: 0 -> +1.0 (0x2), 1 -> -1.0 (0xA)  (as k_search_mfma.hip)
+__device__ __forceinline__ uint32_t sj_expand8(uint32_t x)
+{
+    uint32_t t = (x | (x << 12)) & 0x000F000Fu;
+    t = (t | (t << 6)) & 0x03030303u;
+    t = (t | (t << 3)) & 0x11111111u;
+    return 0x22222222u | (t << 3);
+}
+
+__device__ __forceinline__ v4i sj_expand32(uint32_t w)
+{
+    v4i r;
+    r.x = (int)sj_expand8(w & 0xff);
+    r.y = (int)sj_expand8((w >> 8) & 0xff);
+    r.z = (int)sj_expand8((w >> 16) & 0xff);
+    r.w = (int)sj_expand8(w >> 24);
+    return r;
+}
+
+// dist1 / L1 against dist2 / L2: dist <= 2^24 and L < 2^18, so the products are below 2^42
+__device__ __forceinline__ uint64_t sj_mul(unsigned a, unsigned b) { return (uint64_t)a * (uint64_t)b; }
+
+// Inside a chunk a candidate is two words: dist, and w = (kSjLMax - L) << 10 | lag inside the chunk (28 bits) -- at equal
+// rates the smaller w has the larger L, then the smaller lag.  "none" is (kSjNoDist, L = 1).
+constexpr unsigned kSjNoW = ((kSjLMax - 1) << 10) | 0x3ffu;
+__device__ __forceinline__ bool sj_less(unsigned d1, unsigned w1, unsigned d2, unsigned w2)
+{
+    const uint64_t a = sj_mul(d1, kSjLMax - (w2 >> 10)), b = sj_mul(d2, kSjLMax - (w1 >> 10));
+    return a < b || (a == b && w1 < w2);
+}
+
+// a workgroup's best of one row over the chunks it has done (in rising order of lag)
+struct SjBest {
+    unsigned dist = kSjNoDist, L = 1;
+    int lag = 0;
+    // a candidate of a later chunk: a larger lag, so it wins on a smaller rate or, at the same rate, a larger L
+    __device__ void offer(unsigned d, unsigned l, int g)
+    {
+        const uint64_t a = sj_mul(d, L), b = sj_mul(dist, l);
+        if (a < b || (a == b && l > L)) {
+            dist = d;
+            L = l;
+            lag = g;
+        }
+    }
+    __device__ void store(uint4 *e) const
+    {
+        if (dist != kSjNoDist) *e = make_uint4(dist, L, (unsigned)lag, 0u);
+    }
+};
+
+// dist / L at or below rate_num / rate_den: dist rate_den <= 2^34, rate_num L < 2^34
+__device__ __forceinline__ bool sj_reported(const uint4 &e, unsigned rate_num, unsigned rate_den)
+{
+    return e.x != 0xffffffffu && sj_mul(e.x, rate_den) <= sj_mul(rate_num, e.y);
+}
+} // namespace
+
+struct SelfjoinArgs {
+    const uint64_t *db;
+    const int64_t *db_off;
+    int n_clips;
+    int g0, n_groups;           // the pass: row groups g0 .. g0 + n_groups - 1 (rows 32 g .. 32 g + 31)
+    const uint32_t *pair_first; // [n_groups + 1]: group g0 + i has the pairs pair_first[i] .. pair_first[i + 1] - 1, one per b > 32 (g0 + i)
+    int min_overlap, splits;
+    uint4 *tab;                 // [32 n_groups][n_clips][splits], every byte preset to 0xff
+};
+
+namespace {
+// the workgroup's pair and split; the rows' lengths (0: masked) and starts; kt, the longest unmasked row
+struct SjPair {
+    int gi, b, split, kt;
+};
+__device__ __forceinline__ SjPair sj_pair(const SelfjoinArgs &a, int *lens, int64_t *starts)
+{
+    SjPair p;
+    const unsigned pair = blockIdx.x / (unsigned)a.splits;
+    p.split = (int)(blockIdx.x - pair * (unsigned)a.splits);
+    int lo = 0, hi = a.n_groups; // the last group whose first pair is at or below this one
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.pair_first[mid] <= pair)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    p.gi = lo;
+    p.b = 32 * (a.g0 + lo) + 1 + (int)(pair - a.pair_first[lo]);
+    if (threadIdx.x < 32) {
+        const int row = 32 * (a.g0 + lo) + (int)threadIdx.x;
+        int k = 0;
+        int64_t o = 0;
+        if (row < p.b) { // (b < n_clips: the row exists)
+            o = a.db_off[row];
+            k = (int)(a.db_off[row + 1] - o);
+            if (k < a.min_overlap) k = 0;
+        }
+        lens[threadIdx.x] = k;
+        starts[threadIdx.x] = o;
+    }
+    __syncthreads();
+    p.kt = 0;
+    for (int m = 0; m < 32; ++m) p.kt = max(p.kt, lens[m]);
+    return p;
+}
+} // namespace
+
+__global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(SelfjoinArgs a)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_lane = lane & 31, h = lane >> 5;
+    v4i *ldsB = reinterpret_cast<v4i *>(smem_raw);           // [2][kSjWin]: plane h = bits [32 h, 32 h + 32) of each hashprint
+    v4i *ldsA = ldsB + 2 * kSjWin;                           // [kSjSlice][64]: lane (m, h) of position j
+    int64_t *starts = reinterpret_cast<int64_t *>(ldsA + kSelfjoinSlice * 64); // [32]
+    int *lens = reinterpret_cast<int *>(starts + 32);        // [32]
+    uint2 *red = reinterpret_cast<uint2 *>(ldsA);            // [8 waves][32 rows], over the A operand once the sums are done
+
+    const SjPair p = sj_pair(a, lens, starts);
+    const int64_t r0 = a.db_off[p.b];
+    const int n = (int)(a.db_off[p.b + 1] - r0);
+    const int kt = p.kt, mo = a.min_overlap;
+    if (n < mo || kt == 0) return; // no row of the group has a candidate in this clip
+    const int d_lo = mo - kt, d_hi = n - mo;
+    const int n_wg_chunks = (d_hi - d_lo) / kSelfjoinChunk + 1;
+
+    // staging: thread -> 8 consecutive positions of 8 rows per wave (64-byte runs of a row), two (position, row) items
+    int ja[2], ma[2], ka[2];
+    int64_t oa[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int c = wave * 2 + e;
+        ja[e] = (c & 3) * 8 + (lane & 7);
+        ma[e] = (c >> 2) * 8 + (lane >> 3);
+        ka[e] = lens[ma[e]];
+        oa[e] = starts[ma[e]];
+    }
+    const int one = 0x7f7f7f7f; // E8M0 scale 2^0
+    const v4i *bp = ldsB + h * kSjWin + wave * kSjWaveLags + n_lane;
+    const v4i *ap = ldsA + lane;
+    SjBest best; // (threads below 32)
+
+    for (int wc = p.split; wc < n_wg_chunks; wc += a.splits) {
+        const int d0 = d_lo + wc * kSelfjoinChunk;
+        // slices j0 (multiples of kSjSlice) whose window of b, positions d0 + j0 .. d0 + j0 + kSjWin - 1, meets the clip
+        const int before = -d0 - kSjWin + 1; // j0 >= before
+        const int j_begin = before <= 0 ? 0 : (before + kSelfjoinSlice - 1) / kSelfjoinSlice * kSelfjoinSlice;
+        const int j_end = min(kt, n - d0);   // j0 < j_end
+        f32x16 acc[kSjTiles];
+#pragma unroll
+        for (int t = 0; t < kSjTiles; ++t) acc[t] = f32x16{0};
+        // a wave whose 128 lags all lie past n - min_overlap (the clip's last chunk) multiplies nothing: it only helps staging
+        const bool live = d0 + wave * kSjWaveLags <= d_hi;
+
+        uint64_t ra[2], rb[kSjBLoads];
+        unsigned ok = 0; // bit e: ra[e] is a hashprint of its row; bit 2 + e: rb[e] is a hashprint of b
+        auto load = [&](int j0) {
+            ok = 0;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                ra[e] = 0;
+                if (j0 + ja[e] < ka[e]) {
+                    ra[e] = a.db[oa[e] + j0 + ja[e]];
+                    ok |= 1u << e;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < kSjBLoads; ++e) {
+                const int i = tid + kSjThreads * e, gi = d0 + j0 + i;
+                rb[e] = 0;
+                if (i < kSjWin && gi >= 0 && gi < n) {
+                    rb[e] = a.db[r0 + gi];
+                    ok |= 4u << e;
+                }
+            }
+        };
+        load(j_begin);
+        for (int j0 = j_begin; j0 < j_end; j0 += kSelfjoinSlice) {
+            __syncthreads(); // the slice before this one, or the chunk's candidates, have been read
+            const v4i zero = {0, 0, 0, 0};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const bool v = (ok >> e) & 1u;
+                ldsA[ja[e] * 64 + ma[e]] = v ? sj_expand32((uint32_t)ra[e]) : zero;
+                ldsA[ja[e] * 64 + 32 + ma[e]] = v ? sj_expand32((uint32_t)(ra[e] >> 32)) : zero;
+            }
+#pragma unroll
+            for (int e = 0; e < kSjBLoads; ++e) {
+                const int i = tid + kSjThreads * e;
+                if (i < kSjWin) {
+                    const bool v = (ok >> (2 + e)) & 1u;
+                    ldsB[i] = v ? sj_expand32((uint32_t)rb[e]) : zero;
+                    ldsB[kSjWin + i] = v ? sj_expand32((uint32_t)(rb[e] >> 32)) : zero;
+                }
+            }
+            __syncthreads();
+            if (j0 + kSelfjoinSlice < j_end) load(j0 + kSelfjoinSlice); // the next slice into registers while this one multiplies
+            const int jn = min(kSelfjoinSlice, kt - j0);
+            for (int j = 0; live && j < jn; ++j) {
+                const v4i a4 = ap[j * 64];
+                const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
+#pragma unroll
+                for (int t = 0; t < kSjTiles; ++t) {
+                    const v4i b4 = bp[j + 32 * t];
+                    const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
+                    acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
+                }
+            }
+        }
+        __syncthreads(); // the last slice has been read: the candidates go over the A operand
+
+        // acc[t][reg]: row m = (reg & 3) + 8 (reg >> 2) + 4 h, lag d0 + wave 128 + t 32 + n_lane
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int m = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            const int k = lens[m];
+            unsigned bd = kSjNoDist, bw = kSjNoW;
+#pragma unroll
+            for (int t = 0; t < kSjTiles; ++t) {
+                const int lo = wave * kSjWaveLags + t * 32 + n_lane;
+                const int d = d0 + lo;
+                const int L = min(k, n - d) + min(0, d);
+                const unsigned dist = (unsigned)((64 * L - (int)acc[t][reg]) >> 1);
+                const unsigned w = ((kSjLMax - (unsigned)L) << 10) | (unsigned)lo;
+                if (k > 0 && L >= mo && sj_less(dist, w, bd, bw)) {
+                    bd = dist;
+                    bw = w;
+                }
+            }
+#pragma unroll
+            for (int s = 16; s >= 1; s >>= 1) { // the best of the 32 lag columns of this half-wave
+                const unsigned od = (unsigned)__shfl_xor((int)bd, s), ow = (unsigned)__shfl_xor((int)bw, s);
+                if (sj_less(od, ow, bd, bw)) {
+                    bd = od;
+                    bw = ow;
+                }
+            }
+            if (n_lane == 0) red[wave * 32 + m] = make_uint2(bd, bw);
+        }
+        __syncthreads();
+        if (tid < 32) {
+            uint2 b = red[tid];
+            for (int w = 1; w < kSjThreads / 64; ++w) {
+                const uint2 o = red[w * 32 + tid];
+                if (sj_less(o.x, o.y, b.x, b.y)) b = o;
+            }
+            if (b.x != kSjNoDist) best.offer(b.x, kSjLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
+        }
+    }
+    if (tid < 32 && lens[tid] > 0)
+        best.store(a.tab + ((int64_t)(32 * p.gi + tid) * a.n_clips + p.b) * a.splits + p.split);
+}
+
+// the same pairs, splits and chunks (the chunks of a pair begin at min_overlap - the group's longest row for every row): a
+// thread takes four lags of a chunk and walks their overlaps, one row after the other
+__global__ __launch_bounds__(256) void selfjoin_popc_kernel(SelfjoinArgs a)
+{
+    __shared__ uint2 red[4];
+    __shared__ int lens[32];
+    __shared__ int64_t starts[32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SjPair p = sj_pair(a, lens, starts);
+    const int64_t r0 = a.db_off[p.b];
+    const int n = (int)(a.db_off[p.b + 1] - r0), mo = a.min_overlap;
+    if (n < mo || p.kt == 0) return;
+    const uint64_t *r = a.db + r0;
+    const int d_lo = mo - p.kt, d_hi = n - mo;
+    const int n_wg_chunks = (d_hi - d_lo) / kSelfjoinChunk + 1;
+    for (int m = 0; m < 32; ++m) {
+        const int k = lens[m];
+        if (k == 0) continue;
+        const uint64_t *q = a.db + starts[m];
+        SjBest best; // (thread 0)
+        for (int wc = p.split; wc < n_wg_chunks; wc += a.splits) {
+            const int d0 = d_lo + wc * kSelfjoinChunk;
+            unsigned bd = kSjNoDist, bw = kSjNoW;
+            for (int e = 0; e < kSelfjoinChunk / 256; ++e) {
+                const int lo = tid + 256 * e, d = d0 + lo;
+                if (d > d_hi) break;
+                const int j0 = max(0, -d), j1 = min(k, n - d);
+                if (j1 - j0 < mo) continue; // (a row shorter than the group's longest)
+                unsigned dist = 0;
+                for (int j = j0; j < j1; ++j) dist += (unsigned)__popcll(q[j] ^ r[d + j]);
+                const unsigned w = ((kSjLMax - (unsigned)(j1 - j0)) << 10) | (unsigned)lo;
+                if (sj_less(dist, w, bd, bw)) {
+                    bd = dist;
+                    bw = w;
+                }
+            }
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) {
+                const unsigned od = (unsigned)__shfl_xor((int)bd, s), ow = (unsigned)__shfl_xor((int)bw, s);
+                if (sj_less(od, ow, bd, bw)) {
+                    bd = od;
+                    bw = ow;
+                }
+            }
+            __syncthreads(); // (the chunk before has been read)
+            if (lane == 0) red[wave] = make_uint2(bd, bw);
+            __syncthreads();
+            if (tid == 0) {
+                uint2 b = red[0];
+                for (int w = 1; w < 4; ++w)
+                    if (sj_less(red[w].x, red[w].y, b.x, b.y)) b = red[w];
+                if (b.x != kSjNoDist) best.offer(b.x, kSjLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
+            }
+        }
+        if (tid == 0) best.store(a.tab + ((int64_t)(32 * p.gi + m) * a.n_clips + p.b) * a.splits + p.split);
+    }
+}
+
+// one workgroup per row a of the pass: the splits of every b > a folded into the pair's first entry, and the row's pairs
+// under the threshold counted
+__global__ __launch_bounds__(256) void selfjoin_count_kernel(uint4 *__restrict__ tab, int n_clips, int splits, int row0, unsigned rate_num,
+                                                             unsigned rate_den, int *__restrict__ row_count)
+{
+    __shared__ int red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint4 *row = tab + (int64_t)blockIdx.x * n_clips * splits;
+    int cnt = 0;
+    for (int c = row0 + (int)blockIdx.x + 1 + tid; c < n_clips; c += 256) {
+        uint4 b = row[(int64_t)c * splits];
+        for (int s = 1; s < splits; ++s) {
+            const uint4 e = row[(int64_t)c * splits + s];
+            if (e.x == 0xffffffffu) continue;
+            const uint64_t x = sj_mul(e.x, b.y), y = sj_mul(b.x, e.y);
+            if (b.x == 0xffffffffu || x < y || (x == y && (e.y > b.y || (e.y == b.y && (int)e.z < (int)b.z)))) b = e;
+        }
+        if (splits > 1) row[(int64_t)c * splits] = b;
+        cnt += sj_reported(b, rate_num, rate_den) ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) cnt += __shfl_xor(cnt, s);
+    if (lane == 0) red[wave] = cnt;
+    __syncthreads();
+    if (tid == 0) row_count[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// one workgroup: row_first[i] = *total + the counts of the pass's rows before i, then *total += the pass's pairs
+__global__ __launch_bounds__(1024) void selfjoin_offsets_kernel(const int *__restrict__ row_count, int n_rows, int64_t *__restrict__ row_first,
+                                                                int64_t *__restrict__ total)
+{
+    __shared__ int64_t part[1024];
+    const int tid = threadIdx.x;
+    const int per = (n_rows + 1023) / 1024, i0 = tid * per, i1 = min(n_rows, i0 + per);
+    int64_t sum = 0;
+    for (int i = i0; i < i1; ++i) sum += row_count[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (int s = 1; s < 1024; s <<= 1) { // (inclusive scan of the threads' sums)
+        const int64_t v = tid >= s ? part[tid - s] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    const int64_t base = *total;
+    int64_t at = base + part[tid] - sum;
+    for (int i = i0; i < i1; ++i) {
+        row_first[i] = at;
+        at += row_count[i];
+    }
+    __syncthreads(); // (every thread has read *total)
+    if (tid == 1023) *total = base + part[1023];
+}
+
+namespace {
+struct DupPairDev {
+    uint32_t a, b, dist, overlap;
+    int32_t lag;
+    uint32_t pad;
+};
+static_assert(sizeof(DupPairDev) == sizeof(hpfw_dup_pair), "the record of include/hpfw_gpu.h");
+} // namespace
+
+// one workgroup per row a: its pairs under the threshold in rising b, from position row_first[a] on, while below cap
+__global__ __launch_bounds__(256) void selfjoin_write_kernel(const uint4 *__restrict__ tab, int n_clips, int splits, int row0, unsigned rate_num,
+                                                             unsigned rate_den, const int64_t *__restrict__ row_first, uint32_t clip_base,
+                                                             DupPairDev *__restrict__ out, int64_t cap)
+{
+    __shared__ int wave_n[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int a = row0 + (int)blockIdx.x;
+    const uint4 *row = tab + (int64_t)blockIdx.x * n_clips * splits;
+    int64_t at = row_first[blockIdx.x];
+    for (int c0 = a + 1; c0 < n_clips && at < cap; c0 += 256) {
+        const int c = c0 + tid;
+        uint4 e = make_uint4(0xffffffffu, 0u, 0u, 0u);
+        if (c < n_clips) e = row[(int64_t)c * splits];
+        const bool rep = sj_reported(e, rate_num, rate_den);
+        const unsigned long long mask = __ballot(rep);
+        __syncthreads(); // (the block of 256 before has been read)
+        if (lane == 0) wave_n[wave] = __popcll(mask);
+        __syncthreads();
+        int64_t mine = at + __popcll(mask & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) mine += wave_n[w];
+        if (rep && mine < cap) out[mine] = {clip_base + (uint32_t)a, clip_base + (uint32_t)c, e.x, e.y, (int32_t)e.z, 0u};
+        at += wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    }
+}
+
+size_t selfjoin_mfma_lds_bytes() { return (size_t)2 * kSjWin * 16 + (size_t)kSelfjoinSlice * 64 * 16 + 32 * 8 + 32 * 4; }
+
+static SelfjoinArgs selfjoin_args(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups, const uint32_t *d_pair_first,
+                                  int min_overlap, int splits, void *d_tab)
+{
+    SelfjoinArgs a = {};
+    a.db = d_db;
+    a.db_off = d_db_off;
+    a.n_clips = n_clips;
+    a.g0 = g0;
+    a.n_groups = n_groups;
+    a.pair_first = d_pair_first;
+    a.min_overlap = min_overlap;
+    a.splits = splits;
+    a.tab = reinterpret_cast<uint4 *>(d_tab);
+    return a;
+}
+
+void launch_selfjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups,
+                          const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits, void *d_tab, hipStream_t s)
+{
+    const SelfjoinArgs a = selfjoin_args(d_db, d_db_off, n_clips, g0, n_groups, d_pair_first, min_overlap, splits, d_tab);
+    const dim3 grid(n_pairs * (unsigned)splits);
+    if (popc) {
+        hipLaunchKernelGGL(selfjoin_popc_kernel, grid, dim3(256), 0, s, a);
+        return;
+    }
+    static PerDeviceOnce attr_set;
+    if (attr_set.need()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(selfjoin_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)selfjoin_mfma_lds_bytes());
+        attr_set.mark();
+    }
+    hipLaunchKernelGGL(selfjoin_mfma_kernel, grid, dim3(kSjThreads), selfjoin_mfma_lds_bytes(), s, a);
+}
+
+void launch_selfjoin_select(void *d_tab, int n_clips, int splits, int row0, int n_rows, uint32_t rate_num, uint32_t rate_den, int *d_row_count,
+                            int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s)
+{
+    hipLaunchKernelGGL(selfjoin_count_kernel, dim3(n_rows), dim3(256), 0, s, reinterpret_cast<uint4 *>(d_tab), n_clips, splits, row0, rate_num,
+                       rate_den, d_row_count);
+    hipLaunchKernelGGL(selfjoin_offsets_kernel, dim3(1), dim3(1024), 0, s, d_row_count, n_rows, d_row_first, d_count);
+    if (cap > 0)
+        hipLaunchKernelGGL(selfjoin_write_kernel, dim3(n_rows), dim3(256), 0, s, reinterpret_cast<const uint4 *>(d_tab), n_clips, splits, row0,
+                           rate_num, rate_den, d_row_first, clip_base, reinterpret_cast<DupPairDev *>(d_out), cap);
+}
+
+} // namespace hpfw

@@ -404,6 +404,21 @@ void launch_overlap_select(void *d_tab, int n_q, int n_clips, int splits, const 
 constexpr int kOverlapRateBits = HPFW_OVERLAP_RATE_BITS;
 inline int overlap_stats_slices(int n_clips) { return std::max(1, std::min(64, n_clips / 4096)); } // as launch_dist_stats cuts a row
 void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, void *d_stats, hipStream_t s);
+// the index joined with itself (k_selfjoin.hip): for clips a < b the best lag of a against b by the
+// overlap rule.  The rows a of a pass are row groups g0 .. g0 + n_groups - 1 (32 rows each); the pairs (group, b) with b above
+// the group's first row are numbered by d_pair_first [n_groups + 1], n_pairs of them in all (> 0); each has `splits`
+// workgroups.  d_tab [32 n_groups][n_clips][splits] of 16-byte entries {dist, overlap, lag, 0}, every byte preset to 0xff.
+// A row is walked in slices of kSelfjoinSlice positions, a pair's lags in chunks of kSelfjoinChunk.
+constexpr int kSelfjoinChunk = 1024;
+constexpr int kSelfjoinSlice = 32;
+constexpr int kSelfjoinMaxLen = (1 << 18) - 1; // hashprints of a recording: 64 L < 2^24 keeps the fp32 accumulators exact
+void launch_selfjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups,
+                          const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits, void *d_tab, hipStream_t s);
+// folds the splits (in d_tab), counts the pairs of rows row0 .. row0 + n_rows - 1 with dist rate_den <= rate_num overlap into
+// d_row_count, their positions from *d_count on into d_row_first, writes those below cap to d_out (hpfw_dup_pair, rising
+// (a, b)) and adds the pass's pairs to *d_count
+void launch_selfjoin_select(void *d_tab, int n_clips, int splits, int row0, int n_rows, uint32_t rate_num, uint32_t rate_den, int *d_row_count,
+                            int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s);
 // per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
 // (dist, shift index), then the k best by (dist, clip)
 void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);

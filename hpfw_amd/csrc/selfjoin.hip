@@ -1,0 +1,116 @@
+// selfjoin.hip -- the index joined with itself (k_selfjoin.hip): the entry points, their checks and the
+// passes over the row groups.
+#include "handle.h"
+
+// what can be refused without the handle's contents, before a device is touched
+static int selfjoin_check(const void *h, int min_overlap, int rate_num, int rate_den, const void *out, int64_t cap, const void *count)
+{
+    if (!h) return fail(HPFW_E_INVALID, "null handle");
+    if (rate_den < 1 || rate_den > 1024) return fail(HPFW_E_INVALID, "selfjoin: rate_den must be in 1..1024");
+    if (rate_num < 0 || rate_num > 64 * rate_den) return fail(HPFW_E_INVALID, "selfjoin: rate_num must be in 0..64 rate_den");
+    if (min_overlap < 1 || min_overlap > hpfw::kSelfjoinMaxLen) return fail(HPFW_E_INVALID, "selfjoin: min_overlap must be in 1..262143");
+    if (cap < 0) return fail(HPFW_E_INVALID, "selfjoin: cap must not be negative");
+    if (cap > 0 && !out) return fail(HPFW_E_INVALID, "selfjoin: null out");
+    if (!count) return fail(HPFW_E_INVALID, "selfjoin: null count");
+    return 0;
+}
+
+static int selfjoin_length_check(const hpfw_gpu *h)
+{
+    if (index_longest_clip(h) > hpfw::kSelfjoinMaxLen)
+        return fail(HPFW_E_UNSUPPORTED, "selfjoin: a recording of the index has more than 262143 hashprints");
+    return 0;
+}
+
+extern "C" {
+
+int hpfw_gpu_selfjoin_geometry(int32_t *slice, int32_t *chunk)
+{
+    if (!slice || !chunk) return fail(HPFW_E_INVALID, "null argument");
+    *slice = hpfw::kSelfjoinSlice;
+    *chunk = hpfw::kSelfjoinChunk;
+    return 0;
+}
+
+int hpfw_gpu_index_selfjoin_device(hpfw_gpu *h, int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *d_out, int64_t cap,
+                                   int64_t *d_count, void *stream)
+{
+    if (int rc = selfjoin_check(h, min_overlap, rate_num, rate_den, d_out, cap, d_count)) return rc;
+    if (int rc = selfjoin_length_check(h)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+    if (n_clips * 32 > ((int64_t)1 << 26)) return fail(HPFW_E_UNSUPPORTED, "selfjoin: more than 2097152 clips");
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, s, [&] {
+        int rc;
+        HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
+        const int64_t n_max = index_longest_clip(h);
+        if (n_clips < 2 || n_max < min_overlap) return 0; // no pair has a candidate
+        if ((rc = upload_db_off(h, s))) return rc;
+        const bool popc = std::getenv("HPFW_SELFJOIN_POPC") != nullptr;
+        // the pairs (row group, b): b above the group's first row
+        const int64_t n_groups = (n_clips + 31) / 32;
+        auto group_pairs = [&](int64_t g) { return std::max<int64_t>(n_clips - 32 * g - 1, 0); };
+        int64_t pairs = 0;
+        for (int64_t g = 0; g < n_groups; ++g) pairs += group_pairs(g);
+        // A pair's lags come in chunks of 1024; with few pairs the chunks of a pair go to `splits` workgroups, each with an
+        // entry of its own (HPFW_SELFJOIN_SPLITS: that many, for tests of either shape)
+        const int64_t chunks = (2 * n_max - 2 * min_overlap) / hpfw::kSelfjoinChunk + 1;
+        int64_t splits = std::min<int64_t>({chunks, (2048 + pairs - 1) / pairs, 64});
+        if (const char *e = std::getenv("HPFW_SELFJOIN_SPLITS")) splits = std::min<int64_t>(std::max(std::atoi(e), 1), 64);
+        // row groups are processed in passes so that the table stays at or below 1 GiB (2^26 entries; HPFW_SELFJOIN_TABLE_KB:
+        // that many KiB, at least one row group's, for tests of more than one pass)
+        int64_t budget = (int64_t)1 << 26;
+        if (const char *e = std::getenv("HPFW_SELFJOIN_TABLE_KB")) budget = std::min(std::max<int64_t>(std::atoll(e) * 64, 32 * n_clips), budget);
+        splits = std::min(splits, budget / (32 * n_clips));
+        const int64_t pass_groups = std::min(n_groups, budget / (32 * n_clips * splits));
+        const int64_t n_passes = (n_groups + pass_groups - 1) / pass_groups;
+        // every pass numbers its pairs from 0: pair_first [pass_groups + 1] per pass
+        std::vector<uint32_t> pair_first((size_t)(n_passes * (pass_groups + 1)), 0);
+        for (int64_t p = 0; p < n_passes; ++p) {
+            uint32_t *pf = pair_first.data() + p * (pass_groups + 1);
+            for (int64_t i = 0; i < pass_groups; ++i) pf[i + 1] = pf[i] + (uint32_t)(p * pass_groups + i < n_groups ? group_pairs(p * pass_groups + i) : 0);
+        }
+        if ((rc = ensure(h->index.d_sj_pairs, pair_first.size() * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->index.d_sj_pairs.get(), pair_first.data(), pair_first.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s)); // (pair_first has been read)
+        const size_t tab_bytes = (size_t)(32 * pass_groups * n_clips * splits) * 16;
+        if ((rc = ensure(h->index.d_sj_tab, tab_bytes))) return rc;
+        if ((rc = ensure(h->index.d_sj_rows, (size_t)(32 * pass_groups) * (8 + 4)))) return rc;
+        int64_t *d_row_first = h->index.d_sj_rows.as<int64_t>();
+        int *d_row_count = reinterpret_cast<int *>(d_row_first + 32 * pass_groups);
+        for (int64_t p = 0; p < n_passes; ++p) {
+            const int64_t g0 = p * pass_groups, ng = std::min(pass_groups, n_groups - g0);
+            const uint32_t *d_pf = h->index.d_sj_pairs.as<uint32_t>() + p * (pass_groups + 1);
+            const uint32_t n_pairs = pair_first[(size_t)(p * (pass_groups + 1) + ng)];
+            if (n_pairs == 0) continue; // (the last group is the last clip alone)
+            HIP_TRY(hipMemsetAsync(h->index.d_sj_tab.get(), 0xff, (size_t)(32 * ng * n_clips * splits) * 16, s));
+            {
+                Timed t(h, K_SCAN, s);
+                hpfw::launch_selfjoin_scan(popc, h->index.d_db.as<uint64_t>(), h->index.d_db_off.as<int64_t>(), (int)n_clips, (int)g0, (int)ng, d_pf,
+                                           n_pairs, min_overlap, (int)splits, h->index.d_sj_tab.get(), s);
+            }
+            if ((rc = check_launch("selfjoin scan"))) return rc;
+            {
+                Timed t(h, K_TOPK, s);
+                hpfw::launch_selfjoin_select(h->index.d_sj_tab.get(), (int)n_clips, (int)splits, (int)(32 * g0), (int)(32 * ng), (uint32_t)rate_num,
+                                             (uint32_t)rate_den, d_row_count, d_row_first, h->index.clip_base, d_out, cap, d_count, s);
+            }
+            if ((rc = check_launch("selfjoin select"))) return rc;
+        }
+        return 0;
+    });
+}
+
+int hpfw_gpu_index_selfjoin(hpfw_gpu *h, int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *out, int64_t cap, int64_t *count)
+{
+    if (int rc = selfjoin_check(h, min_overlap, rate_num, rate_den, out, cap, count)) return rc;
+    if (int rc = selfjoin_length_check(h)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    HostTrip t;
+    hpfw_dup_pair *d_out = cap ? t.take<hpfw_dup_pair>((size_t)cap * sizeof(hpfw_dup_pair), nullptr, 0, out) : nullptr;
+    int64_t *d_count = t.take<int64_t>(8, nullptr, -1, count);
+    return t.run(true, [&] { return hpfw_gpu_index_selfjoin_device(h, min_overlap, rate_num, rate_den, d_out, cap, d_count, nullptr); });
+}
+
+} // extern "C"

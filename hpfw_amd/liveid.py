@@ -11,6 +11,7 @@ timeline(file) = the songs of one long recording, window by window (not in the r
 streams(n)     = the same for n feeds that are still running, as their samples arrive
 """
 import os
+from fractions import Fraction
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -47,6 +48,46 @@ class _ShardedIndex:
 
     def close(self):
         self.group.close()
+
+
+def rate_fraction(max_rate) -> Tuple[int, int]:
+    """(rate_num, rate_den) of a threshold in mismatching bits per hashprint for the catalogue self-join: an int or a Fraction
+    is taken as it is, a float through Fraction(max_rate).limit_denominator(1024).  Anything else, a denominator above 1024
+    and a rate outside [0, 64] raise HPFW_E_INVALID."""
+    if isinstance(max_rate, bool) or not isinstance(max_rate, (int, Fraction, float)):
+        raise _lib.HpfwError("max_rate must be an int, a Fraction or a float", _lib.E_INVALID)
+    if isinstance(max_rate, float):
+        if not 0.0 <= max_rate <= 64.0:                   # (NaN and the infinities as well)
+            raise _lib.HpfwError("max_rate must be in [0, 64]", _lib.E_INVALID)
+        max_rate = Fraction(max_rate).limit_denominator(1024)
+    rate = Fraction(max_rate)
+    if rate.denominator > 1024 or not 0 <= rate <= 64:
+        raise _lib.HpfwError("max_rate must be in [0, 64] with a denominator of at most 1024", _lib.E_INVALID)
+    return rate.numerator, rate.denominator
+
+
+def duplicate_groups(pairs, names: Sequence[str]) -> List[List[str]]:
+    """the connected components of duplicates()'s pairs as lists of names: every list in the order of `names` (the index's),
+    the lists by their first member; a name no pair mentions is in no list (a host union-find)"""
+    slot = {}
+    for i, name in enumerate(names):
+        slot.setdefault(name, i)
+    parent = {}
+
+    def find(x):
+        while parent.setdefault(x, x) != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for pair in pairs:
+        a, b = find(slot[pair[0]]), find(slot[pair[1]])
+        if a != b:
+            parent[max(a, b)] = min(a, b)                 # a component's root is its first slot
+    groups = {}
+    for x in sorted(parent):
+        groups.setdefault(find(x), []).append(names[x])
+    return [groups[root] for root in sorted(groups)]
 
 
 class LiveSongIdentification:
@@ -120,6 +161,26 @@ class LiveSongIdentification:
             self.names += [name for _, name in pairs]
             self._added_len += [int(hp.size) for hp, _ in pairs]
         return len(pairs)
+
+    # ---- catalogue self-join: which recordings of the index duplicate or contain each other
+    def duplicates(self, max_rate, min_overlap: int):
+        """the pairs of indexed recordings whose best alignment by the overlap rule, over at least min_overlap hashprints,
+        has at most max_rate mismatching bits per hashprint (an int, a Fraction or a float: rate_fraction()); neither has a
+        default.  [(name_a, name_b, dist, overlap, lag)] in index order of (a, b): column 0 of a lies on column lag of b
+        (negative: a begins before b does), overlap columns are compared and dist bits of them differ.  Removed recordings
+        never appear.  An identifier made with devices= raises HPFW_E_UNSUPPORTED.
+
+        What to remove is the caller's decision, for example everything but the first recording of each group:
+            groups = lsi.duplicate_groups(lsi.duplicates(16, 304))
+            lsi.remove([name for group in groups for name in group[1:]])"""
+        num, den = rate_fraction(max_rate)
+        self._no_shards("the catalogue self-join")
+        pairs = self._gpu.index_selfjoin(int(min_overlap), num, den)
+        return [(self.names[int(p["a"])], self.names[int(p["b"])], int(p["dist"]), int(p["overlap"]), int(p["lag"])) for p in pairs]
+
+    def duplicate_groups(self, pairs) -> List[List[str]]:
+        """the connected components of duplicates()'s pairs as lists of names in index order (duplicate_groups())"""
+        return duplicate_groups(pairs, self.live_names())
 
     def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None,
             tempos: Optional[Sequence[float]] = None):

@@ -190,6 +190,33 @@ public:
         return out;
     }
 
+    /// the catalogue self-join (hpfw_gpu_index_selfjoin): the pairs of indexed recordings a before b
+    /// whose best alignment by the overlap rule, over at least min_overlap hashprints, has dist * rate_den <= rate_num *
+    /// overlap, in database order of (a, b).  min_overlap and the threshold rate_num / rate_den (mismatching bits per
+    /// hashprint) are the caller's: there is no default.  Position 0 of a lies on position lag of b.
+    struct DuplicateResult {
+        std::string name_a, name_b;
+        size_t dist;    // mismatching bits over the overlap
+        size_t overlap; // hashprints compared
+        int64_t lag;
+    };
+    auto duplicates(int min_overlap, int rate_num, int rate_den) const -> std::vector<DuplicateResult>
+    {
+        std::vector<hpfw_dup_pair> pairs(256);
+        int64_t count = 0;
+        check(hpfw_gpu_index_selfjoin(h_, min_overlap, rate_num, rate_den, pairs.data(), (int64_t)pairs.size(), &count));
+        if (count > (int64_t)pairs.size()) { // (the buffer was too small: once more with room for all)
+            pairs.resize((size_t)count);
+            check(hpfw_gpu_index_selfjoin(h_, min_overlap, rate_num, rate_den, pairs.data(), (int64_t)pairs.size(), &count));
+        }
+        std::vector<DuplicateResult> out;
+        for (int64_t i = 0; i < count; ++i) {
+            const hpfw_dup_pair &p = pairs[(size_t)i];
+            out.push_back({names_[p.a], names_[p.b], (size_t)p.dist, (size_t)p.overlap, (int64_t)p.lag});
+        }
+        return out;
+    }
+
     /// the warped search (hpfw_gpu_search_dtw): the query may run faster or slower than the recording
     /// inside the window (local slope 1/2 .. 2).  candidates is the caller's (there is no default): 0 warps every clip of the
     /// index, k..64 re-ranks that many best clips of the plain search.  Query hashprint 0 lies on column start of the

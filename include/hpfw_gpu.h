@@ -536,6 +536,46 @@ int hpfw_gpu_search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const in
 int hpfw_gpu_search_overlap(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q,
                             const int32_t *exclude, int min_overlap, int k, hpfw_overlap_hit *out);
 
+/* ---- catalogue self-join: the recordings of the index that duplicate or contain each other.
+ * The index is joined with itself where it lies; recordings may have any indexed length up to 2^18 - 1 hashprints, every
+ * unordered pair is computed once, and every pair under a threshold is reported.
+ * Take clips a < b of the index in add order, both non-empty and both with at least min_overlap hashprints.  Clip a takes
+ * the part of the query of the overlap search above and b the part of the clip:
+ *   lag d puts position j of a on position d + j of b;
+ *   L(d) = min(n_a, n_b - d) - max(0, -d);    dist(d) = sum of popcount(a[j] ^ b[d + j]) over the positions both have.
+ * A lag is ADMISSIBLE when L(d) >= min_overlap, so d runs from min_overlap - n_a to n_b - min_overlap.  Candidates are
+ * ordered by dist / L as an exact rational, then by larger L, then by smaller d (the overlap search's order); the pair's
+ * candidate is its minimum.  The pair is REPORTED when dist * rate_den <= rate_num * L: rate_num / rate_den is the caller's
+ * threshold in mismatching bits per hashprint, 1 <= rate_den <= 1024, 0 <= rate_num <= 64 rate_den.  Neither min_overlap,
+ * 1 <= min_overlap <= 2^18 - 1, nor the threshold has a default.
+ * Pairs come in ascending (a, b); no floating point takes part, nothing depends on the order in which workgroups run, and
+ * no atomics are used.  Removed recordings (empty clips) and recordings below min_overlap never appear.  The clip base is
+ * added to both ids.
+ * d_out receives the first cap reported pairs, *d_count (int64) their total number, which may exceed cap: the caller
+ * enlarges the buffer and calls again.  An empty index and an index of one clip give count 0.
+ * Refused before a device is touched (HPFW_E_INVALID): a null handle, rate_den outside 1..1024, rate_num outside
+ * 0..64 rate_den, min_overlap outside 1..2^18 - 1, cap < 0, a null out with cap > 0, a null count.  An index that holds a
+ * recording above 2^18 - 1 hashprints is refused before a kernel runs (HPFW_E_UNSUPPORTED): below that bound 64 L < 2^24
+ * and the fp32 accumulators of the fp4 contraction are exact.
+ * HPFW_SELFJOIN_POPC in the environment selects the xor/popcount kernel, HPFW_SELFJOIN_SPLITS (1..64) the workgroups that
+ * share a pair's lags, HPFW_SELFJOIN_TABLE_KB the size of the table of one pass over the rows (default and most 1 GiB);
+ * they are read at every call and change no result. */
+typedef struct {
+    uint32_t a, b;    /* a < b, ids in add order + the clip base      */
+    uint32_t dist;    /* mismatching bits over the overlap            */
+    uint32_t overlap; /* L(lag)                                       */
+    int32_t lag;      /* position 0 of a lies on position lag of b    */
+    uint32_t pad;
+} hpfw_dup_pair;
+int hpfw_gpu_index_selfjoin_device(hpfw_gpu *h, int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *d_out,
+                                   int64_t cap, int64_t *d_count, void *stream);
+/* host buffers (the null stream): out [cap], *count */
+int hpfw_gpu_index_selfjoin(hpfw_gpu *h, int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *out, int64_t cap,
+                            int64_t *count);
+/* host-only: *slice = the positions of a staged per pass over the LDS, *chunk = the lags of b one workgroup pass takes (a
+ * pair's chunks begin at min_overlap - the longest of the 32 rows a that share the workgroup).  NULL is HPFW_E_INVALID. */
+int hpfw_gpu_selfjoin_geometry(int32_t *slice, int32_t *chunk);
+
 /* ---- warped search: subsequence DTW over hashprints.  Every other search lines a query up with a
  * clip rigidly (query position j on clip position offset + j); this one lets the query run faster or slower than the clip
  * inside the window, and tells which clip column every query hashprint lies on.  Exact integers throughout.
