@@ -107,6 +107,7 @@ EXPORTS = (
     "hpfw_gpu_index_remove", "hpfw_gpu_index_reserve", "hpfw_gpu_index_capacity", "hpfw_gpu_index_remove_plan",
     "hpfw_gpu_index_remove_geometry",
     "hpfw_gpu_index_selfjoin_device", "hpfw_gpu_index_selfjoin", "hpfw_gpu_selfjoin_geometry",
+    "hpfw_gpu_index_join_device", "hpfw_gpu_index_join", "hpfw_gpu_join_plan",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -237,6 +238,9 @@ def lib():
     L.hpfw_gpu_index_selfjoin_device.argtypes = [vp, i32, i32, i32, vp, i64, vp, vp]
     L.hpfw_gpu_index_selfjoin.argtypes = [vp, i32, i32, i32, vp, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_selfjoin_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.hpfw_gpu_index_join_device.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, vp, vp]
+    L.hpfw_gpu_index_join.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_join_plan.argtypes = [i64, i64, i32, i64, i64, vp]
     L.hpfw_gpu_timer_start.argtypes = [vp, vp]
     L.hpfw_gpu_timer_stop.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.hpfw_gpu_stage_spectrogram.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -433,6 +437,15 @@ def hit_score(dist, counted, stats):
 
 
 OVERLAP_RATE_BITS = 10                                   # HPFW_OVERLAP_RATE_BITS
+
+
+def join_plan(n_clips, n_x, among_new, group0, n_groups):
+    """uint32 [n_groups + 1]: the numbering of the (row group, external) items of a pass of the join over the row groups
+    group0 .. group0 + n_groups - 1 (hpfw_gpu_join_plan): item pair_first[i] + j is (group0 + i, b = max(n_clips, 32 (group0 + i) +
+    1) + j)"""
+    pair_first = np.zeros(int(n_groups) + 1, np.uint32)
+    check(lib().hpfw_gpu_join_plan(int(n_clips), int(n_x), int(among_new), int(group0), int(n_groups), _hp(pair_first)))
+    return pair_first
 
 
 def selfjoin_geometry():
@@ -1048,6 +1061,31 @@ class Gpu:
         """device pointers: d_out DUP_PAIR_DTYPE [cap] (0 with cap = 0) receives the first cap pairs, d_count (int64) their
         total number, which may exceed cap"""
         check(lib().hpfw_gpu_index_selfjoin_device(self._h, int(min_overlap), int(rate_num), int(rate_den), d_out, int(cap), d_count, stream))
+
+    # ---- ingest check (DESIGN.md section 23): recordings that are not in the index joined against it
+    def index_join(self, x_hp, x_off, min_overlap, rate_num, rate_den, among_new, cap=1024):
+        """DUP_PAIR_DTYPE [n]: the pairs (a, b) that index_add(x_hp, x_off) followed by index_selfjoin would add to the
+        self-join's answer -- b one of the recordings x (id index_size() + its position), a < b an indexed recording or, with
+        among_new, an earlier x -- without the index changing (include/hpfw_gpu.h).  Neither min_overlap nor the threshold nor
+        among_new has a default.  cap: as index_selfjoin's."""
+        x = np.ascontiguousarray(x_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(x_off, np.int64)
+        cap = max(int(cap), 0)
+        while True:
+            out = np.zeros(cap, DUP_PAIR_DTYPE)
+            count = ctypes.c_int64(0)
+            check(lib().hpfw_gpu_index_join(self._h, _hp(x) if x.size else None, _hp(off), off.size - 1, int(among_new), int(min_overlap),
+                                            int(rate_num), int(rate_den), _hp(out), cap, ctypes.byref(count)))
+            if count.value <= cap:
+                return out[:count.value].copy()
+            cap = int(count.value)
+
+    def index_join_dev(self, d_x_hp, x_off, min_overlap, rate_num, rate_den, among_new, d_out, cap, d_count, stream=0):
+        """device pointers: d_x_hp the recordings' hashprints (x_off: host), d_out DUP_PAIR_DTYPE [cap] (0 with cap = 0) receives
+        the first cap pairs, d_count (int64) their total number, which may exceed cap"""
+        off = np.ascontiguousarray(x_off, np.int64)
+        check(lib().hpfw_gpu_index_join_device(self._h, d_x_hp, _hp(off), off.size - 1, int(among_new), int(min_overlap), int(rate_num),
+                                               int(rate_den), d_out, int(cap), d_count, stream))
 
     def search_topk(self, q_hp, q_off, k):
         q = np.ascontiguousarray(q_hp, np.uint64).ravel()

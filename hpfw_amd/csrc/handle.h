@@ -147,6 +147,7 @@ struct hpfw_gpu {
         // self-join (selfjoin.hip): the (row, clip, split) entries of a pass, its rows' counts and first
         // positions, the passes' numbering of their (row group, clip) pairs
         DevBuf d_sj_tab, d_sj_rows, d_sj_pairs;
+        DevBuf d_sj_x_off; // the join with recordings outside the index (section 23): their offsets
         // voting search on the device: the workspaces of one group of windows, carved from one buffer;
         // the first window and first hashprint of every query of the call
         DevBuf d_votes_ws, d_votes_tab;

@@ -18,6 +18,11 @@
 // 16-byte entry {dist, L, lag, 0} per (row, b, split) with ordinary stores, as section 17 does.  selfjoin_count_kernel folds
 // the splits and counts a row's pairs under the threshold, selfjoin_offsets_kernel turns the counts into positions, and
 // selfjoin_write_kernel writes the pairs in (a, b) order: no atomics, nothing depends on the order workgroups run in.
+//
+// The join of the index with recordings that are not in it is the same scan under JoinArgs: the rows
+// are the 32-row groups of the list "index slots, then externals", b runs over the externals only, a clip's hashprints lie in
+// the index or in the caller's buffer, and the table's columns are the externals.  Both scan kernels are templates over
+// their arguments; what differs is in sj_clip, sj_ptr, sj_hp, sj_first_b, sj_row_end and sj_entry.
 #include "kernels.h"
 
 namespace hpfw {
@@ -107,6 +112,16 @@ struct SelfjoinArgs {
     const uint32_t *pair_first; // [n_groups + 1]: group g0 + i has the pairs pair_first[i] .. pair_first[i + 1] - 1, one per b > 32 (g0 + i)
     int min_overlap, splits;
     uint4 *tab;                 // [32 n_groups][n_clips][splits], every byte preset to 0xff
+    static constexpr bool kJoin = false;
+};
+
+// the join: clip ids n_index .. n_index + n_x - 1 are the externals x, n_clips = n_index + n_x, a pass's pairs are numbered as
+// hpfw_gpu_join_plan numbers them, rows at or above row_end are masked (among_new = 0: n_index)
+struct JoinArgs : SelfjoinArgs {
+    const uint64_t *x;
+    const int64_t *x_off;       // [n_x + 1]
+    int n_index, n_x, row_end;  // tab [32 n_groups][n_x][splits]
+    static constexpr bool kJoin = true;
 };
 
 namespace {
@@ -114,7 +129,68 @@ namespace {
 struct SjPair {
     int gi, b, split, kt;
 };
-__device__ __forceinline__ SjPair sj_pair(const SelfjoinArgs &a, int *lens, int64_t *starts)
+// where clip `id` begins and its length: the self-join keeps an offset into the index, the join the address itself (the
+// clip lies in the index or among the externals); sj_hp reads position j from either
+template <class Args>
+__device__ __forceinline__ int64_t sj_clip(const Args &a, int id, int &len)
+{
+    if constexpr (Args::kJoin) {
+        const bool ext = id >= a.n_index;
+        const int64_t *off = ext ? a.x_off + (id - a.n_index) : a.db_off + id;
+        const int64_t o = off[0];
+        len = (int)(off[1] - o);
+        return reinterpret_cast<int64_t>((ext ? a.x : a.db) + o);
+    } else {
+        const int64_t o = a.db_off[id];
+        len = (int)(a.db_off[id + 1] - o);
+        return o;
+    }
+}
+template <class Args>
+__device__ __forceinline__ const uint64_t *sj_ptr(const Args &a, int64_t start)
+{
+    if constexpr (Args::kJoin)
+        return reinterpret_cast<const uint64_t *>(start);
+    else
+        return a.db + start;
+}
+template <class Args>
+__device__ __forceinline__ uint64_t sj_hp(const Args &a, int64_t start, int j)
+{
+    if constexpr (Args::kJoin)
+        return reinterpret_cast<const uint64_t *>(start)[j];
+    else
+        return a.db[start + j];
+}
+// the b of a group's first pair; the rows of a pair are those below sj_row_end: a < b, and for the join a < row_end
+template <class Args>
+__device__ __forceinline__ int sj_first_b(const Args &a, int g)
+{
+    if constexpr (Args::kJoin)
+        return max(a.n_index, 32 * g + 1);
+    else
+        return 32 * g + 1;
+}
+template <class Args>
+__device__ __forceinline__ int sj_row_end(const Args &a, int b)
+{
+    if constexpr (Args::kJoin)
+        return min(b, a.row_end);
+    else
+        return b;
+}
+// the entry of (row of the pass, b, split)
+template <class Args>
+__device__ __forceinline__ uint4 *sj_entry(const Args &a, int row, int b, int split)
+{
+    if constexpr (Args::kJoin)
+        return a.tab + ((int64_t)row * a.n_x + (b - a.n_index)) * a.splits + split;
+    else
+        return a.tab + ((int64_t)row * a.n_clips + b) * a.splits + split;
+}
+
+template <class Args>
+__device__ __forceinline__ SjPair sj_pair(const Args &a, int *lens, int64_t *starts)
 {
     SjPair p;
     const unsigned pair = blockIdx.x / (unsigned)a.splits;
@@ -128,14 +204,13 @@ __device__ __forceinline__ SjPair sj_pair(const SelfjoinArgs &a, int *lens, int6
             hi = mid;
     }
     p.gi = lo;
-    p.b = 32 * (a.g0 + lo) + 1 + (int)(pair - a.pair_first[lo]);
+    p.b = sj_first_b(a, a.g0 + lo) + (int)(pair - a.pair_first[lo]);
     if (threadIdx.x < 32) {
         const int row = 32 * (a.g0 + lo) + (int)threadIdx.x;
         int k = 0;
         int64_t o = 0;
-        if (row < p.b) { // (b < n_clips: the row exists)
-            o = a.db_off[row];
-            k = (int)(a.db_off[row + 1] - o);
+        if (row < sj_row_end(a, p.b)) { // (b < n_clips: the row exists)
+            o = sj_clip(a, row, k);
             if (k < a.min_overlap) k = 0;
         }
         lens[threadIdx.x] = k;
@@ -148,7 +223,8 @@ __device__ __forceinline__ SjPair sj_pair(const SelfjoinArgs &a, int *lens, int6
 }
 } // namespace
 
-__global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(SelfjoinArgs a)
+template <class Args>
+__global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(Args a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_lane = lane & 31, h = lane >> 5;
@@ -159,8 +235,8 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(SelfjoinAr
     uint2 *red = reinterpret_cast<uint2 *>(ldsA);            // [8 waves][32 rows], over the A operand once the sums are done
 
     const SjPair p = sj_pair(a, lens, starts);
-    const int64_t r0 = a.db_off[p.b];
-    const int n = (int)(a.db_off[p.b + 1] - r0);
+    int n;
+    const int64_t r0 = sj_clip(a, p.b, n);
     const int kt = p.kt, mo = a.min_overlap;
     if (n < mo || kt == 0) return; // no row of the group has a candidate in this clip
     const int d_lo = mo - kt, d_hi = n - mo;
@@ -202,7 +278,7 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(SelfjoinAr
             for (int e = 0; e < 2; ++e) {
                 ra[e] = 0;
                 if (j0 + ja[e] < ka[e]) {
-                    ra[e] = a.db[oa[e] + j0 + ja[e]];
+                    ra[e] = sj_hp(a, oa[e], j0 + ja[e]);
                     ok |= 1u << e;
                 }
             }
@@ -211,7 +287,7 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(SelfjoinAr
                 const int i = tid + kSjThreads * e, gi = d0 + j0 + i;
                 rb[e] = 0;
                 if (i < kSjWin && gi >= 0 && gi < n) {
-                    rb[e] = a.db[r0 + gi];
+                    rb[e] = sj_hp(a, r0, gi);
                     ok |= 4u << e;
                 }
             }
@@ -290,28 +366,30 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(SelfjoinAr
         }
     }
     if (tid < 32 && lens[tid] > 0)
-        best.store(a.tab + ((int64_t)(32 * p.gi + tid) * a.n_clips + p.b) * a.splits + p.split);
+        best.store(sj_entry(a, 32 * p.gi + tid, p.b, p.split));
 }
 
 // the same pairs, splits and chunks (the chunks of a pair begin at min_overlap - the group's longest row for every row): a
 // thread takes four lags of a chunk and walks their overlaps, one row after the other
-__global__ __launch_bounds__(256) void selfjoin_popc_kernel(SelfjoinArgs a)
+template <class Args>
+__global__ __launch_bounds__(256) void selfjoin_popc_kernel(Args a)
 {
     __shared__ uint2 red[4];
     __shared__ int lens[32];
     __shared__ int64_t starts[32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SjPair p = sj_pair(a, lens, starts);
-    const int64_t r0 = a.db_off[p.b];
-    const int n = (int)(a.db_off[p.b + 1] - r0), mo = a.min_overlap;
+    int n;
+    const int64_t r0 = sj_clip(a, p.b, n);
+    const int mo = a.min_overlap;
     if (n < mo || p.kt == 0) return;
-    const uint64_t *r = a.db + r0;
+    const uint64_t *r = sj_ptr(a, r0);
     const int d_lo = mo - p.kt, d_hi = n - mo;
     const int n_wg_chunks = (d_hi - d_lo) / kSelfjoinChunk + 1;
     for (int m = 0; m < 32; ++m) {
         const int k = lens[m];
         if (k == 0) continue;
-        const uint64_t *q = a.db + starts[m];
+        const uint64_t *q = sj_ptr(a, starts[m]);
         SjBest best; // (thread 0)
         for (int wc = p.split; wc < n_wg_chunks; wc += a.splits) {
             const int d0 = d_lo + wc * kSelfjoinChunk;
@@ -347,20 +425,21 @@ __global__ __launch_bounds__(256) void selfjoin_popc_kernel(SelfjoinArgs a)
                 if (b.x != kSjNoDist) best.offer(b.x, kSjLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
             }
         }
-        if (tid == 0) best.store(a.tab + ((int64_t)(32 * p.gi + m) * a.n_clips + p.b) * a.splits + p.split);
+        if (tid == 0) best.store(sj_entry(a, 32 * p.gi + m, p.b, p.split));
     }
 }
 
 // one workgroup per row a of the pass: the splits of every b > a folded into the pair's first entry, and the row's pairs
-// under the threshold counted
-__global__ __launch_bounds__(256) void selfjoin_count_kernel(uint4 *__restrict__ tab, int n_clips, int splits, int row0, unsigned rate_num,
-                                                             unsigned rate_den, int *__restrict__ row_count)
+// under the threshold counted.  Column c of the table is clip col0 + c (the self-join: col0 = 0, n_cols = n_clips; the join:
+// the externals)
+__global__ __launch_bounds__(256) void selfjoin_count_kernel(uint4 *__restrict__ tab, int n_cols, int col0, int splits, int row0,
+                                                             unsigned rate_num, unsigned rate_den, int *__restrict__ row_count)
 {
     __shared__ int red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint4 *row = tab + (int64_t)blockIdx.x * n_clips * splits;
+    uint4 *row = tab + (int64_t)blockIdx.x * n_cols * splits;
     int cnt = 0;
-    for (int c = row0 + (int)blockIdx.x + 1 + tid; c < n_clips; c += 256) {
+    for (int c = max(row0 + (int)blockIdx.x + 1 - col0, 0) + tid; c < n_cols; c += 256) {
         uint4 b = row[(int64_t)c * splits];
         for (int s = 1; s < splits; ++s) {
             const uint4 e = row[(int64_t)c * splits + s];
@@ -415,19 +494,19 @@ static_assert(sizeof(DupPairDev) == sizeof(hpfw_dup_pair), "the record of includ
 } // namespace
 
 // one workgroup per row a: its pairs under the threshold in rising b, from position row_first[a] on, while below cap
-__global__ __launch_bounds__(256) void selfjoin_write_kernel(const uint4 *__restrict__ tab, int n_clips, int splits, int row0, unsigned rate_num,
-                                                             unsigned rate_den, const int64_t *__restrict__ row_first, uint32_t clip_base,
-                                                             DupPairDev *__restrict__ out, int64_t cap)
+__global__ __launch_bounds__(256) void selfjoin_write_kernel(const uint4 *__restrict__ tab, int n_cols, int col0, int splits, int row0,
+                                                             unsigned rate_num, unsigned rate_den, const int64_t *__restrict__ row_first,
+                                                             uint32_t clip_base, DupPairDev *__restrict__ out, int64_t cap)
 {
     __shared__ int wave_n[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int a = row0 + (int)blockIdx.x;
-    const uint4 *row = tab + (int64_t)blockIdx.x * n_clips * splits;
+    const uint4 *row = tab + (int64_t)blockIdx.x * n_cols * splits;
     int64_t at = row_first[blockIdx.x];
-    for (int c0 = a + 1; c0 < n_clips && at < cap; c0 += 256) {
+    for (int c0 = max(a + 1 - col0, 0); c0 < n_cols && at < cap; c0 += 256) {
         const int c = c0 + tid;
         uint4 e = make_uint4(0xffffffffu, 0u, 0u, 0u);
-        if (c < n_clips) e = row[(int64_t)c * splits];
+        if (c < n_cols) e = row[(int64_t)c * splits];
         const bool rep = sj_reported(e, rate_num, rate_den);
         const unsigned long long mask = __ballot(rep);
         __syncthreads(); // (the block of 256 before has been read)
@@ -435,7 +514,7 @@ __global__ __launch_bounds__(256) void selfjoin_write_kernel(const uint4 *__rest
         __syncthreads();
         int64_t mine = at + __popcll(mask & ((1ull << lane) - 1ull));
         for (int w = 0; w < wave; ++w) mine += wave_n[w];
-        if (rep && mine < cap) out[mine] = {clip_base + (uint32_t)a, clip_base + (uint32_t)c, e.x, e.y, (int32_t)e.z, 0u};
+        if (rep && mine < cap) out[mine] = {clip_base + (uint32_t)a, clip_base + (uint32_t)(col0 + c), e.x, e.y, (int32_t)e.z, 0u};
         at += wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
     }
 }
@@ -458,33 +537,53 @@ static SelfjoinArgs selfjoin_args(const uint64_t *d_db, const int64_t *d_db_off,
     return a;
 }
 
-void launch_selfjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups,
-                          const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits, void *d_tab, hipStream_t s)
+// either scan under either arguments (the matrix-core kernel's LDS is raised once per device and instantiation)
+template <class Args>
+static void launch_scan(bool popc, const Args &a, uint32_t n_pairs, hipStream_t s)
 {
-    const SelfjoinArgs a = selfjoin_args(d_db, d_db_off, n_clips, g0, n_groups, d_pair_first, min_overlap, splits, d_tab);
-    const dim3 grid(n_pairs * (unsigned)splits);
+    const dim3 grid(n_pairs * (unsigned)a.splits);
     if (popc) {
-        hipLaunchKernelGGL(selfjoin_popc_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(selfjoin_popc_kernel<Args>, grid, dim3(256), 0, s, a);
         return;
     }
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(selfjoin_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(selfjoin_mfma_kernel<Args>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)selfjoin_mfma_lds_bytes());
         attr_set.mark();
     }
-    hipLaunchKernelGGL(selfjoin_mfma_kernel, grid, dim3(kSjThreads), selfjoin_mfma_lds_bytes(), s, a);
+    hipLaunchKernelGGL(selfjoin_mfma_kernel<Args>, grid, dim3(kSjThreads), selfjoin_mfma_lds_bytes(), s, a);
 }
 
-void launch_selfjoin_select(void *d_tab, int n_clips, int splits, int row0, int n_rows, uint32_t rate_num, uint32_t rate_den, int *d_row_count,
-                            int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s)
+void launch_selfjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups,
+                          const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits, void *d_tab, hipStream_t s)
 {
-    hipLaunchKernelGGL(selfjoin_count_kernel, dim3(n_rows), dim3(256), 0, s, reinterpret_cast<uint4 *>(d_tab), n_clips, splits, row0, rate_num,
-                       rate_den, d_row_count);
+    launch_scan(popc, selfjoin_args(d_db, d_db_off, n_clips, g0, n_groups, d_pair_first, min_overlap, splits, d_tab), n_pairs, s);
+}
+
+void launch_join_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_index, const uint64_t *d_x, const int64_t *d_x_off, int n_x,
+                      int among_new, int g0, int n_groups, const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits,
+                      void *d_tab, hipStream_t s)
+{
+    JoinArgs a = {};
+    static_cast<SelfjoinArgs &>(a) = selfjoin_args(d_db, d_db_off, n_index + n_x, g0, n_groups, d_pair_first, min_overlap, splits, d_tab);
+    a.x = d_x;
+    a.x_off = d_x_off;
+    a.n_index = n_index;
+    a.n_x = n_x;
+    a.row_end = among_new ? n_index + n_x : n_index;
+    launch_scan(popc, a, n_pairs, s);
+}
+
+void launch_selfjoin_select(void *d_tab, int n_cols, int col0, int splits, int row0, int n_rows, uint32_t rate_num, uint32_t rate_den,
+                            int *d_row_count, int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s)
+{
+    hipLaunchKernelGGL(selfjoin_count_kernel, dim3(n_rows), dim3(256), 0, s, reinterpret_cast<uint4 *>(d_tab), n_cols, col0, splits, row0,
+                       rate_num, rate_den, d_row_count);
     hipLaunchKernelGGL(selfjoin_offsets_kernel, dim3(1), dim3(1024), 0, s, d_row_count, n_rows, d_row_first, d_count);
     if (cap > 0)
-        hipLaunchKernelGGL(selfjoin_write_kernel, dim3(n_rows), dim3(256), 0, s, reinterpret_cast<const uint4 *>(d_tab), n_clips, splits, row0,
-                           rate_num, rate_den, d_row_first, clip_base, reinterpret_cast<DupPairDev *>(d_out), cap);
+        hipLaunchKernelGGL(selfjoin_write_kernel, dim3(n_rows), dim3(256), 0, s, reinterpret_cast<const uint4 *>(d_tab), n_cols, col0, splits,
+                           row0, rate_num, rate_den, d_row_first, clip_base, reinterpret_cast<DupPairDev *>(d_out), cap);
 }
 
 } // namespace hpfw

@@ -417,8 +417,22 @@ void launch_selfjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_o
 // folds the splits (in d_tab), counts the pairs of rows row0 .. row0 + n_rows - 1 with dist rate_den <= rate_num overlap into
 // d_row_count, their positions from *d_count on into d_row_first, writes those below cap to d_out (hpfw_dup_pair, rising
 // (a, b)) and adds the pass's pairs to *d_count
-void launch_selfjoin_select(void *d_tab, int n_clips, int splits, int row0, int n_rows, uint32_t rate_num, uint32_t rate_den, int *d_row_count,
-                            int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s);
+// (column c of d_tab [n_rows][n_cols][splits] is clip col0 + c: the self-join's col0 is 0 and its n_cols the index's clips)
+void launch_selfjoin_select(void *d_tab, int n_cols, int col0, int splits, int row0, int n_rows, uint32_t rate_num, uint32_t rate_den,
+                            int *d_row_count, int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s);
+// the index joined with n_x recordings that are not in it: launch_selfjoin_scan over the list "the
+// n_index slots of the index, then the externals d_x / d_x_off [n_x + 1]" with b an external only.  The pairs (group, b) of a
+// pass are numbered by d_pair_first as join_group_pairs counts them: pair i of group g is b = max(n_index, 32 g + 1) + i.  Rows
+// at or above n_index are masked unless among_new.  d_tab [32 n_groups][n_x][splits]: the columns are the externals
+// (launch_selfjoin_select with col0 = n_index).
+inline int64_t join_group_pairs(int64_t n_index, int64_t n_x, int among_new, int64_t g)
+{
+    if (32 * g >= (among_new ? n_index + n_x : n_index)) return 0; // (no row of the group is launched)
+    return std::max<int64_t>(n_index + n_x - std::max(n_index, 32 * g + 1), 0);
+}
+void launch_join_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_index, const uint64_t *d_x, const int64_t *d_x_off, int n_x,
+                      int among_new, int g0, int n_groups, const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits,
+                      void *d_tab, hipStream_t s);
 // per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
 // (dist, shift index), then the k best by (dist, clip)
 void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);

@@ -90,6 +90,24 @@ def duplicate_groups(pairs, names: Sequence[str]) -> List[List[str]]:
     return [groups[root] for root in sorted(groups)]
 
 
+def keep_new(pairs, n_index: int, n_new: int) -> List[bool]:
+    """which recordings of a batch add_new() keeps, from the join's pairs with among_new = 1: pairs of ids (a, b, ...) with
+    n_index <= b < n_index + n_new the batch's recordings in their order and a < b an indexed recording (a < n_index) or an
+    earlier one of the batch.  Recording i is kept unless some pair (a, n_index + i) has an a that is indexed or an earlier
+    kept recording of the batch: of a new song that comes twice the first is kept, and a recording that only duplicates a
+    dropped one is kept (what it duplicates is then not in the index).  A pure host function."""
+    partners = [[] for _ in range(n_new)]
+    for pair in pairs:
+        a, b = int(pair[0]), int(pair[1])
+        if not (0 <= a < b and n_index <= b < n_index + n_new):
+            raise ValueError(f"keep_new: ({a}, {b}) is no pair of the join of {n_new} recordings against {n_index}")
+        partners[b - n_index].append(a)
+    keep = []
+    for i in range(n_new):
+        keep.append(not any(a < n_index or keep[a - n_index] for a in partners[i]))
+    return keep
+
+
 class LiveSongIdentification:
     def __init__(self, cache: str = "", device: int = 0, resample: bool = False, devices: Optional[Sequence[int]] = None):
         """resample: index and search WAV files at any rate in [8 000, 192 000] Hz (ParallelCollector(resample=True));
@@ -153,7 +171,14 @@ class LiveSongIdentification:
         in force (nothing is re-learned), their stems behind self.names; returns the recordings added.  A file that yields no
         hashprint is left out.  An identifier made with devices= raises HPFW_E_UNSUPPORTED: a sharded index is rebuilt."""
         self._no_shards("adding to the index")
-        pairs = [(hp, name) for hp, name in self.collector.calc_hashprints(list(filenames)) if hp is not None and hp.size]
+        return self._append(self._new_hashprints(filenames))
+
+    def _new_hashprints(self, filenames):
+        """[(hashprints, name)] of the files that yield any, as add() takes them"""
+        return [(hp, name) for hp, name in self.collector.calc_hashprints(list(filenames)) if hp is not None and hp.size]
+
+    def _append(self, pairs) -> int:
+        """add()'s second half: (hashprints, name) pairs behind the index, with the bookkeeping of their slots"""
         if pairs:
             off = np.zeros(len(pairs) + 1, np.int64)
             np.cumsum([hp.size for hp, _ in pairs], out=off[1:])
@@ -181,6 +206,46 @@ class LiveSongIdentification:
     def duplicate_groups(self, pairs) -> List[List[str]]:
         """the connected components of duplicates()'s pairs as lists of names in index order (duplicate_groups())"""
         return duplicate_groups(pairs, self.live_names())
+
+    # ---- ingest check (DESIGN.md section 23): what of a batch of files the index already holds, before they are added
+    def _join(self, new, rate, min_overlap, among_new):
+        """DUP_PAIR_DTYPE records of the join of _new_hashprints()'s pairs against the index; rate: rate_fraction()'s"""
+        num, den = rate
+        if not new:
+            return np.zeros(0, _lib.DUP_PAIR_DTYPE)
+        off = np.zeros(len(new) + 1, np.int64)
+        np.cumsum([hp.size for hp, _ in new], out=off[1:])
+        return self._gpu.index_join(np.concatenate([hp for hp, _ in new]), off, int(min_overlap), num, den, int(bool(among_new)))
+
+    def _named(self, pairs, new):
+        names = self.names + [name for _, name in new]
+        return [(names[int(p["a"])], names[int(p["b"])], int(p["dist"]), int(p["overlap"]), int(p["lag"])) for p in pairs]
+
+    def known(self, filenames: Sequence[str], max_rate, min_overlap: int, among_new: bool = True):
+        """what duplicates() would report in addition after add(filenames), without the index changing: the pairs (a, b) with b
+        one of the files and a an indexed recording or, with among_new, an earlier file of the batch, by duplicates()'s rule,
+        threshold and order.  [(name_a, name_b, dist, overlap, lag)]; name_b is the name add() would give the file.  Files that
+        yield no hashprint are left out and take no id, as in add().  An identifier made with devices= raises
+        HPFW_E_UNSUPPORTED."""
+        rate = rate_fraction(max_rate)                    # (refused before any file is read)
+        self._no_shards("the ingest check")
+        new = self._new_hashprints(filenames)
+        return self._named(self._join(new, rate, min_overlap, among_new), new)
+
+    def add_new(self, filenames: Sequence[str], max_rate, min_overlap: int):
+        """add() of the files the index does not hold yet: the files are extracted once and joined against the index and each
+        other (known() with among_new), a file is kept unless a reported pair pairs it with an indexed recording or with an
+        earlier kept file of the batch (keep_new()), and the kept files are added from the hashprints already extracted.
+        Returns (the names added, known()'s pairs).  An identifier made with devices= raises HPFW_E_UNSUPPORTED."""
+        rate = rate_fraction(max_rate)
+        self._no_shards("the ingest check")
+        new = self._new_hashprints(filenames)
+        pairs = self._join(new, rate, min_overlap, True)
+        keep = keep_new([(int(p["a"]), int(p["b"])) for p in pairs], len(self.names), len(new))
+        named = self._named(pairs, new)                   # (before the index grows: ids of the batch as the join gave them)
+        kept = [pair for pair, k in zip(new, keep) if k]
+        self._append(kept)
+        return [name for _, name in kept], named
 
     def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None,
             tempos: Optional[Sequence[float]] = None):

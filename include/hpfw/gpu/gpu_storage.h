@@ -217,6 +217,38 @@ public:
         return out;
     }
 
+    /// the ingest check (hpfw_gpu_index_join): what duplicates() would report in addition after
+    /// add(hashprints), without the index changing -- the pairs whose b is one of the recordings given (named as add() would
+    /// name it) and whose a is an indexed recording or, with among_new, an earlier one of the range.  Accepts any range of
+    /// Collector::FilenameFingerprintPair; min_overlap and the threshold are the caller's.
+    template <typename Range>
+    auto join(Range &&hashprints, int min_overlap, int rate_num, int rate_den, bool among_new) const -> std::vector<DuplicateResult>
+    {
+        std::vector<std::string> names = names_;
+        std::vector<uint64_t> all;
+        std::vector<int64_t> off{0};
+        for (auto &p : hashprints) {
+            names.push_back(p.filename);
+            all.insert(all.end(), p.fingerprint.begin(), p.fingerprint.end());
+            off.push_back((int64_t)all.size());
+        }
+        const int64_t n_x = (int64_t)off.size() - 1;
+        std::vector<hpfw_dup_pair> pairs(256);
+        int64_t count = 0;
+        for (int round = 0; round < 2; ++round) { // (the buffer was too small: once more with room for all)
+            check(hpfw_gpu_index_join(h_, all.empty() ? &dummy_ : all.data(), off.data(), n_x, among_new ? 1 : 0, min_overlap, rate_num,
+                                      rate_den, pairs.data(), (int64_t)pairs.size(), &count));
+            if (count <= (int64_t)pairs.size()) break;
+            pairs.resize((size_t)count);
+        }
+        std::vector<DuplicateResult> out;
+        for (int64_t i = 0; i < count; ++i) {
+            const hpfw_dup_pair &p = pairs[(size_t)i];
+            out.push_back({names[p.a], names[p.b], (size_t)p.dist, (size_t)p.overlap, (int64_t)p.lag});
+        }
+        return out;
+    }
+
     /// the warped search (hpfw_gpu_search_dtw): the query may run faster or slower than the recording
     /// inside the window (local slope 1/2 .. 2).  candidates is the caller's (there is no default): 0 warps every clip of the
     /// index, k..64 re-ranks that many best clips of the plain search.  Query hashprint 0 lies on column start of the

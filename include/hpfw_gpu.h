@@ -576,6 +576,40 @@ int hpfw_gpu_index_selfjoin(hpfw_gpu *h, int min_overlap, int rate_num, int rate
  * pair's chunks begin at min_overlap - the longest of the 32 rows a that share the workgroup).  NULL is HPFW_E_INVALID. */
 int hpfw_gpu_selfjoin_geometry(int32_t *slice, int32_t *chunk);
 
+/* ---- ingest check: recordings that are not in the index joined against it, before they are added.
+ * The index has n slots.  The call brings m EXTERNAL recordings x_0 .. x_(m-1): their hashprints in device memory, x_i at
+ * d_x_hp[x_off[i] .. x_off[i + 1]), and the offsets x_off [m + 1] on the host.  x_i is given the id n + i, the id
+ * hpfw_gpu_index_add would give it.  The join reports every pair (a, b) with
+ *   n <= b < n + m,    a < b,    and which the self-join above would report of the index with the m recordings appended,
+ * with that pair's dist, overlap and lag under the same order of candidates (dist / L exact, then larger L, then smaller
+ * lag): a takes the query's part and b the clip's.  among_new = 0 reports only pairs with a < n (an indexed recording
+ * against an external one), among_new = 1 the pairs between two externals as well.  In other words: what index_add followed
+ * by index_selfjoin would add to the self-join's answer, byte for byte -- without the index changing.
+ * Pairs come in ascending (a, b) as hpfw_dup_pair; the clip base is added to both ids; empty slots, removed recordings and
+ * recordings below min_overlap (indexed or external) never appear; the index is not modified; no floating point takes part
+ * in the order, no atomics are used and nothing depends on the order in which workgroups run.  Work is about (n / 32) m
+ * workgroup pairs (among_new = 1: (n + m / 2) / 32 m), not the self-join's n^2 / 64.
+ * cap, *d_count and the call's ordering are the self-join's: d_out receives the first cap pairs, *d_count their total,
+ * which may exceed cap.  n_x = 0 gives count 0; an empty index with among_new = 1 gives the pairs among the batch.
+ * Refused before a device is touched (HPFW_E_INVALID): everything the self-join refuses, a null x_off, n_x < 0, decreasing
+ * offsets, null hashprints when the offsets name any, among_new outside 0..1.  Refused before a kernel runs
+ * (HPFW_E_UNSUPPORTED): an external or an indexed recording above 2^18 - 1 hashprints, n + m above 2 097 152.
+ * HPFW_SELFJOIN_POPC, HPFW_SELFJOIN_SPLITS and HPFW_SELFJOIN_TABLE_KB act as on the self-join; the table of a pass is
+ * [rows of the pass][m][splits]. */
+int hpfw_gpu_index_join_device(hpfw_gpu *h, const uint64_t *d_x_hp, const int64_t *x_off, int64_t n_x, int among_new,
+                               int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *d_out, int64_t cap,
+                               int64_t *d_count, void *stream);
+/* host buffers (the null stream): x_hp, out [cap], *count */
+int hpfw_gpu_index_join(hpfw_gpu *h, const uint64_t *x_hp, const int64_t *x_off, int64_t n_x, int among_new,
+                        int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *out, int64_t cap, int64_t *count);
+/* host-only: how a pass of the join over the row groups group0 .. group0 + n_groups - 1 numbers its work.  Row group g holds
+ * the ids 32 g .. 32 g + 31 of the list "the n_clips slots of the index, then the n_x externals"; its items are the externals
+ * b >= max(n_clips, 32 g + 1), one workgroup pair (group, b) each, and none when no row of the group is launched (among_new =
+ * 0: groups at or above ceil(n_clips / 32)).  pair_first [n_groups + 1]: item pair_first[i] + j is (group0 + i,
+ * b = max(n_clips, 32 (group0 + i) + 1) + j).  Negative counts, among_new outside 0..1 and NULL are HPFW_E_INVALID;
+ * n_clips + n_x above 2 097 152 is HPFW_E_UNSUPPORTED. */
+int hpfw_gpu_join_plan(int64_t n_clips, int64_t n_x, int among_new, int64_t group0, int64_t n_groups, uint32_t *pair_first);
+
 /* ---- warped search: subsequence DTW over hashprints.  Every other search lines a query up with a
  * clip rigidly (query position j on clip position offset + j); this one lets the query run faster or slower than the clip
  * inside the window, and tells which clip column every query hashprint lies on.  Exact integers throughout.
