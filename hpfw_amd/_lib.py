@@ -108,6 +108,8 @@ EXPORTS = (
     "hpfw_gpu_index_remove_geometry",
     "hpfw_gpu_index_selfjoin_device", "hpfw_gpu_index_selfjoin", "hpfw_gpu_selfjoin_geometry",
     "hpfw_gpu_index_join_device", "hpfw_gpu_index_join", "hpfw_gpu_join_plan",
+    "hpfw_gpu_search_topk_within_device", "hpfw_gpu_search_topk_within",
+    "hpfw_gpu_search_topk_transposed_within_device", "hpfw_gpu_search_topk_transposed_within",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
     "par_collector_calc_hashprint", "par_collector_calc_hashprints", "par_collector_save", "par_collector_load",
     "prepare_result_free", "calc_hashprint_result_free",
@@ -326,6 +328,10 @@ def lib():
     L.hpfw_gpu_search_topk_scored.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.hpfw_gpu_search_topk_transposed_scored_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
     L.hpfw_gpu_search_topk_transposed_scored.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    L.hpfw_gpu_search_topk_within_device.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]
+    L.hpfw_gpu_search_topk_within.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp]
+    L.hpfw_gpu_search_topk_transposed_within_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp]
+    L.hpfw_gpu_search_topk_transposed_within.argtypes = [vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
     L.hpfw_gpu_hit_score.argtypes = [u32, i32, ctypes.POINTER(DistStats), ctypes.POINTER(ctypes.c_double)]
     L.hpfw_gpu_window_count.argtypes = [i64, i64, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_extract_windows_pcm16.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp, i32, vp, vp]
@@ -551,6 +557,20 @@ def _shift_arg(shifts):
 def _hp(a):
     """host pointer of a contiguous numpy array"""
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _within_sets(set_off, set_clips, q_set, n_q):
+    """the set arguments of the searches within sets as the C ABI takes them: int64 offsets, int32 clips, int32 [n_q] sets"""
+    so = np.ascontiguousarray(set_off, np.int64).ravel()
+    sc = np.ascontiguousarray(set_clips, np.int32).ravel()
+    qs = np.ascontiguousarray(q_set, np.int32).ravel()
+    if so.size < 1:
+        raise ValueError("set_off must hold n_sets + 1 offsets")
+    if qs.size != n_q:
+        raise ValueError(f"q_set must hold one entry per query ({n_q}), got {qs.size}")
+    if sc.size < so[-1]:
+        raise ValueError("set_clips is shorter than set_off[n_sets]")
+    return so, sc, qs
 
 
 class Gpu:
@@ -1273,6 +1293,50 @@ class Gpu:
         off = np.ascontiguousarray(q_off, np.int64)
         check(lib().hpfw_gpu_search_topk_transposed_scored_device(self._h, d_q, _hp(off), (off.size - 1) // n_shifts, int(n_shifts),
                                                                    int(k), d_out, d_stats, stream))
+
+    # ---- search within sets of clips: every query names the set it may be answered with
+    def search_topk_within(self, q_hp, q_off, k, set_off, set_clips, q_set, scored=False):
+        """search_topk with query q restricted to the clips of set q_set[q] (-1: the whole index): the sets in CSR form,
+        set_off [n_sets + 1] and set_clips (clip indexes in add order, strictly ascending inside a set).  The answer is the one
+        an index of just those clips gives, with this index's clip ids.  HIT_DTYPE [n_q][k]; scored: (hits, STATS_DTYPE [n_q]),
+        the moments over the set's counted clips."""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        so, sc, qs = _within_sets(set_off, set_clips, q_set, off.size - 1)
+        out = np.zeros((off.size - 1, k), HIT_DTYPE)
+        stats = np.zeros(off.size - 1, STATS_DTYPE) if scored else None
+        check(lib().hpfw_gpu_search_topk_within(self._h, _hp(q), _hp(off), off.size - 1, int(k), _hp(so), so.size - 1, _hp(sc), _hp(qs),
+                                                _hp(out), _hp(stats) if scored else None))
+        return (out, stats) if scored else out
+
+    def search_topk_within_dev(self, d_q, q_off, k, set_off, set_clips, q_set, d_out, d_stats=None, stream=0):
+        """the same with the queries, d_out and d_stats (None: no moments) on the device; the sets stay on the host"""
+        off = np.ascontiguousarray(q_off, np.int64)
+        so, sc, qs = _within_sets(set_off, set_clips, q_set, off.size - 1)
+        check(lib().hpfw_gpu_search_topk_within_device(self._h, d_q, _hp(off), off.size - 1, int(k), _hp(so), so.size - 1, _hp(sc), _hp(qs),
+                                                       d_out, d_stats, stream))
+
+    def search_topk_transposed_within(self, q_hp, q_off, n_shifts, k, set_off, set_clips, q_set, scored=False):
+        """search_topk_transposed within sets: q_set has one entry per query (for all its n_shifts variants).
+        SHIFT_HIT_DTYPE [n_q][k]; scored: (hits, STATS_DTYPE [n_q][n_shifts])"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        if (off.size - 1) % n_shifts:
+            raise ValueError("q_off must hold n_q * n_shifts + 1 offsets")
+        n_q = (off.size - 1) // n_shifts
+        so, sc, qs = _within_sets(set_off, set_clips, q_set, n_q)
+        out = np.zeros((n_q, k), SHIFT_HIT_DTYPE)
+        stats = np.zeros((n_q, n_shifts), STATS_DTYPE) if scored else None
+        check(lib().hpfw_gpu_search_topk_transposed_within(self._h, _hp(q), _hp(off), n_q, int(n_shifts), int(k), _hp(so), so.size - 1,
+                                                           _hp(sc), _hp(qs), _hp(out), _hp(stats) if scored else None))
+        return (out, stats) if scored else out
+
+    def search_topk_transposed_within_dev(self, d_q, q_off, n_shifts, k, set_off, set_clips, q_set, d_out, d_stats=None, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        n_q = (off.size - 1) // n_shifts
+        so, sc, qs = _within_sets(set_off, set_clips, q_set, n_q)
+        check(lib().hpfw_gpu_search_topk_transposed_within_device(self._h, d_q, _hp(off), n_q, int(n_shifts), int(k), _hp(so), so.size - 1,
+                                                                  _hp(sc), _hp(qs), d_out, d_stats, stream))
 
     # ---- a sharded search's gathered results (k_merge.hip): device twins of merge_topk and of the sum of the moments
     def merge_topk_dev(self, d_in, n_shards, n_q, k, d_out, stream=0):

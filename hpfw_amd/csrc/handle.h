@@ -144,6 +144,9 @@ struct hpfw_gpu {
         DevBuf d_topk_scratch;
         DevBuf d_shift_hits; // the per-shift top-k lists of a transposed search
         DevBuf d_ov_tab, d_ov_exclude; // overlap search: the (query, clip, split) entries, the clips to skip
+        // search within sets: the sets' slots and the regrouping tables of a call; its queries in the
+        // order of their sets; their hits and moments in that order
+        DevBuf d_within_tab, d_within_q, d_within_out;
         // self-join (selfjoin.hip): the (row, clip, split) entries of a pass, its rows' counts and first
         // positions, the passes' numbering of their (row group, clip) pairs
         DevBuf d_sj_tab, d_sj_rows, d_sj_pairs;

@@ -30,7 +30,8 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
 
 // kHsQt = queries per workgroup (8, or fewer when there are fewer queries: a single streaming query
 // would otherwise pay for seven empty slots)
-template <int kHsQt>
+// SET: the launch's clips are the slots a.set names (kernels.h clip_span)
+template <int kHsQt, bool SET>
 __global__ __launch_bounds__(kHsThreads) void hamming_scan_kernel(SearchArgs a)
 {
     uint64_t *r_lds = reinterpret_cast<uint64_t *>(smem_raw);                  // [256 + k_max]
@@ -38,8 +39,8 @@ __global__ __launch_bounds__(kHsThreads) void hamming_scan_kernel(SearchArgs a)
     const int tid = threadIdx.x;
     const int clip = blockIdx.x;
     const int q0 = blockIdx.y * kHsQt;
-    const int64_t r0 = a.db_off[clip];
-    const int n = (int)(a.db_off[clip + 1] - r0);
+    int n;
+    const int64_t r0 = clip_span<SET>(a.db_off, a.set, clip, n);
     if (n <= 0) return;
 
     int kq[kHsQt];
@@ -129,8 +130,11 @@ struct HitDev {
 };
 
 // one workgroup per query: k rounds of "smallest (dist, clip) key above the previous one"
+// SET: column c of the table is slot set[c]; the set ascends strictly, so the order by (dist, column) is the order by
+// (dist, slot), and the hit names the slot
+template <bool SET>
 __global__ __launch_bounds__(256) void topk_kernel(const uint64_t *__restrict__ best, int n_clips, int k,
-                                                   uint32_t clip_base, HitDev *__restrict__ out)
+                                                   uint32_t clip_base, const int32_t *__restrict__ set, HitDev *__restrict__ out)
 {
     __shared__ uint64_t red[4];
     const int tid = threadIdx.x;
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const uint64_t *__restrict__ 
             } else {
                 const uint32_t c = (uint32_t)sel;
                 h.dist = (uint32_t)(sel >> 32);
-                h.clip = clip_base + c;
+                h.clip = clip_base + (SET ? (uint32_t)set[c] : c);
                 h.offset = (int32_t)(uint32_t)row[c];
             }
             h.pad = 0;
@@ -215,9 +219,10 @@ __global__ __launch_bounds__(256) void topk_slice_kernel(const uint64_t *__restr
     }
 }
 
+template <bool SET>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t *__restrict__ cand_key,
                                                          const int32_t *__restrict__ cand_off, int k, uint32_t clip_base,
-                                                         HitDev *__restrict__ out)
+                                                         const int32_t *__restrict__ set, HitDev *__restrict__ out)
 {
     __shared__ uint64_t red[4];
     __shared__ int red_i[4];
@@ -267,7 +272,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t *__restr
                 h.offset = 0;
             } else {
                 h.dist = (uint32_t)(sel >> 32);
-                h.clip = clip_base + (uint32_t)sel;
+                h.clip = clip_base + (SET ? (uint32_t)set[(uint32_t)sel] : (uint32_t)sel);
                 h.offset = cand_off[(int64_t)q * n + si];
             }
             h.pad = 0;
@@ -350,27 +355,40 @@ void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, vo
 size_t topk_scratch_bytes(int n_q, int k) { return (size_t)n_q * kTkSlices * k * (sizeof(uint64_t) + sizeof(int32_t)); }
 
 void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_scratch,
-                          void *d_out, hipStream_t s)
+                          void *d_out, hipStream_t s, const int32_t *d_set)
 {
     uint64_t *keys = reinterpret_cast<uint64_t *>(d_scratch);
     int32_t *offs = reinterpret_cast<int32_t *>(keys + (size_t)n_q * kTkSlices * k);
     hipLaunchKernelGGL(topk_slice_kernel, dim3(kTkSlices, n_q), dim3(256), 0, s, d_best, n_clips, k, keys, offs);
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(n_q), dim3(256), 0, s, keys, offs, k, clip_base,
-                       reinterpret_cast<HitDev *>(d_out));
+    if (d_set)
+        hipLaunchKernelGGL(topk_merge_kernel<true>, dim3(n_q), dim3(256), 0, s, keys, offs, k, clip_base, d_set,
+                           reinterpret_cast<HitDev *>(d_out));
+    else
+        hipLaunchKernelGGL(topk_merge_kernel<false>, dim3(n_q), dim3(256), 0, s, keys, offs, k, clip_base, d_set,
+                           reinterpret_cast<HitDev *>(d_out));
 }
 
-template <int QT>
-static void launch_hamming_scan_t(const SearchArgs &a, hipStream_t s)
+template <int QT, bool SET>
+static void launch_hamming_scan_ts(const SearchArgs &a, hipStream_t s)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_scan_kernel<QT>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_scan_kernel<QT, SET>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set.mark();
     }
     const size_t lds = ((size_t)kHsThreads + a.k_max + 4 * QT) * sizeof(uint64_t);
     dim3 grid(a.n_clips, (a.n_q + QT - 1) / QT);
-    hipLaunchKernelGGL(hamming_scan_kernel<QT>, grid, dim3(kHsThreads), lds, s, a);
+    hipLaunchKernelGGL((hamming_scan_kernel<QT, SET>), grid, dim3(kHsThreads), lds, s, a);
+}
+
+template <int QT>
+static void launch_hamming_scan_t(const SearchArgs &a, hipStream_t s)
+{
+    if (a.set)
+        launch_hamming_scan_ts<QT, true>(a, s);
+    else
+        launch_hamming_scan_ts<QT, false>(a, s);
 }
 
 void launch_hamming_scan(const SearchArgs &a, hipStream_t s)
@@ -386,10 +404,14 @@ void launch_hamming_scan(const SearchArgs &a, hipStream_t s)
 }
 
 void launch_topk(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_out,
-                 hipStream_t s)
+                 hipStream_t s, const int32_t *d_set)
 {
-    hipLaunchKernelGGL(topk_kernel, dim3(n_q), dim3(256), 0, s, d_best, n_clips, k, clip_base,
-                       reinterpret_cast<HitDev *>(d_out));
+    if (d_set)
+        hipLaunchKernelGGL(topk_kernel<true>, dim3(n_q), dim3(256), 0, s, d_best, n_clips, k, clip_base, d_set,
+                           reinterpret_cast<HitDev *>(d_out));
+    else
+        hipLaunchKernelGGL(topk_kernel<false>, dim3(n_q), dim3(256), 0, s, d_best, n_clips, k, clip_base, d_set,
+                           reinterpret_cast<HitDev *>(d_out));
 }
 
 } // namespace hpfw

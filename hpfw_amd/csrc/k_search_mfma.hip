@@ -105,16 +105,17 @@ struct SearchMfmaArgs {
     // nn smallest (distance, global position) keys of each row are kept in slots [n_q][8]
     int win, nn;
     unsigned long long *slots;
+    const int32_t *set;   // SET: [n_clips] slots of the index (kernels.h clip_span), column p of best is slot set[p]
 };
 
-template <bool KNN>
+template <bool KNN, bool SET>
 __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_lane = lane & 31, h = lane >> 5;
     const int clip = blockIdx.x / a.chunks, g = blockIdx.y;
-    const int64_t r0 = a.db_off[clip];
-    const int n = (int)(a.db_off[clip + 1] - r0);
+    int n;
+    const int64_t r0 = clip_span<SET>(a.db_off, a.set, clip, n);
     const int kt = KNN ? a.win : a.gk[2 * g];
     if (n <= 0 || kt <= 0) return;
     const int o0 = (blockIdx.x - clip * a.chunks) * kSmWgOffs;
@@ -295,6 +296,7 @@ struct SearchShiftArgs {
     uint64_t *best;    // [n_clips], initialised to ~0
     int chunks;        // workgroups (of 1024 MT NT offsets) per clip
     int ws;            // row stride of the transposed window (odd)
+    const int32_t *set; // SET: [n_clips] slots of the index (kernels.h clip_span), entry p of best is slot set[p]
 };
 
 // 32 bits -> 32 E2M1 nibbles (0 -> +1.0 = 0x2, 1 -> -1.0 = 0xA) by byte permutes: a selector byte holds one 2-bit field
@@ -353,15 +355,15 @@ __device__ __forceinline__ v4i shift_rows_feed(const v4i &a, v4i &f)
 
 // WAVES waves split the steps; KST steps of column operands are in flight behind the matrix instructions of the KST
 // before them.  (registers: two workgroups of eight waves on a CU are four waves per SIMD, 128 registers each)
-template <int MT, int NT, int WAVES, int KST>
+template <int MT, int NT, int WAVES, int KST, bool SET>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) void hamming_shift_kernel(SearchShiftArgs a)
 {
     constexpr int kThr = 64 * WAVES, S = 32 * MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m_lane = lane & 31, h = lane >> 5;
     const int clip = blockIdx.x / a.chunks;
-    const int64_t r0 = a.db_off[clip];
-    const int n = (int)(a.db_off[clip + 1] - r0);
+    int n;
+    const int64_t r0 = clip_span<SET>(a.db_off, a.set, clip, n);
     if (n <= 0 || a.k <= 0) return;
     const int keff = a.k < n ? a.k : n; // storage.h:37-39
     const int t0 = (blockIdx.x - clip * a.chunks) * 1024 * MT * NT;
@@ -533,18 +535,21 @@ size_t hamming_shift_image_bytes(int k) { return (size_t)2 * (k + 4 * 32) * 16; 
 
 // one query of k hashprints at d_q against the whole index: best[clip] (preset to ~0) gets (dist << 32) | offset.
 // d_qexp: hamming_shift_image_bytes(k) of scratch for the query's expanded image.
-void launch_hamming_shift(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int n_off_max, const uint64_t *d_q,
-                          int k, void *d_qexp, uint64_t *d_best, hipStream_t s)
+// d_set: NULL, or the n_clips slots of the index the launch is about (entry p of d_best is slot d_set[p])
+template <bool SET>
+static void launch_hamming_shift_t(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int n_off_max, const uint64_t *d_q,
+                                   int k, void *d_qexp, uint64_t *d_best, const int32_t *d_set, hipStream_t s)
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_shift_kernel<1, 1, 4, 4>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_shift_kernel<1, 1, 4, 4, SET>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_shift_kernel<1, 2, 8, 2>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_shift_kernel<1, 2, 8, 2, SET>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set.mark();
     }
     SearchShiftArgs a;
+    a.set = d_set;
     a.db = d_db;
     a.db_off = d_db_off;
     a.n_clips = n_clips;
@@ -563,9 +568,18 @@ void launch_hamming_shift(const uint64_t *d_db, const int64_t *d_db_off, int n_c
     a.ws = shift_ws(k, 1, nt);
     const dim3 grid((unsigned)a.chunks * (unsigned)n_clips);
     if (two)
-        hipLaunchKernelGGL((hamming_shift_kernel<1, 2, 8, 2>), grid, dim3(512), shift_lds_bytes(k, 1, 2, 8), s, a);
+        hipLaunchKernelGGL((hamming_shift_kernel<1, 2, 8, 2, SET>), grid, dim3(512), shift_lds_bytes(k, 1, 2, 8), s, a);
     else
-        hipLaunchKernelGGL((hamming_shift_kernel<1, 1, 4, 4>), grid, dim3(256), shift_lds_bytes(k, 1, 1, 4), s, a);
+        hipLaunchKernelGGL((hamming_shift_kernel<1, 1, 4, 4, SET>), grid, dim3(256), shift_lds_bytes(k, 1, 1, 4), s, a);
+}
+
+void launch_hamming_shift(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int n_off_max, const uint64_t *d_q,
+                          int k, void *d_qexp, uint64_t *d_best, hipStream_t s, const int32_t *d_set)
+{
+    if (d_set)
+        launch_hamming_shift_t<true>(d_db, d_db_off, n_clips, n_off_max, d_q, k, d_qexp, d_best, d_set, s);
+    else
+        launch_hamming_shift_t<false>(d_db, d_db_off, n_clips, n_off_max, d_q, k, d_qexp, d_best, d_set, s);
 }
 
 size_t hamming_mfma_lds_bytes(int kt)
@@ -587,10 +601,10 @@ static void mfma_scan_attrs()
 {
     static PerDeviceOnce attr_set;
     if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_mfma_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_mfma_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (const void *f : {reinterpret_cast<const void *>(hamming_mfma_kernel<false, false>),
+                              reinterpret_cast<const void *>(hamming_mfma_kernel<false, true>),
+                              reinterpret_cast<const void *>(hamming_mfma_kernel<true, false>)})
+            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set.mark();
     }
 }
@@ -620,7 +634,7 @@ void launch_knn_windows(const uint64_t *d_db, const int64_t *d_db_off, int n_cli
     m.slots = reinterpret_cast<unsigned long long *>(d_slots);
     m.chunks = (n_off_max + kSmWgOffs - 1) / kSmWgOffs;
     dim3 grid((unsigned)m.chunks * (unsigned)n_clips, (n_win + 31) / 32);
-    hipLaunchKernelGGL(hamming_mfma_kernel<true>, grid, dim3(kSmThreads), hamming_mfma_lds_bytes(win), s, m);
+    hipLaunchKernelGGL((hamming_mfma_kernel<true, false>), grid, dim3(kSmThreads), hamming_mfma_lds_bytes(win), s, m);
 }
 
 void launch_hamming_mfma(const SearchArgs &a, const void *d_qa, int kt_pad, const int *d_gk, int n_max, hipStream_t s)
@@ -636,10 +650,14 @@ void launch_hamming_mfma(const SearchArgs &a, const void *d_qa, int kt_pad, cons
     m.kt_pad = kt_pad;
     m.gk = d_gk;
     m.best = a.best;
+    m.set = a.set;
     const int n_groups = (a.n_q + 31) / 32;
     m.chunks = (n_max + kSmWgOffs - 1) / kSmWgOffs;
     dim3 grid((unsigned)m.chunks * (unsigned)a.n_clips, n_groups);
-    hipLaunchKernelGGL(hamming_mfma_kernel<false>, grid, dim3(kSmThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
+    if (a.set)
+        hipLaunchKernelGGL((hamming_mfma_kernel<false, true>), grid, dim3(kSmThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
+    else
+        hipLaunchKernelGGL((hamming_mfma_kernel<false, false>), grid, dim3(kSmThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
 }
 
 } // namespace hpfw

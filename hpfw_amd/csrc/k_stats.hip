@@ -30,9 +30,11 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
+// SET: column c of the table is slot set[c] of db_off (search within a set)
+template <bool SET>
 __global__ __launch_bounds__(kStThreads) void dist_stats_kernel(const uint64_t *__restrict__ best, const int64_t *__restrict__ db_off,
                                                                 const int64_t *__restrict__ q_off, int n_clips, int per,
-                                                                DistStatsDev *__restrict__ stats)
+                                                                const int32_t *__restrict__ set, DistStatsDev *__restrict__ stats)
 {
     __shared__ unsigned long long red[3][kStThreads / 64];
     const int tid = threadIdx.x, q = blockIdx.x;
@@ -42,7 +44,9 @@ __global__ __launch_bounds__(kStThreads) void dist_stats_kernel(const uint64_t *
     const uint64_t *row = best + (int64_t)q * n_clips;
     unsigned long long n = 0, sum = 0, sum_sq = 0;
     for (int c = c0 + tid; c < c1; c += kStThreads) {
-        if (db_off[c + 1] - db_off[c] < kq) continue;
+        int len;
+        (void)clip_span<SET>(db_off, set, c, len);
+        if (len < kq) continue;
         const unsigned long long d = row[c] >> 32;
         n += 1;
         sum += d;
@@ -126,13 +130,17 @@ void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, c
 }
 
 void launch_dist_stats(const uint64_t *d_best, const int64_t *d_db_off, const int64_t *d_q_off, int n_q, int n_clips, void *d_stats,
-                       hipStream_t s)
+                       hipStream_t s, const int32_t *d_set)
 {
     // a slice of at least 4096 clips per workgroup (16 loads per lane); at most 64 slices, as the two-step top-k cuts a row
     const int slices = std::max(1, std::min(64, n_clips / 4096));
     const int per = (n_clips + slices - 1) / slices;
-    hipLaunchKernelGGL(dist_stats_kernel, dim3(n_q, slices), dim3(kStThreads), 0, s, d_best, d_db_off, d_q_off, n_clips, per,
-                       static_cast<DistStatsDev *>(d_stats));
+    if (d_set)
+        hipLaunchKernelGGL(dist_stats_kernel<true>, dim3(n_q, slices), dim3(kStThreads), 0, s, d_best, d_db_off, d_q_off, n_clips, per,
+                           d_set, static_cast<DistStatsDev *>(d_stats));
+    else
+        hipLaunchKernelGGL(dist_stats_kernel<false>, dim3(n_q, slices), dim3(kStThreads), 0, s, d_best, d_db_off, d_q_off, n_clips, per,
+                           d_set, static_cast<DistStatsDev *>(d_stats));
 }
 
 } // namespace hpfw

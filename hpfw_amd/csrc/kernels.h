@@ -358,7 +358,19 @@ struct SearchArgs {
     int n_q;
     int k_max;               // longest query
     uint64_t *best;          // [n_q][n_clips]: (dist << 32) | offset
+    // search within a set: NULL, or [n_clips] slots of the index, strictly ascending: "clip" p of
+    // the launch is slot set[p] of db_off, and column p of best.  The launches below pick the kernels' SET instantiation.
+    const int32_t *set = nullptr;
 };
+// first hashprint and length n of position p of a launch's clips: slot p of the index, or slot set[p] (SET)
+template <bool SET>
+__device__ __forceinline__ int64_t clip_span(const int64_t *__restrict__ db_off, const int32_t *__restrict__ set, int p, int &n)
+{
+    const int slot = SET ? set[p] : p;
+    const int64_t r0 = db_off[slot];
+    n = (int)(db_off[slot + 1] - r0);
+    return r0;
+}
 void launch_hamming_scan(const SearchArgs &a, hipStream_t s);
 // the same scan on the matrix cores (k_search_mfma.hip): queries expanded to fp4 +-1 first
 int hamming_mfma_kt_pad(int k_max);            // rows of the expanded-query image per group of 32
@@ -368,7 +380,7 @@ void launch_expand_queries(const uint64_t *d_q, const int64_t *d_q_off, int n_q,
 size_t hamming_shift_lds_bytes(int k);
 size_t hamming_shift_image_bytes(int k);       // scratch for the query's expanded image (d_qexp)
 void launch_hamming_shift(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int n_off_max, const uint64_t *d_q,
-                          int k, void *d_qexp, uint64_t *d_best, hipStream_t s);
+                          int k, void *d_qexp, uint64_t *d_best, hipStream_t s, const int32_t *d_set = nullptr);
 // nearest windows (AnnStorage semantics with exact neighbours): rows = windows of `win` hashprints
 void launch_expand_windows(const uint64_t *d_q, const int64_t *d_w_start, int n_win, int win, int kt_pad, void *d_qa,
                            hipStream_t s);
@@ -377,12 +389,13 @@ void launch_knn_windows(const uint64_t *d_db, const int64_t *d_db_off, int n_cli
                         hipStream_t s);
 // d_gk: per group of 32 queries {longest, shortest non-empty}; n_off_max: most offsets any (query, clip) has
 void launch_hamming_mfma(const SearchArgs &a, const void *d_qa, int kt_pad, const int *d_gk, int n_off_max, hipStream_t s);
+// d_set (here and in the launches below): NULL, or what SearchArgs::set is -- column c of the table is slot d_set[c]
 void launch_topk(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_out,
-                 hipStream_t s);
+                 hipStream_t s, const int32_t *d_set = nullptr);
 // the same result in two steps (64 slices of the clips per query, then a merge): large indexes, few queries
 size_t topk_scratch_bytes(int n_q, int k);
 void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, uint32_t clip_base, void *d_scratch,
-                          void *d_out, hipStream_t s);
+                          void *d_out, hipStream_t s, const int32_t *d_set = nullptr);
 // overlap search (k_search_overlap.hip): lags min_overlap - k .. n - min_overlap of every (query, clip),
 // rated by dist / overlap.  d_tab [n_q][n_clips][splits] of 16-byte entries {dist, overlap, lag, 0}, every byte preset to
 // 0xff; a clip's chunks of kOverlapChunk lags are dealt round robin to its `splits` workgroups.
@@ -439,7 +452,12 @@ void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, vo
 // scored search (k_stats.hip): d_stats [n_q] (hpfw_dist_stats, zeroed by the caller) += per query row the
 // moments n, sum d, sum d^2 of d = best >> 32 over the clips with db_off[c + 1] - db_off[c] >= q_off[q + 1] - q_off[q] >= 1
 void launch_dist_stats(const uint64_t *d_best, const int64_t *d_db_off, const int64_t *d_q_off, int n_q, int n_clips, void *d_stats,
-                       hipStream_t s);
+                       hipStream_t s, const int32_t *d_set = nullptr);
+// search within sets (k_within.hip): the queries regrouped by set and the results put back.
+// d_dst[dst_off[i] ..) = d_src[src_off[i] .. src_off[i] + dst_off[i + 1] - dst_off[i]) for i < n (offsets on the device)
+void launch_within_gather(const uint64_t *d_src, const int64_t *d_src_off, const int64_t *d_dst_off, int64_t n, uint64_t *d_dst, hipStream_t s);
+// rows of `words` 8-byte words: d_out[perm[r]] = d_in[r], r < n (perm on the device, a permutation of 0 .. n - 1)
+void launch_within_scatter(const uint64_t *d_in, const int64_t *d_perm, int64_t n, int words, uint64_t *d_out, hipStream_t s);
 // a sharded search's gathered results (k_merge.hip): per-shard top-k lists in [n_shards][n_q][k] of 16-byte
 // records keyed (dist, clip) (hpfw_hit or hpfw_shift_hit) -> out [n_q][k], as hpfw_gpu_merge_topk orders them; n_shards k <= 4096
 void launch_topk_merge_shards(const void *d_in, int n_shards, int64_t n_q, int k, void *d_out, hipStream_t s);

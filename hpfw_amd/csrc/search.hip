@@ -1,5 +1,5 @@
-// search.hip -- the index of hashprints, its top-k, transposed and overlap searches, and the merges of the shards' hits and
-// moments.  (The voting search is votes.hip, AudioCombiner's calls are combiner.hip.)
+// search.hip -- the index of hashprints, its top-k, transposed and overlap searches, the top-k searches within sets of
+// clips, and the merges of the shards' hits and moments.  (The voting search is votes.hip, AudioCombiner's calls are combiner.hip.)
 #include "handle.h"
 
 extern "C" {
@@ -208,117 +208,131 @@ int hpfw_gpu_index_remove_geometry(int64_t *tile, int64_t *chunk)
     return 0;
 }
 
-// the top-k search of n_q queries; d_stats: NULL, or [n_q] rows that receive the moments of the per-clip best distances
-// (k_stats.hip: one more reader of the table the scan wrote)
+// the clips a search is about: every slot of the index (d_set NULL), or the slots of one set --
+// n_clips of them, the longest of n_max hashprints, d_set [n_clips] on the device
+struct ClipView {
+    int64_t n_clips, n_max;
+    const int32_t *d_set;
+};
+
+static ClipView whole_index(const hpfw_gpu *h) { return {(int64_t)h->index.db_off.size() - 1, index_longest_clip(h), nullptr}; }
+
+// the top-k search of n_q queries over the clips of v (inside an ordered_call); d_stats: NULL, or [n_q] rows that receive
+// the moments of the per-clip best distances (k_stats.hip: one more reader of the table the scan wrote)
+static int search_topk_view(hpfw_gpu *h, const ClipView &v, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
+                            hpfw_hit *d_out, hpfw_dist_stats *d_stats, hipStream_t s)
+{
+    if (n_q == 0) return 0;
+    if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
+    const int64_t n_clips = v.n_clips;
+    int rc;
+    if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_q * sizeof(hpfw_dist_stats), s));
+    if (n_clips == 0) { // nothing indexed: every slot is "none"
+        hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->index.clip_base, d_out, s);
+        return check_launch("topk");
+    }
+    if ((rc = upload_db_off(h, s))) return rc;
+    int64_t k_max = 0;
+    for (int64_t i = 0; i < n_q; ++i) {
+        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
+    }
+    if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    // d <= 64 k_max: the sum of squares stays below 2^64 while n_clips k_max^2 4096 does
+    if (d_stats && (unsigned __int128)n_clips * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
+        return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
+    if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
+    // queries are processed in groups so the (query, clip) table stays below 1 GiB
+    int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 27) / n_clips / 32 * 32);
+    qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
+    qgroup = std::min<int64_t>(qgroup, (int64_t)65535 * 8 / 32 * 32); // the scans put groups of 8 / 32 queries along gridDim.y
+    if ((rc = ensure(h->index.d_best, (size_t)qgroup * n_clips * 8))) return rc;
+    // The scan runs on the matrix cores (k_search_mfma.hip) unless the window does not fit the LDS
+    // (queries of several thousand hashprints) or HPFW_SEARCH_POPC asks for the xor/popcount kernel; fewer than
+    // 8 queries go one by one through the shifted-rows variant (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force
+    // the grouped / the shifted-rows kernel for any number of queries).
+    // A group of 32 queries is one MFMA tile: with fewer than 8 queries most of its rows would be padding
+    // and the popcount kernel (one workgroup per 8 queries) does less work.
+    const bool mfma = !std::getenv("HPFW_SEARCH_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024 &&
+                      k_max > 0 && (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
+    const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
+    const int64_t n_max = v.n_max;
+    if (mfma) {
+        if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
+        if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 8))) return rc;
+    }
+    std::vector<int> gk;
+    for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
+        const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
+        HIP_TRY(hipMemsetAsync(h->index.d_best.get(), 0xff, (size_t)ng * n_clips * 8, s));
+        hpfw::SearchArgs a;
+        a.db = h->index.d_db.as<uint64_t>();
+        a.db_off = h->index.d_db_off.as<int64_t>();
+        a.n_clips = (int)n_clips;
+        a.q = d_q_hp;
+        a.q_off = h->index.d_q_off.as<int64_t>() + g0;
+        a.n_q = ng;
+        a.k_max = (int)k_max;
+        a.best = h->index.d_best.as<uint64_t>();
+        a.set = v.d_set;
+        const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !std::getenv("HPFW_SEARCH_POPC") && k_max > 0 && n_max > 0 &&
+                         hpfw::hamming_shift_lds_bytes((int)k_max) <= 160 * 1024;
+        if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
+            if ((rc = ensure(h->index.d_qa, hpfw::hamming_shift_image_bytes((int)k_max)))) return rc;
+            Timed t(h, K_SCAN, s);
+            for (int i = 0; i < ng; ++i) {
+                const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
+                if (kq <= 0) continue;
+                hpfw::launch_hamming_shift(a.db, a.db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
+                                           d_q_hp + q_off[g0 + i], kq, h->index.d_qa.get(), a.best + (size_t)i * n_clips, s, v.d_set);
+            }
+        } else if (mfma && n_max > 0) {
+            gk.assign((size_t)(ng + 31) / 32 * 2, 0); // per group: longest query, shortest non-empty query
+            int kmin_all = 0;
+            for (int i = 0; i < ng; ++i) {
+                const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
+                int &mx = gk[(size_t)i / 32 * 2], &mn = gk[(size_t)i / 32 * 2 + 1];
+                mx = std::max(mx, kq);
+                if (kq > 0) mn = mn == 0 ? kq : std::min(mn, kq);
+                if (kq > 0) kmin_all = kmin_all == 0 ? kq : std::min(kmin_all, kq);
+            }
+            HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
+            Timed t(h, K_SCAN, s);
+            hpfw::launch_expand_queries(d_q_hp, a.q_off, ng, kt_pad, h->index.d_qa.get(), s);
+            // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
+            hpfw::launch_hamming_mfma(a, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)std::max<int64_t>(n_max - std::min<int64_t>(kmin_all, n_max) + 1, 1), s);
+        } else {
+            Timed t(h, K_SCAN, s);
+            hpfw::launch_hamming_scan(a, s);
+        }
+        if ((rc = check_launch("hamming_scan"))) return rc;
+        {
+            Timed t(h, K_TOPK, s);
+            if (n_clips >= 16384 && ng <= 64) { // one workgroup per query would crawl through the whole table
+                if ((rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes(ng, k)))) return rc;
+                hpfw::launch_topk_two_step(a.best, ng, (int)n_clips, k, h->index.clip_base, h->index.d_topk_scratch.get(), d_out + g0 * k, s, v.d_set);
+            } else {
+                hpfw::launch_topk(a.best, ng, (int)n_clips, k, h->index.clip_base, d_out + g0 * k, s, v.d_set);
+            }
+        }
+        if ((rc = check_launch("topk"))) return rc;
+        if (d_stats) {
+            Timed t(h, K_TOPK, s);
+            hpfw::launch_dist_stats(a.best, a.db_off, a.q_off, ng, (int)n_clips, d_stats + g0, s, v.d_set);
+        }
+        if (d_stats && (rc = check_launch("dist_stats"))) return rc;
+    }
+    return 0;
+}
+
 static int search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *d_out,
                               hpfw_dist_stats *d_stats, hipStream_t s)
 {
     if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64) return fail(HPFW_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    return ordered_call(h, s, [&] {
-        if (n_q == 0) return 0;
-        if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
-        const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
-        int rc;
-        if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_q * sizeof(hpfw_dist_stats), s));
-        if (n_clips == 0) { // nothing indexed: every slot is "none"
-            hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->index.clip_base, d_out, s);
-            return check_launch("topk");
-        }
-        if ((rc = upload_db_off(h, s))) return rc;
-        int64_t k_max = 0;
-        for (int64_t i = 0; i < n_q; ++i) {
-            if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-            k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
-        }
-        if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
-        // d <= 64 k_max: the sum of squares stays below 2^64 while n_clips k_max^2 4096 does
-        if (d_stats && (unsigned __int128)n_clips * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
-            return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
-        if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
-        // queries are processed in groups so the (query, clip) table stays below 1 GiB
-        int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 27) / n_clips / 32 * 32);
-        qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
-        qgroup = std::min<int64_t>(qgroup, (int64_t)65535 * 8 / 32 * 32); // the scans put groups of 8 / 32 queries along gridDim.y
-        if ((rc = ensure(h->index.d_best, (size_t)qgroup * n_clips * 8))) return rc;
-        // The scan runs on the matrix cores (k_search_mfma.hip) unless the window does not fit the LDS
-        // (queries of several thousand hashprints) or HPFW_SEARCH_POPC asks for the xor/popcount kernel; fewer than
-        // 8 queries go one by one through the shifted-rows variant (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force
-        // the grouped / the shifted-rows kernel for any number of queries).
-        // A group of 32 queries is one MFMA tile: with fewer than 8 queries most of its rows would be padding
-        // and the popcount kernel (one workgroup per 8 queries) does less work.
-        const bool mfma = !std::getenv("HPFW_SEARCH_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024 &&
-                          k_max > 0 && (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
-        const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
-        const int64_t n_max = index_longest_clip(h);
-        if (mfma) {
-            if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
-            if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 8))) return rc;
-        }
-        std::vector<int> gk;
-        for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
-            const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
-            HIP_TRY(hipMemsetAsync(h->index.d_best.get(), 0xff, (size_t)ng * n_clips * 8, s));
-            hpfw::SearchArgs a;
-            a.db = h->index.d_db.as<uint64_t>();
-            a.db_off = h->index.d_db_off.as<int64_t>();
-            a.n_clips = (int)n_clips;
-            a.q = d_q_hp;
-            a.q_off = h->index.d_q_off.as<int64_t>() + g0;
-            a.n_q = ng;
-            a.k_max = (int)k_max;
-            a.best = h->index.d_best.as<uint64_t>();
-            const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !std::getenv("HPFW_SEARCH_POPC") && k_max > 0 && n_max > 0 &&
-                             hpfw::hamming_shift_lds_bytes((int)k_max) <= 160 * 1024;
-            if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
-                if ((rc = ensure(h->index.d_qa, hpfw::hamming_shift_image_bytes((int)k_max)))) return rc;
-                Timed t(h, K_SCAN, s);
-                for (int i = 0; i < ng; ++i) {
-                    const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
-                    if (kq <= 0) continue;
-                    hpfw::launch_hamming_shift(a.db, a.db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
-                                               d_q_hp + q_off[g0 + i], kq, h->index.d_qa.get(), a.best + (size_t)i * n_clips, s);
-                }
-            } else if (mfma && n_max > 0) {
-                gk.assign((size_t)(ng + 31) / 32 * 2, 0); // per group: longest query, shortest non-empty query
-                int kmin_all = 0;
-                for (int i = 0; i < ng; ++i) {
-                    const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
-                    int &mx = gk[(size_t)i / 32 * 2], &mn = gk[(size_t)i / 32 * 2 + 1];
-                    mx = std::max(mx, kq);
-                    if (kq > 0) mn = mn == 0 ? kq : std::min(mn, kq);
-                    if (kq > 0) kmin_all = kmin_all == 0 ? kq : std::min(kmin_all, kq);
-                }
-                HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
-                Timed t(h, K_SCAN, s);
-                hpfw::launch_expand_queries(d_q_hp, a.q_off, ng, kt_pad, h->index.d_qa.get(), s);
-                // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
-                hpfw::launch_hamming_mfma(a, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)std::max<int64_t>(n_max - std::min<int64_t>(kmin_all, n_max) + 1, 1), s);
-            } else {
-                Timed t(h, K_SCAN, s);
-                hpfw::launch_hamming_scan(a, s);
-            }
-            if ((rc = check_launch("hamming_scan"))) return rc;
-            {
-                Timed t(h, K_TOPK, s);
-                if (n_clips >= 16384 && ng <= 64) { // one workgroup per query would crawl through the whole table
-                    if ((rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes(ng, k)))) return rc;
-                    hpfw::launch_topk_two_step(a.best, ng, (int)n_clips, k, h->index.clip_base, h->index.d_topk_scratch.get(), d_out + g0 * k, s);
-                } else {
-                    hpfw::launch_topk(a.best, ng, (int)n_clips, k, h->index.clip_base, d_out + g0 * k, s);
-                }
-            }
-            if ((rc = check_launch("topk"))) return rc;
-            if (d_stats) {
-                Timed t(h, K_TOPK, s);
-                hpfw::launch_dist_stats(a.best, a.db_off, a.q_off, ng, (int)n_clips, d_stats + g0, s);
-            }
-            if (d_stats && (rc = check_launch("dist_stats"))) return rc;
-        }
-        return 0;
-    });
+    return ordered_call(h, s, [&] { return search_topk_view(h, whole_index(h), d_q_hp, q_off, n_q, k, d_out, d_stats, s); });
 }
 
 int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
@@ -361,19 +375,175 @@ int hpfw_gpu_search_topk_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t
     return search_topk_host(h, q_hp, q_off, n_q, k, out, stats);
 }
 
+// ---- search within sets (the rule: include/hpfw_gpu.h) ---------------------------------------
+// what can be refused without the handle's contents, before a device is touched; q_set has one entry per n_rep queries
+static int within_check(const void *h, const int64_t *q_off, int64_t n_q, int k, const int64_t *set_off, int64_t n_sets,
+                        const int32_t *set_clips, const int32_t *q_set, int n_rep, const void *out)
+{
+    if (!h || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
+    if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    if (n_sets < 0) return fail(HPFW_E_INVALID, "within: n_sets must not be negative");
+    if (n_sets > 0 && !set_off) return fail(HPFW_E_INVALID, "within: null set_off");
+    if (n_sets > 0 && set_off[0] != 0) return fail(HPFW_E_INVALID, "within: set_off[0] must be 0");
+    for (int64_t i = 0; i < n_sets; ++i)
+        if (set_off[i + 1] < set_off[i]) return fail(HPFW_E_INVALID, "within: set_off must not decrease");
+    if (n_sets > 0 && set_off[n_sets] > 0 && !set_clips) return fail(HPFW_E_INVALID, "within: null set_clips");
+    for (int64_t i = 0; i < n_sets; ++i)
+        for (int64_t p = set_off[i]; p < set_off[i + 1]; ++p)
+            if (set_clips[p] < 0 || (p > set_off[i] && set_clips[p] <= set_clips[p - 1]))
+                return fail(HPFW_E_INVALID, "within: set " + std::to_string(i) + " must hold clips >= 0 in strictly ascending order");
+    if (!q_set) return fail(HPFW_E_INVALID, "within: null q_set");
+    for (int64_t i = 0; i < n_q / n_rep; ++i)
+        if (q_set[i] < -1 || q_set[i] >= n_sets)
+            return fail(HPFW_E_INVALID, "within: q_set[" + std::to_string(i) + "] outside -1 .. n_sets - 1");
+    for (int64_t i = 0; i < n_q; ++i) {
+        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        if (q_off[i + 1] - q_off[i] > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    }
+    return 0;
+}
+
+// what the index decides, before a kernel runs
+static int within_check_index(const hpfw_gpu *h, const int64_t *q_off, int64_t n_q, const int64_t *set_off, int64_t n_sets,
+                              const int32_t *set_clips, const int32_t *q_set, int n_rep, bool scored)
+{
+    const int64_t n_slots = (int64_t)h->index.db_off.size() - 1;
+    for (int64_t i = 0; i < n_sets; ++i) // (a set ascends: its last clip is its largest)
+        if (set_off[i + 1] > set_off[i] && set_clips[set_off[i + 1] - 1] >= n_slots)
+            return fail(HPFW_E_INVALID, "within: set " + std::to_string(i) + " names clip " + std::to_string(set_clips[set_off[i + 1] - 1]) +
+                                            " of an index of " + std::to_string(n_slots));
+    if (!scored) return 0;
+    int64_t n = 0, k_max = 0; // the largest set a query names (the index for -1), the longest query
+    for (int64_t i = 0; i < n_q; ++i) {
+        const int32_t st = q_set[i / n_rep];
+        n = std::max(n, st < 0 ? n_slots : set_off[st + 1] - set_off[st]);
+        k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
+    }
+    if ((unsigned __int128)n * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
+        return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
+    return 0;
+}
+
+// The top-k search of n_q queries, query i within set q_set[i / n_rep] (-1: the whole index).  The queries are put in the
+// order of their sets (stable), every set's range goes through search_topk_view over that set's slots -- its table is as wide
+// as the set, its launches cover the set's clips and follow its longest clip -- and the rows of hits and moments are
+// scattered back to the caller's order.  A call without a restricted query is the unrestricted call on the caller's buffers.
+static int search_topk_within_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k, const int64_t *set_off,
+                                     int64_t n_sets, const int32_t *set_clips, const int32_t *q_set, int n_rep, hpfw_hit *d_out,
+                                     hpfw_dist_stats *d_stats, hipStream_t s)
+{
+    if (int rc = within_check(h, q_off, n_q, k, set_off, n_sets, set_clips, q_set, n_rep, d_out)) return rc;
+    if (int rc = within_check_index(h, q_off, n_q, set_off, n_sets, set_clips, q_set, n_rep, d_stats != nullptr)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    return ordered_call(h, s, [&] {
+        if (n_q == 0) return 0;
+        if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
+        // the caller's queries by set, -1 first: order[r] is the query at place r
+        std::vector<int64_t> order((size_t)n_q);
+        for (int64_t i = 0; i < n_q; ++i) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return q_set[a / n_rep] < q_set[b / n_rep]; });
+        if (q_set[order.back() / n_rep] < 0) return search_topk_view(h, whole_index(h), d_q_hp, q_off, n_q, k, d_out, d_stats, s);
+        // one table of 8-byte words on the device: order [n_q], the queries' first hashprints [n_q], their offsets in the new
+        // order [n_q + 1]; behind it the sets' slots
+        const int64_t n_ids = set_off[n_sets];
+        std::vector<int64_t> tab((size_t)n_q * 3 + 1);
+        int64_t *src_off = tab.data() + n_q, *new_off = src_off + n_q;
+        new_off[0] = 0;
+        for (int64_t r = 0; r < n_q; ++r) {
+            tab[(size_t)r] = order[(size_t)r];
+            src_off[r] = q_off[order[(size_t)r]];
+            new_off[r + 1] = new_off[r] + (q_off[order[(size_t)r] + 1] - q_off[order[(size_t)r]]);
+        }
+        int rc;
+        const size_t tab_bytes = tab.size() * 8, hit_bytes = (size_t)n_q * k * sizeof(hpfw_hit);
+        if ((rc = ensure(h->index.d_within_tab, tab_bytes + (size_t)std::max<int64_t>(n_ids, 1) * 4))) return rc;
+        if ((rc = ensure(h->index.d_within_q, (size_t)std::max<int64_t>(new_off[n_q], 1) * 8))) return rc;
+        if ((rc = ensure(h->index.d_within_out, hit_bytes + (d_stats ? (size_t)n_q * sizeof(hpfw_dist_stats) : 0)))) return rc;
+        const int64_t *d_tab = h->index.d_within_tab.as<int64_t>();
+        const int32_t *d_ids = reinterpret_cast<const int32_t *>(h->index.d_within_tab.as<char>() + tab_bytes);
+        uint64_t *d_q = h->index.d_within_q.as<uint64_t>();
+        hpfw_hit *d_hits = h->index.d_within_out.as<hpfw_hit>();
+        hpfw_dist_stats *d_st = d_stats ? reinterpret_cast<hpfw_dist_stats *>(h->index.d_within_out.as<char>() + hit_bytes) : nullptr;
+        HIP_TRY(hipMemcpyAsync(h->index.d_within_tab.get(), tab.data(), tab_bytes, hipMemcpyHostToDevice, s));
+        if (n_ids) HIP_TRY(hipMemcpyAsync(h->index.d_within_tab.as<char>() + tab_bytes, set_clips, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
+        hpfw::launch_within_gather(d_q_hp, d_tab + n_q, d_tab + 2 * n_q, n_q, d_q, s);
+        if ((rc = check_launch("within_gather"))) return rc;
+        for (int64_t r0 = 0; r0 < n_q;) {
+            const int32_t st = q_set[order[(size_t)r0] / n_rep];
+            int64_t r1 = r0;
+            while (r1 < n_q && q_set[order[(size_t)r1] / n_rep] == st) ++r1;
+            ClipView v;
+            if (st < 0) {
+                v = whole_index(h);
+            } else {
+                v = {set_off[st + 1] - set_off[st], 0, d_ids + set_off[st]};
+                for (int64_t p = set_off[st]; p < set_off[st + 1]; ++p)
+                    v.n_max = std::max(v.n_max, h->index.db_off[(size_t)set_clips[p] + 1] - h->index.db_off[(size_t)set_clips[p]]);
+            }
+            if ((rc = search_topk_view(h, v, d_q, new_off + r0, r1 - r0, k, d_hits + r0 * k, d_st ? d_st + r0 : nullptr, s))) return rc;
+            r0 = r1;
+        }
+        static_assert(sizeof(hpfw_hit) % 8 == 0 && sizeof(hpfw_dist_stats) % 8 == 0, "the scatter moves 8-byte words");
+        hpfw::launch_within_scatter(reinterpret_cast<const uint64_t *>(d_hits), d_tab, n_q, k * (int)(sizeof(hpfw_hit) / 8),
+                                    reinterpret_cast<uint64_t *>(d_out), s);
+        if (d_stats)
+            hpfw::launch_within_scatter(reinterpret_cast<const uint64_t *>(d_st), d_tab, n_q, (int)(sizeof(hpfw_dist_stats) / 8),
+                                        reinterpret_cast<uint64_t *>(d_stats), s);
+        if ((rc = check_launch("within_scatter"))) return rc;
+        HIP_TRY(hipStreamSynchronize(s)); // (the caller's set arrays and the tables above have been read)
+        return 0;
+    });
+}
+
+int hpfw_gpu_search_topk_within_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k, const int64_t *set_off,
+                                       int64_t n_sets, const int32_t *set_clips, const int32_t *q_set, hpfw_hit *d_out,
+                                       hpfw_dist_stats *d_stats, void *stream)
+{
+    return search_topk_within_device(h, d_q_hp, q_off, n_q, k, set_off, n_sets, set_clips, q_set, 1, d_out, d_stats, (hipStream_t)stream);
+}
+
+int hpfw_gpu_search_topk_within(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k, const int64_t *set_off,
+                                int64_t n_sets, const int32_t *set_clips, const int32_t *q_set, hpfw_hit *out, hpfw_dist_stats *stats)
+{
+    if (int rc = within_check(h, q_off, n_q, k, set_off, n_sets, set_clips, q_set, 1, out)) return rc;
+    if (int rc = within_check_index(h, q_off, n_q, set_off, n_sets, set_clips, q_set, 1, stats != nullptr)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_q == 0) return 0;
+    return search_round_trip_scored(q_hp, q_off, n_q, n_q * k, out, stats ? n_q : 0, stats,
+                                    [&](const uint64_t *d_q, const int64_t *rel, hpfw_hit *d_out, hpfw_dist_stats *d_stats) {
+                                        return search_topk_within_device(h, d_q, rel, n_q, k, set_off, n_sets, set_clips, q_set, 1, d_out,
+                                                                         d_stats, nullptr);
+                                    });
+}
+
 // d_stats: NULL, or [n_q][n_shifts] rows, one per query set
+// within: NULL, or the sets of the call (q_set: one entry per query, for its n_shifts variants)
+struct WithinSets {
+    const int64_t *set_off;
+    int64_t n_sets;
+    const int32_t *set_clips, *q_set;
+};
+
 static int search_topk_transposed_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
-                                         hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats, hipStream_t s)
+                                         hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats, hipStream_t s, const WithinSets *within = nullptr)
 {
     if (!h || !q_off || !d_out || n_q < 0 || k < 1 || k > 64 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts)
         return fail(HPFW_E_INVALID, "bad argument");
+    if (within) { // (refused here, while nothing has been touched)
+        if (int rc = within_check(h, q_off, n_q * n_shifts, k, within->set_off, within->n_sets, within->set_clips, within->q_set, n_shifts, d_out)) return rc;
+        if (int rc = within_check_index(h, q_off, n_q * n_shifts, within->set_off, within->n_sets, within->set_clips, within->q_set, n_shifts, d_stats != nullptr)) return rc;
+    }
     HIP_TRY(hipSetDevice(h->device));
     return ordered_call(h, s, [&] {
         if (n_q == 0) return 0;
         int rc;
         // the per-shift lists: n_q * n_shifts queries in one pass of the existing scan, then one workgroup per query merges them
         if ((rc = ensure(h->index.d_shift_hits, (size_t)n_q * n_shifts * k * sizeof(hpfw_hit)))) return rc;
-        if ((rc = search_topk_device(h, d_q_hp, q_off, n_q * n_shifts, k, h->index.d_shift_hits.as<hpfw_hit>(), d_stats, s))) return rc;
+        hpfw_hit *d_lists = h->index.d_shift_hits.as<hpfw_hit>();
+        rc = within ? search_topk_within_device(h, d_q_hp, q_off, n_q * n_shifts, k, within->set_off, within->n_sets, within->set_clips,
+                                                within->q_set, n_shifts, d_lists, d_stats, s)
+                    : search_topk_device(h, d_q_hp, q_off, n_q * n_shifts, k, d_lists, d_stats, s);
+        if (rc) return rc;
         {
             Timed t(h, K_TOPK, s);
             hpfw::launch_topk_merge_shifts(h->index.d_shift_hits.get(), (int)n_q, n_shifts, k, d_out, s);
@@ -396,16 +566,36 @@ int hpfw_gpu_search_topk_transposed_scored_device(hpfw_gpu *h, const uint64_t *d
 }
 
 static int search_topk_transposed_host(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
-                                       hpfw_shift_hit *out, hpfw_dist_stats *stats)
+                                       hpfw_shift_hit *out, hpfw_dist_stats *stats, const WithinSets *within = nullptr)
 {
     if (!h || !q_off || !out || n_q < 0 || n_shifts < 1 || n_shifts > hpfw::kMaxShifts) return fail(HPFW_E_INVALID, "bad argument");
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
+    if (within) {
+        if (int rc = within_check(h, q_off, n_q * n_shifts, k, within->set_off, within->n_sets, within->set_clips, within->q_set, n_shifts, out)) return rc;
+        if (int rc = within_check_index(h, q_off, n_q * n_shifts, within->set_off, within->n_sets, within->set_clips, within->q_set, n_shifts, stats != nullptr)) return rc;
+    }
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
     return search_round_trip_scored(q_hp, q_off, n_q * n_shifts, n_q * k, out, stats ? n_q * n_shifts : 0, stats,
                                     [&](const uint64_t *d_q, const int64_t *rel, hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats) {
-                                        return search_topk_transposed_device(h, d_q, rel, n_q, n_shifts, k, d_out, d_stats, nullptr);
+                                        return search_topk_transposed_device(h, d_q, rel, n_q, n_shifts, k, d_out, d_stats, nullptr, within);
                                     });
+}
+
+int hpfw_gpu_search_topk_transposed_within_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                                  const int64_t *set_off, int64_t n_sets, const int32_t *set_clips, const int32_t *q_set,
+                                                  hpfw_shift_hit *d_out, hpfw_dist_stats *d_stats, void *stream)
+{
+    const WithinSets w{set_off, n_sets, set_clips, q_set};
+    return search_topk_transposed_device(h, d_q_hp, q_off, n_q, n_shifts, k, d_out, d_stats, (hipStream_t)stream, &w);
+}
+
+int hpfw_gpu_search_topk_transposed_within(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,
+                                           const int64_t *set_off, int64_t n_sets, const int32_t *set_clips, const int32_t *q_set,
+                                           hpfw_shift_hit *out, hpfw_dist_stats *stats)
+{
+    const WithinSets w{set_off, n_sets, set_clips, q_set};
+    return search_topk_transposed_host(h, q_hp, q_off, n_q, n_shifts, k, out, stats, &w);
 }
 
 int hpfw_gpu_search_topk_transposed(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts, int k,

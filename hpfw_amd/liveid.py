@@ -247,26 +247,63 @@ class LiveSongIdentification:
         self._append(kept)
         return [name for _, name in kept], named
 
+    # ---- search within a subset of the index
+    def _within_slots(self, within) -> List[int]:
+        """the sorted live slots that carry one of the names; an unknown or removed name raises KeyError, as remove() does"""
+        slots = set()
+        for name in dict.fromkeys(within):
+            live = self._live_slots(name)
+            if not live:
+                raise KeyError(name)
+            slots.update(live)
+        return sorted(slots)
+
+    def _check_within(self, within, min_overlap=None):
+        """what top(), timeline() and streams() refuse of within, before anything runs on a device"""
+        if within is None:
+            return
+        if min_overlap is not None:
+            raise _lib.HpfwError("within: the overlap rule does not search within a set", _lib.E_UNSUPPORTED)
+        if isinstance(self._gpu, _ShardedIndex):
+            raise _lib.HpfwError("the search within a set is not available on a sharded index", _lib.E_UNSUPPORTED)
+
+    def _one_set(self, within, n_q):
+        """within (names or None) as _search_windows and top() take it: None, or (set_off, set_clips, q_set) with every one of
+        the n_q queries in the one set"""
+        if within is None:
+            return None
+        slots = self._within_slots(within)
+        return np.array([0, len(slots)], np.int64), np.array(slots, np.int32), np.zeros(n_q, np.int32)
+
     def top(self, filenames: Sequence[str], k: int = 10, shifts: Optional[Sequence[int]] = None,
-            tempos: Optional[Sequence[float]] = None):
+            tempos: Optional[Sequence[float]] = None, within: Optional[Sequence[str]] = None):
         """per query (label, [(distance, name, offset) x <= k]) ordered by (distance, position in the
         database); None in place of the list for a file that yields no hashprint.  shifts: bin shifts of the query's
         constant-Q spectrogram to search as well (t semitones above the indexed recording is
         s = 2t): each clip's smallest distance over them, and every hit is (distance, name, offset, shift).  tempos:
         tempo factors (query tempo / indexed tempo) to search, each combined with every shift:
         every hit is (distance, name, offset, shift, tempo), shift 0 when shifts is None, offset in the indexed
-        recording; a query too short for the slowest tempo yields None"""
+        recording; a query too short for the slowest tempo yields None.  within: names of indexed recordings -- the search
+        runs over the live slots carrying them alone and answers what an identifier of just those recordings would (DESIGN.md
+        section 24); an unknown or removed name raises KeyError before anything runs, an identifier made with devices= raises
+        HPFW_E_UNSUPPORTED"""
+        self._check_within(within)
+        sets = self._one_set(within, 0)                   # (names -> slots: a KeyError comes before any file is read)
         if tempos is not None:
-            return self._top_tempo(list(filenames), k, None if shifts is None else list(shifts), list(tempos))
+            return self._top_tempo(list(filenames), k, None if shifts is None else list(shifts), list(tempos), sets)
         if shifts is not None:
-            return self._top_transposed(list(filenames), k, list(shifts))
+            return self._top_transposed(list(filenames), k, list(shifts), sets)
         hps = self.collector.calc_hashprints(list(filenames))
         good = [i for i, (hp, _) in enumerate(hps) if hp is not None and hp.size]
         out = [(f, None) for f in filenames]
         if good and self.names:
             off = np.zeros(len(good) + 1, np.int64)
             np.cumsum([hps[i][0].size for i in good], out=off[1:])
-            hits = self._gpu.search_topk(np.concatenate([hps[i][0] for i in good]), off, k)
+            q = np.concatenate([hps[i][0] for i in good])
+            if sets is None:
+                hits = self._gpu.search_topk(q, off, k)
+            else:
+                hits = self._gpu.search_topk_within(q, off, k, sets[0], sets[1], np.zeros(len(good), np.int32))
             for row, i in zip(hits, good):
                 out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"]))
                                          for h in row if h["clip"] != 0xFFFFFFFF])
@@ -360,12 +397,12 @@ class LiveSongIdentification:
         win = int(round(window_s * 44100))
         return np.asarray(columns, np.float64) * (3.0 * win / self._gpu.geometry(win).m / 44100.0)
 
-    def _top_transposed(self, filenames: List[str], k: int, shifts: List[int]):
+    def _top_transposed(self, filenames: List[str], k: int, shifts: List[int], sets=None):
         shifts = _lib.check_shifts(shifts)
         return self._top_sets(filenames, k, len(shifts), lambda g, x: g.extract_transposed(x, shifts)[0],
-                              lambda h: (shifts[int(h["shift_index"])],), "transposed")
+                              lambda h: (shifts[int(h["shift_index"])],), "transposed", sets)
 
-    def _top_tempo(self, filenames: List[str], k: int, shifts: Optional[List[int]], tempos: List[float]):
+    def _top_tempo(self, filenames: List[str], k: int, shifts: Optional[List[int]], tempos: List[float], sets=None):
         if shifts is not None:
             shifts = _lib.check_shifts(shifts)
         n_s = len(shifts) if shifts else 1
@@ -375,11 +412,12 @@ class LiveSongIdentification:
             j, i = divmod(int(h["shift_index"]), n_s)                 # variant v = j max(S, 1) + i
             return (shifts[i] if shifts else 0, tempos[j])
         return self._top_sets(filenames, k, len(tempos) * n_s, lambda g, x: g.extract_tempo(x, tempos, shifts)[0], decode,
-                              "tempo")
+                              "tempo", sets)
 
-    def _top_sets(self, filenames: List[str], k: int, n_sets: int, extract, decode, what: str):
+    def _top_sets(self, filenames: List[str], k: int, n_sets: int, extract, decode, what: str, within=None):
         """the search of n_sets hashprint sets per query (extract(gpu, pcm) -> [n_sets][n_hp]) merged per clip
-        (hpfw_gpu_search_topk_transposed); decode(hit) -> what a hit adds to (distance, name, offset)"""
+        (hpfw_gpu_search_topk_transposed); decode(hit) -> what a hit adds to (distance, name, offset); within: None, or
+        _one_set()'s set of clips for every query"""
         extractor = self.collector.gpu()                  # the collector's filters
         if extractor.get_projection() != 1:
             raise _lib.HpfwError(f"{what} search needs projection mode 1 (fixed point)", _lib.E_INVALID)
@@ -401,7 +439,11 @@ class LiveSongIdentification:
         if good and self.names:
             off = np.zeros(len(sets) + 1, np.int64)
             np.cumsum([hp.size for hp in sets], out=off[1:])
-            hits = self._gpu.search_topk_transposed(np.concatenate(sets), off, n_sets, k)
+            if within is None:
+                hits = self._gpu.search_topk_transposed(np.concatenate(sets), off, n_sets, k)
+            else:
+                hits = self._gpu.search_topk_transposed_within(np.concatenate(sets), off, n_sets, k, within[0], within[1],
+                                                               np.zeros(len(good), np.int32))
             for row, i in zip(hits, good):
                 out[i] = (filenames[i], [(int(h["dist"]), self.names[int(h["clip"])], int(h["offset"])) + decode(h)
                                          for h in row if h["clip"] != 0xFFFFFFFF])
@@ -410,7 +452,7 @@ class LiveSongIdentification:
     def timeline(self, filename: str, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
                  shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
                  tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, windows: bool = False,
-                 min_overlap: Optional[int] = None):
+                 min_overlap: Optional[int] = None, within: Optional[Sequence[str]] = None):
         """the set list of one long recording: windows of window_s seconds every hop_s seconds, each
         searched for its best clip and scored by how far that clip stands out from the others (hpfw_gpu_hit_score);
         consecutive windows with score >= min_score that name the same clip at consistent offsets form a segment
@@ -424,8 +466,15 @@ class LiveSongIdentification:
         offset is then the lag (negative: the window begins before the clip does), the score is that of the hit's rate among
         the rates of the other clips, start_s / end_s are trimmed to the part of the first and last window that lies on the
         clip, offset_s is max(0, first lag) in seconds, and a window tuple carries the overlap as an eighth element.  Not
-        with shifts or tempos and not on an identifier made with devices= (HPFW_E_UNSUPPORTED)."""
+        with shifts or tempos and not on an identifier made with devices= (HPFW_E_UNSUPPORTED).
+        within=names: every window is searched within the live slots carrying those names, as top()
+        does it, and gives what an identifier of just those recordings gives.  The scores are against the moments of the set's
+        clips: how far a song stands out from the set, not from the catalogue; a set with fewer than 3 counted clips scores
+        NaN, as an index of 2 clips does, and no window is strong.  An unknown or removed name raises KeyError before anything
+        runs.  Not with min_overlap and not on an identifier made with devices= (HPFW_E_UNSUPPORTED)."""
         win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
+        self._check_within(within, min_overlap)
+        slots = None if within is None else self._within_slots(within)
         self._check_min_overlap(min_overlap, shifts, tempos, win, hop)
         if shifts is not None:
             shifts = _lib.check_shifts(shifts)
@@ -449,7 +498,8 @@ class LiveSongIdentification:
             hp = self._gpu.extract_windows(extractor, x, win, hop, tempos, shifts)
         else:
             hp = extractor.extract_windows(x, win, hop, tempos, shifts)
-        rows, per_window = self._search_windows(hp, shifts, tempos, min_overlap)
+        sets = None if slots is None else (np.array([0, len(slots)], np.int64), np.array(slots, np.int32), np.zeros(hp.shape[0], np.int32))
+        rows, per_window = self._search_windows(hp, shifts, tempos, min_overlap, sets)
         m = self._gpu.geometry(win).m
         segs = _lib.timeline_segments(rows, min_score, hop * m / (3.0 * win), win, hop, tol_cols, max_gap, min_windows)
         out = [self._segment_tuple(sg, *per_window[int(sg["best_window"])][5:7], 3.0 * win / m / 44100.0,
@@ -502,10 +552,12 @@ class LiveSongIdentification:
         _, b = _lib.overlap_extent(last_lag, n_clip, g.n_hp, g.c - g.n_hp + 1, win, g.m)
         return int(sg["first"]) * hop + a, int(sg["last"]) * hop + b, int(first_lag)
 
-    def _search_windows(self, hp, shifts, tempos, min_overlap=None):
+    def _search_windows(self, hp, shifts, tempos, min_overlap=None, sets=None):
         """the scored search of the windows' hashprints hp [n_w][k_q] or, with variants, [n_w][n_sets][k_q] (shifts and tempos
         as checked): (WINDOW_HIT_DTYPE [n_w] for the segment rule, [(clip index or None, name or None, distance, offset, score,
-        shift, tempo) per window]).  timeline() and LiveStreams.push() share it.  min_overlap: None, or the overlap rule."""
+        shift, tempo) per window]).  timeline() and LiveStreams.push() share it.  min_overlap: None, or the overlap rule.
+        sets: None, or (set_off, set_clips, q_set [n_w]) -- window w is searched within set q_set[w] (-1: the whole index) and
+        scored against that set's moments, in the one search."""
         if min_overlap is not None:
             return self._search_windows_overlap(hp, min_overlap)
         variants = shifts is not None or tempos is not None
@@ -513,8 +565,12 @@ class LiveSongIdentification:
         n_sets = (len(tempos) if tempos else 1) * n_s
         n_w, k_q = hp.shape[0], hp.shape[-1]
         off = np.arange(n_w * n_sets + 1, dtype=np.int64) * k_q
-        if variants:
+        if variants and sets is not None:
+            hits, stats = self._gpu.search_topk_transposed_within(hp, off, n_sets, 1, *sets, scored=True)
+        elif variants:
             hits, stats = self._gpu.search_topk_transposed_scored(hp, off, n_sets, 1)
+        elif sets is not None:
+            hits, stats = self._gpu.search_topk_within(hp, off, 1, *sets, scored=True)
         else:
             hits, stats = self._gpu.search_topk_scored(hp, off, 1)
         clip_len = np.diff(self._gpu.index_offsets())
@@ -546,22 +602,31 @@ class LiveSongIdentification:
     def streams(self, n_streams: int, min_score: float, window_s: float = 5.0, hop_s: float = 2.5,
                 shifts: Optional[Sequence[int]] = None, tempos: Optional[Sequence[float]] = None,
                 tol_cols: Optional[float] = None, max_gap: int = 1, min_windows: int = 1, capacity_s: Optional[float] = None,
-                windows: bool = False, rate=44100, min_overlap: Optional[int] = None):
+                windows: bool = False, rate=44100, min_overlap: Optional[int] = None, within=None):
         """the timelines of n_streams live feeds as their samples arrive (hpfw_amd.streams.LiveStreams):
         per feed exactly what timeline() gives for a file that holds everything pushed to it.  Feeds are mono PCM16.  rate: the
         feeds' sample rate, one int for all or one per feed; another rate than 44 100 Hz is taken only by an identifier made with
         resample=True, as files at other rates are (HPFW_E_UNSUPPORTED otherwise), and is converted chunk by chunk on the GPU:
         the feed then yields what timeline() gives for a file at that rate, once H zero samples have been pushed behind its end
         (LiveStreams.tail).  capacity_s: seconds of audio a feed's ring holds (None: two windows).  min_overlap: as timeline()'s,
-        with its refusals."""
+        with its refusals.  within: None, one list of names for all feeds, or one entry per feed (a list of names or None):
+        a feed's windows are searched within its set and scored against the set's moments, as timeline(within=) does (fewer
+        than 3 counted clips: NaN), and one push is still one search; the names become slots here, with timeline()'s KeyError
+        and refusals."""
         from .streams import LiveStreams
+        self._check_within(within, min_overlap)
+        if within is not None:
+            per_feed = [within] * int(n_streams) if all(isinstance(w, str) for w in within) else list(within)
+            if len(per_feed) != int(n_streams):
+                raise ValueError("within: one list of names, or one entry per feed")
+            within = [None if w is None else self._within_slots(w) for w in per_feed]
         rates = [int(rate)] * int(n_streams) if np.ndim(rate) == 0 else [int(r) for r in rate]
         other = [r for r in rates if r != 44100]
         if other and not self._resample:
             raise _lib.HpfwError(f"live feeds are 44.1 kHz mono PCM16: a feed at {other[0]} Hz has to be converted before it is pushed",
                                  _lib.E_UNSUPPORTED)
         return LiveStreams(self, n_streams, min_score, window_s, hop_s, shifts, tempos, tol_cols, max_gap, min_windows, capacity_s,
-                           windows, rates if other else None, min_overlap)
+                           windows, rates if other else None, min_overlap, within)
 
     def search(self, filenames: Sequence[str], shifts: Optional[Sequence[int]] = None,
                tempos: Optional[Sequence[float]] = None):

@@ -19,12 +19,24 @@ from . import _lib
 
 class LiveStreams:
     def __init__(self, lsi, n_streams, min_score, window_s=5.0, hop_s=2.5, shifts=None, tempos=None, tol_cols=None, max_gap=1,
-                 min_windows=1, capacity_s=None, windows=False, rates=None, min_overlap=None):
+                 min_windows=1, capacity_s=None, windows=False, rates=None, min_overlap=None, within=None):
+        """within: None, or per feed the sorted slots its windows are searched within (None: the whole index), as
+        LiveSongIdentification.streams() makes them from names"""
         self._lsi = lsi
         win, hop = int(round(window_s * 44100)), int(round(hop_s * 44100))
         lsi._check_min_overlap(min_overlap, shifts, tempos, win, hop)
         self._min_overlap = min_overlap
         self._lags = [{} for _ in range(n_streams)]       # overlap rule: per feed {window: lag} from the open segment's first on
+        # search within sets (DESIGN.md section 24): the restricted feeds' sets in CSR form and each feed's set (-1: none)
+        self._sets = None
+        if within is not None and any(w is not None for w in within):
+            if min_overlap is not None:
+                raise _lib.HpfwError("within: the overlap rule does not search within a set", _lib.E_UNSUPPORTED)
+            lists = [w for w in within if w is not None]
+            feed_set = np.cumsum([w is not None for w in within]) - 1
+            self._sets = (np.concatenate([[0], np.cumsum([len(w) for w in lists])]).astype(np.int64),
+                          np.array([c for w in lists for c in w], np.int32),
+                          np.where([w is not None for w in within], feed_set, -1).astype(np.int32))
         self._shifts = None if shifts is None else _lib.check_shifts(shifts)
         self._tempos = None if tempos is None else _lib.check_tempos(tempos, 0 if shifts is None else len(self._shifts))
         self._windows = bool(windows)
@@ -92,7 +104,8 @@ class LiveStreams:
         segments, wins = [], []
         if self._gs.push(chunks):
             which, hp = self._gs.extract()
-            rows, per_window = self._lsi._search_windows(hp, self._shifts, self._tempos, self._min_overlap)
+            sets = None if self._sets is None else (self._sets[0], self._sets[1], self._sets[2][which["feed"]])
+            rows, per_window = self._lsi._search_windows(hp, self._shifts, self._tempos, self._min_overlap, sets)
             wins = [(int(w["feed"]), int(w["window"]), row) for w, row in zip(which, per_window)]
             if self._min_overlap is not None:
                 for f, w, row in wins:

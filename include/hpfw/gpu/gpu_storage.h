@@ -138,6 +138,29 @@ public:
         return out;
     }
 
+    /// find_topk() within a subset of the index (hpfw_gpu_search_topk_within): `clips` are positions in
+    /// the database in strictly ascending order, and the answer is the one a storage built from just those recordings gives.
+    /// The scan covers the listed recordings only.
+    auto find_within(const typename Collector::Hashprint &hp, int k, const std::vector<int32_t> &clips) const -> std::vector<SearchResult>
+    {
+        std::vector<SearchResult> out;
+        for (const ScoredResult &r : within(hp, k, clips, false)) out.push_back({r.filename, r.cnt, r.offset});
+        return out;
+    }
+
+    /// find_within() with scores: per hit how far its distance stands out from the best distances of the other counted
+    /// recordings of the SET (hpfw_gpu_hit_score; NaN below three counted recordings, as an index of two gives)
+    struct ScoredResult {
+        std::string filename;
+        size_t cnt;
+        int64_t offset;
+        double score;
+    };
+    auto find_within_scored(const typename Collector::Hashprint &hp, int k, const std::vector<int32_t> &clips) const -> std::vector<ScoredResult>
+    {
+        return within(hp, k, clips, true);
+    }
+
     /// a query played in another key: per_shift[i] holds the query's hashprints under shift i
     /// (hpfw::transposed_hashprints, include/hpfw/gpu/transposed.h); per clip the smallest distance over the shifts, ties
     /// to the first shift; the k best clips by (distance, position in the database) with the index of their shift
@@ -417,6 +440,24 @@ public:
     }
 
 private:
+    auto within(const typename Collector::Hashprint &hp, int k, const std::vector<int32_t> &clips, bool scored) const -> std::vector<ScoredResult>
+    {
+        std::vector<ScoredResult> out;
+        if (hp.empty() || names_.empty()) return out;
+        const int64_t q_off[2] = {0, (int64_t)hp.size()}, set_off[2] = {0, (int64_t)clips.size()};
+        const int32_t q_set = 0, none = 0;
+        std::vector<hpfw_hit> hits((size_t)k);
+        hpfw_dist_stats stats{};
+        check(hpfw_gpu_search_topk_within(h_, hp.data(), q_off, 1, k, set_off, 1, clips.empty() ? &none : clips.data(), &q_set, hits.data(),
+                                          scored ? &stats : nullptr));
+        for (const hpfw_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            double score = 0;
+            if (scored) check(hpfw_gpu_hit_score(hit.dist, added_len_[hit.clip] >= (int64_t)hp.size(), &stats, &score));
+            out.push_back({names_[hit.clip], (size_t)hit.dist, (int64_t)hit.offset, score});
+        }
+        return out;
+    }
     static int env_device()
     {
         const char *e = std::getenv("HPFW_GPU_DEVICE");

@@ -54,6 +54,7 @@ public:
         constexpr bool sharded = requires { storage.group(); };
         if (hpfw_gpu_geometry(h, opt.win, &g_) != 0) fail("geometry");
         detail::check_min_overlap(opt, sharded, g_.n_hp);
+        within_ = detail::within_sets(opt, sharded, std::max(n_streams, 0));
         lags_.resize((size_t)std::max(n_streams, 0));
         hpfw_streams_params p{n_streams, (int32_t)opt.tempos.size(), (int32_t)opt.shifts.size(), 0, opt.win, opt.hop, opt.capacity,
                               opt.tempos.empty() ? nullptr : opt.tempos.data(), opt.shifts.empty() ? nullptr : opt.shifts.data()};
@@ -104,7 +105,15 @@ public:
         if constexpr (sharded)
             rc = variants ? hpfw_gpu_group_search_topk_transposed_scored(storage_.group(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
                           : hpfw_gpu_group_search_topk_scored(storage_.group(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data());
-        else
+        else if (within_.any) { // every window within its feed's set, in the one search of the push
+            std::vector<int32_t> q_set((size_t)n_w);
+            for (int64_t w = 0; w < n_w; ++w) q_set[(size_t)w] = within_.owner_set[(size_t)which[(size_t)w].feed];
+            const int n_sets = (int)within_.set_off.size() - 1;
+            rc = variants ? hpfw_gpu_search_topk_transposed_within(storage_.handle(), hp.data(), q_off.data(), n_w, sets, 1, within_.set_off.data(),
+                                                                   n_sets, within_.set_clips.data(), q_set.data(), hits.data(), stats.data())
+                          : hpfw_gpu_search_topk_within(storage_.handle(), hp.data(), q_off.data(), n_w, 1, within_.set_off.data(), n_sets,
+                                                        within_.set_clips.data(), q_set.data(), plain.data(), stats.data());
+        } else
             rc = variants ? hpfw_gpu_search_topk_transposed_scored(storage_.handle(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
                           : hpfw_gpu_search_topk_scored(storage_.handle(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data());
         if (rc != 0) fail("search");
@@ -239,6 +248,7 @@ private:
     hpfw_timeline_params tp_{};
     hpfw_geometry g_{};
     std::vector<std::map<int64_t, int32_t>> lags_; // min_overlap: per feed, window -> lag
+    detail::WithinSets within_;                    // opt.within: the feeds' sets
     double col_s_ = 0;
     std::vector<int16_t> pcm_;
     std::vector<LiveWindow> windows_;

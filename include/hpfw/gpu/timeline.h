@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -30,6 +31,11 @@ struct TimelineOptions {
     int max_gap = 1, min_windows = 1;
     int min_overlap = 0;           ///< 0: the plain rule.  N > 0: every window is searched by the overlap rule over at least N
                                    ///< hashprints; no tempos, no shifts, no sharded storage then
+    /// search within a subset of the index.  Empty: the whole index.  hpfw::timeline takes one entry,
+    /// hpfw::LiveStreams one entry for all feeds or one per feed; an entry is the clip ids (positions in the storage, strictly
+    /// ascending) its windows are searched within, or nullopt for the whole index.  Scores are then against the moments of the
+    /// set's clips (NaN below three counted clips).  Not with min_overlap and not with a sharded storage.
+    std::vector<std::optional<std::vector<int32_t>>> within;
 };
 
 struct TimelineSegment {
@@ -57,6 +63,33 @@ inline void check_min_overlap(const TimelineOptions &opt, bool sharded, int64_t 
     if (!opt.tempos.empty() || !opt.shifts.empty()) throw std::runtime_error("hpfw: min_overlap: the overlap rule has no shifts and no tempos (HPFW_E_UNSUPPORTED)");
     if (sharded) throw std::runtime_error("hpfw: min_overlap: the overlap search is not available on a sharded index (HPFW_E_UNSUPPORTED)");
     if (opt.min_overlap < 1 || opt.min_overlap > nhp) throw std::runtime_error("hpfw: min_overlap must be in 1.." + std::to_string(nhp) + ", the hashprints of a window (HPFW_E_INVALID)");
+}
+
+/// TimelineOptions::within as the C ABI takes it, for `owners` owners of windows (1: hpfw::timeline; the feeds of
+/// hpfw::LiveStreams): the sets in CSR form and the set of each owner (-1: the whole index).  `any` is false when nothing is
+/// restricted.  Refuses, before anything runs on a device, what within does not go with.
+struct WithinSets {
+    std::vector<int64_t> set_off{0};
+    std::vector<int32_t> set_clips, owner_set;
+    bool any = false;
+};
+inline WithinSets within_sets(const TimelineOptions &opt, bool sharded, int owners)
+{
+    WithinSets ws;
+    if (opt.within.empty()) return ws;
+    if (opt.min_overlap != 0) throw std::runtime_error("hpfw: within: the overlap rule does not search within a set (HPFW_E_UNSUPPORTED)");
+    if (sharded) throw std::runtime_error("hpfw: within: the search within a set is not available on a sharded index (HPFW_E_UNSUPPORTED)");
+    if (opt.within.size() != 1 && (int)opt.within.size() != owners) throw std::runtime_error("hpfw: within: one entry, or one per feed (HPFW_E_INVALID)");
+    for (int i = 0; i < owners; ++i) {
+        const auto &w = opt.within[opt.within.size() == 1 ? 0 : (size_t)i];
+        ws.owner_set.push_back(w ? (int32_t)ws.set_off.size() - 1 : -1);
+        if (!w) continue;
+        ws.any = true;
+        ws.set_clips.insert(ws.set_clips.end(), w->begin(), w->end());
+        ws.set_off.push_back((int64_t)ws.set_clips.size());
+    }
+    ws.set_clips.push_back(0); // (never empty: data() is a pointer the call may be given)
+    return ws;
 }
 
 /// the best hit of n_w windows of nhp hashprints each by the overlap rule, scored by its rate among the rates of the
@@ -109,6 +142,7 @@ Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, 
     hpfw_geometry g;
     if (hpfw_gpu_geometry(h, opt.win, &g) != 0) fail("geometry");
     detail::check_min_overlap(opt, sharded, g.n_hp);
+    const detail::WithinSets ws = detail::within_sets(opt, sharded, 1);
     if (hpfw_gpu_wav_read_pcm16(path.c_str(), nullptr, 0, &n) != 0) fail(path.c_str());
     std::vector<int16_t> pcm((size_t)std::max<int64_t>(n, 1));
     if (hpfw_gpu_wav_read_pcm16(path.c_str(), pcm.data(), n, &n) != 0) fail(path.c_str());
@@ -171,7 +205,14 @@ Timeline timeline(const Storage &storage, hpfw_gpu *h, const std::string &path, 
     if constexpr (sharded)
         rc = variants ? hpfw_gpu_group_search_topk_transposed_scored(storage.group(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
                       : hpfw_gpu_group_search_topk_scored(storage.group(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data());
-    else
+    else if (ws.any) { // every window within the one set
+        const std::vector<int32_t> q_set((size_t)n_w, ws.owner_set[0]);
+        const int n_sets = (int)ws.set_off.size() - 1;
+        rc = variants ? hpfw_gpu_search_topk_transposed_within(storage.handle(), hp.data(), q_off.data(), n_w, sets, 1, ws.set_off.data(), n_sets,
+                                                               ws.set_clips.data(), q_set.data(), hits.data(), stats.data())
+                      : hpfw_gpu_search_topk_within(storage.handle(), hp.data(), q_off.data(), n_w, 1, ws.set_off.data(), n_sets,
+                                                    ws.set_clips.data(), q_set.data(), plain.data(), stats.data());
+    } else
         rc = variants ? hpfw_gpu_search_topk_transposed_scored(storage.handle(), hp.data(), q_off.data(), n_w, sets, 1, hits.data(), stats.data())
                       : hpfw_gpu_search_topk_scored(storage.handle(), hp.data(), q_off.data(), n_w, 1, plain.data(), stats.data());
     if (rc != 0) fail("search");

@@ -789,6 +789,45 @@ int hpfw_gpu_search_topk_transposed_scored_device(hpfw_gpu *h, const uint64_t *d
                                                   void *stream);
 int hpfw_gpu_search_topk_transposed_scored(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
                                            int k, hpfw_shift_hit *out, hpfw_dist_stats *stats);
+
+/* ---- search within sets of clips: every query names the set of clips it may be answered with.
+ *
+ * Arguments.  A call brings n_sets >= 0 sets in CSR form and a set per query, all on the host:
+ *   set_off [n_sets + 1], set_off[0] = 0, not decreasing;
+ *   set_clips [set_off[n_sets]]: the clips of set s are set_clips[set_off[s] .. set_off[s + 1]), indexes in add order (without
+ *     clip_base), STRICTLY ASCENDING inside a set.  A clip may be in many sets, a set may be empty;
+ *   q_set [n_q]: the set of each query, or -1 for "the whole index".
+ * Equality with the sub-index.  Query q with s = q_set[q] >= 0 is answered exactly as hpfw_gpu_search_topk would answer it on
+ * an index that holds only the clips of set s, in that order, with the clip ids mapped back to this index's (clip_base added
+ * as in hpfw_hit): the order (dist, clip), the offsets, the padding records past the set's size and the rule for clips
+ * shorter than the query (storage.h:37-39) are the sub-index's.  Strict ascent is what makes the sub-index's tie order by
+ * clip id this index's.  With stats (may be NULL) the same holds for hpfw_gpu_search_topk_scored: the moments are those of
+ * the counted clips of the set (n_c >= k_q >= 1).  A set may name an emptied slot (a removed recording, hpfw_gpu_index_remove):
+ * it behaves as an empty clip of the sub-index does.  A query with q_set = -1 gets the bytes of the unrestricted call.
+ * Nothing floats on the device and nothing depends on the order workgroups run in.  The work is that of searching the
+ * sets: the scans are launched for the listed clips only and the table of a query is as wide as its set.
+ * The transposed forms: q_off [n_q n_shifts + 1] and stats [n_q][n_shifts] as hpfw_gpu_search_topk_transposed_scored takes
+ * them, q_set [n_q] with one entry per query (for all its variants); shift_index is the sub-index's.
+ * Refused with HPFW_E_INVALID before a device is touched: n_sets < 0, null set_off with n_sets > 0, set_off[0] != 0, a
+ * decreasing set_off, a set that is not strictly ascending or holds a negative clip, null q_set, a q_set entry below -1 or
+ * at or above n_sets, and everything the unrestricted call refuses.  Refused once the index is known, before a kernel runs:
+ * a clip at or above the number of slots (HPFW_E_INVALID); with stats, n k_max^2 4096 >= 2^64 (HPFW_E_UNSUPPORTED), n the
+ * largest set a query names (the index for a -1 query).  The set arrays have been read when the call returns (the device
+ * forms wait for the stream when a query is restricted). */
+int hpfw_gpu_search_topk_within_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k,
+                                       const int64_t *set_off, int64_t n_sets, const int32_t *set_clips, const int32_t *q_set,
+                                       hpfw_hit *d_out, hpfw_dist_stats *d_stats, void *stream);
+int hpfw_gpu_search_topk_within(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int k,
+                                const int64_t *set_off, int64_t n_sets, const int32_t *set_clips, const int32_t *q_set,
+                                hpfw_hit *out, hpfw_dist_stats *stats);
+int hpfw_gpu_search_topk_transposed_within_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q,
+                                                  int n_shifts, int k, const int64_t *set_off, int64_t n_sets,
+                                                  const int32_t *set_clips, const int32_t *q_set, hpfw_shift_hit *d_out,
+                                                  hpfw_dist_stats *d_stats, void *stream);
+int hpfw_gpu_search_topk_transposed_within(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int n_shifts,
+                                           int k, const int64_t *set_off, int64_t n_sets, const int32_t *set_clips,
+                                           const int32_t *q_set, hpfw_shift_hit *out, hpfw_dist_stats *stats);
+
 /* Host only: how far a hit of distance `dist` stands out from the other counted clips of its row.  counted: whether the
  * hit's clip is counted (the caller knows the query's and the clip's lengths).  With n' = n - 1 the others have mean
  * m = (sum - d) / n' and variance var = (n' (sum_sq - d^2) - (sum - d)^2) / n'^2 (numerators in exact 128-bit integers,
