@@ -105,8 +105,11 @@ int main(int argc, char **argv)
             if (bad < 5) std::fprintf(stderr, "bin %ld: emu %.9g oracle %.9g\n", i / 2 + hp.kmin, got[i], ref[i]);
             ++bad;
         }
-    std::printf("n=%ld n1=%d n2=%d groups=%d gtw=%d values=%ld mismatches=%ld\n", n, hp.n1, hp.n2, a.groups.n, (int)hp.rows_gtw.size(),
-                2 * nk, bad);
+    std::string seq; // the plan's fused groups in order, "7x3,5x3,5x4"
+    for (int g = 0; g < a.groups.n; ++g)
+        seq += (g ? "," : "") + std::to_string(a.groups.r1[g]) + "x" + std::to_string(a.groups.r2[g]);
+    std::printf("n=%ld n1=%d n2=%d groups=%d gtw=%d values=%ld mismatches=%ld seq=%s\n", n, hp.n1, hp.n2, a.groups.n,
+                (int)hp.rows_gtw.size(), 2 * nk, bad, seq.c_str());
     hpfw_oracle_plan_destroy(op);
     return bad ? 1 : 0;
 }
