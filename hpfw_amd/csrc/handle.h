@@ -407,6 +407,15 @@ inline int64_t index_longest_clip(const hpfw_gpu *h)
     return n_max;
 }
 
+// Overlap search and joins (overlap_rule.h): a pair's lags come in chunks of 1024; with few pairs the chunks of a pair go
+// to `splits` workgroups, each with a table entry of its own -- enough for some 2048 workgroups, at most 64 a pair.
+// env_name: that many instead, for tests of either shape
+inline int64_t overlap_splits(int64_t chunks, int64_t pairs, const char *env_name)
+{
+    if (const char *e = std::getenv(env_name)) return std::min<int64_t>(std::max(std::atoi(e), 1), 64);
+    return std::min<int64_t>({chunks, (2048 + pairs - 1) / pairs, 64});
+}
+
 // plans.hip
 int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out);
 hipError_t init_plans(hpfw_gpu *h); // the table stream and event, HPFW_PLAN_TIMING (at the handle's creation)

@@ -18,6 +18,7 @@
 //   nothing), windows past the end of the clip are zeros, and k = min(k, n) (storage.h:37-39) falls
 //   out of that: a query longer than the clip meets zeros beyond n.
 #include "kernels.h"
+#include "overlap_rule.h"
 
 #include <algorithm>
 
@@ -25,9 +26,7 @@ namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSmThreads = 512;            // 8 waves
@@ -35,25 +34,7 @@ constexpr int kSmTiles = 4;                // offset tiles of 32 per wave
 constexpr int kSmWaveOffs = 32 * kSmTiles; // 128
 constexpr int kSmWgOffs = kSmWaveOffs * (kSmThreads / 64); // 1024 offsets per workgroup
 constexpr int kSmChunk = 16;               // positions j per staged chunk of the A operand (16 KB)
-
-// 8 bits -> 8 E2M1 nibbles, bit i in nibble i: 0 -> +1.0 (0x2), 1 -> -1.0 (0xA)
-__device__ __forceinline__ uint32_t expand8(uint32_t x)
-{
-    uint32_t t = (x | (x << 12)) & 0x000F000Fu;
-    t = (t | (t << 6)) & 0x03030303u;
-    t = (t | (t << 3)) & 0x11111111u;
-    return 0x22222222u | (t << 3);
-}
-
-__device__ __forceinline__ v4i expand32(uint32_t w)
-{
-    v4i r;
-    r.x = (int)expand8(w & 0xff);
-    r.y = (int)expand8((w >> 8) & 0xff);
-    r.z = (int)expand8((w >> 16) & 0xff);
-    r.w = (int)expand8(w >> 24);
-    return r;
-}
+// (expand32, 32 bits -> 32 E2M1 nibbles, bit i in nibble i, is overlap_rule.h's: the overlap search reads this file's image)
 
 // qa [n_groups][kt_pad][64 lanes][16 B]: lane (m, h) of step j holds bits [32 h, 32 h + 32) of
 // hashprint j of query 32 g + m, or zeros past the query's end / past the last query.

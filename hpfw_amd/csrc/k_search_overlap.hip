@@ -1,10 +1,9 @@
 // k_search_overlap.hip -- the overlap search (include/hpfw_gpu.h): a query may overhang either end of
 // a clip, and every alignment is rated by its mismatches per overlapping hashprint.
 //
-// Lag d puts query position j on clip position d + j.  Over the L(d) = min(k, n - d) - max(0, -d) positions both have,
-// dist(d) = sum popcount(q[j] ^ r[d + j]).  A lag with L >= min_overlap is a candidate; candidates are ordered by dist / L
-// as an exact rational (cross-multiplied: dist <= 64 L, L <= 16000, products below 2^34), then larger L, then smaller d.
-// No floating point takes part in the order.
+// The rule -- which lags are candidates and how they are ordered -- its comparison, a workgroup's best, the fold of the
+// splits, the expansion to fp4 and the end of a chunk on either route are in overlap_rule.h, shared with the joins
+// (k_selfjoin.hip).  This file instantiates OverlapSearchRule: dist <= 64 L, L <= 16000, 24-bit products below 2^34.
 //
 // (a) overlap_mfma_kernel is hamming_mfma_kernel (k_search_mfma.hip) with the clip's window zero-filled on both sides: with
 // hashprint bits as fp4 +-1 and fp4 0 outside the query and outside the clip, the accumulator of (query row, lag) is
@@ -17,14 +16,13 @@
 // round robin to `splits` workgroups, each of which owns its entry (no atomics, nothing depends on the order workgroups
 // run in).  overlap_select_kernel folds the splits and picks the k best clips per query.
 #include "kernels.h"
+#include "overlap_rule.h"
 
 namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int kOvThreads = 512;                          // 8 waves
@@ -33,60 +31,9 @@ constexpr int kOvWaveLags = 32 * kOvTiles;               // 128
 constexpr int kOvWgLags = kOvWaveLags * (kOvThreads / 64); // 1024 lags per chunk (kOverlapChunk)
 constexpr int kOvChunk = 16;                             // positions j per staged chunk of the A operand, as kSmChunk
 static_assert(kOvWgLags == kOverlapChunk, "kernels.h states the chunk");
-
-constexpr unsigned kNoDist = 1u << 21; // above every distance (64 * 16000 < 2^20); with L = 1 a rate above every rate
-constexpr unsigned kLMax = 16383;      // L <= 16000 < 2^14
-
-// 8 bits -> 8 E2M1 nibbles, bit i in nibble i: 0 -> +1.0 (0x2), 1 -> -1.0 (0xA)  (as k_search_mfma.hip)
-__device__ __forceinline__ uint32_t ov_expand8(uint32_t x)
-{
-    uint32_t t = (x | (x << 12)) & 0x000F000Fu;
-    t = (t | (t << 6)) & 0x03030303u;
-    t = (t | (t << 3)) & 0x11111111u;
-    return 0x22222222u | (t << 3);
-}
-
-__device__ __forceinline__ v4i ov_expand32(uint32_t w)
-{
-    v4i r;
-    r.x = (int)ov_expand8(w & 0xff);
-    r.y = (int)ov_expand8((w >> 8) & 0xff);
-    r.z = (int)ov_expand8((w >> 16) & 0xff);
-    r.w = (int)ov_expand8(w >> 24);
-    return r;
-}
-
-// dist1 / L1 against dist2 / L2: the operands are below 2^24, so the products are two 24-bit multiplies each
-__device__ __forceinline__ uint64_t ov_mul(unsigned a, unsigned b) { return (uint64_t)(a & 0xffffffu) * (uint64_t)(b & 0xffffffu); }
-
-// Inside a chunk a candidate is two words: dist, and w = (kLMax - L) << 10 | lag inside the chunk -- at equal rates the
-// smaller w has the larger L, then the smaller lag.  "none" is (kNoDist, L = 1).
-constexpr unsigned kNoW = ((kLMax - 1) << 10) | 0x3ffu;
-__device__ __forceinline__ bool ov_less(unsigned d1, unsigned w1, unsigned d2, unsigned w2)
-{
-    const uint64_t a = ov_mul(d1, kLMax - (w2 >> 10)), b = ov_mul(d2, kLMax - (w1 >> 10));
-    return a < b || (a == b && w1 < w2);
-}
-
-// a workgroup's best so far over the chunks it has done (in rising order of lag), in one thread per query row
-struct OvBest {
-    unsigned dist = kNoDist, L = 1;
-    int lag = 0;
-    // a candidate of a later chunk: a larger lag, so it wins on a smaller rate or, at the same rate, a larger L
-    __device__ void offer(unsigned d, unsigned l, int g)
-    {
-        const uint64_t a = ov_mul(d, L), b = ov_mul(dist, l);
-        if (a < b || (a == b && l > L)) {
-            dist = d;
-            L = l;
-            lag = g;
-        }
-    }
-    __device__ void store(uint4 *e) const
-    {
-        if (dist != kNoDist) *e = make_uint4(dist, L, (unsigned)lag, 0u);
-    }
-};
+using Rule = OverlapSearchRule;
+static_assert(kOverlapChunk == Rule::kChunk, "a candidate's lag inside the chunk takes 10 bits");
+constexpr unsigned kNoDist = Rule::kNoDist; // the "none" of OvPick below
 } // namespace
 
 struct OverlapArgs {
@@ -131,7 +78,7 @@ __global__ __launch_bounds__(kOvThreads, 4) void overlap_mfma_kernel(OverlapArgs
     const int n_chunks = (kt + kOvChunk - 1) / kOvChunk;
     const int one = 0x7f7f7f7f; // E8M0 scale 2^0
     const v4i *bp = ldsB + h * win + wave * kOvWaveLags + n_lane;
-    OvBest best; // (threads below 32)
+    Rule::Best best; // (threads below 32)
 
     for (int wc = split; wc < n_wg_chunks; wc += a.splits) {
         const int d0 = d_lo + wc * kOvWgLags;
@@ -142,8 +89,8 @@ __global__ __launch_bounds__(kOvThreads, 4) void overlap_mfma_kernel(OverlapArgs
             v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
             if (gi >= 0 && gi < n) {
                 const uint64_t w = a.db[r0 + gi];
-                lo = ov_expand32((uint32_t)w);
-                hi = ov_expand32((uint32_t)(w >> 32));
+                lo = expand32((uint32_t)w);
+                hi = expand32((uint32_t)(w >> 32));
             }
             ldsB[i] = lo;
             ldsB[win + i] = hi;
@@ -185,43 +132,8 @@ __global__ __launch_bounds__(kOvThreads, 4) void overlap_mfma_kernel(OverlapArgs
             __syncthreads();
         }
 
-        // acc[t][reg]: query row m = (reg & 3) + 8 (reg >> 2) + 4 h, lag d0 + wave 128 + t 32 + n_lane
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int m = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            const int k = kq_s[m];
-            unsigned bd = kNoDist, bw = kNoW;
-#pragma unroll
-            for (int t = 0; t < kOvTiles; ++t) {
-                const int lo = wave * kOvWaveLags + t * 32 + n_lane;
-                const int d = d0 + lo;
-                const int L = min(k, n - d) + min(0, d); // L >= min_overlap: min_overlap - k <= d <= n - min_overlap
-                const unsigned dist = (unsigned)((64 * L - (int)acc[t][reg]) >> 1);
-                const unsigned w = ((kLMax - (unsigned)L) << 10) | (unsigned)lo;
-                if (k > 0 && L >= mo && ov_less(dist, w, bd, bw)) {
-                    bd = dist;
-                    bw = w;
-                }
-            }
-#pragma unroll
-            for (int s = 16; s >= 1; s >>= 1) { // the best of the 32 lag columns of this half-wave
-                const unsigned od = (unsigned)__shfl_xor((int)bd, s), ow = (unsigned)__shfl_xor((int)bw, s);
-                if (ov_less(od, ow, bd, bw)) {
-                    bd = od;
-                    bw = ow;
-                }
-            }
-            if (n_lane == 0) red[wave * 32 + m] = make_uint2(bd, bw);
-        }
-        __syncthreads();
-        if (tid < 32) {
-            uint2 b = red[tid];
-            for (int w = 1; w < kOvThreads / 64; ++w) {
-                const uint2 o = red[w * 32 + tid];
-                if (ov_less(o.x, o.y, b.x, b.y)) b = o;
-            }
-            if (b.x != kNoDist) best.offer(b.x, kLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
-        }
+        // the chunk's candidates go over the A operand, the best of each query row to its thread's `best`
+        Rule::tile_epilogue(acc, kq_s, n, mo, d0, red, best, tid, wave, n_lane, h);
     }
     if (tid < 32 && g * 32 + tid < a.n_q)
         best.store(a.tab + ((int64_t)(g * 32 + tid) * a.n_clips + clip) * a.splits + split);
@@ -231,7 +143,7 @@ __global__ __launch_bounds__(kOvThreads, 4) void overlap_mfma_kernel(OverlapArgs
 __global__ __launch_bounds__(256) void overlap_popc_kernel(OverlapArgs a)
 {
     __shared__ uint2 red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int clip = blockIdx.x / a.splits, split = blockIdx.x - clip * a.splits, qi = blockIdx.y;
     const int64_t r0 = a.db_off[clip], q0 = a.q_off[qi];
     const int n = (int)(a.db_off[clip + 1] - r0), k = (int)(a.q_off[qi + 1] - q0), mo = a.min_overlap;
@@ -239,39 +151,10 @@ __global__ __launch_bounds__(256) void overlap_popc_kernel(OverlapArgs a)
     const uint64_t *q = a.q + q0, *r = a.db + r0;
     const int d_lo = mo - k, d_hi = n - mo;
     const int n_wg_chunks = (d_hi - d_lo) / kOvWgLags + 1;
-    OvBest best; // (thread 0)
+    Rule::Best best; // (thread 0)
     for (int wc = split; wc < n_wg_chunks; wc += a.splits) {
         const int d0 = d_lo + wc * kOvWgLags;
-        unsigned bd = kNoDist, bw = kNoW;
-        for (int e = 0; e < kOvWgLags / 256; ++e) {
-            const int lo = tid + 256 * e, d = d0 + lo;
-            if (d > d_hi) break;
-            const int j0 = max(0, -d), j1 = min(k, n - d); // d_lo <= d <= d_hi: j1 - j0 >= min_overlap
-            unsigned dist = 0;
-            for (int j = j0; j < j1; ++j) dist += (unsigned)__popcll(q[j] ^ r[d + j]);
-            const unsigned w = ((kLMax - (unsigned)(j1 - j0)) << 10) | (unsigned)lo;
-            if (ov_less(dist, w, bd, bw)) {
-                bd = dist;
-                bw = w;
-            }
-        }
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-            const unsigned od = (unsigned)__shfl_xor((int)bd, s), ow = (unsigned)__shfl_xor((int)bw, s);
-            if (ov_less(od, ow, bd, bw)) {
-                bd = od;
-                bw = ow;
-            }
-        }
-        __syncthreads(); // (the chunk before has been read)
-        if (lane == 0) red[wave] = make_uint2(bd, bw);
-        __syncthreads();
-        if (tid == 0) {
-            uint2 b = red[0];
-            for (int w = 1; w < 4; ++w)
-                if (ov_less(red[w].x, red[w].y, b.x, b.y)) b = red[w];
-            if (b.x != kNoDist) best.offer(b.x, kLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
-        }
+        Rule::popc_chunk<false>(q, k, r, n, mo, d0, d_hi, red, best, tid); // d_lo <= d <= d_hi: every lag overlaps min_overlap
     }
     if (tid == 0) best.store(a.tab + ((int64_t)qi * a.n_clips + clip) * a.splits + split);
 }
@@ -289,7 +172,7 @@ struct OvPick {
 };
 __device__ __forceinline__ bool ov_pick_less(const OvPick &x, const OvPick &y)
 {
-    const uint64_t a = ov_mul(x.dist, y.L), b = ov_mul(y.dist, x.L);
+    const uint64_t a = Rule::mul(x.dist, y.L), b = Rule::mul(y.dist, x.L);
     return a < b || (a == b && (x.L > y.L || (x.L == y.L && x.clip < y.clip)));
 }
 } // namespace
@@ -307,12 +190,7 @@ __global__ __launch_bounds__(256) void overlap_select_kernel(uint4 *__restrict__
     if (splits > 1) {
         for (int c = tid; c < n_clips; c += 256) {
             uint4 b = row[(int64_t)c * splits];
-            for (int s = 1; s < splits; ++s) {
-                const uint4 e = row[(int64_t)c * splits + s];
-                if (e.x == 0xffffffffu) continue;
-                const uint64_t x = ov_mul(e.x, b.y), y = ov_mul(b.x, e.y);
-                if (b.x == 0xffffffffu || x < y || (x == y && (e.y > b.y || (e.y == b.y && (int)e.z < (int)b.z)))) b = e;
-            }
+            for (int s = 1; s < splits; ++s) Rule::fold(b, row[(int64_t)c * splits + s]);
             row[(int64_t)c * splits] = b;
         }
         __syncthreads();
@@ -324,7 +202,7 @@ __global__ __launch_bounds__(256) void overlap_select_kernel(uint4 *__restrict__
         if (r == 0 || prev.dist != kNoDist) {
             for (int c = tid; c < n_clips; c += 256) {
                 const uint4 e = row[(int64_t)c * splits];
-                if (e.x == 0xffffffffu || c == ex) continue;
+                if (overlap_no_entry(e) || c == ex) continue;
                 const OvPick p = {e.x, e.y, (unsigned)c};
                 if ((r == 0 || ov_pick_less(prev, p)) && ov_pick_less(p, mine)) mine = p;
             }

@@ -2,10 +2,12 @@
 // of a against b by the overlap rule of section 17, and every pair under the caller's threshold.
 //
 // Clip a takes the query's part and b the clip's: lag d puts position j of a on position d + j of b, L(d) =
-// min(n_a, n_b - d) - max(0, -d), dist(d) = sum popcount(a[j] ^ b[d + j]); candidates with L >= min_overlap are ordered by
-// dist / L as an exact rational (cross-multiplied in 64 bits: dist <= 2^24, L < 2^18), then larger L, then smaller d.
+// min(n_a, n_b - d) - max(0, -d), dist(d) = sum popcount(a[j] ^ b[d + j]).  The rule, its comparison, a workgroup's best,
+// the fold of the splits, the threshold test, the expansion to fp4 and the end of a chunk on either route are in
+// overlap_rule.h, shared with the overlap search; this file instantiates JoinRule (dist <= 2^24, L < 2^18: full 64-bit
+// products) and keeps what is its own: the pairs, the staging and the multiply loop.
 //
-// (a) selfjoin_mfma_kernel descends from overlap_mfma_kernel (k_search_overlap.hip): a workgroup = 32 rows (clips a of one
+// (a) selfjoin_mfma_kernel has overlap_mfma_kernel's geometry (k_search_overlap.hip): a workgroup = 32 rows (clips a of one
 // row group) x 1024 lags of one b per chunk, fp4 +-1 operands, fp4 0 outside either recording, accumulator 64 L - 2 dist.
 // Both operands are read from the index where it lies and expanded while they are staged.  The rows are walked in SLICES of
 // kSjSlice positions: per slice the 32 rows' hashprints and the kSjChunk + kSjSlice positions of b that the chunk's lags put
@@ -24,14 +26,13 @@
 // the index or in the caller's buffer, and the table's columns are the externals.  Both scan kernels are templates over
 // their arguments; what differs is in sj_clip, sj_ptr, sj_hp, sj_first_b, sj_row_end and sj_entry.
 #include "kernels.h"
+#include "overlap_rule.h"
 
 namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int kSjThreads = 512;                            // 8 waves
@@ -41,67 +42,9 @@ constexpr int kSjWin = kSelfjoinChunk + kSelfjoinSlice;    // positions of b sta
 constexpr int kSjBLoads = (kSjWin + kSjThreads - 1) / kSjThreads; // positions of b per thread and slice
 static_assert(kSjWaveLags * (kSjThreads / 64) == kSelfjoinChunk, "kernels.h states the chunk");
 static_assert(kSelfjoinSlice == 32 && kSjThreads == 512, "stage_a deals 32 positions x 32 rows to 512 threads, two each");
-static_assert(kSelfjoinChunk == 1024, "a candidate's lag inside the chunk takes 10 bits");
+static_assert(kSelfjoinChunk == JoinRule::kChunk, "a candidate's lag inside the chunk takes 10 bits");
 
-constexpr unsigned kSjNoDist = 1u << 25;                   // above every distance (64 L <= 2^24); with L = 1 above every rate
-constexpr unsigned kSjLMax = (unsigned)kSelfjoinMaxLen;    // 2^18 - 1
-
-// 8 bits -> 8 E2M1 nibbles, bit i in nibble i: 0 -> +1.0 (0x2), 1 -> -1.0 (0xA)  (as k_search_mfma.hip)
-__device__ __forceinline__ uint32_t sj_expand8(uint32_t x)
-{
-    uint32_t t = (x | (x << 12)) & 0x000F000Fu;
-    t = (t | (t << 6)) & 0x03030303u;
-    t = (t | (t << 3)) & 0x11111111u;
-    return 0x22222222u | (t << 3);
-}
-
-__device__ __forceinline__ v4i sj_expand32(uint32_t w)
-{
-    v4i r;
-    r.x = (int)sj_expand8(w & 0xff);
-    r.y = (int)sj_expand8((w >> 8) & 0xff);
-    r.z = (int)sj_expand8((w >> 16) & 0xff);
-    r.w = (int)sj_expand8(w >> 24);
-    return r;
-}
-
-// dist1 / L1 against dist2 / L2: dist <= 2^24 and L < 2^18, so the products are below 2^42
-__device__ __forceinline__ uint64_t sj_mul(unsigned a, unsigned b) { return (uint64_t)a * (uint64_t)b; }
-
-// Inside a chunk a candidate is two words: dist, and w = (kSjLMax - L) << 10 | lag inside the chunk (28 bits) -- at equal
-// rates the smaller w has the larger L, then the smaller lag.  "none" is (kSjNoDist, L = 1).
-constexpr unsigned kSjNoW = ((kSjLMax - 1) << 10) | 0x3ffu;
-__device__ __forceinline__ bool sj_less(unsigned d1, unsigned w1, unsigned d2, unsigned w2)
-{
-    const uint64_t a = sj_mul(d1, kSjLMax - (w2 >> 10)), b = sj_mul(d2, kSjLMax - (w1 >> 10));
-    return a < b || (a == b && w1 < w2);
-}
-
-// a workgroup's best of one row over the chunks it has done (in rising order of lag)
-struct SjBest {
-    unsigned dist = kSjNoDist, L = 1;
-    int lag = 0;
-    // a candidate of a later chunk: a larger lag, so it wins on a smaller rate or, at the same rate, a larger L
-    __device__ void offer(unsigned d, unsigned l, int g)
-    {
-        const uint64_t a = sj_mul(d, L), b = sj_mul(dist, l);
-        if (a < b || (a == b && l > L)) {
-            dist = d;
-            L = l;
-            lag = g;
-        }
-    }
-    __device__ void store(uint4 *e) const
-    {
-        if (dist != kSjNoDist) *e = make_uint4(dist, L, (unsigned)lag, 0u);
-    }
-};
-
-// dist / L at or below rate_num / rate_den: dist rate_den <= 2^34, rate_num L < 2^34
-__device__ __forceinline__ bool sj_reported(const uint4 &e, unsigned rate_num, unsigned rate_den)
-{
-    return e.x != 0xffffffffu && sj_mul(e.x, rate_den) <= sj_mul(rate_num, e.y);
-}
+using Rule = JoinRule;
 } // namespace
 
 struct SelfjoinArgs {
@@ -256,7 +199,7 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(Args a)
     const int one = 0x7f7f7f7f; // E8M0 scale 2^0
     const v4i *bp = ldsB + h * kSjWin + wave * kSjWaveLags + n_lane;
     const v4i *ap = ldsA + lane;
-    SjBest best; // (threads below 32)
+    Rule::Best best; // (threads below 32)
 
     for (int wc = p.split; wc < n_wg_chunks; wc += a.splits) {
         const int d0 = d_lo + wc * kSelfjoinChunk;
@@ -299,16 +242,16 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(Args a)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const bool v = (ok >> e) & 1u;
-                ldsA[ja[e] * 64 + ma[e]] = v ? sj_expand32((uint32_t)ra[e]) : zero;
-                ldsA[ja[e] * 64 + 32 + ma[e]] = v ? sj_expand32((uint32_t)(ra[e] >> 32)) : zero;
+                ldsA[ja[e] * 64 + ma[e]] = v ? expand32((uint32_t)ra[e]) : zero;
+                ldsA[ja[e] * 64 + 32 + ma[e]] = v ? expand32((uint32_t)(ra[e] >> 32)) : zero;
             }
 #pragma unroll
             for (int e = 0; e < kSjBLoads; ++e) {
                 const int i = tid + kSjThreads * e;
                 if (i < kSjWin) {
                     const bool v = (ok >> (2 + e)) & 1u;
-                    ldsB[i] = v ? sj_expand32((uint32_t)rb[e]) : zero;
-                    ldsB[kSjWin + i] = v ? sj_expand32((uint32_t)(rb[e] >> 32)) : zero;
+                    ldsB[i] = v ? expand32((uint32_t)rb[e]) : zero;
+                    ldsB[kSjWin + i] = v ? expand32((uint32_t)(rb[e] >> 32)) : zero;
                 }
             }
             __syncthreads();
@@ -327,43 +270,7 @@ __global__ __launch_bounds__(kSjThreads, 4) void selfjoin_mfma_kernel(Args a)
         }
         __syncthreads(); // the last slice has been read: the candidates go over the A operand
 
-        // acc[t][reg]: row m = (reg & 3) + 8 (reg >> 2) + 4 h, lag d0 + wave 128 + t 32 + n_lane
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int m = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            const int k = lens[m];
-            unsigned bd = kSjNoDist, bw = kSjNoW;
-#pragma unroll
-            for (int t = 0; t < kSjTiles; ++t) {
-                const int lo = wave * kSjWaveLags + t * 32 + n_lane;
-                const int d = d0 + lo;
-                const int L = min(k, n - d) + min(0, d);
-                const unsigned dist = (unsigned)((64 * L - (int)acc[t][reg]) >> 1);
-                const unsigned w = ((kSjLMax - (unsigned)L) << 10) | (unsigned)lo;
-                if (k > 0 && L >= mo && sj_less(dist, w, bd, bw)) {
-                    bd = dist;
-                    bw = w;
-                }
-            }
-#pragma unroll
-            for (int s = 16; s >= 1; s >>= 1) { // the best of the 32 lag columns of this half-wave
-                const unsigned od = (unsigned)__shfl_xor((int)bd, s), ow = (unsigned)__shfl_xor((int)bw, s);
-                if (sj_less(od, ow, bd, bw)) {
-                    bd = od;
-                    bw = ow;
-                }
-            }
-            if (n_lane == 0) red[wave * 32 + m] = make_uint2(bd, bw);
-        }
-        __syncthreads();
-        if (tid < 32) {
-            uint2 b = red[tid];
-            for (int w = 1; w < kSjThreads / 64; ++w) {
-                const uint2 o = red[w * 32 + tid];
-                if (sj_less(o.x, o.y, b.x, b.y)) b = o;
-            }
-            if (b.x != kSjNoDist) best.offer(b.x, kSjLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
-        }
+        Rule::tile_epilogue(acc, lens, n, mo, d0, red, best, tid, wave, n_lane, h);
     }
     if (tid < 32 && lens[tid] > 0)
         best.store(sj_entry(a, 32 * p.gi + tid, p.b, p.split));
@@ -377,7 +284,7 @@ __global__ __launch_bounds__(256) void selfjoin_popc_kernel(Args a)
     __shared__ uint2 red[4];
     __shared__ int lens[32];
     __shared__ int64_t starts[32];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const SjPair p = sj_pair(a, lens, starts);
     int n;
     const int64_t r0 = sj_clip(a, p.b, n);
@@ -390,41 +297,9 @@ __global__ __launch_bounds__(256) void selfjoin_popc_kernel(Args a)
         const int k = lens[m];
         if (k == 0) continue;
         const uint64_t *q = sj_ptr(a, starts[m]);
-        SjBest best; // (thread 0)
-        for (int wc = p.split; wc < n_wg_chunks; wc += a.splits) {
-            const int d0 = d_lo + wc * kSelfjoinChunk;
-            unsigned bd = kSjNoDist, bw = kSjNoW;
-            for (int e = 0; e < kSelfjoinChunk / 256; ++e) {
-                const int lo = tid + 256 * e, d = d0 + lo;
-                if (d > d_hi) break;
-                const int j0 = max(0, -d), j1 = min(k, n - d);
-                if (j1 - j0 < mo) continue; // (a row shorter than the group's longest)
-                unsigned dist = 0;
-                for (int j = j0; j < j1; ++j) dist += (unsigned)__popcll(q[j] ^ r[d + j]);
-                const unsigned w = ((kSjLMax - (unsigned)(j1 - j0)) << 10) | (unsigned)lo;
-                if (sj_less(dist, w, bd, bw)) {
-                    bd = dist;
-                    bw = w;
-                }
-            }
-#pragma unroll
-            for (int s = 32; s >= 1; s >>= 1) {
-                const unsigned od = (unsigned)__shfl_xor((int)bd, s), ow = (unsigned)__shfl_xor((int)bw, s);
-                if (sj_less(od, ow, bd, bw)) {
-                    bd = od;
-                    bw = ow;
-                }
-            }
-            __syncthreads(); // (the chunk before has been read)
-            if (lane == 0) red[wave] = make_uint2(bd, bw);
-            __syncthreads();
-            if (tid == 0) {
-                uint2 b = red[0];
-                for (int w = 1; w < 4; ++w)
-                    if (sj_less(red[w].x, red[w].y, b.x, b.y)) b = red[w];
-                if (b.x != kSjNoDist) best.offer(b.x, kSjLMax - (b.y >> 10), d0 + (int)(b.y & 0x3ffu));
-            }
-        }
+        Rule::Best best; // (thread 0)
+        for (int wc = p.split; wc < n_wg_chunks; wc += a.splits) // (true: a row shorter than the group's longest)
+            Rule::popc_chunk<true>(q, k, r, n, mo, d_lo + wc * kSelfjoinChunk, d_hi, red, best, tid);
         if (tid == 0) best.store(sj_entry(a, 32 * p.gi + m, p.b, p.split));
     }
 }
@@ -441,14 +316,9 @@ __global__ __launch_bounds__(256) void selfjoin_count_kernel(uint4 *__restrict__
     int cnt = 0;
     for (int c = max(row0 + (int)blockIdx.x + 1 - col0, 0) + tid; c < n_cols; c += 256) {
         uint4 b = row[(int64_t)c * splits];
-        for (int s = 1; s < splits; ++s) {
-            const uint4 e = row[(int64_t)c * splits + s];
-            if (e.x == 0xffffffffu) continue;
-            const uint64_t x = sj_mul(e.x, b.y), y = sj_mul(b.x, e.y);
-            if (b.x == 0xffffffffu || x < y || (x == y && (e.y > b.y || (e.y == b.y && (int)e.z < (int)b.z)))) b = e;
-        }
+        for (int s = 1; s < splits; ++s) Rule::fold(b, row[(int64_t)c * splits + s]);
         if (splits > 1) row[(int64_t)c * splits] = b;
-        cnt += sj_reported(b, rate_num, rate_den) ? 1 : 0;
+        cnt += Rule::reported(b, rate_num, rate_den) ? 1 : 0;
     }
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) cnt += __shfl_xor(cnt, s);
@@ -505,9 +375,9 @@ __global__ __launch_bounds__(256) void selfjoin_write_kernel(const uint4 *__rest
     int64_t at = row_first[blockIdx.x];
     for (int c0 = max(a + 1 - col0, 0); c0 < n_cols && at < cap; c0 += 256) {
         const int c = c0 + tid;
-        uint4 e = make_uint4(0xffffffffu, 0u, 0u, 0u);
+        uint4 e = make_uint4(kOverlapNoEntry, 0u, 0u, 0u);
         if (c < n_cols) e = row[(int64_t)c * splits];
-        const bool rep = sj_reported(e, rate_num, rate_den);
+        const bool rep = Rule::reported(e, rate_num, rate_den);
         const unsigned long long mask = __ballot(rep);
         __syncthreads(); // (the block of 256 before has been read)
         if (lane == 0) wave_n[wave] = __popcll(mask);

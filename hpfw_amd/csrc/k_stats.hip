@@ -13,6 +13,7 @@
 // reduced over the wave by shuffles, over the workgroup through LDS, and thread 0 adds the slice to the row with vector
 // atomics on the 64-bit words (the row is zeroed by the host before the launch).
 #include "kernels.h"
+#include "overlap_rule.h"
 
 namespace hpfw {
 
@@ -30,28 +31,11 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-// SET: column c of the table is slot set[c] of db_off (search within a set, DESIGN.md section 24)
-template <bool SET>
-__global__ __launch_bounds__(kStThreads) void dist_stats_kernel(const uint64_t *__restrict__ best, const int64_t *__restrict__ db_off,
-                                                                const int64_t *__restrict__ q_off, int n_clips, int per,
-                                                                const int32_t *__restrict__ set, DistStatsDev *__restrict__ stats)
+// the threads' moments summed over the workgroup (wave shuffles, then LDS) and added to row q by thread 0
+__device__ __forceinline__ void add_moments(unsigned long long n, unsigned long long sum, unsigned long long sum_sq, DistStatsDev *stats, int q)
 {
     __shared__ unsigned long long red[3][kStThreads / 64];
-    const int tid = threadIdx.x, q = blockIdx.x;
-    const int64_t kq = q_off[q + 1] - q_off[q];
-    if (kq < 1) return; // an empty query counts nothing (uniform over the workgroup)
-    const int c0 = blockIdx.y * per, c1 = min(n_clips, c0 + per);
-    const uint64_t *row = best + (int64_t)q * n_clips;
-    unsigned long long n = 0, sum = 0, sum_sq = 0;
-    for (int c = c0 + tid; c < c1; c += kStThreads) {
-        int len;
-        (void)clip_span<SET>(db_off, set, c, len);
-        if (len < kq) continue;
-        const unsigned long long d = row[c] >> 32;
-        n += 1;
-        sum += d;
-        sum_sq += d * d;
-    }
+    const int tid = threadIdx.x;
     n = wave_sum_u64(n);
     sum = wave_sum_u64(sum);
     sum_sq = wave_sum_u64(sum_sq);
@@ -75,6 +59,30 @@ __global__ __launch_bounds__(kStThreads) void dist_stats_kernel(const uint64_t *
     }
 }
 
+// SET: column c of the table is slot set[c] of db_off (search within a set, DESIGN.md section 24)
+template <bool SET>
+__global__ __launch_bounds__(kStThreads) void dist_stats_kernel(const uint64_t *__restrict__ best, const int64_t *__restrict__ db_off,
+                                                                const int64_t *__restrict__ q_off, int n_clips, int per,
+                                                                const int32_t *__restrict__ set, DistStatsDev *__restrict__ stats)
+{
+    const int tid = threadIdx.x, q = blockIdx.x;
+    const int64_t kq = q_off[q + 1] - q_off[q];
+    if (kq < 1) return; // an empty query counts nothing (uniform over the workgroup)
+    const int c0 = blockIdx.y * per, c1 = min(n_clips, c0 + per);
+    const uint64_t *row = best + (int64_t)q * n_clips;
+    unsigned long long n = 0, sum = 0, sum_sq = 0;
+    for (int c = c0 + tid; c < c1; c += kStThreads) {
+        int len;
+        (void)clip_span<SET>(db_off, set, c, len);
+        if (len < kq) continue;
+        const unsigned long long d = row[c] >> 32;
+        n += 1;
+        sum += d;
+        sum_sq += d * d;
+    }
+    add_moments(n, sum, sum_sq, stats, q);
+}
+
 // The scored overlap search's second reader: the table of k_search_overlap.hip after
 // overlap_select_kernel has folded a clip's splits into its first entry {dist, L, lag, 0}.  Per query row the moments of
 // rate = floor(dist 2^10 / L) over the clips that have a candidate and are not the row's excluded clip.  dist <= 64 L and
@@ -84,7 +92,6 @@ __global__ __launch_bounds__(kStThreads) void overlap_stats_kernel(const uint4 *
                                                                    const int32_t *__restrict__ exclude, int per,
                                                                    DistStatsDev *__restrict__ stats)
 {
-    __shared__ unsigned long long red[3][kStThreads / 64];
     const int tid = threadIdx.x, q = blockIdx.x;
     const int c0 = blockIdx.y * per, c1 = min(n_clips, c0 + per);
     const uint4 *row = tab + (int64_t)q * n_clips * splits;
@@ -92,33 +99,13 @@ __global__ __launch_bounds__(kStThreads) void overlap_stats_kernel(const uint4 *
     unsigned long long n = 0, sum = 0, sum_sq = 0;
     for (int c = c0 + tid; c < c1; c += kStThreads) {
         const uint4 e = row[(int64_t)c * splits];
-        if (e.x == 0xffffffffu || c == ex) continue; // no candidate (every byte still 0xff), or left out
+        if (overlap_no_entry(e) || c == ex) continue; // no candidate, or left out
         const unsigned long long r = (e.x << kOverlapRateBits) / e.y;
         n += 1;
         sum += r;
         sum_sq += r * r;
     }
-    n = wave_sum_u64(n);
-    sum = wave_sum_u64(sum);
-    sum_sq = wave_sum_u64(sum_sq);
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = n;
-        red[1][tid >> 6] = sum;
-        red[2][tid >> 6] = sum_sq;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < kStThreads / 64; ++w) {
-            n += red[0][w];
-            sum += red[1][w];
-            sum_sq += red[2][w];
-        }
-        if (n) {
-            atomicAdd(&stats[q].sum, sum);
-            atomicAdd(&stats[q].sum_sq, sum_sq);
-            atomicAdd(&stats[q].n, (uint32_t)n);
-        }
-    }
+    add_moments(n, sum, sum_sq, stats, q);
 }
 
 void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, void *d_stats, hipStream_t s)

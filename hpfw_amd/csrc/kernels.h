@@ -400,6 +400,10 @@ void launch_topk_two_step(const uint64_t *d_best, int n_q, int n_clips, int k, u
 // rated by dist / overlap.  d_tab [n_q][n_clips][splits] of 16-byte entries {dist, overlap, lag, 0}, every byte preset to
 // 0xff; a clip's chunks of kOverlapChunk lags are dealt round robin to its `splits` workgroups.
 constexpr int kOverlapChunk = 1024;
+// the rule on the device (overlap_rule.h: overlap of at most LMAX, "none" at dist NODIST, 24-bit products or full ones)
+template <unsigned LMAX, unsigned NODIST, bool MUL24>
+struct OverlapRule;
+using OverlapSearchRule = OverlapRule<16383, 1u << 21, true>; // L <= 16000 < 2^14, dist <= 64 * 16000 < 2^20
 // the matrix-core scan: d_qa the image of launch_expand_queries, d_gk [group] the longest query of each group of 32,
 // k_max the longest query of the call (hamming_mfma_lds_bytes(k_max) <= 160 KB)
 void launch_overlap_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const int64_t *d_q_off, int n_q, const void *d_qa,
@@ -425,6 +429,7 @@ void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, c
 constexpr int kSelfjoinChunk = 1024;
 constexpr int kSelfjoinSlice = 32;
 constexpr int kSelfjoinMaxLen = (1 << 18) - 1; // hashprints of a recording: 64 L < 2^24 keeps the fp32 accumulators exact
+using JoinRule = OverlapRule<(unsigned)kSelfjoinMaxLen, 1u << 25, false>; // dist <= 64 L < 2^24: products below 2^42
 void launch_selfjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups,
                           const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits, void *d_tab, hipStream_t s);
 // folds the splits (in d_tab), counts the pairs of rows row0 .. row0 + n_rows - 1 with dist rate_den <= rate_num overlap into

@@ -630,6 +630,15 @@ static int overlap_check(const void *h, const int64_t *q_off, int64_t n_q, const
     return 0;
 }
 
+// what overlap_check leaves to the handle: the clips that `exclude` names exist
+static int overlap_check_exclude(const hpfw_gpu *h, const int32_t *exclude, int64_t n_q)
+{
+    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
+    for (int64_t i = 0; exclude && i < n_q; ++i)
+        if (exclude[i] >= n_clips) return fail(HPFW_E_INVALID, "exclude: an entry at or above the number of clips (query " + std::to_string(i) + ")");
+    return 0;
+}
+
 // d_stats: NULL, or [n_q] rows that receive the moments of the per-clip rates (k_stats.hip: one more reader of the table)
 static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, const int32_t *exclude,
                                  int min_overlap, int k, hpfw_overlap_hit *d_out, hpfw_dist_stats *d_stats, hipStream_t s)
@@ -637,9 +646,8 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
     int64_t k_max = 0;
     if (int rc = overlap_check(h, q_off, n_q, exclude, min_overlap, k, d_out, &k_max)) return rc;
     if (n_q > 0 && !d_q_hp) return fail(HPFW_E_INVALID, "null queries");
+    if (int rc = overlap_check_exclude(h, exclude, n_q)) return rc;
     const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
-    for (int64_t i = 0; exclude && i < n_q; ++i)
-        if (exclude[i] >= n_clips) return fail(HPFW_E_INVALID, "exclude: an entry at or above the number of clips (query " + std::to_string(i) + ")");
     HIP_TRY(hipSetDevice(h->device));
     return ordered_call(h, s, [&] {
         if (n_q == 0) return 0;
@@ -661,12 +669,10 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
         // HPFW_OVERLAP_POPC asks for the xor/popcount kernel.
         const bool mfma = !std::getenv("HPFW_OVERLAP_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024;
         const int64_t n_max = index_longest_clip(h);
-        // A clip's lags come in chunks of 1024; with few (group, clip) pairs the chunks of a clip go to `splits` workgroups,
-        // each with an entry of its own (HPFW_OVERLAP_SPLITS: that many, for tests of either shape)
+        // the chunks of a (group, clip) pair go to `splits` workgroups
         const int64_t chunks = std::max<int64_t>((n_max + k_max - 2 * min_overlap) / hpfw::kOverlapChunk + 1, 1);
         const int64_t pairs = n_clips * (mfma ? (n_q + 31) / 32 : n_q);
-        int64_t splits = std::min<int64_t>({chunks, (2048 + pairs - 1) / pairs, 64});
-        if (const char *e = std::getenv("HPFW_OVERLAP_SPLITS")) splits = std::min<int64_t>(std::max(std::atoi(e), 1), 64);
+        const int64_t splits = overlap_splits(chunks, pairs, "HPFW_OVERLAP_SPLITS");
         // queries are processed in groups so the table stays below 1 GiB
         int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 26) / (n_clips * splits) / 32 * 32);
         qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
@@ -736,9 +742,7 @@ static int search_overlap_host(hpfw_gpu *h, const uint64_t *q_hp, const int64_t 
     int64_t k_max = 0;
     if (int rc = overlap_check(h, q_off, n_q, exclude, min_overlap, k, out, &k_max)) return rc;
     if (n_q > 0 && q_off[n_q] > q_off[0] && !q_hp) return fail(HPFW_E_INVALID, "null queries");
-    const int64_t n_clips = (int64_t)h->index.db_off.size() - 1;
-    for (int64_t i = 0; exclude && i < n_q; ++i)
-        if (exclude[i] >= n_clips) return fail(HPFW_E_INVALID, "exclude: an entry at or above the number of clips (query " + std::to_string(i) + ")");
+    if (int rc = overlap_check_exclude(h, exclude, n_q)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     if (n_q == 0) return 0;
     return search_round_trip_scored(q_hp, q_off, n_q, n_q * k, out, stats ? n_q : 0, stats,

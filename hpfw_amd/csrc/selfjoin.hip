@@ -68,11 +68,9 @@ static int join_passes(hpfw_gpu *h, hipStream_t s, const JoinSide *x, int min_ov
     int64_t pairs = 0;
     for (int64_t g = 0; g < n_groups; ++g) pairs += group_pairs(g);
     if (pairs == 0) return 0; // (an empty index joined without among_new)
-    // A pair's lags come in chunks of 1024; with few pairs the chunks of a pair go to `splits` workgroups, each with an
-    // entry of its own (HPFW_SELFJOIN_SPLITS: that many, for tests of either shape)
+    // the chunks of a pair go to `splits` workgroups
     const int64_t chunks = (2 * n_max - 2 * min_overlap) / hpfw::kSelfjoinChunk + 1;
-    int64_t splits = std::min<int64_t>({chunks, (2048 + pairs - 1) / pairs, 64});
-    if (const char *e = std::getenv("HPFW_SELFJOIN_SPLITS")) splits = std::min<int64_t>(std::max(std::atoi(e), 1), 64);
+    int64_t splits = overlap_splits(chunks, pairs, "HPFW_SELFJOIN_SPLITS");
     // row groups are processed in passes so that the table stays at or below 1 GiB (2^26 entries; HPFW_SELFJOIN_TABLE_KB:
     // that many KiB, at least one row group's, for tests of more than one pass)
     int64_t budget = (int64_t)1 << 26;
