@@ -25,6 +25,11 @@ DTW_HIT_DTYPE = np.dtype([("dist", "<u4"), ("clip", "<u4"), ("start", "<i4"), ("
 DTW_MAX_PATH_CELLS = 1 << 31                             # the path call's cap on K n
 # the pairs kernel: a lane holds DTW_STRIP columns, a wave's pass DTW_BLOCK; a wider clip runs in blocks (hpfw_gpu_dtw_geometry)
 DTW_STRIP, DTW_BLOCK = 8, 512
+# hpfw_local_hit: a hit of the local search; padding: clip = 0xffffffff, the rest 0
+LOCAL_HIT_DTYPE = np.dtype([("score", "<i4"), ("clip", "<u4"), ("lag", "<i4"), ("q_start", "<u4"), ("length", "<u4"), ("dist", "<u4")])
+# a clip's lags 1 - k .. n - 1 are scanned in chunks of this many, the first at 1 - (the query's length; on the matrix cores the
+# longest of its group of 32) -- kLocalChunk of csrc/kernels.h, for tests that plant passages on the seams
+LOCAL_CHUNK = 1024
 # hpfw_index_move: a piece of the plan of a removal from the index
 # hpfw_dup_pair: a pair of the catalogue self-join: clips a < b, position 0 of a on position lag of b
 DUP_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("dist", "<u4"), ("overlap", "<u4"), ("lag", "<i4"), ("pad", "<u4")])
@@ -104,6 +109,7 @@ EXPORTS = (
     "hpfw_gpu_knn_windows_device", "hpfw_gpu_vote_windows_device", "hpfw_gpu_search_votes_device", "hpfw_gpu_merge_knn_device",
     "hpfw_gpu_dtw_pairs_device", "hpfw_gpu_dtw_pairs", "hpfw_gpu_search_dtw_device", "hpfw_gpu_search_dtw",
     "hpfw_gpu_dtw_path_device", "hpfw_gpu_dtw_path", "hpfw_gpu_dtw_geometry",
+    "hpfw_gpu_search_local_device", "hpfw_gpu_search_local",
     "hpfw_gpu_index_remove", "hpfw_gpu_index_reserve", "hpfw_gpu_index_capacity", "hpfw_gpu_index_remove_plan",
     "hpfw_gpu_index_remove_geometry",
     "hpfw_gpu_index_selfjoin_device", "hpfw_gpu_index_selfjoin", "hpfw_gpu_selfjoin_geometry",
@@ -231,6 +237,8 @@ def lib():
     L.hpfw_gpu_dtw_path_device.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.hpfw_gpu_dtw_path.argtypes = [vp, vp, i64, i32, vp, vp]
     L.hpfw_gpu_dtw_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.hpfw_gpu_search_local_device.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    L.hpfw_gpu_search_local.argtypes = [vp, vp, vp, i64, i32, i32, vp]
     L.hpfw_gpu_index_remove.argtypes = [vp, vp, i64, vp]
     L.hpfw_gpu_index_reserve.argtypes = [vp, i64]
     L.hpfw_gpu_index_capacity.argtypes = [vp]
@@ -1206,6 +1214,20 @@ class Gpu:
 
     def dtw_path_dev(self, d_q, k_q, clip, d_path, d_hit, stream=0):
         check(lib().hpfw_gpu_dtw_path_device(self._h, d_q, int(k_q), int(clip), d_path, d_hit, stream))
+
+    # ---- local search: the best-scoring run of query hashprints on any diagonal of a clip
+    def search_local(self, q_hp, q_off, k, max_rate):
+        """LOCAL_HIT_DTYPE [n_q][k] by the rule of include/hpfw_gpu.h: per query the k clips with the best run, larger score
+        first, then the smaller clip.  max_rate (no default), 1..31: a run's score is max_rate * length - dist"""
+        q = np.ascontiguousarray(q_hp, np.uint64).ravel()
+        off = np.ascontiguousarray(q_off, np.int64)
+        out = np.zeros((off.size - 1, k), LOCAL_HIT_DTYPE)
+        check(lib().hpfw_gpu_search_local(self._h, _hp(q), _hp(off), off.size - 1, int(max_rate), int(k), _hp(out)))
+        return out
+
+    def search_local_dev(self, d_q, q_off, k, max_rate, d_out, stream=0):
+        off = np.ascontiguousarray(q_off, np.int64)
+        check(lib().hpfw_gpu_search_local_device(self._h, d_q, _hp(off), off.size - 1, int(max_rate), int(k), d_out, stream))
 
     def search_votes(self, q_hp, q_off):
         """AnnStorage-style voting search with exact neighbours: VOTE_DTYPE [n_q]"""

@@ -1,5 +1,5 @@
 // handle.h -- what the sources of the C-ABI declared in include/hpfw_gpu.h (handle.hip, plans.hip, extract.hip, learn.hip,
-// search.hip, selfjoin.hip, dtw.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
+// search.hip, selfjoin.hip, dtw.hip, local.hip, votes.hip, combiner.hip, warp.hip) share.  Host orchestration only: plans, workspaces, batching over clips (the role of
 // ParallelCollector::collect_fingerprints' parallel_for, reference
 // include/hpfw/core/parallel_collector.h:115-137) and MemoryStorage::build/find
 // (include/hpfw/audioproblems/live-song-id/storage.h:21-64).  All arithmetic is in the kernels.
@@ -157,6 +157,9 @@ struct hpfw_gpu {
         // warped search (dtw.hip): the queries' offsets, the caller's pairs, the boundary rows of the
         // workgroups, the pairs' hits, the top lists (the plain search's candidates, launch_topk's hits), a path's choices
         DevBuf d_dtw_q_off, d_dtw_pairs, d_dtw_bnd, d_dtw_hits, d_dtw_top, d_dtw_choices;
+        // local search (local.hip): launch_topk's hits of a group of queries; the count of winners whose
+        // walk disagreed with the scan
+        DevBuf d_local_top, d_local_flag;
         // removal in place (k_index.hip): the staging buffer of one chunk; the moves of the last
         // removal on the device and the host copy their upload reads, which moves_ev says has been read
         DevBuf d_stage, d_moves;

@@ -415,6 +415,24 @@ void launch_overlap_popc(const uint64_t *d_db, const int64_t *d_db_off, int n_cl
 // d_exclude: NULL or [n_q] clips to skip (-1: none); n_clips == 0: padding records
 void launch_overlap_select(void *d_tab, int n_q, int n_clips, int splits, const int32_t *d_exclude, int k, uint32_t clip_base, void *d_out,
                            hipStream_t s);
+// local search (k_search_local.hip): per (query, clip) the best-scoring run of consecutive query positions
+// on any diagonal, score = sum of max_rate - popcount over the run.  d_best [n_q][n_clips], every byte preset to 0xff, takes
+// (kLocalScoreBias - score) << 32 | (lag + kLocalLagBias) of every pair with a positive run: smaller is better, so launch_topk
+// picks a query's clips (its hit's dist = kLocalScoreBias - score, its offset = lag + kLocalLagBias).  A clip's lags
+// 1 - k .. n - 1 are cut into `chunks` workgroups of kLocalChunk.
+constexpr int kLocalChunk = 1024;
+constexpr int kLocalScoreBias = 1 << 20; // above every score: 31 * 16000
+constexpr int kLocalLagBias = 1 << 14;   // above every query's length: lag + bias >= 0
+// the matrix-core scan: d_qa, d_gk [group], k_max as launch_overlap_mfma's
+void launch_local_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const int64_t *d_q_off, int n_q, const void *d_qa,
+                       int kt_pad, const int *d_gk, int k_max, int max_rate, int chunks, uint64_t *d_best, hipStream_t s);
+// the same keys by xor/popcount, one workgroup per (query, clip, chunk)
+void launch_local_popc(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const uint64_t *d_q, const int64_t *d_q_off, int n_q,
+                       int max_rate, int chunks, uint64_t *d_best, hipStream_t s);
+// d_top [n_q][k]: launch_topk's hits of d_best (NULL: padding everywhere) -> d_out [n_q][k] (hpfw_local_hit): the winning
+// diagonals walked once; *d_disagree += the winners whose walk does not give the scan's score
+void launch_local_ends(const void *d_top, const uint64_t *d_db, const int64_t *d_db_off, const uint64_t *d_q, const int64_t *d_q_off,
+                       int64_t n_q, int k, int max_rate, uint32_t clip_base, void *d_out, unsigned *d_disagree, hipStream_t s);
 // scored overlap search (k_stats.hip), after launch_overlap_select on the same d_tab: d_stats [n_q]
 // (hpfw_dist_stats, zeroed by the caller) += per query row the moments of floor(dist 2^kOverlapRateBits / overlap) over the
 // clips with a candidate but d_exclude's.  A row is cut into overlap_stats_slices(n_clips) workgroups.

@@ -375,6 +375,26 @@ class LiveSongIdentification:
                                          for h in row if h["clip"] != _lib.NO_CLIP])
         return out
 
+    def top_local(self, filenames: Sequence[str], k: int, max_rate: int):
+        """top() by the local search: which part of the query is which part of which recording.  A run
+        of consecutive query hashprints on one diagonal of a recording scores max_rate * length - dist; max_rate, 1..31
+        mismatching bits per hashprint, has no default: the caller decides.  Per query (label, [(score, name, lag, q_start,
+        length, dist) x <= k]), larger score first: query hashprints q_start .. q_start + length - 1 lie on columns lag + q_start
+        onwards of the recording and differ from them in dist bits.  None in place of the list for a file that yields no
+        hashprint.  No shifts, no tempos; an identifier made with devices= raises HPFW_E_UNSUPPORTED."""
+        self._no_shards("the local search")
+        hps = self.collector.calc_hashprints(list(filenames))
+        good = [i for i, (hp, _) in enumerate(hps) if hp is not None and hp.size]
+        out = [(f, None) for f in filenames]
+        if good and self.names:
+            off = np.zeros(len(good) + 1, np.int64)
+            np.cumsum([hps[i][0].size for i in good], out=off[1:])
+            hits = self._gpu.search_local(np.concatenate([hps[i][0] for i in good]), off, k, max_rate)
+            for row, i in zip(hits, good):
+                out[i] = (filenames[i], [(int(h["score"]), self.names[int(h["clip"])], int(h["lag"]), int(h["q_start"]),
+                                         int(h["length"]), int(h["dist"])) for h in row if h["clip"] != _lib.NO_CLIP])
+        return out
+
     def warp_path(self, filename: str, name: str):
         """(distance, columns): columns int32, the column of the indexed recording `name` every hashprint of the query file
         lies on (DESIGN.md section 20).  None for a file that yields no hashprint or a recording too short for the query;

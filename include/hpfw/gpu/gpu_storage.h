@@ -296,6 +296,33 @@ public:
         return out;
     }
 
+    /// the local search (hpfw_gpu_search_local): which part of the query is which part of which
+    /// recording.  A run of consecutive query hashprints on one diagonal of a recording scores max_rate * length - cnt;
+    /// max_rate, 1..31 mismatching bits per hashprint, is the caller's (there is no default).  Recordings come by larger
+    /// score, then by their position in the database.  Query hashprints q_start .. q_start + length - 1 lie on columns
+    /// lag + q_start onwards of the recording.
+    struct LocalResult {
+        std::string filename;
+        int64_t score;  // max_rate * length - cnt
+        int64_t lag;    // column of the recording query hashprint 0 lies on (negative: before it begins)
+        size_t q_start; // first query hashprint of the run
+        size_t length;  // hashprints of the run
+        size_t cnt;     // mismatching bits over the run
+    };
+    auto find_local(const typename Collector::Hashprint &hp, int k, int max_rate) const -> std::vector<LocalResult>
+    {
+        std::vector<LocalResult> out;
+        if (hp.empty() || names_.empty()) return out;
+        const int64_t q_off[2] = {0, (int64_t)hp.size()};
+        std::vector<hpfw_local_hit> hits((size_t)k);
+        check(hpfw_gpu_search_local(h_, hp.data(), q_off, 1, max_rate, k, hits.data()));
+        for (const hpfw_local_hit &hit : hits) {
+            if (hit.clip == 0xffffffffu) break;
+            out.push_back({names_[hit.clip], (int64_t)hit.score, (int64_t)hit.lag, (size_t)hit.q_start, (size_t)hit.length, (size_t)hit.dist});
+        }
+        return out;
+    }
+
     /// the column of recording `clip` (position in the database) every hashprint of the query lies on, and the distance
     /// along that path; nullopt when the recording is too short for the query (fewer than hp.size() / 2 + 1 columns)
     struct WarpPath {

@@ -662,6 +662,40 @@ int hpfw_gpu_dtw_path(hpfw_gpu *h, const uint64_t *q_hp, int64_t k_q, int32_t cl
  * which a clip crosses into the next lane and the next block */
 int hpfw_gpu_dtw_geometry(int32_t *strip, int32_t *block);
 
+/* ---- local search: which part of the query is which part of which clip.  Every search above rates a
+ * whole alignment; this one rates the best RUN of consecutive query hashprints on any diagonal, so a query that shares only
+ * a passage with a recording (a window of a mix, a sample, an edit with its own intro) is found with the passage's ends.
+ *
+ * max_rate = T, 1 <= T <= 31, in mismatching bits per hashprint, is the caller's and has no default.
+ * Query q[0..k), 1 <= k <= 16000; clip r[0..n).  Lags d = 1 - k .. n - 1; at lag d both have the positions j in [ja, jb),
+ * ja = max(0, -d), jb = min(k, n - d).  x_j = T - popcount(q[j] ^ r[d + j]).  A run is a non-empty [j0, j1) inside
+ * [ja, jb): score = sum of x_j, dist = sum of popcount, length = j1 - j0, so score = T length - dist.
+ * A clip's candidate is its best run over all lags: larger score, then smaller lag, then smaller j1, then smaller j0 (what
+ * a forward pass gives with a running prefix minimum updated on strict <, a best updated on strict >, lags in rising
+ * order).  A clip is a hit only with a score >= 1; a query's k <= 64 hits are ordered by larger score, then smaller clip
+ * id.  Exact integers: no floating point takes part in any order, and the result does not depend on scheduling.
+ * Refused before a device is touched: null pointers, k outside 1..64, max_rate outside 1..31, decreasing q_off
+ * (HPFW_E_INVALID); a query above 16000 hashprints (HPFW_E_UNSUPPORTED).  An empty index, empty queries, removed (empty)
+ * clips, clips without a positive run and the slots past the last hit give padding records.  The ends of every hit come
+ * from a walk of its diagonal that computes the score again; a walk that does not give the scan's score fails the call
+ * (HPFW_E_HIP); the device form waits for its stream to learn that, unless there was nothing to scan.
+ * Environment (tests; the results are the same bytes): HPFW_LOCAL_POPC -- the xor/popcount kernel for every query (it
+ * otherwise serves queries whose window does not fit the LDS).  The sharded index (hpfw_gpu_multi.h) has no local search. */
+typedef struct {
+    int32_t score;    /* T length - dist                                   */
+    uint32_t clip;    /* as hpfw_hit; 0xffffffff = none                    */
+    int32_t lag;      /* clip position of query position 0                 */
+    uint32_t q_start; /* first query position of the run                   */
+    uint32_t length;  /* hashprints of the run                             */
+    uint32_t dist;    /* mismatching bits over the run                     */
+} hpfw_local_hit; /* 24 B; padding: clip = 0xffffffff, rest 0 */
+/* d_q_hp, d_out [n_q][k] device; q_off host */
+int hpfw_gpu_search_local_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int max_rate, int k,
+                                 hpfw_local_hit *d_out, void *stream);
+/* host convenience: copies queries in and hits out, synchronises */
+int hpfw_gpu_search_local(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int max_rate, int k,
+                          hpfw_local_hit *out);
+
 /* ---- events: time a region on `stream` with HIP events (bench.py uses these so that the
  * timing is taken on the stream the kernels run on) ---------------------------------------- */
 int hpfw_gpu_timer_start(hpfw_gpu *h, void *stream);
