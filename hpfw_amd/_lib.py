@@ -33,6 +33,10 @@ LOCAL_CHUNK = 1024
 # hpfw_index_move: a piece of the plan of a removal from the index
 # hpfw_dup_pair: a pair of the catalogue self-join: clips a < b, position 0 of a on position lag of b
 DUP_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("dist", "<u4"), ("overlap", "<u4"), ("lag", "<i4"), ("pad", "<u4")])
+# hpfw_passage_pair: a pair of the local self-join: clips a < b, a[a_start .. a_start + length) lies on
+# b[lag + a_start ..), score = max_rate length - dist
+PASSAGE_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("score", "<i4"), ("lag", "<i4"), ("a_start", "<u4"), ("length", "<u4"),
+                               ("dist", "<u4"), ("pad", "<u4")])
 INDEX_MOVE_DTYPE = np.dtype([("dst", "<i8"), ("src", "<i8"), ("len", "<i8"), ("chunk", "<i8"), ("staged", "<i4"), ("pad", "<i4")])
 VOTE_DTYPE = np.dtype([("clip", "<u4"), ("pad", "<u4"), ("offset", "<i8"), ("cnt", "<f4"), ("pad2", "<f4")])
 # hpfw_combine_result / hpfw_align_hit (AudioCombiner::find and the per-recording alignment peaks)
@@ -114,6 +118,7 @@ EXPORTS = (
     "hpfw_gpu_index_remove_geometry",
     "hpfw_gpu_index_selfjoin_device", "hpfw_gpu_index_selfjoin", "hpfw_gpu_selfjoin_geometry",
     "hpfw_gpu_index_join_device", "hpfw_gpu_index_join", "hpfw_gpu_join_plan",
+    "hpfw_gpu_index_localjoin_device", "hpfw_gpu_index_localjoin", "hpfw_gpu_localjoin_geometry",
     "hpfw_gpu_search_topk_within_device", "hpfw_gpu_search_topk_within",
     "hpfw_gpu_search_topk_transposed_within_device", "hpfw_gpu_search_topk_transposed_within",
     "par_collector_new", "par_collector_del", "par_collector_prepare",
@@ -248,6 +253,9 @@ def lib():
     L.hpfw_gpu_index_selfjoin_device.argtypes = [vp, i32, i32, i32, vp, i64, vp, vp]
     L.hpfw_gpu_index_selfjoin.argtypes = [vp, i32, i32, i32, vp, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_selfjoin_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.hpfw_gpu_index_localjoin_device.argtypes = [vp, i32, i32, vp, i64, vp, vp]
+    L.hpfw_gpu_index_localjoin.argtypes = [vp, i32, i32, vp, i64, ctypes.POINTER(i64)]
+    L.hpfw_gpu_localjoin_geometry.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.hpfw_gpu_index_join_device.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, vp, vp]
     L.hpfw_gpu_index_join.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, ctypes.POINTER(i64)]
     L.hpfw_gpu_join_plan.argtypes = [i64, i64, i32, i64, i64, vp]
@@ -467,6 +475,14 @@ def selfjoin_geometry():
     (hpfw_gpu_selfjoin_geometry)"""
     sl, ch = ctypes.c_int32(0), ctypes.c_int32(0)
     check(lib().hpfw_gpu_selfjoin_geometry(ctypes.byref(sl), ctypes.byref(ch)))
+    return int(sl.value), int(ch.value)
+
+
+def localjoin_geometry():
+    """(slice, chunk) of the local self-join: positions of a staged per pass, lags of b per workgroup pass; a pair's chunks
+    begin at ceil(min_score / max_rate) - (the longest a of the row group) (hpfw_gpu_localjoin_geometry)"""
+    sl, ch = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().hpfw_gpu_localjoin_geometry(ctypes.byref(sl), ctypes.byref(ch)))
     return int(sl.value), int(ch.value)
 
 
@@ -1089,6 +1105,25 @@ class Gpu:
         """device pointers: d_out DUP_PAIR_DTYPE [cap] (0 with cap = 0) receives the first cap pairs, d_count (int64) their
         total number, which may exceed cap"""
         check(lib().hpfw_gpu_index_selfjoin_device(self._h, int(min_overlap), int(rate_num), int(rate_den), d_out, int(cap), d_count, stream))
+
+    # ---- local self-join (DESIGN.md section 26): the passages that recordings of the index share
+    def index_localjoin(self, max_rate, min_score, cap=1024):
+        """PASSAGE_PAIR_DTYPE [n]: every pair of clips a < b whose best run of consecutive hashprints on any diagonal, at
+        max_rate - popcount a hashprint, scores at least min_score, in ascending (a, b) (include/hpfw_gpu.h).  Neither
+        max_rate (1..31) nor min_score (>= 1) has a default.  cap: as index_selfjoin's."""
+        cap = max(int(cap), 0)
+        while True:
+            out = np.zeros(cap, PASSAGE_PAIR_DTYPE)
+            count = ctypes.c_int64(0)
+            check(lib().hpfw_gpu_index_localjoin(self._h, int(max_rate), int(min_score), _hp(out), cap, ctypes.byref(count)))
+            if count.value <= cap:
+                return out[:count.value].copy()
+            cap = int(count.value)
+
+    def index_localjoin_dev(self, max_rate, min_score, d_out, cap, d_count, stream=0):
+        """device pointers: d_out PASSAGE_PAIR_DTYPE [cap] (0 with cap = 0) receives the first cap pairs, d_count (int64) their
+        total number, which may exceed cap"""
+        check(lib().hpfw_gpu_index_localjoin_device(self._h, int(max_rate), int(min_score), d_out, int(cap), d_count, stream))
 
     # ---- ingest check (DESIGN.md section 23): recordings that are not in the index joined against it
     def index_join(self, x_hp, x_off, min_overlap, rate_num, rate_den, among_new, cap=1024):

@@ -148,7 +148,8 @@ struct hpfw_gpu {
         // order of their sets; their hits and moments in that order
         DevBuf d_within_tab, d_within_q, d_within_out;
         // self-join (selfjoin.hip): the (row, clip, split) entries of a pass, its rows' counts and first
-        // positions, the passes' numbering of their (row group, clip) pairs
+        // positions, the passes' numbering of their (row group, clip) pairs; the local self-join (localjoin.hip, section 26)
+        // keeps its own table, rows and numbering in the same three, and its count of disagreeing walks in d_local_flag
         DevBuf d_sj_tab, d_sj_rows, d_sj_pairs;
         DevBuf d_sj_x_off; // the join with recordings outside the index (section 23): their offsets
         // voting search on the device: the workspaces of one group of windows, carved from one buffer;

@@ -469,6 +469,26 @@ inline int64_t join_group_pairs(int64_t n_index, int64_t n_x, int among_new, int
 void launch_join_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_index, const uint64_t *d_x, const int64_t *d_x_off, int n_x,
                       int among_new, int g0, int n_groups, const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits,
                       void *d_tab, hipStream_t s);
+// the local self-join (k_localjoin.hip): for clips a < b the best-scoring run of consecutive hashprints
+// of a on any diagonal of b, score = sum of max_rate - popcount over the run.  Passes, row groups, d_pair_first, n_pairs,
+// splits, slices and chunks are launch_selfjoin_scan's; min_len = ceil(min_score / max_rate) takes min_overlap's part.
+// d_tab [32 n_groups][n_clips][splits] of 8-byte keys (kLocaljoinScoreBias - score) << 32 | (lag + kLocaljoinLagBias), every
+// byte preset to 0xff: smaller is better, and the fold of a pair's splits is their minimum.
+constexpr int kLocaljoinScoreBias = 1 << 24; // above every score: 31 * kSelfjoinMaxLen < 2^23
+constexpr int kLocaljoinLagBias = 1 << 19;   // above every recording's length: lag + bias >= 0
+// the accumulators hold twice the running score, and one product on top of it, before the step's constant is taken off
+static_assert(2 * 31 * (int64_t)kSelfjoinMaxLen + 64 < (1 << 24), "the doubled running score is exact in f32 below 2^24");
+void launch_localjoin_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_clips, int g0, int n_groups,
+                           const uint32_t *d_pair_first, uint32_t n_pairs, int min_len, int max_rate, int splits, void *d_tab, hipStream_t s);
+// folds the splits (in d_tab), counts the pairs of rows row0 .. row0 + n_rows - 1 with score >= min_score into d_row_count,
+// their positions from *d_count on into d_row_first, writes those below cap to d_out (hpfw_passage_pair, rising (a, b), the
+// run's ends still 0) and adds the pass's pairs to *d_count
+void launch_localjoin_select(void *d_tab, int n_clips, int splits, int row0, int n_rows, int min_score, int *d_row_count, int64_t *d_row_first,
+                             uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s);
+// after the last pass: the diagonals of the min(*d_count, cap) pairs in d_out walked once -- a_start, length, dist and the
+// score again; *d_disagree += the pairs whose walk does not give the scan's score
+void launch_localjoin_ends(const uint64_t *d_db, const int64_t *d_db_off, int max_rate, uint32_t clip_base, void *d_out, int64_t cap,
+                           const int64_t *d_count, unsigned *d_disagree, hipStream_t s);
 // per-shift top-k lists in [n_q][n_shifts][k] (hpfw_hit) -> out [n_q][k] (hpfw_shift_hit): per clip its smallest
 // (dist, shift index), then the k best by (dist, clip)
 void launch_topk_merge_shifts(const void *d_in, int n_q, int n_shifts, int k, void *d_out, hipStream_t s);

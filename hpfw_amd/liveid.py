@@ -203,6 +203,19 @@ class LiveSongIdentification:
         pairs = self._gpu.index_selfjoin(int(min_overlap), num, den)
         return [(self.names[int(p["a"])], self.names[int(p["b"])], int(p["dist"]), int(p["overlap"]), int(p["lag"])) for p in pairs]
 
+    # ---- local self-join: which recordings of the index share a passage, and where
+    def shared_passages(self, max_rate: int, min_score: int):
+        """the pairs of indexed recordings that share a passage: the best run of consecutive hashprints on any diagonal of
+        the two, at max_rate - (mismatching bits) a hashprint, scores at least min_score.  max_rate, 1..31 mismatching bits
+        per hashprint, and min_score >= 1 have no default: the caller decides.  [(name_a, name_b, score, lag, a_start, length,
+        dist)] in index order of (a, b): columns a_start .. a_start + length - 1 of a lie on columns lag + a_start onwards of b
+        and differ from them in dist bits; score = max_rate * length - dist.  One passage a pair; removed recordings never
+        appear.  An identifier made with devices= raises HPFW_E_UNSUPPORTED."""
+        self._no_shards("the local self-join")
+        pairs = self._gpu.index_localjoin(int(max_rate), int(min_score))
+        return [(self.names[int(p["a"])], self.names[int(p["b"])], int(p["score"]), int(p["lag"]), int(p["a_start"]), int(p["length"]),
+                 int(p["dist"])) for p in pairs]
+
     def duplicate_groups(self, pairs) -> List[List[str]]:
         """the connected components of duplicates()'s pairs as lists of names in index order (duplicate_groups())"""
         return duplicate_groups(pairs, self.live_names())

@@ -240,6 +240,35 @@ public:
         return out;
     }
 
+    /// the local self-join (hpfw_gpu_index_localjoin): the pairs of indexed recordings a before b that
+    /// share a passage -- the best run of consecutive hashprints on any diagonal of the two scores at least min_score, at
+    /// max_rate - (mismatching bits) a hashprint.  max_rate, 1..31, and min_score >= 1 are the caller's: there is no default.
+    /// Hashprints a_start .. a_start + length - 1 of a lie on columns lag + a_start onwards of b; score = max_rate * length - cnt.
+    struct PassageResult {
+        std::string name_a, name_b;
+        int64_t score;  // max_rate * length - cnt
+        int64_t lag;    // column of b that hashprint 0 of a lies on (negative: before b begins)
+        size_t a_start; // first hashprint of the passage in a
+        size_t length;  // hashprints of the passage
+        size_t cnt;     // mismatching bits over the passage
+    };
+    auto shared_passages(int max_rate, int min_score) const -> std::vector<PassageResult>
+    {
+        std::vector<hpfw_passage_pair> pairs(256);
+        int64_t count = 0;
+        check(hpfw_gpu_index_localjoin(h_, max_rate, min_score, pairs.data(), (int64_t)pairs.size(), &count));
+        if (count > (int64_t)pairs.size()) { // (the buffer was too small: once more with room for all)
+            pairs.resize((size_t)count);
+            check(hpfw_gpu_index_localjoin(h_, max_rate, min_score, pairs.data(), (int64_t)pairs.size(), &count));
+        }
+        std::vector<PassageResult> out;
+        for (int64_t i = 0; i < count; ++i) {
+            const hpfw_passage_pair &p = pairs[(size_t)i];
+            out.push_back({names_[p.a], names_[p.b], (int64_t)p.score, (int64_t)p.lag, (size_t)p.a_start, (size_t)p.length, (size_t)p.dist});
+        }
+        return out;
+    }
+
     /// the ingest check (hpfw_gpu_index_join): what duplicates() would report in addition after
     /// add(hashprints), without the index changing -- the pairs whose b is one of the recordings given (named as add() would
     /// name it) and whose a is an indexed recording or, with among_new, an earlier one of the range.  Accepts any range of

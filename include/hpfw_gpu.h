@@ -696,6 +696,56 @@ int hpfw_gpu_search_local_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
 int hpfw_gpu_search_local(hpfw_gpu *h, const uint64_t *q_hp, const int64_t *q_off, int64_t n_q, int max_rate, int k,
                           hpfw_local_hit *out);
 
+/* ---- local self-join: which recordings of the index share a passage, and where -- a sample lifted
+ * into another track, one intro under two programmes, a medley, a set recorded twice with different talk around it.  The
+ * self-join above rates everything two recordings have in common at a lag, so foreign material around a shared passage
+ * hides the pair from it; this join rates the best RUN of consecutive hashprints, as the local search does, for every
+ * unordered pair of the index once, where the index lies, at any indexed length up to 2^18 - 1 hashprints.
+ *
+ * The caller passes max_rate = T, 1 <= T <= 31, in mismatching bits per hashprint, and min_score >= 1; neither has a
+ * default in any binding.
+ * Take clips a < b of the index in add order, both live and non-empty.  Clip a takes the part of the query of the local
+ * search above and b the part of the clip:
+ *   lag d puts position j of a on position d + j of b, d = 1 - n_a .. n_b - 1;
+ *   x_j = T - popcount(a[j] ^ b[d + j]);    a run [j0, j1) of positions both have scores the sum of its x_j.
+ * The pair's candidate is its best run over all lags: larger score, then smaller lag, then smaller j1, then smaller j0
+ * (what a forward pass gives with a running prefix minimum updated on strict <, a best updated on strict >, lags in rising
+ * order).  The pair is REPORTED when score >= min_score.
+ * Pairs come in ascending (a, b) with the clip base added to both ids.  The passage is a[a_start .. a_start + length) on
+ * b[lag + a_start .. lag + a_start + length); score = T length - dist.  Exact integers: no floating point takes part in
+ * any order, no atomics are used, and nothing depends on the order in which workgroups run.  Empty slots, removed
+ * recordings and pairs without a qualifying run never appear.  A run that scores min_score has at least
+ * ceil(min_score / T) positions, so only lags that overlap that much are scanned; that changes the work, not the result.
+ * d_out receives the first cap reported pairs, *d_count (int64) their total number, which may exceed cap: the caller
+ * enlarges the buffer and calls again.  An empty index and an index of one clip give count 0.
+ * Refused before a device is touched (HPFW_E_INVALID): a null handle, max_rate outside 1..31, min_score < 1, cap < 0, a
+ * null out with cap > 0, a null count.  An index that holds a recording above 2^18 - 1 hashprints is refused before a
+ * kernel runs (HPFW_E_UNSUPPORTED): below that bound 2 * 31 * L < 2^24 and the doubled running score is exact in the fp32
+ * accumulators.  The ends of every written pair come from a walk of its diagonal that computes the score again; a walk
+ * that does not give the scan's score fails the call (HPFW_E_HIP); the device form waits for its stream to learn that,
+ * unless there was nothing to scan.
+ * HPFW_LOCALJOIN_POPC in the environment selects the xor/popcount kernel, HPFW_LOCALJOIN_SPLITS (1..64) the workgroups
+ * that share a pair's lags, HPFW_LOCALJOIN_TABLE_KB the size of the table of one pass over the rows (default and most
+ * 512 MiB); they are read at every call and change no result.  The sharded index (hpfw_gpu_multi.h) has no local
+ * self-join. */
+typedef struct {
+    uint32_t a, b;    /* a < b, ids in add order + the clip base       */
+    int32_t score;    /* T length - dist                               */
+    int32_t lag;      /* position 0 of a lies on position lag of b     */
+    uint32_t a_start; /* first position of the run in a                */
+    uint32_t length;  /* hashprints of the run                         */
+    uint32_t dist;    /* mismatching bits over the run                 */
+    uint32_t pad;
+} hpfw_passage_pair; /* 32 B */
+int hpfw_gpu_index_localjoin_device(hpfw_gpu *h, int max_rate, int min_score, hpfw_passage_pair *d_out, int64_t cap,
+                                    int64_t *d_count, void *stream);
+/* host buffers (the null stream): out [cap], *count */
+int hpfw_gpu_index_localjoin(hpfw_gpu *h, int max_rate, int min_score, hpfw_passage_pair *out, int64_t cap, int64_t *count);
+/* host-only: *slice = the positions of a staged per pass over the LDS, *chunk = the lags of b one workgroup pass takes (a
+ * pair's chunks begin at ceil(min_score / max_rate) - the longest of the 32 rows a that share the workgroup).  NULL is
+ * HPFW_E_INVALID. */
+int hpfw_gpu_localjoin_geometry(int32_t *slice, int32_t *chunk);
+
 /* ---- events: time a region on `stream` with HIP events (bench.py uses these so that the
  * timing is taken on the stream the kernels run on) ---------------------------------------- */
 int hpfw_gpu_timer_start(hpfw_gpu *h, void *stream);
