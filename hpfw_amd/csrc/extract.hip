@@ -2,6 +2,8 @@
 // transposed and tempo variants, the stage entry points, the host-buffer round trips, resampling.
 #include "handle.h"
 
+#include <optional>
+
 // nb: clips per front-end pass (large intermediates); ns: clips per back-end pass (S and P only)
 // clips per front-end pass: the handle's batch, the number of clips, and what ~24 GB of workspace hold
 int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips)
@@ -11,7 +13,7 @@ int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips)
     if (p.bluestein)
         per_clip += 2 * hpfw::bz_plane_bytes(dp->bz, 1) + (size_t)(p.kmax - p.kmin) * 8;
     else
-        per_clip += (size_t)hpfw::z_floats_per_clip(p.hq, p.n2) * 4 + (size_t)p.n1 * p.q2w * 8;
+        per_clip += (size_t)hpfw::z_floats_per_clip(p.hq, p.n2) * 4 + (size_t)p.n1 * p.q2w * 8 * (h->pass_pipeline ? 2 : 1); // (X[0], X[1])
     size_t work = 0;
     for (const hpfw::CqClassDev &cd : dp->cls) work = std::max(work, hpfw::cq_big_work_bytes(cd, 1));
     per_clip += work;
@@ -22,7 +24,7 @@ int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips)
     return (int)((n + passes - 1) / passes);
 }
 
-int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns)
+int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns, int x_bufs)
 {
     const hpfw::HostPlan &p = dp->hp;
     size_t work = 0;
@@ -32,9 +34,10 @@ int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns)
         if (rc) return rc;
     }
     const size_t planar = p.bluestein ? hpfw::bz_plane_bytes(dp->bz, nb) : 0;
-    // ws[0]: the column stage's output z [hq][n2] (chirp-z path: a planar buffer); ws[1]: the forward bins (XsView layout)
+    // ws[0]: the column stage's output z [hq][n2] (chirp-z path: a planar buffer); ws[1]: the forward bins (XsView layout),
+    // x_bufs buffers of nb clips one behind the other (two where the passes of a group are pipelined)
     const size_t need[7] = {p.bluestein ? planar : (size_t)nb * hpfw::z_floats_per_clip(p.hq, p.n2) * 4,
-                            p.bluestein ? (size_t)nb * (p.kmax - p.kmin) * 8 : (size_t)nb * p.n1 * p.q2w * 8,
+                            p.bluestein ? (size_t)nb * (p.kmax - p.kmin) * 8 : (size_t)x_bufs * nb * p.n1 * p.q2w * 8,
                             (size_t)ns * 121 * p.c * 4, (size_t)ns * 64 * (size_t)std::max(p.n_frames, 1) * 4, // (P: the f32-chain projection only)
                             (size_t)ns * 121 * hpfw::kCqMaxWaves * 4,
                             0, planar};
@@ -52,6 +55,8 @@ int ensure_side_streams(hpfw_gpu *h)
 {
     if (h->cq_join[hpfw_gpu::kCqSide - 1]) return HPFW_OK;
     bool ok = h->cq_fork.create() == hipSuccess;
+    for (int b = 0; b < 2 && ok; ++b)
+        for (int k = 0; k <= hpfw_gpu::kCqSide && ok; ++k) ok = h->pp_fwd[b][k].create() == hipSuccess && h->pp_cq[b][k].create() == hipSuccess;
     for (int k = 0; k < hpfw_gpu::kCqSide && ok; ++k) ok = h->cq_side[k].create() == hipSuccess && h->cq_join[k].create() == hipSuccess;
     return ok ? HPFW_OK : fail(HPFW_E_HIP, "side streams");
 }
@@ -99,6 +104,35 @@ private:
 #if defined(HPFW_ROWS_SNAP) || defined(HPFW_ROWS_STAMPS)
 hpfw::cf *g_rows_snap = nullptr; // diagnosis builds: fft_rows.h HPFW_SNAP / HPFW_STAMP
 #endif
+
+// the forward transform of nb clips (7-smooth lengths) queued in chunks that the first fwd_streams lanes of `fan` take in
+// turn (or the lanes `turns` lists, over and over): PCM -> bins in x.  A lane's chunks follow each other in order, so
+// every lane has one region of z of its own
+void queue_fwd_chunks(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf *x, Fanout &fan,
+                      const std::vector<int> *turns = nullptr)
+{
+    const hpfw::HostPlan &p = dp->hp;
+    hpfw::ColsQArgs cols = dp->cols;
+    cols.variant = h->cols_variant;
+    float *yp = h->ws[0].as<float>();
+    const int lanes = h->fwd_streams;
+    const int64_t region = (int64_t)h->fwd_chunk * dp->rows_out.zclip;
+    int i = 0;
+    for (int c0 = 0; c0 < nb; c0 += h->fwd_chunk, ++i) {
+        const int nc = std::min(nb - c0, h->fwd_chunk);
+        const int lane = turns ? (*turns)[i % turns->size()] : i % lanes;
+        hipStream_t st = fan.lane(lane);
+        float *zr = yp + lane * region;
+        {
+            Timed t(h, K_COLS, st);
+            hpfw::launch_fwd_cols_q(cols, d_pcm + (int64_t)c0 * p.n, p.n, nc, zr, st);
+        }
+        {
+            Timed t(h, K_ROWS, st);
+            hpfw::launch_fwd_rows2(dp->rows, dp->rows_out, zr, nc, x + (int64_t)c0 * dp->rows_out.n1 * dp->rows_out.q2w, st);
+        }
+    }
+}
 
 // a1 + the forward transform for nb clips: PCM -> bins [kmin, kmax) in x
 int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf *x, hipStream_t s)
@@ -158,23 +192,7 @@ int run_forward(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, hpfw::cf
         const int lanes = h->fwd_streams;
         Fanout fan(h, s);
         if (lanes > 1 && (rc = fan.fork(lanes - 1))) return rc;
-        // a stream's chunks follow each other in order, so every stream has one region of z of its own
-        const int64_t region = (int64_t)h->fwd_chunk * dp->rows_out.zclip;
-        int i = 0;
-        for (int c0 = 0; c0 < nb; c0 += h->fwd_chunk, ++i) {
-            const int nc = std::min(nb - c0, h->fwd_chunk);
-            const int lane = i % lanes;
-            hipStream_t st = fan.lane(lane);
-            float *zr = yp + lane * region;
-            {
-                Timed t(h, K_COLS, st);
-                hpfw::launch_fwd_cols_q(cols, d_pcm + (int64_t)c0 * p.n, p.n, nc, zr, st);
-            }
-            {
-                Timed t(h, K_ROWS, st);
-                hpfw::launch_fwd_rows2(dp->rows, dp->rows_out, zr, nc, x + (int64_t)c0 * dp->rows_out.n1 * dp->rows_out.q2w, st);
-            }
-        }
+        queue_fwd_chunks(h, dp, d_pcm, nb, x, fan);
         return check_launch("fwd_chunks");
     }
     {
@@ -285,6 +303,95 @@ int run_back(hpfw_gpu *h, DevPlan *dp, const void *images, int n_shifts, int ns,
 }
 
 constexpr int kBackBatch = 1024; // clips per projection launch: ~10^4 workgroups, a small launch tail
+
+// whether the passes of a group of ns clips, nbmax to a pass, run pipelined (run_group_pipelined) instead of joined one
+// after the other (run_front): 7-smooth length, every class in LDS alone and side by side, two passes or more, each with
+// chunks enough for the forward lanes; and no timing but the hashprint kernel's and the forward span, so that every
+// other kind keeps the launches and the meaning it has in the joined loop
+bool group_pipelines(const hpfw_gpu *h, const DevPlan *dp, int ns, int nbmax)
+{
+    constexpr unsigned kept = 1u << K_PROJECT | 1u << K_FWD;
+    if (!h->pass_pipeline || dp->hp.bluestein || !h->cq_concurrent || h->fwd_chunk <= 0 || (h->timing_mask & ~kept)) return false;
+    for (const hpfw::CqClassDev &cd : dp->cls)
+        if (cd.outer) return false;
+    const int passes = (ns + nbmax - 1) / nbmax, last = ns - (passes - 1) * nbmax; // (the last pass is the smallest)
+    return passes >= 2 && last >= 6 * h->fwd_chunk;
+}
+
+// The front ends of a group of ns clips, nbmax to a pass, with the passes pipelined: PCM -> dB terms in slots 0 .. ns of the S
+// workspace and their per-clip maxima.  Units: F(p), the forward chunks of pass p on the forward lanes (lanes 0 ..
+// fwd_streams - 1; lane 0 is the caller's stream), into X[p & 1]; Q(p), its chirp-z classes; M, one clipmax launch over the
+// group (the wave maxima lie by slot).  Queued as F(0), then Q(p), F(p + 1) for every p, ordered by events alone:
+// Q(p) waits for every lane of F(p); F(p + 2) waits for every class of Q(p) (X[p & 1]); F(p + 1) waits for nothing of Q(p)
+// but what was queued before it on its own lane; M follows the join of every lane into s.  The largest class goes to the
+// first lane without forward chunks, so that what ends last holds up no chunk of the next pass; the second largest goes
+// ahead of the chunks of the last forward lane, the others ahead of those of lane 0 (streams that share a hardware queue
+// run one after the other, and three of a process's four queues are to be had: handle.h).  HPFW_PASS_PLAN names another
+// plan.  S and the wave maxima are written by slot, z by lane.
+// fwd_span (K_FWD): per pass, on s, from before its first chunk there to after s has waited for its last; from the second
+// pass on the span begins under the largest class of the pass before.
+int run_group_pipelined(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int ns, int nbmax, hipStream_t s)
+{
+    using hpfw::cf;
+    const hpfw::HostPlan &p = dp->hp;
+    constexpr int kLanes = hpfw_gpu::kCqSide + 1;
+    const int passes = (ns + nbmax - 1) / nbmax;
+    const int64_t xbuf = (int64_t)nbmax * p.n1 * p.q2w;
+    const int db = h->db_fast ? hpfw::kDbFast : hpfw::kDbSpec;
+    // the plan: the lane of every chunk in turn, the lane of every class (dp->cls is in ascending order of size)
+    std::vector<int> turns = h->pp_turns, lane_of(dp->cls.size());
+    if (turns.empty())
+        for (int k = 0; k < h->fwd_streams; ++k) turns.push_back(k);
+    unsigned fwd_lanes = 0, cq_lanes = 0;
+    for (int k : turns) fwd_lanes |= 1u << k;
+    const int fl = h->fwd_streams;
+    for (size_t ci = dp->cls.size(), i = 0; ci-- > 0; ++i) {
+        if (!h->pp_class_lane.empty()) lane_of[ci] = h->pp_class_lane[std::min(i, h->pp_class_lane.size() - 1)];
+        else lane_of[ci] = i == 0 ? std::min(fl, kLanes - 1) : i == 1 ? fl - 1 : 0;
+        cq_lanes |= 1u << lane_of[ci];
+    }
+    int rc;
+    {
+        Fanout fan(h, s);
+        if ((rc = fan.fork(hpfw_gpu::kCqSide))) return rc;
+        std::optional<Timed> span;
+        auto forward = [&](int pass) -> int {
+            const int c0 = pass * nbmax, nb = std::min(nbmax, ns - c0), b = pass & 1;
+            span.emplace(h, K_FWD, s);
+            if (pass >= 2) // X[b] is read by the classes of pass - 2
+                for (int k = 0; k < kLanes; ++k)
+                    for (int j = 0; j < kLanes; ++j)
+                        if ((fwd_lanes >> k & 1u) && (cq_lanes >> j & 1u) && j != k) HIP_TRY(hipStreamWaitEvent(fan.lane(k), h->pp_cq[b][j].get(), 0));
+            queue_fwd_chunks(h, dp, d_pcm + (int64_t)c0 * p.n, nb, h->ws[1].as<cf>() + b * xbuf, fan, &turns);
+            for (int k = 0; k < kLanes; ++k)
+                if (fwd_lanes >> k & 1u) HIP_TRY(hipEventRecord(h->pp_fwd[b][k].get(), fan.lane(k)));
+            return check_launch("fwd_chunks");
+        };
+        auto classes = [&](int pass) -> int {
+            const int c0 = pass * nbmax, nb = std::min(nbmax, ns - c0), b = pass & 1;
+            const bool timed = span && span->on;
+            for (int j = 0; j < kLanes; ++j)
+                if ((cq_lanes >> j & 1u) || (j == 0 && timed))
+                    for (int k = 0; k < kLanes; ++k)
+                        if ((fwd_lanes >> k & 1u) && k != j) HIP_TRY(hipStreamWaitEvent(fan.lane(j), h->pp_fwd[b][k].get(), 0));
+            span.reset();
+            for (size_t ci = dp->cls.size(); ci-- > 0;)
+                hpfw::launch_cq_class(dp->cq, dp->cls[ci], h->ws[1].as<cf>() + b * xbuf, nb, h->ws[2].as<float>() + (size_t)c0 * 121 * p.c,
+                                      h->ws[4].as<float>() + (size_t)c0 * 121 * hpfw::kCqMaxWaves, db, fan.lane(lane_of[ci]));
+            if (pass + 2 < passes)
+                for (int j = 0; j < kLanes; ++j)
+                    if (cq_lanes >> j & 1u) HIP_TRY(hipEventRecord(h->pp_cq[b][j].get(), fan.lane(j)));
+            return check_launch("cq_chirpz");
+        };
+        if ((rc = forward(0))) return rc;
+        for (int pass = 0; pass < passes; ++pass) {
+            if ((rc = classes(pass))) return rc;
+            if (pass + 1 < passes && (rc = forward(pass + 1))) return rc;
+        }
+    } // (every lane used joins s)
+    hpfw::launch_clipmax(h->ws[4].as<float>(), h->d_clipmax.as<float>(), ns, s);
+    return check_launch("db");
+}
 
 // the one report of a handle without filters
 int check_filters(const hpfw_gpu *h) { return h->has_filters ? 0 : fail(HPFW_E_NOFILTERS, "no filters: call hpfw_gpu_set_filters or hpfw_gpu_learn_filters first"); }
@@ -483,12 +590,17 @@ int extract_pcm16(hpfw_gpu *h, const int16_t *d_pcm, int64_t n_samples, int64_t 
         const void *images = n_shifts ? h->d_shift_images.get() : h->d_fq_image.get();
         const int nbmax = pass_clips(h, dp, n_clips);
         const int nsmax = (int)std::min<int64_t>(std::max(kBackBatch, nbmax), std::max<int64_t>(n_clips, 1));
-        if ((rc = ensure_ws(h, dp, nbmax, nsmax))) return rc;
+        const bool pipelined = group_pipelines(h, dp, (int)std::min<int64_t>(nsmax, n_clips), nbmax); // (the first group is the largest)
+        if ((rc = ensure_ws(h, dp, nbmax, nsmax, pipelined ? 2 : 1))) return rc;
         for (int64_t s0 = 0; s0 < n_clips; s0 += nsmax) {
             const int ns = (int)std::min<int64_t>(nsmax, n_clips - s0);
-            for (int c0 = 0; c0 < ns; c0 += nbmax) {
-                const int nb = std::min(nbmax, ns - c0);
-                if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
+            if (pipelined && group_pipelines(h, dp, ns, nbmax)) {
+                if ((rc = run_group_pipelined(h, dp, d_pcm + s0 * n_samples, ns, nbmax, s))) return rc;
+            } else {
+                for (int c0 = 0; c0 < ns; c0 += nbmax) {
+                    const int nb = std::min(nbmax, ns - c0);
+                    if ((rc = run_front(h, dp, d_pcm + (s0 + c0) * n_samples, nb, c0, false, s))) return rc;
+                }
             }
             if ((rc = run_back(h, dp, images, n_shifts, ns, d_hp + s0 * std::max(n_shifts, 1) * dp->hp.n_hp, s))) return rc;
         }

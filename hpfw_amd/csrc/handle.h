@@ -202,6 +202,19 @@ struct hpfw_gpu {
     Stream cq_side[kCqSide];
     Event cq_fork, cq_join[kCqSide];
     int cq_concurrent = 1; // HPFW_CQ_SERIAL=1 in the environment at creation: one class after the other on the caller's stream
+    // The passes of a back-end group pipelined over the same lanes (extract.hip run_group_pipelined): the
+    // forward chunks of pass p + 1 are queued behind the classes of pass p instead of behind their join and the per-pass
+    // maximum, so they start under the tail of the largest class.  Pass p keeps its forward bins in X[p & 1] (two halves
+    // of ws[1]); lane k's last chunk of pass p records pp_fwd[p & 1][k], its classes of pass p record pp_cq[p & 1][k].
+    // Three lanes are in use, because a process has four hardware queues and streams that share one run one after the
+    // other (the five streams of the class fork sit on three queues): the largest class alone on lane fwd_streams
+    // (cq_side[fwd_streams - 1]), which carries no chunks, the second largest ahead of the chunks of the last forward lane, the others on the
+    // caller's stream.  HPFW_PASS_PIPELINE=0 in the environment at creation: every pass joined, as run_front does.
+    // HPFW_PASS_PLAN="<lane of each class, largest first>:<lanes of the chunks in turn>" (timing, tests): another plan,
+    // lane 0 the caller's stream, lane k cq_side[k - 1]; "23401:01" spreads the classes over all five lanes
+    Event pp_fwd[2][kCqSide + 1], pp_cq[2][kCqSide + 1];
+    int pass_pipeline = 1;
+    std::vector<int> pp_class_lane, pp_turns;
     // the forward transform of a large batch in chunks of fwd_chunk clips taken in turn by fwd_streams streams (the
     // caller's and side streams): column stage and row stage of a chunk back to back, so that the column stage's output
     // (5.3 MB per clip) is read back out of the Infinity Cache instead of HBM.  HPFW_FWD_CHUNK (0: one launch per stage
@@ -429,7 +442,7 @@ void clear_plans(hpfw_gpu *h);      // every length's tables and host half (no w
 // where the call runs the nine-product kernel (shifted images, HPFW_Q_PRODUCTS=9)
 int q_split(hpfw_gpu *h, int n_shifts, int64_t n_clips, int64_t c, hpfw::QSplit *qs, const hpfw::QSplit **use);
 int pass_clips(hpfw_gpu *h, const DevPlan *dp, int64_t n_clips);
-int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns);
+int ensure_ws(hpfw_gpu *h, const DevPlan *dp, int nb, int ns, int x_bufs = 1); // x_bufs: forward-bin buffers of nb clips in ws[1]
 int run_front(hpfw_gpu *h, DevPlan *dp, const int16_t *d_pcm, int nb, int slot, bool finish_db, hipStream_t s);
 // the device image of the table of `rate` (not 44 100 Hz, inside the range), made and cached on first use; the device is set
 int rs_table(hpfw_gpu *h, int rate, hpfw_gpu::Resample::Table **out);

@@ -34,6 +34,14 @@ int hpfw_gpu_create(int device, hpfw_gpu **out)
     h->device = device;
     if (std::getenv("HPFW_CQ_SERIAL")) h->cq_concurrent = 0;
     if (const char *e = std::getenv("HPFW_FWD_CHUNK")) h->fwd_chunk = std::max(0, atoi(e));
+    if (const char *e = std::getenv("HPFW_PASS_PIPELINE")) h->pass_pipeline = atoi(e) != 0;
+    if (const char *e = std::getenv("HPFW_PASS_PLAN")) {
+        std::vector<int> *to = &h->pp_class_lane;
+        for (; *e; ++e) {
+            if (*e == ':') to = &h->pp_turns;
+            else if (*e >= '0' && *e <= '0' + hpfw_gpu::kCqSide) to->push_back(*e - '0');
+        }
+    }
     if (const char *e = std::getenv("HPFW_BZ_CHUNK")) h->bz_chunk = std::max(0, atoi(e));
     if (const char *e = std::getenv("HPFW_COLS_VARIANT")) h->cols_variant = atoi(e);
     if (const char *e = std::getenv("HPFW_PRUNE")) h->prune = (unsigned)std::strtoul(e, nullptr, 0);
