@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <functional>
 #include <chrono>
 #include <map>
 #include <memory>
@@ -424,14 +425,35 @@ inline int64_t index_longest_clip(const hpfw_gpu *h)
     return n_max;
 }
 
-// Overlap search and joins (overlap_rule.h): a pair's lags come in chunks of 1024; with few pairs the chunks of a pair go
-// to `splits` workgroups, each with a table entry of its own -- enough for some 2048 workgroups, at most 64 a pair.
-// env_name: that many instead, for tests of either shape
-inline int64_t overlap_splits(int64_t chunks, int64_t pairs, const char *env_name)
+// what hpfw::overlap_splits and hpfw::join_plan (join_plan.h) take as forced_splits and table_kb: the value of the
+// variable, or "not set"
+inline int64_t env_forced_splits(const char *env_name)
 {
-    if (const char *e = std::getenv(env_name)) return std::min<int64_t>(std::max(std::atoi(e), 1), 64);
-    return std::min<int64_t>({chunks, (2048 + pairs - 1) / pairs, 64});
+    const char *e = std::getenv(env_name);
+    return e ? std::min<int64_t>(std::max(std::atoi(e), 1), 64) : 0;
 }
+inline int64_t env_table_kb(const char *env_name)
+{
+    const char *e = std::getenv(env_name);
+    return e ? std::max<int64_t>(std::atoll(e), 0) : -1;
+}
+
+// selfjoin.hip: the passes of a join, inside ordered_call.  pair_first goes to d_sj_pairs, and the stream is waited for
+// once (whatever else the caller enqueued from host memory has been read); d_sj_tab and d_sj_rows are sized for a pass of
+// entry_bytes entries; every pass with pairs presets its table to 0xff, then runs scan under K_SCAN and select under
+// K_TOPK, each launch checked under its label
+struct JoinPass {
+    int g0, n_groups;            // its row groups
+    const uint32_t *d_pair_first;
+    uint32_t n_pairs;            // > 0
+    int splits;
+    void *d_tab;
+    int *d_row_count;            // [32 n_groups]
+    int64_t *d_row_first;
+};
+int join_run_passes(hpfw_gpu *h, hipStream_t s, const hpfw::JoinPlan &plan, int64_t n_groups, int64_t n_cols, size_t entry_bytes,
+                    const char *scan_what, const std::function<void(const JoinPass &)> &scan, const char *select_what,
+                    const std::function<void(const JoinPass &)> &select);
 
 // plans.hip
 int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out);

@@ -11,7 +11,8 @@
 // two sums: cur_j = max(cur_{j-1}, 0) + 2 x_j is twice the best run that ends at j, and best = max(best, cur_j) from 0 (only
 // positive runs are hits).  The step's constant -(64 - 2 T) comes from the matrix pipe as well -- a second instruction per
 // tile multiplies a row of +1 by a column with 64 - 2 T values of -1 -- so the vector pipe is left with two operations per
-// accumulator register and step: best = max(best, cur), cur = max(cur, 0).  Padding lies at a diagonal's two ends only and
+// accumulator register and step: best = max(best, cur), cur = max(cur, 0) (scan_tile; local_rule.h has it, the constant's
+// column and the walk of a diagonal, shared with the local self-join).  Padding lies at a diagonal's two ends only and
 // every step of it is strictly negative, so no best run reaches into it: the scores are those of a masked scan.  All values
 // are integers below 2^21: exact in f32, in any order.
 // A register's lag is fixed, so the scan tracks no position.  A workgroup reduces each row over its lags (larger score, then
@@ -22,14 +23,13 @@
 // (c) local_ends_kernel walks the winning diagonal of each of the n_q k winners once: the run's first position, its length
 // and its mismatching bits, and the score again, which must be the scan's.
 #include "kernels.h"
-#include "overlap_rule.h"
+#include "local_rule.h"
 
 namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int kLcThreads = 512;                            // 8 waves
@@ -66,32 +66,6 @@ __device__ __forceinline__ void offer(unsigned long long *best, unsigned key, in
     atomicMin(best, full);
 }
 
-// one accumulator tile after a step: cur is twice the best run that ends here; a run that scores below 0 is not continued.
-// Both maxima are taken on the bit patterns as signed integers (bs holds best's): the other operand is never negative, and
-// against a value >= 0 the two orders agree -- a negative float, -0 included, is a negative integer.  A float maximum would
-// cost a second instruction per operand, the canonicalisation of a value the compiler cannot see the origin of.
-__device__ __forceinline__ void scan_tile(f32x16 &cur, i32x16 &bs)
-{
-    i32x16 c = __builtin_bit_cast(i32x16, cur);
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        bs[reg] = max(bs[reg], c[reg]);
-        c[reg] = max(c[reg], 0);
-    }
-    cur = __builtin_bit_cast(f32x16, c);
-}
-
-// 32 fp4 values of a lane's half of K: the first `cnt` are -1.0 (0xA), the others 0
-__device__ __forceinline__ v4i minus_ones(int cnt)
-{
-    v4i r;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int nib = min(max(cnt - 8 * w, 0), 8);
-        r[w] = nib == 8 ? (int)0xAAAAAAAAu : (int)(0xAAAAAAAAu & ((1u << (4 * nib)) - 1u));
-    }
-    return r;
-}
 } // namespace
 
 __global__ __launch_bounds__(kLcThreads, 2) void local_mfma_kernel(LocalArgs a)
@@ -260,7 +234,7 @@ struct LocalHitDev {
 };
 } // namespace
 
-// one thread per winner: the forward pass over its diagonal -- prefix minimum updated on strict <, best on strict >
+// one thread per winner: the walk of its diagonal (local_walk)
 __global__ __launch_bounds__(64) void local_ends_kernel(const TopHitDev *__restrict__ top, const uint64_t *__restrict__ db,
                                                         const int64_t *__restrict__ db_off, const uint64_t *__restrict__ q_hp,
                                                         const int64_t *__restrict__ q_off, int64_t n_hits, int k_hits, int T,
@@ -275,23 +249,9 @@ __global__ __launch_bounds__(64) void local_ends_kernel(const TopHitDev *__restr
         const int d = top[i].offset - kLocalLagBias, score = kLocalScoreBias - (int)top[i].dist;
         const int64_t r0 = db_off[c], q0 = q_off[qi];
         const int n = (int)(db_off[c + 1] - r0), k = (int)(q_off[qi + 1] - q0);
-        const uint64_t *q = q_hp + q0, *r = db + r0;
-        const int ja = max(0, -d), jb = min(k, n - d);
-        int p = 0, mn = 0, mpos = ja, bs = 0, j0 = ja, j1 = ja;
-        for (int j = ja; j < jb; ++j) {
-            p += T - __popcll(q[j] ^ r[d + j]);
-            if (p - mn > bs) {
-                bs = p - mn;
-                j0 = mpos;
-                j1 = j + 1;
-            }
-            if (p < mn) {
-                mn = p;
-                mpos = j + 1;
-            }
-        }
-        if (bs != score) atomicAdd(disagree, 1u);
-        hit = {bs, top[i].clip, d, (uint32_t)j0, (uint32_t)(j1 - j0), (uint32_t)(T * (j1 - j0) - bs)};
+        const LocalRun run = local_walk(q_hp + q0, db + r0, d, k, n, T);
+        if (run.score != score) atomicAdd(disagree, 1u);
+        hit = {run.score, top[i].clip, d, (uint32_t)run.j0, (uint32_t)(run.j1 - run.j0), (uint32_t)(T * (run.j1 - run.j0) - run.score)};
     }
     out[i] = hit;
 }

@@ -13,6 +13,7 @@
 #include "fft_lds.h"
 #include "fft_rows.h"
 #include "index_plan.h"
+#include "join_plan.h"
 #include "streams_plan.h"
 #include "xcorr_plan.h"
 
@@ -443,7 +444,9 @@ void launch_overlap_stats(const void *d_tab, int n_q, int n_clips, int splits, c
 // overlap rule.  The rows a of a pass are row groups g0 .. g0 + n_groups - 1 (32 rows each); the pairs (group, b) with b above
 // the group's first row are numbered by d_pair_first [n_groups + 1], n_pairs of them in all (> 0); each has `splits`
 // workgroups.  d_tab [32 n_groups][n_clips][splits] of 16-byte entries {dist, overlap, lag, 0}, every byte preset to 0xff.
-// A row is walked in slices of kSelfjoinSlice positions, a pair's lags in chunks of kSelfjoinChunk.
+// A row is walked in slices of kSelfjoinSlice positions, a pair's lags in chunks of kSelfjoinChunk.  The scan's geometry, a
+// workgroup's pair, the walk of a chunk and the selection kernels are in join_scan.h, shared by the three joins; the plan
+// of the passes is join_plan.h's.
 constexpr int kSelfjoinChunk = 1024;
 constexpr int kSelfjoinSlice = 32;
 constexpr int kSelfjoinMaxLen = (1 << 18) - 1; // hashprints of a recording: 64 L < 2^24 keeps the fp32 accumulators exact
@@ -458,20 +461,16 @@ void launch_selfjoin_select(void *d_tab, int n_cols, int col0, int splits, int r
                             int *d_row_count, int64_t *d_row_first, uint32_t clip_base, void *d_out, int64_t cap, int64_t *d_count, hipStream_t s);
 // the index joined with n_x recordings that are not in it: launch_selfjoin_scan over the list "the
 // n_index slots of the index, then the externals d_x / d_x_off [n_x + 1]" with b an external only.  The pairs (group, b) of a
-// pass are numbered by d_pair_first as join_group_pairs counts them: pair i of group g is b = max(n_index, 32 g + 1) + i.  Rows
-// at or above n_index are masked unless among_new.  d_tab [32 n_groups][n_x][splits]: the columns are the externals
-// (launch_selfjoin_select with col0 = n_index).
-inline int64_t join_group_pairs(int64_t n_index, int64_t n_x, int among_new, int64_t g)
-{
-    if (32 * g >= (among_new ? n_index + n_x : n_index)) return 0; // (no row of the group is launched)
-    return std::max<int64_t>(n_index + n_x - std::max(n_index, 32 * g + 1), 0);
-}
+// pass are numbered by d_pair_first as join_group_pairs (join_plan.h) counts them: pair i of group g is
+// b = max(n_index, 32 g + 1) + i.  Rows at or above n_index are masked unless among_new.  d_tab [32 n_groups][n_x][splits]:
+// the columns are the externals (launch_selfjoin_select with col0 = n_index).
 void launch_join_scan(bool popc, const uint64_t *d_db, const int64_t *d_db_off, int n_index, const uint64_t *d_x, const int64_t *d_x_off, int n_x,
                       int among_new, int g0, int n_groups, const uint32_t *d_pair_first, uint32_t n_pairs, int min_overlap, int splits,
                       void *d_tab, hipStream_t s);
 // the local self-join (k_localjoin.hip): for clips a < b the best-scoring run of consecutive hashprints
 // of a on any diagonal of b, score = sum of max_rate - popcount over the run.  Passes, row groups, d_pair_first, n_pairs,
-// splits, slices and chunks are launch_selfjoin_scan's; min_len = ceil(min_score / max_rate) takes min_overlap's part.
+// splits, slices and chunks are launch_selfjoin_scan's -- the same code, join_scan.h; min_len = ceil(min_score / max_rate)
+// takes min_overlap's part.  The step's pieces and the walk of a diagonal are the local search's (local_rule.h).
 // d_tab [32 n_groups][n_clips][splits] of 8-byte keys (kLocaljoinScoreBias - score) << 32 | (lag + kLocaljoinLagBias), every
 // byte preset to 0xff: smaller is better, and the fold of a pair's splits is their minimum.
 constexpr int kLocaljoinScoreBias = 1 << 24; // above every score: 31 * kSelfjoinMaxLen < 2^23

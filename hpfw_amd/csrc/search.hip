@@ -672,7 +672,7 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
         // the chunks of a (group, clip) pair go to `splits` workgroups
         const int64_t chunks = std::max<int64_t>((n_max + k_max - 2 * min_overlap) / hpfw::kOverlapChunk + 1, 1);
         const int64_t pairs = n_clips * (mfma ? (n_q + 31) / 32 : n_q);
-        const int64_t splits = overlap_splits(chunks, pairs, "HPFW_OVERLAP_SPLITS");
+        const int64_t splits = hpfw::overlap_splits(chunks, pairs, env_forced_splits("HPFW_OVERLAP_SPLITS"));
         // queries are processed in groups so the table stays below 1 GiB
         int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 26) / (n_clips * splits) / 32 * 32);
         qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);

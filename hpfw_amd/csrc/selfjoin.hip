@@ -48,6 +48,7 @@ struct JoinSide {
 
 // The passes of either join, inside ordered_call.  The rows are the 32-row groups of the index's slots (the join: then the
 // externals), a pass's table is [its rows][columns][splits] with the index's clips as columns (the join: the externals).
+// The plan of the passes is join_plan.h's, their loop join_run_passes below, shared with the local self-join (localjoin.hip).
 static int join_passes(hpfw_gpu *h, hipStream_t s, const JoinSide *x, int min_overlap, int rate_num, int rate_den, hpfw_dup_pair *d_out,
                        int64_t cap, int64_t *d_count)
 {
@@ -60,65 +61,73 @@ static int join_passes(hpfw_gpu *h, hipStream_t s, const JoinSide *x, int min_ov
     if (n_clips < 2 || n_cols < 1 || (x ? x->longest : n_max) < min_overlap) return 0; // no pair has a candidate
     if ((rc = upload_db_off(h, s))) return rc;
     const bool popc = std::getenv("HPFW_SELFJOIN_POPC") != nullptr;
-    // the pairs (row group, b): b above the group's first row (the join: an external, hpfw_gpu_join_plan)
+    // the pairs (row group, b): b above the group's first row (the join: an external, hpfw_gpu_join_plan); no pairs: an empty
+    // index joined without among_new.  The table stays at or below 1 GiB
     const int64_t n_groups = ((x && !x->among_new ? n_index : n_clips) + 31) / 32;
-    auto group_pairs = [&](int64_t g) {
-        return x ? hpfw::join_group_pairs(n_index, x->n, x->among_new, g) : std::max<int64_t>(n_clips - 32 * g - 1, 0);
-    };
-    int64_t pairs = 0;
-    for (int64_t g = 0; g < n_groups; ++g) pairs += group_pairs(g);
-    if (pairs == 0) return 0; // (an empty index joined without among_new)
-    // the chunks of a pair go to `splits` workgroups
-    const int64_t chunks = (2 * n_max - 2 * min_overlap) / hpfw::kSelfjoinChunk + 1;
-    int64_t splits = overlap_splits(chunks, pairs, "HPFW_SELFJOIN_SPLITS");
-    // row groups are processed in passes so that the table stays at or below 1 GiB (2^26 entries; HPFW_SELFJOIN_TABLE_KB:
-    // that many KiB, at least one row group's, for tests of more than one pass)
-    int64_t budget = (int64_t)1 << 26;
-    if (const char *e = std::getenv("HPFW_SELFJOIN_TABLE_KB")) budget = std::min(std::max<int64_t>(std::atoll(e) * 64, 32 * n_cols), budget);
-    splits = std::min(splits, budget / (32 * n_cols));
-    const int64_t pass_groups = std::min(n_groups, budget / (32 * n_cols * splits));
-    const int64_t n_passes = (n_groups + pass_groups - 1) / pass_groups;
-    // every pass numbers its pairs from 0: pair_first [pass_groups + 1] per pass
-    std::vector<uint32_t> pair_first((size_t)(n_passes * (pass_groups + 1)), 0);
-    for (int64_t p = 0; p < n_passes; ++p) {
-        uint32_t *pf = pair_first.data() + p * (pass_groups + 1);
-        for (int64_t i = 0; i < pass_groups; ++i) pf[i + 1] = pf[i] + (uint32_t)(p * pass_groups + i < n_groups ? group_pairs(p * pass_groups + i) : 0);
-    }
-    if ((rc = ensure(h->index.d_sj_pairs, pair_first.size() * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->index.d_sj_pairs.get(), pair_first.data(), pair_first.size() * 4, hipMemcpyHostToDevice, s));
-    if (x) {
+    const hpfw::JoinPlan plan = hpfw::join_plan(
+        n_groups,
+        [&](int64_t g) { return x ? hpfw::join_group_pairs(n_index, x->n, x->among_new, g) : hpfw::selfjoin_group_pairs(n_clips, g); }, n_cols,
+        n_max, min_overlap, hpfw::kSelfjoinChunk, 16, env_forced_splits("HPFW_SELFJOIN_SPLITS"), env_table_kb("HPFW_SELFJOIN_TABLE_KB"));
+    if (x && plan.pairs) { // (join_run_passes waits for the stream: the caller's offsets have been read)
         if ((rc = ensure(h->index.d_sj_x_off, (size_t)(x->n + 1) * 8))) return rc;
         HIP_TRY(hipMemcpyAsync(h->index.d_sj_x_off.get(), x->off, (size_t)(x->n + 1) * 8, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(hipStreamSynchronize(s)); // (pair_first and the caller's offsets have been read)
-    const size_t tab_bytes = (size_t)(32 * pass_groups * n_cols * splits) * 16;
-    if ((rc = ensure(h->index.d_sj_tab, tab_bytes))) return rc;
+    const uint64_t *db = h->index.d_db.as<uint64_t>();
+    const int64_t *db_off = h->index.d_db_off.as<int64_t>();
+    return join_run_passes(
+        h, s, plan, n_groups, n_cols, 16, "selfjoin scan",
+        [&](const JoinPass &p) {
+            if (x)
+                hpfw::launch_join_scan(popc, db, db_off, (int)n_index, x->d_hp, h->index.d_sj_x_off.as<int64_t>(), (int)x->n, x->among_new, p.g0,
+                                       p.n_groups, p.d_pair_first, p.n_pairs, min_overlap, p.splits, p.d_tab, s);
+            else
+                hpfw::launch_selfjoin_scan(popc, db, db_off, (int)n_clips, p.g0, p.n_groups, p.d_pair_first, p.n_pairs, min_overlap, p.splits,
+                                           p.d_tab, s);
+        },
+        "selfjoin select",
+        [&](const JoinPass &p) {
+            hpfw::launch_selfjoin_select(p.d_tab, (int)n_cols, (int)col0, p.splits, 32 * p.g0, 32 * p.n_groups, (uint32_t)rate_num,
+                                         (uint32_t)rate_den, p.d_row_count, p.d_row_first, h->index.clip_base, d_out, cap, d_count, s);
+        });
+}
+
+int join_run_passes(hpfw_gpu *h, hipStream_t s, const hpfw::JoinPlan &plan, int64_t n_groups, int64_t n_cols, size_t entry_bytes,
+                    const char *scan_what, const std::function<void(const JoinPass &)> &scan, const char *select_what,
+                    const std::function<void(const JoinPass &)> &select)
+{
+    int rc;
+    if (plan.pairs == 0) return 0;
+    const int64_t pass_groups = plan.pass_groups;
+    if ((rc = ensure(h->index.d_sj_pairs, plan.pair_first.size() * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->index.d_sj_pairs.get(), plan.pair_first.data(), plan.pair_first.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (pair_first has been read)
+    if ((rc = ensure(h->index.d_sj_tab, (size_t)(32 * pass_groups * n_cols * plan.splits) * entry_bytes))) return rc;
     if ((rc = ensure(h->index.d_sj_rows, (size_t)(32 * pass_groups) * (8 + 4)))) return rc;
     int64_t *d_row_first = h->index.d_sj_rows.as<int64_t>();
     int *d_row_count = reinterpret_cast<int *>(d_row_first + 32 * pass_groups);
-    for (int64_t p = 0; p < n_passes; ++p) {
+    for (int64_t p = 0; p < plan.n_passes; ++p) {
         const int64_t g0 = p * pass_groups, ng = std::min(pass_groups, n_groups - g0);
-        const uint32_t *d_pf = h->index.d_sj_pairs.as<uint32_t>() + p * (pass_groups + 1);
-        const uint32_t n_pairs = pair_first[(size_t)(p * (pass_groups + 1) + ng)];
-        if (n_pairs == 0) continue; // (the last group is the last clip alone)
-        HIP_TRY(hipMemsetAsync(h->index.d_sj_tab.get(), 0xff, (size_t)(32 * ng * n_cols * splits) * 16, s));
+        JoinPass pass = {};
+        pass.g0 = (int)g0;
+        pass.n_groups = (int)ng;
+        pass.d_pair_first = h->index.d_sj_pairs.as<uint32_t>() + p * (pass_groups + 1);
+        pass.n_pairs = plan.pass(p)[ng];
+        pass.splits = (int)plan.splits;
+        pass.d_tab = h->index.d_sj_tab.get();
+        pass.d_row_count = d_row_count;
+        pass.d_row_first = d_row_first;
+        if (pass.n_pairs == 0) continue; // (the last group is the last clip alone)
+        HIP_TRY(hipMemsetAsync(pass.d_tab, 0xff, (size_t)(32 * ng * n_cols * plan.splits) * entry_bytes, s));
         {
             Timed t(h, K_SCAN, s);
-            if (x)
-                hpfw::launch_join_scan(popc, h->index.d_db.as<uint64_t>(), h->index.d_db_off.as<int64_t>(), (int)n_index, x->d_hp,
-                                       h->index.d_sj_x_off.as<int64_t>(), (int)x->n, x->among_new, (int)g0, (int)ng, d_pf, n_pairs, min_overlap,
-                                       (int)splits, h->index.d_sj_tab.get(), s);
-            else
-                hpfw::launch_selfjoin_scan(popc, h->index.d_db.as<uint64_t>(), h->index.d_db_off.as<int64_t>(), (int)n_clips, (int)g0, (int)ng,
-                                           d_pf, n_pairs, min_overlap, (int)splits, h->index.d_sj_tab.get(), s);
+            scan(pass);
         }
-        if ((rc = check_launch("selfjoin scan"))) return rc;
+        if ((rc = check_launch(scan_what))) return rc;
         {
             Timed t(h, K_TOPK, s);
-            hpfw::launch_selfjoin_select(h->index.d_sj_tab.get(), (int)n_cols, (int)col0, (int)splits, (int)(32 * g0), (int)(32 * ng),
-                                         (uint32_t)rate_num, (uint32_t)rate_den, d_row_count, d_row_first, h->index.clip_base, d_out, cap, d_count, s);
+            select(pass);
         }
-        if ((rc = check_launch("selfjoin select"))) return rc;
+        if ((rc = check_launch(select_what))) return rc;
     }
     return 0;
 }
@@ -162,12 +171,8 @@ int hpfw_gpu_join_plan(int64_t n_clips, int64_t n_x, int among_new, int64_t grou
     if (among_new < 0 || among_new > 1) return fail(HPFW_E_INVALID, "join: among_new must be 0 or 1");
     if (!pair_first) return fail(HPFW_E_INVALID, "null argument");
     if (n_clips + n_x > ((int64_t)1 << 21)) return fail(HPFW_E_UNSUPPORTED, "join: more than 2097152 recordings");
-    pair_first[0] = 0;
-    for (int64_t i = 0; i < n_groups; ++i) {
-        const int64_t next = (int64_t)pair_first[i] + hpfw::join_group_pairs(n_clips, n_x, among_new, group0 + i);
-        if (next > (int64_t)UINT32_MAX) return fail(HPFW_E_UNSUPPORTED, "join plan: more than 2^32 - 1 pairs in a pass");
-        pair_first[i + 1] = (uint32_t)next;
-    }
+    if (!hpfw::join_pair_first(group0, n_groups, [&](int64_t g) { return hpfw::join_group_pairs(n_clips, n_x, among_new, g); }, pair_first))
+        return fail(HPFW_E_UNSUPPORTED, "join plan: more than 2^32 - 1 pairs in a pass");
     return 0;
 }
 

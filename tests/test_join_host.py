@@ -5,6 +5,7 @@ import ctypes
 import inspect
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -227,6 +228,22 @@ def test_refused_before_any_file_is_read():
         with pytest.raises(hpfw_amd.HpfwError) as e:
             call(16)
         assert e.value.status == E_UNSUPPORTED
+
+
+def test_pass_plan_under_sanitizers(tmp_path):
+    """join_plan.h is plain C++: the passes of the three joins for 0 to 70 clips and recordings, both entry sizes, tables
+    that force 1, 2, 3 and many passes and forced splits -- the plan's properties and the formulas the joins had before
+    the header, in a program of its own under ASan and UBSan"""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    exe = tmp_path / "join_plan_check"
+    src = os.path.join(ROOT, "tests", "emu", "join_plan_check.cpp")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "join_plan_check ok" in r.stdout
 
 
 FACADE = r"""
