@@ -15,13 +15,7 @@ int dtw_check_queries(const void *h, const int64_t *q_off, int64_t n_q, const vo
 {
     if (!h || !q_off || !out) return fail(HPFW_E_INVALID, "null argument");
     if (n_q < 0) return fail(HPFW_E_INVALID, "n_q must not be negative");
-    *k_max = 0;
-    for (int64_t i = 0; i < n_q; ++i) {
-        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-        *k_max = std::max(*k_max, q_off[i + 1] - q_off[i]);
-    }
-    if (*k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
-    return 0;
+    return check_q_off(q_off, n_q, k_max);
 }
 
 int dtw_check_pairs(const int32_t *pairs, int64_t n_pairs)
@@ -164,12 +158,7 @@ int search_dtw_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off,
             if (candidates) {
                 hpfw::launch_dtw_rank(a.out, ng, candidates, k, base, d_out + g0 * k, s);
             } else {
-                if (n_clips >= 16384 && ng <= 64) { // (as the plain search chooses)
-                    if ((rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes((int)ng, k)))) return rc;
-                    hpfw::launch_topk_two_step(a.table, (int)ng, (int)n_clips, k, base, h->index.d_topk_scratch.get(), d_top, s);
-                } else {
-                    hpfw::launch_topk(a.table, (int)ng, (int)n_clips, k, base, d_top, s);
-                }
+                if ((rc = search_topk_rows(h, a.table, (int)ng, n_clips, k, d_top, s))) return rc;
                 hpfw::launch_dtw_finish(d_top, a.out, ng, k, per_q, base, d_out + g0 * k, s);
             }
             if ((rc = check_launch("dtw top-k"))) return rc;

@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "legacy_internal.h" // hpfw_internal_set_error (handle.hip), hpfw_internal_note_idle (plans.hip)
 #include "plan.h"
+#include "search_plan.h"
 
 using hpfw::DevBuf, hpfw::Event, hpfw::HostBuf, hpfw::Stream;
 
@@ -437,6 +438,58 @@ inline int64_t env_table_kb(const char *env_name)
     const char *e = std::getenv(env_name);
     return e ? std::max<int64_t>(std::atoll(e), 0) : -1;
 }
+
+// the offsets of n_q queries: in order, no query longer than 16000 hashprints; *k_max: the longest.  A call with both faults is
+// told of the order, or with in_turn (the search within sets) of the fault of its first faulty query
+inline int check_q_off(const int64_t *q_off, int64_t n_q, int64_t *k_max, bool in_turn = false)
+{
+    *k_max = 0;
+    for (int64_t i = 0; i < n_q; ++i) {
+        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
+        *k_max = std::max(*k_max, q_off[i + 1] - q_off[i]);
+        if (in_turn && *k_max > 16000) break;
+    }
+    if (*k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    return 0;
+}
+
+// the k smallest keys of each of ng rows of d_table [ng][n_clips] -> d_out [ng][k] (hpfw_hit).  One workgroup per query would
+// crawl through the whole table of a large index for a few queries: those go in two steps, through d_topk_scratch
+inline int search_topk_rows(hpfw_gpu *h, const uint64_t *d_table, int ng, int64_t n_clips, int k, void *d_out, hipStream_t s,
+                            const int32_t *d_set = nullptr)
+{
+    if (n_clips >= 16384 && ng <= 64) {
+        if (int rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes(ng, k))) return rc;
+        hpfw::launch_topk_two_step(d_table, ng, (int)n_clips, k, h->index.clip_base, h->index.d_topk_scratch.get(), d_out, s, d_set);
+    } else {
+        hpfw::launch_topk(d_table, ng, (int)n_clips, k, h->index.clip_base, d_out, s, d_set);
+    }
+    return 0;
+}
+
+// search.hip: the passes of a search over its queries, inside ordered_call (the plain, overlap and local searches; the group
+// size is search_plan.h's).  The index's and the queries' offsets go to the device, and with `expand` (the matrix-core scans)
+// d_qa is sized for a pass and the lengths of every group of 32 queries of the call go to d_gk, once.  Every pass of at most
+// qgroup queries (a multiple of 32) presets its ng rows of row_bytes in `table` to 0xff, then runs the steps in turn, each
+// under its kind's timer and its launches checked under its label; with `expand` the pass's image of the queries is
+// made ahead of the step marked `scan`, under its timer.
+struct QueryGroup {
+    int64_t g0;             // the pass's first query
+    int ng;                 // and how many it has
+    const int64_t *d_q_off; // [ng + 1] (device), the pass's first query at d_q_off[0]
+    const void *d_qa;       // with expand: launch_expand_queries' image of the pass, kt_pad rows per group of 32 ...
+    int kt_pad;
+    const int *d_gk;        // ... and [2 per group] the group's longest query and its shortest non-empty one
+    int k_min;              // with expand: the pass's shortest non-empty query (0: none)
+};
+struct SearchStep {
+    int kind; // K_SCAN, K_TOPK
+    const char *what;
+    bool scan; // the scan: it reads the pass's image of the queries
+    std::function<int(const QueryGroup &)> run;
+};
+int search_run_groups(hpfw_gpu *h, hipStream_t s, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int64_t k_max, int64_t qgroup,
+                      bool expand, DevBuf &table, size_t row_bytes, const std::vector<SearchStep> &steps);
 
 // selfjoin.hip: the passes of a join, inside ordered_call.  pair_first goes to d_sj_pairs, and the stream is waited for
 // once (whatever else the caller enqueued from host memory has been read); d_sj_tab and d_sj_rows are sized for a pass of

@@ -37,13 +37,12 @@
 #pragma once
 #include "kernels.h"
 #include "overlap_rule.h"
+#include "query_scan.h" // scan_products: a position's products
 
 namespace hpfw {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 constexpr int kJoinThreads = 512;                              // 8 waves
-constexpr int kJoinTiles = 4;                                  // lag tiles of 32 per wave
+constexpr int kJoinTiles = kScanTiles;                         // lag tiles of 32 per wave
 constexpr int kJoinWaveLags = 32 * kJoinTiles;                 // 128
 constexpr int kJoinWin = kSelfjoinChunk + kSelfjoinSlice;      // positions of b staged per slice (one spare)
 constexpr int kJoinBLoads = (kJoinWin + kJoinThreads - 1) / kJoinThreads; // positions of b per thread and slice

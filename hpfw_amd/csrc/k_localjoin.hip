@@ -74,15 +74,8 @@ __global__ __launch_bounds__(kJoinThreads, 2) void localjoin_mfma_kernel(Localjo
     const JoinChunk c = join_scan(
         a, smem_raw,
         [&](const v4i *ap, const v4i *bp, int j) {
-            const v4i a4 = ap[j * 64];
-            const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
+            scan_products(acc, ap, bp, j);
             // the tiles in turn: the vector work of one tile under the matrix instructions of the tiles after it
-#pragma unroll
-            for (int t = 0; t < kJoinTiles; ++t) {
-                const v4i b4 = bp[j + 32 * t];
-                const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
-            }
 #pragma unroll
             for (int t = 0; t < kJoinTiles; ++t) {
                 acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones_a, step_b, acc[t], 4, 4, 0, one, 0, one);

@@ -3,8 +3,7 @@
 // [j0, j1) at lag d scores sum x_j; a clip's candidate is its best run over all lags: larger score, then smaller lag, then
 // smaller j1, then smaller j0.  Exact integers throughout.
 //
-// (a) local_mfma_kernel is hamming_mfma_kernel (k_search_mfma.hip) with the clip's window zero-filled on both sides, as
-// overlap_mfma_kernel's: 32 queries x 1024 lags of one clip per workgroup, the same image of the queries.  The accumulators
+// (a) local_mfma_kernel is the scan of query_scan.h with the clip's window zero-filled on both sides.  The accumulators
 // are read after every position j.  With acc_j the accumulator after step j, acc_j - (64 - 2 T)(j + 1) is twice the prefix
 // sum of x, where a position outside the query or the clip (fp4 zeros: the product adds nothing) counts as x = T - 32 < 0.
 // The best run's score is the largest prefix sum minus the smallest one before it; the scan keeps that difference, not the
@@ -24,22 +23,14 @@
 // and its mismatching bits, and the score again, which must be the scan's.
 #include "kernels.h"
 #include "local_rule.h"
+#include "query_scan.h"
 
 namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 namespace {
-constexpr int kLcThreads = 512;                            // 8 waves
-constexpr int kLcTiles = 4;                                // lag tiles of 32 per wave
-constexpr int kLcWaveLags = 32 * kLcTiles;                 // 128
-constexpr int kLcWgLags = kLcWaveLags * (kLcThreads / 64); // 1024 lags per workgroup
-constexpr int kLcChunk = 16;                               // positions j per staged chunk of the A operand, as kSmChunk
-static_assert(kLcWgLags == kLocalChunk, "kernels.h states the chunk");
 static_assert(31 * 16000 < kLocalScoreBias, "a score is below the bias");
-constexpr unsigned kNoKey = 0xffffffffu;
 
 struct LocalArgs {
     const uint64_t *db;
@@ -50,7 +41,7 @@ struct LocalArgs {
     int n_q;
     const v4i *qa;        // expanded queries of this launch (expand_queries_kernel's image)
     int kt_pad;
-    const int *gk;        // [g]: longest query of group g
+    const int *gk;        // [2 g]: longest query of group g
     int max_rate;
     int chunks;           // workgroups (of 1024 lags) per clip; the first begins at lag 1 - (the group's longest query; on the
                           // popcount route: the query's length)
@@ -68,118 +59,54 @@ __device__ __forceinline__ void offer(unsigned long long *best, unsigned key, in
 
 } // namespace
 
-__global__ __launch_bounds__(kLcThreads, 2) void local_mfma_kernel(LocalArgs a)
+__global__ __launch_bounds__(kScanThreads, 2) void local_mfma_kernel(LocalArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_lane = lane & 31, h = lane >> 5;
     const int clip = blockIdx.x / a.chunks, wc = blockIdx.x - clip * a.chunks, g = blockIdx.y;
     const int64_t r0 = a.db_off[clip];
     const int n = (int)(a.db_off[clip + 1] - r0);
-    const int kt = a.gk[g];
+    const int kt = a.gk[2 * g];
     if (n <= 0 || kt <= 0) return;
-    const int d0 = 1 - kt + wc * kLcWgLags; // the group's lags run 1 - kt .. n - 1
+    const int d0 = 1 - kt + wc * kScanWgLags; // the group's lags run 1 - kt .. n - 1
     if (d0 > n - 1) return;
 
-    const int win = kLcWgLags + kt;                      // window slots (one spare)
-    v4i *ldsB = reinterpret_cast<v4i *>(smem_raw);       // [2][win]: plane h = bits [32 h, 32 h + 32) of each hashprint
-    v4i *ldsA = ldsB + 2 * win;                          // [2][kLcChunk][64]
-    unsigned *red = reinterpret_cast<unsigned *>(ldsA + 2 * kLcChunk * 64) + 32; // [8 waves][32 queries]
+    const int win = kScanWgLags + kt;
+    const ScanLds l = scan_lds(smem_raw, win);
+    scan_stage_window(l.B, win, a.db, r0, n, d0, tid);
 
-    // clip positions d0 .. d0 + win - 1, expanded; fp4 zeros before the clip's start and past its end
-    for (int i = tid; i < win; i += kLcThreads) {
-        const int gi = d0 + i;
-        v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-        if (gi >= 0 && gi < n) {
-            const uint64_t w = a.db[r0 + gi];
-            lo = expand32((uint32_t)w);
-            hi = expand32((uint32_t)(w >> 32));
-        }
-        ldsB[i] = lo;
-        ldsB[win + i] = hi;
-    }
-    const v4i *qa = a.qa + (int64_t)g * a.kt_pad * 64;
-    const int n_chunks = (kt + kLcChunk - 1) / kLcChunk;
-    v4i st0 = qa[tid], st1 = qa[tid + kLcThreads]; // 16 steps x 64 lanes = 1024 entries: two per thread
-    ldsA[tid] = st0;
-    ldsA[tid + kLcThreads] = st1;
-    __syncthreads();
-
-    f32x16 acc[kLcTiles];
-    i32x16 bs[kLcTiles];
+    f32x16 acc[kScanTiles];
+    i32x16 bs[kScanTiles];
 #pragma unroll
-    for (int t = 0; t < kLcTiles; ++t) {
+    for (int t = 0; t < kScanTiles; ++t) {
         acc[t] = f32x16{0};
         bs[t] = i32x16{0};
     }
     const int one = 0x7f7f7f7f; // E8M0 scale 2^0
-    const v4i *bp = ldsB + h * win + wave * kLcWaveLags + n_lane;
-    // a wave whose 128 lags all lie past n - 1 (the clip's last chunk) multiplies nothing: it only helps staging
-    const bool live = d0 + wave * kLcWaveLags <= n - 1;
     // the step's constant: every row of +1 times every column with 64 - 2 T values of -1 over K, half h of K in lanes 32 h ..
     const v8i ones_a = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};
     const v4i c4 = minus_ones(64 - 2 * a.max_rate - 32 * h);
     const v8i step_b = {c4.x, c4.y, c4.z, c4.w, 0, 0, 0, 0};
-
-    for (int c = 0; c < n_chunks; ++c) {
-        const bool more = c + 1 < n_chunks;
-        if (more) { // next chunk of A into registers while this one multiplies
-            st0 = qa[(c + 1) * (kLcChunk * 64) + tid];
-            st1 = qa[(c + 1) * (kLcChunk * 64) + tid + kLcThreads];
-        }
-        const v4i *ap = ldsA + (c & 1) * (kLcChunk * 64) + lane;
-        const int jn = min(kLcChunk, kt - c * kLcChunk);
-        const v4i *bj = bp + c * kLcChunk;
-        for (int j = 0; live && j < jn; ++j) {
-            const v4i a4 = ap[j * 64];
-            const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
-            // the tiles in turn: the vector work of one tile under the matrix instructions of the tiles after it
+    // a wave whose 128 lags all lie past n - 1 (the clip's last chunk) is not live
+    scan_walk(a.qa + (int64_t)g * a.kt_pad * 64, l.A, l.B + h * win + wave * kScanWaveLags + n_lane, kt, d0 + wave * kScanWaveLags <= n - 1, tid,
+              lane, [&](const v4i *ap, const v4i *bj, int j) {
+                  scan_products(acc, ap, bj, j);
+                  // the tiles in turn: the vector work of one tile under the matrix instructions of the tiles after it
 #pragma unroll
-            for (int t = 0; t < kLcTiles; ++t) {
-                const v4i b4 = bj[j + 32 * t];
-                const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
-            }
-#pragma unroll
-            for (int t = 0; t < kLcTiles; ++t) {
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones_a, step_b, acc[t], 4, 4, 0, one, 0, one);
-                if (t > 0) scan_tile(acc[t - 1], bs[t - 1]);
-            }
-            scan_tile(acc[kLcTiles - 1], bs[kLcTiles - 1]);
-        }
-        if (more) {
-            v4i *dst = ldsA + ((c + 1) & 1) * (kLcChunk * 64);
-            dst[tid] = st0;
-            dst[tid + kLcThreads] = st1;
-        }
-        __syncthreads();
-    }
+                  for (int t = 0; t < kScanTiles; ++t) {
+                      acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones_a, step_b, acc[t], 4, 4, 0, one, 0, one);
+                      if (t > 0) scan_tile(acc[t - 1], bs[t - 1]);
+                  }
+                  scan_tile(acc[kScanTiles - 1], bs[kScanTiles - 1]);
+              });
 
     // bs[t][reg]: twice the best score of query row m = (reg & 3) + 8 (reg >> 2) + 4 h at lag d0 + wave 128 + t 32 + n_lane
-    unsigned *wave_red = red + wave * 32;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int m = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        unsigned key = kNoKey;
-#pragma unroll
-        for (int t = 0; t < kLcTiles; ++t) {
-            const int score = (int)__int_as_float(bs[t][reg]) >> 1;
-            const unsigned cand = chunk_key(score, wave * kLcWaveLags + t * 32 + n_lane);
-            if (score > 0 && cand < key) key = cand;
-        }
-#pragma unroll
-        for (int s = 16; s >= 1; s >>= 1) { // the best of the 32 lag columns of this half-wave
-            const unsigned o = (unsigned)__shfl_xor((int)key, s);
-            key = o < key ? o : key;
-        }
-        if (n_lane == 0) wave_red[m] = key;
-    }
-    __syncthreads();
-    if (tid < 32) {
-        unsigned key = red[tid];
-        for (int w = 1; w < kLcThreads / 64; ++w) key = red[w * 32 + tid] < key ? red[w * 32 + tid] : key;
-        const int qi = g * 32 + tid;
-        if (qi < a.n_q && key != kNoKey) offer(a.best + (int64_t)qi * a.n_clips + clip, key, d0);
-    }
+    const unsigned key = scan_row_min(l.red, tid, wave, n_lane, h, [&](int reg, int t) {
+        const int score = (int)__int_as_float(bs[t][reg]) >> 1;
+        return score > 0 ? chunk_key(score, wave * kScanWaveLags + t * 32 + n_lane) : kScanNoKey;
+    });
+    const int qi = g * 32 + tid;
+    if (tid < 32 && qi < a.n_q && key != kScanNoKey) offer(a.best + (int64_t)qi * a.n_clips + clip, key, d0);
 }
 
 // one workgroup per (query, clip, chunk): a thread takes four lags of the chunk and walks their diagonals
@@ -191,11 +118,11 @@ __global__ __launch_bounds__(256) void local_popc_kernel(LocalArgs a)
     const int64_t r0 = a.db_off[clip], q0 = a.q_off[qi];
     const int n = (int)(a.db_off[clip + 1] - r0), k = (int)(a.q_off[qi + 1] - q0), T = a.max_rate;
     if (n <= 0 || k <= 0) return;
-    const int d0 = 1 - k + wc * kLcWgLags;
+    const int d0 = 1 - k + wc * kScanWgLags;
     if (d0 > n - 1) return;
     const uint64_t *q = a.q + q0, *r = a.db + r0;
-    unsigned key = kNoKey;
-    for (int e = 0; e < kLcWgLags / 256; ++e) {
+    unsigned key = kScanNoKey;
+    for (int e = 0; e < kScanWgLags / 256; ++e) {
         const int lo = tid + 256 * e, d = d0 + lo;
         if (d > n - 1) break;
         const int ja = max(0, -d), jb = min(k, n - d);
@@ -216,7 +143,7 @@ __global__ __launch_bounds__(256) void local_popc_kernel(LocalArgs a)
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 4; ++w) key = red[w] < key ? red[w] : key;
-        if (key != kNoKey) offer(a.best + (int64_t)qi * a.n_clips + clip, key, d0);
+        if (key != kScanNoKey) offer(a.best + (int64_t)qi * a.n_clips + clip, key, d0);
     }
 }
 
@@ -260,10 +187,7 @@ void launch_local_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_clip
                        int kt_pad, const int *d_gk, int k_max, int max_rate, int chunks, uint64_t *d_best, hipStream_t s)
 {
     static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(local_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set.mark();
-    }
+    scan_allow_lds(attr_set, {reinterpret_cast<const void *>(local_mfma_kernel)});
     LocalArgs a = {};
     a.db = d_db;
     a.db_off = d_db_off;
@@ -277,7 +201,7 @@ void launch_local_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_clip
     a.chunks = chunks;
     a.best = reinterpret_cast<unsigned long long *>(d_best);
     const dim3 grid((unsigned)n_clips * (unsigned)chunks, (unsigned)((n_q + 31) / 32));
-    hipLaunchKernelGGL(local_mfma_kernel, grid, dim3(kLcThreads), hamming_mfma_lds_bytes(k_max), s, a);
+    hipLaunchKernelGGL(local_mfma_kernel, grid, dim3(kScanThreads), query_scan_lds_bytes(k_max), s, a);
 }
 
 void launch_local_popc(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const uint64_t *d_q, const int64_t *d_q_off, int n_q,

@@ -9,16 +9,12 @@
 // one hashprint position (K = 64 bits): 1024 pairs in 32 cycles per SIMD, against 4 VALU lane-ops
 // per pair for xor/popcount -- the scan is issue-bound, not memory-bound, so this is where the time is.
 //
-// Layout of the contraction (no diagonal sums, no lane shuffles in the loop):
-//   M = 32 queries of a group, N = offsets, K = (position j, bit): the operand B of step j for offset
-//   column n is the reference hashprint off + j -- a window of the clip sliding through LDS, one
-//   ds_read_b128 per MFMA; the operand A of step j (the 32 queries' hashprint j) is read once per
-//   step and used by the wave's 4 offset tiles.  Workgroup = 8 waves = one query group x 1024
-//   offsets of one clip; queries shorter than the group's longest are zero-padded (fp4 0 adds
-//   nothing), windows past the end of the clip are zeros, and k = min(k, n) (storage.h:37-39) falls
-//   out of that: a query longer than the clip meets zeros beyond n.
+// Layout of the contraction (no diagonal sums, no lane shuffles in the loop): query_scan.h, shared with the overlap and local
+// searches.  What is this kernel's own: the offsets of a clip are 0 .. n - k, a workgroup has one chunk of them, queries shorter
+// than the group's longest are zero-padded (fp4 0 adds nothing), windows past the end of the clip are zeros, and k = min(k, n)
+// (storage.h:37-39) falls out of that: a query longer than the clip meets zeros beyond n.
 #include "kernels.h"
-#include "overlap_rule.h"
+#include "query_scan.h"
 
 #include <algorithm>
 
@@ -26,15 +22,7 @@ namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
-typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kSmThreads = 512;            // 8 waves
-constexpr int kSmTiles = 4;                // offset tiles of 32 per wave
-constexpr int kSmWaveOffs = 32 * kSmTiles; // 128
-constexpr int kSmWgOffs = kSmWaveOffs * (kSmThreads / 64); // 1024 offsets per workgroup
-constexpr int kSmChunk = 16;               // positions j per staged chunk of the A operand (16 KB)
-// (expand32, 32 bits -> 32 E2M1 nibbles, bit i in nibble i, is overlap_rule.h's: the overlap search reads this file's image)
 
 // qa [n_groups][kt_pad][64 lanes][16 B]: lane (m, h) of step j holds bits [32 h, 32 h + 32) of
 // hashprint j of query 32 g + m, or zeros past the query's end / past the last query.
@@ -78,7 +66,7 @@ struct SearchMfmaArgs {
     const int64_t *q_off; // [n_q + 1] (device), this launch's first query at q_off[0]
     int n_q;
     const v4i *qa;        // expanded queries of this launch
-    int kt_pad;           // rows of qa per group (multiple of kSmChunk)
+    int kt_pad;           // rows of qa per group (multiple of kScanChunk)
     const int *gk;        // [2 g]: longest query of group g; [2 g + 1]: its shortest non-empty one
     uint64_t *best;       // [n_q][n_clips], initialised to ~0
     int chunks;           // workgroups (of 1024 offsets) per clip
@@ -90,7 +78,7 @@ struct SearchMfmaArgs {
 };
 
 template <bool KNN, bool SET>
-__global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaArgs a)
+__global__ __launch_bounds__(kScanThreads, 4) void hamming_mfma_kernel(SearchMfmaArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_lane = lane & 31, h = lane >> 5;
@@ -99,29 +87,14 @@ __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaA
     const int64_t r0 = clip_span<SET>(a.db_off, a.set, clip, n);
     const int kt = KNN ? a.win : a.gk[2 * g];
     if (n <= 0 || kt <= 0) return;
-    const int o0 = (blockIdx.x - clip * a.chunks) * kSmWgOffs;
+    const int o0 = (blockIdx.x - clip * a.chunks) * kScanWgLags;
     const int kmin = KNN ? a.win : min(a.gk[2 * g + 1], n);
     if (o0 > n - kmin) return; // no query of the group has an offset in this chunk (off <= n - k)
 
-    const int win = kSmWgOffs + kt;                      // window slots (one spare)
-    v4i *ldsB = reinterpret_cast<v4i *>(smem_raw);       // [2][win]: plane h = bits [32 h, 32 h + 32) of each hashprint
-                                                         // (lanes of a half-wave read 16 B apart: no bank conflicts)
-    v4i *ldsA = ldsB + 2 * win;                          // [2][kSmChunk][64]
-    int *kq_s = reinterpret_cast<int *>(ldsA + 2 * kSmChunk * 64); // [32] effective k of the group's queries
-    unsigned *red = reinterpret_cast<unsigned *>(kq_s + 32);       // [8 waves][32 queries]
-
-    // the clip's hashprints o0 .. o0 + win - 1, expanded; zeros past the end of the clip
-    for (int i = tid; i < win; i += kSmThreads) {
-        const int gi = o0 + i;
-        v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-        if (gi < n) {
-            const uint64_t w = a.db[r0 + gi];
-            lo = expand32((uint32_t)w);
-            hi = expand32((uint32_t)(w >> 32));
-        }
-        ldsB[i] = lo;
-        ldsB[win + i] = hi;
-    }
+    const int win = kScanWgLags + kt;
+    const ScanLds l = scan_lds(smem_raw, win);
+    int *kq_s = l.len; // effective k of the group's queries
+    scan_stage_window(l.B, win, a.db, r0, n, o0, tid);
     if (tid < 32) {
         const int qi = g * 32 + tid;
         int k = 0;
@@ -133,45 +106,46 @@ __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaA
         }
         kq_s[tid] = k;
     }
-    // first chunk of the A operand
-    const v4i *qa = a.qa + (int64_t)g * a.kt_pad * 64;
-    const int n_chunks = (kt + kSmChunk - 1) / kSmChunk;
-    v4i st0 = qa[tid], st1 = qa[tid + kSmThreads]; // 16 steps x 64 lanes = 1024 entries: two per thread
-    ldsA[tid] = st0;
-    ldsA[tid + kSmThreads] = st1;
-    __syncthreads();
-
-    f32x16 acc[kSmTiles];
+    f32x16 acc[kScanTiles];
 #pragma unroll
-    for (int t = 0; t < kSmTiles; ++t) acc[t] = f32x16{0};
-    const int one = 0x7f7f7f7f; // E8M0 scale 2^0
-    const v4i *bp = ldsB + h * win + wave * kSmWaveOffs + n_lane;
-
-    for (int c = 0; c < n_chunks; ++c) {
-        const bool more = c + 1 < n_chunks;
-        if (more) { // next chunk of A into registers while this one multiplies
-            st0 = qa[(c + 1) * (kSmChunk * 64) + tid];
-            st1 = qa[(c + 1) * (kSmChunk * 64) + tid + kSmThreads];
-        }
-        const v4i *ap = ldsA + (c & 1) * (kSmChunk * 64) + lane;
-        const int jn = min(kSmChunk, kt - c * kSmChunk);
-        const v4i *bj = bp + c * kSmChunk;
-        for (int j = 0; j < jn; ++j) {
-            const v4i a4 = ap[j * 64];
-            const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
-#pragma unroll
-            for (int t = 0; t < kSmTiles; ++t) {
-                const v4i b4 = bj[j + 32 * t];
-                const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
-            }
-        }
-        if (more) {
-            v4i *dst = ldsA + ((c + 1) & 1) * (kSmChunk * 64);
-            dst[tid] = st0;
-            dst[tid + kSmThreads] = st1;
-        }
+    for (int t = 0; t < kScanTiles; ++t) acc[t] = f32x16{0};
+    const v4i *qa = a.qa + (int64_t)g * a.kt_pad * 64, *bp = l.B + h * win + wave * kScanWaveLags + n_lane;
+    if constexpr (KNN) {
+        // scan_walk and scan_products written out, as they stood: as the shared functions they leave this instantiation's
+        // epilogue with a scalar round counter, 80 scalar instructions more, and the voting search 1.4 % slower
+        // (profiles/query_scan_shared.md)
+        const int n_chunks = (kt + kScanChunk - 1) / kScanChunk, one = 0x7f7f7f7f;
+        v4i st0 = qa[tid], st1 = qa[tid + kScanThreads];
+        l.A[tid] = st0;
+        l.A[tid + kScanThreads] = st1;
         __syncthreads();
+        for (int c = 0; c < n_chunks; ++c) {
+            const bool more = c + 1 < n_chunks;
+            if (more) {
+                st0 = qa[(c + 1) * (kScanChunk * 64) + tid];
+                st1 = qa[(c + 1) * (kScanChunk * 64) + tid + kScanThreads];
+            }
+            const v4i *ap = l.A + (c & 1) * (kScanChunk * 64) + lane, *bj = bp + c * kScanChunk;
+            const int jn = min(kScanChunk, kt - c * kScanChunk);
+            for (int j = 0; j < jn; ++j) {
+                const v4i a4 = ap[j * 64];
+                const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
+#pragma unroll
+                for (int t = 0; t < kScanTiles; ++t) {
+                    const v4i b4 = bj[j + 32 * t];
+                    const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
+                    acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
+                }
+            }
+            if (more) {
+                v4i *dst = l.A + ((c + 1) & 1) * (kScanChunk * 64);
+                dst[tid] = st0;
+                dst[tid + kScanThreads] = st1;
+            }
+            __syncthreads();
+        }
+    } else {
+        scan_walk(qa, l.A, bp, kt, true, tid, lane, [&](const v4i *ap, const v4i *bj, int j) { scan_products(acc, ap, bj, j); });
     }
 
     if constexpr (KNN) {
@@ -182,10 +156,10 @@ __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaA
         for (int reg = 0; reg < 16; ++reg) {
             const int m = (reg & 3) + 8 * (reg >> 2) + 4 * h;
             const int k = kq_s[m];
-            unsigned cand[kSmTiles];
+            unsigned cand[kScanTiles];
 #pragma unroll
-            for (int t = 0; t < kSmTiles; ++t) {
-                const int lo = wave * kSmWaveOffs + t * 32 + n_lane;
+            for (int t = 0; t < kScanTiles; ++t) {
+                const int lo = wave * kScanWaveLags + t * 32 + n_lane;
                 const int dist = (64 * k - (int)acc[t][reg]) >> 1;
                 cand[t] = (k > 0 && o0 + lo <= n - k) ? (((unsigned)dist << 12) | (unsigned)lo) : 0xffffffffu;
             }
@@ -193,7 +167,7 @@ __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaA
             for (int r = 0; r < a.nn; ++r) {
                 unsigned mine = cand[0];
 #pragma unroll
-                for (int t = 1; t < kSmTiles; ++t) mine = cand[t] < mine ? cand[t] : mine;
+                for (int t = 1; t < kScanTiles; ++t) mine = cand[t] < mine ? cand[t] : mine;
                 unsigned best = mine;
 #pragma unroll
                 for (int s2 = 16; s2 >= 1; s2 >>= 1) {
@@ -202,7 +176,7 @@ __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaA
                 }
                 if (best == 0xffffffffu) break; // uniform across the half-wave
 #pragma unroll
-                for (int t = 0; t < kSmTiles; ++t)
+                for (int t = 0; t < kScanTiles; ++t)
                     if (cand[t] == best) cand[t] = 0xffffffffu; // keys are unique: exactly one lane and tile
                 if (n_lane == 0 && row < a.n_q) {
                     unsigned long long *sl = a.slots + (int64_t)row * 8;
@@ -219,37 +193,19 @@ __global__ __launch_bounds__(kSmThreads, 4) void hamming_mfma_kernel(SearchMfmaA
         }
         return;
     } else {
-        // acc[t][reg]: query row m = (reg & 3) + 8 (reg >> 2) + 4 h, offset o0 + wave 128 + t 32 + n_lane.
         // key = dist << 12 | offset inside the workgroup's 1024 (dist <= 64 k < 2^20): smaller distance, then
         // smaller offset -- the first strict minimum of storage.h:50.
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int m = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            const int k = kq_s[m];
-            unsigned key = 0xffffffffu;
-#pragma unroll
-            for (int t = 0; t < kSmTiles; ++t) {
-                const int lo = wave * kSmWaveOffs + t * 32 + n_lane;
-                const int dist = (64 * k - (int)acc[t][reg]) >> 1;
-                const unsigned cand = ((unsigned)dist << 12) | (unsigned)lo;
-                if (k > 0 && o0 + lo <= n - k && cand < key) key = cand;
-            }
-#pragma unroll
-            for (int s = 16; s >= 1; s >>= 1) { // minimum over the 32 offset columns of this half-wave
-                const unsigned o = (unsigned)__shfl_xor((int)key, s);
-                key = o < key ? o : key;
-            }
-            if (n_lane == 0) red[wave * 32 + m] = key;
-        }
-        __syncthreads();
-        if (tid < 32) {
-            unsigned key = red[tid];
-            for (int w = 1; w < kSmThreads / 64; ++w) key = red[w * 32 + tid] < key ? red[w * 32 + tid] : key;
-            const int qi = g * 32 + tid;
-            if (qi < a.n_q && key != 0xffffffffu) {
-                const unsigned long long full = ((unsigned long long)(key >> 12) << 32) | (unsigned)(o0 + (int)(key & 0xfff));
-                atomicMin(reinterpret_cast<unsigned long long *>(a.best) + (int64_t)qi * a.n_clips + clip, full);
-            }
+        const unsigned key = scan_row_min(l.red, tid, wave, n_lane, h, [&](int reg, int t) {
+            const int k = kq_s[(reg & 3) + 8 * (reg >> 2) + 4 * h];
+            const int lo = wave * kScanWaveLags + t * 32 + n_lane;
+            const int dist = (64 * k - (int)acc[t][reg]) >> 1;
+            const bool valid = (k > 0) & (o0 + lo <= n - k); // (& for a select: && makes 64 branches of the epilogue)
+            return valid ? (((unsigned)dist << 12) | (unsigned)lo) : kScanNoKey;
+        });
+        const int qi = g * 32 + tid;
+        if (tid < 32 && qi < a.n_q && key != kScanNoKey) {
+            const unsigned long long full = ((unsigned long long)(key >> 12) << 32) | (unsigned)(o0 + (int)(key & 0xfff));
+            atomicMin(reinterpret_cast<unsigned long long *>(a.best) + (int64_t)qi * a.n_clips + clip, full);
         }
     }
 }
@@ -563,12 +519,9 @@ void launch_hamming_shift(const uint64_t *d_db, const int64_t *d_db_off, int n_c
         launch_hamming_shift_t<false>(d_db, d_db_off, n_clips, n_off_max, d_q, k, d_qexp, d_best, d_set, s);
 }
 
-size_t hamming_mfma_lds_bytes(int kt)
-{
-    return (size_t)2 * (kSmWgOffs + kt) * 16 + (size_t)2 * kSmChunk * 64 * 16 + 32 * 4 + (kSmThreads / 64) * 32 * 4;
-}
+size_t hamming_mfma_lds_bytes(int kt) { return query_scan_lds_bytes(kt); }
 
-int hamming_mfma_kt_pad(int k_max) { return (k_max + kSmChunk - 1) / kSmChunk * kSmChunk + kSmChunk; }
+int hamming_mfma_kt_pad(int k_max) { return (k_max + kScanChunk - 1) / kScanChunk * kScanChunk + kScanChunk; }
 
 void launch_expand_queries(const uint64_t *d_q, const int64_t *d_q_off, int n_q, int kt_pad, void *d_qa, hipStream_t s)
 {
@@ -581,13 +534,8 @@ void launch_expand_queries(const uint64_t *d_q, const int64_t *d_q_off, int n_q,
 static void mfma_scan_attrs()
 {
     static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        for (const void *f : {reinterpret_cast<const void *>(hamming_mfma_kernel<false, false>),
-                              reinterpret_cast<const void *>(hamming_mfma_kernel<false, true>),
-                              reinterpret_cast<const void *>(hamming_mfma_kernel<true, false>)})
-            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set.mark();
-    }
+    scan_allow_lds(attr_set, {reinterpret_cast<const void *>(hamming_mfma_kernel<false, false>), reinterpret_cast<const void *>(hamming_mfma_kernel<false, true>),
+                              reinterpret_cast<const void *>(hamming_mfma_kernel<true, false>)});
 }
 
 void launch_expand_windows(const uint64_t *d_q, const int64_t *d_w_start, int n_win, int win, int kt_pad, void *d_qa,
@@ -613,9 +561,9 @@ void launch_knn_windows(const uint64_t *d_db, const int64_t *d_db_off, int n_cli
     m.win = win;
     m.nn = nn;
     m.slots = reinterpret_cast<unsigned long long *>(d_slots);
-    m.chunks = (n_off_max + kSmWgOffs - 1) / kSmWgOffs;
+    m.chunks = (n_off_max + kScanWgLags - 1) / kScanWgLags;
     dim3 grid((unsigned)m.chunks * (unsigned)n_clips, (n_win + 31) / 32);
-    hipLaunchKernelGGL((hamming_mfma_kernel<true, false>), grid, dim3(kSmThreads), hamming_mfma_lds_bytes(win), s, m);
+    hipLaunchKernelGGL((hamming_mfma_kernel<true, false>), grid, dim3(kScanThreads), hamming_mfma_lds_bytes(win), s, m);
 }
 
 void launch_hamming_mfma(const SearchArgs &a, const void *d_qa, int kt_pad, const int *d_gk, int n_max, hipStream_t s)
@@ -633,12 +581,12 @@ void launch_hamming_mfma(const SearchArgs &a, const void *d_qa, int kt_pad, cons
     m.best = a.best;
     m.set = a.set;
     const int n_groups = (a.n_q + 31) / 32;
-    m.chunks = (n_max + kSmWgOffs - 1) / kSmWgOffs;
+    m.chunks = (n_max + kScanWgLags - 1) / kScanWgLags;
     dim3 grid((unsigned)m.chunks * (unsigned)a.n_clips, n_groups);
     if (a.set)
-        hipLaunchKernelGGL((hamming_mfma_kernel<false, true>), grid, dim3(kSmThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
+        hipLaunchKernelGGL((hamming_mfma_kernel<false, true>), grid, dim3(kScanThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
     else
-        hipLaunchKernelGGL((hamming_mfma_kernel<false, false>), grid, dim3(kSmThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
+        hipLaunchKernelGGL((hamming_mfma_kernel<false, false>), grid, dim3(kScanThreads), hamming_mfma_lds_bytes(a.k_max), s, m);
 }
 
 } // namespace hpfw

@@ -5,10 +5,9 @@
 // splits, the expansion to fp4 and the end of a chunk on either route are in overlap_rule.h, shared with the joins
 // (k_selfjoin.hip).  This file instantiates OverlapSearchRule: dist <= 64 L, L <= 16000, 24-bit products below 2^34.
 //
-// (a) overlap_mfma_kernel is hamming_mfma_kernel (k_search_mfma.hip) with the clip's window zero-filled on both sides: with
-// hashprint bits as fp4 +-1 and fp4 0 outside the query and outside the clip, the accumulator of (query row, lag) is
-// 64 L - 2 dist.  A workgroup = 32 queries x 1024 lags of one clip per chunk; the lags of a clip start at
-// min_overlap - (the group's longest query) and end at n - min_overlap.
+// (a) overlap_mfma_kernel is the scan of query_scan.h with the clip's window zero-filled on both sides: with hashprint bits as
+// fp4 +-1 and fp4 0 outside the query and outside the clip, the accumulator of (query row, lag) is 64 L - 2 dist.  The lags of
+// a clip start at min_overlap - (the group's longest query) and end at n - min_overlap; the window is restaged per chunk.
 // (b) overlap_popc_kernel computes the same by xor/popcount: queries whose window does not fit the LDS, and the second
 // opinion on the device (HPFW_OVERLAP_POPC).
 //
@@ -16,21 +15,13 @@
 // round robin to `splits` workgroups, each of which owns its entry (no atomics, nothing depends on the order workgroups
 // run in).  overlap_select_kernel folds the splits and picks the k best clips per query.
 #include "kernels.h"
-#include "overlap_rule.h"
+#include "query_scan.h"
 
 namespace hpfw {
 
 extern __shared__ __align__(16) unsigned char smem_raw[];
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 namespace {
-constexpr int kOvThreads = 512;                          // 8 waves
-constexpr int kOvTiles = 4;                              // lag tiles of 32 per wave
-constexpr int kOvWaveLags = 32 * kOvTiles;               // 128
-constexpr int kOvWgLags = kOvWaveLags * (kOvThreads / 64); // 1024 lags per chunk (kOverlapChunk)
-constexpr int kOvChunk = 16;                             // positions j per staged chunk of the A operand, as kSmChunk
-static_assert(kOvWgLags == kOverlapChunk, "kernels.h states the chunk");
 using Rule = OverlapSearchRule;
 static_assert(kOverlapChunk == Rule::kChunk, "a candidate's lag inside the chunk takes 10 bits");
 constexpr unsigned kNoDist = Rule::kNoDist; // the "none" of OvPick below
@@ -45,28 +36,27 @@ struct OverlapArgs {
     int n_q;
     const v4i *qa;        // expanded queries of this launch (expand_queries_kernel's image)
     int kt_pad;
-    const int *gk;        // [g]: longest query of group g
+    const int *gk;        // [2 g]: longest query of group g
     int min_overlap, splits;
     uint4 *tab;           // [n_q][n_clips][splits], every byte preset to 0xff
 };
 
-__global__ __launch_bounds__(kOvThreads, 4) void overlap_mfma_kernel(OverlapArgs a)
+__global__ __launch_bounds__(kScanThreads, 4) void overlap_mfma_kernel(OverlapArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_lane = lane & 31, h = lane >> 5;
     const int clip = blockIdx.x / a.splits, split = blockIdx.x - clip * a.splits, g = blockIdx.y;
     const int64_t r0 = a.db_off[clip];
     const int n = (int)(a.db_off[clip + 1] - r0);
-    const int kt = a.gk[g], mo = a.min_overlap;
+    const int kt = a.gk[2 * g], mo = a.min_overlap;
     if (n < mo || kt < mo) return; // no row of the group has a candidate in this clip
     const int d_lo = mo - kt, d_hi = n - mo;
-    const int n_wg_chunks = (d_hi - d_lo) / kOvWgLags + 1;
+    const int n_wg_chunks = (d_hi - d_lo) / kScanWgLags + 1;
 
-    const int win = kOvWgLags + kt;                      // window slots (one spare)
-    v4i *ldsB = reinterpret_cast<v4i *>(smem_raw);       // [2][win]: plane h = bits [32 h, 32 h + 32) of each hashprint
-    v4i *ldsA = ldsB + 2 * win;                          // [2][kOvChunk][64]
-    int *kq_s = reinterpret_cast<int *>(ldsA + 2 * kOvChunk * 64); // [32] lengths of the group's queries (0: no candidate)
-    uint2 *red = reinterpret_cast<uint2 *>(ldsA);        // [8 waves][32 queries], over the A operand once the sums are done
+    const int win = kScanWgLags + kt;
+    const ScanLds l = scan_lds(smem_raw, win);
+    int *kq_s = l.len;                                // lengths of the group's queries (0: no candidate)
+    uint2 *red = reinterpret_cast<uint2 *>(l.A);      // [8 waves][32 queries], over the A operand once the sums are done
 
     if (tid < 32) {
         const int qi = g * 32 + tid;
@@ -75,63 +65,19 @@ __global__ __launch_bounds__(kOvThreads, 4) void overlap_mfma_kernel(OverlapArgs
         kq_s[tid] = k >= mo ? k : 0;
     }
     const v4i *qa = a.qa + (int64_t)g * a.kt_pad * 64;
-    const int n_chunks = (kt + kOvChunk - 1) / kOvChunk;
-    const int one = 0x7f7f7f7f; // E8M0 scale 2^0
-    const v4i *bp = ldsB + h * win + wave * kOvWaveLags + n_lane;
+    const v4i *bp = l.B + h * win + wave * kScanWaveLags + n_lane;
     Rule::Best best; // (threads below 32)
 
     for (int wc = split; wc < n_wg_chunks; wc += a.splits) {
-        const int d0 = d_lo + wc * kOvWgLags;
+        const int d0 = d_lo + wc * kScanWgLags;
         __syncthreads(); // the chunk before this one has read its window and its candidates
-        // clip positions d0 .. d0 + win - 1, expanded; fp4 zeros before the clip's start and past its end
-        for (int i = tid; i < win; i += kOvThreads) {
-            const int gi = d0 + i;
-            v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-            if (gi >= 0 && gi < n) {
-                const uint64_t w = a.db[r0 + gi];
-                lo = expand32((uint32_t)w);
-                hi = expand32((uint32_t)(w >> 32));
-            }
-            ldsB[i] = lo;
-            ldsB[win + i] = hi;
-        }
-        v4i st0 = qa[tid], st1 = qa[tid + kOvThreads]; // 16 steps x 64 lanes = 1024 entries: two per thread
-        ldsA[tid] = st0;
-        ldsA[tid + kOvThreads] = st1;
-        __syncthreads();
-
-        f32x16 acc[kOvTiles];
+        scan_stage_window(l.B, win, a.db, r0, n, d0, tid);
+        f32x16 acc[kScanTiles];
 #pragma unroll
-        for (int t = 0; t < kOvTiles; ++t) acc[t] = f32x16{0};
-        // a wave whose 128 lags all lie past n - min_overlap (the clip's last chunk) multiplies nothing: it only helps staging
-        const bool live = d0 + wave * kOvWaveLags <= d_hi;
-        for (int c = 0; c < n_chunks; ++c) {
-            const bool more = c + 1 < n_chunks;
-            if (more) { // next chunk of A into registers while this one multiplies
-                st0 = qa[(c + 1) * (kOvChunk * 64) + tid];
-                st1 = qa[(c + 1) * (kOvChunk * 64) + tid + kOvThreads];
-            }
-            const v4i *ap = ldsA + (c & 1) * (kOvChunk * 64) + lane;
-            const int jn = min(kOvChunk, kt - c * kOvChunk);
-            const v4i *bj = bp + c * kOvChunk;
-            for (int j = 0; live && j < jn; ++j) {
-                const v4i a4 = ap[j * 64];
-                const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
-#pragma unroll
-                for (int t = 0; t < kOvTiles; ++t) {
-                    const v4i b4 = bj[j + 32 * t];
-                    const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
-                    acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
-                }
-            }
-            if (more) {
-                v4i *dst = ldsA + ((c + 1) & 1) * (kOvChunk * 64);
-                dst[tid] = st0;
-                dst[tid + kOvThreads] = st1;
-            }
-            __syncthreads();
-        }
-
+        for (int t = 0; t < kScanTiles; ++t) acc[t] = f32x16{0};
+        // a wave whose 128 lags all lie past n - min_overlap (the clip's last chunk) is not live
+        scan_walk(qa, l.A, bp, kt, d0 + wave * kScanWaveLags <= d_hi, tid, lane,
+                  [&](const v4i *ap, const v4i *bj, int j) { scan_products(acc, ap, bj, j); });
         // the chunk's candidates go over the A operand, the best of each query row to its thread's `best`
         Rule::tile_epilogue(acc, kq_s, n, mo, d0, red, best, tid, wave, n_lane, h);
     }
@@ -150,10 +96,10 @@ __global__ __launch_bounds__(256) void overlap_popc_kernel(OverlapArgs a)
     if (n < mo || k < mo) return;
     const uint64_t *q = a.q + q0, *r = a.db + r0;
     const int d_lo = mo - k, d_hi = n - mo;
-    const int n_wg_chunks = (d_hi - d_lo) / kOvWgLags + 1;
+    const int n_wg_chunks = (d_hi - d_lo) / kScanWgLags + 1;
     Rule::Best best; // (thread 0)
     for (int wc = split; wc < n_wg_chunks; wc += a.splits) {
-        const int d0 = d_lo + wc * kOvWgLags;
+        const int d0 = d_lo + wc * kScanWgLags;
         Rule::popc_chunk<false>(q, k, r, n, mo, d0, d_hi, red, best, tid); // d_lo <= d <= d_hi: every lag overlaps min_overlap
     }
     if (tid == 0) best.store(a.tab + ((int64_t)qi * a.n_clips + clip) * a.splits + split);
@@ -232,11 +178,7 @@ void launch_overlap_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_cl
                          int kt_pad, const int *d_gk, int k_max, int min_overlap, int splits, void *d_tab, hipStream_t s)
 {
     static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(overlap_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set.mark();
-    }
+    scan_allow_lds(attr_set, {reinterpret_cast<const void *>(overlap_mfma_kernel)});
     OverlapArgs a = {};
     a.db = d_db;
     a.db_off = d_db_off;
@@ -249,9 +191,8 @@ void launch_overlap_mfma(const uint64_t *d_db, const int64_t *d_db_off, int n_cl
     a.min_overlap = min_overlap;
     a.splits = splits;
     a.tab = reinterpret_cast<uint4 *>(d_tab);
-    // (the candidates lie over the A operand: hamming_mfma_lds_bytes covers this kernel too)
     const dim3 grid((unsigned)n_clips * (unsigned)splits, (unsigned)((n_q + 31) / 32));
-    hipLaunchKernelGGL(overlap_mfma_kernel, grid, dim3(kOvThreads), hamming_mfma_lds_bytes(k_max), s, a);
+    hipLaunchKernelGGL(overlap_mfma_kernel, grid, dim3(kScanThreads), query_scan_lds_bytes(k_max), s, a);
 }
 
 void launch_overlap_popc(const uint64_t *d_db, const int64_t *d_db_off, int n_clips, const uint64_t *d_q, const int64_t *d_q_off, int n_q,

@@ -59,23 +59,13 @@ __device__ __forceinline__ uint4 *sj_entry(const Args &a, int row, int b, int sp
 template <class Args>
 __global__ __launch_bounds__(kJoinThreads, 4) void selfjoin_mfma_kernel(Args a)
 {
-    const int one = 0x7f7f7f7f; // E8M0 scale 2^0
-    Rule::Best best;            // (threads below 32)
+    Rule::Best best; // (threads below 32)
     f32x16 acc[kJoinTiles];
 #pragma unroll
     for (int t = 0; t < kJoinTiles; ++t) acc[t] = f32x16{0};
     const JoinChunk c = join_scan(
         a, smem_raw,
-        [&](const v4i *ap, const v4i *bp, int j) {
-            const v4i a4 = ap[j * 64];
-            const v8i av = {a4.x, a4.y, a4.z, a4.w, 0, 0, 0, 0};
-#pragma unroll
-            for (int t = 0; t < kJoinTiles; ++t) {
-                const v4i b4 = bp[j + 32 * t];
-                const v8i bv = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[t], 4, 4, 0, one, 0, one);
-            }
-        },
+        [&](const v4i *ap, const v4i *bp, int j) { scan_products(acc, ap, bp, j); },
         [&](const JoinChunk &c) { // the candidates [8 waves][32 rows] go over the A operand now that the sums are done
             Rule::tile_epilogue(acc, c.lens, c.n, a.min_overlap, c.d0, static_cast<uint2 *>(c.red), best, c.tid, c.wave, c.n_lane, c.h);
 #pragma unroll

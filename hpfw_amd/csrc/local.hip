@@ -16,13 +16,7 @@ int local_check(const void *h, const int64_t *q_off, int64_t n_q, int max_rate, 
     if (!h || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
     if (max_rate < 1 || max_rate > 31) return fail(HPFW_E_INVALID, "max_rate must be in 1..31");
-    *k_max = 0;
-    for (int64_t i = 0; i < n_q; ++i) {
-        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-        *k_max = std::max(*k_max, q_off[i + 1] - q_off[i]);
-    }
-    if (*k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
-    return 0;
+    return check_q_off(q_off, n_q, k_max);
 }
 
 int search_local_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int max_rate, int k, hpfw_local_hit *d_out,
@@ -42,64 +36,36 @@ int search_local_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_of
             hpfw::launch_local_ends(nullptr, nullptr, nullptr, nullptr, nullptr, n_q, k, max_rate, h->index.clip_base, d_out, nullptr, s);
             return check_launch("local_ends");
         }
-        if ((rc = upload_db_off(h, s))) return rc;
-        if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
         if ((rc = ensure(h->index.d_local_flag, 4))) return rc;
         HIP_TRY(hipMemsetAsync(h->index.d_local_flag.get(), 0, 4, s));
-        // The scan runs on the matrix cores unless the window does not fit the LDS (the bound of the plain search) or
-        // HPFW_LOCAL_POPC asks for the xor/popcount kernel.
-        const bool mfma = !std::getenv("HPFW_LOCAL_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024;
+        const bool mfma = hpfw::search_on_matrix_cores(std::getenv("HPFW_LOCAL_POPC") != nullptr, hpfw::hamming_mfma_lds_bytes((int)k_max));
         // lags 1 - k_max .. n_max - 1 in chunks
         const int64_t chunks = (n_max + k_max - 2) / hpfw::kLocalChunk + 1;
         if (n_clips * chunks > 0x7fffffff) return fail(HPFW_E_UNSUPPORTED, "local search: too many clips");
-        // queries are processed in groups so the table stays below 512 MiB
-        int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 26) / n_clips / 32 * 32);
-        qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
-        qgroup = std::min<int64_t>(qgroup, 65504); // the popcount kernel puts one query per gridDim.y
-        if ((rc = ensure(h->index.d_best, (size_t)qgroup * n_clips * 8))) return rc;
+        const int64_t qgroup = hpfw::search_group_queries(n_q, n_clips, hpfw::kLocalTableEntries, hpfw::kPopcGridQueries, 8,
+                                                          env_table_kb("HPFW_LOCAL_TABLE_KB"));
         if ((rc = ensure(h->index.d_local_top, (size_t)qgroup * k * sizeof(hpfw_hit)))) return rc;
-        const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
-        if (mfma) {
-            if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
-            if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 4))) return rc;
-        }
-        std::vector<int> gk;
         const uint64_t *db = h->index.d_db.as<uint64_t>();
-        const int64_t *db_off = h->index.d_db_off.as<int64_t>();
-        uint64_t *d_best = h->index.d_best.as<uint64_t>();
-        for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
-            const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
-            const int64_t *d_q_off = h->index.d_q_off.as<int64_t>() + g0;
-            HIP_TRY(hipMemsetAsync(d_best, 0xff, (size_t)ng * n_clips * 8, s));
-            if (mfma) {
-                gk.assign((size_t)(ng + 31) / 32, 0);
-                for (int i = 0; i < ng; ++i) gk[(size_t)i / 32] = std::max(gk[(size_t)i / 32], (int)(q_off[g0 + i + 1] - q_off[g0 + i]));
-                HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
-                Timed t(h, K_SCAN, s);
-                hpfw::launch_expand_queries(d_q_hp, d_q_off, ng, kt_pad, h->index.d_qa.get(), s);
-                hpfw::launch_local_mfma(db, db_off, (int)n_clips, d_q_off, ng, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)k_max,
-                                        max_rate, (int)chunks, d_best, s);
-            } else {
-                Timed t(h, K_SCAN, s);
-                hpfw::launch_local_popc(db, db_off, (int)n_clips, d_q_hp, d_q_off, ng, max_rate, (int)chunks, d_best, s);
-            }
-            if ((rc = check_launch("local scan"))) return rc;
-            {
-                Timed t(h, K_TOPK, s);
-                void *d_top = h->index.d_local_top.get();
-                if (n_clips >= 16384 && ng <= 64) { // (as the plain search chooses)
-                    if ((rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes(ng, k)))) return rc;
-                    hpfw::launch_topk_two_step(d_best, ng, (int)n_clips, k, h->index.clip_base, h->index.d_topk_scratch.get(), d_top, s);
-                } else {
-                    hpfw::launch_topk(d_best, ng, (int)n_clips, k, h->index.clip_base, d_top, s);
-                }
-                hpfw::launch_local_ends(d_top, db, db_off, d_q_hp, d_q_off, ng, k, max_rate, h->index.clip_base, d_out + g0 * k,
-                                        h->index.d_local_flag.as<unsigned>(), s);
-            }
-            if ((rc = check_launch("local top-k"))) return rc;
-        }
+        rc = search_run_groups(
+            h, s, d_q_hp, q_off, n_q, k_max, qgroup, mfma, h->index.d_best, (size_t)n_clips * 8,
+            {{K_SCAN, "local scan", true,
+              [&](const QueryGroup &g) {
+                  const int64_t *db_off = h->index.d_db_off.as<int64_t>();
+                  uint64_t *d_best = h->index.d_best.as<uint64_t>();
+                  if (mfma)
+                      hpfw::launch_local_mfma(db, db_off, (int)n_clips, g.d_q_off, g.ng, g.d_qa, g.kt_pad, g.d_gk, (int)k_max, max_rate, (int)chunks, d_best, s);
+                  else
+                      hpfw::launch_local_popc(db, db_off, (int)n_clips, d_q_hp, g.d_q_off, g.ng, max_rate, (int)chunks, d_best, s);
+                  return 0;
+              }},
+             {K_TOPK, "local top-k", false, [&](const QueryGroup &g) {
+                  void *d_top = h->index.d_local_top.get();
+                  if (int rc2 = search_topk_rows(h, h->index.d_best.as<uint64_t>(), g.ng, n_clips, k, d_top, s)) return rc2;
+                  hpfw::launch_local_ends(d_top, db, h->index.d_db_off.as<int64_t>(), d_q_hp, g.d_q_off, g.ng, k, max_rate, h->index.clip_base,
+                                          d_out + g.g0 * k, h->index.d_local_flag.as<unsigned>(), s);
+                  return 0;
+              }}});
+        if (rc) return rc;
         // the walk of every winner gave the scan's score (and q_off has been read)
         unsigned disagree = 0;
         HIP_TRY(hipMemcpyAsync(&disagree, h->index.d_local_flag.get(), 4, hipMemcpyDeviceToHost, s));

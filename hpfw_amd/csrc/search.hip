@@ -2,6 +2,48 @@
 // clips, and the merges of the shards' hits and moments.  (The voting search is votes.hip, AudioCombiner's calls are combiner.hip.)
 #include "handle.h"
 
+// the passes of a search over its queries (handle.h)
+int search_run_groups(hpfw_gpu *h, hipStream_t s, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int64_t k_max, int64_t qgroup,
+                      bool expand, DevBuf &table, size_t row_bytes, const std::vector<SearchStep> &steps)
+{
+    int rc;
+    if ((rc = upload_db_off(h, s))) return rc;
+    if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((rc = ensure(table, (size_t)qgroup * row_bytes))) return rc;
+    const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
+    std::vector<int> gk;
+    if (expand) {
+        if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
+        gk = hpfw::search_group_lengths(q_off, n_q);
+        if ((rc = ensure(h->index.d_gk, gk.size() * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s)); // (gk has been read)
+    }
+    for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
+        QueryGroup g = {};
+        g.g0 = g0;
+        g.ng = (int)std::min<int64_t>(qgroup, n_q - g0);
+        g.d_q_off = h->index.d_q_off.as<int64_t>() + g0;
+        if (expand) {
+            g.d_qa = h->index.d_qa.get();
+            g.kt_pad = kt_pad;
+            g.d_gk = h->index.d_gk.as<int>() + g0 / 32 * 2;
+            g.k_min = hpfw::search_shortest_query(gk, g0 / 32, (g0 + g.ng + 31) / 32);
+        }
+        HIP_TRY(hipMemsetAsync(table.get(), 0xff, (size_t)g.ng * row_bytes, s));
+        for (const SearchStep &step : steps) {
+            {
+                Timed t(h, step.kind, s);
+                if (expand && step.scan) hpfw::launch_expand_queries(d_q_hp, g.d_q_off, g.ng, kt_pad, h->index.d_qa.get(), s);
+                rc = step.run(g);
+            }
+            if (rc || (rc = check_launch(step.what))) return rc;
+        }
+    }
+    return 0;
+}
+
 extern "C" {
 
 // ---- index + search ----------------------------------------------------------------------------
@@ -224,107 +266,69 @@ static int search_topk_view(hpfw_gpu *h, const ClipView &v, const uint64_t *d_q_
 {
     if (n_q == 0) return 0;
     if (!d_q_hp) return fail(HPFW_E_INVALID, "null queries");
-    const int64_t n_clips = v.n_clips;
-    int rc;
+    const int64_t n_clips = v.n_clips, n_max = v.n_max;
     if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_q * sizeof(hpfw_dist_stats), s));
     if (n_clips == 0) { // nothing indexed: every slot is "none"
         hpfw::launch_topk(nullptr, (int)n_q, 0, k, h->index.clip_base, d_out, s);
         return check_launch("topk");
     }
-    if ((rc = upload_db_off(h, s))) return rc;
     int64_t k_max = 0;
-    for (int64_t i = 0; i < n_q; ++i) {
-        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-        k_max = std::max(k_max, q_off[i + 1] - q_off[i]);
-    }
-    if (k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    if (int rc = check_q_off(q_off, n_q, &k_max)) return rc;
     // d <= 64 k_max: the sum of squares stays below 2^64 while n_clips k_max^2 4096 does
     if (d_stats && (unsigned __int128)n_clips * (uint64_t)(k_max * k_max) * 4096 >= ((unsigned __int128)1 << 64))
         return fail(HPFW_E_UNSUPPORTED, "scored search: n_clips * k_max^2 * 4096 must stay below 2^64");
-    if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
-    // queries are processed in groups so the (query, clip) table stays below 1 GiB
-    int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 27) / n_clips / 32 * 32);
-    qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
-    qgroup = std::min<int64_t>(qgroup, (int64_t)65535 * 8 / 32 * 32); // the scans put groups of 8 / 32 queries along gridDim.y
-    if ((rc = ensure(h->index.d_best, (size_t)qgroup * n_clips * 8))) return rc;
-    // The scan runs on the matrix cores (k_search_mfma.hip) unless the window does not fit the LDS
-    // (queries of several thousand hashprints) or HPFW_SEARCH_POPC asks for the xor/popcount kernel; fewer than
-    // 8 queries go one by one through the shifted-rows variant (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force
-    // the grouped / the shifted-rows kernel for any number of queries).
+    const int64_t qgroup = hpfw::search_group_queries(n_q, n_clips, hpfw::kSearchTableEntries, hpfw::kSearchGridQueries, 8,
+                                                      env_table_kb("HPFW_SEARCH_TABLE_KB"));
+    // search_plan.h's choice (HPFW_SEARCH_POPC); fewer than 8 queries go one by one through the shifted-rows variant
+    // (HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT force the grouped / the shifted-rows kernel for any number of queries).
     // A group of 32 queries is one MFMA tile: with fewer than 8 queries most of its rows would be padding
     // and the popcount kernel (one workgroup per 8 queries) does less work.
-    const bool mfma = !std::getenv("HPFW_SEARCH_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024 &&
-                      k_max > 0 && (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
-    const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
-    const int64_t n_max = v.n_max;
-    if (mfma) {
-        if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
-        if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 8))) return rc;
-    }
-    std::vector<int> gk;
-    for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
-        const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
-        HIP_TRY(hipMemsetAsync(h->index.d_best.get(), 0xff, (size_t)ng * n_clips * 8, s));
+    const bool popc = std::getenv("HPFW_SEARCH_POPC") != nullptr;
+    const bool mfma = hpfw::search_on_matrix_cores(popc, hpfw::hamming_mfma_lds_bytes((int)k_max)) && k_max > 0 &&
+                      (n_q >= 8 || std::getenv("HPFW_SEARCH_MFMA"));
+    const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !popc && k_max > 0 && n_max > 0 &&
+                     hpfw::hamming_shift_lds_bytes((int)k_max) <= hpfw::kScanLdsLimit;
+    const bool grouped = mfma && !few && n_max > 0;
+    auto args = [&](const QueryGroup &g) {
         hpfw::SearchArgs a;
         a.db = h->index.d_db.as<uint64_t>();
         a.db_off = h->index.d_db_off.as<int64_t>();
         a.n_clips = (int)n_clips;
         a.q = d_q_hp;
-        a.q_off = h->index.d_q_off.as<int64_t>() + g0;
-        a.n_q = ng;
+        a.q_off = g.d_q_off;
+        a.n_q = g.ng;
         a.k_max = (int)k_max;
-        a.best = h->index.d_best.as<uint64_t>();
+        a.best = h->index.d_best.as<uint64_t>(); // (the runner has sized the table)
         a.set = v.d_set;
-        const bool few = (!mfma || std::getenv("HPFW_SEARCH_SHIFT")) && !std::getenv("HPFW_SEARCH_POPC") && k_max > 0 && n_max > 0 &&
-                         hpfw::hamming_shift_lds_bytes((int)k_max) <= 160 * 1024;
-        if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
-            if ((rc = ensure(h->index.d_qa, hpfw::hamming_shift_image_bytes((int)k_max)))) return rc;
-            Timed t(h, K_SCAN, s);
-            for (int i = 0; i < ng; ++i) {
-                const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
-                if (kq <= 0) continue;
-                hpfw::launch_hamming_shift(a.db, a.db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
-                                           d_q_hp + q_off[g0 + i], kq, h->index.d_qa.get(), a.best + (size_t)i * n_clips, s, v.d_set);
-            }
-        } else if (mfma && n_max > 0) {
-            gk.assign((size_t)(ng + 31) / 32 * 2, 0); // per group: longest query, shortest non-empty query
-            int kmin_all = 0;
-            for (int i = 0; i < ng; ++i) {
-                const int kq = (int)(q_off[g0 + i + 1] - q_off[g0 + i]);
-                int &mx = gk[(size_t)i / 32 * 2], &mn = gk[(size_t)i / 32 * 2 + 1];
-                mx = std::max(mx, kq);
-                if (kq > 0) mn = mn == 0 ? kq : std::min(mn, kq);
-                if (kq > 0) kmin_all = kmin_all == 0 ? kq : std::min(kmin_all, kq);
-            }
-            HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
-            Timed t(h, K_SCAN, s);
-            hpfw::launch_expand_queries(d_q_hp, a.q_off, ng, kt_pad, h->index.d_qa.get(), s);
-            // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
-            hpfw::launch_hamming_mfma(a, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)std::max<int64_t>(n_max - std::min<int64_t>(kmin_all, n_max) + 1, 1), s);
-        } else {
-            Timed t(h, K_SCAN, s);
-            hpfw::launch_hamming_scan(a, s);
-        }
-        if ((rc = check_launch("hamming_scan"))) return rc;
-        {
-            Timed t(h, K_TOPK, s);
-            if (n_clips >= 16384 && ng <= 64) { // one workgroup per query would crawl through the whole table
-                if ((rc = ensure(h->index.d_topk_scratch, hpfw::topk_scratch_bytes(ng, k)))) return rc;
-                hpfw::launch_topk_two_step(a.best, ng, (int)n_clips, k, h->index.clip_base, h->index.d_topk_scratch.get(), d_out + g0 * k, s, v.d_set);
-            } else {
-                hpfw::launch_topk(a.best, ng, (int)n_clips, k, h->index.clip_base, d_out + g0 * k, s, v.d_set);
-            }
-        }
-        if ((rc = check_launch("topk"))) return rc;
-        if (d_stats) {
-            Timed t(h, K_TOPK, s);
-            hpfw::launch_dist_stats(a.best, a.db_off, a.q_off, ng, (int)n_clips, d_stats + g0, s, v.d_set);
-        }
-        if (d_stats && (rc = check_launch("dist_stats"))) return rc;
-    }
-    return 0;
+        return a;
+    };
+    std::vector<SearchStep> steps;
+    steps.push_back({K_SCAN, "hamming_scan", true, [&](const QueryGroup &g) {
+                         const hpfw::SearchArgs a = args(g);
+                         if (few) { // a handful of queries: one launch each, the tile rows are shifts of the query
+                             if (int rc = ensure(h->index.d_qa, hpfw::hamming_shift_image_bytes((int)k_max))) return rc;
+                             for (int i = 0; i < g.ng; ++i) {
+                                 const int kq = (int)(q_off[g.g0 + i + 1] - q_off[g.g0 + i]);
+                                 if (kq <= 0) continue;
+                                 hpfw::launch_hamming_shift(a.db, a.db_off, (int)n_clips, (int)std::max<int64_t>(n_max - std::min<int64_t>(kq, n_max) + 1, 1),
+                                                            d_q_hp + q_off[g.g0 + i], kq, h->index.d_qa.get(), a.best + (size_t)i * n_clips, s, v.d_set);
+                             }
+                         } else if (grouped) {
+                             // offsets exist up to n_max - (shortest query): that many chunks of workgroups per clip
+                             hpfw::launch_hamming_mfma(a, g.d_qa, g.kt_pad, g.d_gk, (int)std::max<int64_t>(n_max - std::min<int64_t>(g.k_min, n_max) + 1, 1), s);
+                         } else {
+                             hpfw::launch_hamming_scan(a, s);
+                         }
+                         return 0;
+                     }});
+    steps.push_back({K_TOPK, "topk", false,
+                     [&](const QueryGroup &g) { return search_topk_rows(h, h->index.d_best.as<uint64_t>(), g.ng, n_clips, k, d_out + g.g0 * k, s, v.d_set); }});
+    if (d_stats)
+        steps.push_back({K_TOPK, "dist_stats", false, [&](const QueryGroup &g) {
+                             hpfw::launch_dist_stats(h->index.d_best.as<uint64_t>(), h->index.d_db_off.as<int64_t>(), g.d_q_off, g.ng, (int)n_clips, d_stats + g.g0, s, v.d_set);
+                             return 0;
+                         }});
+    return search_run_groups(h, s, d_q_hp, q_off, n_q, k_max, qgroup, grouped, h->index.d_best, (size_t)n_clips * 8, steps);
 }
 
 static int search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off, int64_t n_q, int k, hpfw_hit *d_out,
@@ -396,11 +400,8 @@ static int within_check(const void *h, const int64_t *q_off, int64_t n_q, int k,
     for (int64_t i = 0; i < n_q / n_rep; ++i)
         if (q_set[i] < -1 || q_set[i] >= n_sets)
             return fail(HPFW_E_INVALID, "within: q_set[" + std::to_string(i) + "] outside -1 .. n_sets - 1");
-    for (int64_t i = 0; i < n_q; ++i) {
-        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-        if (q_off[i + 1] - q_off[i] > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
-    }
-    return 0;
+    int64_t k_max = 0;
+    return check_q_off(q_off, n_q, &k_max, true);
 }
 
 // what the index decides, before a kernel runs
@@ -619,12 +620,7 @@ static int overlap_check(const void *h, const int64_t *q_off, int64_t n_q, const
     if (!h || !q_off || !out || n_q < 0) return fail(HPFW_E_INVALID, "bad argument");
     if (k < 1 || k > 64) return fail(HPFW_E_INVALID, "k must be in 1..64");
     if (min_overlap < 1 || min_overlap > 16000) return fail(HPFW_E_INVALID, "min_overlap must be in 1..16000");
-    *k_max = 0;
-    for (int64_t i = 0; i < n_q; ++i) {
-        if (q_off[i + 1] < q_off[i]) return fail(HPFW_E_INVALID, "q_off must be non-decreasing");
-        *k_max = std::max(*k_max, q_off[i + 1] - q_off[i]);
-    }
-    if (*k_max > 16000) return fail(HPFW_E_UNSUPPORTED, "query longer than 16000 hashprints");
+    if (int rc = check_q_off(q_off, n_q, k_max)) return rc;
     for (int64_t i = 0; exclude && i < n_q; ++i)
         if (exclude[i] < -1) return fail(HPFW_E_INVALID, "exclude: an entry below -1 (query " + std::to_string(i) + ")");
     return 0;
@@ -658,65 +654,43 @@ static int search_overlap_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int6
                 hpfw::launch_overlap_select(nullptr, (int)std::min<int64_t>(1 << 20, n_q - g0), 0, 1, nullptr, k, h->index.clip_base, d_out + g0 * k, s);
             return check_launch("overlap_select");
         }
-        if ((rc = upload_db_off(h, s))) return rc;
-        if ((rc = ensure(h->index.d_q_off, (size_t)(n_q + 1) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->index.d_q_off.get(), q_off, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
         if (exclude) {
             if ((rc = ensure(h->index.d_ov_exclude, (size_t)n_q * 4))) return rc;
             HIP_TRY(hipMemcpyAsync(h->index.d_ov_exclude.get(), exclude, (size_t)n_q * 4, hipMemcpyHostToDevice, s));
         }
-        // The scan runs on the matrix cores unless the window does not fit the LDS (the bound of the plain search) or
-        // HPFW_OVERLAP_POPC asks for the xor/popcount kernel.
-        const bool mfma = !std::getenv("HPFW_OVERLAP_POPC") && hpfw::hamming_mfma_lds_bytes((int)k_max) <= 160 * 1024;
+        const bool mfma = hpfw::search_on_matrix_cores(std::getenv("HPFW_OVERLAP_POPC") != nullptr, hpfw::hamming_mfma_lds_bytes((int)k_max));
         const int64_t n_max = index_longest_clip(h);
         // the chunks of a (group, clip) pair go to `splits` workgroups
         const int64_t chunks = std::max<int64_t>((n_max + k_max - 2 * min_overlap) / hpfw::kOverlapChunk + 1, 1);
         const int64_t pairs = n_clips * (mfma ? (n_q + 31) / 32 : n_q);
-        const int64_t splits = hpfw::overlap_splits(chunks, pairs, env_forced_splits("HPFW_OVERLAP_SPLITS"));
-        // queries are processed in groups so the table stays below 1 GiB
-        int64_t qgroup = std::max<int64_t>(32, ((int64_t)1 << 26) / (n_clips * splits) / 32 * 32);
-        qgroup = std::min<int64_t>(qgroup, (n_q + 31) / 32 * 32);
-        qgroup = std::min<int64_t>(qgroup, 65504); // the popcount kernel puts one query per gridDim.y
+        const int splits = (int)hpfw::overlap_splits(chunks, pairs, env_forced_splits("HPFW_OVERLAP_SPLITS"));
         if ((int64_t)n_clips * splits > 0x7fffffff) return fail(HPFW_E_UNSUPPORTED, "overlap search: too many clips");
-        if ((rc = ensure(h->index.d_ov_tab, (size_t)qgroup * n_clips * splits * 16))) return rc;
-        const int kt_pad = hpfw::hamming_mfma_kt_pad((int)k_max);
-        if (mfma) {
-            if ((rc = ensure(h->index.d_qa, (size_t)(qgroup / 32) * kt_pad * 1024))) return rc;
-            if ((rc = ensure(h->index.d_gk, (size_t)(qgroup / 32) * 4))) return rc;
-        }
-        std::vector<int> gk;
-        for (int64_t g0 = 0; g0 < n_q; g0 += qgroup) {
-            const int ng = (int)std::min<int64_t>(qgroup, n_q - g0);
-            HIP_TRY(hipMemsetAsync(h->index.d_ov_tab.get(), 0xff, (size_t)ng * n_clips * splits * 16, s));
-            const uint64_t *db = h->index.d_db.as<uint64_t>();
-            const int64_t *db_off = h->index.d_db_off.as<int64_t>(), *d_q_off = h->index.d_q_off.as<int64_t>() + g0;
-            if (mfma && k_max > 0) {
-                gk.assign((size_t)(ng + 31) / 32, 0);
-                for (int i = 0; i < ng; ++i) gk[(size_t)i / 32] = std::max(gk[(size_t)i / 32], (int)(q_off[g0 + i + 1] - q_off[g0 + i]));
-                HIP_TRY(hipMemcpyAsync(h->index.d_gk.get(), gk.data(), gk.size() * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipStreamSynchronize(s)); // gk is reused by the next group of queries
-                Timed t(h, K_SCAN, s);
-                hpfw::launch_expand_queries(d_q_hp, d_q_off, ng, kt_pad, h->index.d_qa.get(), s);
-                hpfw::launch_overlap_mfma(db, db_off, (int)n_clips, d_q_off, ng, h->index.d_qa.get(), kt_pad, h->index.d_gk.as<int>(), (int)k_max,
-                                          min_overlap, (int)splits, h->index.d_ov_tab.get(), s);
-            } else if (k_max > 0) {
-                Timed t(h, K_SCAN, s);
-                hpfw::launch_overlap_popc(db, db_off, (int)n_clips, d_q_hp, d_q_off, ng, min_overlap, (int)splits, h->index.d_ov_tab.get(), s);
-            }
-            if ((rc = check_launch("overlap scan"))) return rc;
-            {
-                Timed t(h, K_TOPK, s);
-                hpfw::launch_overlap_select(h->index.d_ov_tab.get(), ng, (int)n_clips, (int)splits,
-                                            exclude ? h->index.d_ov_exclude.as<int32_t>() + g0 : nullptr, k, h->index.clip_base, d_out + g0 * k, s);
-            }
-            if ((rc = check_launch("overlap_select"))) return rc;
-            if (d_stats) { // (the select kernel has folded every clip's splits into its first entry)
-                Timed t(h, K_TOPK, s);
-                hpfw::launch_overlap_stats(h->index.d_ov_tab.get(), ng, (int)n_clips, (int)splits,
-                                           exclude ? h->index.d_ov_exclude.as<int32_t>() + g0 : nullptr, d_stats + g0, s);
-            }
-            if (d_stats && (rc = check_launch("overlap_stats"))) return rc;
-        }
+        const int64_t qgroup = hpfw::search_group_queries(n_q, n_clips * splits, hpfw::kOverlapTableEntries, hpfw::kPopcGridQueries, 16,
+                                                          env_table_kb("HPFW_OVERLAP_TABLE_KB"));
+        const uint64_t *db = h->index.d_db.as<uint64_t>();
+        auto skip = [&](const QueryGroup &g) { return exclude ? h->index.d_ov_exclude.as<int32_t>() + g.g0 : nullptr; };
+        std::vector<SearchStep> steps;
+        if (k_max > 0)
+            steps.push_back({K_SCAN, "overlap scan", true, [&](const QueryGroup &g) {
+                                 const int64_t *db_off = h->index.d_db_off.as<int64_t>();
+                                 if (mfma)
+                                     hpfw::launch_overlap_mfma(db, db_off, (int)n_clips, g.d_q_off, g.ng, g.d_qa, g.kt_pad, g.d_gk, (int)k_max, min_overlap,
+                                                               splits, h->index.d_ov_tab.get(), s);
+                                 else
+                                     hpfw::launch_overlap_popc(db, db_off, (int)n_clips, d_q_hp, g.d_q_off, g.ng, min_overlap, splits, h->index.d_ov_tab.get(), s);
+                                 return 0;
+                             }});
+        steps.push_back({K_TOPK, "overlap_select", false, [&](const QueryGroup &g) {
+                             hpfw::launch_overlap_select(h->index.d_ov_tab.get(), g.ng, (int)n_clips, splits, skip(g), k, h->index.clip_base, d_out + g.g0 * k, s);
+                             return 0;
+                         }});
+        if (d_stats) // (the select kernel has folded every clip's splits into its first entry)
+            steps.push_back({K_TOPK, "overlap_stats", false, [&](const QueryGroup &g) {
+                                 hpfw::launch_overlap_stats(h->index.d_ov_tab.get(), g.ng, (int)n_clips, splits, skip(g), d_stats + g.g0, s);
+                                 return 0;
+                             }});
+        if ((rc = search_run_groups(h, s, d_q_hp, q_off, n_q, k_max, qgroup, mfma && k_max > 0, h->index.d_ov_tab, (size_t)n_clips * splits * 16, steps)))
+            return rc;
         if (exclude) HIP_TRY(hipStreamSynchronize(s)); // (the caller's array has been read)
         return 0;
     });

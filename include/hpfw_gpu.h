@@ -435,7 +435,13 @@ int hpfw_gpu_index_remove_plan(const int64_t *offsets, int64_t n_clips, const in
 int hpfw_gpu_index_remove_geometry(int64_t *tile, int64_t *chunk);
 
 /* top-k clips per query, ascending (dist, clip): query q is q_hp[q_off[q] .. q_off[q+1]).
- * d_q_hp device; q_off host; d_out device [n_q][k].  k <= 64. */
+ * d_q_hp device; q_off host; d_out device [n_q][k].  k <= 64.
+ * Environment (tests, timing; the results are the same bytes), read per call: HPFW_SEARCH_POPC -- the xor/popcount scan for
+ * every query (it otherwise serves queries whose window does not fit the LDS); HPFW_SEARCH_MFMA / HPFW_SEARCH_SHIFT -- the
+ * grouped / the shifted-rows matrix-core scan for any number of queries (the default: shifted rows below 8 queries);
+ * HPFW_SEARCH_TABLE_KB=<KiB> -- the size of the (query, clip) table of one pass over the queries (default and most 1 GiB,
+ * at least 32 queries' rows), for tests of more than one pass.  They act on the scored, transposed and within-sets forms
+ * too. */
 int hpfw_gpu_search_topk_device(hpfw_gpu *h, const uint64_t *d_q_hp, const int64_t *q_off,
                                 int64_t n_q, int k, hpfw_hit *d_out, void *stream);
 /* host convenience: copies queries in and hits out, synchronises */
@@ -521,7 +527,9 @@ int hpfw_gpu_merge_topk(const hpfw_hit *in, int n_shards, int64_t n_q, int k, hp
  * entry below -1 or at or above the number of clips (HPFW_E_INVALID); a query above 16000 hashprints (HPFW_E_UNSUPPORTED).
  * An empty index, a query without candidates and the slots past the last candidate give padding records.
  * Environment (tests; the results are the same bytes): HPFW_OVERLAP_POPC -- the xor/popcount kernel for every query (it
- * otherwise serves queries whose window does not fit the LDS); HPFW_OVERLAP_SPLITS=<1..64> -- workgroups per clip. */
+ * otherwise serves queries whose window does not fit the LDS); HPFW_OVERLAP_SPLITS=<1..64> -- workgroups per clip;
+ * HPFW_OVERLAP_TABLE_KB=<KiB> -- the size of the (query, clip, split) table of one pass over the queries (default and most
+ * 1 GiB, at least 32 queries' rows), for tests of more than one pass. */
 typedef struct {
     uint32_t dist;    /* mismatching bits over the overlap                 */
     uint32_t clip;    /* as hpfw_hit; 0xffffffff = none                    */
@@ -680,7 +688,9 @@ int hpfw_gpu_dtw_geometry(int32_t *strip, int32_t *block);
  * from a walk of its diagonal that computes the score again; a walk that does not give the scan's score fails the call
  * (HPFW_E_HIP); the device form waits for its stream to learn that, unless there was nothing to scan.
  * Environment (tests; the results are the same bytes): HPFW_LOCAL_POPC -- the xor/popcount kernel for every query (it
- * otherwise serves queries whose window does not fit the LDS).  The sharded index (hpfw_gpu_multi.h) has no local search. */
+ * otherwise serves queries whose window does not fit the LDS); HPFW_LOCAL_TABLE_KB=<KiB> -- the size of the (query, clip)
+ * table of one pass over the queries (default and most 512 MiB, at least 32 queries' rows), for tests of more than one
+ * pass.  The sharded index (hpfw_gpu_multi.h) has no local search. */
 typedef struct {
     int32_t score;    /* T length - dist                                   */
     uint32_t clip;    /* as hpfw_hit; 0xffffffff = none                    */

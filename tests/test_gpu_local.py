@@ -8,6 +8,7 @@ import pytest
 import hpfw_amd
 from hpfw_amd import _lib, synth
 
+import group_case
 import local_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -174,6 +175,24 @@ def test_batches(lc, kernel):
             got = _check(lc, db, queries, 3, T, ("batch", n_q, T))
         assert (got["clip"][[len(q) == 0 for q in queries]] == NONE).all()
         assert got["clip"][[len(q) > 0 for q in queries], 0].max() < NONE
+
+
+def test_query_groups(lc, kernel):
+    """HPFW_LOCAL_TABLE_KB=1: the table holds 32 queries' rows (5 clips x 8 bytes each), so the 70 queries of group_case run in
+    passes of 32, 32 and 6 -- the later passes' offsets into the queries and the hits, and the reuse of the table and the image.
+    The call returns, so no winner's walk disagreed with the scan in any pass."""
+    clips, queries = group_case.case()
+    db = _index(lc, clips)
+    T, k = 12, 2
+    with group_case.env(HPFW_LOCAL_TABLE_KB=1):
+        got = _check(lc, db, queries, k, T, ("query groups", T))
+    assert got.tobytes() == lc.search_local(*_lib._ragged(queries, np.uint64), k, T).tobytes()
+    assert "HPFW_LOCAL_TABLE_KB" not in os.environ
+    for i in range(group_case.N_Q):                      # a planted passage of at least 11 hashprints: some 9 a hashprint
+        assert (got[i, 0]["clip"] != NONE and got[i, 0]["score"] >= 60) == group_case.planted(i), i
+    assert (got[group_case.EMPTY]["clip"] == NONE).all()
+    assert int(got[group_case.LONG, 0]["clip"]) == 0 and int(got[group_case.LONG, 0]["length"]) >= 20   # the clip inside the query
+    assert got[group_case.TWINS[0]].tobytes() == got[group_case.TWINS[1]].tobytes()
 
 
 def test_ties_and_padding(lc, kernel):

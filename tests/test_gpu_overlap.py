@@ -8,7 +8,9 @@ import pytest
 import hpfw_amd
 from hpfw_amd import _lib, synth
 
+import group_case
 import overlap_ref as ref
+import overlap_score_ref
 
 pytestmark = pytest.mark.gpu
 CHUNK = _lib.OVERLAP_CHUNK
@@ -222,6 +224,33 @@ def test_exclude_all_against_all(ov, kernel):
     want = got.copy()
     want["clip"][got["clip"] != 0xFFFFFFFF] += 1000
     _same(based, want, "clip_base")
+
+
+def test_query_groups(ov, kernel):
+    """HPFW_OVERLAP_TABLE_KB=4 with two splits a clip: the table holds 32 queries' rows (5 clips x 2 splits x 16 bytes each,
+    5 KiB -- the floor), so the 70 queries of group_case run in passes of 32, 32 and 6.  `exclude` names another clip for
+    every query, so a later pass must read its own part of it; plain and scored."""
+    clips, queries = group_case.case()
+    db = _index(ov, clips)
+    q_hp, q_off = _lib._ragged(queries, np.uint64)
+    mo, k = 8, 3
+    exclude = [(-1, 0, 1, 3, 4)[i % 5] for i in range(group_case.N_Q)]
+    with group_case.env(HPFW_OVERLAP_TABLE_KB=4, HPFW_OVERLAP_SPLITS=2):
+        got = _check(ov, db, queries, k, mo, ("query groups", mo), exclude=exclude)
+        hits, stats = ov.search_overlap_scored(q_hp, q_off, k, mo, exclude=exclude)
+    assert "HPFW_OVERLAP_TABLE_KB" not in os.environ and "HPFW_OVERLAP_SPLITS" not in os.environ
+    assert got.tobytes() == hits.tobytes() == ov.search_overlap(q_hp, q_off, k, mo, exclude=exclude).tobytes()
+    one_pass = ov.search_overlap_scored(q_hp, q_off, k, mo, exclude=exclude)
+    assert hits.tobytes() == one_pass[0].tobytes() and stats.tobytes() == one_pass[1].tobytes()
+    if "query groups, moments" not in _REF:
+        _REF["query groups, moments"] = [overlap_score_ref.row_moments(overlap_score_ref.candidates(db[0], db[1], q, mo), ex)
+                                         for q, ex in zip(queries, exclude)]
+    assert [(int(r["n"]), int(r["sum"]), int(r["sum_sq"])) for r in stats] == _REF["query groups, moments"]
+    for i, (q, ex) in enumerate(zip(queries, exclude)):  # every clip of 8 hashprints or more but the excluded one, if the query has 8
+        live = [c for c, n in enumerate(group_case.CLIP_LENGTHS) if n >= mo and c != ex] if len(q) >= mo else []
+        assert (got[i]["clip"] != 0xFFFFFFFF).sum() == min(k, len(live)) and ex not in got[i]["clip"], i
+    assert (got[group_case.EMPTY]["clip"] == 0xFFFFFFFF).all()
+    assert int(got[group_case.LONG, 0]["clip"]) == 0 and int(got[group_case.LONG, 0]["overlap"]) == 40   # it overhangs clip 0 on both sides
 
 
 def test_min_overlap_k_is_search_topk(ov, kernel):

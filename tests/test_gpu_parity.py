@@ -4,6 +4,8 @@ offsets and top-k order; the float stages are also required to be bit-exact agai
 (both implement DESIGN.md's arithmetic specification) and within 1e-4 of the maximum against the
 float64 definition (oracle/nsgt_f64.py) -- the tolerance BASELINE.json's north_star states for the
 CQT magnitudes."""
+import os
+
 import numpy as np
 import pytest
 
@@ -196,6 +198,9 @@ def test_projection_edge_values(gpu, torch_cuda, oracle, filters):
     assert (hp_ref[1] == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
 
 
+_GROUPS = {}                                             # test_search_query_groups' references, shared by the scans
+
+
 def _ragged(rng, lens):
     hp = [rng.integers(0, 2 ** 64, size=n, dtype=np.uint64) for n in lens]
     off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -278,6 +283,51 @@ def test_search_many_ragged_queries(gpu, oracle, scan_path):
     want = oracle.search_topk(db, db_off, q, q_off, 7, n_threads=4)
     assert np.array_equal(got, want)
     assert (got[0]["clip"] == 0xFFFFFFFF).all()          # the empty query matches nothing
+
+
+def test_search_query_groups(gpu, oracle, scan_path):
+    """HPFW_SEARCH_TABLE_KB=1: the table holds 32 queries' rows (5 clips x 8 bytes each), so the 70 queries of group_case run in
+    passes of 32, 32 and 6, and a transposed call of the 70 queries with 2 variants each (140 rows) in five (32, 32, 32, 32 and
+    12) -- the later passes' offsets into the queries, the hits and the moments, and the reuse of the table and the queries'
+    image; plain and scored, on every scan"""
+    import group_case
+    import within_ref
+    from hpfw_amd import _lib
+    clips, queries = group_case.case()
+    db, db_off = _lib._ragged(clips, np.uint64)
+    q, q_off = _lib._ragged(queries, np.uint64)
+    gpu.index_clear()
+    gpu.index_add(db, db_off)
+    k, everywhere = 3, np.full(group_case.N_Q, -1, np.int32)
+    # variant 1 of query i: the query with one bit of every hashprint flipped
+    q2, q2_off = _lib._ragged([v for i, qq in enumerate(queries) for v in (qq, qq ^ np.uint64(1 << (i % 64)))], np.uint64)
+    assert q2_off.size - 1 == 140
+    if "want" not in _GROUPS:
+        _GROUPS["want"] = (oracle.search_topk(db, db_off, q, q_off, k, n_threads=4),
+                           within_ref.moments_within(oracle, db, db_off, q, q_off, [0], [], everywhere),
+                           within_ref.transposed_within(oracle, db, db_off, q2, q2_off, 2, k, [0], [], everywhere),
+                           within_ref.moments_within(oracle, db, db_off, q2, q2_off, [0], [], np.repeat(everywhere, 2)))
+    want, want_moments, want_transposed, want_transposed_moments = _GROUPS["want"]
+    with group_case.env(HPFW_SEARCH_TABLE_KB=1):
+        got = gpu.search_topk(q, q_off, k)
+        hits, stats = gpu.search_topk_scored(q, q_off, k)
+        shifted, shifted_stats = gpu.search_topk_transposed_scored(q2, q2_off, 2, k)
+    assert "HPFW_SEARCH_TABLE_KB" not in os.environ
+    assert np.array_equal(got, want) and got.tobytes() == hits.tobytes() == gpu.search_topk(q, q_off, k).tobytes()
+    one_pass = gpu.search_topk_scored(q, q_off, k)
+    assert hits.tobytes() == one_pass[0].tobytes() and stats.tobytes() == one_pass[1].tobytes()
+    assert [(int(r["n"]), int(r["sum"]), int(r["sum_sq"])) for r in stats] == want_moments
+    one_pass = gpu.search_topk_transposed_scored(q2, q2_off, 2, k)
+    assert shifted.shape == (group_case.N_Q, k) and shifted_stats.shape == (group_case.N_Q, 2)
+    assert shifted.tobytes() == one_pass[0].tobytes() and shifted_stats.tobytes() == one_pass[1].tobytes()
+    assert [[tuple(int(v) for v in h) for h in row] for row in shifted] == want_transposed
+    assert [(int(r["n"]), int(r["sum"]), int(r["sum_sq"])) for r in shifted_stats.ravel()] == want_transposed_moments
+    assert shifted.tobytes() == gpu.search_topk_transposed(q2, q2_off, 2, k).tobytes()
+    # every query but the empty one has a hit in each of the four clips that hold hashprints (storage.h:37-39: k = min(k, n),
+    # the query that is longer than every clip included); a planted passage of a whole query comes first
+    assert (got[group_case.EMPTY]["clip"] == 0xFFFFFFFF).all() and want_moments[group_case.EMPTY] == (0, 0, 0)
+    assert (np.delete(got["clip"], group_case.EMPTY, axis=0) != 0xFFFFFFFF).all()
+    assert got[group_case.TWINS[0]].tobytes() == got[group_case.TWINS[1]].tobytes()
 
 
 def test_search_large_index_few_queries(gpu, oracle):

@@ -11,6 +11,7 @@ import pytest
 import hpfw_amd
 from hpfw_amd import _lib, synth
 
+import group_case
 import overlap_score_ref
 import timeline_ref
 import within_ref as ref
@@ -304,6 +305,38 @@ def test_scored(wg, twin, oracle, scan_path):
             assert (math.isnan(sc) and math.isnan(got)) or abs(got - sc) <= 1e-12 * abs(sc), (s, qi, got, sc)
             if want[qi][0] < 3:
                 assert math.isnan(got)                        # fewer than 3 counted clips: as an index of 2 clips
+
+
+def test_query_groups(wg, oracle, scan_path):
+    """HPFW_SEARCH_TABLE_KB=1: a table of 32 queries' rows (-1: 5 clips, 1 280 bytes; the set of 2 clips: 512 bytes, so 32 rows
+    are the floor).  q_set mixes -1, a set of 2 clips and an empty set, so the 70 queries of group_case are regrouped into
+    ranges of 33, 33 and 4: the range of -1 and the range of the set each run in passes of 32 and 1 -- the set's second pass
+    meets the ClipView with offsets into the regrouped q_off, hits and moments -- where the call without the switch takes one
+    pass each; scored"""
+    clips, queries = group_case.case()
+    db_hp, db_off = _lib._ragged(clips, np.uint64)
+    q_hp, q_off = _lib._ragged(queries, np.uint64)
+    _index(wg, db_hp, db_off)
+    sets = [[1, 3], []]
+    set_off, set_clips = _csr(sets)
+    q_set = np.array([-1, 0] * (group_case.N_Q // 2), np.int32)
+    q_set[[5, 25, 44, 64]] = 1                                # (two of the set's and two of -1's go to the empty set)
+    assert [int((q_set == s).sum()) for s in (-1, 0, 1)] == [33, 33, 4]
+    k = 3
+    with group_case.env(HPFW_SEARCH_TABLE_KB=1):
+        got, stats = wg.search_topk_within(q_hp, q_off, k, set_off, set_clips, q_set, scored=True)
+    assert "HPFW_SEARCH_TABLE_KB" not in os.environ
+    one_pass = wg.search_topk_within(q_hp, q_off, k, set_off, set_clips, q_set, scored=True)
+    assert got.tobytes() == one_pass[0].tobytes() and stats.tobytes() == one_pass[1].tobytes()
+    want = _restated(oracle, "query groups", db_hp, db_off, q_hp, q_off, set_off, set_clips, q_set)[:, :k]
+    _same(got, want, "against the restatement")
+    if "query groups, moments" not in _REF:
+        _REF["query groups, moments"] = ref.moments_within(oracle, db_hp, db_off, q_hp, q_off, set_off, set_clips, q_set)
+    assert _moments(stats) == _REF["query groups, moments"]
+    for i in range(group_case.N_Q):                           # every clip of the query's set that holds hashprints, no other
+        live = 0 if i == group_case.EMPTY else {-1: 4, 0: 2, 1: 0}[int(q_set[i])]
+        assert (got[i]["clip"] != NONE).sum() == min(k, live), i
+        assert q_set[i] != 0 or i == group_case.EMPTY or np.isin(got[i]["clip"][:2], [1, 3]).all(), i
 
 
 def test_transposed(wg, twin, oracle, scan_path):

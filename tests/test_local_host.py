@@ -5,6 +5,7 @@ import ctypes
 import inspect
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -75,6 +76,24 @@ def test_bad_arguments_are_refused_without_a_device():
     assert rc == E_INVALID and b"non-decreasing" in msg
     rc, msg = both(q_off=np.array([0, 4, 16005], np.int64))
     assert rc == E_UNSUPPORTED and b"16000" in msg
+    rc, msg = both(q_off=np.array([0, 16005, 10], np.int64))  # both faults: the order is reported
+    assert rc == E_INVALID and b"non-decreasing" in msg
+
+
+def test_query_group_plan_under_sanitizers(tmp_path):
+    """search_plan.h is plain C++: the queries of one pass of the plain, overlap and local searches for a sweep of queries,
+    clips, splits and tables against the formulas the searches had before the header, a table switch's properties, and the
+    groups' lengths -- in a program of its own under ASan and UBSan"""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    exe = tmp_path / "search_plan_check"
+    src = os.path.join(ROOT, "tests", "emu", "search_plan_check.cpp")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "search_plan_check ok" in r.stdout
 
 
 def test_restatement_equals_enumeration_of_all_runs():

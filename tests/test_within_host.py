@@ -106,6 +106,8 @@ def test_bad_arguments_are_refused_without_a_device():
     assert rc == E_INVALID and b"non-decreasing" in msg
     rc, msg = all4(q_off=i64(0, 4, 16005))
     assert rc == E_UNSUPPORTED and b"16000" in msg
+    rc, msg = all4(q_off=i64(0, 16005, 10))                   # both faults: the first faulty query's is reported
+    assert rc == E_UNSUPPORTED and b"16000" in msg
     # the transposed forms refuse a bad n_shifts as the unrestricted ones do
     a = (_p(i64(0, 2, 3)), 2, _p(i32(0, 5, 2)), _p(i32(0, -1)))
     for n_shifts in (0, -1, 65):
