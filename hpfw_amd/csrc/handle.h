@@ -60,7 +60,10 @@ struct DevPlan {
     hpfw::BzArgs bz; // clip lengths with a prime factor above 7 (hp.bluestein)
     hpfw::CqPlanDev cq;
     std::vector<hpfw::CqClassDev> cls;
-    size_t bytes = 0;      // device memory of the tables
+    int cq_rows_max = 0;   // the largest band of cq.g2, in entries (what its generator's launch is sized by)
+    // the tables' bytes as they are asked for (not the pool's block sizes): every upload and every device-generated table adds
+    // its own while the plan is built; the cache's budget is charged in this
+    size_t bytes = 0;
     uint64_t last_use = 0; // for the least-recently-used eviction in get_plan
     ~DevPlan(); // (gives its blocks back to the handle's pool)
 };

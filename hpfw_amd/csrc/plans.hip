@@ -1,6 +1,7 @@
 // plans.hip -- the per-length tables (plan.h's host half, generated or uploaded to the device) and their cache, the
 // handle's pool of device memory, and the workspaces that may take memory back from that pool.
 #include "handle.h"
+#include "plan_cache.h"
 
 // HPFW_PLAN_TIMING=1: where the first use of a clip length spends the host's time (printed when the handle goes)
 struct PlanTiming {
@@ -10,7 +11,8 @@ struct PlanTiming {
 };
 
 namespace {
-thread_local size_t g_uploaded = 0; // bytes uploaded by upload() since get_plan last reset it
+using hpfw::cf;
+static_assert(sizeof(hpfw::HostCf) == sizeof(cf), "complex layout");
 
 hpfw::RadixList to_radix(const std::vector<int> &r)
 {
@@ -27,11 +29,11 @@ void pool_release(hpfw_gpu *h);
 
 constexpr size_t kPlanChunk = (size_t)4 << 20;
 
-thread_local PlanTiming *g_plan_timing = nullptr;
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// adds its lifetime to one part of the handle's PlanTiming (nothing without HPFW_PLAN_TIMING)
 struct PlanTimer {
     double *acc, t0;
-    explicit PlanTimer(double PlanTiming::*m) : acc(g_plan_timing ? &(g_plan_timing->*m) : nullptr), t0(acc ? now_s() : 0.0) {}
+    PlanTimer(hpfw_gpu *h, double PlanTiming::*m) : acc(h->cache.plan_timing ? &(h->cache.plan_timing.get()->*m) : nullptr), t0(acc ? now_s() : 0.0) {}
     ~PlanTimer()
     {
         if (acc) *acc += now_s() - t0;
@@ -54,7 +56,7 @@ int plan_flush(DevPlan *dp)
 
 int plan_alloc(DevPlan *dp, size_t bytes, void **out)
 {
-    PlanTimer t(&PlanTiming::alloc);
+    PlanTimer t(dp->owner, &PlanTiming::alloc);
     bytes = (bytes + 255) / 256 * 256;
     if (bytes >= kPlanChunk / 4) { // a block of its own, in 64 KB steps (equal sizes recur: lengths near each other share n1 and n2)
         DevBuf b = pool_take(dp->owner, (bytes + 65535) / 65536 * 65536);
@@ -82,7 +84,7 @@ int plan_alloc(DevPlan *dp, size_t bytes, void **out)
 template <class T>
 int upload(const std::vector<T> &v, const T **out, DevPlan *dp)
 {
-    g_uploaded += v.size() * sizeof(T);
+    dp->bytes += v.size() * sizeof(T);
     if (v.empty()) {
         *out = nullptr;
         return 0;
@@ -104,14 +106,25 @@ int upload(const std::vector<T> &v, const T **out, DevPlan *dp)
     return 0;
 }
 
+// room for a table that the device generates, counted like an uploaded one (an empty table still gets a valid pointer)
+template <class T>
+int device_table(DevPlan *dp, size_t bytes, const T **out)
+{
+    void *d = nullptr;
+    dp->bytes += bytes;
+    const int rc = plan_alloc(dp, std::max<size_t>(bytes, 1), &d);
+    *out = static_cast<const T *>(d);
+    return rc;
+}
+
 constexpr size_t kPinRing = (size_t)48 << 20;
 
 hipError_t plan_h2d(hpfw_gpu *h, void *dst, const void *src, size_t bytes)
 {
-    PlanTimer t(&PlanTiming::upload);
-    if (g_plan_timing) {
-        ++g_plan_timing->copies;
-        g_plan_timing->copied += bytes;
+    PlanTimer t(h, &PlanTiming::upload);
+    if (PlanTiming *pt = h->cache.plan_timing.get()) {
+        ++pt->copies;
+        pt->copied += bytes;
     }
     if (!h->cache.pin_ring && h->cache.pin_ring.alloc(kPinRing) != hipSuccess) (void)hipGetLastError();
     const hipStream_t ps = h->cache.plan_stream.get();
@@ -191,47 +204,66 @@ DevPlan::~DevPlan()
     for (DevBuf &b : blocks) pool_give(owner, std::move(b));
 }
 
-int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
+// ---- the tables of a new clip length: get_plan's steps, in its order ------------------------------
+namespace {
+// HPFW_FORCE_BLUESTEIN=1 (tests): the chirp-z forward transform for 7-smooth lengths too.  Read whenever a plan is built.
+bool force_bluestein() { return std::getenv("HPFW_FORCE_BLUESTEIN") != nullptr; }
+// HPFW_PLAN_CACHE_GB (default 16): the bytes of tables the cache keeps.  Read whenever a plan is built.
+size_t plan_cache_budget()
 {
-    auto it = h->cache.plans.find(n);
-    if (it != h->cache.plans.end()) {
-        it->second->last_use = ++h->cache.plan_clock;
-        *out = it->second.get();
-        return 0;
-    }
-    g_uploaded = 0;
-    g_plan_timing = h->cache.plan_timing.get();
-    PlanTimer whole(&PlanTiming::total);
-    if (g_plan_timing) ++g_plan_timing->plans;
-    auto dp = std::make_unique<DevPlan>();
-    dp->owner = h;
+    const char *e = std::getenv("HPFW_PLAN_CACHE_GB");
+    return e ? (size_t)(std::max(0.0, std::atof(e)) * 1073741824.0) : (size_t)16 << 30;
+}
+int unsupported(int64_t n, const std::string &why) { return fail(HPFW_E_UNSUPPORTED, "clip length " + std::to_string(n) + ": " + why); }
+// the host plan of a clip length (geometry_only: its sizes alone, microseconds), or why the length is not supported
+int host_plan(const hpfw_gpu *h, int64_t n, hpfw::HostPlan &hp, bool geometry_only)
+{
     std::string why;
-    bool have_host = false;
+    return hpfw::build_plan(n, hp, why, geometry_only, force_bluestein(), h->conventions, false) ? 0 : unsupported(n, why);
+}
+
+// The host half may have been prepared (or be in preparation) by a reader thread: take it, or wait for it.  Registers the
+// length as seen; false: there is no host half (a failed preparation leaves an empty plan: rebuilt for its message).
+bool take_host_half(hpfw_gpu *h, DevPlan *dp, int64_t n)
+{
+    PlanTimer t(h, &PlanTiming::host_wait);
+    bool have = false;
+    std::unique_lock<std::mutex> lock(h->cache.host_mtx);
+    auto ready = h->cache.host_ready.find(n);
+    if (ready != h->cache.host_ready.end()) {
+        h->cache.host_cv.wait(lock, [&] { return h->cache.host_ready.find(n)->second != nullptr; });
+        ready = h->cache.host_ready.find(n);
+        have = ready->second->n == n;
+        if (have) dp->hp = std::move(*ready->second);
+        h->cache.host_ready.erase(ready);
+    }
+    h->cache.host_seen.insert(n);
+    return have;
+}
+// A get_plan that fails leaves the cache as it found it: the length is not seen any more, so hpfw_gpu_prepare_length builds
+// (and an unsupported length says so) every time it is asked for.  The plan's blocks go back to the pool with the DevPlan.
+struct SeenGuard {
+    hpfw_gpu *h;
+    int64_t n;
+    bool dismissed = false;
+    ~SeenGuard()
     {
-        PlanTimer t(&PlanTiming::host_wait);
-        // the host half may have been prepared (or be in preparation) by a reader thread: take it, or wait for it
-        std::unique_lock<std::mutex> lock(h->cache.host_mtx);
-        auto ready = h->cache.host_ready.find(n);
-        if (ready != h->cache.host_ready.end()) {
-            h->cache.host_cv.wait(lock, [&] { return h->cache.host_ready.find(n)->second != nullptr; });
-            ready = h->cache.host_ready.find(n);
-            have_host = ready->second->n == n;     // (a failed preparation leaves an empty plan: rebuilt below for its message)
-            if (have_host) dp->hp = std::move(*ready->second);
-            h->cache.host_ready.erase(ready);
-        }
-        h->cache.host_seen.insert(n);
+        if (dismissed) return;
+        std::scoped_lock lock(h->cache.host_mtx);
+        h->cache.host_seen.erase(n);
     }
-    // HPFW_FORCE_BLUESTEIN=1 (tests): the chirp-z forward transform for 7-smooth lengths too
-    if (!have_host) {
-        PlanTimer t(&PlanTiming::host_build);
-        if (!hpfw::build_plan(n, dp->hp, why, false, std::getenv("HPFW_FORCE_BLUESTEIN") != nullptr, h->conventions, false))
-            return fail(HPFW_E_UNSUPPORTED, "clip length " + std::to_string(n) + ": " + why);
-    }
-    const hpfw::HostPlan &p = dp->hp;
-    using hpfw::cf;
-    int rc;
-    static_assert(sizeof(hpfw::HostCf) == sizeof(cf), "complex layout");
-    hpfw::RowsArgs &ra = dp->rows;
+};
+
+int build_host_half(hpfw_gpu *h, DevPlan *dp, int64_t n)
+{
+    PlanTimer t(h, &PlanTiming::host_build);
+    return host_plan(h, n, dp->hp, false);
+}
+
+// the row transform's arguments, its tables not yet in place
+hpfw::RowsArgs rows_args(const hpfw::HostPlan &p)
+{
+    hpfw::RowsArgs ra;
     std::memset(&ra, 0, sizeof(ra));
     ra.n1 = p.n1;
     ra.n2 = p.n2;
@@ -244,89 +276,96 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
         ra.groups.r2[g] = p.groups[g].second;
         ra.groups.tw_off[g] = p.rows_gtw_off[g];
     }
-    if ((rc = upload(p.rows_gtw, reinterpret_cast<const hpfw::HostCf **>(&ra.gtw), dp.get()))) return rc;
-    if ((rc = upload(p.pos_n2, &ra.pos_n2, dp.get()))) return rc;
-    if ((rc = upload(p.kb_last, &ra.kb_last, dp.get()))) return rc;
-    if (hpfw::fwd_rows_lds_bytes(ra) > 160 * 1024) return fail(HPFW_E_UNSUPPORTED, "n2 exceeds the LDS");
+    return ra;
+}
+
+// what cannot run is refused before any device memory is taken: both bounds depend on the host plan alone
+int refuse_unrunnable(hpfw_gpu *, DevPlan *dp)
+{
+    if (hpfw::fwd_rows_lds_bytes(rows_args(dp->hp)) > 160 * 1024 || !hpfw::row_fits_lds(dp->hp.n2))
+        return fail(HPFW_E_UNSUPPORTED, "n2 exceeds the LDS");
+    return 0;
+}
+
+int rows_tables(hpfw_gpu *, DevPlan *dp)
+{
+    const hpfw::HostPlan &p = dp->hp;
+    hpfw::RowsArgs &ra = dp->rows;
+    ra = rows_args(p);
+    int rc;
+    if ((rc = upload(p.rows_gtw, reinterpret_cast<const hpfw::HostCf **>(&ra.gtw), dp))) return rc;
+    if ((rc = upload(p.pos_n2, &ra.pos_n2, dp))) return rc;
+    return upload(p.kb_last, &ra.kb_last, dp);
+}
+
+// Temporaries of table generation (T_n1, the generation scratch) come from the handle's pool and go back to it: hipFree
+// waits for every stream of the device, which would stop a caller that extracts on a stream of its own from preparing the
+// next length while the previous file's kernels run.  (No host wait before they go back either: the pool's next user is
+// ordered after the generating kernels on the handle's table stream like every table generation and upload; the stream that
+// extracts waits for the event get_plan records.)
+struct PoolTmp {
+    hpfw_gpu *h;
+    std::vector<DevBuf> v;
+    ~PoolTmp() { for (DevBuf &b : v) pool_give(h, std::move(b)); }
+    int take(size_t bytes, void **out)
+    {
+        DevBuf b = pool_take(h, (bytes + 65535) / 65536 * 65536);
+        if (!b) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
+        v.push_back(std::move(b));
+        *out = v.back().get();
+        return 0;
+    }
+};
+
+// Clip lengths with a prime factor above 7: the coefficient images of the column transforms (the first one's two stages; the
+// second one's rows that hold consumed bins) are packed on the device, and chirp, T_L, w[k] / L and Bhat are generated there
+// (k_bluestein.hip): a corpus of real recordings brings a new length with every file.
+int chirpz_tables(hpfw_gpu *h, DevPlan *dp)
+{
+    const hpfw::HostPlan &p = dp->hp;
     hpfw::BzArgs &bz = dp->bz;
     std::memset(&bz, 0, sizeof(bz));
-    if (p.bluestein) {
-        PlanTimer t_dev(&PlanTiming::device_tables);
-        bz.n1 = p.n1;
-        bz.n2 = p.n2;
-        bz.n2pad = (p.n2 + 31) / 32 * 32;
-        bz.kmin = p.kmin;
-        bz.kmax = p.kmax;
-        {
-            const hpfw::BzShape s = hpfw::bz_shape(p.n1, p.n2, p.kmin, p.kmax); // (plan.h)
-            bz.a = s.a;
-            bz.n_tiles1 = s.n_tiles1;
-            bz.k1lo = s.k1lo;
-            bz.k1n = s.k1n;
-            bz.nt2 = s.nt2;
-            bz.n_tiles2 = s.n_tiles2;
-        }
-        // coefficient images of the column transforms (the first one's two stages; the second one's rows that hold
-        // consumed bins), packed on the device
-        // temporaries of this block (T_n1, the generation scratch) come from the handle's pool and go back to it: hipFree
-        // waits for every stream of the device, which would stop a caller that extracts on a stream of its own from
-        // preparing the next length while the previous file's kernels run
-        const cf *d_tw_n1 = nullptr;
-        struct PoolTmp {
-            hpfw_gpu *h;
-            std::vector<DevBuf> v;
-            ~PoolTmp() { for (DevBuf &b : v) pool_give(h, std::move(b)); }
-            void *take(size_t bytes)
-            {
-                DevBuf b = pool_take(h, (bytes + 65535) / 65536 * 65536);
-                if (!b) return nullptr;
-                v.push_back(std::move(b));
-                return v.back().get();
-            }
-        } tmp{h, {}};
-        {
-            void *d = tmp.take(p.tw_n1.size() * sizeof(cf));
-            if (!d) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
-            HIP_TRY(plan_h2d(h, d, p.tw_n1.data(), p.tw_n1.size() * sizeof(cf)));
-            d_tw_n1 = static_cast<const cf *>(d);
-        }
-        {
-            const size_t bytes[3] = {(size_t)bz.a * bz.n_tiles1 * 64 * sizeof(float), (size_t)bz.a * 16 * 64 * sizeof(float),
-                                     (size_t)p.n1 * bz.n_tiles2 * 64 * sizeof(float)};
-            const float **slot[3] = {&bz.apack1, &bz.apack3, &bz.apack2};
-            for (int i = 0; i < 3; ++i) {
-                void *d = nullptr;
-                if ((rc = plan_alloc(dp.get(), bytes[i], &d))) return rc;
-                g_uploaded += bytes[i];
-                *slot[i] = static_cast<const float *>(d);
-            }
-            if ((rc = plan_flush(dp.get()))) return rc; // the row transform's tables are used by the kernels below
-            hpfw::launch_bz_pack_stages(bz, d_tw_n1, const_cast<float *>(bz.apack1), const_cast<float *>(bz.apack3), h->cache.plan_stream.get());
-            hpfw::launch_bz_pack_coefficients(p.n1, bz.k1lo, bz.k1n, d_tw_n1, bz.n_tiles2, const_cast<float *>(bz.apack2), h->cache.plan_stream.get());
-        }
-        // chirp, T_L, w[k] / L and Bhat are generated on the device (k_bluestein.hip): a corpus of
-        // real recordings brings a new length with every file
-        const size_t big_l = (size_t)p.n1 * p.n2, plane = hpfw::bz_plane_bytes(bz, 1);
-        {
-            const size_t bytes[4] = {big_l * sizeof(cf), big_l * sizeof(cf), big_l * sizeof(cf), (size_t)(p.kmax - p.kmin) * sizeof(cf)};
-            const void **slot[4] = {reinterpret_cast<const void **>(&bz.wp), reinterpret_cast<const void **>(&bz.tl),
-                                    reinterpret_cast<const void **>(&bz.bhat), reinterpret_cast<const void **>(&bz.wk)};
-            for (int i = 0; i < 4; ++i) {
-                void *d = nullptr;
-                if ((rc = plan_alloc(dp.get(), bytes[i], &d))) return rc;
-                g_uploaded += bytes[i];
-                *slot[i] = d;
-            }
-        }
-        void *scratch = tmp.take(big_l * 8 + plane); // back to the pool with T_n1 when this block ends, after the synchronisation below
-        if (!scratch) return fail(HPFW_E_HIP, "out of device memory for the tables of a clip length");
-        hpfw::launch_bz_make_tables(ra, bz, n, static_cast<float *>(scratch), static_cast<float *>(scratch) + 2 * big_l, h->cache.plan_stream.get());
-        // (no host wait: the temporaries go back to the pool, whose next user is ordered after these kernels on the handle's
-        // table stream like every table generation and upload; the stream that extracts waits for the event recorded below)
-        const hipError_t launched = hipGetLastError();
-        if (launched != hipSuccess) return fail(HPFW_E_HIP, std::string("chirp-z tables: ") + hipGetErrorString(launched));
-    }
-    // S6 (7-smooth lengths): the column stage's twiddle digits, digit-offset correction and inter-stage twiddles
+    if (!p.bluestein) return 0;
+    PlanTimer t(h, &PlanTiming::device_tables);
+    const hipStream_t ps = h->cache.plan_stream.get();
+    const hpfw::BzShape s = hpfw::bz_shape(p.n1, p.n2, p.kmin, p.kmax); // (plan.h)
+    bz.n1 = p.n1;
+    bz.n2 = p.n2;
+    bz.n2pad = (p.n2 + 31) / 32 * 32;
+    bz.kmin = p.kmin;
+    bz.kmax = p.kmax;
+    bz.a = s.a;
+    bz.n_tiles1 = s.n_tiles1;
+    bz.k1lo = s.k1lo;
+    bz.k1n = s.k1n;
+    bz.nt2 = s.nt2;
+    bz.n_tiles2 = s.n_tiles2;
+    int rc;
+    PoolTmp tmp{h, {}};
+    void *d_tw_n1 = nullptr, *scratch = nullptr;
+    if ((rc = tmp.take(p.tw_n1.size() * sizeof(cf), &d_tw_n1))) return rc;
+    HIP_TRY(plan_h2d(h, d_tw_n1, p.tw_n1.data(), p.tw_n1.size() * sizeof(cf)));
+    if ((rc = device_table(dp, (size_t)bz.a * bz.n_tiles1 * 64 * sizeof(float), &bz.apack1))) return rc;
+    if ((rc = device_table(dp, (size_t)bz.a * 16 * 64 * sizeof(float), &bz.apack3))) return rc;
+    if ((rc = device_table(dp, (size_t)p.n1 * bz.n_tiles2 * 64 * sizeof(float), &bz.apack2))) return rc;
+    if ((rc = plan_flush(dp))) return rc; // the row transform's tables are used by the kernels below
+    hpfw::launch_bz_pack_stages(bz, static_cast<const cf *>(d_tw_n1), const_cast<float *>(bz.apack1), const_cast<float *>(bz.apack3), ps);
+    hpfw::launch_bz_pack_coefficients(p.n1, bz.k1lo, bz.k1n, static_cast<const cf *>(d_tw_n1), bz.n_tiles2, const_cast<float *>(bz.apack2), ps);
+    const size_t big_l = (size_t)p.n1 * p.n2;
+    if ((rc = device_table(dp, big_l * sizeof(cf), &bz.wp))) return rc;
+    if ((rc = device_table(dp, big_l * sizeof(cf), &bz.tl))) return rc;
+    if ((rc = device_table(dp, big_l * sizeof(cf), &bz.bhat))) return rc;
+    if ((rc = device_table(dp, (size_t)(p.kmax - p.kmin) * sizeof(cf), &bz.wk))) return rc;
+    if ((rc = tmp.take(big_l * 8 + hpfw::bz_plane_bytes(bz, 1), &scratch))) return rc;
+    hpfw::launch_bz_make_tables(dp->rows, bz, p.n, static_cast<float *>(scratch), static_cast<float *>(scratch) + 2 * big_l, ps);
+    const hipError_t launched = hipGetLastError();
+    return launched == hipSuccess ? 0 : fail(HPFW_E_HIP, std::string("chirp-z tables: ") + hipGetErrorString(launched));
+}
+
+// S6 (7-smooth lengths): the column stage's twiddle digits, digit-offset correction and inter-stage twiddles
+int cols_tables(hpfw_gpu *h, DevPlan *dp)
+{
+    const hpfw::HostPlan &p = dp->hp;
     hpfw::ColsQArgs &ca = dp->cols;
     std::memset(&ca, 0, sizeof(ca));
     dp->rows_out = hpfw::Rows2Out{p.n1, p.hq, p.q2lo, p.q2w, nullptr, nullptr, (p.n2 + 3) / 4, 5 /* kZBlock / 4 = 2^5 pieces */,
@@ -336,169 +375,176 @@ int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
     // are among the first and last two of a block
     dp->rows_out.last_edges = (h->prune & 1u) && !p.bluestein && !p.groups.empty() &&
                               hpfw::rows_last_edges_ok(p.rows_last_mask, p.groups.back().first * p.groups.back().second);
-    if (!p.bluestein) {
-        ca.n1 = p.n1;
-        ca.n2 = p.n2;
-        ca.hq = p.hq;
-        ca.mt = p.cols_mt;
-        ca.ks = p.cols_ks;
-        ca.zclip = hpfw::z_floats_per_clip(p.hq, p.n2);
-        const int8_t *img = nullptr;
-        if ((rc = upload(p.cols_image, &img, dp.get()))) return rc;
-        ca.image = img;
-        if (!p.cols2_image.empty()) {
-            ca.mt2 = p.cols2_mt;
-            ca.ks2 = p.cols2_ks;
-            if ((rc = upload(p.cols2_image, &img, dp.get()))) return rc;
-            ca.image2 = img;
-        }
-        if ((rc = upload(p.cols_corr, &ca.corr, dp.get()))) return rc;
-        if ((rc = upload(p.ts_seed, reinterpret_cast<const hpfw::HostCf **>(&dp->rows_out.seed), dp.get()))) return rc;
-        if ((rc = upload(p.ts_step, reinterpret_cast<const hpfw::HostCf **>(&dp->rows_out.step), dp.get()))) return rc;
+    if (p.bluestein) return 0;
+    ca.n1 = p.n1;
+    ca.n2 = p.n2;
+    ca.hq = p.hq;
+    ca.mt = p.cols_mt;
+    ca.ks = p.cols_ks;
+    ca.zclip = hpfw::z_floats_per_clip(p.hq, p.n2);
+    int rc;
+    const int8_t *img = nullptr;
+    if ((rc = upload(p.cols_image, &img, dp))) return rc;
+    ca.image = img;
+    if (!p.cols2_image.empty()) {
+        ca.mt2 = p.cols2_mt;
+        ca.ks2 = p.cols2_ks;
+        if ((rc = upload(p.cols2_image, &img, dp))) return rc;
+        ca.image2 = img;
     }
+    if ((rc = upload(p.cols_corr, &ca.corr, dp))) return rc;
+    if ((rc = upload(p.ts_seed, reinterpret_cast<const hpfw::HostCf **>(&dp->rows_out.seed), dp))) return rc;
+    return upload(p.ts_step, reinterpret_cast<const hpfw::HostCf **>(&dp->rows_out.step), dp);
+}
+
+// where the constant-Q stage finds the forward bins (plan_cache.h), its band tables, and room for the windows, which the
+// device generates behind these uploads (generate_windows)
+int cq_layout_tables(hpfw_gpu *, DevPlan *dp)
+{
+    const hpfw::HostPlan &p = dp->hp;
     hpfw::CqPlanDev &c = dp->cq;
+    std::memset(&c, 0, sizeof(c)); // (g2 and its band tables stay null after the chirp-z forward transform)
+    const hpfw::CqXLayout x = hpfw::cq_x_layout(p);
     c.kmin = p.kmin;
     c.nk = p.kmax - p.kmin;
     c.c = p.c;
-    if (p.bluestein) { // natural order from kmin on
-        c.xn1 = 1;
-        c.xw = 0;
-        c.xq0 = p.kmin;
-        c.xclip = c.nk;
-        c.xmagic = 0;
-    } else {           // x[k mod n1][k / n1 - q2lo], rows of q2w
-        c.xn1 = p.n1;
-        c.xw = p.q2w;
-        c.xq0 = p.q2lo;
-        c.xclip = (int64_t)p.n1 * p.q2w;
-        c.xmagic = ((1ull << 40) + (unsigned long long)p.n1 - 1) / (unsigned long long)p.n1;
-    }
-    std::vector<int> start(p.start, p.start + 121), lg(p.lg, p.lg + 121);
-    if ((rc = upload(start, &c.start, dp.get()))) return rc;
-    if ((rc = upload(lg, &c.lg, dp.get()))) return rc;
-    if ((rc = upload(p.g_off, &c.g_off, dp.get()))) return rc;
-    // the window table itself is generated on the device, behind the uploads (below): S5, k_cq_tables.hip
-    {
-        void *d = nullptr;
-        if ((rc = plan_alloc(dp.get(), (size_t)std::max<int64_t>(p.g_total, 1) * sizeof(cf), &d))) return rc;
-        g_uploaded += (size_t)p.g_total * sizeof(cf);
-        c.g = static_cast<const cf *>(d);
-    }
-    int g2_max_entries = 0;
-    c.g2 = nullptr;
-    c.g2_off = nullptr;
-    c.q2a = c.nq2 = nullptr;
-    c.nq2_magic = nullptr;
+    c.xn1 = x.xn1;
+    c.xw = x.xw;
+    c.xq0 = x.xq0;
+    c.xclip = x.xclip;
+    c.xmagic = x.xmagic;
+    int rc;
+    const std::vector<int> start(p.start, p.start + 121), lg(p.lg, p.lg + 121);
+    if ((rc = upload(start, &c.start, dp))) return rc;
+    if ((rc = upload(lg, &c.lg, dp))) return rc;
+    if ((rc = upload(p.g_off, &c.g_off, dp))) return rc;
+    if ((rc = device_table(dp, (size_t)p.g_total * sizeof(cf), &c.g))) return rc;
     c.rows_min = 4; // (measured on one box: 0..8 alike, 16 and above slower; element by element throughout +0.4 ms per 1000 clips)
-    if (!p.bluestein) { // the windows once more, in the order the rows layout of the forward bins is read (kernels.h XsBandRows)
-        std::vector<int> q2a(121), nq2(121);
-        std::vector<unsigned> magic(121);
-        std::vector<int64_t> g2_off(121);
-        int64_t total = 0;
-        for (int j = 0; j < 121; ++j) {
-            q2a[j] = p.start[j] / p.n1;
-            nq2[j] = (p.start[j] + p.lg[j] - 1) / p.n1 - q2a[j] + 1;
-            magic[j] = nq2[j] >= 2 ? (unsigned)(((1ull << 32) + (unsigned)nq2[j] - 1) / (unsigned)nq2[j]) : 0u;
-            g2_off[j] = total;
-            total += (int64_t)p.n1 * nq2[j];
-        }
-        for (int j = 0; j < 121; ++j) g2_max_entries = std::max(g2_max_entries, p.n1 * nq2[j]);
-        {
-            void *d = nullptr;
-            if ((rc = plan_alloc(dp.get(), (size_t)std::max<int64_t>(total, 1) * sizeof(cf), &d))) return rc;
-            g_uploaded += (size_t)total * sizeof(cf);
-            c.g2 = static_cast<const cf *>(d);
-        }
-        if ((rc = upload(g2_off, &c.g2_off, dp.get()))) return rc;
-        if ((rc = upload(q2a, &c.q2a, dp.get()))) return rc;
-        if ((rc = upload(nq2, &c.nq2, dp.get()))) return rc;
-        if ((rc = upload(magic, &c.nq2_magic, dp.get()))) return rc;
-    }
-    for (const hpfw::BluesteinClass &bc : p.classes) {
+    if (p.bluestein) return 0;
+    // the windows once more, in the order the rows layout of the forward bins is read (kernels.h XsBandRows)
+    const hpfw::CqRowsLayout r = hpfw::cq_rows_layout(p);
+    dp->cq_rows_max = r.max_entries;
+    if ((rc = device_table(dp, (size_t)r.total * sizeof(cf), &c.g2))) return rc;
+    if ((rc = upload(r.g2_off, &c.g2_off, dp))) return rc;
+    if ((rc = upload(r.q2a, &c.q2a, dp))) return rc;
+    if ((rc = upload(r.nq2, &c.nq2, dp))) return rc;
+    return upload(r.magic, &c.nq2_magic, dp);
+}
+
+// one chirp-z size class for all bands that share a transform length
+int size_class_tables(hpfw_gpu *, DevPlan *dp)
+{
+    int rc;
+    for (const hpfw::BluesteinClass &bc : dp->hp.classes) {
         hpfw::CqClassDev cd;
         cd.p = bc.p;
         cd.n_bands = (int)bc.bands.size();
         cd.radix = to_radix(bc.radix);
-        if ((rc = upload(bc.tw, reinterpret_cast<const hpfw::HostCf **>(&cd.tw), dp.get()))) return rc;
-        if ((rc = upload(bc.gtw, reinterpret_cast<const hpfw::HostCf **>(&cd.gtw.tab), dp.get()))) return rc;
+        if ((rc = upload(bc.tw, reinterpret_cast<const hpfw::HostCf **>(&cd.tw), dp))) return rc;
+        if ((rc = upload(bc.gtw, reinterpret_cast<const hpfw::HostCf **>(&cd.gtw.tab), dp))) return rc;
         for (int g = 0; g < 4; ++g) cd.gtw.off[g] = bc.goff[g];
         cd.gtw.mid_off = bc.mid_off;
-        if ((rc = upload(bc.vrev, reinterpret_cast<const hpfw::HostCf **>(&cd.vrev), dp.get()))) return rc;
-        if ((rc = upload(bc.bands, &cd.band, dp.get()))) return rc;
+        if ((rc = upload(bc.vrev, reinterpret_cast<const hpfw::HostCf **>(&cd.vrev), dp))) return rc;
+        if ((rc = upload(bc.bands, &cd.band, dp))) return rc;
         cd.len0 = bc.len0;
         cd.outer = bc.outer;
         dp->cls.push_back(cd);
     }
-    if ((size_t)p.n2 * sizeof(cf) > 150 * 1024) return fail(HPFW_E_UNSUPPORTED, "n2 exceeds the LDS");
-    // the tables live on the device now: drop the host copies (only the sizes are read from here on)
-    {
-        hpfw::HostPlan &hp = dp->hp;
-        std::vector<hpfw::HostCf>().swap(hp.rows_gtw);
-        std::vector<hpfw::HostCf>().swap(hp.tw_n2);
-        std::vector<hpfw::HostCf>().swap(hp.tw_n1);
-        std::vector<hpfw::HostCf>().swap(hp.ts_seed);
-        std::vector<int8_t>().swap(hp.cols_image);
-        std::vector<int8_t>().swap(hp.cols2_image);
-        std::vector<hpfw::HostCf>().swap(hp.g);
-        for (hpfw::BluesteinClass &bc : hp.classes) {
-            std::vector<hpfw::HostCf>().swap(bc.tw);
-            std::vector<hpfw::HostCf>().swap(bc.gtw);
-            std::vector<hpfw::HostCf>().swap(bc.vrev);
+    return 0;
+}
+
+// the tables live on the device now (or in the staged image): drop the host copies; only the sizes are read from here on
+int drop_host_copies(hpfw_gpu *, DevPlan *dp)
+{
+    hpfw::HostPlan &hp = dp->hp;
+    for (auto *v : {&hp.rows_gtw, &hp.tw_n2, &hp.tw_n1, &hp.ts_seed, &hp.g}) std::vector<hpfw::HostCf>().swap(*v);
+    for (auto *v : {&hp.cols_image, &hp.cols2_image}) std::vector<int8_t>().swap(*v);
+    for (hpfw::BluesteinClass &bc : hp.classes)
+        for (auto *v : {&bc.tw, &bc.gtw, &bc.vrev}) std::vector<hpfw::HostCf>().swap(*v);
+    return 0;
+}
+
+// A corpus of files of many different lengths would otherwise keep one set of tables per length (14 MB for 30 s clips,
+// growing with the length): the cache is bounded by evicting the least recently used plans.  Which ones, and where the
+// device-wide wait falls (work already queued may still read a victim's tables), is plan_cache.h's choice.
+int make_room(hpfw_gpu *h, DevPlan *dp)
+{
+    hpfw_gpu::PlanCache &c = h->cache;
+    dp->last_use = ++c.plan_clock;
+    const size_t budget = plan_cache_budget();
+    if (c.plan_bytes + dp->bytes <= budget || c.plans.empty()) return 0;
+    PlanTimer t(h, &PlanTiming::evict);
+    std::vector<hpfw::CachedPlan> cached;
+    cached.reserve(c.plans.size());
+    for (const auto &kv : c.plans) cached.push_back({kv.first, kv.second->last_use, kv.second->bytes});
+    const hpfw::Evictions ev = hpfw::choose_evictions(std::move(cached), c.plan_bytes, dp->bytes, budget, c.idle_clock);
+    for (size_t i = 0; i < ev.victims.size(); ++i) {
+        if ((int)i == ev.wait_before) {
+            HIP_TRY(hipDeviceSynchronize());
+            c.idle_clock = c.plan_clock;
         }
-    }
-    dp->bytes = g_uploaded;
-    dp->last_use = ++h->cache.plan_clock;
-    // a corpus of files of many different lengths would otherwise keep one set of tables per length
-    // (14 MB for 30 s clips, growing with the length): bound the cache (HPFW_PLAN_CACHE_GB, default 16) by
-    // evicting the least recently used plans; work already queued may still read their tables, hence the sync
-    size_t budget = (size_t)16 << 30;
-    if (const char *e = std::getenv("HPFW_PLAN_CACHE_GB")) budget = (size_t)(std::max(0.0, std::atof(e)) * 1073741824.0);
-    if (h->cache.plan_bytes + dp->bytes > budget && !h->cache.plans.empty()) {
-        PlanTimer t(&PlanTiming::evict);
-        // Plans known to be idle go one at a time, as many as the new one needs: their blocks pass through the pool to the
-        // next length's tables (sizes of neighbouring lengths recur), no hipMalloc, no hipFree.  A plan that queued work may
-        // still read costs a device-wide wait first: then room for a quarter of the budget is made at once, so that a corpus
-        // of distinct lengths larger than the cache does not pay that wait with every file.
-        size_t goal = budget;
-        while (h->cache.plan_bytes + dp->bytes > goal && !h->cache.plans.empty()) {
-            auto lru = h->cache.plans.begin();
-            for (auto q = h->cache.plans.begin(); q != h->cache.plans.end(); ++q)
-                if (q->second->last_use < lru->second->last_use) lru = q;
-            if (lru->second->last_use > h->cache.idle_clock) {
-                HIP_TRY(hipDeviceSynchronize());
-                h->cache.idle_clock = h->cache.plan_clock;
-                goal = budget - budget / 4;
-            }
-            h->cache.plan_bytes -= lru->second->bytes;
-            {
-                // an evicted length may be prepared ahead again by the reader threads the next time a file brings it
-                std::scoped_lock lock(h->cache.host_mtx);
-                h->cache.host_seen.erase(lru->first);
-            }
-            h->cache.plans.erase(lru);
+        auto victim = c.plans.find(ev.victims[i]);
+        c.plan_bytes -= victim->second->bytes;
+        {
+            // an evicted length may be prepared ahead again by the reader threads the next time a file brings it
+            std::scoped_lock lock(c.host_mtx);
+            c.host_seen.erase(victim->first);
         }
+        c.plans.erase(victim);
     }
-    if ((rc = plan_flush(dp.get()))) return rc;
+    return 0;
+}
+
+// the constant-Q windows, generated behind the uploads of the band tables they read (S5, k_cq_tables.hip)
+int generate_windows(hpfw_gpu *h, DevPlan *dp)
+{
+    int rc = plan_flush(dp);
+    if (rc) return rc;
     std::vector<char>().swap(dp->stage);
-    // the constant-Q windows, generated behind the uploads of the band tables they read (S5, k_cq_tables.hip)
-    {
-        PlanTimer t(&PlanTiming::device_tables);
-        hpfw::CqWindowBands wb;
-        int lg_max = 0;
-        for (int j = 0; j < 121; ++j) {
-            wb.scale[j] = hpfw::cq_window_scale(h->conventions, p.big_m, p.psize[j]);
-            wb.hann_den[j] = (int)hpfw::cq_hann_den(h->conventions, p.lg[j]);
-            lg_max = std::max(lg_max, p.lg[j]);
-        }
-        hpfw::launch_cq_windows(c, wb, p.big_m, lg_max, const_cast<cf *>(c.g), h->cache.plan_stream.get());
-        if (c.g2) hpfw::launch_cq_windows_rows(c, p.n1, g2_max_entries, const_cast<cf *>(c.g2), h->cache.plan_stream.get());
-        const hipError_t launched = hipGetLastError();
-        if (launched != hipSuccess) return fail(HPFW_E_HIP, std::string("constant-Q window tables: ") + hipGetErrorString(launched));
+    PlanTimer t(h, &PlanTiming::device_tables);
+    const hpfw::HostPlan &p = dp->hp;
+    const hpfw::CqPlanDev &c = dp->cq;
+    hpfw::CqWindowBands wb;
+    int lg_max = 0;
+    for (int j = 0; j < 121; ++j) {
+        wb.scale[j] = hpfw::cq_window_scale(h->conventions, p.big_m, p.psize[j]);
+        wb.hann_den[j] = (int)hpfw::cq_hann_den(h->conventions, p.lg[j]);
+        lg_max = std::max(lg_max, p.lg[j]);
     }
+    hpfw::launch_cq_windows(c, wb, p.big_m, lg_max, const_cast<cf *>(c.g), h->cache.plan_stream.get());
+    if (c.g2) hpfw::launch_cq_windows_rows(c, p.n1, dp->cq_rows_max, const_cast<cf *>(c.g2), h->cache.plan_stream.get());
+    const hipError_t launched = hipGetLastError();
+    return launched == hipSuccess ? 0 : fail(HPFW_E_HIP, std::string("constant-Q window tables: ") + hipGetErrorString(launched));
+}
+} // namespace
+
+int get_plan(hpfw_gpu *h, int64_t n, DevPlan **out)
+{
+    auto it = h->cache.plans.find(n);
+    if (it != h->cache.plans.end()) {
+        it->second->last_use = ++h->cache.plan_clock;
+        *out = it->second.get();
+        return 0;
+    }
+    PlanTimer whole(h, &PlanTiming::total);
+    if (h->cache.plan_timing) ++h->cache.plan_timing->plans;
+    auto dp = std::make_unique<DevPlan>();
+    dp->owner = h;
+    const bool have_host = take_host_half(h, dp.get(), n);
+    SeenGuard seen{h, n};
+    int rc;
+    if (!have_host && (rc = build_host_half(h, dp.get(), n))) return rc;
+    // uploads and kernels queued on the table stream keep this order; the windows are generated behind the last flush
+    using Step = int (*)(hpfw_gpu *, DevPlan *);
+    static constexpr Step steps[] = {refuse_unrunnable, rows_tables,      chirpz_tables, cols_tables,     cq_layout_tables,
+                                     size_class_tables, drop_host_copies, make_room,     generate_windows};
+    for (Step step : steps)
+        if ((rc = step(h, dp.get()))) return rc;
     // every table of the length is on its way on the table stream: whoever uses them first waits for this (ordered_call)
     HIP_TRY(hipEventRecord(h->cache.plan_ev.get(), h->cache.plan_stream.get()));
     h->cache.plan_ev_pending = true;
     h->cache.plan_bytes += dp->bytes;
+    seen.dismissed = true;
     *out = dp.get();
     h->cache.plans[n] = std::move(dp);
     return 0;
@@ -567,12 +613,10 @@ int hpfw_gpu_geometry(hpfw_gpu *h, int64_t n_samples, hpfw_geometry *out)
         }
     }
     hpfw::HostPlan hp;
-    std::string why;
-    if (!hpfw::build_plan(n_samples, hp, why, true, std::getenv("HPFW_FORCE_BLUESTEIN") != nullptr, h->conventions))
-        return fail(HPFW_E_UNSUPPORTED, "clip length " + std::to_string(n_samples) + ": " + why);
+    const int rc = host_plan(h, n_samples, hp, true);
+    if (rc) return rc;
     // what get_plan would refuse later is refused here (callers size their buffers from this answer)
-    if ((size_t)hp.n2 * sizeof(hpfw::cf) > 150 * 1024)
-        return fail(HPFW_E_UNSUPPORTED, "clip length " + std::to_string(n_samples) + ": n2 exceeds the LDS");
+    if (!hpfw::row_fits_lds(hp.n2)) return unsupported(n_samples, "n2 exceeds the LDS");
     fill(hp);
     return 0;
 }
@@ -589,20 +633,19 @@ int hpfw_gpu_prepare_length(hpfw_gpu *h, int64_t n_samples)
         h->cache.host_ready[n_samples] = nullptr;                   // in preparation
     }
     auto hp = std::make_unique<hpfw::HostPlan>();
-    std::string why;
-    bool ok;
+    int rc;
     {
         hpfw::PlanSerial serial;
-        ok = hpfw::build_plan(n_samples, *hp, why, false, std::getenv("HPFW_FORCE_BLUESTEIN") != nullptr, h->conventions, false);
+        rc = host_plan(h, n_samples, *hp, false);
     }
-    if (!ok) *hp = hpfw::HostPlan(); // n = 0: get_plan builds it again and reports why
+    if (rc) *hp = hpfw::HostPlan(); // n = 0: get_plan builds it again and reports why
     {
         std::scoped_lock lock(h->cache.host_mtx);
         h->cache.host_ready[n_samples] = std::move(hp);
-        if (!ok) h->cache.host_seen.erase(n_samples); // an unsupported length says so every time it is asked for
+        if (rc) h->cache.host_seen.erase(n_samples); // an unsupported length says so every time it is asked for
     }
     h->cache.host_cv.notify_all();
-    return ok ? 0 : fail(HPFW_E_UNSUPPORTED, "clip length " + std::to_string(n_samples) + ": " + why);
+    return rc; // (the reason is the thread's last error already)
 }
 
 // ---- diagnostic: the device-generated tables of the chirp-z forward transform ------------------

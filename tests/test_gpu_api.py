@@ -485,3 +485,23 @@ def test_tables_prepared_by_other_threads(torch_cuda, oracle, filters):
             g.prepare_length(1000)                                # too short, every time it is asked for
     g.prepare_length(132300)                                      # known already: nothing happens
     g.close()
+
+
+def test_refused_length_leaves_the_table_cache_as_it_was(torch_cuda, oracle, filters):
+    """a device entry point meets an unsupported length first: the call is refused, and the length is not kept as known --
+    hpfw_gpu_prepare_length still says so every time it is asked; a supported length then extracts as ever"""
+    torch = torch_cuda
+    g = hpfw_amd.Gpu(0)
+    g.set_filters(filters)
+    d_pcm = torch.zeros((1, 1000), dtype=torch.int16, device="cuda")
+    d_hp = torch.zeros(16, dtype=torch.int64, device="cuda")
+    with pytest.raises(hpfw_amd.HpfwError) as e:
+        g.extract_dev(d_pcm.data_ptr(), 1000, 1, d_hp.data_ptr())
+    assert e.value.status == _lib.E_UNSUPPORTED
+    for _ in range(2):
+        with pytest.raises(hpfw_amd.HpfwError) as e:
+            g.prepare_length(1000)
+        assert e.value.status == _lib.E_UNSUPPORTED
+    clip = synth.gen_clip(701, 3.0)[:132300]
+    assert np.array_equal(g.extract(clip[None]), oracle.Plan(132300).extract(filters, clip)[None])
+    g.close()
